@@ -7,17 +7,21 @@ MaskGIT-decode frame t (maskgit_steps full forwards each), accumulate the factor
 logits and the sampled-token accuracy.  15*B frames are sampled per step per GPU.
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR     # + the last timed step's outputs as DIR/*.npy
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full                 # + every secondary leg and check (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (schema in the task contract) with two extra objects:
-  roofline     -- the dominant kernel (the MFMA GEMM): algorithmic FLOPs / measured launch time (HIP events
-                  recorded on the launch stream inside the timed region) against the MFMA peak of the dtype
+A plain run sets up, warms up, times exactly --steps steps and prints ONE JSON line from rank 0 (schema in the task contract)
+with the `roofline` object: the dominant kernel (the MFMA GEMM): algorithmic FLOPs / measured launch time (HIP events recorded on
+the launch stream inside the timed region) against the MFMA peak of the dtype.  --full adds, after the timed region:
   cpu_baseline -- the torch-CPU port of the reference forward (oracle/genie_torch_port.py) driving the oracle's MaskGIT loop,
                   timed on this host's cores on a bounded sample of the same workload (all 15 timesteps of one clip)
-and a parity self-check of the timed schedule (parity_selfcheck): on a prefix of the headline's clips the prefix-reuse
-schedule and the reference's full-forward schedule must give the same CE, and clip 0 -- the clip of the committed reference
-run tests/golden/ev_c138.npz -- must reproduce the reference's ids and CE.  A failed check exits non-zero.
+  a parity self-check of the timed schedule (parity_selfcheck): on a prefix of the headline's clips the prefix-reuse
+  schedule and the reference's full-forward schedule must give the same CE, and clip 0 -- the clip of the committed reference
+  run tests/golden/ev_c138.npz -- must reproduce the reference's ids and CE.  A failed check exits non-zero.
+  the secondary legs (full_forward_schedule, bf16_evaluate, exact_evaluate, legs: one self-checked leg per BASELINE config),
+  the training step (train_step) and the board's power / clock during the timed region (roofline.board).
 """
 import argparse
 import ctypes
@@ -583,16 +587,23 @@ def main():
                     help="clips per GPU of the training leg (141 GiB of saved activations at 32; halved on out-of-memory)")
     ap.add_argument("--no-events", action="store_true",
                     help="do not bracket GEMM launches with HIP events (for rocprofv3 --pmc passes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the secondary legs, the parity self-checks against the reference's runs, "
+                         "the training leg, the CPU baseline and the board power / clock sampler (--no-* above switch single "
+                         "ones off); a plain run does only the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step to DIR/<name>.npy (rank 0; float64)")
     args = ap.parse_args()
 
     # watchdog: a rank stuck in a collective (a peer died, a mismatched sequence) must not hang the node -- dump every
-    # thread's Python stack to stderr and exit after GENIE_BENCH_WATCHDOG seconds (default 900; the default run takes ~2 min)
+    # thread's Python stack to stderr and exit after GENIE_BENCH_WATCHDOG seconds (default 900; a --full run takes ~2.5 min)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus)  # never returns (the parent only waits for its child launcher)
     # the power / clock sampler's helper process must exist before this process touches the GPU (rank 0 only)
     # (not under a profiler: its preloaded library may already have initialised the GPU in this process)
     profiled = any("ROCPROF" in k.upper() for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "").lower()
-    sampler = BoardSampler() if int(os.environ.get("RANK", "0")) == 0 and not args.no_board_sampler and not profiled else None
+    sampler = (BoardSampler() if args.full and int(os.environ.get("RANK", "0")) == 0 and not args.no_board_sampler and not profiled
+               else None)
     import faulthandler
     wd = int(os.environ.get("GENIE_BENCH_WATCHDOG", "900"))
     if wd > 0:
@@ -694,6 +705,12 @@ def main():
     if world > 1:
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
     seconds = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        # what step() hands its caller: the node's six metric sums of the last timed step [sum CE, n CE tokens, sum (gt == sample),
+        # n sampled tokens, n frames, n clips] (1xgpt_amd/distributed.py means_from_sums); the inputs are seeded, so two builds
+        # given the same arguments can be compared file for file
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "metric_sums.npy"), sums.detach().cpu().numpy().astype(np.float64))
     prof = (ctypes.c_double * 4)()
     _lib.check(lib.genie_profile_read(_lib.KC_GEMM, prof), "profile_read")
     gemm_launches, gemm_ms, gemm_flops, gemm_bytes = list(prof)
@@ -733,7 +750,7 @@ def main():
     # secondary leg (N=1 only): a PREFIX of the headline's clips through the reference's full-forward schedule (1 timed step), and
     # the parity self-check of the timed schedule on those same clips and draws
     full_forward, selfcheck = None, None
-    if reuse and world == 1 and not args.no_secondary:
+    if args.full and reuse and world == 1 and not args.no_secondary:
         nb = min(B, {"exact": 4, "f16x3": 16, "bf16": 32}[args.precision])
         clips_full, noise_full = clips[:nb], noise[:, :, :nb].contiguous()
         ev.evaluate_metric_sums(clips_full, noise=noise_full)  # warm-up
@@ -783,7 +800,7 @@ def main():
     # the headline -- it does not meet the north star's 1e-4 CE / bit-exact-ids clause, which is why
     # f16x3 is the default; its CE is printed so the deviation can be read off the same line
     other_precision = None
-    if reuse and world == 1 and not args.no_secondary and args.precision == "f16x3":
+    if args.full and reuse and world == 1 and not args.no_secondary and args.precision == "f16x3":
         try:
             m2 = STMaskGIT(cfg, precision="bf16").load_numpy_state_dict(sd).to(dev)
             ev2 = evalmod.GenieEvaluator(ev_args, None, dev, model=m2)
@@ -807,7 +824,7 @@ def main():
     # its own roofline object against the f32 MFMA peak: the north star's ">= 50 % of the MFMA roofline with CE within 1e-4" is met in
     # THIS precision (the headline stays f16x3: f32-class results at 3x the frames/s)
     exact_leg = None
-    if reuse and world == 1 and not args.no_secondary and args.precision == "f16x3":
+    if args.full and reuse and world == 1 and not args.no_secondary and args.precision == "f16x3":
         try:
             nb = min(B, 64)
             m3 = STMaskGIT(cfg, precision="exact").load_numpy_state_dict(sd).to(dev)
@@ -853,7 +870,7 @@ def main():
             exact_leg = {"error": f"{type(e).__name__}: {e}"}
 
     legs = None
-    if world == 1 and not args.no_secondary and os.environ.get("GENIE_BENCH_LEGS", "1") != "0":
+    if args.full and world == 1 and not args.no_secondary and os.environ.get("GENIE_BENCH_LEGS", "1") != "0":
         legs = config_legs(dev, cfgmod, synth, STMaskGIT, evalmod, dist_mod,
                            model if (args.precision == "f16x3" and args.model == "c138" and not args.qk_norm) else None, args.maskgit_steps)
 
@@ -878,7 +895,7 @@ def main():
     # secondary leg: training step (every rank takes part: the gradient all-reduce is the path's one real exchange).  Rank 0 runs
     # it AFTER the headline line is assembled and under a timer: a training leg that hangs (a collective that never completes)
     # must not take the measured headline down with it.
-    want_train = not args.no_train_leg and os.environ.get("GENIE_BENCH_TRAIN", "1") != "0"
+    want_train = args.full and not args.no_train_leg and os.environ.get("GENIE_BENCH_TRAIN", "1") != "0"
 
     def run_train_leg():
         nonlocal ev, model
@@ -1052,7 +1069,7 @@ def main():
             out["train_step"] = train
     if breakdown:
         out["breakdown"] = breakdown
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, sd, all_clips, args.maskgit_steps)
     # LAST key of the line (a harness that keeps only the tail of stdout still sees it): one compact number per BASELINE config
     # and per secondary precision, details in the objects above / DESIGN.md section 5

@@ -89,7 +89,8 @@ def test_bench_two_ranks_on_one_gpu_matches_one_rank():
     """bench.py --gpus 2 end to end on the one GPU of the test box (BASELINE config 4's code path at N = 2: per-rank
     supervisor, rendezvous, sharded clips, all-reduce of the metric sums, the training leg's bucketed gradient exchange) against
     bench.py --gpus 1 on the same 16 global clips: same CE (step-0 logits do not depend on the unmasking draws)."""
-    common = ["--steps", "1", "--warmup", "0", "--no-secondary", "--no-cpu-baseline", "--no-board-sampler", "--train-batch", "2"]
+    common = ["--steps", "1", "--warmup", "0", "--full", "--no-secondary", "--no-cpu-baseline", "--no-board-sampler",
+              "--train-batch", "2"]
     one = _bench(["--gpus", "1", "--batch", "16"] + common, {})
     two = _bench(["--gpus", "2", "--batch", "8"] + common, {"GENIE_FORCE_DEVICE": "0", "GENIE_DIST_BACKEND": "gloo",
                                                              "GENIE_RDZV_TIMEOUT": "240"})
@@ -99,6 +100,22 @@ def test_bench_two_ranks_on_one_gpu_matches_one_rank():
     assert abs(two["ce"] - one["ce"]) < 1e-5, (two["ce"], one["ce"])
     assert "error" not in two["train_step"] and two["train_step"]["n_gpus"] == 2 and two["train_step"]["value"] > 0
     assert "bucketed" in two["train_step"]["gradient_exchange"]
+
+
+def test_bench_plain_run_times_the_asked_steps_and_dumps_their_outputs(tmp_path):
+    """bench.py without --full: the headline only (no secondary leg, check, training leg or CPU baseline), exactly --steps timed
+    steps, and --dump-outputs writes the last timed step's metric sums -- the numbers the line's CE and accuracy come from."""
+    out = tmp_path / "outputs"
+    r = _bench(["--gpus", "1", "--batch", "16", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)], {})
+    assert r["steps"] == 2 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["value"] > 0
+    assert abs(r["value"] - 15 * 16 / (r["ms_per_step"] / 1e3)) < 1e-6 * r["value"]
+    for k in ("legs", "cpu_baseline", "train_step", "parity_selfcheck", "full_forward_schedule", "bf16_evaluate", "exact_evaluate"):
+        assert k not in r, k
+    assert sorted(os.listdir(out)) == ["metric_sums.npy"]
+    sums = np.load(out / "metric_sums.npy")
+    assert sums.dtype == np.float64 and sums.shape == (6,)
+    assert sums[5] == 16 and sums[4] == 15 * 16 and sums[3] == 15 * 16 * 256
+    assert sums[0] / sums[1] == r["ce"] and sums[2] / sums[3] == r["sampled_token_acc"]
 
 
 def test_rccl_world1():

@@ -3,7 +3,7 @@
 # Everything is written under gpurun_out/<tag>_*; what is worth keeping is copied into profiles/ by hand.
 #
 #   suite   <tag> [pytest args]        the -m gpu suite (measured bf16 deltas -> <tag>_measured_deltas.txt), then nothing else
-#   bench   <tag> [bench.py args]      bench.py as the driver runs it (--gpus 1 --steps 20 --warmup 5 unless args are given), wall-clock measured
+#   bench   <tag> [bench.py args]      bench.py --gpus 1 --steps 20 --warmup 5 --full (every leg and self-check) unless args are given, wall-clock measured
 #   full    <tag>                      suite + bench
 #   trace   <tag> [bench.py args]      rocprofv3 --kernel-trace of one bench step -> <tag>_kernel_stats.txt (per-kernel table)
 #   tracecmd <tag> <python file> [args]  the same for any python entry (tools/bench_generate.py ...)
@@ -23,7 +23,7 @@ suite() {
 }
 bench() {
   local t0=$(date +%s)
-  if [ $# -eq 0 ]; then set -- --gpus 1 --steps 20 --warmup 5; fi
+  if [ $# -eq 0 ]; then set -- --gpus 1 --steps 20 --warmup 5 --full; fi
   timeout 1200 python bench.py "$@" > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
   echo "bench rc=$? wall=$(( $(date +%s) - t0 )) s"
   tail -c 2500 gpurun_out/${TAG}_bench.json; tail -3 gpurun_out/${TAG}_bench.err
