@@ -277,11 +277,7 @@ __global__ __launch_bounds__(512, 2) void attn_spatial_dma_kernel(const uint16_t
                     }
                     sc[(p & 3) * 2 + t] = a;
                 }
-#ifdef GENIE_VAR_ATTN_BLOCK_SOFTMAX   // (A/B variant: all exponentials in one block behind the last S tile, as before round 6)
-                if (p == 3) { softmax_chunk(0); softmax_chunk(1); softmax_chunk(2); }
-#else
                 if (p >= 1) softmax_chunk(p - 1);     // (independent of this phase's matrix instructions: the scheduler interleaves them)
-#endif
             } else {
                 if (p == 4) {
                     // chunk 3's maximum closes the row maximum (both halves of the row: mloc is already lane-pair uniform); its

@@ -997,12 +997,7 @@ int st_block_bf16(const genie_cfg& c, const genie_layer_weights& lw, float* x, W
     // MLP
     if (w.frame_t < 0) {   // LayerNorm + fc1 + GELU + fc2 + residual in one kernel for the shipped geometry (kernels_fused.hip)
         const genie_layer_weights* nx = w.next_layer;
-#ifdef GENIE_VAR_NO_LNOUT
-        constexpr int lnout = 0;
-#else
-        constexpr int lnout = 1;
-#endif
-        if (lnout && nx && nx->norm1_w && nx->norm1_b && w.skip_shadow_mlp) {
+        if (nx && nx->norm1_w && nx->norm1_b && w.skip_shadow_mlp) {
             rc = GENIE_E_UNSUPPORTED;
             if (nx->spatial.fused_w16 && (nx->spatial.w16_wide & GENIE_FUSED_QKV_STREAM)) {
                 // ... and the next block's spatial qkv Linear too: its operand planes (in `big`, where its qkv GEMM would put them)

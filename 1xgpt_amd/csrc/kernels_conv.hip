@@ -270,7 +270,7 @@ __global__ __launch_bounds__(512, OCC) void conv3x3_igemm_kernel(const uint16_t*
 // away: the taps dx = -1, 0, +1 are the same slab read one LDS row up or down.  So the K loop runs (dy, chunk) slabs of 33 KB
 // (256 pixels + one halo chunk) with three weight stages each, instead of nine 32 KB A tiles per chunk: the LDS-DMA bytes of
 // a 128-column tile drop from 864 KB to 486 KB per 256 x 128 x 1152 tile (the DMA path alone took 0.4 of the kernel's time,
-// tools/gpu_conv_abl.sh).  Rows whose horizontal neighbour lies outside the image get their fragment zeroed in registers.
+// profiles/r02m_conv_ablation.txt; profiles/HISTORY.md).  Rows whose horizontal neighbour lies outside the image get their fragment zeroed in registers.
 //   slab rows: L = 0: pixel -1, L = 1: pixel 256, L = 8 + q: pixel q of the tile; XOR swizzle keyed on L.
 //   BN = 128: 4 x 2 waves of 64 x 64;  BN = 32: 8 x 1 waves of 32 x 32 for the narrow head (conv_out, 3 -> 8 padded columns).
 typedef float cv_f4 __attribute__((ext_vector_type(4)));

@@ -112,19 +112,10 @@ constexpr int FS_RING = FS_NS * FS_STAGE;
 __device__ __forceinline__ void fs_barrier() {
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("" ::: "memory");
-#if defined(GENIE_VAR_T_ABL) && (GENIE_VAR_T_ABL & 16)
-#else
     __builtin_amdgcn_s_barrier();
-#endif
     asm volatile("" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
 }
-#ifndef GENIE_VAR_M_ABL
-#define GENIE_VAR_M_ABL 0   // timing variants of the region loop (results WRONG): 1 no barrier, 2 no LDS-DMA, 4 no vmcnt wait, 8 no GELU, 16 no fragment reads, 32 no MFMA
-#endif
-#ifndef GENIE_VAR_M_PF
-#define GENIE_VAR_M_PF 2   // fragment prefetch depth of the mlp kernel's region loop (0: compiler-scheduled reads; 3 = 256 registers)
-#endif
 template <int N>
 __device__ __forceinline__ void fs_wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -152,15 +143,7 @@ __device__ __forceinline__ void fs_wave_lds_fence() {
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
-#ifndef GENIE_VAR_T_ABL
-#define GENIE_VAR_T_ABL 0   // variant builds only (results wrong): 4 no matrix instructions, 8 no fragment reads, 16 no barriers
-#endif
 __device__ __forceinline__ f32x4 mma32(const s16x8& a, const s16x8& b, const f32x4& c) {
-    if constexpr (GENIE_VAR_T_ABL & 4) {
-        f32x4 r = c;
-        asm volatile("" : "+v"(r) : "v"(a), "v"(b));
-        return r;
-    }
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 __device__ __forceinline__ f32x4 mma16k(const s16x4& a, const s16x4& b, const f32x4& c) {
@@ -257,48 +240,10 @@ __global__ __launch_bounds__(256, 2) void temporal_fused_bf16_kernel(const uint1
         ++n_use;
         return p;
     };
-    auto frag = [&](const unsigned char* stage, int f) {
-        if constexpr (GENIE_VAR_T_ABL & 8) {   // (variant: no LDS fragment reads -- a lane-dependent constant instead)
-            const short v = (short)(lane + f);
-            return s16x8{v, v, v, v, v, v, v, v};
-        } else {
-            return *reinterpret_cast<const s16x8*>(stage + f * 1024);
-        }
-    };
-#ifdef GENIE_VAR_T_PAIR
-    // variant: 32 KB stages (two 16-fragment parts per barrier), two slots: half the barriers, prefetch distance one stage
-    int s_issue = 0;   // 32 KB stages requested so far (stream position = s & 15, slot = s & 1)
-    auto issue_pair = [&]() {
-        const int soff = (s_issue & 15) * 2 * FS_STAGE + wid * 8192;
-        unsigned char* dst = smem + (s_issue & 1) * 2 * FS_STAGE + wid * 8192;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (__attribute__((address_space(3))) void*)(dst + j * 1024), 16, voff,
-                                                     soff + j * 1024, 0, 0);
-        ++s_issue;
-    };
-    int s_use = 0;
-    const unsigned char* pair_base = nullptr;
-    // part p of the block (p = 0..31, a compile-time constant at every call site): even parts open a new 32 KB stage
-    auto acquire_part = [&](int p) -> const unsigned char* {
-        if (!(p & 1)) {
-            fs_wait_vm<0>();
-            fs_barrier();
-            if (!FS_ABL(1)) issue_pair();
-            pair_base = smem + (s_use & 1) * 2 * FS_STAGE + lane * 16;
-            ++s_use;
-            return pair_base;
-        }
-        return pair_base + FS_STAGE;
-    };
-    issue_pair();
-#else
-    auto acquire_part = [&](int) -> const unsigned char* { return acquire(); };
-
+    auto frag = [&](const unsigned char* stage, int f) { return *reinterpret_cast<const s16x8*>(stage + f * 1024); };
     issue_stage();
     issue_stage();
     issue_stage();
-#endif
 
     const int bps = S / 8;  // blocks per clip
     FS_STAMP_ID();
@@ -334,41 +279,12 @@ __global__ __launch_bounds__(256, 2) void temporal_fused_bf16_kernel(const uint1
             }
             fs_wait_vm<0>();
         } else {
-#ifdef GENIE_VAR_T_XTILE
-        {   // operand rows as whole 128-byte lines (8 tokens x 64 columns per request), re-laid through the wave's tile
-            unsigned char* tile = smem + FS_RING + 4096 + wid * 2304;
-            const int tt = lane >> 3, c8 = (lane & 7) * 8;
-            const uint16_t* xb = x16 + (((size_t)b * T + tt) * S + s0) * D + c8;
-            const size_t half_stride = (size_t)8 * S * D;
-            s16x8 raw[2][4][2];
-#pragma unroll
-            for (int grp = 0; grp < 2; ++grp)
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-#pragma unroll
-                    for (int hf = 0; hf < 2; ++hf)
-                        raw[grp][c][hf] = *reinterpret_cast<const s16x8*>(xb + grp * D + 64 * c + hf * half_stride);
-            fs_wait_vm<0>();
-#pragma unroll
-            for (int grp = 0; grp < 2; ++grp)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-#pragma unroll
-                    for (int hf = 0; hf < 2; ++hf) *reinterpret_cast<s16x8*>(tile + (8 * hf + tt) * 144 + c8 * 2) = raw[grp][c][hf];
-                    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                    for (int k2 = 0; k2 < 2; ++k2) xf[grp][2 * c + k2] = *reinterpret_cast<const s16x8*>(tile + r * 144 + (32 * k2 + 8 * g) * 2);
-                    __builtin_amdgcn_wave_barrier();
-                }
-        }
-#else
 #pragma unroll
         for (int grp = 0; grp < 2; ++grp)
 #pragma unroll
             for (int ks = 0; ks < 8; ++ks)
                 xf[grp][ks] = *reinterpret_cast<const s16x8*>(x16 + (row0 + grp) * D + 32 * ks + 8 * g);
         fs_wait_vm<0>();
-#endif
         }
         FS_STAMP(blk_i, 1);
         FS_CYC_RESET();
@@ -380,7 +296,7 @@ __global__ __launch_bounds__(256, 2) void temporal_fused_bf16_kernel(const uint1
             s16x4 vb[2][2];
 #pragma unroll
             for (int part = 0; part < 3; ++part) {
-                const unsigned char* stg = acquire_part(3 * h + part);
+                const unsigned char* stg = acquire();
                 f32x4 acc[2][2];
 #pragma unroll
                 for (int ft = 0; ft < 2; ++ft) {
@@ -457,7 +373,7 @@ __global__ __launch_bounds__(256, 2) void temporal_fused_bf16_kernel(const uint1
         }
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
-            const unsigned char* stg = acquire_part(24 + h);
+            const unsigned char* stg = acquire();
 #pragma unroll
             for (int ct = 0; ct < 16; ++ct) {
                 const s16x8 wf = frag(stg, ct);
@@ -471,7 +387,6 @@ __global__ __launch_bounds__(256, 2) void temporal_fused_bf16_kernel(const uint1
         // issued behind a store would also wait for the store).
         FS_STAMP(blk_i, 2);
         if (FS_ABL(2)) continue;
-#ifndef GENIE_VAR_T_NO_TILE
         // Through a wave-private LDS tile (16 tokens x 32 columns, rows padded to 144 bytes): the accumulators hold 64-byte pieces of
         // 16 rows per instruction; row-major, an instruction moves 8 whole 128-byte lines (requests, not bytes, are what this
         // kernel's memory side costs).  lane -> token 8 half + (lane >> 3), columns 4 (lane & 7) .. + 3 of the 32-column slab.
@@ -481,10 +396,7 @@ __global__ __launch_bounds__(256, 2) void temporal_fused_bf16_kernel(const uint1
             // row of (group grp, token 8 half + tt): ((b T + 8 half + tt) S + s0 + grp) D
             float* xb = x + (((size_t)b * T + tt) * S + s0) * D + cc;
             const size_t half_stride = (size_t)8 * S * D;
-#ifndef GENIE_VAR_T_EPF
-#define GENIE_VAR_T_EPF 1      // residual slabs requested ahead of their use
-#endif
-            constexpr int EPF = GENIE_VAR_T_EPF;
+            constexpr int EPF = 1;   // residual slabs requested ahead of their use
             f32x4 rs[EPF + 1][2];
             auto load_slab = [&](int i, f32x4* dst) {   // slab i = (grp = i >> 3, columns 32 (i & 7) ..)
                 const float* p = xb + (i >> 3) * D + 32 * (i & 7);
@@ -509,25 +421,6 @@ __global__ __launch_bounds__(256, 2) void temporal_fused_bf16_kernel(const uint1
                 fs_wave_lds_fence();
             }
         }
-#else
-        float* xr0 = x + row0 * D + 4 * g;
-        f32x4 res[2][8];
-        auto load_round = [&](int k, f32x4* dst) {
-            float* xr = xr0 + (k >> 1) * D + (k & 1) * 128;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) dst[c] = *reinterpret_cast<const f32x4*>(xr + c * 16);
-        };
-        load_round(0, res[0]);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (k + 1 < 4) load_round(k + 1, res[(k + 1) & 1]);
-            float* xr = xr0 + (k >> 1) * D + (k & 1) * 128;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) res[k & 1][c] += out[k >> 1][(k & 1) * 8 + c];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) *reinterpret_cast<f32x4*>(xr + c * 16) = res[k & 1][c];
-        }
-#endif
         FS_STAMP(blk_i, 3);
     }
     FS_CYC_DUMP();
@@ -693,14 +586,12 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_bf16_kernel(float* __restric
 #pragma unroll
                 for (int i2 = 0; i2 < 4; ++i2) raw[ct][i2] = *reinterpret_cast<const f32x4*>(xw + (size_t)(8 * i2) * D + 32 * ct);
             };
-#ifndef GENIE_VAR_M_TILE_PF
-#define GENIE_VAR_M_TILE_PF 2   // slabs requested ahead (4 measured the same)
-#endif
+            constexpr int TPF = 2;   // slabs requested ahead (4 measured the same)
 #pragma unroll
-            for (int ct = 0; ct < GENIE_VAR_M_TILE_PF; ++ct) load_slab(ct);
+            for (int ct = 0; ct < TPF; ++ct) load_slab(ct);
 #pragma unroll
             for (int ct = 0; ct < 8; ++ct) {
-                if (ct + GENIE_VAR_M_TILE_PF < 8) load_slab(ct + GENIE_VAR_M_TILE_PF);
+                if (ct + TPF < 8) load_slab(ct + TPF);
 #pragma unroll
                 for (int i2 = 0; i2 < 4; ++i2) *reinterpret_cast<f32x4*>(tile + (rr + 8 * i2) * 36 + cc) = raw[ct][i2];
                 fs_wave_lds_fence();
@@ -759,12 +650,8 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_bf16_kernel(float* __restric
             float gz[16];
 #pragma unroll
             for (int i = 0; i < 16; i += 2) {
-#ifdef GENIE_VAR_M_GELU_AS   // (variant: the 1.5e-7 GELU of the GEMM epilogues)
-                gz[i] = FS_ABL(4) ? a[i] : gelu_erf_fast(a[i]); gz[i + 1] = FS_ABL(4) ? a[i + 1] : gelu_erf_fast(a[i + 1]);
-#else
-                const genie_f2 g2 = (FS_ABL(4) || (GENIE_VAR_M_ABL & 8)) ? genie_f2{a[i], a[i + 1]} : gelu_erf_poly2(genie_f2{a[i], a[i + 1]});
+                const genie_f2 g2 = FS_ABL(4) ? genie_f2{a[i], a[i + 1]} : gelu_erf_poly2(genie_f2{a[i], a[i + 1]});
                 gz[i] = g2[0]; gz[i + 1] = g2[1];
-#endif
             }
             h0 = pack8(f32x4{gz[0], gz[1], gz[2], gz[3]}, f32x4{gz[4], gz[5], gz[6], gz[7]});
             h1 = pack8(f32x4{gz[8], gz[9], gz[10], gz[11]}, f32x4{gz[12], gz[13], gz[14], gz[15]});
@@ -785,30 +672,27 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_bf16_kernel(float* __restric
         FS_CYC(3);
         // regions 1..31: fc1 of chunk j next to fc2 of chunk j - 1
         for (int j = 1; j < 32; ++j) {
-            if constexpr (!(GENIE_VAR_M_ABL & 4)) fs_wait_vm<0>();
-            if constexpr (!(GENIE_VAR_M_ABL & 1)) fs_barrier();
+            fs_wait_vm<0>();
+            fs_barrier();
             FS_CYC(0);
-            if constexpr (!(GENIE_VAR_M_ABL & 2)) issue_region(j + 1);
+            issue_region(j + 1);
             FS_CYC(1);
             const unsigned char* sa = lbase + (j & 1) * 2 * FS_STAGE;
             acc1 = bias1(j);
-#if GENIE_VAR_M_PF > 0
-            {   // the region's 32 fragments [A_0 B_0 A_1 B_1 ...] through GENIE_VAR_M_PF rotating buffers
-                constexpr int PF = GENIE_VAR_M_PF;
+            {   // the region's 32 fragments [A_0 B_0 A_1 B_1 ...] through PF rotating buffers
+                constexpr int PF = 2;   // (3 = 256 registers)
                 const unsigned la = fs_lds_addr(sa);
                 s16x8 fb[PF];
 #define ML_OFF(n) ((((n) & 1) ? FS_STAGE : 0) + ((n) >> 1) * 1024)
 #define ML_STEP(n)                                                                                                       \
     {                                                                                                                    \
-        if constexpr (!(GENIE_VAR_M_ABL & 16)) fs_lds_wait<((31 - (n)) < (PF - 1) ? (31 - (n)) : (PF - 1))>(fb[(n) % PF]); \
-        if constexpr ((GENIE_VAR_M_ABL & 32) != 0) { asm volatile("" : "+v"(acc1) : "v"(fb[(n) % PF])); }              \
-        else if constexpr (((n) & 1) != 0) out[((n) >> 1) & 7] = mma32x32(fb[(n) % PF], ((n) >> 4) ? hk1 : hk0, out[((n) >> 1) & 7]); \
+        fs_lds_wait<((31 - (n)) < (PF - 1) ? (31 - (n)) : (PF - 1))>(fb[(n) % PF]);                                       \
+        if constexpr (((n) & 1) != 0) out[((n) >> 1) & 7] = mma32x32(fb[(n) % PF], ((n) >> 4) ? hk1 : hk0, out[((n) >> 1) & 7]); \
         else acc1 = mma32x32(fb[(n) % PF], xf[(n) >> 1], acc1);                                                         \
-        if constexpr ((n) + PF < 32 && !(GENIE_VAR_M_ABL & 16)) fs_lds_rd<ML_OFF(((n) + PF) & 31)>(fb[(n) % PF], la);   \
+        if constexpr ((n) + PF < 32) fs_lds_rd<ML_OFF(((n) + PF) & 31)>(fb[(n) % PF], la);                              \
     }
-                if constexpr ((GENIE_VAR_M_ABL & 16) != 0) { fb[0] = xf[0]; fb[1 % PF] = xf[1]; }   /* (timing variant: no fragment reads) */
-                else fs_lds_rd<ML_OFF(0)>(fb[0], la);
-                if constexpr (PF > 1 && !(GENIE_VAR_M_ABL & 16)) fs_lds_rd<ML_OFF(1)>(fb[1 % PF], la);
+                fs_lds_rd<ML_OFF(0)>(fb[0], la);
+                if constexpr (PF > 1) fs_lds_rd<ML_OFF(1)>(fb[1 % PF], la);
                 if constexpr (PF > 2) fs_lds_rd<ML_OFF(2)>(fb[2 % PF], la);
                 if constexpr (PF > 3) fs_lds_rd<ML_OFF(3)>(fb[3 % PF], la);
                 ML_STEP(0) ML_STEP(1) ML_STEP(2) ML_STEP(3) ML_STEP(4) ML_STEP(5) ML_STEP(6) ML_STEP(7)
@@ -818,13 +702,6 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_bf16_kernel(float* __restric
 #undef ML_STEP
 #undef ML_OFF
             }
-#else
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                acc1 = mma32x32(frag(sa, i), xf[i], acc1);
-                out[i & 7] = mma32x32(frag(sa + FS_STAGE, i), (i >> 3) ? hk1 : hk0, out[i & 7]);
-            }
-#endif
             FS_CYC(2);
             gelu_pack(acc1, hk0, hk1);
             FS_CYC(3);
@@ -955,14 +832,11 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_bf16_kernel(float* __restric
                 int ln = lane;
                 asm volatile("" : "+v"(ln));       // (everything lane-derived below is formed here, per block: hoisted to kernel entry it is spilled)
                 const int t4 = ln >> 2, pc = (ln & 3) * 8, rq = ln & 31, hq = ln >> 5;
-#ifndef GENIE_VAR_M_QWAIT
-#define GENIE_VAR_M_QWAIT 2     // (0: every stage also waits out the previous stage's two plane stores)
-#endif
                 for (int n = 0; n < 24; ++n) {
                     // stage n's four LDS-DMA loads were requested at the top of stage n - 1; the only younger vector-memory operations are
                     // that stage's two plane stores (vmcnt retires in order) -- they stay in flight.  n = 0: behind the row stores above.
                     if (n == 0) fs_wait_vm<0>();
-                    else fs_wait_vm<GENIE_VAR_M_QWAIT>();
+                    else fs_wait_vm<2>();
                     fs_barrier();      // stage n landed for every wave; the other half is free (n = 0: everyone's phase above is over too)
                     if (n + 1 < 24) issue_q(n + 1);
                     const unsigned char* sb = smem + ((n & 1) ? 2 * FS_STAGE : FS_STAGE) + ln * 16;
@@ -970,40 +844,31 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_bf16_kernel(float* __restric
                     f32x16 acc;
 #pragma unroll
                     for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-                    // the stage's 16 fragments through 8 rotating buffers, reads the compiler does not schedule (it pairs them: read, read,
-                    // wait, MFMA, wait, MFMA -- one LDS round trip per two matrix instructions, 44 % of the matrix rate; GENIE_VAR_M_QPF 0)
-#ifndef GENIE_VAR_M_QPF
-#define GENIE_VAR_M_QPF 8
-#endif
-#if GENIE_VAR_M_QPF > 0
+                    // the stage's 16 fragments through QPF rotating buffers, reads the compiler does not schedule (left to it, they are paired:
+                    // read, read, wait, MFMA, wait, MFMA -- one LDS round trip per two matrix instructions, 44 % of the matrix rate)
+                    constexpr int QPF = 8;
                     const unsigned lq = fs_lds_addr(sb);
-                    s16x8 qf[GENIE_VAR_M_QPF];
-#define QS_SWAPPED(f) acc = mma32x32(qf[(f) % GENIE_VAR_M_QPF], yk[f], acc);
-#define QS_PLAIN(f) acc = mma32x32(yk[f], qf[(f) % GENIE_VAR_M_QPF], acc);
+                    s16x8 qf[QPF];
+#define QS_SWAPPED(f) acc = mma32x32(qf[(f) % QPF], yk[f], acc);
+#define QS_PLAIN(f) acc = mma32x32(yk[f], qf[(f) % QPF], acc);
 #define QS_STEP(f, OP)                                                                                                            \
     {                                                                                                                             \
-        fs_lds_wait<((15 - (f)) < (GENIE_VAR_M_QPF - 1) ? (15 - (f)) : (GENIE_VAR_M_QPF - 1))>(qf[(f) % GENIE_VAR_M_QPF]);          \
+        fs_lds_wait<((15 - (f)) < (QPF - 1) ? (15 - (f)) : (QPF - 1))>(qf[(f) % QPF]);                                            \
         OP(f)                                                                                                                     \
-        if constexpr ((f) + GENIE_VAR_M_QPF < 16) fs_lds_rd<((f) + GENIE_VAR_M_QPF) * 1024>(qf[(f) % GENIE_VAR_M_QPF], lq);        \
+        if constexpr ((f) + QPF < 16) fs_lds_rd<((f) + QPF) * 1024>(qf[(f) % QPF], lq);                                           \
     }
 #define QS_ALL(OP)                                                                                                                 \
     {                                                                                                                             \
         fs_lds_rd<0>(qf[0], lq);                                                                                                  \
-        if constexpr (GENIE_VAR_M_QPF > 1) fs_lds_rd<1024>(qf[1 % GENIE_VAR_M_QPF], lq);                                          \
-        if constexpr (GENIE_VAR_M_QPF > 2) { fs_lds_rd<2048>(qf[2 % GENIE_VAR_M_QPF], lq); fs_lds_rd<3072>(qf[3 % GENIE_VAR_M_QPF], lq); } \
-        if constexpr (GENIE_VAR_M_QPF > 4) {                                                                                      \
-            fs_lds_rd<4096>(qf[4 % GENIE_VAR_M_QPF], lq); fs_lds_rd<5120>(qf[5 % GENIE_VAR_M_QPF], lq);                             \
-            fs_lds_rd<6144>(qf[6 % GENIE_VAR_M_QPF], lq); fs_lds_rd<7168>(qf[7 % GENIE_VAR_M_QPF], lq);                             \
+        if constexpr (QPF > 1) fs_lds_rd<1024>(qf[1 % QPF], lq);                                                                  \
+        if constexpr (QPF > 2) { fs_lds_rd<2048>(qf[2 % QPF], lq); fs_lds_rd<3072>(qf[3 % QPF], lq); }                            \
+        if constexpr (QPF > 4) {                                                                                                  \
+            fs_lds_rd<4096>(qf[4 % QPF], lq); fs_lds_rd<5120>(qf[5 % QPF], lq);                                                   \
+            fs_lds_rd<6144>(qf[6 % QPF], lq); fs_lds_rd<7168>(qf[7 % QPF], lq);                                                   \
         }                                                                                                                         \
         QS_STEP(0, OP) QS_STEP(1, OP) QS_STEP(2, OP) QS_STEP(3, OP) QS_STEP(4, OP) QS_STEP(5, OP) QS_STEP(6, OP) QS_STEP(7, OP)     \
         QS_STEP(8, OP) QS_STEP(9, OP) QS_STEP(10, OP) QS_STEP(11, OP) QS_STEP(12, OP) QS_STEP(13, OP) QS_STEP(14, OP) QS_STEP(15, OP) \
     }
-#else
-#define QS_SWAPPED(f) acc = mma32x32(frag(sb, f), yk[f], acc);
-#define QS_PLAIN(f) acc = mma32x32(yk[f], frag(sb, f), acc);
-#define QS_ALL(OP)                                                                                                                 \
-    { OP(0) OP(1) OP(2) OP(3) OP(4) OP(5) OP(6) OP(7) OP(8) OP(9) OP(10) OP(11) OP(12) OP(13) OP(14) OP(15) }
-#endif
                     if (part < 2) {    // swapped: D[feature][token]
                         QS_ALL(QS_SWAPPED)
                         const float sc = part == 0 ? qscale : 1.0f;
@@ -1058,15 +923,8 @@ int launch_pack_spatial_qkv(const float* qkv_w, uint16_t* out, hipStream_t st) {
 
 // x += Mlp(LayerNorm(x)) on (rows, 256); x16_out (optional): bf16 shadow of the result, or -- when nx_g / nx_b are given --
 // LayerNorm(result; nx_g, nx_b) as bf16.  GENIE_E_UNSUPPORTED outside the geometry.
-#ifndef GENIE_VAR_S_MIN_SEQ
-#define GENIE_VAR_S_MIN_SEQ 128   // fewest sequences the fused spatial kernel takes (one workgroup each; measured: 64 sequences lose 15 %, 128 gain 5 %, 192 gain 9 % over attention + proj GEMM)
-#endif
-// (mode 2 of the fused MLP kernel writes planes for any consumer of the format: the stand-alone attention kernel takes them below
-// the fused spatial kernel's threshold, so no lower bound is needed on the producer side)
-#define GENIE_VAR_S_MIN_SEQ_DECL 0
-#ifndef GENIE_VAR_M_MIN_CLIPS
-#define GENIE_VAR_M_MIN_CLIPS 2   // fewest clips' worth of rows (4,096 each; same measurement)
-#endif
+constexpr int S_MIN_SEQ = 128;   // fewest sequences the fused spatial kernel takes (one workgroup each; measured: 64 sequences lose 15 %, 128 gain 5 %, 192 gain 9 % over attention + proj GEMM)
+constexpr int M_MIN_CLIPS = 2;   // fewest clips' worth of rows (4,096 each; same measurement)
 // The spatial operand planes of n_seq sequences are addressed with 32-bit scalar offsets: one plane (n_seq * 256 * 256 bf16 values)
 // plus a tile of slack must stay below 2^31 bytes.  ONE predicate for the producer (fused MLP kernel, mode 2) and the consumer
 // (spatial_attn_proj): planes that are written can always be read (n_seq < ~15,200).
@@ -1075,14 +933,15 @@ static int device_cus() { return device_cu_count(); }   // (common.hpp: cached p
 
 int launch_mlp_fused_bf16(const genie_cfg& c, const genie_layer_weights& lw, float* x, uint16_t* x16_out, long rows, hipStream_t st,
                           const float* nx_g, const float* nx_b, const uint16_t* nx_qkv_stream, uint16_t* planes) {
-    if (c.precision != GENIE_PREC_BF16 || !lw.mlp_fused_w16 || c.d_model != 256 || c.hidden != 1024 || c.qk_norm || rows % 128 || rows < GENIE_VAR_M_MIN_CLIPS * 4096 || !lw.norm2_w ||
+    if (c.precision != GENIE_PREC_BF16 || !lw.mlp_fused_w16 || c.d_model != 256 || c.hidden != 1024 || c.qk_norm || rows % 128 || rows < M_MIN_CLIPS * 4096 || !lw.norm2_w ||
         !lw.norm2_b)
         return GENIE_E_UNSUPPORTED;
     GENIE_CHECK_ARG((nx_g == nullptr) == (nx_b == nullptr) && (!nx_g || x16_out || planes), "mlp_fused: next-norm parameters need both pointers and an output");
     // planes: the next block's spatial operand planes instead of its norm1 output (needs its qkv fragment stream, no qkv bias,
-    // sequences of 256 tokens -- a wave's 32 rows never straddle one -- and the scalar offsets of the planes inside 2^31)
+    // sequences of 256 tokens -- a wave's 32 rows never straddle one -- and the scalar offsets of the planes inside 2^31).  No lower
+    // bound on the sequences: the planes serve any consumer of the format, and the stand-alone attention kernel takes them below S_MIN_SEQ.
     const bool qkv = planes && nx_qkv_stream && nx_g && !c.qkv_bias && c.S == 256 && c.num_heads == 8 && c.head_dim == 32 && rows % 256 == 0 &&
-                     spatial_planes_addressable(rows / 256) && rows / 256 >= GENIE_VAR_S_MIN_SEQ_DECL;
+                     spatial_planes_addressable(rows / 256);
     if (planes && !qkv) return GENIE_E_UNSUPPORTED;
     const int n_blocks = (int)(rows / 128);
     const int cus = device_cus();
@@ -1129,25 +988,10 @@ int launch_mlp_fused_bf16(const genie_cfg& c, const genie_layer_weights& lw, flo
 //     features) -> after the last tile O / sum, rounded to bf16, is the B operand of the head's two out-projection K-steps.
 // Numerics = the bf16 attention contract of attn_spatial_dma_kernel (q, k, v, p, o rounded to bf16, f32 accumulation and softmax);
 // the probabilities are taken against the running maximum instead of the row maximum (same value up to the rounding of p).
-#ifndef GENIE_VAR_S_ABL
-#define GENIE_VAR_S_ABL 0   // variant builds only (results wrong): 1 no LDS-DMA after the first item, 2 no residual epilogue,
-#endif                      // 4 no matrix instructions, 8 no exponentials, 16 no LDS fragment reads
 namespace {
-__device__ __forceinline__ f32x16 sa_mma(const s16x8& a, const s16x8& b, const f32x16& c) {
-    if constexpr (GENIE_VAR_S_ABL & 4) {
-        f32x16 r_ = c;
-        asm volatile("" : "+v"(r_) : "v"(a), "v"(b));
-        return r_;
-    }
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
+// (a function rather than the builtin at its two call sites: written inline, the kernel schedules differently)
 __device__ __forceinline__ float sa_exp2(float v) {
-    if constexpr (GENIE_VAR_S_ABL & 8) return v * 0.001f;
     return __builtin_amdgcn_exp2f(v);
-}
-__device__ __forceinline__ s16x8 sa_frag(const unsigned char* p, int lane) {
-    if constexpr (GENIE_VAR_S_ABL & 16) { const short v = (short)lane; return s16x8{v, v, v, v, v, v, v, v}; }
-    return *reinterpret_cast<const s16x8*>(p);
 }
 constexpr int SA_BUF = 4 * 16384;                 // K | V^T | Wp fragments | Q of one head
 constexpr int SA_LDS = 2 * SA_BUF + 1024;         // double buffer + out-projection bias
@@ -1169,9 +1013,6 @@ int launch_pack_spatial_proj(const float* proj_w, uint16_t* out, hipStream_t st)
     return GENIE_OK;
 }
 
-#ifndef GENIE_VAR_S_RES_AT_START
-#define GENIE_VAR_S_RESEND 1   // the residual row joins in the epilogue, row-major (variant: as the accumulators' initial value)
-#endif
 __global__ __launch_bounds__(512, 2) void spatial_attn_proj_bf16_kernel(const uint16_t* __restrict__ qkv16, long P,
                                                                         const uint16_t* __restrict__ wstream,
                                                                         const float* __restrict__ proj_b, float* __restrict__ x,
@@ -1250,41 +1091,31 @@ __global__ __launch_bounds__(512, 2) void spatial_attn_proj_bf16_kernel(const ui
     issue_item(seq0, 0, 0);
     int buf = 0;
     for (long seq = seq0; seq < n_seq; seq += step) {
-        // The residual row: either the accumulators' initial value (GENIE_VAR_S_RES_AT_START: 32 row PIECES of 32 bytes per request, issued
-        // here and first needed at the end of head 0 -- fully hidden, 320-325 us), or -- shipped -- added in the epilogue from row-major
-        // loads (8 whole 128-byte segments per request, one column tile ahead of its use: 317-318 us, config 2 -0.5 % same-box).
+        // The residual row joins in the epilogue, from row-major loads (8 whole 128-byte segments per request, one column tile ahead
+        // of its use): 317-318 us, against 320-325 us as the accumulators' initial value (32 row pieces of 32 bytes per request, fully
+        // hidden behind head 0) -- config 2 -0.5 % same-box.
+        // (xrow is unused, but deleting it changes the schedule of the kernel's scalar prologue)
         [[maybe_unused]] float* xrow = x + ((size_t)seq * 256 + wid * 32 + r) * D + 4 * h;
         f32x16 out[8];
 #pragma unroll
         for (int ct = 0; ct < 8; ++ct)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-#ifdef GENIE_VAR_S_RESEND
-                const f32x4 xv = f32x4{0.f, 0.f, 0.f, 0.f};   // (variant: the residual joins in the epilogue, row-major)
-#else
-                const f32x4 xv = (GENIE_VAR_S_ABL & 64) ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(xrow + 32 * ct + 8 * j);
-#endif
-                out[ct][4 * j] = xv.x; out[ct][4 * j + 1] = xv.y; out[ct][4 * j + 2] = xv.z; out[ct][4 * j + 3] = xv.w;
-            }
+            for (int e = 0; e < 16; ++e) out[ct][e] = 0.f;
 #pragma unroll 1
         for (int hd = 0; hd < NH; ++hd) {
             // this head's 64 KB have landed for every wave; the other buffer is free.  Head 0 of every sequence but the first: the
             // 64 stores of the previous sequence's epilogue are YOUNGER than this head's 8 LDS-DMA pieces (requested at that
             // sequence's last barrier) and may stay in flight -- vmcnt retires in order, so 63 outstanding means the pieces are in.
-            // The count must not exceed the number of epilogue operations that are ALWAYS issued: 32 f32 stores, plus -- in the shipped
-            // form, GENIE_VAR_S_RESEND -- the 32 residual loads of the row-major epilogue (the 32 bf16 stores only exist with x16).
-#ifdef GENIE_VAR_S_RESEND
+            // The count must not exceed the number of epilogue operations that are ALWAYS issued: 32 residual loads and 32 f32 stores
+            // (the 32 bf16 stores only exist with x16).
             constexpr int YOUNGER_MIN = 64;
-#else
-            constexpr int YOUNGER_MIN = 32;   // (GENIE_VAR_S_RES_AT_START: the residual loads sit in front of the head loop)
-#endif
             if (hd == 0 && seq != seq0) fs_wait_vm<YOUNGER_MIN - 1>(); else fs_wait_vm<0>();
             fs_barrier();
             {
                 const bool last_h = hd == NH - 1;
                 const long nseq = last_h ? seq + step : seq;
                 const int nhd = last_h ? 0 : hd + 1;
-                if (nseq < n_seq && !(GENIE_VAR_S_ABL & 1)) issue_item(nseq, nhd, buf ^ 1);
+                if (nseq < n_seq) issue_item(nseq, nhd, buf ^ 1);
             }
             const unsigned char* kb = smem + buf * SA_BUF;
             s16x8 qf[2];   // B operand of S^T = K Q^T: lane = query r, 8 features 16 kk + 8 h ..
@@ -1304,7 +1135,7 @@ __global__ __launch_bounds__(512, 2) void spatial_attn_proj_bf16_kernel(const ui
                 for (int e = 0; e < 16; ++e) sc[e] = 0.f;
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk)
-                    sc = sa_mma(sa_frag(kb + c * 4096 + t * 2048 + offK[kk], lane), qf[kk], sc);
+                    sc = mma32x32(*reinterpret_cast<const s16x8*>(kb + c * 4096 + t * 2048 + offK[kk]), qf[kk], sc);
                 float mc = sc[0];
 #pragma unroll
                 for (int e = 1; e < 16; ++e) mc = fmaxf(mc, sc[e]);
@@ -1327,8 +1158,8 @@ __global__ __launch_bounds__(512, 2) void spatial_attn_proj_bf16_kernel(const ui
                 for (int mm = 0; mm < 2; ++mm) {
                     const s16x8 pa = pack8(f32x4{sc[8 * mm], sc[8 * mm + 1], sc[8 * mm + 2], sc[8 * mm + 3]},
                                            f32x4{sc[8 * mm + 4], sc[8 * mm + 5], sc[8 * mm + 6], sc[8 * mm + 7]});
-                    const s16x8 vf = sa_frag(vb + c * 4096 + offV + (((t * 4 + 2 * mm + h) ^ vsw) << 4), lane);
-                    o = sa_mma(vf, pa, o);
+                    const s16x8 vf = *reinterpret_cast<const s16x8*>(vb + c * 4096 + offV + (((t * 4 + 2 * mm + h) ^ vsw) << 4));
+                    o = mma32x32(vf, pa, o);
                 }
             }
             l += __shfl_xor(l, 32);
@@ -1337,7 +1168,7 @@ __global__ __launch_bounds__(512, 2) void spatial_attn_proj_bf16_kernel(const ui
             const s16x8 ob1 = pack8(f32x4{o[8], o[9], o[10], o[11]} * inv, f32x4{o[12], o[13], o[14], o[15]} * inv);
 #pragma unroll
             for (int f = 0; f < 16; ++f)
-                out[f & 7] = sa_mma(sa_frag(wb + f * 1024, lane), (f >> 3) ? ob1 : ob0, out[f & 7]);
+                out[f & 7] = mma32x32(*reinterpret_cast<const s16x8*>(wb + f * 1024), (f >> 3) ? ob1 : ob0, out[f & 7]);
             buf ^= 1;
         }
         // ---- epilogue: x = out + bias (the row already holds x + all heads' projections) and its bf16 shadow (the temporal
@@ -1346,7 +1177,6 @@ __global__ __launch_bounds__(512, 2) void spatial_attn_proj_bf16_kernel(const ui
         // -40 us of 350).  So each 32-column tile goes through a wave-private 4.5 KB LDS tile (rows padded to 144 bytes) and leaves as
         // whole 128-byte lines: 8 rows per store instruction.  The tile lives in the buffer of the head just finished (one extra
         // barrier per sequence makes sure every wave is done reading it).
-        if constexpr (GENIE_VAR_S_ABL & 2) { asm volatile("" :: "v"(out[0]), "v"(out[1]), "v"(out[2]), "v"(out[3]), "v"(out[4]), "v"(out[5]), "v"(out[6]), "v"(out[7])); continue; }
         fs_barrier();
         {
             float* tile = reinterpret_cast<float*>(smem + (buf ^ 1) * SA_BUF + wid * 8192);   // (buf was toggled after the last head)
@@ -1363,11 +1193,7 @@ __global__ __launch_bounds__(512, 2) void spatial_attn_proj_bf16_kernel(const ui
             asm volatile("" : "+v"(le));
             const int rr = le >> 3, cc = (le & 7) * 4;        // row-major side: row rr + 8 i, columns cc .. cc + 3 of the tile
             const int re = le & 31, he = le >> 5;             // accumulator side: (r, h) of this lane
-#ifdef GENIE_VAR_S_RESEND
-#ifndef GENIE_VAR_S_EPF
-#define GENIE_VAR_S_EPF 1      // residual column tiles requested ahead of their use
-#endif
-            constexpr int EPF = GENIE_VAR_S_EPF;
+            constexpr int EPF = 1;   // residual column tiles requested ahead of their use
             f32x4 rs[EPF + 1][4];
             auto load_res = [&](int ct_, f32x4* dst) {
 #pragma unroll
@@ -1375,12 +1201,9 @@ __global__ __launch_bounds__(512, 2) void spatial_attn_proj_bf16_kernel(const ui
             };
 #pragma unroll
             for (int i = 0; i < EPF; ++i) load_res(i, rs[i % (EPF + 1)]);
-#endif
 #pragma unroll
             for (int ct = 0; ct < 8; ++ct) {
-#ifdef GENIE_VAR_S_RESEND
                 if (ct + EPF < 8) load_res(ct + EPF, rs[(ct + EPF) % (EPF + 1)]);
-#endif
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
                     *reinterpret_cast<f32x4*>(tile + re * 36 + 8 * j + 4 * he) =
@@ -1391,11 +1214,7 @@ __global__ __launch_bounds__(512, 2) void spatial_attn_proj_bf16_kernel(const ui
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
                 for (int i2 = 0; i2 < 4; ++i2) {
-#ifdef GENIE_VAR_S_RESEND
                     const f32x4 v = *reinterpret_cast<const f32x4*>(tile + (rr + 8 * i2) * 36 + cc) + rs[ct % (EPF + 1)][i2];
-#else
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(tile + (rr + 8 * i2) * 36 + cc);
-#endif
                     *reinterpret_cast<f32x4*>(xw + (size_t)(rr + 8 * i2) * D + 32 * ct + cc) = v;
                     if (w16) *reinterpret_cast<s16x4*>(xw16 + (size_t)(rr + 8 * i2) * D + 32 * ct + cc) = pack4(v);
                 }
@@ -1412,7 +1231,7 @@ __global__ __launch_bounds__(512, 2) void spatial_attn_proj_bf16_kernel(const ui
 int launch_spatial_attn_proj_bf16(const genie_cfg& c, const genie_attn_weights& aw, const uint16_t* qkv16, float* x, uint16_t* x16,
                                   long n_seq, hipStream_t st) {
     if (c.precision != GENIE_PREC_BF16 || !aw.fused_w16 || c.d_model != 256 || c.num_heads != 8 || c.head_dim != 32 || c.S != 256 || c.qk_norm ||
-        n_seq < GENIE_VAR_S_MIN_SEQ)
+        n_seq < S_MIN_SEQ)
         return GENIE_E_UNSUPPORTED;
     const long P = n_seq * 256 * 256;
     if (!spatial_planes_addressable(n_seq)) return GENIE_E_UNSUPPORTED;   // 32-bit scalar offsets inside the plane descriptors
@@ -1422,26 +1241,22 @@ int launch_spatial_attn_proj_bf16(const genie_cfg& c, const genie_attn_weights& 
     ProfScope prof(GENIE_KC_FUSED, M * (4.0 * 256 * 256 + 2.0 * 256 * 256), M * (3 * 512.0 + 2048.0 + 512.0), st,
                    "spatial_attn_proj_bf16_kernel (attention over S, all heads + proj + residual)");
     { static PerDevice<bool> once; if (once.needs()) { (void)hipFuncSetAttribute((const void*)spatial_attn_proj_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SA_LDS); once.set(true); } }
-#ifndef GENIE_VAR_S_STAGGER
-#define GENIE_VAR_S_STAGGER 0     // (measured: 3-15 us per class only adds the delay -- profiles/r04_fused_experiments.txt)
-#endif
-    const int stagger = n_seq >= 2 * (long)grid ? study_env("GENIE_FUSED_STAGGER_S", GENIE_VAR_S_STAGGER) : 0;
+    // no stagger by default (measured: 3-15 us per class only adds the delay -- profiles/r04_fused_experiments.txt)
+    const int stagger = n_seq >= 2 * (long)grid ? study_env("GENIE_FUSED_STAGGER_S", 0) : 0;
     spatial_attn_proj_bf16_kernel<<<grid, 512, SA_LDS, st>>>(qkv16, P, aw.fused_w16, c.proj_bias ? aw.proj_b : nullptr, x, x16, n_seq,
                                                              stagger);
     GENIE_LAUNCH_CHECK("spatial_attn_proj_bf16");
     return GENIE_OK;
 }
 
-#ifndef GENIE_VAR_T_MIN_CLIPS
-#define GENIE_VAR_T_MIN_CLIPS 2   // (measured at 1 / 2 / 3 / 4 / 6 clips: 1 clip is 14 % slower fused, from 2 clips on 6-30 % faster)
-#endif
+constexpr int T_MIN_CLIPS = 2;   // (measured at 1 / 2 / 3 / 4 / 6 clips: 1 clip is 14 % slower fused, from 2 clips on 6-30 % faster)
 // x += proj_t(attention_T(qkv_t(x16))) on dense (B, 16, S, 256) buffers; GENIE_E_UNSUPPORTED for any other geometry
 bool temporal_fused_takes(const genie_cfg& c, const genie_attn_weights& aw, int B) {
     // (precision: in GENIE_PREC_F16X3 `fused_w16` is the split-f16 qkv stream of kernels_fused_f16x3.hip, not this kernel's bf16
     // [qkv | proj] stream; qk_norm: the shipped config -- genie/configs/magvit_n32_h8_d256.json -- has LayerNorm blocks, and the d = 256
     // fused kernels are specialisations for it: a qk-norm model of this width runs the unfused launches)
     return c.precision == GENIE_PREC_BF16 && aw.fused_w16 && c.d_model == 256 && c.num_heads == 8 && c.head_dim == 32 && c.T == 16 &&
-           c.S % 8 == 0 && !c.qk_norm && (long)B * c.S >= GENIE_VAR_T_MIN_CLIPS * 256;
+           c.S % 8 == 0 && !c.qk_norm && (long)B * c.S >= T_MIN_CLIPS * 256;
 }
 
 int launch_temporal_fused_bf16(const genie_cfg& c, const genie_attn_weights& aw, const uint16_t* x16, float* x, int B,
@@ -1453,11 +1268,7 @@ int launch_temporal_fused_bf16(const genie_cfg& c, const genie_attn_weights& aw,
     const double M = (double)B * c.T * c.S;
     ProfScope prof(GENIE_KC_FUSED, M * (2.0 * 256 * 1024 + 4.0 * 16 * 256), M * (512.0 + 2048.0), st,
                    "temporal_fused_bf16_kernel (qkv + causal attention over T + proj + residual)");
-#ifndef GENIE_VAR_T_NO_TILE
     const size_t lds = FS_RING + 4096 + 4 * 2304;   // ring, biases, one 16 x 36-float tile per wave
-#else
-    const size_t lds = FS_RING + 4096;
-#endif
     fs_stamps_prepare();
     const float sl2e = c.attn_scale * 1.4426950408889634f;
     const int abl = study_env("GENIE_FUSED_ABL", 0);

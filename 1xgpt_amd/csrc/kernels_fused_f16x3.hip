@@ -376,18 +376,13 @@ __global__ __launch_bounds__(256, 2) void temporal_qkv_attn_f16x3_kernel(const f
     qa_wait_vm<0>();  // the ring's run-ahead stages must not outlive the workgroup's LDS allocation
 }
 
-#ifndef GENIE_VAR_TQA_MIN_CLIPS
-#define GENIE_VAR_TQA_MIN_CLIPS 2
-#endif
+constexpr int TQA_MIN_CLIPS = 2;
 // The geometry the kernel covers.  cache_mode: the pass keeps the k, v accumulators in the layer's cache slice (clean pass / masked pass of
 // the evaluator) -- ONE predicate for producer and consumer, as temporal_prefix_fused_takes: fewer frames than the model's T (a cache
 // genie_frame_pass could continue never takes this form) and at least 11 (32 KB per position must fit the slice).
 bool temporal_qkv_attn_f16x3_takes(const genie_cfg& c, const genie_attn_weights& aw, int B, int model_T, bool cache_mode) {
-#ifdef GENIE_VAR_TQA_OFF   // (A/B variant: the unfused launches)
-    return false;
-#endif
     if (!(aw.fused_w16 && c.precision == GENIE_PREC_F16X3 && c.d_model == 256 && c.num_heads == 8 && c.head_dim == 32 && c.T >= 1 && c.T <= 16 &&
-          c.S % 4 == 0 && !c.qk_norm && (long)B * c.S >= GENIE_VAR_TQA_MIN_CLIPS * 256))
+          c.S % 4 == 0 && !c.qk_norm && (long)B * c.S >= TQA_MIN_CLIPS * 256))
         return false;
     return !cache_mode || (c.T >= 11 && c.T < model_T && model_T <= 16);
 }
@@ -398,17 +393,10 @@ int launch_temporal_qkv_attn_f16x3(const genie_cfg& c, const genie_attn_weights&
     if (!temporal_qkv_attn_f16x3_takes(c, aw, B, model_T, mode != 0)) return GENIE_E_UNSUPPORTED;
     GENIE_CHECK_ARG(x && a16 && (mode == 0 || kv) && mode >= 0 && mode <= 2 && (shift == 0 || shift == 1), "temporal_qkv_attn_f16x3: bad argument");
     const bool qb = c.qkv_bias && aw.qkv_b;
-#ifndef GENIE_VAR_TQA_G2
-#define GENIE_VAR_TQA_G2 1     // two 16-token groups per wave where the registers allow (plain / clean pass, no qkv bias)
-#endif
-    const int G = (GENIE_VAR_TQA_G2 && mode != 2 && !qb && c.S % 8 == 0) ? 2 : 1;
+    // two 16-token groups per wave where the registers allow (plain / clean pass, no qkv bias)
+    const int G = (mode != 2 && !qb && c.S % 8 == 0) ? 2 : 1;
     const int n_blocks = B * c.S / (4 * G);
-    static const int cus = [] {
-        int dev = 0, n = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n;
-    }();
+    const int cus = device_cu_count();
     const int grid = n_blocks < 2 * cus ? n_blocks : 2 * cus;
     const double M = (double)B * c.T * c.S;
     ProfScope prof(GENIE_KC_FUSED, M * (2.0 * 256 * 768 + 4.0 * 16 * 256 * (mode == 2 ? 2 : 1)), M * (1024.0 + 1024.0 + (mode ? 2048.0 : 0.0)), st,

@@ -365,19 +365,14 @@ __global__ __launch_bounds__(256, 2) void temporal_prefix_fused_bf16_kernel(floa
     pf_wait_vm<0>();  // the ring's run-ahead stages must not outlive the workgroup's LDS allocation
 }
 
-#ifndef GENIE_VAR_TP_MIN_CLIPS
-#define GENIE_VAR_TP_MIN_CLIPS 2
-#endif
+constexpr int TP_MIN_CLIPS = 2;
 // ONE predicate for the clean pass (which then writes fragment images instead of qkv rows into the cache) and the masked passes
 // that read them: the model's geometry, a pass of fewer frames than the model's T (a cache that genie_frame_pass could continue
 // always has T frame slots, so it never takes this form; and at least 8 frames: the fragment images of 16 frame slots must fit the
 // layer's slice of the cache), the same B.
 bool temporal_prefix_fused_takes(const genie_cfg& c, const genie_attn_weights& aw, int B, int model_T) {
-#ifdef GENIE_VAR_TP_OFF   // (A/B variant: the prefix-cache passes on the unfused launches)
-    return false;
-#endif
     return aw.fused_w16 && c.precision == GENIE_PREC_BF16 && c.d_model == 256 && c.num_heads == 8 && c.head_dim == 32 && c.T >= 8 &&
-           c.T <= 16 && c.T < model_T && model_T <= 16 && c.S % 8 == 0 && !c.qk_norm && (long)B * c.S >= GENIE_VAR_TP_MIN_CLIPS * 256;
+           c.T <= 16 && c.T < model_T && model_T <= 16 && c.S % 8 == 0 && !c.qk_norm && (long)B * c.S >= TP_MIN_CLIPS * 256;
 }
 
 // mode 1: clean pass (kv written); mode 2: masked pass (kv read, query slot i sees cached slots j < i + shift and itself)
@@ -386,12 +381,7 @@ int launch_temporal_prefix_fused_bf16(const genie_cfg& c, const genie_attn_weigh
     if (!temporal_prefix_fused_takes(c, aw, B, model_T)) return GENIE_E_UNSUPPORTED;
     GENIE_CHECK_ARG(x && kv && (mode == 1 || mode == 2) && (shift == 0 || shift == 1), "temporal_prefix_fused: bad argument");
     const int n_blocks = B * c.S / 8;
-    static const int cus = [] {
-        int dev = 0, n = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n;
-    }();
+    const int cus = device_cu_count();
     const int grid = n_blocks < 2 * cus ? n_blocks : 2 * cus;
     const double M = (double)B * c.T * c.S;
     ProfScope prof(GENIE_KC_FUSED, M * (2.0 * 256 * 1024 + 4.0 * 16 * 256 * (mode == 2 ? 2 : 1)), M * (2048.0 + 1024.0), st,

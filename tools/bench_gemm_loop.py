@@ -1,5 +1,5 @@
 """Keeps the 4096^3 f16x3 GEMM (gemm16_pp) running for ~12 s on zero-filled or random operands and prints its rate: the load
-under which tools/gpu_power_probe.sh samples board power and shader clock."""
+under which board power and shader clock were sampled (profiles/r02_power_clock_zero_vs_random.txt; profiles/HISTORY.md)."""
 import importlib, os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

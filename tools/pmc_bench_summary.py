@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Reduce the three rocprofv3 --pmc passes of bench.py (tools/gpu_pmc_bench.sh) to profiles/pmc_bench.json:
+"""Reduce the three rocprofv3 --pmc passes of bench.py (`tools/gpu_run.sh pmc`) to profiles/pmc_bench.json:
 per kernel class (gemm / attention_spatial / attention_temporal) HBM-side bytes per launch, matrix-pipe busy fraction and
 shader clock.  usage: tools/pmc_bench_summary.py <precision> <clips> <fetch.csv> <write.csv> <sq.csv> <out.json> "<source note>"
 
