@@ -58,7 +58,8 @@ static Workspace carve(const genie_cfg& c, int B, void* base) {
     w.x = (float*)take(M * c.d_model * 4);
     w.xn = take(M * c.d_model * 4);
     w.big = take(M * wide * 4);
-    w.logits = (float*)take(M * V * 4);
+    // w.logits doubles as the (M, d) f32 scratch of the 16-bit blocks' generic attention path (kernels_bf16.hip): V < d happens
+    w.logits = (float*)take(M * (V > (size_t)c.d_model ? V : (size_t)c.d_model) * 4);
     w.samples = (int64_t*)take((size_t)B * c.S * 8);
     w.conf = (float*)take((size_t)B * c.S * 4);
     w.unmasked = (uint8_t*)take((size_t)B * c.S);
@@ -89,6 +90,12 @@ static int check_cfg(const genie_cfg* c) {
                       c->head_dim);
     GENIE_CHECK_SHAPE(c->num_factored >= 1 && c->num_factored <= 4, "num_factored %d unsupported", c->num_factored);
     GENIE_CHECK_SHAPE(c->factored_vocab >= 1, "factored_vocab must be >= 1");
+    {   // image_vocab_size (the mask id) must be factored_vocab ^ num_factored: sampled ids hi * vf + lo stay below it
+        int64_t p = 1;
+        for (int j = 0; j < c->num_factored && p <= c->image_vocab_size; ++j) p *= c->factored_vocab;
+        GENIE_CHECK_SHAPE(p == c->image_vocab_size, "image_vocab_size %d != factored_vocab %d ^ num_factored %d",
+                          c->image_vocab_size, c->factored_vocab, c->num_factored);
+    }
     GENIE_CHECK_SHAPE(c->precision == GENIE_PREC_EXACT || c->precision == GENIE_PREC_BF16 ||
                           c->precision == GENIE_PREC_F16X3,
                       "unknown precision %d", c->precision);

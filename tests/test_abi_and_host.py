@@ -64,6 +64,51 @@ def test_config_checks_without_gpu():
         lib_mod.check(L.genie_linear(0, 0, 0, 0, 1, 1, 16, 0, 0, 0), "genie_linear")
 
 
+def test_config_check_refuses_inconsistent_vocabulary():
+    """genie_check_config: image_vocab_size (the mask id) must be factored_vocab ^ num_factored -- else a sampled id hi * vf + lo
+    can reach or pass the mask id.  The power is formed without overflow (factored_vocab up to 2^31 - 1, four factors)."""
+    lib_mod = pkg("_lib")
+    L = lib_mod.load()
+    C = pkg("config")
+    for iv, nv in [(262144, 1), (262144, 2), (262144, 3), (65536, 4), (10000, 2), (4096, 1), (1, 4)]:
+        c = lib_mod.make_cfg(C.GenieConfig(num_layers=1, num_heads=2, d_model=64, T=4, S=16, image_vocab_size=iv,
+                                           num_factored_vocabs=nv))
+        assert L.genie_check_config(c) == 0, (iv, nv, L.genie_last_error())
+        assert L.genie_workspace_bytes(c, 1) > 0
+    ok = lib_mod.make_cfg(C.c35())
+    for vf, nv, iv in [(512, 2, 262143), (512, 2, 262145), (512, 2, 512), (512, 1, 262144), (64, 3, 262144 * 64),
+                       (100, 2, 10001), (2 ** 31 - 1, 2, 2 ** 31 - 1), (2 ** 31 - 1, 4, 1), (65536, 2, 0), (46341, 2, 2 ** 31 - 1)]:
+        bad = lib_mod.make_cfg(C.c35())
+        bad.factored_vocab, bad.num_factored, bad.image_vocab_size = vf, nv, iv
+        assert L.genie_check_config(bad) == lib_mod.E_SHAPE, (vf, nv, iv)
+        assert b"image_vocab_size" in L.genie_last_error()
+        assert L.genie_workspace_bytes(bad, 1) == 0
+        assert L.genie_generate_workspace_bytes(bad, 1, 2) == 0
+    assert L.genie_check_config(ok) == 0
+
+
+def test_workspace_holds_the_16bit_scratch_when_the_vocabulary_is_narrower_than_d():
+    """The 16-bit blocks' generic attention kernels write an (M, d) f32 scratch into the logits region of the workspace: with
+    V < d that region (and hence the workspace) must grow to M * d floats, while V >= d keeps its size."""
+    lib_mod = pkg("_lib")
+    L = lib_mod.load()
+    C = pkg("config")
+
+    def ws(**kw):
+        c = lib_mod.make_cfg(C.GenieConfig(num_layers=1, num_heads=kw["d_model"] // 64, T=4, S=64, **kw))
+        c.precision = lib_mod.PREC_BF16
+        assert L.genie_check_config(c) == 0, L.genie_last_error()
+        return L.genie_workspace_bytes(c, 1), L.genie_generate_workspace_bytes(c, 1, 2)
+
+    M = 4 * 64
+    for d in (256, 1536):
+        narrow, gen_narrow = ws(d_model=d, image_vocab_size=64 ** 3, num_factored_vocabs=3)   # V = 192 < d
+        assert gen_narrow >= narrow
+        assert ws(d_model=d, image_vocab_size=16, num_factored_vocabs=1)[0] == narrow      # any V <= d: M * d floats
+        assert ws(d_model=d, image_vocab_size=d, num_factored_vocabs=1)[0] == narrow       # V = d
+        assert ws(d_model=d, image_vocab_size=4 * d, num_factored_vocabs=1)[0] == narrow + M * 3 * d * 4   # V = 4d: M * V floats
+
+
 def test_config_roundtrip_and_derived(tmp_path):
     C = pkg("config")
     c = C.c35()

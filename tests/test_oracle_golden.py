@@ -202,3 +202,66 @@ def test_bench_workload_golden(golden, name):
         lab = np.concatenate([z["ids"].reshape(1, 16, 256)[:, :1], z["ids"].reshape(1, 16, 256)[:, t:t + 1]], 1).reshape(1, -1)
         ce = O.compute_loss(lab, fl[:, :, :, None], cfg)
         assert abs(ce - float(z["ev_loss_per_t"][t - 1])) < 1e-4, (t, ce, float(z["ev_loss_per_t"][t - 1]))
+
+
+# vocabularies other than 2 x 512 (tools/make_goldens.py vocab): 1 x 4096, 3 x 64 (qk-norm), 4 x 16, 2 x 100
+VOCAB = ["vocab_v4096_n1", "vocab_v64_n3_qknorm", "vocab_v16_n4", "vocab_v100_n2"]
+
+
+def vocab_logits(z, lg, cfg):
+    """The golden's logits, whole or at its probe columns, beside the same view of lg (B, V, T, H, W)."""
+    if "probe_t" not in z.files:
+        return lg, z["logits"]
+    W = math.isqrt(cfg.S)
+    return np.stack([lg[:, :, t, s // W, s % W] for t, s in zip(z["probe_t"], z["probe_s"])], 1), z["probe_logits"]
+
+
+@pytest.mark.parametrize("name", VOCAB)
+def test_vocab_compute_logits(golden, name):
+    z, cfg, sd = golden(name)
+    V = cfg.factored_vocab_size * cfg.num_factored_vocabs
+    assert cfg.factored_vocab_size ** cfg.num_factored_vocabs == cfg.image_vocab_size and V != 1024
+    H = W = math.isqrt(cfg.S)
+    ids = z["ids"].reshape(-1, cfg.T, H, W)
+    for nm in (O.F32, O.F64):
+        lg = O.compute_logits(ids, sd, cfg, nm)
+        assert lg.shape == (ids.shape[0], V, cfg.T, H, W)
+        mine, ref = vocab_logits(z, lg, cfg)
+        scale = max(1.0, float(np.abs(ref).max()) / 8)
+        assert np.abs(mine - ref).max() < LOGIT_TOL * scale
+        assert abs(lg.astype(np.float64).sum() - float(z["logits_sum"])) < 0.05
+
+
+@pytest.mark.parametrize("name", VOCAB)
+def test_vocab_forward_loss_acc(golden, name):
+    z, cfg, sd = golden(name)
+    loss, acc, logits = O.forward_loss_acc(z["fwd_input"], z["ids"], sd, cfg)
+    assert abs(loss - float(z["fwd_loss"])) < 1e-4
+    assert abs(acc - float(z["fwd_acc"])) < 1e-7
+    assert abs(logits.astype(np.float64).sum() - float(z["fwd_logits_sum"])) < 0.05
+
+
+@pytest.mark.parametrize("name", VOCAB)
+@pytest.mark.parametrize("steps", [1, 2, 3, 8])
+@pytest.mark.parametrize("mode", ["random", "greedy"])
+def test_vocab_maskgit_generate(golden, name, steps, mode):
+    z, cfg, sd = golden(name)
+    H = W = math.isqrt(cfg.S)
+    prompt = z["ids"].reshape(-1, cfg.T, H, W).copy()
+    prompt[:, 2:] = cfg.image_vocab_size
+    k = f"mg_s{steps}_{mode}"
+    s, fl = O.maskgit_generate(prompt, 2, sd, cfg, steps, 0.0, mode, noise=z[k + "_noise"])
+    assert np.array_equal(s, z[k + "_samples"])
+    assert s.max() < cfg.image_vocab_size
+    assert np.array_equal(prompt, z[k + "_prompt_after"])
+    if steps == 2 and mode == "random":
+        ref = z["mg_step0_factored_logits"]   # (B, vf, nv, H, W), or its first row of tokens
+        assert fl.shape[:3] == ref.shape[:3] == (prompt.shape[0], cfg.factored_vocab_size, cfg.num_factored_vocabs)
+        assert np.abs(fl[:, :, :, :ref.shape[3]] - ref).max() < 1e-4
+
+
+@pytest.mark.parametrize("name", VOCAB)
+def test_vocab_generate(golden, name):
+    z, cfg, sd = golden(name)
+    out = O.generate(z["ids"][:, :2 * cfg.S], 2 * cfg.S, sd, cfg, maskgit_steps=2, noise=z["gen_noise"])
+    assert np.array_equal(out, z["gen_out"])

@@ -118,9 +118,10 @@ class Recorder:
         def compute_logits(x):
             lg = self._orig_logits(x)
             if self.out_t is not None:
-                f = lg[:, :, self.out_t]  # (B, 1024, H, W)
+                f = lg[:, :, self.out_t]  # (B, nv * vf, H, W), channel = factor * vf + k
                 B = f.shape[0]
-                ff = f.reshape(B, 2, 512, -1)
+                c = self.model.config
+                ff = f.reshape(B, c.num_factored_vocabs, c.factored_vocab_size, -1)
                 top2 = ff.topk(2, dim=2).values
                 self.min_gap = min(self.min_gap, float((top2[:, :, 0] - top2[:, :, 1]).min()))
                 conf = ff.softmax(2).amax(2).prod(1)  # (B, S) confidence of the argmax sample
@@ -233,6 +234,91 @@ def tiny_fixture(name, cfg_kwargs, wseed):
     np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
     print(f"{name}: clip_seed={clip_seed} min_gap={min_gap:.3e} ev_loss={out['ev_loss']:.6f} "
           f"fwd_loss={out['fwd_loss']:.6f}")
+
+
+def vocab_fixture(name, cfg_kwargs, wseed, n_probe=None):
+    """tiny_fixture's contents for a vocabulary other than 2 x 512 (image_vocab_size = vf ** nv, V = nv * vf logits per token).
+    The reference's compute_loss_and_acc factorises its targets with factorize_labels' DEFAULTS (st_mask_git.py:241: 2 x 512),
+    which raises for any other vocabulary; for the forward loss / acc it is called here with the model's own factorisation,
+    the operation the surrounding code (rearrange with the config's vocab_size / num_vocabs, :236-239) means.  Everything else
+    (FactorizedEmbedding, readout, maskgit_generate's per-factor sampling, generate) reads the config already.
+    n_probe: keep that many (t, s) probe columns of the logits instead of all of them (file size)."""
+    import genie.st_mask_git as ref_smg
+    from genie.factorization_utils import factorize_labels as ref_factorize_labels
+    model, cfg = build_ref_model(cfg_kwargs, wseed)
+    nv, vf = cfg.num_factored_vocabs, cfg.factored_vocab_size
+    H = W = math.isqrt(cfg.S)
+    B = 2
+    orig_fl = ref_smg.factorize_labels
+    ref_smg.factorize_labels = lambda t: ref_factorize_labels(t, nv, vf)
+    try:
+        for clip_seed in range(100, 140):
+            ids = synthetic.make_clips(B, cfg, seed=clip_seed)
+            x = torch.from_numpy(ids).reshape(B, cfg.T, H, W)
+            out = {"clip_seed": clip_seed, "weight_seed": wseed, "ids": ids}
+            gaps = []
+            lg = model.compute_logits(x)  # (B, V, T, H, W)
+            if n_probe is None:
+                out["logits"] = lg.numpy()
+            else:
+                g = np.random.default_rng(5)
+                pt, ps = g.integers(0, cfg.T, n_probe), g.integers(0, cfg.S, n_probe)
+                out["probe_t"], out["probe_s"] = pt, ps
+                out["probe_logits"] = np.stack([lg[:, :, t, s // W, s % W].numpy() for t, s in zip(pt, ps)], 1)  # (B, n, V)
+            out["logits_sum"] = np.float64(lg.double().sum().item())
+            # masked forward: frames >= 2 fully masked plus scattered masks in frame 1
+            xm = x.clone()
+            xm[:, 2:] = model.mask_token_id
+            g = np.random.default_rng(clip_seed + 7)
+            scatter = torch.from_numpy(g.random((B, H, W)) < 0.3)
+            xm[:, 1][scatter] = model.mask_token_id
+            fo = model(xm.reshape(B, -1), torch.from_numpy(ids))
+            out["fwd_input"] = xm.reshape(B, -1).numpy()
+            out["fwd_loss"] = np.float64(fo.loss.item())
+            out["fwd_acc"] = np.float64(fo.acc.item())
+            out["fwd_logits_sum"] = np.float64(fo.logits.double().sum().item())
+            # maskgit on frame 2 with the captured draws
+            prompt = x.clone()
+            prompt[:, 2:] = model.mask_token_id
+            for steps in (1, 2, 3, 8):
+                for mode in ("random", "greedy"):
+                    torch.manual_seed(1000 + steps)
+                    s, fl, p_after, noise, gap = run_maskgit(model, prompt, 2, steps, mode)
+                    k = f"mg_s{steps}_{mode}"
+                    out[k + "_samples"] = s
+                    out[k + "_prompt_after"] = p_after
+                    out[k + "_noise"] = noise
+                    if steps == 2 and mode == "random":
+                        out["mg_step0_factored_logits"] = fl if n_probe is None else fl[:, :, :, :1, :]
+                    gaps.append(gap)
+            # generate(): 2 prompt frames -> 2 new frames
+            orig_mg = model.maskgit_generate
+            with Recorder(model) as rec:
+                def mg(prompt, out_t, **kw):  # gap-track the frame each of generate()'s decodes samples
+                    rec.out_t = out_t
+                    return orig_mg(prompt, out_t, **kw)
+
+                model.maskgit_generate = mg
+                torch.manual_seed(77)
+                try:
+                    gen = model.generate(torch.from_numpy(ids[:, :2 * cfg.S]), None, max_new_tokens=2 * cfg.S,
+                                         maskgit_steps=2, temperature=0.0)
+                finally:
+                    model.maskgit_generate = orig_mg
+            out["gen_out"] = gen.numpy()
+            out["gen_noise"] = np.stack(rec.noise).reshape(2, 1, B, cfg.S)
+            gaps.append(rec.min_gap if conf_gap(out["gen_noise"]) > 0 else 0.0)
+            min_gap = min(gaps)
+            if min_gap > 2e-4:
+                break
+    finally:
+        ref_smg.factorize_labels = orig_fl
+    out["min_gap"] = np.float64(min_gap)
+    out["mup_pinned"] = np.int64(0 if cfg.use_mup else 1)
+    out["cfg"] = np.array(repr(cfg_kwargs))
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
+    print(f"{name}: clip_seed={clip_seed} min_gap={min_gap:.3e} fwd_loss={out['fwd_loss']:.6f} "
+          f"fwd_acc={out['fwd_acc']:.6f} bytes={os.path.getsize(os.path.join(OUT, name + '.npz'))}")
 
 
 def shape_fixture(name, cfg_kwargs, wseed, gap_thr, do_eval=True, B=1, steps_list=(2,), n_probe=64):
@@ -600,7 +686,7 @@ def robust_evaluate_fixture(name, cfg_kwargs, wseed, first_seed, bar=6e-5, max_t
 
 def main():
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["tiny", "shape", "c35", "c138", "harness", "magvit", "magvit_full", "c138_gen"]
+    which = sys.argv[1:] or ["tiny", "shape", "c35", "c138", "harness", "magvit", "magvit_full", "c138_gen", "vocab"]
     if "magvit_full" in which:
         magvit_full_fixture()
     c138 = dict(num_layers=32, d_model=512, T=16, S=256, num_factored_vocabs=2, qk_norm=False, use_mup=False)
@@ -638,6 +724,12 @@ def main():
         tiny_fixture("tiny_qknorm", dict(base, qk_norm=True, use_mup=False), 12)
         tiny_fixture("tiny_mup", dict(base, qk_norm=False, use_mup=True), 13)
         tiny_fixture("tiny_qknorm_mup", dict(base, qk_norm=True, use_mup=True), 14)
+    if "vocab" in which:        # vocabularies other than 2 x 512 (image_vocab_size, num_factored_vocabs -> vf, V = nv * vf)
+        small = dict(num_layers=2, num_heads=2, d_model=64, T=4, S=16, use_mup=False)
+        vocab_fixture("vocab_v4096_n1", dict(small, image_vocab_size=4096, num_factored_vocabs=1, qk_norm=False), 41, n_probe=16)
+        vocab_fixture("vocab_v64_n3_qknorm", dict(small, image_vocab_size=262144, num_factored_vocabs=3, qk_norm=True), 42)
+        vocab_fixture("vocab_v16_n4", dict(small, image_vocab_size=65536, num_factored_vocabs=4, qk_norm=False), 43)
+        vocab_fixture("vocab_v100_n2", dict(small, image_vocab_size=10000, num_factored_vocabs=2, qk_norm=False), 44)
     if "shape" in which:
         real = dict(num_layers=2, T=16, S=256, num_factored_vocabs=2)
         shape_fixture("shape_dh32", dict(real, num_heads=2, d_model=64, qk_norm=False, use_mup=False), 21, 5e-5)
