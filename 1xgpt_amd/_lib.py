@@ -45,6 +45,11 @@ class Weights(C.Structure):
                 ("out_b", c_ptr), ("out_w16", c_ptr), ("layers_host", C.POINTER(LayerWeights)), ("out_w16_wide", C.c_int32),
                 ("out_frame_w16", c_ptr)]
 
+class FrameCond(C.Structure):
+    """genie_frame_cond: per-frame action conditioning (table (n_actions, d) f32 and ids (B, T) int64, device pointers)."""
+    _fields_ = [("table", c_ptr), ("ids", c_ptr), ("n_actions", C.c_int32)]
+
+
 WIDE_QKV, WIDE_PROJ, WIDE_FC1, WIDE_FC2 = 1, 2, 1, 2          # bits of the w16_wide fields (genie_hip.h)
 FUSED_QKV_STREAM = 4                                        # spatial attention: fused_w16 = [proj stream | qkv stream]
 TEMPORAL_QKV_F16X3_ELEMS = 393216   # f16 values of the f16x3 temporal qkv stream (csrc/kernels_fused_f16x3.hip)
@@ -111,6 +116,8 @@ SIGNATURES = {
                                              c_ptr]),
     "genie_train_backward_embed": (C.c_int, [C.POINTER(GenieCfg), C.POINTER(Weights), c_ptr, C.c_int, c_ptr, C.c_size_t,
                                              C.c_int, c_ptr]),
+    "genie_train_backward_embed_cond": (C.c_int, [C.POINTER(GenieCfg), C.POINTER(Weights), c_ptr, C.c_int, c_ptr, C.c_size_t,
+                                                  C.c_int, c_ptr, c_ptr, C.POINTER(FrameCond)]),
     "genie_sumsq": (C.c_int, [c_ptr, C.c_size_t, c_ptr, c_ptr, c_ptr]),
     "genie_adamw_step": (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float,
                                    C.c_float, C.c_int, C.c_float, c_ptr, C.c_float, c_ptr]),
@@ -162,6 +169,12 @@ SIGNATURES = {
     "genie_tokens_from_bits": (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, c_ptr]),
 }
 
+# the *_cond variants: the plain entry point's arguments + a trailing genie_frame_cond* (NULL = unconditioned)
+for _n in ("genie_embed", "genie_compute_logits", "genie_maskgit_generate", "genie_clean_pass", "genie_masked_frames_logits",
+           "genie_frame_pass", "genie_frames_pass", "genie_generate_cached", "genie_train_forward"):
+    SIGNATURES[_n + "_cond"] = (SIGNATURES[_n][0], SIGNATURES[_n][1] + [C.POINTER(FrameCond)])
+del _n
+
 _lib = None
 
 
@@ -206,6 +219,13 @@ def check(rc, where):
         if rc == E_UNSUPPORTED and "unmask_mode" in msg:
             raise NotImplementedError(msg)
         raise GenieHipError(rc, where, msg)
+
+
+def call_cond(lib, name, cond, *args):
+    """lib.<name>(*args) when `cond` is None (the unconditioned entry point, unchanged), else lib.<name>_cond(*args, cond)."""
+    if cond is None:
+        return getattr(lib, name)(*args)
+    return getattr(lib, name + "_cond")(*args, cond)
 
 
 def make_cfg(config, precision=PREC_EXACT) -> GenieCfg:

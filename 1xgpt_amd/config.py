@@ -42,12 +42,24 @@ class GenieConfig:
     mlp_drop: float = 0.0
     mlp_bias: bool = True
 
+    # per-frame action conditioning (not in the reference): A > 0 adds a learned (A, d_model) table whose row
+    # action_ids[b, t] joins the positional embedding of every token of frame t.  0 = unconditioned, today's model.
+    action_vocab_size: int = 0
+
     def __post_init__(self):
         self.factored_vocab_size = nth_root(self.image_vocab_size, self.num_factored_vocabs)
 
+    def to_json_dict(self) -> dict:
+        """What config.json holds: every field, except action_vocab_size when it is 0 -- the reference's from_pretrained is
+        cls(**config) and would refuse the unknown key, so unconditioned checkpoints stay loadable there (byte-identical)."""
+        d = dict(vars(self))
+        if not d.get("action_vocab_size"):
+            d.pop("action_vocab_size", None)
+        return d
+
     def save_pretrained(self, json_path):
         with open(json_path, "w") as f:
-            json.dump(vars(self), f)
+            json.dump(self.to_json_dict(), f)
 
     @classmethod
     def from_pretrained(cls, json_path):

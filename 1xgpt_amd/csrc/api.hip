@@ -285,10 +285,17 @@ int genie_pack_split_f16(const float* src, uint16_t* dst, size_t n, void* stream
 }
 
 int genie_embed(const genie_cfg* cfg, const genie_weights* w, const int64_t* ids, int B, float* x, void* stream) {
+    return genie_embed_cond(cfg, w, ids, B, x, stream, nullptr);
+}
+
+int genie_embed_cond(const genie_cfg* cfg, const genie_weights* w, const int64_t* ids, int B, float* x, void* stream,
+                     const genie_frame_cond* cond) {
     GENIE_TRY(check_cfg(cfg));
     GENIE_CHECK_ARG(w && ids && x && B >= 1, "embed: bad argument");
     GENIE_CHECK_ARG(w->pos_embed && w->mask_embed && w->embed[0], "embed: weight table incomplete");
-    return launch_embed(*cfg, *w, ids, B, x, as_stream(stream));
+    GENIE_TRY(check_frame_cond(cond, "embed"));
+    EmbedAct act;
+    return launch_embed(*cfg, *w, ids, B, x, as_stream(stream), frame_act(cond, cfg->S, 0, cfg->T, act));
 }
 
 int genie_layer_norm(const float* x, const float* gamma, const float* beta, float* y, int rows, int C, float eps,
@@ -386,13 +393,21 @@ int genie_readout_logits(const genie_cfg* cfg, const genie_weights* wt, const fl
 
 int genie_compute_logits(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int t0, int t1,
                          int layout, float* logits, void* workspace, size_t workspace_bytes, void* stream) {
+    return genie_compute_logits_cond(cfg, wt, ids, B, t0, t1, layout, logits, workspace, workspace_bytes, stream, nullptr);
+}
+
+int genie_compute_logits_cond(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int t0, int t1,
+                              int layout, float* logits, void* workspace, size_t workspace_bytes, void* stream,
+                              const genie_frame_cond* cond) {
     GENIE_TRY(check_cfg(cfg));
     GENIE_CHECK_ARG(wt && wt->layers_host && ids && logits, "compute_logits: NULL pointer");
     GENIE_CHECK_ARG(0 <= t0 && t0 <= t1 && t1 <= cfg->T, "compute_logits: bad frame range [%d,%d)", t0, t1);
+    GENIE_TRY(check_frame_cond(cond, "compute_logits"));
     GENIE_TRY(check_ws(*cfg, B, workspace, workspace_bytes));
     Workspace w = carve(*cfg, B, workspace);
     hipStream_t st = as_stream(stream);
-    GENIE_TRY(launch_embed(*cfg, *wt, ids, B, w.x, st));
+    EmbedAct act;
+    GENIE_TRY(launch_embed(*cfg, *wt, ids, B, w.x, st, frame_act(cond, cfg->S, 0, cfg->T, act)));
     GENIE_TRY(decoder(*cfg, *wt, w.x, w, B, st));
     if (t0 == t1) return GENIE_OK;
     return readout(*cfg, *wt, w.x, w, B, t0, t1, layout, logits, st);
@@ -405,10 +420,11 @@ size_t genie_prefix_cache_bytes(const genie_cfg* cfg, int B) {
 }
 
 static int prefix_forward(const genie_cfg& c, const genie_weights& wt, const int64_t* ids, int B, float* cache,
-                          bool clean, int tshift, Workspace& w, hipStream_t st, int cache_frames = 0) {
+                          bool clean, int tshift, Workspace& w, hipStream_t st, int cache_frames = 0,
+                          const EmbedAct* act = nullptr) {
     if (cache_frames <= 0) cache_frames = c.T;  // frames per clip in the cache layout (L, B, cache_frames, S, 3d)
     const size_t per_layer = (size_t)B * cache_frames * c.S * 3 * c.d_model;
-    GENIE_TRY(launch_embed(c, wt, ids, B, w.x, st));
+    GENIE_TRY(launch_embed(c, wt, ids, B, w.x, st, act));
     if (c.precision == GENIE_PREC_BF16) GENIE_TRY(prepare_bf16(c, w.x, w, B, st));
     if (c.precision == GENIE_PREC_F16X3) GENIE_TRY(prepare_f16x3(c, w.x, w, B, st));
     w.ln1_done = w.qkv_planes_done = false;
@@ -452,8 +468,16 @@ static int prefix_view(const genie_cfg* cfg, const genie_weights* wt, int B, int
 
 int genie_clean_pass(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int nframes, int cache_frames,
                      float* cache, size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    return genie_clean_pass_cond(cfg, wt, ids, B, nframes, cache_frames, cache, cache_bytes, workspace, workspace_bytes, stream,
+                                 nullptr);
+}
+
+int genie_clean_pass_cond(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int nframes,
+                          int cache_frames, float* cache, size_t cache_bytes, void* workspace, size_t workspace_bytes,
+                          void* stream, const genie_frame_cond* cond) {
     GENIE_TRY(check_cfg(cfg));
     GENIE_CHECK_ARG(wt && wt->layers_host && ids && cache, "clean_pass: NULL pointer");
+    GENIE_TRY(check_frame_cond(cond, "clean_pass"));
     GENIE_TRY(check_ws(*cfg, B, workspace, workspace_bytes));
     genie_cfg c2;
     genie_weights w2;
@@ -465,14 +489,23 @@ int genie_clean_pass(const genie_cfg* cfg, const genie_weights* wt, const int64_
     }
     Workspace w = carve(c2, B, workspace);
     w.model_T = cfg->T;
-    return prefix_forward(c2, w2, ids, B, cache, true, 0, w, as_stream(stream), cache_frames);
+    EmbedAct act;
+    return prefix_forward(c2, w2, ids, B, cache, true, 0, w, as_stream(stream), cache_frames, frame_act(cond, cfg->S, 0, cfg->T, act));
 }
 
 int genie_masked_frames_logits(const genie_cfg* cfg, const genie_weights* wt, const int64_t* frames, int B, int frame0,
                                int nframes, const float* cache, size_t cache_bytes, float* logits, void* workspace,
                                size_t workspace_bytes, void* stream) {
+    return genie_masked_frames_logits_cond(cfg, wt, frames, B, frame0, nframes, cache, cache_bytes, logits, workspace,
+                                           workspace_bytes, stream, nullptr);
+}
+
+int genie_masked_frames_logits_cond(const genie_cfg* cfg, const genie_weights* wt, const int64_t* frames, int B,
+                                    int frame0, int nframes, const float* cache, size_t cache_bytes, float* logits,
+                                    void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond) {
     GENIE_TRY(check_cfg(cfg));
     GENIE_CHECK_ARG(wt && wt->layers_host && frames && cache && logits, "masked_frames_logits: NULL pointer");
+    GENIE_TRY(check_frame_cond(cond, "masked_frames_logits"));
     GENIE_CHECK_ARG(frame0 == 0 || frame0 == 1, "masked_frames_logits: frame0 = %d (0 or 1)", frame0);
     GENIE_TRY(check_ws(*cfg, B, workspace, workspace_bytes));
     genie_cfg c2;
@@ -481,14 +514,24 @@ int genie_masked_frames_logits(const genie_cfg* cfg, const genie_weights* wt, co
     Workspace w = carve(c2, B, workspace);
     w.model_T = cfg->T;
     hipStream_t st = as_stream(stream);
-    GENIE_TRY(prefix_forward(c2, w2, frames, B, const_cast<float*>(cache), false, frame0, w, st));
+    EmbedAct act;   // slot i is clip frame frame0 + i
+    GENIE_TRY(prefix_forward(c2, w2, frames, B, const_cast<float*>(cache), false, frame0, w, st, 0,
+                             frame_act(cond, cfg->S, frame0, cfg->T, act)));
     return readout(c2, w2, w.x, w, B, 0, nframes, GENIE_LAYOUT_TOKEN_MAJOR, logits, st);
 }
 
 int genie_frames_pass(const genie_cfg* cfg, const genie_weights* wt, const int64_t* frame_ids, int B, int t0, int nf, float* cache,
                       size_t cache_bytes, float* logits, void* workspace, size_t workspace_bytes, void* stream) {
+    return genie_frames_pass_cond(cfg, wt, frame_ids, B, t0, nf, cache, cache_bytes, logits, workspace, workspace_bytes, stream,
+                                  nullptr);
+}
+
+int genie_frames_pass_cond(const genie_cfg* cfg, const genie_weights* wt, const int64_t* frame_ids, int B, int t0, int nf,
+                           float* cache, size_t cache_bytes, float* logits, void* workspace, size_t workspace_bytes,
+                           void* stream, const genie_frame_cond* cond) {
     GENIE_TRY(check_cfg(cfg));
     GENIE_CHECK_ARG(wt && wt->layers_host && frame_ids && cache, "frames_pass: NULL pointer");
+    GENIE_TRY(check_frame_cond(cond, "frames_pass"));
     GENIE_CHECK_ARG(nf >= 1 && t0 >= 0 && t0 + nf <= cfg->T, "frames_pass: frames [%d, %d) out of range", t0, t0 + nf);
     GENIE_CHECK_ARG(cache_bytes >= genie_prefix_cache_bytes(cfg, B), "frames_pass: cache too small");
     GENIE_TRY(check_ws(*cfg, B, workspace, workspace_bytes));
@@ -509,7 +552,8 @@ int genie_frames_pass(const genie_cfg* cfg, const genie_weights* wt, const int64
     hipStream_t st = as_stream(stream);
     genie_weights w1 = *wt;
     w1.pos_embed = wt->pos_embed + (size_t)t0 * cfg->S * cfg->d_model;  // pos_embed_TSC[0, t0 + i]
-    GENIE_TRY(launch_embed(c1, w1, frame_ids, B, w.x, st));
+    EmbedAct act;   // ... and the action of clip frame t0 + i
+    GENIE_TRY(launch_embed(c1, w1, frame_ids, B, w.x, st, frame_act(cond, cfg->S, t0, cfg->T, act)));
     if (!fr) {
         if (c1.precision == GENIE_PREC_BF16) GENIE_TRY(prepare_bf16(c1, w.x, w, B, st));
         if (c1.precision == GENIE_PREC_F16X3) GENIE_TRY(prepare_f16x3(c1, w.x, w, B, st));
@@ -534,7 +578,14 @@ int genie_frames_pass(const genie_cfg* cfg, const genie_weights* wt, const int64
 
 int genie_frame_pass(const genie_cfg* cfg, const genie_weights* wt, const int64_t* frame_ids, int B, int t, float* cache,
                      size_t cache_bytes, float* logits, void* workspace, size_t workspace_bytes, void* stream) {
-    return genie_frames_pass(cfg, wt, frame_ids, B, t, 1, cache, cache_bytes, logits, workspace, workspace_bytes, stream);
+    return genie_frame_pass_cond(cfg, wt, frame_ids, B, t, cache, cache_bytes, logits, workspace, workspace_bytes, stream, nullptr);
+}
+
+int genie_frame_pass_cond(const genie_cfg* cfg, const genie_weights* wt, const int64_t* frame_ids, int B, int t,
+                          float* cache, size_t cache_bytes, float* logits, void* workspace, size_t workspace_bytes,
+                          void* stream, const genie_frame_cond* cond) {
+    return genie_frames_pass_cond(cfg, wt, frame_ids, B, t, 1, cache, cache_bytes, logits, workspace, workspace_bytes, stream,
+                                  cond);
 }
 
 int genie_frame_linear(const uint16_t* a_fr, const uint16_t* w_fr, const float* bias, float* y, int M, int N, int K, int mode, void* stream) {
@@ -576,9 +627,20 @@ int genie_generate_cached(const genie_cfg* cfg, const genie_weights* wt, const i
                           float temperature, int unmask_mode, const float* noise, const float* uniforms, int teacher_force_time,
                           int merge_commit, int64_t* gen_out, float* logits0_out, float* cache, size_t cache_bytes, void* workspace,
                           size_t workspace_bytes, void* stream) {
+    return genie_generate_cached_cond(cfg, wt, ids, B, P, n_new, steps, temperature, unmask_mode, noise, uniforms, teacher_force_time,
+                                      merge_commit, gen_out, logits0_out, cache, cache_bytes, workspace, workspace_bytes, stream,
+                                      nullptr);
+}
+
+int genie_generate_cached_cond(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int P, int n_new,
+                               int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                               int teacher_force_time, int merge_commit, int64_t* gen_out, float* logits0_out, float* cache,
+                               size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
+                               const genie_frame_cond* cond) {
     GENIE_TRY(check_cfg(cfg));
     const genie_cfg& c = *cfg;
     GENIE_CHECK_ARG(wt && wt->layers_host && ids && gen_out && cache, "generate_cached: NULL pointer");
+    GENIE_TRY(check_frame_cond(cond, "generate_cached"));
     GENIE_CHECK_ARG(B >= 1 && P >= 1 && n_new >= 1 && P + n_new <= c.T && steps >= 1,
                     "generate_cached: B=%d, %d prompt + %d new frames of at most %d, steps %d", B, P, n_new, c.T, steps);
     if (unmask_mode != GENIE_UNMASK_RANDOM && unmask_mode != GENIE_UNMASK_GREEDY) {
@@ -614,14 +676,14 @@ int genie_generate_cached(const genie_cfg* cfg, const genie_weights* wt, const i
     for (int t = 0; t < P; ++t) GENIE_TRY(put_frame_ids(ids + (size_t)t * S, (long)T * S, idsP + (size_t)t * S, (long)P * S, S, B, 0, st));
     int rc = GENIE_E_UNSUPPORTED;
     if (P > 1) {
-        rc = genie_frames_pass(cfg, wt, idsP, B, 0, P, cache, cache_bytes, nullptr, workspace, workspace_bytes, stream);
+        rc = genie_frames_pass_cond(cfg, wt, idsP, B, 0, P, cache, cache_bytes, nullptr, workspace, workspace_bytes, stream, cond);
         if (rc == GENIE_E_UNSUPPORTED)
-            rc = genie_clean_pass(cfg, wt, idsP, B, P, c.T, cache, cache_bytes, workspace, workspace_bytes, stream);
+            rc = genie_clean_pass_cond(cfg, wt, idsP, B, P, c.T, cache, cache_bytes, workspace, workspace_bytes, stream, cond);
     }
     if (rc == GENIE_E_UNSUPPORTED) {
         for (int t = 0; t < P; ++t) {
             GENIE_TRY(put_frame_ids(ids + (size_t)t * S, (long)T * S, fin, S, S, B, 0, st));
-            GENIE_TRY(genie_frames_pass(cfg, wt, fin, B, t, 1, cache, cache_bytes, nullptr, workspace, workspace_bytes, stream));
+            GENIE_TRY(genie_frames_pass_cond(cfg, wt, fin, B, t, 1, cache, cache_bytes, nullptr, workspace, workspace_bytes, stream, cond));
         }
     } else {
         GENIE_TRY(rc);
@@ -633,7 +695,7 @@ int genie_generate_cached(const genie_cfg* cfg, const genie_weights* wt, const i
         if (hipMemsetAsync(unmasked, 0, BS, st) != hipSuccess) { set_error("memset failed"); return GENIE_E_LAUNCH; }
         for (int step = 0; step < steps; ++step) {
             if (!(step == 0 && opened))
-                GENIE_TRY(genie_frames_pass(cfg, wt, cur, B, t, 1, cache, cache_bytes, logits, workspace, workspace_bytes, stream));
+                GENIE_TRY(genie_frames_pass_cond(cfg, wt, cur, B, t, 1, cache, cache_bytes, logits, workspace, workspace_bytes, stream, cond));
             if (step == 0 && logits0_out) {   // orig_logits of the frame (st_mask_git.py:165,226): the step-0 logits, (B, n_new, S, V)
                 if (hipMemcpy2DAsync(logits0_out + (size_t)k * S * V, (size_t)n_new * S * V * 4, logits, (size_t)S * V * 4, (size_t)S * V * 4,
                                      (size_t)B, hipMemcpyDeviceToDevice, st) != hipSuccess) {
@@ -655,13 +717,13 @@ int genie_generate_cached(const genie_cfg* cfg, const genie_weights* wt, const i
             if (merge) {   // ... in the pass that also carries MaskGIT step 0 of frame t + 1 (all-mask tokens)
                 GENIE_TRY(put_frame_ids(fsrc, fstride, two, 2L * S, S, B, 0, st));
                 GENIE_TRY(put_frame_ids(nullptr, 0, two + S, 2L * S, S, B, c.image_vocab_size, st));
-                rc = genie_frames_pass(cfg, wt, two, B, t, 2, cache, cache_bytes, logits, workspace, workspace_bytes, stream);
+                rc = genie_frames_pass_cond(cfg, wt, two, B, t, 2, cache, cache_bytes, logits, workspace, workspace_bytes, stream, cond);
                 if (rc == GENIE_E_UNSUPPORTED) merge = false;
                 else { GENIE_TRY(rc); opened = true; }
             }
             if (!opened) {
                 GENIE_TRY(put_frame_ids(fsrc, fstride, fin, S, S, B, 0, st));
-                GENIE_TRY(genie_frames_pass(cfg, wt, fin, B, t, 1, cache, cache_bytes, nullptr, workspace, workspace_bytes, stream));
+                GENIE_TRY(genie_frames_pass_cond(cfg, wt, fin, B, t, 1, cache, cache_bytes, nullptr, workspace, workspace_bytes, stream, cond));
             }
         }
     }
@@ -724,9 +786,18 @@ int genie_maskgit_generate(const genie_cfg* cfg, const genie_weights* wt, int64_
                            float temperature, int unmask_mode, const float* noise, const float* uniforms,
                            int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
                            void* workspace, size_t workspace_bytes, void* stream) {
+    return genie_maskgit_generate_cond(cfg, wt, prompt, B, out_t, steps, temperature, unmask_mode, noise, uniforms, samples_out,
+                                       logits0_out, layout, status_flag, workspace, workspace_bytes, stream, nullptr);
+}
+
+int genie_maskgit_generate_cond(const genie_cfg* cfg, const genie_weights* wt, int64_t* prompt, int B, int out_t, int steps,
+                                float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                                int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
+                                void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond) {
     GENIE_TRY(check_cfg(cfg));
     const genie_cfg& c = *cfg;
     GENIE_CHECK_ARG(wt && wt->layers_host && prompt && samples_out, "maskgit_generate: NULL pointer");
+    GENIE_TRY(check_frame_cond(cond, "maskgit_generate"));
     if (!(out_t >= 1 && out_t < c.T)) {  // assert out_t  (st_mask_git.py:154)
         set_error("maskgit_generate requires 0 < out_t < T (got %d)", out_t);
         return GENIE_E_ASSERT;
@@ -747,8 +818,10 @@ int genie_maskgit_generate(const genie_cfg* cfg, const genie_weights* wt, int64_
 
     GENIE_TRY(launch_check_masked(prompt, B, c.T, c.S, out_t, c.image_vocab_size, status_flag, st));
     if (hipMemsetAsync(w.unmasked, 0, BS, st) != hipSuccess) { set_error("memset failed"); return GENIE_E_LAUNCH; }
+    EmbedAct act;
+    const EmbedAct* pact = frame_act(cond, c.S, 0, c.T, act);
     for (int step = 0; step < steps; ++step) {
-        GENIE_TRY(launch_embed(c, *wt, prompt, B, w.x, st));
+        GENIE_TRY(launch_embed(c, *wt, prompt, B, w.x, st, pact));
         GENIE_TRY(decoder(c, *wt, w.x, w, B, st));
         GENIE_TRY(readout(c, *wt, w.x, w, B, out_t, out_t + 1, GENIE_LAYOUT_TOKEN_MAJOR, w.logits, st));
         if (step == 0 && logits0_out) {  // orig_logits_CHW: step-0 logits are what is returned (:165,226)

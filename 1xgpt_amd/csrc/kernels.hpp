@@ -100,7 +100,35 @@ struct ProfScope {
     ~ProfScope();
 };
 
-int launch_embed(const genie_cfg& c, const genie_weights& w, const int64_t* ids, int B, float* x, hipStream_t st);
+// Per-frame action conditioning of the embedding (genie_frame_cond): token (b, t, s) of a pass over c.T frames adds row
+// ids[b * clip_stride + t] of `table` (n_act rows of d_model) to its position row; `ids` already points at the pass's first
+// frame (the absolute frame t0 of a window pass: ids = cond->ids + t0, clip_stride = the model's T).
+struct EmbedAct {
+    const float* table = nullptr;
+    const int64_t* ids = nullptr;
+    long clip_stride = 0;
+    int S = 1;
+    int n_act = 0;
+};
+// genie_frame_cond -> EmbedAct of a pass over frames [t0, t0 + pass T) of clips with model_T frames; NULL = unconditioned
+inline const EmbedAct* frame_act(const genie_frame_cond* fc, int S, int t0, int model_T, EmbedAct& a) {
+    if (!fc || fc->n_actions <= 0) return nullptr;
+    a.table = fc->table;
+    a.ids = fc->ids + t0;
+    a.clip_stride = model_T;
+    a.S = S;
+    a.n_act = fc->n_actions;
+    return &a;
+}
+inline int check_frame_cond(const genie_frame_cond* fc, const char* where) {
+    if (!fc) return GENIE_OK;
+    GENIE_CHECK_ARG(fc->n_actions >= 0, "%s: n_actions = %d", where, (int)fc->n_actions);
+    GENIE_CHECK_ARG(fc->n_actions == 0 || (fc->table && fc->ids), "%s: frame condition without table / ids", where);
+    return GENIE_OK;
+}
+// act == NULL or act->n_act == 0: the unconditioned kernel
+int launch_embed(const genie_cfg& c, const genie_weights& w, const int64_t* ids, int B, float* x, hipStream_t st,
+                 const EmbedAct* act = nullptr);
 int launch_layer_norm(const float* x, const float* g, const float* b, float* y, long rows, int C, float eps,
                       hipStream_t st);
 int launch_layer_norm_bf16(const float* x, const float* g, const float* b, uint16_t* y, long rows, int C, float eps,
@@ -199,6 +227,10 @@ int launch_ce_fwd_bwd(const genie_cfg& c, float* logits, const int64_t* ids, con
                       hipStream_t st);
 int launch_embed_bwd(const genie_cfg& c, const float* dx, const int64_t* ids, int B, float* dpos, float* dmask,
                      float* const* tables_host, float beta, float* colpart, hipStream_t st);
+// gradient of the action table: d_table[k] = sum over frames (b, t) with act_ids[b, t] == k (ascending) of sum_s dx[b, t, s, :];
+// frame_sums: (B * T, d) f32 scratch.  Fixed order, no atomics.
+int launch_action_embed_bwd(const genie_cfg& c, const float* dx, const int64_t* act_ids, int n_act, int B, float* d_table,
+                            float beta, float* frame_sums, hipStream_t st);
 int launch_sumsq(const float* x, size_t n, double* out, double* scratch, hipStream_t st);
 // 16-bit operand copies (kernels_train16.hip); npl = 1 bf16, 2 = f16 split planes [hi | lo]
 // colpart != NULL: also the column sums of the (post-gelu') values: slabs [rows/64][cols] for launch_slab_reduce

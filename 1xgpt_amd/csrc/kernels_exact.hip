@@ -11,12 +11,16 @@ namespace genie {
 // ------------------------------------------------------------------------------------------------
 // a2  FactorizedEmbedding.forward + pos_embed (factorization_utils.py:29-52, st_mask_git.py:257-261)
 // one thread per float4 of the output; ids are read through L1 (d/4 threads share one id).
+// ACT (per-frame action conditioning, genie_frame_cond): the action row of the token's frame is added to the position row
+// first, then the sum to the token term -- x = tok + (pos + act) -- so that a run with actions is bit-identical to an
+// unconditioned model whose positional table is pos + act.  An action id outside [0, n_act) adds zero and reads nothing.
 // ------------------------------------------------------------------------------------------------
+template <bool ACT>
 __global__ void embed_kernel(const int64_t* __restrict__ ids, const float* __restrict__ pos,
                              const float* __restrict__ mask_embed, const float* __restrict__ e0,
                              const float* __restrict__ e1, const float* __restrict__ e2,
                              const float* __restrict__ e3, float* __restrict__ x, long n_tok, int TS, int d,
-                             int nfac, int vf, int64_t mask_id) {
+                             int nfac, int vf, int64_t mask_id, EmbedAct act) {
     const int d4 = d >> 2;
     long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n_tok * d4) return;
@@ -37,18 +41,35 @@ __global__ void embed_kernel(const int64_t* __restrict__ ids, const float* __res
             v.x += e.x; v.y += e.y; v.z += e.z; v.w += e.w;
         }
     }
-    float4 p = *reinterpret_cast<const float4*>(pos + (size_t)(tok % TS) * d + c);
+    const long ts = tok % TS;
+    float4 p = *reinterpret_cast<const float4*>(pos + (size_t)ts * d + c);
+    if constexpr (ACT) {
+        const long b = tok / TS, t = ts / act.S;  // clip, frame of the pass
+        const int64_t a = act.ids[b * act.clip_stride + t];
+        if (a >= 0 && a < act.n_act) {
+            float4 e = *reinterpret_cast<const float4*>(act.table + (size_t)a * d + c);
+            p.x += e.x; p.y += e.y; p.z += e.z; p.w += e.w;
+        }
+    }
     v.x += p.x; v.y += p.y; v.z += p.z; v.w += p.w;
     *reinterpret_cast<float4*>(x + (size_t)tok * d + c) = v;
 }
 
-int launch_embed(const genie_cfg& c, const genie_weights& w, const int64_t* ids, int B, float* x, hipStream_t st) {
+int launch_embed(const genie_cfg& c, const genie_weights& w, const int64_t* ids, int B, float* x, hipStream_t st,
+                 const EmbedAct* act) {
     long n_tok = (long)B * c.T * c.S;
     long n = n_tok * (c.d_model / 4);
     int blocks = (int)((n + 255) / 256);
-    embed_kernel<<<blocks, 256, 0, st>>>(ids, w.pos_embed, w.mask_embed, w.embed[0], w.embed[1], w.embed[2],
-                                         w.embed[3], x, n_tok, c.T * c.S, c.d_model, c.num_factored,
-                                         c.factored_vocab, (int64_t)c.image_vocab_size);
+    if (act && act->n_act > 0) {
+        embed_kernel<true><<<blocks, 256, 0, st>>>(ids, w.pos_embed, w.mask_embed, w.embed[0], w.embed[1], w.embed[2],
+                                                   w.embed[3], x, n_tok, c.T * c.S, c.d_model, c.num_factored,
+                                                   c.factored_vocab, (int64_t)c.image_vocab_size, *act);
+        GENIE_LAUNCH_CHECK("embed_act");
+        return GENIE_OK;
+    }
+    embed_kernel<false><<<blocks, 256, 0, st>>>(ids, w.pos_embed, w.mask_embed, w.embed[0], w.embed[1], w.embed[2],
+                                                w.embed[3], x, n_tok, c.T * c.S, c.d_model, c.num_factored,
+                                                c.factored_vocab, (int64_t)c.image_vocab_size, EmbedAct{});
     GENIE_LAUNCH_CHECK("embed");
     return GENIE_OK;
 }

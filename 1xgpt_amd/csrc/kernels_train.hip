@@ -1337,6 +1337,66 @@ int launch_embed_bwd(const genie_cfg& c, const float* dx, const int64_t* ids, in
                                colpart, st);
 }
 
+// action-table gradient (per-frame action conditioning, genie_frame_cond): the action row of frame (b, t) is added to every
+// token of that frame, so
+//   stage 1: fs[b*T + t, :] = sum_s dx[b, t, s, :]                (s ascending; one thread per (frame, channel))
+//   stage 2: d_table[k, :]  = sum over frames n (ascending) with act_ids[n] == k of fs[n, :]
+// stage 2 is embed_bwd_tables_kernel's ordered ballot walk over the B*T frame ids, one block per action: no atomics.
+__global__ void frame_sum_kernel(const float* __restrict__ dx, float* __restrict__ fs, long n_frames, int S, int d) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_frames * d) return;
+    const long f = i / d;
+    const int c = (int)(i - f * d);
+    const float* r = dx + (size_t)f * S * d + c;
+    float s = 0.f;
+    for (int k = 0; k < S; ++k) s += r[(size_t)k * d];
+    fs[i] = s;
+}
+__global__ __launch_bounds__(256) void action_bwd_kernel(const float* __restrict__ fs, const int64_t* __restrict__ act_ids,
+                                                         long n_frames, int d, float* __restrict__ d_table, float beta) {
+    __shared__ unsigned long long masks[4];  // [wave]: frames base + wave*64 + bit
+    const int64_t k = blockIdx.x;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};  // channels threadIdx.x + 256*j, d <= 1024
+    for (long base = 0; base < n_frames; base += 256) {
+        const long i = base + threadIdx.x;
+        const unsigned long long bal = __ballot(i < n_frames && act_ids[i] == k);
+        if (lane == 0) masks[wid] = bal;
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            unsigned long long bits = masks[w];
+            while (bits) {
+                const int bit = __ffsll((long long)bits) - 1;
+                bits &= bits - 1;
+                const float* r = fs + (size_t)(base + w * 64 + bit) * d;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int c = threadIdx.x + 256 * j;
+                    if (c < d) acc[j] += r[c];
+                }
+            }
+        }
+        __syncthreads();
+    }
+    float* out = d_table + (size_t)k * d;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = threadIdx.x + 256 * j;
+        if (c < d) out[c] = (beta != 0.f ? beta * out[c] : 0.f) + acc[j];
+    }
+}
+int launch_action_embed_bwd(const genie_cfg& c, const float* dx, const int64_t* act_ids, int n_act, int B, float* d_table,
+                            float beta, float* frame_sums, hipStream_t st) {
+    GENIE_CHECK_SHAPE(c.d_model <= 1024, "action embed backward: d_model > 1024");
+    const long n_frames = (long)B * c.T;
+    frame_sum_kernel<<<(unsigned)((n_frames * c.d_model + 255) / 256), 256, 0, st>>>(dx, frame_sums, n_frames, c.S, c.d_model);
+    GENIE_LAUNCH_CHECK("frame_sum");
+    action_bwd_kernel<<<(unsigned)n_act, 256, 0, st>>>(frame_sums, act_ids, n_frames, c.d_model, d_table, beta);
+    GENIE_LAUNCH_CHECK("action_embed_bwd");
+    return GENIE_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // optimizer: sum of squares (two-stage, f64) and torch.optim.AdamW's update with clip_grad_norm_ folded in
 // ------------------------------------------------------------------------------------------------

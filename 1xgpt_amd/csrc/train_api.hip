@@ -316,7 +316,7 @@ static int need16(const genie_weights* wt, const genie_cfg& c, const char* what)
 }
 
 static int train_forward16(const genie_cfg& c, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels,
-                           int B, char* acts, size_t acts_bytes, double* sums, hipStream_t st) {
+                           int B, char* acts, size_t acts_bytes, double* sums, hipStream_t st, const EmbedAct* act) {
     const int npl = npl_of(c);
     GENIE_TRY(need16(wt, c, "genie_train_forward"));
     const TrainActs16 a = train_acts16(c, B, npl);
@@ -327,7 +327,7 @@ static int train_forward16(const genie_cfg& c, const genie_weights* wt, const in
     float* tmp = (float*)(acts + a.logits);  // free until the readout
     auto F = [&](int l, size_t off) { return (float*)(acts + a.per_layer * l + off); };
     auto H16 = [&](int l, size_t off) { return (uint16_t*)(acts + a.per_layer * l + off); };
-    GENIE_TRY(launch_embed(c, *wt, input_ids, B, F(0, a.x0), st));
+    GENIE_TRY(launch_embed(c, *wt, input_ids, B, F(0, a.x0), st, act));
     if (c.qk_norm) GENIE_TRY(launch_cast16(npl, F(0, a.x0), H16(0, a.u1), pd, st));
     for (int l = 0; l < c.num_layers; ++l) {
         const genie_layer_weights& lw = wt->layers_host[l];
@@ -482,17 +482,26 @@ int genie_train_pack_weights(const genie_cfg* cfg, const genie_weights* w, const
 
 int genie_train_forward(const genie_cfg* cfg, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels,
                         int B, float* acts, size_t acts_bytes, double* sums, void* stream) {
+    return genie_train_forward_cond(cfg, wt, input_ids, labels, B, acts, acts_bytes, sums, stream, nullptr);
+}
+
+int genie_train_forward_cond(const genie_cfg* cfg, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels,
+                             int B, float* acts, size_t acts_bytes, double* sums, void* stream,
+                             const genie_frame_cond* cond) {
     GENIE_TRY(train_check(cfg, B));
     GENIE_CHECK_ARG(wt && input_ids && labels && acts && sums, "genie_train_forward: NULL argument");
+    GENIE_TRY(check_frame_cond(cond, "genie_train_forward"));
     const genie_cfg& c = *cfg;
+    EmbedAct ea;
+    const EmbedAct* act = frame_act(cond, c.S, 0, c.T, ea);
     if (c.precision != GENIE_PREC_EXACT)
-        return train_forward16(c, wt, input_ids, labels, B, (char*)acts, acts_bytes, sums, (hipStream_t)stream);
+        return train_forward16(c, wt, input_ids, labels, B, (char*)acts, acts_bytes, sums, (hipStream_t)stream, act);
     const TrainActs a = train_acts(c, B);
     GENIE_CHECK_ARG(acts_bytes >= a.total * sizeof(float), "genie_train_forward: activation buffer too small: %zu < %zu",
                     acts_bytes, a.total * sizeof(float));
     hipStream_t st = (hipStream_t)stream;
     const int d = c.d_model, hid = c.hidden, M = B * c.T * c.S;
-    GENIE_TRY(launch_embed(c, *wt, input_ids, B, acts + a.o_x0, st));
+    GENIE_TRY(launch_embed(c, *wt, input_ids, B, acts + a.o_x0, st, act));
     for (int l = 0; l < c.num_layers; ++l) {
         const genie_layer_weights& lw = wt->layers_host[l];
         float* L = acts + a.per_layer * l;
@@ -626,14 +635,29 @@ int genie_train_backward_layer(const genie_cfg* cfg, const genie_weights* wt, co
 
 int genie_train_backward_embed(const genie_cfg* cfg, const genie_weights* grads, const int64_t* input_ids, int B,
                                void* workspace, size_t workspace_bytes, int accumulate, void* stream) {
+    return genie_train_backward_embed_cond(cfg, grads, input_ids, B, workspace, workspace_bytes, accumulate, stream, nullptr,
+                                           nullptr);
+}
+
+int genie_train_backward_embed_cond(const genie_cfg* cfg, const genie_weights* grads, const int64_t* input_ids, int B,
+                                    void* workspace, size_t workspace_bytes, int accumulate, void* stream,
+                                    float* d_table, const genie_frame_cond* cond) {
     GENIE_TRY(train_check(cfg, B));
     GENIE_CHECK_ARG(grads && input_ids && workspace, "genie_train_backward_embed: NULL argument");
+    GENIE_TRY(check_frame_cond(cond, "genie_train_backward_embed"));
+    const bool act = cond && cond->n_actions > 0;
+    GENIE_CHECK_ARG(!act || d_table, "genie_train_backward_embed: actions without d_table");
     TrainWs w = train_ws(*cfg, B, workspace);
     GENIE_CHECK_ARG(workspace_bytes >= w.total, "training workspace too small: %zu < %zu", workspace_bytes, w.total);
     float* tables[4] = {nullptr, nullptr, nullptr, nullptr};
     for (int j = 0; j < cfg->num_factored && j < 4; ++j) tables[j] = (float*)grads->embed[j];
-    return launch_embed_bwd(*cfg, w.dx, input_ids, B, (float*)grads->pos_embed, (float*)grads->mask_embed, tables,
-                            accumulate ? 1.0f : 0.0f, w.colpart, (hipStream_t)stream);
+    const float beta = accumulate ? 1.0f : 0.0f;
+    hipStream_t st = (hipStream_t)stream;
+    GENIE_TRY(launch_embed_bwd(*cfg, w.dx, input_ids, B, (float*)grads->pos_embed, (float*)grads->mask_embed, tables, beta,
+                               w.colpart, st));
+    if (!act) return GENIE_OK;
+    // per-frame sums of dx in w.d1 ((M, d) floats, dead after the last layer's backward; B*T rows needed)
+    return launch_action_embed_bwd(*cfg, w.dx, cond->ids, cond->n_actions, B, d_table, beta, w.d1, st);
 }
 
 int genie_sumsq(const float* x, size_t n, double* out, double* scratch, void* stream) {

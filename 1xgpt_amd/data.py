@@ -1,7 +1,8 @@
 """RawTokenDataset -- reader of the 1X token dataset layout (counterpart of the reference's data.py:17-106).
 
 On disk: ``metadata.json`` {num_images, s, vocab_size, hz, token_dtype?}, ``video.bin`` = (num_images, s, s) tokens
-(uint32 by default), optional ``segment_ids.bin`` = (num_images,) int32.  Windows of ``window_size`` frames spaced
+(uint32 by default), optional ``segment_ids.bin`` = (num_images,) int32, optional ``actions.bin`` = (num_images,) uint16 (the
+action of each frame; items then carry ``action_ids`` (window_size,) int64 aligned with the frames).  Windows of ``window_size`` frames spaced
 ``stride`` apart; ``filter_interrupts`` drops windows whose first and last frame belong to different segments,
 ``filter_overlaps`` keeps each frame in at most one window.  Same constructor, attributes (``data``,
 ``metadata``, ``valid_start_inds``) and item dict as the reference.  ``get_maskgit_collator`` is the training
@@ -49,6 +50,8 @@ class RawTokenDataset(TorchDataset):
                               dtype=np.dtype(self.metadata.get("token_dtype", "uint32")))
         seg_file = root / "segment_ids.bin"
         self.segment_ids = np.memmap(seg_file, dtype=np.int32, mode="r", shape=(n,)) if seg_file.is_file() else None
+        act_file = root / "actions.bin"   # (the reference names it and leaves it commented out, data.py:44-48)
+        self.actions = np.memmap(act_file, dtype=np.uint16, mode="r", shape=(n,)) if act_file.is_file() else None
         if filter_interrupts and self.segment_ids is None:
             raise NotImplementedError("Cannot filter interrupted sequences without segment ids.")
         self.window_size, self.stride = window_size, stride
@@ -64,22 +67,37 @@ class RawTokenDataset(TorchDataset):
         start_ind = self.valid_start_inds[idx]
         x = torch.from_numpy((self.data[start_ind: start_ind + self.video_len + 1: self.stride]).astype(np.int64))
         x = x.flatten()
-        return {"input_ids": x, "labels": x, "attention_mask": torch.ones_like(x)}
+        item = {"input_ids": x, "labels": x, "attention_mask": torch.ones_like(x)}
+        if self.actions is not None:   # same frames as the window
+            item["action_ids"] = torch.from_numpy(self.actions[start_ind: start_ind + self.video_len + 1: self.stride].astype(np.int64))
+        return item
 
     def batch(self, idxs):
         """Stack several windows -> (len(idxs), window_size * s * s) int64 (what default_data_collator builds)."""
         return torch.stack([self[i]["input_ids"] for i in idxs])
 
+    def action_batch(self, idxs):
+        """The windows' per-frame actions -> (len(idxs), window_size) int64 (needs actions.bin)."""
+        if self.actions is None:
+            raise FileNotFoundError("this dataset has no actions.bin")
+        return torch.stack([self[i]["action_ids"] for i in idxs])
+
 
 def write_token_dataset(data_dir, tokens: np.ndarray, segment_ids: np.ndarray = None, hz=30, vocab_size=262144,
-                        token_dtype="uint32", extra_metadata=None):
-    """Write (num_images, s, s) tokens in the dataset layout (used by generate and by the tests)."""
+                        token_dtype="uint32", extra_metadata=None, actions: np.ndarray = None):
+    """Write (num_images, s, s) tokens in the dataset layout (used by generate and by the tests); `actions`: (num_images,)
+    per-frame action ids in [0, 65536) -> actions.bin (uint16)."""
     data_dir = Path(data_dir)
     data_dir.mkdir(parents=True, exist_ok=True)
     tokens = np.asarray(tokens)
     tokens.astype(np.dtype(token_dtype)).tofile(data_dir / "video.bin")
     if segment_ids is not None:
         np.asarray(segment_ids, dtype=np.int32).tofile(data_dir / "segment_ids.bin")
+    if actions is not None:
+        a = np.asarray(actions)
+        if a.shape != (tokens.shape[0],) or (a.size and (a.min() < 0 or a.max() > 0xFFFF)):
+            raise ValueError(f"actions must be ({tokens.shape[0]},) integers in [0, 65536), got shape {a.shape}")
+        a.astype(np.uint16).tofile(data_dir / "actions.bin")
     meta = {"num_images": int(tokens.shape[0]), "s": int(tokens.shape[1]), "vocab_size": vocab_size, "hz": hz,
             "token_dtype": token_dtype}
     meta.update(extra_metadata or {})
@@ -113,10 +131,11 @@ class TorchDraws:
         return random.uniform(a, b)
 
 
-def maskgit_collate(input_ids, config, draws=None):
+def maskgit_collate(input_ids, config, draws=None, action_ids=None):
     """(B, T*S) int64 clips -> {"input_ids", "labels"} following data.py:112-167 draw for draw.
 
-    `draws` replays captured draws (parity tests); None draws fresh ones on the clips' device."""
+    `draws` replays captured draws (parity tests); None draws fresh ones on the clips' device.  `action_ids` (B, T), if given,
+    are passed through as batch["action_ids"] (int64, on the clips' device) and draw nothing."""
     ids = input_ids.to(torch.int64)
     dev = ids.device
     draws = draws or TorchDraws(dev)
@@ -156,11 +175,15 @@ def maskgit_collate(input_ids, config, draws=None):
             break
     x = (x_THWC * powers).sum(-1)
     x[:, first:][mask] = mask_token_id
-    return {"input_ids": x.reshape(B, -1), "labels": labels.reshape(B, -1)}
+    out = {"input_ids": x.reshape(B, -1), "labels": labels.reshape(B, -1)}
+    if action_ids is not None:
+        out["action_ids"] = torch.as_tensor(action_ids).to(device=dev, dtype=torch.int64).reshape(B, config.T)
+    return out
 
 
 def get_maskgit_collator(config):
     """collate_fn(features: list of {"input_ids": (T*S,) tensor}) -> batch dict, as data.py:109."""
     def collate_fn(features):
-        return maskgit_collate(torch.stack([ex["input_ids"] for ex in features]), config)
+        acts = torch.stack([ex["action_ids"] for ex in features]) if "action_ids" in features[0] else None
+        return maskgit_collate(torch.stack([ex["input_ids"] for ex in features]), config, action_ids=acts)
     return collate_fn

@@ -33,11 +33,12 @@ class GenieEvaluator:
         self.device = device
         self.args = args
 
-    def predict_zframe_logits(self, input_ids: torch.LongTensor, noise=None, return_logits=True):
+    def predict_zframe_logits(self, input_ids: torch.LongTensor, noise=None, return_logits=True, action_ids=None):
         """input_ids (B, T*H*W) -> (samples (B,T-1,H,W), factored logits (B,512,2,T-1,H,W)).
 
         Total forward passes = (T-1) * maskgit_steps (evaluate.py:90).
-        noise: optional (T-1, maskgit_steps-1, B, S) replay of the "random" unmasking draws."""
+        noise: optional (T-1, maskgit_steps-1, B, S) replay of the "random" unmasking draws.
+        action_ids: (B, T) per-frame actions of an action-conditioned model."""
         m, a = self.model, self.args
         T = m.config.T
         clips = input_ids.to(self.device).to(torch.int64).view(-1, T, a.latent_h, a.latent_w)
@@ -48,7 +49,7 @@ class GenieEvaluator:
             timeline[:, t:] = m.mask_token_id
             frame, lg = m.maskgit_generate(timeline, out_t=t, maskgit_steps=a.maskgit_steps, temperature=a.temperature,
                                            noise=None if noise is None else noise[t - 1], return_logits=return_logits,
-                                           check=False)
+                                           check=False, action_ids=action_ids)
             frames.append(frame)
             logits.append(lg)
         return torch.stack(frames, dim=1), (torch.stack(logits, dim=3) if return_logits else None)
@@ -63,7 +64,7 @@ class GenieEvaluator:
     # ------------------------------------------------------------------ teacher-forced prefix reuse
     @torch.no_grad()
     def predict_zframe_logits_reuse(self, input_ids: torch.LongTensor, noise=None, return_logits=True,
-                                    unmask_mode="random", step0_hook=None):
+                                    unmask_mode="random", step0_hook=None, action_ids=None):
         """Same contract and same per-row arithmetic as ``predict_zframe_logits`` in (1 + steps) passes over T-1 frames
         instead of 15 * steps forwards over T: the ground-truth frames < t of every timeline t are identical to one clean
         pass (temporal attention is causal, everything else per-frame), so they are computed once (frames 0..T-2: no
@@ -72,7 +73,9 @@ class GenieEvaluator:
         Returns (samples (B,T-1,H,W), logits (B,512,2,T-1,H,W)).
         step0_hook(logits_token_major (B,T-1,S,V)): called right after the step-0 pass is enqueued, while the logits buffer
         still holds the step-0 logits (later steps overwrite it in place); with a hook and return_logits=False no copy of the
-        (2 GB at 128 clips) logits is kept."""
+        (2 GB at 128 clips) logits is kept.
+        action_ids: (B, T) per-frame actions of an action-conditioned model (slot i of the masked passes is clip frame i + 1 and
+        takes action_ids[:, i + 1])."""
         import math
         lib = _lib.load()
         m = self.model
@@ -84,6 +87,7 @@ class GenieEvaluator:
         ids = input_ids.to(self.device).to(torch.int64).view(-1, T, S)
         B = ids.shape[0]
         dev = ids.device
+        cond = m._cond(action_ids, B)
         ws = m._workspace(B)
         nbytes = lib.genie_prefix_cache_bytes(cfg, B)
         if getattr(self, "_cache", None) is None or self._cache.numel() < nbytes or self._cache.device != dev:
@@ -92,8 +96,8 @@ class GenieEvaluator:
         cache = self._cache
         st = torch.cuda.current_stream().cuda_stream
         ctx = ids[:, :n].contiguous()                       # ground-truth context frames 0..T-2
-        _lib.check(lib.genie_clean_pass(cfg, w, ctx.data_ptr(), B, n, n, cache.data_ptr(), nbytes, ws.data_ptr(), ws.numel(),
-                                        st), "genie_clean_pass")
+        _lib.check(_lib.call_cond(lib, "genie_clean_pass", cond, cfg, w, ctx.data_ptr(), B, n, n, cache.data_ptr(), nbytes,
+                                  ws.data_ptr(), ws.numel(), st), "genie_clean_pass")
         cur = torch.full((B, n, S), m.mask_token_id, dtype=torch.int64, device=dev)
         unmasked = torch.zeros(B * n, S, dtype=torch.uint8, device=dev)
         samples = torch.empty(B * n, S, dtype=torch.int64, device=dev)
@@ -101,8 +105,8 @@ class GenieEvaluator:
         logits = torch.empty(B, n, S, V, dtype=torch.float32, device=dev)
         logits0 = None
         for step in range(steps):
-            _lib.check(lib.genie_masked_frames_logits(cfg, w, cur.data_ptr(), B, 1, n, cache.data_ptr(), nbytes,
-                                                      logits.data_ptr(), ws.data_ptr(), ws.numel(), st),
+            _lib.check(_lib.call_cond(lib, "genie_masked_frames_logits", cond, cfg, w, cur.data_ptr(), B, 1, n, cache.data_ptr(),
+                                      nbytes, logits.data_ptr(), ws.data_ptr(), ws.numel(), st),
                        "genie_masked_frames_logits")
             if step == 0:
                 if step0_hook is not None:
@@ -137,7 +141,7 @@ class GenieEvaluator:
         return samples_THW, fl
 
     @torch.no_grad()
-    def evaluate_metric_sums_reuse(self, input_ids, labels=None, noise=None):
+    def evaluate_metric_sums_reuse(self, input_ids, labels=None, noise=None, action_ids=None):
         """``evaluate_metric_sums`` on the prefix-reuse path (same six sums)."""
         lib = _lib.load()
         m = self.model
@@ -157,7 +161,9 @@ class GenieEvaluator:
                                              ce.data_ptr(), st), "genie_factored_ce")
 
         # the CE is taken from the step-0 logits on the stream BEFORE the next MaskGIT step overwrites them: no 2 GB copy
-        samples, _ = self.predict_zframe_logits_reuse(ids, noise=noise, return_logits=False, step0_hook=ce_of_step0)
+        m._cond(action_ids, B)   # (argument errors before anything is enqueued)
+        samples, _ = self.predict_zframe_logits_reuse(ids, noise=noise, return_logits=False, step0_hook=ce_of_step0,
+                                                      action_ids=action_ids)
         # (ground truth frames 1..T-1 == samples).sum() and the vector's sizes, on the device (no torch arithmetic)
         _lib.check(lib.genie_metric_hits(ids.data_ptr() + S * 8, T * S, samples.data_ptr(), (T - 1) * S, B, (T - 1) * S,
                                          ce.data_ptr(), float(B * (T - 1) * S), float(B * (T - 1)), float(B), sums.data_ptr(), st),
@@ -165,7 +171,7 @@ class GenieEvaluator:
         return sums
 
     @torch.no_grad()
-    def evaluate_metric_sums(self, input_ids, labels=None, noise=None):
+    def evaluate_metric_sums(self, input_ids, labels=None, noise=None, action_ids=None):
         """One batch of the metric loop (evaluate.py:167-179) as device-side sums, no logits materialised
         for the caller: returns float64 tensor [sum CE, n CE tokens, sum (gt == sample), n sampled tokens,
         n frames, n clips]."""
@@ -180,12 +186,13 @@ class GenieEvaluator:
         sums = torch.zeros(6, dtype=torch.float64, device=ids.device)
         stream = torch.cuda.current_stream().cuda_stream
         sizes = (float(B * (T - 1) * S), float(B * (T - 1)), float(B))
+        m._cond(action_ids, B)   # (argument errors before anything is enqueued)
         for k, t in enumerate(range(1, T)):
             p = ids.clone()
             p[:, t:] = m.mask_token_id
             s, fl = m.maskgit_generate(p, out_t=t, maskgit_steps=self.args.maskgit_steps,
                                        temperature=self.args.temperature,
-                                       noise=None if noise is None else noise[k], check=False)
+                                       noise=None if noise is None else noise[k], check=False, action_ids=action_ids)
             # fl is a permuted view of the contiguous (B, V, H, W) step-0 logits of frame t
             lg = fl.permute(0, 2, 1, 3, 4)
             assert lg.is_contiguous()
@@ -201,7 +208,7 @@ class GenieEvaluator:
 
 @torch.no_grad()
 def evaluate_clips(evaluator: GenieEvaluator, clips: torch.LongTensor, batch_size=16, noise_seed=None,
-                   distributed=False, reuse=True, clip_offset=0):
+                   distributed=False, reuse=True, clip_offset=0, action_ids=None):
     """Metric loop over ``clips`` (N, T*H*W) with the reference's AvgMetric weighting (eval_utils.py:16-25).
 
     With ``distributed=True`` every rank passes ITS shard of the clips; the six sums are all-reduced (SUM)
@@ -209,7 +216,8 @@ def evaluate_clips(evaluator: GenieEvaluator, clips: torch.LongTensor, batch_siz
     means, identical on every rank.  Returns dict(loss, acc, frames, clips, seconds, frames_per_sec).
     clip_offset: index of this shard's first clip in the whole job; the "random" unmasking draws of a batch are keyed by
     (noise_seed, global index of its first clip), so a job gives the same draws however it is sharded over ranks (given
-    shard boundaries that are multiples of batch_size)."""
+    shard boundaries that are multiples of batch_size).
+    action_ids: (N, T) per-frame actions of the clips (an action-conditioned model), sharded like them."""
     dev = evaluator.device
     total = torch.zeros(6, dtype=torch.float64, device=dev)
     torch.cuda.synchronize()
@@ -223,7 +231,7 @@ def evaluate_clips(evaluator: GenieEvaluator, clips: torch.LongTensor, batch_siz
             noise = torch.rand(m.config.T - 1, evaluator.args.maskgit_steps - 1, batch.shape[0], m.config.S,
                                generator=g).to(dev)
         fn = evaluator.evaluate_metric_sums_reuse if reuse else evaluator.evaluate_metric_sums
-        total += fn(batch, noise=noise)
+        total += fn(batch, noise=noise, action_ids=None if action_ids is None else action_ids[i:i + batch_size])
     torch.cuda.synchronize()
     seconds = time.perf_counter() - t0
     if distributed:

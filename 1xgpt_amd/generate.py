@@ -17,10 +17,11 @@ STRIDE = 15
 
 @torch.no_grad()
 def generate_frames(model, example_THW: torch.LongTensor, num_prompt_frames=8, maskgit_steps=2, temperature=0.0,
-                    teacher_force_time=False, noise=None):
+                    teacher_force_time=False, noise=None, action_ids=None):
     """example_THW (B, T, H, W) on the model's device -> outputs (B, T + (T - num_prompt_frames), H, W):
     [prompt frames | predicted frames | ground-truth frames] (generate.py:97-103).
-    noise: optional (T - num_prompt_frames, maskgit_steps-1, B, S)."""
+    noise: optional (T - num_prompt_frames, maskgit_steps-1, B, S).
+    action_ids: (B, T) per-frame actions of an action-conditioned model (config.action_vocab_size > 0)."""
     window_size = example_THW.shape[1]
     assert num_prompt_frames <= window_size
     example_THW = example_THW.to(torch.int64).contiguous()
@@ -33,7 +34,7 @@ def generate_frames(model, example_THW: torch.LongTensor, num_prompt_frames=8, m
             prompt_THW[:, timestep:] = model.mask_token_id
         samples_HW, _ = model.maskgit_generate(prompt_THW, out_t=timestep, maskgit_steps=maskgit_steps,
                                                temperature=temperature, noise=None if noise is None else noise[k],
-                                               return_logits=False)
+                                               return_logits=False, action_ids=action_ids)
         samples.append(samples_HW)
         if not teacher_force_time:
             prompt_THW[:, timestep] = samples_HW  # autoregressive (already written in place by maskgit_generate)
@@ -44,7 +45,8 @@ def generate_frames(model, example_THW: torch.LongTensor, num_prompt_frames=8, m
 
 @torch.no_grad()
 def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_frames=8, maskgit_steps=2, temperature=0.0,
-                           teacher_force_time=False, noise=None, unmask_mode="random", merge_commit=True, host_loop=False):
+                           teacher_force_time=False, noise=None, unmask_mode="random", merge_commit=True, host_loop=False,
+                           action_ids=None):
     """``generate_frames`` with a temporal KV cache (genie_frame_pass): every pass runs ONE frame through the stack
     against the cached temporal keys/values of the earlier frames instead of the full 16-frame forward --
     one P-frame pass for the prompt + (T-P)*(steps+1) single-frame passes (= 2 full-pass equivalents at P=8, steps=2) instead of (T-P)*steps full
@@ -52,7 +54,9 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
     merge_commit: where the library covers it (genie_frames_pass: f16x3, heads of 64 or 32, up to 16,384 rows per pass) the pass that commits frame t's
     final tokens also carries MaskGIT step 0 of frame t+1, so a frame costs `steps` passes instead of `steps + 1`.
     host_loop: False = the whole loop is ONE library call (genie_generate_cached: every pass, sampling and mask step enqueued
-    without a host step in between); True = the same loop driven from Python (one C-ABI call per pass / sample / mask step)."""
+    without a host step in between); True = the same loop driven from Python (one C-ABI call per pass / sample / mask step).
+    action_ids: (B, T) per-frame actions of an action-conditioned model (config.action_vocab_size > 0); every pass embeds
+    frame t with action_ids[:, t]."""
     import math
     from . import _lib
     lib = _lib.load()
@@ -64,6 +68,7 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
     assert P <= T and P >= 1
     dev = ex.device
     ids = ex.view(B, T, S)
+    cond = model._cond(action_ids, B, n_frames=T)
     ws = model._workspace(B, generate_prompt_frames=P)
     nbytes = lib.genie_prefix_cache_bytes(cfg, B)
     cache = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -79,7 +84,7 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
                   else noise.to(dev)[:, :steps - 1].reshape(T - P, steps - 1, B, S).float().contiguous())
         uni = torch.rand(T - P, steps, model.config.num_factored_vocabs, B, S, device=dev) if temperature > 1e-8 else None
         gen = torch.empty(B, T - P, S, dtype=torch.int64, device=dev)
-        _lib.check(lib.genie_generate_cached(cfg, w, ids.data_ptr(), B, P, T - P, steps, float(temperature),
+        _lib.check(_lib.call_cond(lib, "genie_generate_cached", cond, cfg, w, ids.data_ptr(), B, P, T - P, steps, float(temperature),
                                              _lib.UNMASK_GREEDY if unmask_mode == "greedy" else _lib.UNMASK_RANDOM,
                                              0 if nz is None else nz.data_ptr(), 0 if uni is None else uni.data_ptr(),
                                              int(bool(teacher_force_time)), int(bool(merge_commit)), gen.data_ptr(), 0, cache.data_ptr(),
@@ -88,8 +93,8 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
         return torch.cat([outputs, ex[:, P:]], dim=1)
 
     def frame_pass(tokens_BS, t, logits=None):
-        _lib.check(lib.genie_frame_pass(cfg, w, tokens_BS.data_ptr(), B, t, cache.data_ptr(), nbytes,
-                                        0 if logits is None else logits.data_ptr(), ws.data_ptr(), ws.numel(), st),
+        _lib.check(_lib.call_cond(lib, "genie_frame_pass", cond, cfg, w, tokens_BS.data_ptr(), B, t, cache.data_ptr(), nbytes,
+                                  0 if logits is None else logits.data_ptr(), ws.data_ptr(), ws.numel(), st),
                    "genie_frame_pass")
 
     def commit_and_open(final_BS, mask_BS, t, logits):
@@ -97,8 +102,8 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
         (genie_frames_pass): frame t + 1 attends the slot the same pass writes.  False = the library does not cover two
         frames per pass for this model / batch (nothing was enqueued): the caller runs the two passes one by one."""
         two = torch.stack([final_BS, mask_BS], dim=1).contiguous()
-        rc = lib.genie_frames_pass(cfg, w, two.data_ptr(), B, t, 2, cache.data_ptr(), nbytes, logits.data_ptr(), ws.data_ptr(),
-                                   ws.numel(), st)
+        rc = _lib.call_cond(lib, "genie_frames_pass", cond, cfg, w, two.data_ptr(), B, t, 2, cache.data_ptr(), nbytes,
+                            logits.data_ptr(), ws.data_ptr(), ws.numel(), st)
         if rc == _lib.E_UNSUPPORTED:
             return False
         _lib.check(rc, "genie_frames_pass")
@@ -109,11 +114,11 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
     # slots frame by frame
     rc = _lib.E_UNSUPPORTED
     if P > 1:
-        rc = lib.genie_frames_pass(cfg, w, ids[:, :P].contiguous().data_ptr(), B, 0, P, cache.data_ptr(), nbytes, 0, ws.data_ptr(),
-                                   ws.numel(), st)
+        rc = _lib.call_cond(lib, "genie_frames_pass", cond, cfg, w, ids[:, :P].contiguous().data_ptr(), B, 0, P, cache.data_ptr(),
+                            nbytes, 0, ws.data_ptr(), ws.numel(), st)
         if rc == _lib.E_UNSUPPORTED:
-            rc = lib.genie_clean_pass(cfg, w, ids[:, :P].contiguous().data_ptr(), B, P, T, cache.data_ptr(), nbytes, ws.data_ptr(),
-                                      ws.numel(), st)
+            rc = _lib.call_cond(lib, "genie_clean_pass", cond, cfg, w, ids[:, :P].contiguous().data_ptr(), B, P, T, cache.data_ptr(),
+                                nbytes, ws.data_ptr(), ws.numel(), st)
     if rc == _lib.E_UNSUPPORTED:
         for t in range(P):
             frame_pass(ids[:, t].contiguous(), t)

@@ -12,6 +12,9 @@ Differences that are deliberate and visible:
     ``torch.rand_like``, :206) and ``uniforms`` (for temperature > 0), so a test can replay an exact stream.
   * ``precision``: "exact" (f32 MFMA), "f16x3" (split-f16 operands on the f16 matrix cores, f32-class
     results: the parity-grade fast mode) or "bf16" (bf16 MFMA operands, f32 accumulate: throughput mode).
+  * per-frame action conditioning (not in the reference): with ``config.action_vocab_size = A > 0`` the model has an
+    ``action_embed`` table (A, d_model) and every entry point takes ``action_ids`` (B, T): row ``action_ids[b, t]`` is
+    added to every token of frame t of clip b, next to the positional embedding.
 """
 import json
 import math
@@ -173,6 +176,8 @@ class STMaskGIT(nn.Module):
         # nn.Linear holds the readout parameters for both the plain and the muP readout; the muP factor
         # output_mult/width_mult (reference :316-323) is applied inside the readout GEMM (cfg.readout_mult).
         self.out_x_proj = nn.Linear(config.d_model, config.factored_vocab_size * config.num_factored_vocabs)
+        if config.action_vocab_size:
+            self.action_embed = nn.Embedding(config.action_vocab_size, config.d_model)
         self.config = config
         self._table = None
         self._wide = []
@@ -256,6 +261,33 @@ class STMaskGIT(nn.Module):
     def _stream():
         return torch.cuda.current_stream().cuda_stream
 
+    def _cond(self, action_ids, B, n_frames=None):
+        """The genie_frame_cond of a call on B clips (None for an unconditioned model), checked on the host before anything
+        is enqueued.  action_ids: (B, T) integers in [0, A); (B, n_frames) with n_frames < T is padded to T (frames the
+        call never embeds)."""
+        A, T = self.config.action_vocab_size, self.config.T
+        if not A:
+            if action_ids is not None:
+                raise ValueError("action_ids given to a model without actions (config.action_vocab_size == 0)")
+            return None
+        if action_ids is None:
+            raise ValueError(f"this model is action-conditioned (action_vocab_size={A}): pass action_ids (B, T)")
+        a = torch.as_tensor(action_ids)
+        if a.dtype.is_floating_point or a.dtype == torch.bool:
+            raise RuntimeError(f"action_ids must be an integer tensor, got {a.dtype}")
+        n = T if n_frames is None else n_frames
+        if a.dim() != 2 or a.shape[0] != B or a.shape[1] not in (n, T):
+            raise RuntimeError(f"expected action_ids of shape ({B}, {T}), got {tuple(a.shape)}")
+        if a.numel() and (int(a.min()) < 0 or int(a.max()) >= A):
+            raise IndexError(f"action id out of range [0, {A}): min {int(a.min())}, max {int(a.max())}")
+        a = a.to(device=self._device(), dtype=torch.int64)
+        if a.shape[1] < T:
+            a = torch.cat([a, a.new_zeros(B, T - a.shape[1])], dim=1)
+        a = a.contiguous()
+        fc = _lib.FrameCond(table=self.action_embed.weight.data_ptr(), ids=a.data_ptr(), n_actions=A)
+        fc.keep = a   # the ids tensor lives as long as the struct
+        return fc
+
     def _ids(self, t, whole_clips=False):
         if not t.is_cuda:
             raise RuntimeError("1xgpt_amd runs on the GPU only (no CPU fallback): move inputs to cuda")
@@ -267,24 +299,26 @@ class STMaskGIT(nn.Module):
         return t.to(torch.int64).contiguous()
 
     # ------------------------------------------------------------------ forward pieces
-    def hidden_states(self, x_THW: torch.LongTensor):
+    def hidden_states(self, x_THW: torch.LongTensor, action_ids=None):
         """Run embed + decoder; the (B,T,S,d) result stays at offset 0 of the workspace (returned as a view)."""
         lib = _lib.load()
         cfg, w = self._weights()[:2]
         ids = self._ids(x_THW, whole_clips=True)
         B = ids.shape[0]
+        cond = self._cond(action_ids, B)
         ws = self._workspace(B)
-        _lib.check(lib.genie_compute_logits(cfg, w, ids.data_ptr(), B, 0, 0, 0, ws.data_ptr(), ws.data_ptr(),
-                                            ws.numel(), self._stream()), "genie_compute_logits(hidden)")
+        _lib.check(_lib.call_cond(lib, "genie_compute_logits", cond, cfg, w, ids.data_ptr(), B, 0, 0, 0, ws.data_ptr(),
+                                  ws.data_ptr(), ws.numel(), self._stream()), "genie_compute_logits(hidden)")
         n = B * self.config.T * self.config.S * self.config.d_model
         return ws[: n * 4].view(torch.float32).view(B, self.config.T, self.config.S, self.config.d_model)
 
-    def compute_logits_frames(self, x_THW, t0, t1, layout="bcthw"):
+    def compute_logits_frames(self, x_THW, t0, t1, layout="bcthw", action_ids=None):
         """Logits of frames [t0,t1): (B, V, t1-t0, H, W) for layout='bcthw', (B, t1-t0, S, V) for 'token'."""
         lib = _lib.load()
         cfg, w = self._weights()[:2]
         ids = self._ids(x_THW, whole_clips=True)
         B = ids.shape[0]
+        cond = self._cond(action_ids, B)
         ws = self._workspace(B)
         nt, V = t1 - t0, self.config.factored_vocab_size * self.config.num_factored_vocabs
         if layout == "bcthw":
@@ -293,15 +327,15 @@ class STMaskGIT(nn.Module):
         else:
             out = torch.empty(B, nt, self.config.S, V, dtype=torch.float32, device=ids.device)
             lay = _lib.LAYOUT_TOKEN_MAJOR
-        _lib.check(lib.genie_compute_logits(cfg, w, ids.data_ptr(), B, t0, t1, lay, out.data_ptr(), ws.data_ptr(),
-                                            ws.numel(), self._stream()), "genie_compute_logits")
+        _lib.check(_lib.call_cond(lib, "genie_compute_logits", cond, cfg, w, ids.data_ptr(), B, t0, t1, lay, out.data_ptr(),
+                                  ws.data_ptr(), ws.numel(), self._stream()), "genie_compute_logits")
         return out
 
-    def compute_logits(self, x_THW):
+    def compute_logits(self, x_THW, action_ids=None):
         """ids (B,T,H,W) -> logits (B, V, T, H, W), channels [vocab0(512) | vocab1(512)]  (reference :255-265)."""
-        return self.compute_logits_frames(x_THW, 0, self.config.T, "bcthw")
+        return self.compute_logits_frames(x_THW, 0, self.config.T, "bcthw", action_ids=action_ids)
 
-    def ce_sums(self, x_THW, labels_THW, t0=1, t1=None, masked_only=True):
+    def ce_sums(self, x_THW, labels_THW, t0=1, t1=None, masked_only=True, action_ids=None):
         """Fused forward + readout + factored CE: returns a (3,) float64 device tensor
         [sum CE, sum all-factors-correct, n counted] over frames [t0,t1); no logits leave the workspace."""
         lib = _lib.load()
@@ -309,8 +343,9 @@ class STMaskGIT(nn.Module):
         ids, lab = self._ids(x_THW, whole_clips=True), self._ids(labels_THW, whole_clips=True)
         B = ids.shape[0]
         t1 = self.config.T if t1 is None else t1
+        self._cond(action_ids, B)   # (argument errors before anything is enqueued)
         ws = self._workspace(B)
-        self.hidden_states(ids)
+        self.hidden_states(ids, action_ids=action_ids)
         sums = torch.zeros(3, dtype=torch.float64, device=ids.device)
         _lib.check(lib.genie_readout_ce(cfg, w, ws.data_ptr(), lab.data_ptr(), ids.data_ptr() if masked_only else 0,
                                         B, t0, t1, sums.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
@@ -331,14 +366,15 @@ class STMaskGIT(nn.Module):
                                          sums.data_ptr(), self._stream()), "genie_factored_ce")
         return (sums[0] / sums[2]).float(), (sums[1] / sums[2]).float()  # 0/0 -> nan like the reference
 
-    def forward(self, input_ids, labels):
+    def forward(self, input_ids, labels, action_ids=None):
         """(B, T*H*W) ids + labels -> GenieOutput(loss, acc, logits (B,V,T,H,W))  (reference :267-279)."""
         T, H, W = self.config.T, self.h, self.w
         x_THW = self._ids(input_ids).view(-1, T, H, W)
         lab = self._ids(labels).view(-1, T, H, W)
         if lab.shape != x_THW.shape:
             raise RuntimeError(f"labels {tuple(labels.shape)} do not match input_ids {tuple(input_ids.shape)}")
-        logits = self.compute_logits(x_THW)  # leaves the hidden state in the workspace
+        self._cond(action_ids, x_THW.shape[0])
+        logits = self.compute_logits(x_THW, action_ids=action_ids)  # leaves the hidden state in the workspace
         lib = _lib.load()
         cfg, w = self._weights()[:2]
         B = x_THW.shape[0]
@@ -358,13 +394,14 @@ class STMaskGIT(nn.Module):
 
     @torch.no_grad()
     def maskgit_generate(self, prompt_THW, out_t, maskgit_steps=1, temperature=0.0, unmask_mode="random",
-                         noise=None, uniforms=None, return_logits=True, check=True):
+                         noise=None, uniforms=None, return_logits=True, check=True, action_ids=None):
         """MaskGIT decode of frame ``out_t`` (reference :123-229): the whole loop runs on the device.
 
         Mutates ``prompt_THW[:, out_t]`` in place (reference :223) and returns
         ``(samples (B,H,W) int64, step-0 factored logits (B, 512, 2, H, W))``.
         noise: optional (maskgit_steps-1, B, S) float32 draws for "random" unmasking (default: torch.rand).
         uniforms: (maskgit_steps, num_factored_vocabs, B, S) for temperature > 1e-8 (default: torch.rand).
+        action_ids: (B, T) actions of an action-conditioned model (config.action_vocab_size > 0), else None.
         """
         if unmask_mode not in ("greedy", "random"):
             raise NotImplementedError(f"Expected `unmask_mode` to be one of ['greedy', 'random'], got {unmask_mode}")
@@ -382,6 +419,7 @@ class STMaskGIT(nn.Module):
             raise RuntimeError(f"maskgit_generate expects a (B, T={self.config.T}, H, W) prompt, got {tuple(prompt_THW.shape)}")
         S, V = self.config.S, self.config.factored_vocab_size * self.config.num_factored_vocabs
         dev = prompt.device
+        cond = self._cond(action_ids, B)
         ws = self._workspace(B)
         if unmask_mode == "random" and maskgit_steps > 1:
             if noise is None:
@@ -399,8 +437,8 @@ class STMaskGIT(nn.Module):
         samples = torch.empty(B, self.h, self.w, dtype=torch.int64, device=dev)
         logits0 = torch.empty(B, V, self.h, self.w, dtype=torch.float32, device=dev) if return_logits else None
         status = torch.zeros(1, dtype=torch.int32, device=dev) if check else None
-        rc = lib.genie_maskgit_generate(
-            cfg, w, prompt.data_ptr(), B, int(out_t), int(maskgit_steps), float(temperature),
+        rc = _lib.call_cond(
+            lib, "genie_maskgit_generate", cond, cfg, w, prompt.data_ptr(), B, int(out_t), int(maskgit_steps), float(temperature),
             _lib.UNMASK_GREEDY if unmask_mode == "greedy" else _lib.UNMASK_RANDOM,
             0 if noise is None else noise.data_ptr(), 0 if uniforms is None else uniforms.data_ptr(),
             samples.data_ptr(), 0 if logits0 is None else logits0.data_ptr(), _lib.LAYOUT_BCTHW,
@@ -417,7 +455,7 @@ class STMaskGIT(nn.Module):
         return samples, logits0.view(B, nv, vf, self.h, self.w).permute(0, 2, 1, 3, 4)
 
     def generate(self, input_ids, attention_mask=None, max_new_tokens=None, min_new_tokens=None, return_logits=False,
-                 maskgit_steps=1, temperature=0.0, noise=None, kv_cache=True):
+                 maskgit_steps=1, temperature=0.0, noise=None, kv_cache=True, action_ids=None):
         """Autoregressive frame generation behind the reference's Llama-style signature (st_mask_git.py:65-113):
         ``input_ids`` (B, n_prompt_frames * S) holds the prompt frames; ``max_new_tokens // S`` further frames are decoded one
         after the other with ``maskgit_generate``, each seeing every frame before it.  Returns the (B, (n_prompt + n_new) * S)
@@ -425,7 +463,8 @@ class STMaskGIT(nn.Module):
         ``attention_mask`` is accepted and ignored, as in the reference.  ``min_new_tokens`` may only repeat ``max_new_tokens``.
         noise: optional (n_new_frames, maskgit_steps - 1, B, S) unmasking draws to replay (the reference draws them itself).
         kv_cache: True (default) = the frames are decoded by one-frame passes against a temporal KV cache; False = the reference's
-        own schedule, a full forward over the canvas per MaskGIT step (same frames up to f32 accumulation order)."""
+        own schedule, a full forward over the canvas per MaskGIT step (same frames up to f32 accumulation order).
+        action_ids: (B, T) -- or (B, n_prompt + n_new), padded to T -- actions of an action-conditioned model."""
         S = self.config.S
         if min_new_tokens is not None and min_new_tokens != max_new_tokens:
             raise AssertionError("Expecting `min_new_tokens`, if specified, to match `max_new_tokens`.")
@@ -434,6 +473,7 @@ class STMaskGIT(nn.Module):
         ids = self._ids(input_ids)
         B, n_new = ids.size(0), max_new_tokens // S
         n_prompt = ids.numel() // (B * S)
+        cond = self._cond(action_ids, B, n_frames=n_prompt + n_new)
         if kv_cache and n_new >= 1 and n_prompt >= 1 and n_prompt + n_new <= self.config.T:
             # the same frames on the temporal KV cache, the whole loop one library call (genie_generate_cached): every MaskGIT step
             # runs the rows of the frame being decoded instead of a full forward over the canvas (causal in time: the all-MASK
@@ -455,10 +495,11 @@ class STMaskGIT(nn.Module):
             nbytes = lib.genie_prefix_cache_bytes(cfg, B)
             cache = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             ws = self._workspace(B, generate_prompt_frames=n_prompt)
-            _lib.check(lib.genie_generate_cached(cfg, w, clip.data_ptr(), B, n_prompt, n_new, steps, float(temperature), _lib.UNMASK_RANDOM,
-                                                 0 if nz is None else nz.data_ptr(), 0 if uni is None else uni.data_ptr(), 0, 1,
-                                                 gen.data_ptr(), 0 if lg0 is None else lg0.data_ptr(), cache.data_ptr(), nbytes,
-                                                 ws.data_ptr(), ws.numel(), self._stream()), "genie_generate_cached")
+            _lib.check(_lib.call_cond(lib, "genie_generate_cached", cond, cfg, w, clip.data_ptr(), B, n_prompt, n_new, steps,
+                                      float(temperature), _lib.UNMASK_RANDOM,
+                                      0 if nz is None else nz.data_ptr(), 0 if uni is None else uni.data_ptr(), 0, 1,
+                                      gen.data_ptr(), 0 if lg0 is None else lg0.data_ptr(), cache.data_ptr(), nbytes,
+                                      ws.data_ptr(), ws.numel(), self._stream()), "genie_generate_cached")
             tokens = torch.cat([ids.view(B, n_prompt * S), gen.view(B, n_new * S)], dim=1)
             if not return_logits:
                 return tokens
@@ -472,7 +513,8 @@ class STMaskGIT(nn.Module):
         step0_logits = []
         for k in range(n_new):
             frame, logits = self.maskgit_generate(canvas, n_prompt + k, maskgit_steps=maskgit_steps, temperature=temperature,
-                                                  noise=None if noise is None else noise[k], return_logits=return_logits)
+                                                  noise=None if noise is None else noise[k], return_logits=return_logits,
+                                                  action_ids=None if cond is None else cond.keep)
             canvas[:, n_prompt + k] = frame
             step0_logits.append(logits)
         tokens = canvas.view(B, -1)
@@ -499,17 +541,19 @@ class STMaskGIT(nn.Module):
 
     def save_pretrained(self, save_directory):
         """config.json (flat GenieConfig dict) + model.safetensors, the layout the reference's
-        PyTorchModelHubMixin writes."""
+        PyTorchModelHubMixin writes.  An unconditioned model's config.json has no action key."""
         from safetensors.torch import save_file
         os.makedirs(save_directory, exist_ok=True)
         with open(os.path.join(save_directory, "config.json"), "w") as f:
-            json.dump(vars(self.config), f)
+            json.dump(self.config.to_json_dict(), f)
         save_file({k: v.detach().cpu().contiguous() for k, v in self.state_dict().items()},
                   os.path.join(save_directory, "model.safetensors"))
 
     @classmethod
-    def from_pretrained(cls, pretrained_model_name_or_path, precision="exact", **kwargs):
-        """Load a local HF-style checkpoint directory (hub ids need a network and are not supported offline)."""
+    def from_pretrained(cls, pretrained_model_name_or_path, precision="exact", action_vocab_size=None, **kwargs):
+        """Load a local HF-style checkpoint directory (hub ids need a network and are not supported offline).
+        action_vocab_size=A > 0 on an unconditioned checkpoint: a warm start -- every stored tensor loads strictly and the new
+        action table is zero, so the model computes exactly what the checkpoint does until the table is trained."""
         from safetensors.torch import load_file
         d = str(pretrained_model_name_or_path)
         if not os.path.isdir(d):
@@ -525,8 +569,18 @@ class STMaskGIT(nn.Module):
             warnings.warn("use_mup=True: the readout factor follows mup's documented formula output_mult * x / width_mult "
                           "(base width 256); the reference's own mup fork is not vendored, so this factor is not pinned "
                           "against reference outputs (DESIGN.md section 7, 'parity unpinned')")
+        sd = load_file(os.path.join(d, "model.safetensors"))
+        warm = False
+        if action_vocab_size is not None and action_vocab_size != config.action_vocab_size:
+            if config.action_vocab_size:
+                raise ValueError(f"checkpoint has action_vocab_size={config.action_vocab_size}, asked for {action_vocab_size}")
+            config.action_vocab_size = int(action_vocab_size)
+            warm = config.action_vocab_size > 0
         model = cls(config, precision=precision)
-        model.load_state_dict(load_file(os.path.join(d, "model.safetensors")), strict=True)
+        if warm:
+            sd = dict(sd)
+            sd["action_embed.weight"] = torch.zeros(config.action_vocab_size, config.d_model)
+        model.load_state_dict(sd, strict=True)
         model.eval()
         return model
 

@@ -53,6 +53,8 @@ def state_dict_spec(cfg: GenieConfig):
         spec.append((f"token_embed.factored_embeds.{j}.weight", (cfg.factored_vocab_size, d), "emb", 1))
     spec.append(("out_x_proj.weight", (V, d), "readout", d))
     spec.append(("out_x_proj.bias", (V,), "bias", 1))
+    if cfg.action_vocab_size:
+        spec.append(("action_embed.weight", (cfg.action_vocab_size, d), "emb", 1))
     return spec
 
 

@@ -98,12 +98,17 @@ def weights_table(config, tensors, w16=None):
     return w, layers
 
 
+def _embedding_side(name):
+    return name.startswith("token_embed.") or name in ("pos_embed_TSC", "action_embed.weight")
+
+
 def ready_order(config, names):
     """Parameter names in the order their gradients are final during the backward: readout, layers L-1..0 (within a
-    layer: decaying tensors first, so each layer is two AdamW ranges), then the embedding side."""
+    layer: decaying tensors first, so each layer is two AdamW ranges), then the embedding side (with the action table of an
+    action-conditioned model last)."""
     names = list(names)
     head = [n for n in names if n.startswith("out_x_proj.")]
-    emb = [n for n in names if n.startswith("token_embed.") or n == "pos_embed_TSC"]
+    emb = [n for n in names if _embedding_side(n)]
     out = sorted(head, key=lambda n: not decays(n))
     for i in reversed(range(config.num_layers)):
         p = f"decoder.layers.{i}."
@@ -231,7 +236,7 @@ class GenieTrainer:
         segs, L = [], self.config.num_layers
         groups = [[n for n in self.order if n.startswith("out_x_proj.")]]
         groups += [[n for n in self.order if n.startswith(f"decoder.layers.{i}.")] for i in reversed(range(L))]
-        groups += [[n for n in self.order if n.startswith("token_embed.") or n == "pos_embed_TSC"]]
+        groups += [[n for n in self.order if _embedding_side(n)]]
         for gnames in groups:
             lo = offs[gnames[0]][0]
             hi = offs[gnames[-1]][0] + (named[gnames[-1]].numel() + 63) // 64 * 64
@@ -276,20 +281,22 @@ class GenieTrainer:
         return torch.cuda.current_stream().cuda_stream
 
     # ------------------------------------------------------------------ forward / backward (train.py:611-617)
-    def forward_backward(self, input_ids, labels, accumulate=False, reduce=True):
+    def forward_backward(self, input_ids, labels, accumulate=False, reduce=True, action_ids=None):
         """One micro-batch: loss/acc of STMaskGIT.forward and gradients into the flat buffer (added when
-        `accumulate`).  Returns (loss, acc) as 0-dim float64 CUDA tensors (no host sync)."""
+        `accumulate`).  Returns (loss, acc) as 0-dim float64 CUDA tensors (no host sync).
+        action_ids: (B, T) per-frame actions of an action-conditioned model (config.action_vocab_size > 0)."""
         if not (input_ids.is_cuda and labels.is_cuda):
             raise RuntimeError("1xgpt_amd runs on the GPU only (no CPU fallback): move the batch to cuda")
         ids = input_ids.to(torch.int64).contiguous()
         lab = labels.to(torch.int64).contiguous()
         B = ids.shape[0]
         assert ids.shape == lab.shape == (B, self.config.T * self.config.S), ids.shape
+        cond = self.model._cond(action_ids, B)
         acts, ws = self._buffers(B)
         lib, cfg, st = self.lib, self.cfg, self._stream()
         acc_flag = 1 if accumulate else 0
-        _lib.check(lib.genie_train_forward(cfg, self.w_table, ids.data_ptr(), lab.data_ptr(), B, acts.data_ptr(),
-                                           acts.numel(), self.sums.data_ptr(), st), "genie_train_forward")
+        _lib.check(_lib.call_cond(lib, "genie_train_forward", cond, cfg, self.w_table, ids.data_ptr(), lab.data_ptr(), B,
+                                  acts.data_ptr(), acts.numel(), self.sums.data_ptr(), st), "genie_train_forward")
         sums = self.sums.clone()
         self.reducer.reset()
         _lib.check(lib.genie_train_backward_head(cfg, self.w_table, self.wT_table, self.g_table, B, acts.data_ptr(),
@@ -303,8 +310,13 @@ class GenieTrainer:
                        "genie_train_backward_layer")
             if reduce:
                 self.reducer.ready(self.segments[1 + k][1])
-        _lib.check(lib.genie_train_backward_embed(cfg, self.g_table, ids.data_ptr(), B, ws.data_ptr(), ws.numel(),
-                                                  acc_flag, st), "genie_train_backward_embed")
+        if cond is None:
+            _lib.check(lib.genie_train_backward_embed(cfg, self.g_table, ids.data_ptr(), B, ws.data_ptr(), ws.numel(),
+                                                      acc_flag, st), "genie_train_backward_embed")
+        else:
+            _lib.check(lib.genie_train_backward_embed_cond(cfg, self.g_table, ids.data_ptr(), B, ws.data_ptr(), ws.numel(),
+                                                           acc_flag, st, self.g_views["action_embed.weight"].data_ptr(), cond),
+                       "genie_train_backward_embed_cond")
         if reduce:
             self.reducer.finish()
         return sums[0] / sums[2], sums[1] / sums[2]
@@ -344,7 +356,7 @@ class GenieTrainer:
         `gradient_accumulation_steps` calls.  Returns device scalars (no host sync)."""
         is_update = (self._micro + 1) % self.accum == 0
         loss, acc = self.forward_backward(batch["input_ids"], batch["labels"], accumulate=self._micro % self.accum != 0,
-                                          reduce=is_update and self.accum == 1)
+                                          reduce=is_update and self.accum == 1, action_ids=batch.get("action_ids"))
         self._micro += 1
         out = {"loss": loss, "acc": acc}
         if is_update:

@@ -119,6 +119,20 @@ typedef struct genie_weights {
     const uint16_t* out_frame_w16; /* GENIE_PREC_F16X3 (ABI 3): out_w in fragment order (genie_pack_frame_w16), or NULL */
 } genie_weights;
 
+/* Per-frame action conditioning (ABI 3 addition; the structs above are unchanged).  The model has a learned table of
+ * n_actions rows of d_model; row ids[b, t] is added to every token of frame t of clip b, masked tokens included, where the
+ * positional embedding is added:  x[b,t,s] = token_embed(id) + (pos_embed[t,s] + table[ids[b,t]])  -- position row plus
+ * action row first, so one clip with actions is bit-identical to an unconditioned model whose positional table is
+ * pos + table[a_t].  The *_cond entry points below take this as a trailing argument; NULL (or n_actions == 0) is exactly the
+ * unconditioned entry point.  `ids` always addresses ABSOLUTE clip frames with a clip stride of cfg->T, also in the
+ * window passes (genie_frames_pass at t0, genie_masked_frames_logits at frame0, ...): frame i of such a pass reads
+ * ids[b * cfg->T + t0 + i].  An id outside [0, n_actions) adds zero (callers should reject it: nn.Embedding raises). */
+typedef struct genie_frame_cond {
+    const float* table;   /* (n_actions, d_model) f32, device */
+    const int64_t* ids;   /* (B, T) device: action of clip b at ABSOLUTE frame t (clip stride = cfg->T) */
+    int32_t n_actions;
+} genie_frame_cond;
+
 int genie_version(void);
 /* The compiler's view of the POD structs above, for bindings to check their own declarations against (tests/test_abi_and_host.py):
  * out[0..8) = sizeof(genie_cfg), sizeof(genie_attn_weights), offsetof(.., fused_w16), offsetof(.., w16_wide),
@@ -210,6 +224,8 @@ int genie_pack_spatial_qkv_fused_bf16(const float* qkv_w, uint16_t* dst, void* s
 /* FactorizedEmbedding.forward + pos-embed add (factorization_utils.py:29-52, st_mask_git.py:257-261).
  * ids (B,T,S) int64 -> x (B,T,S,d). */
 int genie_embed(const genie_cfg* cfg, const genie_weights* w, const int64_t* ids, int B, float* x, void* stream);
+int genie_embed_cond(const genie_cfg* cfg, const genie_weights* w, const int64_t* ids, int B, float* x, void* stream,
+                     const genie_frame_cond* cond);
 
 /* nn.LayerNorm(C, eps) over the last dim of (rows, C) (st_transformer.py:44,67). */
 int genie_layer_norm(const float* x, const float* gamma, const float* beta, float* y, int rows, int C, float eps,
@@ -257,6 +273,9 @@ int genie_readout_logits(const genie_cfg* cfg, const genie_weights* w, const flo
 /* STMaskGIT.compute_logits (st_mask_git.py:255-265): ids (B,T,S) -> logits of frames [t0,t1). */
 int genie_compute_logits(const genie_cfg* cfg, const genie_weights* w, const int64_t* ids, int B, int t0, int t1,
                          int layout, float* logits, void* workspace, size_t workspace_bytes, void* stream);
+int genie_compute_logits_cond(const genie_cfg* cfg, const genie_weights* w, const int64_t* ids, int B, int t0, int t1,
+                              int layout, float* logits, void* workspace, size_t workspace_bytes, void* stream,
+                              const genie_frame_cond* cond);
 
 /* ---- teacher-forced prefix reuse (evaluate.py:107-116 recomputes frames < t in every timeline) -----------------
  * Temporal attention is causal and every other op is per-frame, so in the evaluator's timeline t the activations of
@@ -288,9 +307,15 @@ int genie_compute_logits(const genie_cfg* cfg, const genie_weights* w, const int
 size_t genie_prefix_cache_bytes(const genie_cfg* cfg, int B);
 int genie_clean_pass(const genie_cfg* cfg, const genie_weights* w, const int64_t* ids, int B, int nframes, int cache_frames,
                      float* cache, size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int genie_clean_pass_cond(const genie_cfg* cfg, const genie_weights* w, const int64_t* ids, int B, int nframes,
+                          int cache_frames, float* cache, size_t cache_bytes, void* workspace, size_t workspace_bytes,
+                          void* stream, const genie_frame_cond* cond);
 int genie_masked_frames_logits(const genie_cfg* cfg, const genie_weights* w, const int64_t* frames, int B, int frame0,
                                int nframes, const float* cache, size_t cache_bytes, float* logits, void* workspace,
                                size_t workspace_bytes, void* stream);
+int genie_masked_frames_logits_cond(const genie_cfg* cfg, const genie_weights* w, const int64_t* frames, int B,
+                                    int frame0, int nframes, const float* cache, size_t cache_bytes, float* logits,
+                                    void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond);
 
 /* Temporal KV cache for autoregressive generation (generate.py:81-95 re-runs the full 16-frame forward for every
  * MaskGIT step of every new frame): run ONE frame (frame_ids (B,S), frame index t) through the stack; each layer writes
@@ -300,6 +325,9 @@ int genie_masked_frames_logits(const genie_cfg* cfg, const genie_weights* w, con
  * to commit them.  Same per-row arithmetic as the full forward restricted to frame t. */
 int genie_frame_pass(const genie_cfg* cfg, const genie_weights* w, const int64_t* frame_ids, int B, int t, float* cache,
                      size_t cache_bytes, float* logits, void* workspace, size_t workspace_bytes, void* stream);
+int genie_frame_pass_cond(const genie_cfg* cfg, const genie_weights* w, const int64_t* frame_ids, int B, int t,
+                          float* cache, size_t cache_bytes, float* logits, void* workspace, size_t workspace_bytes,
+                          void* stream, const genie_frame_cond* cond);
 /* The same for nf CONSECUTIVE frames t0 .. t0 + nf - 1 in one pass (ABI 3): frame_ids (B, nf, S); every layer writes the nf
  * cache slots and frame t0 + i attends slots 0 .. t0 + i (those of this pass included); `logits` (B, S, V) token-major are those
  * of the LAST frame of the pass (NULL = not wanted).  generate()'s use: the pass that commits the final tokens of frame t also
@@ -310,6 +338,9 @@ int genie_frame_pass(const genie_cfg* cfg, const genie_weights* w, const int64_t
  * runs the frames one by one. */
 int genie_frames_pass(const genie_cfg* cfg, const genie_weights* w, const int64_t* frame_ids, int B, int t0, int nf, float* cache,
                       size_t cache_bytes, float* logits, void* workspace, size_t workspace_bytes, void* stream);
+int genie_frames_pass_cond(const genie_cfg* cfg, const genie_weights* w, const int64_t* frame_ids, int B, int t0, int nf,
+                           float* cache, size_t cache_bytes, float* logits, void* workspace, size_t workspace_bytes,
+                           void* stream, const genie_frame_cond* cond);
 /* generate.py:77-103 / STMaskGIT.generate (st_mask_git.py:65-113) on the temporal KV cache, the WHOLE loop enqueued by one call (no
  * host synchronisation, no host work between passes): ids (B, P + n_new, S) = the clip (frames [0, P) are the prompt; frames >= P are
  * read only when teacher_force_time); gen_out (B, n_new, S) receives the generated frames; logits0_out (B, n_new, S, V) f32
@@ -326,6 +357,11 @@ int genie_generate_cached(const genie_cfg* cfg, const genie_weights* w, const in
                           float temperature, int unmask_mode, const float* noise, const float* uniforms, int teacher_force_time,
                           int merge_commit, int64_t* gen_out, float* logits0_out, float* cache, size_t cache_bytes, void* workspace,
                           size_t workspace_bytes, void* stream);
+int genie_generate_cached_cond(const genie_cfg* cfg, const genie_weights* w, const int64_t* ids, int B, int P, int n_new,
+                               int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                               int teacher_force_time, int merge_commit, int64_t* gen_out, float* logits0_out, float* cache,
+                               size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
+                               const genie_frame_cond* cond);
 /* f32 (N, K) row-major weight -> split f16 in FRAGMENT ORDER (2 N K 16-bit values) for the one-frame kernels
  * (csrc/kernels_frame.hip): blocks of 32 rows x 64 k, per block [plane hi | lo'][MFMA step 0..3] fragments of 1 KB = the 64 lanes'
  * 16-byte operand pieces (lane 32 h + r: row r, k = 16 step + 8 h .. + 7), so that every operand load of those kernels is a
@@ -388,6 +424,10 @@ int genie_maskgit_generate(const genie_cfg* cfg, const genie_weights* w, int64_t
                            float temperature, int unmask_mode, const float* noise, const float* uniforms,
                            int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
                            void* workspace, size_t workspace_bytes, void* stream);
+int genie_maskgit_generate_cond(const genie_cfg* cfg, const genie_weights* w, int64_t* prompt, int B, int out_t, int steps,
+                                float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                                int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
+                                void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond);
 
 /* ---- optional per-launch timing (bench.py's roofline leg) ------------------------------------------------
  * When enabled, every launch of a kernel whose class bit is set in `class_mask` is bracketed by a pair of
@@ -498,6 +538,9 @@ size_t genie_train_workspace_bytes(const genie_cfg* cfg, int B);
  * On return the logits slot of `acts` holds d loss / d logits. */
 int genie_train_forward(const genie_cfg* cfg, const genie_weights* w, const int64_t* input_ids, const int64_t* labels,
                         int B, float* acts, size_t acts_bytes, double* sums_out, void* stream);
+int genie_train_forward_cond(const genie_cfg* cfg, const genie_weights* w, const int64_t* input_ids, const int64_t* labels,
+                             int B, float* acts, size_t acts_bytes, double* sums_out, void* stream,
+                             const genie_frame_cond* cond);
 
 /* 16-bit precisions only: refresh the 16-bit copies of every Linear weight from the f32 parameters in `w`:
  * row-major (out, in) into the *_w16 members of `w16` (read by the forward) and transposed (in, out) into the *_w16
@@ -518,6 +561,12 @@ int genie_train_backward_layer(const genie_cfg* cfg, const genie_weights* w, con
                                size_t workspace_bytes, int accumulate, void* stream);
 int genie_train_backward_embed(const genie_cfg* cfg, const genie_weights* grads, const int64_t* input_ids, int B,
                                void* workspace, size_t workspace_bytes, int accumulate, void* stream);
+/* ... and, with actions, the gradient of the action table into d_table (n_actions, d_model): the sum over the frames whose
+ * action is k of their tokens' d loss / d x, in a fixed order (no atomics); rows of unused actions are 0 (or kept with
+ * `accumulate`).  Its scratch is a region of the training workspace that is dead by then (same workspace size). */
+int genie_train_backward_embed_cond(const genie_cfg* cfg, const genie_weights* grads, const int64_t* input_ids, int B,
+                                    void* workspace, size_t workspace_bytes, int accumulate, void* stream,
+                                    float* d_table, const genie_frame_cond* cond);
 
 /* *out += sum x[i]^2 in f64, two-stage with a fixed order (scratch: 1024 doubles).  The global gradient norm of
  * clip_grad_norm_ (train.py:628-629) is sqrt of this summed over all gradient buffers. */

@@ -5,7 +5,8 @@
   python tools/evaluate.py --synthetic 32 --model c138            # no checkpoint / dataset offline: synthetic weights + clips
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/evaluate.py ...   # data-parallel
 
-Prints the running means like the reference ({gen_time, loss, acc}); LPIPS is out of scope (needs the `lpips` AlexNet)."""
+Prints the running means like the reference ({gen_time, loss, acc}); LPIPS is out of scope (needs the `lpips` AlexNet).
+An action-conditioned checkpoint (action_vocab_size > 0) is evaluated with the dataset's actions.bin (refused without one)."""
 import argparse
 import importlib
 import json
@@ -40,6 +41,7 @@ def main():
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
 
+    actions = None
     if args.synthetic:
         cfg = cfgmod.c138() if args.model == "c138" else cfgmod.c35()
         model = STMaskGIT(cfg, precision=args.precision).load_numpy_state_dict(synth.make_state_dict(cfg, seed=0))
@@ -52,11 +54,15 @@ def main():
         n = len(ds) if args.max_examples is None else min(len(ds), args.max_examples)
         clips = ds.batch(range(n))
         side = ds.metadata["s"]
+        if model.config.action_vocab_size:
+            if ds.actions is None:
+                sys.exit(f"evaluate.py: the model is action-conditioned but {args.val_data_dir} has no actions.bin")
+            actions = ds.action_batch(range(n))
     args.latent_h = args.latent_w = side
     lo, hi = dist_mod.shard_range(clips.shape[0], rank, world)
     ev = ev_mod.GenieEvaluator(args, None, dev, model=model)
     res = ev_mod.evaluate_clips(ev, clips[lo:hi], batch_size=args.batch_size, distributed=world > 1,
-                                reuse=not args.no_reuse)
+                                reuse=not args.no_reuse, action_ids=None if actions is None else actions[lo:hi])
     if rank == 0:
         res["gen_time_s_per_frame"] = res["seconds"] / max(res["frames"], 1)
         print(json.dumps(res))

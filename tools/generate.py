@@ -3,7 +3,9 @@
 written as [prompt | generated | ground truth] video.bin + metadata.json (readable by RawTokenDataset / visualize).
 
   python tools/generate.py --checkpoint_dir DIR --val_data_dir data/val_v1.1 --output_dir data/genie_generated
-  python tools/generate.py --synthetic --model c35 --output_dir /tmp/gen"""
+  python tools/generate.py --synthetic --model c35 --output_dir /tmp/gen
+An action-conditioned checkpoint (action_vocab_size > 0) generates with the example's actions from the dataset's actions.bin
+(refused without one)."""
 import argparse
 import importlib
 import os
@@ -32,6 +34,7 @@ def main():
                     help="kv_cache: one-frame passes against a temporal KV cache (same frames up to f32 accumulation order); "
                          "full_forward: the reference's schedule, a full 16-frame forward per MaskGIT step (generate.py:81-95)")
     args = ap.parse_args()
+    actions = None
     G = importlib.import_module("1xgpt_amd.generate")
     STMaskGIT = importlib.import_module("1xgpt_amd.st_mask_git").STMaskGIT
     if args.synthetic:
@@ -45,12 +48,18 @@ def main():
         model = STMaskGIT.from_pretrained(args.checkpoint_dir, precision=args.precision)
         ds = importlib.import_module("1xgpt_amd.data").RawTokenDataset(args.val_data_dir, window_size=args.window_size,
                                                                       stride=G.STRIDE)
-        example = ds[args.example_ind]["input_ids"][None]
+        item = ds[args.example_ind]
+        example = item["input_ids"][None]
         meta = ds.metadata
+        if model.config.action_vocab_size:
+            if "action_ids" not in item:
+                sys.exit(f"generate.py: the model is action-conditioned but {args.val_data_dir} has no actions.bin")
+            actions = item["action_ids"][None]
     model = model.to("cuda")
     ex = example.to("cuda").view(1, args.window_size, model.h, model.w)
     fn = G.generate_frames_cached if args.schedule == "kv_cache" else G.generate_frames
-    out = fn(model, ex, args.num_prompt_frames, args.maskgit_steps, args.temperature, args.teacher_force_time)
+    out = fn(model, ex, args.num_prompt_frames, args.maskgit_steps, args.temperature, args.teacher_force_time,
+             action_ids=None if actions is None else actions.to("cuda"))
     print(G.write_outputs(out, args.output_dir, meta, vars(args)))
 
 

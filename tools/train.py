@@ -3,6 +3,8 @@
 what is built (dataset windows, GenieConfig json, AdamW + decay grouping, linear / custom_cosine schedules, gradient
 accumulation, clipping, periodic teacher-forced eval, `save_pretrained` checkpoints with the optimizer state, resume).
 Not built: accelerate/wandb logging, torch.compile, the Llama baseline, MuAdamW (--mu_transfer).
+A config with action_vocab_size > 0 trains an action-conditioned model on the datasets' actions.bin (refused without one);
+--warmstart_path from an unconditioned checkpoint then starts from a zero action table.
 
   python tools/train.py --genie_config genie/configs/magvit_n32_h8_d256.json --train_data_dir data/train_v1.1 \\
       --val_data_dir data/val_v1.1 --output_dir out --per_device_train_batch_size 8 --max_train_steps 1000
@@ -74,6 +76,7 @@ def main():
         random.seed(args.seed)  # the collator's branch draws are host-side: keep the ranks in step
 
     # ---- data (train.py:421-436)
+    get_train_acts = get_eval_acts = None   # per-frame actions (action-conditioned configs)
     if args.synthetic:
         cfg = (cfgmod.GenieConfig.from_pretrained(args.genie_config) if args.genie_config else
                {"c138": cfgmod.c138, "c35": cfgmod.c35,
@@ -84,6 +87,11 @@ def main():
         get_train = lambda idx: train_clips[idx]  # noqa: E731
         get_eval = lambda idx: eval_clips[idx]  # noqa: E731
         n_train, n_eval = len(train_clips), len(eval_clips)
+        if cfg.action_vocab_size:   # synthetic per-frame actions
+            g = torch.Generator().manual_seed(2)
+            train_acts = torch.randint(0, cfg.action_vocab_size, (len(train_clips), cfg.T), generator=g)
+            get_train_acts = lambda idx: train_acts[idx]  # noqa: E731
+            get_eval_acts = lambda idx: train_acts[: len(eval_clips)][idx]  # noqa: E731
     else:
         tds = datamod.RawTokenDataset(args.train_data_dir, window_size=args.window_size, stride=args.stride,
                                       filter_overlaps=args.filter_overlaps)
@@ -94,10 +102,20 @@ def main():
         cfg.image_vocab_size, cfg.T, cfg.S = tds.metadata["vocab_size"], args.window_size, tds.metadata["s"] ** 2
         cfg.__post_init__()
         get_train, get_eval, n_train, n_eval = tds.batch, eds.batch, len(tds), len(eds)
+        if cfg.action_vocab_size:
+            for name, ds in (("train", tds), ("val", eds)):
+                if ds.actions is None:
+                    sys.exit(f"train.py: the config is action-conditioned (action_vocab_size {cfg.action_vocab_size}) but the "
+                             f"{name} dataset has no actions.bin")
+            get_train_acts, get_eval_acts = tds.action_batch, eds.action_batch
 
     load_from = args.resume_from_checkpoint or args.warmstart_path
-    model = (STMaskGIT.from_pretrained(load_from, precision=args.precision) if load_from
+    warm_actions = cfg.action_vocab_size if (args.warmstart_path and not args.resume_from_checkpoint) else None
+    model = (STMaskGIT.from_pretrained(load_from, precision=args.precision, action_vocab_size=warm_actions or None) if load_from
              else STMaskGIT(cfg, precision=args.precision))
+    acts_of = (lambda get, idx: get(idx).to(dev)) if model.config.action_vocab_size else (lambda get, idx: None)
+    if model.config.action_vocab_size and not cfg.action_vocab_size:
+        sys.exit("train.py: the checkpoint is action-conditioned: give a --genie_config with its action_vocab_size")
     if not load_from and args.mu_transfer:
         # reference train.py:420-424: init_weights() only on the muP path; otherwise PyTorch's default initialisation
         # of nn.Linear / nn.Embedding stays (kept here too, so from-scratch dynamics follow the reference recipe)
@@ -134,8 +152,9 @@ def main():
         sums = torch.zeros(3, dtype=torch.float64, device=dev)
         eb = args.per_device_eval_batch_size
         for k, s0 in enumerate(range(rank * eb, n_eval - eb * world + 1, eb * world)):
-            batch = datamod.maskgit_collate(get_eval(range(s0, s0 + eb)).to(dev), cfg)
-            out = model(batch["input_ids"], batch["labels"])
+            batch = datamod.maskgit_collate(get_eval(range(s0, s0 + eb)).to(dev), cfg,
+                                            action_ids=acts_of(get_eval_acts, range(s0, s0 + eb)))
+            out = model(batch["input_ids"], batch["labels"], action_ids=batch.get("action_ids"))
             sums += torch.stack([out.loss.double() * eb, out.acc.double() * eb, torch.tensor(float(eb), device=dev).double()])
             if k + 1 >= args.max_eval_steps:
                 break
@@ -152,7 +171,7 @@ def main():
         perm = torch.randperm(n_train, generator=g)  # same permutation on every rank; rank r takes its slice
         for m in range(consumed % micro_per_epoch if epoch == consumed // micro_per_epoch else 0, micro_per_epoch):
             idx = perm[(m * world + rank) * B:(m * world + rank + 1) * B].tolist()
-            batch = datamod.maskgit_collate(get_train(idx).to(dev), cfg)
+            batch = datamod.maskgit_collate(get_train(idx).to(dev), cfg, action_ids=acts_of(get_train_acts, idx))
             out = tr.train_step(batch)
             loss_info += torch.stack([out["loss"] * B, torch.tensor(float(B), device=dev, dtype=torch.float64)])
             if "lr" not in out:
