@@ -291,7 +291,8 @@ int launch_attn_spatial_bwd_bf16(const float* qkv, const float* qk, long qk_ld, 
     static const int on = study_env("GENIE_ATTN_BWD16", 1);
     if (!on || S != 256 || (Dh != 64 && Dh != 32) || qk_ld % 4 || d % 4) return GENIE_E_UNSUPPORTED;
     if (n_bt <= 0) return GENIE_OK;
-    ProfScope prof(GENIE_KC_ATTN_SPATIAL, 14.0 * S * S * Dh * (double)n_bt * H, 4.0 * 10 * S * Dh * (double)n_bt * H, st);
+    ProfScope prof(GENIE_KC_ATTN_SPATIAL, 14.0 * S * S * Dh * (double)n_bt * H, 4.0 * 10 * S * Dh * (double)n_bt * H, st,
+                   "attn_bwd16_q_kernel + attn_bwd16_kv_kernel");
     const unsigned grid = (unsigned)(n_bt * H);
 #define BWD16(DH_)                                                                                                        \
     do {                                                                                                                  \

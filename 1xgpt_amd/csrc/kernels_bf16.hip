@@ -24,7 +24,7 @@ typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 enum { G16_GELU = 1, G16_ACCUM = 2, G16_OUT16 = 4, G16_OUTF32 = 8,
-       G16_GELU16 = 16, /* erf-GELU on the 16-bit output only: Cf keeps the pre-activation (training forward) */
+       G16_GELU16 = 16, /* GELU on the 16-bit output only (bf16: gelu16_2 polynomial): Cf keeps the pre-activation (training forward) */
        G16_NT = 32,     /* non-temporal output stores: the output is larger than the on-die caches (launcher) */
        G16_WIDEW = 1024 /* launcher only (never reaches a kernel): the f16x3 weight's hi plane reaches |w| >= 32 -> not the
                            2^11-scaling single-accumulator kernel (the `w16_wide` flags of genie_hip.h) */ };
@@ -232,7 +232,10 @@ __global__ __launch_bounds__(256, 2) void gemm16_nt_kernel(const uint16_t* __res
             }
         }
         if (out16) {
-            if (flags & G16_GELU16) { v.x = gelu_erf_fast(v.x); v.y = gelu_erf_fast(v.y); v.z = gelu_erf_fast(v.z); v.w = gelu_erf_fast(v.w); }
+            if (flags & G16_GELU16) {   // bf16: the polynomial form, as in gemm16_pp (the hidden must not depend on the tile kernel)
+                const genie_f2 g0 = gelu16_2<NPL == 1>(genie_f2{v.x, v.y}), g1 = gelu16_2<NPL == 1>(genie_f2{v.z, v.w});
+                v.x = g0[0]; v.y = g0[1]; v.z = g1[0]; v.w = g1[1];
+            }
             store16<NPL>(C16, (size_t)plane16, idx, v.x); store16<NPL>(C16, (size_t)plane16, idx + 1, v.y);
             store16<NPL>(C16, (size_t)plane16, idx + 2, v.z); store16<NPL>(C16, (size_t)plane16, idx + 3, v.w);
         }
@@ -287,7 +290,7 @@ __global__ __launch_bounds__(256, 2) void gemm16_nt_kernel(const uint16_t* __res
                 const size_t idx = (size_t)row * ldc + col + c;
                 if (do_acc) v += Rsrc[idx];
                 if (outf) Cf[idx] = v;
-                if (out16) store16<NPL>(C16, (size_t)plane16, idx, (flags & G16_GELU16) ? gelu_erf_fast(v) : v);
+                if (out16) store16<NPL>(C16, (size_t)plane16, idx, (flags & G16_GELU16) ? gelu16_1<NPL == 1>(v) : v);
             }
         }
     }
@@ -565,7 +568,10 @@ __global__ __launch_bounds__(256 * NWN, 1) void gemm16_v2_kernel(const uint16_t*
             }
         }
         if (out16) {
-            if (flags & G16_GELU16) { v.x = gelu_erf_fast(v.x); v.y = gelu_erf_fast(v.y); v.z = gelu_erf_fast(v.z); v.w = gelu_erf_fast(v.w); }
+            if (flags & G16_GELU16) {   // bf16: the polynomial form, as in gemm16_pp (the hidden must not depend on the tile kernel)
+                const genie_f2 g0 = gelu16_2<NPL == 1>(genie_f2{v.x, v.y}), g1 = gelu16_2<NPL == 1>(genie_f2{v.z, v.w});
+                v.x = g0[0]; v.y = g0[1]; v.z = g1[0]; v.w = g1[1];
+            }
             if constexpr (NPL == 1) {
                 uint2 pk;
                 pk.x = (uint32_t)f32_to_bf16(v.x) | ((uint32_t)f32_to_bf16(v.y) << 16);

@@ -272,8 +272,8 @@ __global__ __launch_bounds__(NW * 64, 1) void gemm16_sm_kernel(const uint16_t* _
         }
         if (outf) *reinterpret_cast<float4*>(Cf + idx) = v;
         if (out16) {
-            if (flags & G16X_GELU16) {
-                const genie_f2 g0 = gelu_erf_fast2(genie_f2{v.x, v.y}), g1 = gelu_erf_fast2(genie_f2{v.z, v.w});
+            if (flags & G16X_GELU16) {   // bf16: the polynomial form, as in gemm16_pp
+                const genie_f2 g0 = gelu16_2<NPL == 1>(genie_f2{v.x, v.y}), g1 = gelu16_2<NPL == 1>(genie_f2{v.z, v.w});
                 v.x = g0[0]; v.y = g0[1]; v.z = g1[0]; v.w = g1[1];
             }
             if (NPL == 1 || plane16 == 0) {

@@ -147,7 +147,8 @@ int launch_wgrad16_tn(const uint16_t* dY, long ldy, const uint16_t* X, long ldx,
     int ns = 1;
     while (ns < 64 && tiles * ns < want && Mtok % (64 * ns * 2) == 0 && (size_t)(ns * 2) * N * K <= slab_floats) ns *= 2;
     const size_t lds = 2 * 2 * 64 * 256;
-    ProfScope prof(GENIE_KC_GEMM, 2.0 * Mtok * (double)N * K, 2.0 * Mtok * ((double)N + K) + 8.0 * ns * (double)N * K, st);
+    ProfScope prof(GENIE_KC_GEMM, 2.0 * Mtok * (double)N * K, 2.0 * Mtok * ((double)N + K) + 8.0 * ns * (double)N * K, st,
+                   "wgrad16_tn_kernel");
     (void)hipFuncSetAttribute((const void*)wgrad16_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     wgrad16_tn_kernel<<<tiles * ns, 256, lds, st>>>(dY, ldy, X, ldx, slabs, N, K, Mtok / ns, ns, alpha);
     GENIE_LAUNCH_CHECK("wgrad16_tn");

@@ -159,7 +159,8 @@ int launch_gemm_f32_gen(bool ta, bool tb, const float* A, long lda, long sA1, lo
     dim3 grid(mt * nt, batch1, batch2 * nsplit);
     const double mn = (double)M * N * batch1 * batch2;
     ProfScope prof(GENIE_KC_GEMM, 2.0 * mn * K,
-                   4.0 * (((double)M * K + (double)N * K) * batch1 * batch2 + mn * nsplit * (R ? 2 : 1)), st);
+                   4.0 * (((double)M * K + (double)N * K) * batch1 * batch2 + mn * nsplit * (R ? 2 : 1)), st,
+                   "gemm_f32_gen_kernel");
 #define GG_LAUNCH(TA_, TB_)                                                                                          \
     gemm_f32_gen_kernel<TA_, TB_><<<grid, 256, 0, st>>>(A, lda, sA1, sA2, W, ldw, sW1, sW2, bias, R, C, ldc, sC1, sC2, \
                                                         M, N, K, alpha, nsplit, sCsplit)
@@ -1046,7 +1047,8 @@ int launch_attn_spatial_bwd_fused(const float* qkv, const float* qk, long qk_ld,
     if (S != 256 || (Dh != 64 && Dh != 32)) return GENIE_E_UNSUPPORTED;
     if (n_bt <= 0) return GENIE_OK;
     const size_t lds = (size_t)((2 * 256 + 2 * 32) * (Dh + 4) + 12 * 32 + 3 * 256) * sizeof(float);
-    ProfScope prof(GENIE_KC_ATTN_SPATIAL, 14.0 * S * S * Dh * (double)n_bt * H, 4.0 * 10 * S * Dh * (double)n_bt * H, st);
+    ProfScope prof(GENIE_KC_ATTN_SPATIAL, 14.0 * S * S * Dh * (double)n_bt * H, 4.0 * 10 * S * Dh * (double)n_bt * H, st,
+                   "attn_spatial_bwd_fused_kernel");
     if (Dh == 64) {
         (void)hipFuncSetAttribute((const void*)attn_spatial_bwd_fused_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds);

@@ -8,7 +8,7 @@ a mean error of 1e-3 of the update, with Adam's sign sensitivity on near-zero gr
 import numpy as np
 import pytest
 
-from conftest import pkg
+from conftest import pkg, record_measure
 from oracle import genie_train_oracle as TO
 
 pytestmark = pytest.mark.gpu
@@ -160,9 +160,11 @@ def test_bf16_attention_backward_vs_exact(H, d, qk_norm):
     assert not bad, bad
 
 
-@pytest.mark.parametrize("H,d,B,qk_norm,T", [(4, 128, 3, False, 4), (2, 64, 1, False, 4), (2, 128, 2, True, 4),
-                                              (4, 128, 1, True, 4), (4, 128, 2, False, 16), (2, 128, 1, True, 16),
-                                              (4, 256, 2, False, 4), (8, 512, 1, False, 4)])
+ORACLE_CASES = [(4, 128, 3, False, 4), (2, 64, 1, False, 4), (2, 128, 2, True, 4), (4, 128, 1, True, 4), (4, 128, 2, False, 16),
+                (2, 128, 1, True, 16), (4, 256, 2, False, 4), (8, 512, 1, False, 4)]
+
+
+@pytest.mark.parametrize("H,d,B,qk_norm,T", ORACLE_CASES)
 @pytest.mark.parametrize("use_mup", [False, True])
 def test_gradients_vs_oracle(H, d, B, qk_norm, T, use_mup):
     """Other widths / head sizes (Dh = 32, 64), an odd batch, T = 16 (the MFMA temporal kernels, forward and backward,
@@ -170,6 +172,23 @@ def test_gradients_vs_oracle(H, d, B, qk_norm, T, use_mup):
     kernels) against the NumPy restatement."""
     if use_mup and (B != 1 or T != 4):
         pytest.skip("muP scaling (attention scale 8/Dh, readout multiplier 256/d) is covered on the single-clip cases")
+    gradients_vs_oracle(H, d, B, qk_norm, T, use_mup, "exact")
+
+
+@pytest.mark.parametrize("H,d,B,qk_norm,T,use_mup", [c + (False,) for c in ORACLE_CASES] +
+                         [c + (True,) for c in ORACLE_CASES if c[2] == 1 and c[4] == 4])
+def test_gradients_vs_oracle_f16x3(H, d, B, qk_norm, T, use_mup):
+    """The same cases in f16x3 at the same bar as exact ("f32-class gradients"): at d >= 128 the
+    split-f16 copies go through the multi-tile cast_transpose / token-slab wgrad path that the d = 64 fixtures never reach.
+
+    Measured on an MI355X: 1.6e-6 .. 4.0e-5, except the two tight cases, H8 d512 muP 7.0e-5 and H4 d256 B2 5.3e-5 (the
+    margins under GRAD_TOL are 1.4x and 1.9x).  There the split-f16 contract itself accounts for much of it:
+    oracle.F16X3_TRAIN is 3.5e-5 and 1.8e-5 from the f32 oracle.  f16x3 has no bf16 rounding to flip, so its distance does
+    not drift chaotically with accumulation order the way bf16's does (test_hip_train_bf16.py)."""
+    gradients_vs_oracle(H, d, B, qk_norm, T, use_mup, "f16x3")
+
+
+def gradients_vs_oracle(H, d, B, qk_norm, T, use_mup, precision):
     cfg = pkg("config").GenieConfig(num_layers=2, num_heads=H, d_model=d, T=T, S=16, num_factored_vocabs=2,
                                     qk_norm=qk_norm, num_prompt_frames=2, use_mup=use_mup)
     syn = pkg("synthetic")
@@ -177,12 +196,16 @@ def test_gradients_vs_oracle(H, d, B, qk_norm, T, use_mup):
     ids = syn.make_clips(B, cfg, seed=900 + d)
     batch = TO.maskgit_collate(ids, cfg, TO.NumpyDraws(5 + B))
     loss_o, acc_o, g_o = TO.forward_backward(batch["input_ids"], batch["labels"], sd, cfg)
-    tr = make_trainer(cfg, sd)
+    tr = make_trainer(cfg, sd, precision)
     loss, acc = tr.forward_backward(dev(batch["input_ids"]), dev(batch["labels"]))
     assert abs(float(loss) - loss_o) < 1e-5 * abs(loss_o)
     assert abs(float(acc) - acc_o) < 1e-7
-    for k, g in tr.gradients().items():
-        assert rel_err(g.cpu().numpy(), g_o[k]) < GRAD_TOL, k
+    worst = {k: rel_err(g.cpu().numpy(), g_o[k]) for k, g in tr.gradients().items()}
+    if precision != "exact":
+        record_measure(f"train_vs_oracle/{precision}/H{H}_d{d}_B{B}_qk{int(qk_norm)}_T{T}_mup{int(use_mup)}",
+                       max(worst.values()))
+    bad = {k: v for k, v in worst.items() if v >= GRAD_TOL}
+    assert not bad, bad
 
 
 @pytest.mark.parametrize("H,d,qk_norm", [(2, 64, False), (1, 64, True)])
