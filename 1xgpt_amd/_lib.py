@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("GENIE_HIP_LIBRARY") or os.path.join(HERE, "libgenie_h
 
 PREC_EXACT, PREC_BF16, PREC_F16X3 = 0, 1, 2
 LAYOUT_TOKEN_MAJOR, LAYOUT_BCTHW = 0, 1
-UNMASK_RANDOM, UNMASK_GREEDY = 0, 1
+UNMASK_RANDOM, UNMASK_GREEDY, UNMASK_CONFIDENCE = 0, 1, 2
 KC_GEMM, KC_ATTN_SPATIAL, KC_ATTN_TEMPORAL, KC_LAYERNORM, KC_OTHER, KC_FUSED = range(6)
 E_ARG, E_SHAPE, E_UNSUPPORTED, E_LAUNCH, E_ASSERT = -1, -2, -3, -4, -5
 
@@ -50,6 +50,11 @@ class FrameCond(C.Structure):
     _fields_ = [("table", c_ptr), ("ids", c_ptr), ("n_actions", C.c_int32)]
 
 
+class Sampling(C.Structure):
+    """genie_sampling: logit temperature, top-k, top-p, choice temperature of the "confidence" unmasking (1xgpt_amd/sampling.py)."""
+    _fields_ = [("logit_temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("choice_temperature", C.c_float)]
+
+
 WIDE_QKV, WIDE_PROJ, WIDE_FC1, WIDE_FC2 = 1, 2, 1, 2          # bits of the w16_wide fields (genie_hip.h)
 FUSED_QKV_STREAM = 4                                        # spatial attention: fused_w16 = [proj stream | qkv stream]
 TEMPORAL_QKV_F16X3_ELEMS = 393216   # f16 values of the f16x3 temporal qkv stream (csrc/kernels_fused_f16x3.hip)
@@ -61,6 +66,7 @@ ABI_VERSION = 3
 SIGNATURES = {
     "genie_version": (C.c_int, []),
     "genie_abi_layout": (C.c_int, [C.POINTER(C.c_size_t), C.c_int]),
+    "genie_sampling_layout": (C.c_int, [C.POINTER(C.c_size_t), C.c_int]),
     "genie_last_error": (C.c_char_p, []),
     "genie_check_config": (C.c_int, [C.POINTER(GenieCfg)]),
     "genie_workspace_bytes": (C.c_size_t, [C.POINTER(GenieCfg), C.c_int]),
@@ -174,6 +180,12 @@ for _n in ("genie_embed", "genie_compute_logits", "genie_maskgit_generate", "gen
            "genie_frame_pass", "genie_frames_pass", "genie_generate_cached", "genie_train_forward"):
     SIGNATURES[_n + "_cond"] = (SIGNATURES[_n][0], SIGNATURES[_n][1] + [C.POINTER(FrameCond)])
 del _n
+# the *_ex variants: the *_cond arguments + a trailing genie_sampling* (NULL = the *_cond entry point); genie_sample_ex: genie_sample's
+# arguments + sampling, keys_out, noise, anneal
+for _n in ("genie_maskgit_generate", "genie_generate_cached"):
+    SIGNATURES[_n + "_ex"] = (SIGNATURES[_n][0], SIGNATURES[_n + "_cond"][1] + [C.POINTER(Sampling)])
+del _n
+SIGNATURES["genie_sample_ex"] = (C.c_int, SIGNATURES["genie_sample"][1] + [C.POINTER(Sampling), c_ptr, c_ptr, C.c_float])
 
 _lib = None
 
@@ -203,6 +215,10 @@ def load():
             fn.restype, fn.argtypes = res, args
         if lib.genie_version() != ABI_VERSION:
             raise RuntimeError(f"libgenie_hip ABI version {lib.genie_version()} != {ABI_VERSION}")
+        lay = (C.c_size_t * 5)()
+        mine = [C.sizeof(Sampling)] + [getattr(Sampling, n).offset for n, _ in Sampling._fields_]
+        if lib.genie_sampling_layout(lay, 5) != 5 or list(lay) != mine:
+            raise RuntimeError(f"genie_sampling layout {list(lay)} != the ctypes declaration {mine}")
         if os.environ.get("GENIE_HIP_LIBRARY") or lib.genie_study_build():
             import sys
             print(f"1xgpt_amd: using {LIB_PATH} (study build: {bool(lib.genie_study_build())}) -- not the shipping library",
@@ -226,6 +242,13 @@ def call_cond(lib, name, cond, *args):
     if cond is None:
         return getattr(lib, name)(*args)
     return getattr(lib, name + "_cond")(*args, cond)
+
+
+def call_ex(lib, name, cond, sampling, *args):
+    """call_cond when `sampling` is None (the entry points of before, unchanged), else lib.<name>_ex(*args, cond, sampling)."""
+    if sampling is None:
+        return call_cond(lib, name, cond, *args)
+    return getattr(lib, name + "_ex")(*args, cond, sampling)
 
 
 def make_cfg(config, precision=PREC_EXACT) -> GenieCfg:

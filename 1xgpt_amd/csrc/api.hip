@@ -254,6 +254,34 @@ static int mask_count(int step, int steps, int S) {
 
 using namespace genie;
 
+// a genie_sampling law (NULL = none), checked on the host before anything is enqueued
+static int check_sampling(const genie_sampling* sp, const char* where) {
+    if (!sp) return GENIE_OK;
+    GENIE_CHECK_ARG(sp->logit_temperature > 0.f && sp->logit_temperature <= 3.0e38f,
+                    "%s: sampling: logit_temperature %g must be positive and finite", where, (double)sp->logit_temperature);
+    GENIE_CHECK_ARG(sp->top_k >= 0, "%s: sampling: top_k %d must be >= 0", where, sp->top_k);
+    GENIE_CHECK_ARG(sp->top_p == sp->top_p, "%s: sampling: top_p is NaN", where);
+    GENIE_CHECK_ARG(sp->choice_temperature >= 0.f, "%s: sampling: choice_temperature %g must be >= 0", where,
+                    (double)sp->choice_temperature);
+    return GENIE_OK;
+}
+// unmask_mode and the draws it needs; GENIE_UNMASK_CONFIDENCE only through the *_ex entry points (ex)
+static int check_unmask(int unmask_mode, bool ex, int steps, const float* noise, const char* where) {
+    const bool known = unmask_mode == GENIE_UNMASK_RANDOM || unmask_mode == GENIE_UNMASK_GREEDY ||
+                       (ex && unmask_mode == GENIE_UNMASK_CONFIDENCE);
+    if (!known) {
+        set_error(ex ? "Expected `unmask_mode` to be one of ['greedy', 'random', 'confidence']"
+                     : "Expected `unmask_mode` to be one of ['greedy', 'random']");
+        return GENIE_E_UNSUPPORTED;
+    }
+    GENIE_CHECK_ARG(steps <= 1 || unmask_mode == GENIE_UNMASK_GREEDY || noise,
+                    "%s: '%s' unmasking with steps > 1 needs the caller's U[0,1) draws", where,
+                    unmask_mode == GENIE_UNMASK_CONFIDENCE ? "confidence" : "random");
+    return GENIE_OK;
+}
+// the confidence mode's scale when the caller gave no law: the documented default of choice_temperature
+static const genie_sampling kDefaultSampling = {1.0f, 0, 1.0f, 4.5f};
+
 extern "C" {
 
 int genie_version(void) { return GENIE_ABI_VERSION; }
@@ -265,6 +293,12 @@ int genie_abi_layout(size_t* out_host, int n) {
                           offsetof(genie_layer_weights, mlp_frame_w16), offsetof(genie_weights, out_frame_w16)};
     for (int i = 0; i < n && i < 12 && out_host; ++i) out_host[i] = v[i];
     return 12;
+}
+int genie_sampling_layout(size_t* out_host, int n) {
+    const size_t v[5] = {sizeof(genie_sampling), offsetof(genie_sampling, logit_temperature), offsetof(genie_sampling, top_k),
+                         offsetof(genie_sampling, top_p), offsetof(genie_sampling, choice_temperature)};
+    for (int i = 0; i < n && i < 5 && out_host; ++i) out_host[i] = v[i];
+    return 5;
 }
 const char* genie_last_error(void) { return g_err; }
 int genie_check_config(const genie_cfg* cfg) { return check_cfg(cfg); }
@@ -637,19 +671,28 @@ int genie_generate_cached_cond(const genie_cfg* cfg, const genie_weights* wt, co
                                int teacher_force_time, int merge_commit, int64_t* gen_out, float* logits0_out, float* cache,
                                size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
                                const genie_frame_cond* cond) {
+    if (unmask_mode == GENIE_UNMASK_CONFIDENCE) unmask_mode = -1;   // (only genie_generate_cached_ex knows that mode)
+    return genie_generate_cached_ex(cfg, wt, ids, B, P, n_new, steps, temperature, unmask_mode, noise, uniforms, teacher_force_time,
+                                    merge_commit, gen_out, logits0_out, cache, cache_bytes, workspace, workspace_bytes, stream, cond,
+                                    nullptr);
+}
+
+int genie_generate_cached_ex(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int P, int n_new,
+                             int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                             int teacher_force_time, int merge_commit, int64_t* gen_out, float* logits0_out, float* cache,
+                             size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
+                             const genie_frame_cond* cond, const genie_sampling* sampling) {
     GENIE_TRY(check_cfg(cfg));
     const genie_cfg& c = *cfg;
     GENIE_CHECK_ARG(wt && wt->layers_host && ids && gen_out && cache, "generate_cached: NULL pointer");
     GENIE_TRY(check_frame_cond(cond, "generate_cached"));
     GENIE_CHECK_ARG(B >= 1 && P >= 1 && n_new >= 1 && P + n_new <= c.T && steps >= 1,
                     "generate_cached: B=%d, %d prompt + %d new frames of at most %d, steps %d", B, P, n_new, c.T, steps);
-    if (unmask_mode != GENIE_UNMASK_RANDOM && unmask_mode != GENIE_UNMASK_GREEDY) {
-        set_error("Expected `unmask_mode` to be one of ['greedy', 'random']");
-        return GENIE_E_UNSUPPORTED;
-    }
-    GENIE_CHECK_ARG(steps == 1 || unmask_mode == GENIE_UNMASK_GREEDY || noise,
-                    "generate_cached: 'random' unmasking with steps > 1 needs the caller's U[0,1) draws");
+    GENIE_TRY(check_sampling(sampling, "generate_cached"));
+    GENIE_TRY(check_unmask(unmask_mode, unmask_mode != -1, steps, noise, "generate_cached"));
     GENIE_CHECK_ARG(temperature <= 1e-8f || uniforms, "generate_cached: temperature > 0 needs uniforms");
+    const bool by_conf = unmask_mode == GENIE_UNMASK_CONFIDENCE;
+    const genie_sampling* law = (by_conf && !sampling) ? &kDefaultSampling : sampling;
     GENIE_CHECK_ARG(cache_bytes >= genie_prefix_cache_bytes(cfg, B), "generate_cached: cache too small");
     GENIE_TRY(check_ws(c, B, workspace, workspace_bytes));
     hipStream_t st = as_stream(stream);
@@ -704,9 +747,12 @@ int genie_generate_cached_cond(const genie_cfg* cfg, const genie_weights* wt, co
                 }
             }
             const float* u = temperature > 1e-8f ? uniforms + ((size_t)k * steps + step) * c.num_factored * BS : nullptr;
-            GENIE_TRY(launch_sample(c, logits, GENIE_LAYOUT_TOKEN_MAJOR, B, temperature, u, samples, conf, st));
             const bool last = step == steps - 1;
-            const float* keys = last ? nullptr : (unmask_mode == GENIE_UNMASK_GREEDY ? conf : noise + ((size_t)k * (steps - 1) + step) * BS);
+            const float* draws = (last || unmask_mode == GENIE_UNMASK_GREEDY) ? nullptr : noise + ((size_t)k * (steps - 1) + step) * BS;
+            // "confidence": the sample launch writes the keys over conf (nothing else reads conf in this loop)
+            GENIE_TRY(launch_sample_ex(c, logits, GENIE_LAYOUT_TOKEN_MAJOR, B, temperature, u, samples, conf, law,
+                                       (by_conf && !last) ? conf : nullptr, draws, 1.0f - (float)(step + 1) / (float)steps, st));
+            const float* keys = last ? nullptr : (unmask_mode == GENIE_UNMASK_RANDOM ? draws : conf);
             GENIE_TRY(launch_mask_step(keys, last ? 0 : mask_count(step, steps, S), last, c.image_vocab_size, unmasked, samples, cur, S, B, S, st));
         }
         GENIE_TRY(put_frame_ids(cur, S, gen_out + (size_t)k * S, (long)n_new * S, S, B, 0, st));
@@ -773,6 +819,19 @@ int genie_sample(const genie_cfg* cfg, const float* logits, int layout, int B, f
     return launch_sample(*cfg, logits, layout, B, temperature, uniforms, samples, conf, as_stream(stream));
 }
 
+int genie_sample_ex(const genie_cfg* cfg, const float* logits, int layout, int B, float temperature, const float* uniforms,
+                    int64_t* samples, float* conf, void* stream, const genie_sampling* sampling, float* keys_out,
+                    const float* noise, float anneal) {
+    GENIE_TRY(check_cfg(cfg));
+    GENIE_CHECK_ARG(logits && samples && conf && B >= 1, "sample: bad argument");
+    GENIE_CHECK_ARG(temperature <= 1e-8f || uniforms, "sample: temperature > 0 needs caller-supplied uniforms");
+    GENIE_TRY(check_sampling(sampling, "sample"));
+    GENIE_CHECK_ARG(!keys_out || noise, "sample: keys_out needs the caller's U[0,1) noise draws");
+    GENIE_CHECK_ARG(!keys_out || anneal == anneal, "sample: anneal is NaN");
+    return launch_sample_ex(*cfg, logits, layout, B, temperature, uniforms, samples, conf,
+                            (keys_out && !sampling) ? &kDefaultSampling : sampling, keys_out, noise, anneal, as_stream(stream));
+}
+
 int genie_mask_step(const float* keys, int n, int last_step, int64_t mask_id, uint8_t* unmasked, int64_t* samples,
                     int64_t* prompt_frame, int64_t prompt_clip_stride, int B, int S, void* stream) {
     GENIE_CHECK_ARG(unmasked && samples && prompt_frame && B >= 1 && S >= 1, "mask_step: bad argument");
@@ -794,6 +853,16 @@ int genie_maskgit_generate_cond(const genie_cfg* cfg, const genie_weights* wt, i
                                 float temperature, int unmask_mode, const float* noise, const float* uniforms,
                                 int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
                                 void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond) {
+    if (unmask_mode == GENIE_UNMASK_CONFIDENCE) unmask_mode = -1;   // (only genie_maskgit_generate_ex knows that mode)
+    return genie_maskgit_generate_ex(cfg, wt, prompt, B, out_t, steps, temperature, unmask_mode, noise, uniforms, samples_out,
+                                     logits0_out, layout, status_flag, workspace, workspace_bytes, stream, cond, nullptr);
+}
+
+int genie_maskgit_generate_ex(const genie_cfg* cfg, const genie_weights* wt, int64_t* prompt, int B, int out_t, int steps,
+                              float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                              int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
+                              void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond,
+                              const genie_sampling* sampling) {
     GENIE_TRY(check_cfg(cfg));
     const genie_cfg& c = *cfg;
     GENIE_CHECK_ARG(wt && wt->layers_host && prompt && samples_out, "maskgit_generate: NULL pointer");
@@ -803,13 +872,11 @@ int genie_maskgit_generate_cond(const genie_cfg* cfg, const genie_weights* wt, i
         return GENIE_E_ASSERT;
     }
     GENIE_CHECK_ARG(steps >= 1, "maskgit_generate: steps=%d must be >= 1", steps);
-    if (unmask_mode != GENIE_UNMASK_RANDOM && unmask_mode != GENIE_UNMASK_GREEDY) {
-        set_error("Expected `unmask_mode` to be one of ['greedy', 'random']");
-        return GENIE_E_UNSUPPORTED;
-    }
-    GENIE_CHECK_ARG(steps == 1 || unmask_mode == GENIE_UNMASK_GREEDY || noise,
-                    "maskgit_generate: 'random' unmasking with steps > 1 needs the caller's U[0,1) draws");
+    GENIE_TRY(check_sampling(sampling, "maskgit_generate"));
+    GENIE_TRY(check_unmask(unmask_mode, unmask_mode != -1, steps, noise, "maskgit_generate"));
     GENIE_CHECK_ARG(temperature <= 1e-8f || uniforms, "maskgit_generate: temperature > 0 needs uniforms");
+    const bool by_conf = unmask_mode == GENIE_UNMASK_CONFIDENCE;
+    const genie_sampling* law = (by_conf && !sampling) ? &kDefaultSampling : sampling;
     GENIE_TRY(check_ws(c, B, workspace, workspace_bytes));
     Workspace w = carve(c, B, workspace);
     hipStream_t st = as_stream(stream);
@@ -835,13 +902,16 @@ int genie_maskgit_generate_cond(const genie_cfg* cfg, const genie_weights* wt, i
             }
         }
         const float* u = (temperature > 1e-8f) ? uniforms + (size_t)step * c.num_factored * BS : nullptr;
-        GENIE_TRY(launch_sample(c, w.logits, GENIE_LAYOUT_TOKEN_MAJOR, B, temperature, u, w.samples, w.conf, st));
         const int last = (step == steps - 1);
+        const float* draws = (last || unmask_mode == GENIE_UNMASK_GREEDY) ? nullptr : noise + (size_t)step * BS;
+        // "confidence": the sample launch writes the keys over conf (nothing else reads conf in this loop)
+        GENIE_TRY(launch_sample_ex(c, w.logits, GENIE_LAYOUT_TOKEN_MAJOR, B, temperature, u, w.samples, w.conf, law,
+                                   (by_conf && !last) ? w.conf : nullptr, draws, 1.0f - (float)(step + 1) / (float)steps, st));
         const float* keys = nullptr;
         int n = 0;
         if (!last) {
             n = mask_count(step, steps, c.S);
-            keys = (unmask_mode == GENIE_UNMASK_GREEDY) ? w.conf : noise + (size_t)step * BS;
+            keys = (unmask_mode == GENIE_UNMASK_RANDOM) ? draws : w.conf;
         }
         GENIE_TRY(launch_mask_step(keys, n, last, c.image_vocab_size, w.unmasked, w.samples,
                                    prompt + (size_t)out_t * c.S, (long)c.T * c.S, B, c.S, st));

@@ -170,6 +170,11 @@ int launch_factored_ce(const genie_cfg& c, const float* logits, int layout, cons
                        const int64_t* weight_ids, int B, int t0, int t1, double* sums, hipStream_t st);
 int launch_sample(const genie_cfg& c, const float* logits, int layout, int B, float temperature,
                   const float* uniforms, int64_t* samples, float* conf, hipStream_t st);
+// kernels_sample.hip: the tempered / top-k / top-p filtered law (genie_sampling); NULL or all-off without keys_out = launch_sample
+bool sampling_is_neutral(const genie_sampling* sp, int vf);
+int launch_sample_ex(const genie_cfg& c, const float* logits, int layout, int B, float temperature, const float* uniforms,
+                     int64_t* samples, float* conf, const genie_sampling* sp, float* keys_out, const float* noise, float anneal,
+                     hipStream_t st);
 int launch_mask_step(const float* keys, int n, int last_step, int64_t mask_id, uint8_t* unmasked, int64_t* samples,
                      int64_t* prompt_frame, long clip_stride, int B, int S, hipStream_t st);
 int launch_check_masked(const int64_t* prompt, int B, int T, int S, int out_t, int64_t mask_id, int32_t* flag,

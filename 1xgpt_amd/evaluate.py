@@ -33,6 +33,12 @@ class GenieEvaluator:
         self.device = device
         self.args = args
 
+    def _sampling(self):
+        """(SamplingConfig or None, unmask_mode) read from the args with defaults, so that namespaces that predate them still work:
+        top_k, top_p, logit_temperature, choice_temperature (all missing / None = the reference's law) and unmask_mode ("random")."""
+        from .sampling import SamplingConfig
+        return SamplingConfig.from_args(self.args), getattr(self.args, "unmask_mode", None) or "random"
+
     def predict_zframe_logits(self, input_ids: torch.LongTensor, noise=None, return_logits=True, action_ids=None):
         """input_ids (B, T*H*W) -> (samples (B,T-1,H,W), factored logits (B,512,2,T-1,H,W)).
 
@@ -42,6 +48,7 @@ class GenieEvaluator:
         m, a = self.model, self.args
         T = m.config.T
         clips = input_ids.to(self.device).to(torch.int64).view(-1, T, a.latent_h, a.latent_w)
+        sampling, unmask_mode = self._sampling()
         frames, logits = [], []
         for t in range(1, T):
             # timeline t: frames < t are ground truth, frame t and everything after it all-MASK; decode frame t
@@ -49,7 +56,7 @@ class GenieEvaluator:
             timeline[:, t:] = m.mask_token_id
             frame, lg = m.maskgit_generate(timeline, out_t=t, maskgit_steps=a.maskgit_steps, temperature=a.temperature,
                                            noise=None if noise is None else noise[t - 1], return_logits=return_logits,
-                                           check=False, action_ids=action_ids)
+                                           check=False, action_ids=action_ids, sampling=sampling, unmask_mode=unmask_mode)
             frames.append(frame)
             logits.append(lg)
         return torch.stack(frames, dim=1), (torch.stack(logits, dim=3) if return_logits else None)
@@ -64,7 +71,7 @@ class GenieEvaluator:
     # ------------------------------------------------------------------ teacher-forced prefix reuse
     @torch.no_grad()
     def predict_zframe_logits_reuse(self, input_ids: torch.LongTensor, noise=None, return_logits=True,
-                                    unmask_mode="random", step0_hook=None, action_ids=None):
+                                    unmask_mode=None, step0_hook=None, action_ids=None, uniforms=None):
         """Same contract and same per-row arithmetic as ``predict_zframe_logits`` in (1 + steps) passes over T-1 frames
         instead of 15 * steps forwards over T: the ground-truth frames < t of every timeline t are identical to one clean
         pass (temporal attention is causal, everything else per-frame), so they are computed once (frames 0..T-2: no
@@ -75,9 +82,18 @@ class GenieEvaluator:
         still holds the step-0 logits (later steps overwrite it in place); with a hook and return_logits=False no copy of the
         (2 GB at 128 clips) logits is kept.
         action_ids: (B, T) per-frame actions of an action-conditioned model (slot i of the masked passes is clip frame i + 1 and
-        takes action_ids[:, i + 1])."""
+        takes action_ids[:, i + 1]).
+        unmask_mode: None = the args' (default "random"); the sampling law comes from the args too (``_sampling``).
+        uniforms: optional (steps, num_factored_vocabs, B * (T-1), S) sampling draws to replay."""
         import math
+        from .sampling import SamplingConfig, as_struct, unmask_code
         lib = _lib.load()
+        sampling, args_mode = self._sampling()
+        unmask_mode = unmask_mode or args_mode
+        mode = unmask_code(unmask_mode)
+        law = as_struct(sampling)
+        if mode == _lib.UNMASK_CONFIDENCE and law is None:
+            law = as_struct(SamplingConfig())
         m = self.model
         cfg, w = m._weights()[:2]
         T, S = m.config.T, m.config.S
@@ -115,10 +131,8 @@ class GenieEvaluator:
                     logits0 = logits.clone() if steps > 1 else logits
             uni = None
             if temperature > 1e-8:
-                uni = torch.rand(m.config.num_factored_vocabs, B * n, S, device=dev)
-            _lib.check(lib.genie_sample(cfg, logits.data_ptr(), _lib.LAYOUT_TOKEN_MAJOR, B * n, temperature,
-                                        0 if uni is None else uni.data_ptr(), samples.data_ptr(), conf.data_ptr(), st),
-                       "genie_sample")
+                uni = (torch.rand(m.config.num_factored_vocabs, B * n, S, device=dev) if uniforms is None
+                       else uniforms[step].to(device=dev, dtype=torch.float32).contiguous())
             last = step == steps - 1
             keys, k_unmask = None, 0
             if not last:
@@ -129,6 +143,17 @@ class GenieEvaluator:
                     keys = torch.rand(B, n, S, device=dev)
                 else:  # reference draw order: one (B,S) tensor per timeline t and step
                     keys = noise[:, step].to(dev).reshape(n, B, S).permute(1, 0, 2).contiguous()
+            if law is None:
+                _lib.check(lib.genie_sample(cfg, logits.data_ptr(), _lib.LAYOUT_TOKEN_MAJOR, B * n, temperature,
+                                            0 if uni is None else uni.data_ptr(), samples.data_ptr(), conf.data_ptr(), st),
+                           "genie_sample")
+            else:   # "confidence": the same launch turns the step's draws into its keys
+                by_conf = mode == _lib.UNMASK_CONFIDENCE and not last
+                draws, keys = keys, (torch.empty(B, n, S, device=dev) if by_conf else keys)
+                _lib.check(lib.genie_sample_ex(cfg, logits.data_ptr(), _lib.LAYOUT_TOKEN_MAJOR, B * n, temperature,
+                                               0 if uni is None else uni.data_ptr(), samples.data_ptr(), conf.data_ptr(), st, law,
+                                               keys.data_ptr() if by_conf else 0, draws.data_ptr() if by_conf else 0,
+                                               1.0 - (step + 1) / steps), "genie_sample_ex")
             _lib.check(lib.genie_mask_step(0 if keys is None else keys.data_ptr(), k_unmask, int(last), m.mask_token_id,
                                            unmasked.data_ptr(), samples.data_ptr(), cur.data_ptr(), S, B * n, S, st),
                        "genie_mask_step")
@@ -187,12 +212,14 @@ class GenieEvaluator:
         stream = torch.cuda.current_stream().cuda_stream
         sizes = (float(B * (T - 1) * S), float(B * (T - 1)), float(B))
         m._cond(action_ids, B)   # (argument errors before anything is enqueued)
+        sampling, unmask_mode = self._sampling()
         for k, t in enumerate(range(1, T)):
             p = ids.clone()
             p[:, t:] = m.mask_token_id
             s, fl = m.maskgit_generate(p, out_t=t, maskgit_steps=self.args.maskgit_steps,
                                        temperature=self.args.temperature,
-                                       noise=None if noise is None else noise[k], check=False, action_ids=action_ids)
+                                       noise=None if noise is None else noise[k], check=False, action_ids=action_ids,
+                                       sampling=sampling, unmask_mode=unmask_mode)
             # fl is a permuted view of the contiguous (B, V, H, W) step-0 logits of frame t
             lg = fl.permute(0, 2, 1, 3, 4)
             assert lg.is_contiguous()

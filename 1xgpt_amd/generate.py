@@ -17,11 +17,13 @@ STRIDE = 15
 
 @torch.no_grad()
 def generate_frames(model, example_THW: torch.LongTensor, num_prompt_frames=8, maskgit_steps=2, temperature=0.0,
-                    teacher_force_time=False, noise=None, action_ids=None):
+                    teacher_force_time=False, noise=None, action_ids=None, sampling=None, unmask_mode="random", uniforms=None):
     """example_THW (B, T, H, W) on the model's device -> outputs (B, T + (T - num_prompt_frames), H, W):
     [prompt frames | predicted frames | ground-truth frames] (generate.py:97-103).
     noise: optional (T - num_prompt_frames, maskgit_steps-1, B, S).
-    action_ids: (B, T) per-frame actions of an action-conditioned model (config.action_vocab_size > 0)."""
+    action_ids: (B, T) per-frame actions of an action-conditioned model (config.action_vocab_size > 0).
+    sampling: a SamplingConfig (1xgpt_amd/sampling.py) or None = the reference's law; unmask_mode: "random" (the reference's
+    harness), "greedy" or "confidence"; uniforms: optional (T - num_prompt_frames, maskgit_steps, num_factored_vocabs, B, S)."""
     window_size = example_THW.shape[1]
     assert num_prompt_frames <= window_size
     example_THW = example_THW.to(torch.int64).contiguous()
@@ -34,7 +36,8 @@ def generate_frames(model, example_THW: torch.LongTensor, num_prompt_frames=8, m
             prompt_THW[:, timestep:] = model.mask_token_id
         samples_HW, _ = model.maskgit_generate(prompt_THW, out_t=timestep, maskgit_steps=maskgit_steps,
                                                temperature=temperature, noise=None if noise is None else noise[k],
-                                               return_logits=False, action_ids=action_ids)
+                                               return_logits=False, action_ids=action_ids, sampling=sampling,
+                                               unmask_mode=unmask_mode, uniforms=None if uniforms is None else uniforms[k])
         samples.append(samples_HW)
         if not teacher_force_time:
             prompt_THW[:, timestep] = samples_HW  # autoregressive (already written in place by maskgit_generate)
@@ -46,7 +49,7 @@ def generate_frames(model, example_THW: torch.LongTensor, num_prompt_frames=8, m
 @torch.no_grad()
 def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_frames=8, maskgit_steps=2, temperature=0.0,
                            teacher_force_time=False, noise=None, unmask_mode="random", merge_commit=True, host_loop=False,
-                           action_ids=None):
+                           action_ids=None, sampling=None, uniforms=None):
     """``generate_frames`` with a temporal KV cache (genie_frame_pass): every pass runs ONE frame through the stack
     against the cached temporal keys/values of the earlier frames instead of the full 16-frame forward --
     one P-frame pass for the prompt + (T-P)*(steps+1) single-frame passes (= 2 full-pass equivalents at P=8, steps=2) instead of (T-P)*steps full
@@ -56,10 +59,20 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
     host_loop: False = the whole loop is ONE library call (genie_generate_cached: every pass, sampling and mask step enqueued
     without a host step in between); True = the same loop driven from Python (one C-ABI call per pass / sample / mask step).
     action_ids: (B, T) per-frame actions of an action-conditioned model (config.action_vocab_size > 0); every pass embeds
-    frame t with action_ids[:, t]."""
+    frame t with action_ids[:, t].
+    sampling: a SamplingConfig or None = the reference's law; unmask_mode may be "confidence" (both as in maskgit_generate);
+    uniforms: optional (T - num_prompt_frames, maskgit_steps, num_factored_vocabs, B, S) sampling draws to replay."""
     import math
     from . import _lib
+    from .sampling import SamplingConfig, as_struct, unmask_code
     lib = _lib.load()
+    mode = unmask_code(unmask_mode)
+    law = as_struct(sampling)
+    if mode == _lib.UNMASK_CONFIDENCE and law is None:
+        law = as_struct(SamplingConfig())
+    nv = model.config.num_factored_vocabs
+    if uniforms is not None:
+        uniforms = uniforms.to(device=example_THW.device, dtype=torch.float32).contiguous()
     cfg, w = model._weights()[:2]
     ex = example_THW.to(torch.int64).contiguous()
     B, T = ex.shape[0], ex.shape[1]
@@ -76,16 +89,17 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
 
     if not host_loop and P < T:
         steps = int(maskgit_steps)
-        if unmask_mode not in ("random", "greedy"):
-            raise NotImplementedError(f"Expected `unmask_mode` to be one of ['greedy', 'random'], got {unmask_mode}")
         nz = None
-        if steps > 1 and unmask_mode == "random":   # the draws of torch.rand_like (st_mask_git.py:204-206): the caller's, or fresh ones
+        if steps > 1 and unmask_mode != "greedy":   # the draws of torch.rand_like (st_mask_git.py:204-206): the caller's, or fresh ones
             nz = (torch.rand(T - P, steps - 1, B, S, device=dev) if noise is None
                   else noise.to(dev)[:, :steps - 1].reshape(T - P, steps - 1, B, S).float().contiguous())
-        uni = torch.rand(T - P, steps, model.config.num_factored_vocabs, B, S, device=dev) if temperature > 1e-8 else None
+        uni = None
+        if temperature > 1e-8:
+            uni = torch.rand(T - P, steps, nv, B, S, device=dev) if uniforms is None else uniforms
+            assert uni.numel() == (T - P) * steps * nv * B * S, "uniforms: (T - P, maskgit_steps, num_factored_vocabs, B, S)"
         gen = torch.empty(B, T - P, S, dtype=torch.int64, device=dev)
-        _lib.check(_lib.call_cond(lib, "genie_generate_cached", cond, cfg, w, ids.data_ptr(), B, P, T - P, steps, float(temperature),
-                                             _lib.UNMASK_GREEDY if unmask_mode == "greedy" else _lib.UNMASK_RANDOM,
+        _lib.check(_lib.call_ex(lib, "genie_generate_cached", cond, law, cfg, w, ids.data_ptr(), B, P, T - P, steps, float(temperature),
+                                             mode,
                                              0 if nz is None else nz.data_ptr(), 0 if uni is None else uni.data_ptr(),
                                              int(bool(teacher_force_time)), int(bool(merge_commit)), gen.data_ptr(), 0, cache.data_ptr(),
                                              nbytes, ws.data_ptr(), ws.numel(), st), "genie_generate_cached")
@@ -135,10 +149,10 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
         for step in range(maskgit_steps):
             if not (step == 0 and opened):
                 frame_pass(cur, t, logits)
-            uni = torch.rand(model.config.num_factored_vocabs, B, S, device=dev) if temperature > 1e-8 else None
-            _lib.check(lib.genie_sample(cfg, logits.data_ptr(), _lib.LAYOUT_TOKEN_MAJOR, B, float(temperature),
-                                        0 if uni is None else uni.data_ptr(), samples.data_ptr(), conf.data_ptr(), st),
-                       "genie_sample")
+            uni = None
+            if temperature > 1e-8:
+                uni = (torch.rand(nv, B, S, device=dev) if uniforms is None
+                       else uniforms.view(T - P, maskgit_steps, nv, B, S)[k, step].contiguous())
             last = step == maskgit_steps - 1
             keys, n = None, 0
             if not last:
@@ -149,6 +163,17 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
                     keys = torch.rand(B, S, device=dev)
                 else:
                     keys = noise[k][step].to(dev).reshape(B, S).float().contiguous()
+            by_conf = mode == _lib.UNMASK_CONFIDENCE and not last
+            if law is None:
+                _lib.check(lib.genie_sample(cfg, logits.data_ptr(), _lib.LAYOUT_TOKEN_MAJOR, B, float(temperature),
+                                            0 if uni is None else uni.data_ptr(), samples.data_ptr(), conf.data_ptr(), st),
+                           "genie_sample")
+            else:   # "confidence": the same launch turns the step's draws into its keys
+                draws, keys = keys, (torch.empty(B, S, device=dev) if by_conf else keys)
+                _lib.check(lib.genie_sample_ex(cfg, logits.data_ptr(), _lib.LAYOUT_TOKEN_MAJOR, B, float(temperature),
+                                               0 if uni is None else uni.data_ptr(), samples.data_ptr(), conf.data_ptr(), st, law,
+                                               keys.data_ptr() if by_conf else 0, draws.data_ptr() if by_conf else 0,
+                                               1.0 - (step + 1) / maskgit_steps), "genie_sample_ex")
             _lib.check(lib.genie_mask_step(0 if keys is None else keys.data_ptr(), n, int(last), model.mask_token_id,
                                            unmasked.data_ptr(), samples.data_ptr(), cur.data_ptr(), S, B, S, st),
                        "genie_mask_step")

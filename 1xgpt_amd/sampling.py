@@ -1,0 +1,88 @@
+"""The sampling law of the MaskGIT decoder: logit temperature, top-k, top-p, and the "confidence" unmasking mode's
+choice temperature (genie_sampling in include/genie_hip.h, which states the semantics).
+
+A departure from the reference: its ``temperature`` only switches arg-max to sampling (st_mask_git.py:184-186 builds
+``Categorical(probs=probs / temperature)``, which renormalises) and it has no filter.  ``sampling=None`` everywhere means the
+reference's behaviour, bit for bit.
+"""
+import math
+from dataclasses import dataclass
+
+UNMASK_MODES = ("random", "greedy", "confidence")
+
+
+@dataclass
+class SamplingConfig:
+    logit_temperature: float = 1.0   # tau > 0: z = logit / tau (1 = off)
+    top_k: int = 0                   # keep the k best entries of each factored vocabulary (0 = off)
+    top_p: float = 1.0               # ... then the smallest prefix of them whose mass reaches top_p (>= 1 or <= 0 = off)
+    choice_temperature: float = 4.5  # c >= 0 of unmask_mode="confidence": key = log(conf) + c * (1 - (step+1)/steps) * gumbel
+
+    def __post_init__(self):
+        self.validate()
+
+    def validate(self):
+        tau, k, p, c = self.logit_temperature, self.top_k, self.top_p, self.choice_temperature
+        if isinstance(k, bool) or int(k) != k:
+            raise ValueError(f"top_k must be an integer, got {k!r}")
+        if not (isinstance(tau, (int, float)) and math.isfinite(tau) and tau > 0):
+            raise ValueError(f"logit_temperature must be positive and finite, got {tau!r}")
+        if k < 0:
+            raise ValueError(f"top_k must be >= 0, got {k!r}")
+        if not isinstance(p, (int, float)) or math.isnan(p):
+            raise ValueError(f"top_p must be a number, got {p!r}")
+        if not (isinstance(c, (int, float)) and c >= 0):
+            raise ValueError(f"choice_temperature must be >= 0, got {c!r}")
+        return self
+
+    def is_neutral(self, factored_vocab_size=None):
+        """True when the law filters and tempers nothing (the library then runs the reference's kernels)."""
+        k_off = self.top_k == 0 or (factored_vocab_size is not None and self.top_k >= factored_vocab_size)
+        return self.logit_temperature == 1.0 and k_off and not (0.0 < self.top_p < 1.0)
+
+    def to_struct(self):
+        """The ctypes genie_sampling of this law."""
+        from . import _lib
+        self.validate()
+        return _lib.Sampling(logit_temperature=float(self.logit_temperature), top_k=int(self.top_k), top_p=float(self.top_p),
+                             choice_temperature=float(self.choice_temperature))
+
+    @classmethod
+    def from_args(cls, args):
+        """From an argparse / SimpleNamespace carrying any of the four fields (missing ones take the defaults); None when the
+        namespace names none of them."""
+        names = ("logit_temperature", "top_k", "top_p", "choice_temperature")
+        given = {n: getattr(args, n) for n in names if getattr(args, n, None) is not None}
+        return cls(**given) if given else None
+
+
+def as_struct(sampling):
+    """None -> None (the unchanged entry points); a SamplingConfig -> its genie_sampling."""
+    if sampling is None:
+        return None
+    if not isinstance(sampling, SamplingConfig):
+        raise ValueError(f"sampling must be a SamplingConfig or None, got {type(sampling).__name__}")
+    return sampling.to_struct()
+
+
+def unmask_code(unmask_mode):
+    from . import _lib
+    if unmask_mode not in UNMASK_MODES:
+        raise NotImplementedError(f"Expected `unmask_mode` to be one of ['greedy', 'random', 'confidence'], got {unmask_mode}")
+    return {"random": _lib.UNMASK_RANDOM, "greedy": _lib.UNMASK_GREEDY, "confidence": _lib.UNMASK_CONFIDENCE}[unmask_mode]
+
+
+def add_cli_arguments(parser):
+    """--logit_temperature / --top_k / --top_p / --unmask_mode / --choice_temperature for tools/generate.py and tools/evaluate.py."""
+    parser.add_argument("--logit_temperature", type=float, default=None,
+                        help="Divide the logits by this before the softmax (> 0). This is the flag that tempers; "
+                             "--temperature is the reference's switch between arg-max and sampling and does not.")
+    parser.add_argument("--top_k", type=int, default=None, help="Sample among the k most likely entries of each factored vocabulary.")
+    parser.add_argument("--top_p", type=float, default=None,
+                        help="Nucleus sampling: the smallest set of most likely entries whose mass reaches this.")
+    parser.add_argument("--unmask_mode", default="random", choices=list(UNMASK_MODES),
+                        help="Which tokens a MaskGIT step re-masks: random draws, lowest confidence (greedy), or confidence plus "
+                             "annealed Gumbel noise (confidence).")
+    parser.add_argument("--choice_temperature", type=float, default=None,
+                        help="Scale of the annealed Gumbel noise of --unmask_mode confidence (default 4.5).")
+    return parser

@@ -46,6 +46,7 @@ enum { GENIE_LAYOUT_TOKEN_MAJOR = 0, /* (B, nt, S, V)              */
        GENIE_LAYOUT_BCTHW = 1        /* (B, V, nt, S) == "B C T H W" (st_mask_git.py:264) */ };
 
 enum { GENIE_UNMASK_RANDOM = 0, GENIE_UNMASK_GREEDY = 1 }; /* st_mask_git.py:200-209 */
+enum { GENIE_UNMASK_CONFIDENCE = 2 }; /* no reference counterpart: confidence + annealed Gumbel noise (genie_sampling below) */
 
 /* GenieConfig (genie/config.py:7-55) reduced to what the kernels need. */
 typedef struct genie_cfg {
@@ -133,7 +134,31 @@ typedef struct genie_frame_cond {
     int32_t n_actions;
 } genie_frame_cond;
 
+/* The sampling law of the MaskGIT decoder (ABI 3 addition; NULL = every field off = the reference's behaviour, bit for bit).
+ * Departure from the reference: st_mask_git.py:184-186 builds Categorical(probs=probs / temperature), which renormalises, so
+ * its `temperature` only switches arg-max to sampling and there is no top-k or nucleus filter.  Here, per token and per factored
+ * vocabulary (most significant first):
+ *   z_i = logit_i * (1.0f / logit_temperature)                                     -- one f32 multiply; off at 1
+ *   top_k: keep i iff #{j : z_j > z_i or (z_j == z_i and j < i)} < top_k             -- stable rank by count; off at 0 or >= factored_vocab
+ *   top_p: among those survivors in that rank order, keep i iff the probability mass (softmax of z over the survivors) of the
+ *          survivors ranked strictly before i is < top_p; the best entry is always kept   -- off at >= 1 (and <= 0)
+ * temperature > 1e-8 draws by the inverse CDF in index order over the kept entries on the caller's uniform (pick = #{kept prefix
+ * sums < u * total}, the last kept entry at most); temperature <= 1e-8 takes the arg-max, which no filter changes.  The
+ * confidence is the picked entry's probability under the TEMPERED, UNFILTERED softmax (top_k = 1 does not report 1 everywhere).
+ * choice_temperature c >= 0 belongs to GENIE_UNMASK_CONFIDENCE (the MaskGIT paper's schedule, which the reference lacks; its
+ * docstring notes that greedy unmasking "tends to copy the previous frame"): at step `step` of `steps` the re-masking key of a
+ * token is log(conf) + c * (1 - (step + 1) / steps) * g, g = -log(-log(u)), u = the caller's U[0,1) draw of the `noise` array the
+ * random mode takes (same shape), clamped to [2^-24, 1 - 2^-24]; the keys go through genie_mask_step unchanged. */
+typedef struct genie_sampling {
+    float logit_temperature;  /* tau > 0 */
+    int32_t top_k;            /* >= 0 */
+    float top_p;
+    float choice_temperature; /* c >= 0 */
+} genie_sampling;
+
 int genie_version(void);
+/* sizeof(genie_sampling) and the offsets of its four fields, in declaration order: writes min(n, 5) entries, returns 5. */
+int genie_sampling_layout(size_t* out_host, int n);
 /* The compiler's view of the POD structs above, for bindings to check their own declarations against (tests/test_abi_and_host.py):
  * out[0..8) = sizeof(genie_cfg), sizeof(genie_attn_weights), offsetof(.., fused_w16), offsetof(.., w16_wide),
  * sizeof(genie_layer_weights), offsetof(.., mlp_fused_w16), offsetof(.., w16_wide), sizeof(genie_weights),
@@ -362,6 +387,13 @@ int genie_generate_cached_cond(const genie_cfg* cfg, const genie_weights* w, con
                                int teacher_force_time, int merge_commit, int64_t* gen_out, float* logits0_out, float* cache,
                                size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
                                const genie_frame_cond* cond);
+/* The same under a genie_sampling law (NULL = genie_generate_cached_cond); accepts GENIE_UNMASK_CONFIDENCE, whose draws are
+ * `noise` (n_new, steps - 1, B, S), required when steps > 1.  The reference's generate has no counterpart of either. */
+int genie_generate_cached_ex(const genie_cfg* cfg, const genie_weights* w, const int64_t* ids, int B, int P, int n_new,
+                             int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                             int teacher_force_time, int merge_commit, int64_t* gen_out, float* logits0_out, float* cache,
+                             size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
+                             const genie_frame_cond* cond, const genie_sampling* sampling);
 /* f32 (N, K) row-major weight -> split f16 in FRAGMENT ORDER (2 N K 16-bit values) for the one-frame kernels
  * (csrc/kernels_frame.hip): blocks of 32 rows x 64 k, per block [plane hi | lo'][MFMA step 0..3] fragments of 1 KB = the 64 lanes'
  * 16-byte operand pieces (lane 32 h + r: row r, k = 16 step + 8 h .. + 7), so that every operand load of those kernels is a
@@ -406,6 +438,16 @@ int genie_readout_ce(const genie_cfg* cfg, const genie_weights* w, const float* 
 int genie_sample(const genie_cfg* cfg, const float* logits, int layout, int B, float temperature,
                  const float* uniforms, int64_t* samples, float* conf, void* stream);
 
+/* genie_sample under a genie_sampling law (above).  sampling NULL or all-off and keys_out NULL: genie_sample itself.
+ *   keys_out (B,S) float32 or NULL: the GENIE_UNMASK_CONFIDENCE key of every token, log(conf) + sampling->choice_temperature *
+ *   anneal * g(noise), written by the same launch; needs noise (B,S) float32 U[0,1); anneal = 1 - (step + 1) / steps.
+ *   keys_out may be the conf pointer itself: then only the keys are written.
+ * Argument errors (logit_temperature <= 0 or not finite, top_k < 0, NaN top_p, choice_temperature < 0 or NaN, keys_out without
+ * noise) return GENIE_E_ARG before anything is enqueued.  Reference counterpart: none beyond st_mask_git.py:171-190. */
+int genie_sample_ex(const genie_cfg* cfg, const float* logits, int layout, int B, float temperature, const float* uniforms,
+                    int64_t* samples, float* conf, void* stream, const genie_sampling* sampling, float* keys_out,
+                    const float* noise, float anneal);
+
 /* MaskGIT mask half for one step (st_mask_git.py:192-223), one frame of B clips.
  *   keys (B,S) float32: caller's torch.rand draws ("random") or conf ("greedy"); ignored if last_step
  *   n: tokens to re-mask (ceil(cos(pi/2 (step+1)/steps) S)); unmasked (B,S) uint8 in/out;
@@ -428,6 +470,13 @@ int genie_maskgit_generate_cond(const genie_cfg* cfg, const genie_weights* w, in
                                 float temperature, int unmask_mode, const float* noise, const float* uniforms,
                                 int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
                                 void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond);
+/* The same under a genie_sampling law (NULL = genie_maskgit_generate_cond); accepts GENIE_UNMASK_CONFIDENCE, whose draws are
+ * `noise` (steps-1, B, S), required when steps > 1.  The reference has no counterpart of the law or of that mode. */
+int genie_maskgit_generate_ex(const genie_cfg* cfg, const genie_weights* w, int64_t* prompt, int B, int out_t, int steps,
+                              float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                              int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
+                              void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond,
+                              const genie_sampling* sampling);
 
 /* ---- optional per-launch timing (bench.py's roofline leg) ------------------------------------------------
  * When enabled, every launch of a kernel whose class bit is set in `class_mask` is bracketed by a pair of

@@ -18,19 +18,27 @@ sys.path.insert(0, REPO)
 import torch  # noqa: E402
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser(description="Evaluate GENIE-style models (MI355X path).")
     ap.add_argument("--val_data_dir", type=str, default="data/val_v1.1")
     ap.add_argument("--checkpoint_dir", type=str)
     ap.add_argument("--batch_size", type=int, default=16)
     ap.add_argument("--maskgit_steps", type=int, default=2)
-    ap.add_argument("--temperature", type=float, default=0)
+    ap.add_argument("--temperature", type=float, default=0,
+                    help="The reference's switch: 0 = arg-max, any value above 1e-8 = sample from the softmax. It does NOT temper "
+                         "(0.7 and 1.0 draw from the same law); use --logit_temperature, --top_k, --top_p for that.")
+    importlib.import_module("1xgpt_amd.sampling").add_cli_arguments(ap)
     ap.add_argument("--max_examples", type=int)
     ap.add_argument("--precision", choices=["exact", "f16x3", "bf16"], default="f16x3")
     ap.add_argument("--synthetic", type=int, default=0, help="evaluate N synthetic clips with synthetic weights")
     ap.add_argument("--model", choices=["c138", "c35"], default="c35", help="shape for --synthetic")
     ap.add_argument("--no_reuse", action="store_true", help="reference schedule (15 x steps full forwards)")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
+    importlib.import_module("1xgpt_amd.sampling").SamplingConfig.from_args(args)   # (argument errors before the model loads)
 
     ev_mod = importlib.import_module("1xgpt_amd.evaluate")
     dist_mod = importlib.import_module("1xgpt_amd.distributed")

@@ -16,7 +16,7 @@ sys.path.insert(0, REPO)
 import torch  # noqa: E402
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--val_data_dir", type=str, default="data/val_v1.1")
     ap.add_argument("--checkpoint_dir", type=str)
@@ -26,14 +26,22 @@ def main():
     ap.add_argument("--example_ind", type=int, default=0)
     ap.add_argument("--teacher_force_time", action="store_true")
     ap.add_argument("--maskgit_steps", type=int, default=2)
-    ap.add_argument("--temperature", type=float, default=0)
+    ap.add_argument("--temperature", type=float, default=0,
+                    help="The reference's switch: 0 = arg-max, any value above 1e-8 = sample from the softmax. It does NOT temper "
+                         "(0.7 and 1.0 draw from the same law); use --logit_temperature, --top_k, --top_p for that.")
+    importlib.import_module("1xgpt_amd.sampling").add_cli_arguments(ap)
     ap.add_argument("--precision", choices=["exact", "f16x3", "bf16"], default="f16x3")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--model", choices=["c138", "c35"], default="c35")
     ap.add_argument("--schedule", choices=["kv_cache", "full_forward"], default="kv_cache",
                     help="kv_cache: one-frame passes against a temporal KV cache (same frames up to f32 accumulation order); "
                          "full_forward: the reference's schedule, a full 16-frame forward per MaskGIT step (generate.py:81-95)")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
+    sampling = importlib.import_module("1xgpt_amd.sampling").SamplingConfig.from_args(args)
     actions = None
     G = importlib.import_module("1xgpt_amd.generate")
     STMaskGIT = importlib.import_module("1xgpt_amd.st_mask_git").STMaskGIT
@@ -59,7 +67,7 @@ def main():
     ex = example.to("cuda").view(1, args.window_size, model.h, model.w)
     fn = G.generate_frames_cached if args.schedule == "kv_cache" else G.generate_frames
     out = fn(model, ex, args.num_prompt_frames, args.maskgit_steps, args.temperature, args.teacher_force_time,
-             action_ids=None if actions is None else actions.to("cuda"))
+             action_ids=None if actions is None else actions.to("cuda"), sampling=sampling, unmask_mode=args.unmask_mode)
     print(G.write_outputs(out, args.output_dir, meta, vars(args)))
 
 
