@@ -527,11 +527,15 @@ int genie_tokens_from_bits(const float* h, int64_t* ids, int n, int hw, int bits
  *   (no atomics): the same input gives the same bytes on every call.
  * genie_bits_from_tokens_nhwc_bf16: tokens (n_pix) -> (n_pix, cpad) bf16: channel c < bits = +-1 for bit c (a18 in
  *   operand layout), channels >= bits zero (cpad %% 64 == 0 lets conv_in run on the implicit GEMM).
- * genie_rescale_u8_nhwc_bf16: decoder tail: (n, HW, cpad) bf16 -> (n, cout, HW) uint8 with the reference's bf16 rescale. */
+ * genie_rescale_u8_nhwc_bf16: decoder tail: (n, HW, cpad) bf16 -> (n, cout, HW) uint8 with the reference's bf16 rescale.
+ * Tests: tests/test_hip_conv.py holds every entry point of this section to the plain references of tests/conv_reference.py (f64 conv2d /
+ *   matmul / group_norm, bit-exact NumPy tokenizer ends; pinned on the CPU by tests/test_conv_reference_cpu.py) and checks that an image's
+ *   bytes do not depend on the rest of the batch; tests/test_hip_harness.py: the decoder / encoder stacks against the reference's goldens. */
 int genie_pack_conv_weight(const float* w, uint16_t* out, int Cout, int Cin, int taps, void* stream);
 int genie_conv3x3_bf16(const uint16_t* x, const uint16_t* w_packed, const float* bias, const uint16_t* residual, uint16_t* y,
                        const uint16_t* zero_page, int n, int H, int W, int Cin, int Cout, int depth_to_space, void* stream);
-/* The encoder's downsample: 3x3 / pad 1 / stride 2 (improved_model.py:90); H, W are the OUTPUT size, input is (2H, 2W). */
+/* The encoder's downsample: 3x3 / pad 1 / stride 2 (improved_model.py:90); H, W are the OUTPUT size, input is (2H, 2W).
+ * Tests: tests/test_hip_conv.py::test_conv3x3_s2_against_f64. */
 int genie_conv3x3_s2_bf16(const uint16_t* x, const uint16_t* w_packed, const float* bias, uint16_t* y,
                           const uint16_t* zero_page, int n, int H, int W, int Cin, int Cout, void* stream);
 /* Encoder ends: uint8 frames (n, cin, HW) -> (n, HW, cpad) bf16 in [-1,1] (x/127.5 - 1; channels >= cin zero), and the
@@ -552,7 +556,9 @@ int genie_group_norm_swish_bf16(const uint16_t* x, const float* gamma, const flo
  *   C_out %% 128 == 0 and groups of 4, 8 or 16 channels; returns GENIE_E_UNSUPPORTED otherwise
  *   without launching, and the caller uses the separate-statistics path.
  * genie_group_norm_swish_fused_bf16: GroupNorm(groups, eps) [+ swish] of that convolution's output x from its partials:
- *   no statistics pass over x.  H, W, Cout, depth_to_space are the CONVOLUTION's; stats_ws: n * groups * 2 floats. */
+ *   no statistics pass over x.  H, W, Cout, depth_to_space are the CONVOLUTION's; stats_ws: n * groups * 2 floats.
+ * Tests: tests/test_hip_harness.py::test_conv_fused_groupnorm_statistics (against the separate pass and f64 group_norm);
+ *   tests/test_hip_conv.py (same bytes as the plain convolution, refusal without a write, batch invariance). */
 size_t genie_conv_gn_part_floats(int n, int H, int W, int Cout);
 int genie_conv3x3_gn_bf16(const uint16_t* x, const uint16_t* w_packed, const float* bias, const uint16_t* residual, uint16_t* y,
                           const uint16_t* zero_page, int n, int H, int W, int Cin, int Cout, int depth_to_space, int stride,
