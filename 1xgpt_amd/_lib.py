@@ -55,6 +55,11 @@ class Sampling(C.Structure):
     _fields_ = [("logit_temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("choice_temperature", C.c_float)]
 
 
+class Guidance(C.Structure):
+    """genie_guidance: classifier-free guidance scale w and the action-table row of the null action (1xgpt_amd/sampling.py)."""
+    _fields_ = [("scale", C.c_float), ("null_action", C.c_int32)]
+
+
 WIDE_QKV, WIDE_PROJ, WIDE_FC1, WIDE_FC2 = 1, 2, 1, 2          # bits of the w16_wide fields (genie_hip.h)
 FUSED_QKV_STREAM = 4                                        # spatial attention: fused_w16 = [proj stream | qkv stream]
 TEMPORAL_QKV_F16X3_ELEMS = 393216   # f16 values of the f16x3 temporal qkv stream (csrc/kernels_fused_f16x3.hip)
@@ -67,6 +72,7 @@ SIGNATURES = {
     "genie_version": (C.c_int, []),
     "genie_abi_layout": (C.c_int, [C.POINTER(C.c_size_t), C.c_int]),
     "genie_sampling_layout": (C.c_int, [C.POINTER(C.c_size_t), C.c_int]),
+    "genie_guidance_layout": (C.c_int, [C.POINTER(C.c_size_t), C.c_int]),
     "genie_last_error": (C.c_char_p, []),
     "genie_check_config": (C.c_int, [C.POINTER(GenieCfg)]),
     "genie_workspace_bytes": (C.c_size_t, [C.POINTER(GenieCfg), C.c_int]),
@@ -99,6 +105,8 @@ SIGNATURES = {
     "genie_frames_pass": (C.c_int, [C.POINTER(GenieCfg), C.POINTER(Weights), c_ptr, C.c_int, C.c_int, C.c_int, c_ptr, C.c_size_t,
                                     c_ptr, c_ptr, C.c_size_t, c_ptr]),
     "genie_generate_workspace_bytes": (C.c_size_t, [C.POINTER(GenieCfg), C.c_int, C.c_int]),
+    "genie_generate_guided_workspace_bytes": (C.c_size_t, [C.POINTER(GenieCfg), C.c_int, C.c_int]),
+    "genie_guide_logits": (C.c_int, [c_ptr, c_ptr, c_ptr, C.c_size_t, C.c_float, c_ptr]),
     "genie_generate_cached": (C.c_int, [C.POINTER(GenieCfg), C.POINTER(Weights), c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                         C.c_int, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, c_ptr, c_ptr, C.c_size_t, c_ptr, C.c_size_t, c_ptr]),
     "genie_pack_frame_w16": (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, c_ptr]),
@@ -186,6 +194,13 @@ for _n in ("genie_maskgit_generate", "genie_generate_cached"):
     SIGNATURES[_n + "_ex"] = (SIGNATURES[_n][0], SIGNATURES[_n + "_cond"][1] + [C.POINTER(Sampling)])
 del _n
 SIGNATURES["genie_sample_ex"] = (C.c_int, SIGNATURES["genie_sample"][1] + [C.POINTER(Sampling), c_ptr, c_ptr, C.c_float])
+# the *_guided variants: the *_ex arguments + a trailing genie_guidance* (NULL = the *_ex entry point); genie_sample_guided: genie_sample_ex
+# with a second logits pointer (the null logits) after the first and a trailing scale
+for _n in ("genie_maskgit_generate", "genie_generate_cached"):
+    SIGNATURES[_n + "_guided"] = (SIGNATURES[_n][0], SIGNATURES[_n + "_ex"][1] + [C.POINTER(Guidance)])
+del _n
+SIGNATURES["genie_sample_guided"] = (C.c_int, SIGNATURES["genie_sample_ex"][1][:2] + [c_ptr] + SIGNATURES["genie_sample_ex"][1][2:]
+                                     + [C.c_float])
 
 _lib = None
 
@@ -219,6 +234,9 @@ def load():
         mine = [C.sizeof(Sampling)] + [getattr(Sampling, n).offset for n, _ in Sampling._fields_]
         if lib.genie_sampling_layout(lay, 5) != 5 or list(lay) != mine:
             raise RuntimeError(f"genie_sampling layout {list(lay)} != the ctypes declaration {mine}")
+        mine = [C.sizeof(Guidance)] + [getattr(Guidance, n).offset for n, _ in Guidance._fields_]
+        if lib.genie_guidance_layout(lay, 3) != 3 or list(lay)[:3] != mine:
+            raise RuntimeError(f"genie_guidance layout {list(lay)[:3]} != the ctypes declaration {mine}")
         if os.environ.get("GENIE_HIP_LIBRARY") or lib.genie_study_build():
             import sys
             print(f"1xgpt_amd: using {LIB_PATH} (study build: {bool(lib.genie_study_build())}) -- not the shipping library",
@@ -249,6 +267,13 @@ def call_ex(lib, name, cond, sampling, *args):
     if sampling is None:
         return call_cond(lib, name, cond, *args)
     return getattr(lib, name + "_ex")(*args, cond, sampling)
+
+
+def call_guided(lib, name, cond, sampling, guidance, *args):
+    """call_ex when `guidance` is None (the entry points of before, unchanged), else lib.<name>_guided(*args, cond, sampling, guidance)."""
+    if guidance is None:
+        return call_ex(lib, name, cond, sampling, *args)
+    return getattr(lib, name + "_guided")(*args, cond, sampling, guidance)
 
 
 def make_cfg(config, precision=PREC_EXACT) -> GenieCfg:

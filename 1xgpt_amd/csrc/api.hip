@@ -279,6 +279,15 @@ static int check_unmask(int unmask_mode, bool ex, int steps, const float* noise,
                     unmask_mode == GENIE_UNMASK_CONFIDENCE ? "confidence" : "random");
     return GENIE_OK;
 }
+// a genie_guidance (NULL = none) and the condition it needs, checked on the host before anything is enqueued
+static int check_guidance(const genie_guidance* g, const genie_frame_cond* cond, const char* where) {
+    if (!g) return GENIE_OK;
+    GENIE_CHECK_ARG(isfinite(g->scale), "%s: guidance: scale %g must be finite", where, (double)g->scale);
+    GENIE_CHECK_ARG(cond && cond->n_actions > 0, "%s: guidance needs an action condition (cond with n_actions > 0)", where);
+    GENIE_CHECK_ARG(g->null_action >= 0 && g->null_action < cond->n_actions, "%s: guidance: null_action %d outside [0, %d)", where,
+                    (int)g->null_action, (int)cond->n_actions);
+    return GENIE_OK;
+}
 // the confidence mode's scale when the caller gave no law: the documented default of choice_temperature
 static const genie_sampling kDefaultSampling = {1.0f, 0, 1.0f, 4.5f};
 
@@ -299,6 +308,11 @@ int genie_sampling_layout(size_t* out_host, int n) {
                          offsetof(genie_sampling, top_p), offsetof(genie_sampling, choice_temperature)};
     for (int i = 0; i < n && i < 5 && out_host; ++i) out_host[i] = v[i];
     return 5;
+}
+int genie_guidance_layout(size_t* out_host, int n) {
+    const size_t v[3] = {sizeof(genie_guidance), offsetof(genie_guidance, scale), offsetof(genie_guidance, null_action)};
+    for (int i = 0; i < n && i < 3 && out_host; ++i) out_host[i] = v[i];
+    return 3;
 }
 const char* genie_last_error(void) { return g_err; }
 int genie_check_config(const genie_cfg* cfg) { return check_cfg(cfg); }
@@ -627,17 +641,32 @@ int genie_frame_linear(const uint16_t* a_fr, const uint16_t* w_fr, const float* 
     return launch_frame_linear(a_fr, w_fr, bias, y, M, N, K, mode, as_stream(stream));
 }
 
-// rows of S token ids: dst[b][0..S) = src[b][0..S) (clip strides in elements) or, src == NULL, the fill value
+// rows of S token ids: dst[b][0..S) = src[b][0..S) (clip strides in elements) or, src == NULL, the fill value; `copies` > 1 repeats the
+// B rows at dst rows B .. 2B - 1, ... (the doubled batch of the guided loops)
 __global__ void frame_ids_kernel(const int64_t* __restrict__ src, long src_stride, int64_t* __restrict__ dst, long dst_stride, int S, int B,
-                                 int64_t fill) {
+                                 int64_t fill, int copies) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)B * S) return;
-    const long b = i / S, s = i - b * S;
-    dst[b * dst_stride + s] = src ? src[b * src_stride + s] : fill;
+    const long per = (long)B * S;
+    if (i >= per * copies) return;
+    const long r = i / per, j = i - r * per;
+    const long b = j / S, s = j - b * S;
+    dst[(r * B + b) * dst_stride + s] = src ? src[b * src_stride + s] : fill;
 }
-static int put_frame_ids(const int64_t* src, long src_stride, int64_t* dst, long dst_stride, int S, int B, int64_t fill, hipStream_t st) {
-    frame_ids_kernel<<<(unsigned)(((long)B * S + 255) / 256), 256, 0, st>>>(src, src_stride, dst, dst_stride, S, B, fill);
+static int put_frame_ids(const int64_t* src, long src_stride, int64_t* dst, long dst_stride, int S, int B, int64_t fill, hipStream_t st,
+                         int copies = 1) {
+    frame_ids_kernel<<<(unsigned)(((long)B * S * copies + 255) / 256), 256, 0, st>>>(src, src_stride, dst, dst_stride, S, B, fill, copies);
     GENIE_LAUNCH_CHECK("frame_ids");
+    return GENIE_OK;
+}
+// the (2B, T) actions of a guided pass: the clips' own ids, then null_action at every frame
+__global__ void guided_actions_kernel(const int64_t* __restrict__ ids, int64_t* __restrict__ out, long n, int64_t null_action) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 2 * n) out[i] = i < n ? ids[i] : null_action;
+}
+static int put_guided_actions(const genie_frame_cond& cond, const genie_guidance& g, int B, int T, int64_t* out, hipStream_t st) {
+    const long n = (long)B * T;
+    guided_actions_kernel<<<(unsigned)((2 * n + 255) / 256), 256, 0, st>>>(cond.ids, out, n, g.null_action);
+    GENIE_LAUNCH_CHECK("guided_actions");
     return GENIE_OK;
 }
 
@@ -648,12 +677,57 @@ static size_t generate_scratch_offset(const genie_cfg& c, int B, int P) {
     return carve(cm, B, nullptr).total;
 }
 
+// The loop scratch of genie_generate_cached_*: B clips are decoded, NB clips run through every pass (NB == B, or 2 B under guidance:
+// [conditional ; null]).  The size functions and the loop both carve here (base == NULL: sizes only).
+struct GenScratch {
+    int64_t *idsP, *two, *cur, *fin, *samples, *acts;
+    float *conf, *logits;
+    uint8_t* unmasked;
+    size_t end;
+};
+static GenScratch carve_generate(const genie_cfg& c, int B, int NB, int P, char* base) {
+    const size_t BS = (size_t)B * c.S, NBS = (size_t)NB * c.S, V = (size_t)c.factored_vocab * c.num_factored;
+    size_t off = generate_scratch_offset(c, NB, P);
+    auto take = [&](size_t bytes) { char* r = base ? base + off : nullptr; off += align_up(bytes, 256); return r; };
+    GenScratch g;
+    g.idsP = (int64_t*)take(NBS * P * 8);
+    g.two = (int64_t*)take(NBS * 2 * 8);
+    g.cur = (int64_t*)take(NBS * 8);
+    g.fin = (int64_t*)take(NBS * 8);
+    g.samples = (int64_t*)take(BS * 8);
+    g.conf = (float*)take(BS * 4);
+    g.unmasked = (uint8_t*)take(BS);
+    g.logits = (float*)take(NBS * V * 4);
+    g.acts = NB != B ? (int64_t*)take((size_t)NB * c.T * 8) : nullptr;
+    g.end = off;
+    return g;
+}
+// ... of genie_maskgit_generate_guided behind the model's workspace for 2 B clips: the doubled prompt and the (2B, T) actions
+struct GuidedPrompt {
+    int64_t *prompt2, *acts;
+    size_t end;
+};
+static GuidedPrompt carve_guided_prompt(const genie_cfg& c, int NB, char* base) {
+    size_t off = carve(c, NB, nullptr).total;
+    auto take = [&](size_t bytes) { char* r = base ? base + off : nullptr; off += align_up(bytes, 256); return r; };
+    GuidedPrompt g;
+    g.prompt2 = (int64_t*)take((size_t)NB * c.T * c.S * 8);
+    g.acts = (int64_t*)take((size_t)NB * c.T * 8);
+    g.end = off;
+    return g;
+}
+
 size_t genie_generate_workspace_bytes(const genie_cfg* cfg, int B, int P) {
     if (check_cfg(cfg) != GENIE_OK || B < 1 || P < 1 || P > cfg->T) return 0;
-    const size_t BS = (size_t)B * cfg->S, V = (size_t)cfg->factored_vocab * cfg->num_factored;
-    size_t off = generate_scratch_offset(*cfg, B, P);
-    for (size_t bytes : {BS * P * 8, BS * 2 * 8, BS * 8, BS * 8, BS * 8, BS * 4, BS, BS * V * 4}) off += align_up(bytes, 256);
+    const size_t off = carve_generate(*cfg, B, B, P, nullptr).end;
     const size_t full = carve(*cfg, B, nullptr).total;   // (the passes themselves check against the model's own workspace size)
+    return off > full ? off : full;
+}
+
+size_t genie_generate_guided_workspace_bytes(const genie_cfg* cfg, int B, int P) {
+    if (check_cfg(cfg) != GENIE_OK || B < 1 || B > 0x3fffffff || P < 1 || P > cfg->T) return 0;
+    const size_t off = carve_generate(*cfg, B, 2 * B, P, nullptr).end;
+    const size_t full = carve_guided_prompt(*cfg, 2 * B, nullptr).end;   // (>= the model's own workspace for 2 B clips)
     return off > full ? off : full;
 }
 
@@ -677,15 +751,17 @@ int genie_generate_cached_cond(const genie_cfg* cfg, const genie_weights* wt, co
                                     nullptr);
 }
 
-int genie_generate_cached_ex(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int P, int n_new,
-                             int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
-                             int teacher_force_time, int merge_commit, int64_t* gen_out, float* logits0_out, float* cache,
-                             size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
-                             const genie_frame_cond* cond, const genie_sampling* sampling) {
+// genie_generate_cached_ex (guidance NULL or of scale 1) and genie_generate_cached_guided: one loop, B clips decoded, NB per pass
+static int generate_cached_loop(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int P, int n_new,
+                                int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                                int teacher_force_time, int merge_commit, int64_t* gen_out, float* logits0_out, float* cache,
+                                size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
+                                const genie_frame_cond* cond, const genie_sampling* sampling, const genie_guidance* guidance) {
     GENIE_TRY(check_cfg(cfg));
     const genie_cfg& c = *cfg;
     GENIE_CHECK_ARG(wt && wt->layers_host && ids && gen_out && cache, "generate_cached: NULL pointer");
     GENIE_TRY(check_frame_cond(cond, "generate_cached"));
+    GENIE_TRY(check_guidance(guidance, cond, "generate_cached"));
     GENIE_CHECK_ARG(B >= 1 && P >= 1 && n_new >= 1 && P + n_new <= c.T && steps >= 1,
                     "generate_cached: B=%d, %d prompt + %d new frames of at most %d, steps %d", B, P, n_new, c.T, steps);
     GENIE_TRY(check_sampling(sampling, "generate_cached"));
@@ -693,40 +769,47 @@ int genie_generate_cached_ex(const genie_cfg* cfg, const genie_weights* wt, cons
     GENIE_CHECK_ARG(temperature <= 1e-8f || uniforms, "generate_cached: temperature > 0 needs uniforms");
     const bool by_conf = unmask_mode == GENIE_UNMASK_CONFIDENCE;
     const genie_sampling* law = (by_conf && !sampling) ? &kDefaultSampling : sampling;
-    GENIE_CHECK_ARG(cache_bytes >= genie_prefix_cache_bytes(cfg, B), "generate_cached: cache too small");
-    GENIE_TRY(check_ws(c, B, workspace, workspace_bytes));
+    // under guidance every pass runs 2 B clips, [conditional ; null]: rows b and b + B hold the same tokens, the second half's actions are
+    // null_action at every frame; B rows are sampled, masked and written out
+    const bool guided = guidance && guidance->scale != 1.0f;
+    GENIE_CHECK_ARG(!guided || B <= 0x3fffffff, "generate_cached: B=%d too large for guidance", B);
+    const int NB = guided ? 2 * B : B, copies = guided ? 2 : 1;
+    GENIE_CHECK_ARG(cache_bytes >= genie_prefix_cache_bytes(cfg, NB), "generate_cached: cache too small");
+    GENIE_TRY(check_ws(c, NB, workspace, workspace_bytes));
     hipStream_t st = as_stream(stream);
     const int S = c.S, T = P + n_new;   // frames per clip in `ids` (the cache keeps the model's c.T slots per clip)
     const size_t BS = (size_t)B * S, V = (size_t)c.factored_vocab * c.num_factored;
     // scratch of the loop behind the workspace of its largest pass (the prompt's P frames; two frames for the merged passes):
-    // genie_generate_workspace_bytes(cfg, B, P) is the size to allocate
-    char* base = (char*)workspace;
-    size_t off = generate_scratch_offset(c, B, P);
-    auto take = [&](size_t bytes) { char* r = base + off; off += align_up(bytes, 256); return r; };
-    int64_t* idsP = (int64_t*)take(BS * P * 8);
-    int64_t* two = (int64_t*)take(BS * 2 * 8);
-    int64_t* cur = (int64_t*)take(BS * 8);
-    int64_t* fin = (int64_t*)take(BS * 8);
-    int64_t* samples = (int64_t*)take(BS * 8);
-    float* conf = (float*)take(BS * 4);
-    uint8_t* unmasked = (uint8_t*)take(BS);
-    float* logits = (float*)take(BS * V * 4);
-    GENIE_CHECK_ARG(off <= workspace_bytes, "generate_cached: workspace too small (%zu < %zu bytes: size it with genie_generate_workspace_bytes)",
-                    workspace_bytes, off);
+    // genie_generate_workspace_bytes / genie_generate_guided_workspace_bytes (cfg, B, P) is the size to allocate
+    const GenScratch g = carve_generate(c, B, NB, P, (char*)workspace);
+    GENIE_CHECK_ARG(g.end <= workspace_bytes, "generate_cached: workspace too small (%zu < %zu bytes: size it with %s)", workspace_bytes,
+                    g.end, guided ? "genie_generate_guided_workspace_bytes" : "genie_generate_workspace_bytes");
+    int64_t *idsP = g.idsP, *two = g.two, *cur = g.cur, *fin = g.fin, *samples = g.samples;
+    float *conf = g.conf, *logits = g.logits;
+    uint8_t* unmasked = g.unmasked;
+    genie_frame_cond cond2;
+    if (guided) {
+        GENIE_TRY(put_guided_actions(*cond, *guidance, B, c.T, g.acts, st));
+        cond2 = *cond;
+        cond2.ids = g.acts;
+        cond = &cond2;
+    }
+    const float* logits_null = logits + BS * V;   // guided: rows B .. 2B - 1 of every pass's logits
 
     // ---- the prompt fills cache slots 0 .. P-1: one P-frame pass where the fragment-order kernels cover it, else the clean pass
     // with the cache's T-frame layout, else frame by frame
-    for (int t = 0; t < P; ++t) GENIE_TRY(put_frame_ids(ids + (size_t)t * S, (long)T * S, idsP + (size_t)t * S, (long)P * S, S, B, 0, st));
+    for (int t = 0; t < P; ++t)
+        GENIE_TRY(put_frame_ids(ids + (size_t)t * S, (long)T * S, idsP + (size_t)t * S, (long)P * S, S, B, 0, st, copies));
     int rc = GENIE_E_UNSUPPORTED;
     if (P > 1) {
-        rc = genie_frames_pass_cond(cfg, wt, idsP, B, 0, P, cache, cache_bytes, nullptr, workspace, workspace_bytes, stream, cond);
+        rc = genie_frames_pass_cond(cfg, wt, idsP, NB, 0, P, cache, cache_bytes, nullptr, workspace, workspace_bytes, stream, cond);
         if (rc == GENIE_E_UNSUPPORTED)
-            rc = genie_clean_pass_cond(cfg, wt, idsP, B, P, c.T, cache, cache_bytes, workspace, workspace_bytes, stream, cond);
+            rc = genie_clean_pass_cond(cfg, wt, idsP, NB, P, c.T, cache, cache_bytes, workspace, workspace_bytes, stream, cond);
     }
     if (rc == GENIE_E_UNSUPPORTED) {
         for (int t = 0; t < P; ++t) {
-            GENIE_TRY(put_frame_ids(ids + (size_t)t * S, (long)T * S, fin, S, S, B, 0, st));
-            GENIE_TRY(genie_frames_pass_cond(cfg, wt, fin, B, t, 1, cache, cache_bytes, nullptr, workspace, workspace_bytes, stream, cond));
+            GENIE_TRY(put_frame_ids(ids + (size_t)t * S, (long)T * S, fin, S, S, B, 0, st, copies));
+            GENIE_TRY(genie_frames_pass_cond(cfg, wt, fin, NB, t, 1, cache, cache_bytes, nullptr, workspace, workspace_bytes, stream, cond));
         }
     } else {
         GENIE_TRY(rc);
@@ -734,14 +817,17 @@ int genie_generate_cached_ex(const genie_cfg* cfg, const genie_weights* wt, cons
     bool opened = false, merge = merge_commit != 0;
     for (int k = 0; k < n_new; ++k) {
         const int t = P + k;
-        GENIE_TRY(put_frame_ids(nullptr, 0, cur, S, S, B, c.image_vocab_size, st));
+        GENIE_TRY(put_frame_ids(nullptr, 0, cur, S, S, B, c.image_vocab_size, st, copies));
         if (hipMemsetAsync(unmasked, 0, BS, st) != hipSuccess) { set_error("memset failed"); return GENIE_E_LAUNCH; }
         for (int step = 0; step < steps; ++step) {
             if (!(step == 0 && opened))
-                GENIE_TRY(genie_frames_pass_cond(cfg, wt, cur, B, t, 1, cache, cache_bytes, logits, workspace, workspace_bytes, stream, cond));
+                GENIE_TRY(genie_frames_pass_cond(cfg, wt, cur, NB, t, 1, cache, cache_bytes, logits, workspace, workspace_bytes, stream, cond));
             if (step == 0 && logits0_out) {   // orig_logits of the frame (st_mask_git.py:165,226): the step-0 logits, (B, n_new, S, V)
-                if (hipMemcpy2DAsync(logits0_out + (size_t)k * S * V, (size_t)n_new * S * V * 4, logits, (size_t)S * V * 4, (size_t)S * V * 4,
-                                     (size_t)B, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+                if (guided) {                 // ... the guided ones
+                    GENIE_TRY(launch_guide_logits(logits, logits_null, logits0_out + (size_t)k * S * V, B, (long)(S * V), (long)(S * V),
+                                                  (long)((size_t)n_new * S * V), guidance->scale, st));
+                } else if (hipMemcpy2DAsync(logits0_out + (size_t)k * S * V, (size_t)n_new * S * V * 4, logits, (size_t)S * V * 4,
+                                            (size_t)S * V * 4, (size_t)B, hipMemcpyDeviceToDevice, st) != hipSuccess) {
                     set_error("memcpy failed");
                     return GENIE_E_LAUNCH;
                 }
@@ -750,10 +836,16 @@ int genie_generate_cached_ex(const genie_cfg* cfg, const genie_weights* wt, cons
             const bool last = step == steps - 1;
             const float* draws = (last || unmask_mode == GENIE_UNMASK_GREEDY) ? nullptr : noise + ((size_t)k * (steps - 1) + step) * BS;
             // "confidence": the sample launch writes the keys over conf (nothing else reads conf in this loop)
-            GENIE_TRY(launch_sample_ex(c, logits, GENIE_LAYOUT_TOKEN_MAJOR, B, temperature, u, samples, conf, law,
-                                       (by_conf && !last) ? conf : nullptr, draws, 1.0f - (float)(step + 1) / (float)steps, st));
+            const float anneal = 1.0f - (float)(step + 1) / (float)steps;
+            if (guided)
+                GENIE_TRY(launch_sample_guided(c, logits, logits_null, GENIE_LAYOUT_TOKEN_MAJOR, B, temperature, u, samples, conf, law,
+                                               (by_conf && !last) ? conf : nullptr, draws, anneal, guidance->scale, st));
+            else
+                GENIE_TRY(launch_sample_ex(c, logits, GENIE_LAYOUT_TOKEN_MAJOR, B, temperature, u, samples, conf, law,
+                                           (by_conf && !last) ? conf : nullptr, draws, anneal, st));
             const float* keys = last ? nullptr : (unmask_mode == GENIE_UNMASK_RANDOM ? draws : conf);
             GENIE_TRY(launch_mask_step(keys, last ? 0 : mask_count(step, steps, S), last, c.image_vocab_size, unmasked, samples, cur, S, B, S, st));
+            if (guided) GENIE_TRY(put_frame_ids(cur, S, cur + BS, S, S, B, 0, st));   // the null half sees the same tokens
         }
         GENIE_TRY(put_frame_ids(cur, S, gen_out + (size_t)k * S, (long)n_new * S, S, B, 0, st));
         opened = false;
@@ -761,19 +853,37 @@ int genie_generate_cached_ex(const genie_cfg* cfg, const genie_weights* wt, cons
             const int64_t* fsrc = teacher_force_time ? ids + (size_t)t * S : cur;
             const long fstride = teacher_force_time ? (long)T * S : S;
             if (merge) {   // ... in the pass that also carries MaskGIT step 0 of frame t + 1 (all-mask tokens)
-                GENIE_TRY(put_frame_ids(fsrc, fstride, two, 2L * S, S, B, 0, st));
-                GENIE_TRY(put_frame_ids(nullptr, 0, two + S, 2L * S, S, B, c.image_vocab_size, st));
-                rc = genie_frames_pass_cond(cfg, wt, two, B, t, 2, cache, cache_bytes, logits, workspace, workspace_bytes, stream, cond);
+                GENIE_TRY(put_frame_ids(fsrc, fstride, two, 2L * S, S, B, 0, st, copies));
+                GENIE_TRY(put_frame_ids(nullptr, 0, two + S, 2L * S, S, B, c.image_vocab_size, st, copies));
+                rc = genie_frames_pass_cond(cfg, wt, two, NB, t, 2, cache, cache_bytes, logits, workspace, workspace_bytes, stream, cond);
                 if (rc == GENIE_E_UNSUPPORTED) merge = false;
                 else { GENIE_TRY(rc); opened = true; }
             }
             if (!opened) {
-                GENIE_TRY(put_frame_ids(fsrc, fstride, fin, S, S, B, 0, st));
-                GENIE_TRY(genie_frames_pass_cond(cfg, wt, fin, B, t, 1, cache, cache_bytes, nullptr, workspace, workspace_bytes, stream, cond));
+                GENIE_TRY(put_frame_ids(fsrc, fstride, fin, S, S, B, 0, st, copies));
+                GENIE_TRY(genie_frames_pass_cond(cfg, wt, fin, NB, t, 1, cache, cache_bytes, nullptr, workspace, workspace_bytes, stream, cond));
             }
         }
     }
     return GENIE_OK;
+}
+
+int genie_generate_cached_ex(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int P, int n_new,
+                             int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                             int teacher_force_time, int merge_commit, int64_t* gen_out, float* logits0_out, float* cache,
+                             size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
+                             const genie_frame_cond* cond, const genie_sampling* sampling) {
+    return generate_cached_loop(cfg, wt, ids, B, P, n_new, steps, temperature, unmask_mode, noise, uniforms, teacher_force_time, merge_commit,
+                                gen_out, logits0_out, cache, cache_bytes, workspace, workspace_bytes, stream, cond, sampling, nullptr);
+}
+
+int genie_generate_cached_guided(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int P, int n_new,
+                                 int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                                 int teacher_force_time, int merge_commit, int64_t* gen_out, float* logits0_out, float* cache,
+                                 size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
+                                 const genie_frame_cond* cond, const genie_sampling* sampling, const genie_guidance* guidance) {
+    return generate_cached_loop(cfg, wt, ids, B, P, n_new, steps, temperature, unmask_mode, noise, uniforms, teacher_force_time, merge_commit,
+                                gen_out, logits0_out, cache, cache_bytes, workspace, workspace_bytes, stream, cond, sampling, guidance);
 }
 
 int genie_pack_frame_w16(const float* src, uint16_t* dst, int N, int K, void* stream) {
@@ -832,6 +942,28 @@ int genie_sample_ex(const genie_cfg* cfg, const float* logits, int layout, int B
                             (keys_out && !sampling) ? &kDefaultSampling : sampling, keys_out, noise, anneal, as_stream(stream));
 }
 
+int genie_sample_guided(const genie_cfg* cfg, const float* logits_cond, const float* logits_null, int layout, int B, float temperature,
+                        const float* uniforms, int64_t* samples, float* conf, void* stream, const genie_sampling* sampling,
+                        float* keys_out, const float* noise, float anneal, float scale) {
+    GENIE_CHECK_ARG(isfinite(scale), "sample_guided: scale %g must be finite", (double)scale);
+    if (scale == 1.0f)
+        return genie_sample_ex(cfg, logits_cond, layout, B, temperature, uniforms, samples, conf, stream, sampling, keys_out, noise, anneal);
+    GENIE_TRY(check_cfg(cfg));
+    GENIE_CHECK_ARG(logits_cond && logits_null && samples && conf && B >= 1, "sample_guided: bad argument");
+    GENIE_CHECK_ARG(temperature <= 1e-8f || uniforms, "sample_guided: temperature > 0 needs caller-supplied uniforms");
+    GENIE_TRY(check_sampling(sampling, "sample_guided"));
+    GENIE_CHECK_ARG(!keys_out || noise, "sample_guided: keys_out needs the caller's U[0,1) noise draws");
+    GENIE_CHECK_ARG(!keys_out || anneal == anneal, "sample_guided: anneal is NaN");
+    return launch_sample_guided(*cfg, logits_cond, logits_null, layout, B, temperature, uniforms, samples, conf,
+                                (keys_out && !sampling) ? &kDefaultSampling : sampling, keys_out, noise, anneal, scale, as_stream(stream));
+}
+
+int genie_guide_logits(const float* cond, const float* null_logits, float* out, size_t n, float scale, void* stream) {
+    GENIE_CHECK_ARG(isfinite(scale), "guide_logits: scale %g must be finite", (double)scale);
+    GENIE_CHECK_ARG(cond && null_logits && out && n <= (size_t)0x7fffffffffffffffLL, "guide_logits: bad argument");
+    return launch_guide_logits(cond, null_logits, out, 1, (long)n, 0, 0, scale, as_stream(stream));
+}
+
 int genie_mask_step(const float* keys, int n, int last_step, int64_t mask_id, uint8_t* unmasked, int64_t* samples,
                     int64_t* prompt_frame, int64_t prompt_clip_stride, int B, int S, void* stream) {
     GENIE_CHECK_ARG(unmasked && samples && prompt_frame && B >= 1 && S >= 1, "mask_step: bad argument");
@@ -858,15 +990,17 @@ int genie_maskgit_generate_cond(const genie_cfg* cfg, const genie_weights* wt, i
                                      logits0_out, layout, status_flag, workspace, workspace_bytes, stream, cond, nullptr);
 }
 
-int genie_maskgit_generate_ex(const genie_cfg* cfg, const genie_weights* wt, int64_t* prompt, int B, int out_t, int steps,
-                              float temperature, int unmask_mode, const float* noise, const float* uniforms,
-                              int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
-                              void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond,
-                              const genie_sampling* sampling) {
+// genie_maskgit_generate_ex (guidance NULL or of scale 1) and genie_maskgit_generate_guided: one loop, B clips decoded, NB per forward
+static int maskgit_generate_loop(const genie_cfg* cfg, const genie_weights* wt, int64_t* prompt, int B, int out_t, int steps,
+                                 float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                                 int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
+                                 void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond,
+                                 const genie_sampling* sampling, const genie_guidance* guidance) {
     GENIE_TRY(check_cfg(cfg));
     const genie_cfg& c = *cfg;
     GENIE_CHECK_ARG(wt && wt->layers_host && prompt && samples_out, "maskgit_generate: NULL pointer");
     GENIE_TRY(check_frame_cond(cond, "maskgit_generate"));
+    GENIE_TRY(check_guidance(guidance, cond, "maskgit_generate"));
     if (!(out_t >= 1 && out_t < c.T)) {  // assert out_t  (st_mask_git.py:154)
         set_error("maskgit_generate requires 0 < out_t < T (got %d)", out_t);
         return GENIE_E_ASSERT;
@@ -877,36 +1011,64 @@ int genie_maskgit_generate_ex(const genie_cfg* cfg, const genie_weights* wt, int
     GENIE_CHECK_ARG(temperature <= 1e-8f || uniforms, "maskgit_generate: temperature > 0 needs uniforms");
     const bool by_conf = unmask_mode == GENIE_UNMASK_CONFIDENCE;
     const genie_sampling* law = (by_conf && !sampling) ? &kDefaultSampling : sampling;
-    GENIE_TRY(check_ws(c, B, workspace, workspace_bytes));
-    Workspace w = carve(c, B, workspace);
+    // under guidance every forward runs 2 B clips, [conditional ; null], on a doubled copy of the prompt behind the workspace
+    const bool guided = guidance && guidance->scale != 1.0f;
+    GENIE_CHECK_ARG(!guided || B <= 0x3fffffff, "maskgit_generate: B=%d too large for guidance", B);
+    const int NB = guided ? 2 * B : B;
+    GENIE_TRY(check_ws(c, NB, workspace, workspace_bytes));
+    Workspace w = carve(c, NB, workspace);
     hipStream_t st = as_stream(stream);
     const size_t BS = (size_t)B * c.S;
     const long V = (long)c.factored_vocab * c.num_factored;
+    const long clip = (long)c.T * c.S;
+    const int64_t* tokens = prompt;   // what every forward embeds
+    genie_frame_cond cond2;
+    if (guided) {
+        const GuidedPrompt gp = carve_guided_prompt(c, NB, (char*)workspace);
+        GENIE_CHECK_ARG(gp.end <= workspace_bytes, "maskgit_generate: workspace too small (%zu < %zu bytes: size it with "
+                        "genie_generate_guided_workspace_bytes)", workspace_bytes, gp.end);
+        GENIE_TRY(put_guided_actions(*cond, *guidance, B, c.T, gp.acts, st));
+        cond2 = *cond;
+        cond2.ids = gp.acts;
+        cond = &cond2;
+        GENIE_TRY(put_frame_ids(prompt, clip, gp.prompt2, clip, (int)clip, B, 0, st, 2));
+        tokens = gp.prompt2;
+    }
+    // guided: the null half of the frame's logits, and room behind both halves for the guided step-0 logits (w.logits holds T >= 2 frames)
+    const float* logits_null = w.logits + BS * V;
+    float* logits_g = w.logits + 2 * BS * V;
 
     GENIE_TRY(launch_check_masked(prompt, B, c.T, c.S, out_t, c.image_vocab_size, status_flag, st));
     if (hipMemsetAsync(w.unmasked, 0, BS, st) != hipSuccess) { set_error("memset failed"); return GENIE_E_LAUNCH; }
     EmbedAct act;
     const EmbedAct* pact = frame_act(cond, c.S, 0, c.T, act);
     for (int step = 0; step < steps; ++step) {
-        GENIE_TRY(launch_embed(c, *wt, prompt, B, w.x, st, pact));
-        GENIE_TRY(decoder(c, *wt, w.x, w, B, st));
-        GENIE_TRY(readout(c, *wt, w.x, w, B, out_t, out_t + 1, GENIE_LAYOUT_TOKEN_MAJOR, w.logits, st));
-        if (step == 0 && logits0_out) {  // orig_logits_CHW: step-0 logits are what is returned (:165,226)
-            if (layout == GENIE_LAYOUT_TOKEN_MAJOR) {
-                if (hipMemcpyAsync(logits0_out, w.logits, BS * V * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        GENIE_TRY(launch_embed(c, *wt, tokens, NB, w.x, st, pact));
+        GENIE_TRY(decoder(c, *wt, w.x, w, NB, st));
+        GENIE_TRY(readout(c, *wt, w.x, w, NB, out_t, out_t + 1, GENIE_LAYOUT_TOKEN_MAJOR, w.logits, st));
+        if (step == 0 && logits0_out) {  // orig_logits_CHW: step-0 logits are what is returned (:165,226); the guided ones under guidance
+            const bool tm = layout == GENIE_LAYOUT_TOKEN_MAJOR;
+            if (guided) GENIE_TRY(launch_guide_logits(w.logits, logits_null, tm ? logits0_out : logits_g, 1, (long)(BS * V), 0, 0, guidance->scale, st));
+            if (tm) {
+                if (!guided && hipMemcpyAsync(logits0_out, w.logits, BS * V * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
                     set_error("memcpy failed");
                     return GENIE_E_LAUNCH;
                 }
             } else {
-                GENIE_TRY(launch_transpose(w.logits, logits0_out, B, c.S, (int)V, st));
+                GENIE_TRY(launch_transpose(guided ? logits_g : w.logits, logits0_out, B, c.S, (int)V, st));
             }
         }
         const float* u = (temperature > 1e-8f) ? uniforms + (size_t)step * c.num_factored * BS : nullptr;
         const int last = (step == steps - 1);
         const float* draws = (last || unmask_mode == GENIE_UNMASK_GREEDY) ? nullptr : noise + (size_t)step * BS;
         // "confidence": the sample launch writes the keys over conf (nothing else reads conf in this loop)
-        GENIE_TRY(launch_sample_ex(c, w.logits, GENIE_LAYOUT_TOKEN_MAJOR, B, temperature, u, w.samples, w.conf, law,
-                                   (by_conf && !last) ? w.conf : nullptr, draws, 1.0f - (float)(step + 1) / (float)steps, st));
+        const float anneal = 1.0f - (float)(step + 1) / (float)steps;
+        if (guided)
+            GENIE_TRY(launch_sample_guided(c, w.logits, logits_null, GENIE_LAYOUT_TOKEN_MAJOR, B, temperature, u, w.samples, w.conf, law,
+                                           (by_conf && !last) ? w.conf : nullptr, draws, anneal, guidance->scale, st));
+        else
+            GENIE_TRY(launch_sample_ex(c, w.logits, GENIE_LAYOUT_TOKEN_MAJOR, B, temperature, u, w.samples, w.conf, law,
+                                       (by_conf && !last) ? w.conf : nullptr, draws, anneal, st));
         const float* keys = nullptr;
         int n = 0;
         if (!last) {
@@ -914,13 +1076,33 @@ int genie_maskgit_generate_ex(const genie_cfg* cfg, const genie_weights* wt, int
             keys = (unmask_mode == GENIE_UNMASK_RANDOM) ? draws : w.conf;
         }
         GENIE_TRY(launch_mask_step(keys, n, last, c.image_vocab_size, w.unmasked, w.samples,
-                                   prompt + (size_t)out_t * c.S, (long)c.T * c.S, B, c.S, st));
+                                   prompt + (size_t)out_t * c.S, clip, B, c.S, st));
+        if (guided && !last)   // both halves of the next forward see the frame's current tokens
+            GENIE_TRY(put_frame_ids(prompt + (size_t)out_t * c.S, clip, const_cast<int64_t*>(tokens) + (size_t)out_t * c.S, clip, c.S, B, 0, st, 2));
     }
     if (hipMemcpyAsync(samples_out, w.samples, BS * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) {
         set_error("memcpy failed");
         return GENIE_E_LAUNCH;
     }
     return GENIE_OK;
+}
+
+int genie_maskgit_generate_ex(const genie_cfg* cfg, const genie_weights* wt, int64_t* prompt, int B, int out_t, int steps,
+                              float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                              int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
+                              void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond,
+                              const genie_sampling* sampling) {
+    return maskgit_generate_loop(cfg, wt, prompt, B, out_t, steps, temperature, unmask_mode, noise, uniforms, samples_out, logits0_out, layout,
+                                 status_flag, workspace, workspace_bytes, stream, cond, sampling, nullptr);
+}
+
+int genie_maskgit_generate_guided(const genie_cfg* cfg, const genie_weights* wt, int64_t* prompt, int B, int out_t, int steps,
+                                  float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                                  int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
+                                  void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond,
+                                  const genie_sampling* sampling, const genie_guidance* guidance) {
+    return maskgit_generate_loop(cfg, wt, prompt, B, out_t, steps, temperature, unmask_mode, noise, uniforms, samples_out, logits0_out, layout,
+                                 status_flag, workspace, workspace_bytes, stream, cond, sampling, guidance);
 }
 
 int genie_profile_enable(int class_mask) {

@@ -175,6 +175,13 @@ bool sampling_is_neutral(const genie_sampling* sp, int vf);
 int launch_sample_ex(const genie_cfg& c, const float* logits, int layout, int B, float temperature, const float* uniforms,
                      int64_t* samples, float* conf, const genie_sampling* sp, float* keys_out, const float* noise, float anneal,
                      hipStream_t st);
+// ... under classifier-free guidance (genie_guidance): logits g = (scale * cond) + ((1 - scale) * null) formed at load time; scale == 1
+// is launch_sample_ex on the conditional logits.  launch_guide_logits materialises g for `rows` rows of `len` values (row strides in elements).
+int launch_sample_guided(const genie_cfg& c, const float* logits_c, const float* logits_u, int layout, int B, float temperature,
+                         const float* uniforms, int64_t* samples, float* conf, const genie_sampling* sp, float* keys_out,
+                         const float* noise, float anneal, float scale, hipStream_t st);
+int launch_guide_logits(const float* cond, const float* null_, float* out, long rows, long len, long in_stride, long out_stride, float scale,
+                        hipStream_t st);
 int launch_mask_step(const float* keys, int n, int last_step, int64_t mask_id, uint8_t* unmasked, int64_t* samples,
                      int64_t* prompt_frame, long clip_stride, int B, int S, hipStream_t st);
 int launch_check_masked(const int64_t* prompt, int B, int T, int S, int out_t, int64_t mask_id, int32_t* flag,

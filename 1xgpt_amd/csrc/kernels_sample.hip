@@ -15,6 +15,10 @@
 //
 // The two flavours share every line but the fetch: Rows keeps the 64 * PER token-major values of a factor in registers
 // (16-byte loads, one read of the logits), Strided re-reads them per pass through the layout's strides (any vocabulary size).
+//
+// Classifier-free guidance (genie_guidance, genie_sample_guided) is a third and a fourth fetch: the Guided flavours read the
+// conditional and the null row of the same token and form g = (w * c) + ((1 - w) * u) -- three separately rounded f32 operations --
+// where the unguided ones read one logit; everything from z = g * (1 / tau) on is the code above, in the same launch.
 #include "kernels.hpp"
 
 // the per-entry loops ask for unrolling: complete in the Rows flavour (compile-time trip count, values in registers); in the
@@ -99,6 +103,46 @@ struct StridedVals {   // any layout, any vocabulary size: memory
     __device__ __forceinline__ bool valid(int q) const { return lane * n_per + q < vf; }
     __device__ __forceinline__ int idx(int q) const { return lane * n_per + q; }
     __device__ __forceinline__ float z(int q) const { return lf[(size_t)(lane * n_per + q) * vstride] * inv_tau; }
+};
+
+// guided logit: g = (w * c) + (omw * u), omw = 1.0f - w from the host; three roundings, never an FMA
+struct Guide {
+    float w, omw;
+};
+__device__ __forceinline__ float guide(float c, float u, Guide g) { return __fadd_rn(__fmul_rn(g.w, c), __fmul_rn(g.omw, u)); }
+
+template <int PER>
+struct GuidedRowsVals {   // RowsVals on two rows: two 16-byte loads per four entries, combined into the same registers
+    float zr[PER];
+    int lane;
+    __device__ __forceinline__ void load(const float* lc, const float* lu, Guide g, float inv_tau) {
+#pragma unroll
+        for (int q = 0; q < PER; q += 4) {
+            const f32x4s a = *reinterpret_cast<const f32x4s*>(lc + lane * PER + q);
+            const f32x4s b = *reinterpret_cast<const f32x4s*>(lu + lane * PER + q);
+            zr[q] = guide(a.x, b.x, g) * inv_tau; zr[q + 1] = guide(a.y, b.y, g) * inv_tau;
+            zr[q + 2] = guide(a.z, b.z, g) * inv_tau; zr[q + 3] = guide(a.w, b.w, g) * inv_tau;
+        }
+    }
+    __device__ __forceinline__ int per() const { return PER; }
+    __device__ __forceinline__ bool valid(int) const { return true; }
+    __device__ __forceinline__ int idx(int q) const { return lane * PER + q; }
+    __device__ __forceinline__ float z(int q) const { return zr[q]; }
+};
+struct GuidedStridedVals {   // StridedVals on two bases with the same strides
+    const float* lc;
+    const float* lu;
+    long vstride;
+    int lane, vf, n_per;
+    float inv_tau;
+    Guide g;
+    __device__ __forceinline__ int per() const { return n_per; }
+    __device__ __forceinline__ bool valid(int q) const { return lane * n_per + q < vf; }
+    __device__ __forceinline__ int idx(int q) const { return lane * n_per + q; }
+    __device__ __forceinline__ float z(int q) const {
+        const size_t o = (size_t)(lane * n_per + q) * vstride;
+        return guide(lc[o], lu[o], g) * inv_tau;
+    }
 };
 
 // survivors of top-k: key above the threshold, or equal to it and among the first `room` such entries in index order
@@ -349,8 +393,95 @@ __global__ __launch_bounds__(256) void sample_filtered_kernel(const float* __res
     }
 }
 
+// the two kernels above with the guided fetch: token n of the B * S reads row n of both logits tensors
+template <int PER>
+__global__ __launch_bounds__(256) void sample_guided_rows_kernel(const float* __restrict__ logits_c, const float* __restrict__ logits_u,
+                                                                 Guide g, long n_tok, long V, int vf, int nfac, float temperature,
+                                                                 SampleFilter f, const float* __restrict__ uniforms,
+                                                                 int64_t* __restrict__ samples, float* conf, float* keys_out,
+                                                                 const float* __restrict__ noise, float key_scale) {
+    static_assert(PER % 4 == 0, "16-byte loads");
+    const int lane = threadIdx.x & 63;
+    const long n = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= n_tok) return;
+    const float* lc = logits_c + (size_t)n * V;
+    const float* lu = logits_u + (size_t)n * V;
+    const bool draw = temperature > 1e-8f;
+    int64_t sample = 0;
+    float cf = 1.0f;
+    for (int k = 0; k < nfac; ++k) {
+        const int fac = nfac - 1 - k;
+        GuidedRowsVals<PER> X;
+        X.lane = lane;
+        X.load(lc + (size_t)fac * vf, lu + (size_t)fac * vf, g, f.inv_tau);
+        int pick;
+        float p;
+        sample_factor(X, lane, vf, draw, f, draw ? uniforms[(size_t)k * n_tok + n] : 0.f, pick, p);
+        sample = sample * vf + pick;
+        cf *= p;
+    }
+    if (lane == 0) {
+        samples[n] = sample;
+        if (keys_out != conf) conf[n] = cf;
+        if (keys_out) keys_out[n] = confidence_key(cf, noise[n], key_scale);
+    }
+}
+
+__global__ __launch_bounds__(256) void sample_guided_kernel(const float* __restrict__ logits_c, const float* __restrict__ logits_u, Guide g,
+                                                            long tok_stride_b, long tok_stride_s, long vstride, int B, int S, int vf,
+                                                            int nfac, float temperature, SampleFilter f,
+                                                            const float* __restrict__ uniforms, int64_t* __restrict__ samples, float* conf,
+                                                            float* keys_out, const float* __restrict__ noise, float key_scale) {
+    const int lane = threadIdx.x & 63;
+    const long n = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= (long)B * S) return;
+    const long b = n / S, s = n - b * S;
+    const size_t tok = (size_t)b * tok_stride_b + (size_t)s * tok_stride_s;
+    const bool draw = temperature > 1e-8f;
+    int64_t sample = 0;
+    float cf = 1.0f;
+    for (int k = 0; k < nfac; ++k) {
+        const int fac = nfac - 1 - k;
+        const size_t o = tok + (size_t)fac * vf * vstride;
+        const GuidedStridedVals X{logits_c + o, logits_u + o, vstride, lane, vf, (vf + 63) / 64, f.inv_tau, g};
+        int pick;
+        float p;
+        sample_factor(X, lane, vf, draw, f, draw ? uniforms[((size_t)k * B + b) * S + s] : 0.f, pick, p);
+        sample = sample * vf + pick;
+        cf *= p;
+    }
+    if (lane == 0) {
+        samples[n] = sample;
+        if (keys_out != conf) conf[n] = cf;
+        if (keys_out) keys_out[n] = confidence_key(cf, noise[n], key_scale);
+    }
+}
+
+// out[r][i] = guide(cond[r][i], null[r][i]) for `rows` rows of `len` values (row strides in elements): the guided step-0 logits
+__global__ __launch_bounds__(256) void guide_logits_kernel(const float* __restrict__ cond, const float* __restrict__ null_, float* __restrict__ out,
+                                                           long rows, long len, long in_stride, long out_stride, Guide g) {
+    const long total = rows * len;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long r = i / len, j = i - r * len;
+        out[r * out_stride + j] = guide(cond[r * in_stride + j], null_[r * in_stride + j], g);
+    }
+}
+
 bool sampling_is_neutral(const genie_sampling* sp, int vf) {
     return !sp || (sp->logit_temperature == 1.0f && (sp->top_k <= 0 || sp->top_k >= vf) && !(sp->top_p > 0.f && sp->top_p < 1.f));
+}
+
+// the kernels' view of a law (NULL = every field off) and the scale of the confidence-mode key
+static SampleFilter make_filter(const genie_sampling* sp, int vf, float anneal, float& key_scale) {
+    SampleFilter f{1.0f, 0, 1.0f};
+    key_scale = 0.f;
+    if (sp) {
+        f.inv_tau = 1.0f / sp->logit_temperature;
+        f.top_k = (sp->top_k > 0 && sp->top_k < vf) ? sp->top_k : 0;
+        f.top_p = (sp->top_p > 0.f && sp->top_p < 1.f) ? sp->top_p : 1.0f;
+        key_scale = sp->choice_temperature * anneal;
+    }
+    return f;
 }
 
 int launch_sample_ex(const genie_cfg& c, const float* logits, int layout, int B, float temperature, const float* uniforms,
@@ -359,14 +490,8 @@ int launch_sample_ex(const genie_cfg& c, const float* logits, int layout, int B,
     const int vf = c.factored_vocab;
     if (sampling_is_neutral(sp, vf) && !keys_out)   // today's kernels, bit for bit
         return launch_sample(c, logits, layout, B, temperature, uniforms, samples, conf, st);
-    SampleFilter f{1.0f, 0, 1.0f};
-    float key_scale = 0.f;
-    if (sp) {
-        f.inv_tau = 1.0f / sp->logit_temperature;
-        f.top_k = (sp->top_k > 0 && sp->top_k < vf) ? sp->top_k : 0;
-        f.top_p = (sp->top_p > 0.f && sp->top_p < 1.f) ? sp->top_p : 1.0f;
-        key_scale = sp->choice_temperature * anneal;
-    }
+    float key_scale;
+    const SampleFilter f = make_filter(sp, vf, anneal, key_scale);
     const long V = (long)vf * c.num_factored, n = (long)B * c.S;
     if (layout == GENIE_LAYOUT_TOKEN_MAJOR && vf == 512 && ((uintptr_t)logits & 15) == 0) {
         sample_filtered_rows_kernel<8><<<(unsigned)((n + 3) / 4), 256, 0, st>>>(logits, n, V, vf, c.num_factored, temperature, f, uniforms,
@@ -380,6 +505,42 @@ int launch_sample_ex(const genie_cfg& c, const float* logits, int layout, int B,
     sample_filtered_kernel<<<(unsigned)((n + 3) / 4), 256, 0, st>>>(logits, sb, ss, vs, B, c.S, vf, c.num_factored, temperature, f,
                                                                      uniforms, samples, conf, keys_out, noise, key_scale);
     GENIE_LAUNCH_CHECK("sample_filtered");
+    return GENIE_OK;
+}
+
+int launch_sample_guided(const genie_cfg& c, const float* logits_c, const float* logits_u, int layout, int B, float temperature,
+                         const float* uniforms, int64_t* samples, float* conf, const genie_sampling* sp, float* keys_out,
+                         const float* noise, float anneal, float scale, hipStream_t st) {
+    if (scale == 1.0f)   // g = c: the unguided launch, the null logits are not read
+        return launch_sample_ex(c, logits_c, layout, B, temperature, uniforms, samples, conf, sp, keys_out, noise, anneal, st);
+    const int vf = c.factored_vocab;
+    float key_scale;
+    const SampleFilter f = make_filter(sp, vf, anneal, key_scale);
+    const Guide g{scale, 1.0f - scale};
+    const long V = (long)vf * c.num_factored, n = (long)B * c.S;
+    if (layout == GENIE_LAYOUT_TOKEN_MAJOR && vf == 512 && (((uintptr_t)logits_c | (uintptr_t)logits_u) & 15) == 0) {
+        sample_guided_rows_kernel<8><<<(unsigned)((n + 3) / 4), 256, 0, st>>>(logits_c, logits_u, g, n, V, vf, c.num_factored, temperature, f,
+                                                                              uniforms, samples, conf, keys_out, noise, key_scale);
+        GENIE_LAUNCH_CHECK("sample_guided_rows");
+        return GENIE_OK;
+    }
+    long sb = (long)c.S * V, ss, vs;
+    if (layout == GENIE_LAYOUT_TOKEN_MAJOR) { ss = V; vs = 1; }
+    else { ss = 1; vs = c.S; }
+    sample_guided_kernel<<<(unsigned)((n + 3) / 4), 256, 0, st>>>(logits_c, logits_u, g, sb, ss, vs, B, c.S, vf, c.num_factored, temperature,
+                                                                   f, uniforms, samples, conf, keys_out, noise, key_scale);
+    GENIE_LAUNCH_CHECK("sample_guided");
+    return GENIE_OK;
+}
+
+int launch_guide_logits(const float* cond, const float* null_, float* out, long rows, long len, long in_stride, long out_stride, float scale,
+                        hipStream_t st) {
+    const long total = rows * len;
+    if (total <= 0) return GENIE_OK;
+    const long blocks = (total + 255) / 256;
+    guide_logits_kernel<<<(unsigned)(blocks < 65536 ? blocks : 65536), 256, 0, st>>>(cond, null_, out, rows, len, in_stride, out_stride,
+                                                                                      Guide{scale, 1.0f - scale});
+    GENIE_LAUNCH_CHECK("guide_logits");
     return GENIE_OK;
 }
 

@@ -131,11 +131,21 @@ class TorchDraws:
         return random.uniform(a, b)
 
 
-def maskgit_collate(input_ids, config, draws=None, action_ids=None):
+def maskgit_collate(input_ids, config, draws=None, action_ids=None, action_dropout=0.0, null_action=None):
     """(B, T*S) int64 clips -> {"input_ids", "labels"} following data.py:112-167 draw for draw.
 
     `draws` replays captured draws (parity tests); None draws fresh ones on the clips' device.  `action_ids` (B, T), if given,
-    are passed through as batch["action_ids"] (int64, on the clips' device) and draw nothing."""
+    are passed through as batch["action_ids"] (int64, on the clips' device) and draw nothing.
+    `action_dropout` > 0 (no reference counterpart) trains the null action of classifier-free guidance: after every other draw, ONE
+    uniform per clip is drawn (draws.rand((B,))) and a clip whose draw is below `action_dropout` gets `null_action` at all T frames.
+    At 0.0 nothing is drawn: the generator state and the batch are those of before."""
+    if not 0.0 <= action_dropout <= 1.0:
+        raise ValueError(f"action_dropout must be in [0, 1], got {action_dropout!r}")
+    if action_dropout > 0.0:
+        if action_ids is None:
+            raise ValueError("action_dropout needs action_ids")
+        if null_action is None or not 0 <= int(null_action) < max(int(config.action_vocab_size), 1):
+            raise ValueError(f"action_dropout needs null_action in [0, {config.action_vocab_size}), got {null_action!r}")
     ids = input_ids.to(torch.int64)
     dev = ids.device
     draws = draws or TorchDraws(dev)
@@ -178,12 +188,17 @@ def maskgit_collate(input_ids, config, draws=None, action_ids=None):
     out = {"input_ids": x.reshape(B, -1), "labels": labels.reshape(B, -1)}
     if action_ids is not None:
         out["action_ids"] = torch.as_tensor(action_ids).to(device=dev, dtype=torch.int64).reshape(B, config.T)
+        if action_dropout > 0.0:
+            drop = t(draws.rand((B,)), torch.float32) < action_dropout
+            out["action_ids"] = torch.where(drop[:, None], int(null_action), out["action_ids"])
     return out
 
 
-def get_maskgit_collator(config):
-    """collate_fn(features: list of {"input_ids": (T*S,) tensor}) -> batch dict, as data.py:109."""
+def get_maskgit_collator(config, action_dropout=0.0, null_action=None):
+    """collate_fn(features: list of {"input_ids": (T*S,) tensor}) -> batch dict, as data.py:109; action_dropout / null_action as in
+    maskgit_collate."""
     def collate_fn(features):
         acts = torch.stack([ex["action_ids"] for ex in features]) if "action_ids" in features[0] else None
-        return maskgit_collate(torch.stack([ex["input_ids"] for ex in features]), config, action_ids=acts)
+        return maskgit_collate(torch.stack([ex["input_ids"] for ex in features]), config, action_ids=acts,
+                               action_dropout=action_dropout, null_action=null_action)
     return collate_fn

@@ -17,13 +17,15 @@ STRIDE = 15
 
 @torch.no_grad()
 def generate_frames(model, example_THW: torch.LongTensor, num_prompt_frames=8, maskgit_steps=2, temperature=0.0,
-                    teacher_force_time=False, noise=None, action_ids=None, sampling=None, unmask_mode="random", uniforms=None):
+                    teacher_force_time=False, noise=None, action_ids=None, sampling=None, unmask_mode="random", uniforms=None,
+                    guidance=None):
     """example_THW (B, T, H, W) on the model's device -> outputs (B, T + (T - num_prompt_frames), H, W):
     [prompt frames | predicted frames | ground-truth frames] (generate.py:97-103).
     noise: optional (T - num_prompt_frames, maskgit_steps-1, B, S).
     action_ids: (B, T) per-frame actions of an action-conditioned model (config.action_vocab_size > 0).
     sampling: a SamplingConfig (1xgpt_amd/sampling.py) or None = the reference's law; unmask_mode: "random" (the reference's
-    harness), "greedy" or "confidence"; uniforms: optional (T - num_prompt_frames, maskgit_steps, num_factored_vocabs, B, S)."""
+    harness), "greedy" or "confidence"; uniforms: optional (T - num_prompt_frames, maskgit_steps, num_factored_vocabs, B, S).
+    guidance: a Guidance(scale, null_action) or None: classifier-free guidance of an action-conditioned model."""
     window_size = example_THW.shape[1]
     assert num_prompt_frames <= window_size
     example_THW = example_THW.to(torch.int64).contiguous()
@@ -37,7 +39,8 @@ def generate_frames(model, example_THW: torch.LongTensor, num_prompt_frames=8, m
         samples_HW, _ = model.maskgit_generate(prompt_THW, out_t=timestep, maskgit_steps=maskgit_steps,
                                                temperature=temperature, noise=None if noise is None else noise[k],
                                                return_logits=False, action_ids=action_ids, sampling=sampling,
-                                               unmask_mode=unmask_mode, uniforms=None if uniforms is None else uniforms[k])
+                                               unmask_mode=unmask_mode, uniforms=None if uniforms is None else uniforms[k],
+                                               guidance=guidance)
         samples.append(samples_HW)
         if not teacher_force_time:
             prompt_THW[:, timestep] = samples_HW  # autoregressive (already written in place by maskgit_generate)
@@ -49,7 +52,7 @@ def generate_frames(model, example_THW: torch.LongTensor, num_prompt_frames=8, m
 @torch.no_grad()
 def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_frames=8, maskgit_steps=2, temperature=0.0,
                            teacher_force_time=False, noise=None, unmask_mode="random", merge_commit=True, host_loop=False,
-                           action_ids=None, sampling=None, uniforms=None):
+                           action_ids=None, sampling=None, uniforms=None, guidance=None):
     """``generate_frames`` with a temporal KV cache (genie_frame_pass): every pass runs ONE frame through the stack
     against the cached temporal keys/values of the earlier frames instead of the full 16-frame forward --
     one P-frame pass for the prompt + (T-P)*(steps+1) single-frame passes (= 2 full-pass equivalents at P=8, steps=2) instead of (T-P)*steps full
@@ -61,7 +64,10 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
     action_ids: (B, T) per-frame actions of an action-conditioned model (config.action_vocab_size > 0); every pass embeds
     frame t with action_ids[:, t].
     sampling: a SamplingConfig or None = the reference's law; unmask_mode may be "confidence" (both as in maskgit_generate);
-    uniforms: optional (T - num_prompt_frames, maskgit_steps, num_factored_vocabs, B, S) sampling draws to replay."""
+    uniforms: optional (T - num_prompt_frames, maskgit_steps, num_factored_vocabs, B, S) sampling draws to replay.
+    guidance: a Guidance(scale, null_action) or None: classifier-free guidance.  Every pass then runs 2 B clips -- the clips under their
+    actions, and the same tokens under null_action at every frame --, genie_sample_guided draws B rows from scale * conditional +
+    (1 - scale) * null, and the frame's current tokens are mirrored into the second half before the next pass (both loop forms)."""
     import math
     from . import _lib
     from .sampling import SamplingConfig, as_struct, unmask_code
@@ -82,8 +88,10 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
     dev = ex.device
     ids = ex.view(B, T, S)
     cond = model._cond(action_ids, B, n_frames=T)
-    ws = model._workspace(B, generate_prompt_frames=P)
-    nbytes = lib.genie_prefix_cache_bytes(cfg, B)
+    guide = model._guidance(guidance)
+    NB = B if guide is None else 2 * B   # clips per pass: [conditional ; null] under guidance
+    ws = model._workspace(B, generate_prompt_frames=P, guided=guide is not None)
+    nbytes = lib.genie_prefix_cache_bytes(cfg, NB)
     cache = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     st = torch.cuda.current_stream().cuda_stream
 
@@ -98,7 +106,7 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
             uni = torch.rand(T - P, steps, nv, B, S, device=dev) if uniforms is None else uniforms
             assert uni.numel() == (T - P) * steps * nv * B * S, "uniforms: (T - P, maskgit_steps, num_factored_vocabs, B, S)"
         gen = torch.empty(B, T - P, S, dtype=torch.int64, device=dev)
-        _lib.check(_lib.call_ex(lib, "genie_generate_cached", cond, law, cfg, w, ids.data_ptr(), B, P, T - P, steps, float(temperature),
+        _lib.check(_lib.call_guided(lib, "genie_generate_cached", cond, law, guide, cfg, w, ids.data_ptr(), B, P, T - P, steps, float(temperature),
                                              mode,
                                              0 if nz is None else nz.data_ptr(), 0 if uni is None else uni.data_ptr(),
                                              int(bool(teacher_force_time)), int(bool(merge_commit)), gen.data_ptr(), 0, cache.data_ptr(),
@@ -106,8 +114,12 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
         outputs = torch.cat([ex[:, :P], gen.view(B, T - P, model.h, model.w)], dim=1)
         return torch.cat([outputs, ex[:, P:]], dim=1)
 
+    if guide is not None:   # the doubled inputs: tokens twice, actions [the clips' ; null_action]
+        cond = model._frame_cond(torch.cat([cond.keep, torch.full_like(cond.keep, guide.null_action)]).contiguous())
+        ids = torch.cat([ids, ids]).contiguous()
+
     def frame_pass(tokens_BS, t, logits=None):
-        _lib.check(_lib.call_cond(lib, "genie_frame_pass", cond, cfg, w, tokens_BS.data_ptr(), B, t, cache.data_ptr(), nbytes,
+        _lib.check(_lib.call_cond(lib, "genie_frame_pass", cond, cfg, w, tokens_BS.data_ptr(), NB, t, cache.data_ptr(), nbytes,
                                   0 if logits is None else logits.data_ptr(), ws.data_ptr(), ws.numel(), st),
                    "genie_frame_pass")
 
@@ -116,7 +128,7 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
         (genie_frames_pass): frame t + 1 attends the slot the same pass writes.  False = the library does not cover two
         frames per pass for this model / batch (nothing was enqueued): the caller runs the two passes one by one."""
         two = torch.stack([final_BS, mask_BS], dim=1).contiguous()
-        rc = _lib.call_cond(lib, "genie_frames_pass", cond, cfg, w, two.data_ptr(), B, t, 2, cache.data_ptr(), nbytes,
+        rc = _lib.call_cond(lib, "genie_frames_pass", cond, cfg, w, two.data_ptr(), NB, t, 2, cache.data_ptr(), nbytes,
                             logits.data_ptr(), ws.data_ptr(), ws.numel(), st)
         if rc == _lib.E_UNSUPPORTED:
             return False
@@ -128,23 +140,23 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
     # slots frame by frame
     rc = _lib.E_UNSUPPORTED
     if P > 1:
-        rc = _lib.call_cond(lib, "genie_frames_pass", cond, cfg, w, ids[:, :P].contiguous().data_ptr(), B, 0, P, cache.data_ptr(),
+        rc = _lib.call_cond(lib, "genie_frames_pass", cond, cfg, w, ids[:, :P].contiguous().data_ptr(), NB, 0, P, cache.data_ptr(),
                             nbytes, 0, ws.data_ptr(), ws.numel(), st)
         if rc == _lib.E_UNSUPPORTED:
-            rc = _lib.call_cond(lib, "genie_clean_pass", cond, cfg, w, ids[:, :P].contiguous().data_ptr(), B, P, T, cache.data_ptr(),
+            rc = _lib.call_cond(lib, "genie_clean_pass", cond, cfg, w, ids[:, :P].contiguous().data_ptr(), NB, P, T, cache.data_ptr(),
                                 nbytes, ws.data_ptr(), ws.numel(), st)
     if rc == _lib.E_UNSUPPORTED:
         for t in range(P):
             frame_pass(ids[:, t].contiguous(), t)
     else:
         _lib.check(rc, "genie_frames_pass / genie_clean_pass (prompt)")
-    logits = torch.empty(B, S, V, dtype=torch.float32, device=dev)
+    logits = torch.empty(NB, S, V, dtype=torch.float32, device=dev)
     samples = torch.empty(B, S, dtype=torch.int64, device=dev)
     conf = torch.empty(B, S, dtype=torch.float32, device=dev)
     gen = []
     opened = False   # step 0 of the current frame already ran inside the previous frame's commit pass
     for k, t in enumerate(range(P, T)):
-        cur = torch.full((B, S), model.mask_token_id, dtype=torch.int64, device=dev)
+        cur = torch.full((NB, S), model.mask_token_id, dtype=torch.int64, device=dev)   # (mask step: rows [0, B))
         unmasked = torch.zeros(B, S, dtype=torch.uint8, device=dev)
         for step in range(maskgit_steps):
             if not (step == 0 and opened):
@@ -164,7 +176,14 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
                 else:
                     keys = noise[k][step].to(dev).reshape(B, S).float().contiguous()
             by_conf = mode == _lib.UNMASK_CONFIDENCE and not last
-            if law is None:
+            if guide is not None:
+                draws, keys = keys, (torch.empty(B, S, device=dev) if by_conf else keys)
+                _lib.check(lib.genie_sample_guided(cfg, logits[:B].data_ptr(), logits[B:].data_ptr(), _lib.LAYOUT_TOKEN_MAJOR, B,
+                                                   float(temperature), 0 if uni is None else uni.data_ptr(), samples.data_ptr(),
+                                                   conf.data_ptr(), st, law, keys.data_ptr() if by_conf else 0,
+                                                   draws.data_ptr() if by_conf else 0, 1.0 - (step + 1) / maskgit_steps, guide.scale),
+                           "genie_sample_guided")
+            elif law is None:
                 _lib.check(lib.genie_sample(cfg, logits.data_ptr(), _lib.LAYOUT_TOKEN_MAJOR, B, float(temperature),
                                             0 if uni is None else uni.data_ptr(), samples.data_ptr(), conf.data_ptr(), st),
                            "genie_sample")
@@ -177,7 +196,9 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
             _lib.check(lib.genie_mask_step(0 if keys is None else keys.data_ptr(), n, int(last), model.mask_token_id,
                                            unmasked.data_ptr(), samples.data_ptr(), cur.data_ptr(), S, B, S, st),
                        "genie_mask_step")
-        gen.append(cur.view(B, model.h, model.w))
+            if guide is not None:
+                cur[B:] = cur[:B]   # the null half sees the same tokens
+        gen.append(cur[:B].view(B, model.h, model.w))
         opened = False
         if t + 1 < T:  # commit frame t (its final tokens, or the ground truth when teacher-forcing in time)
             final = ids[:, t].contiguous() if teacher_force_time else cur

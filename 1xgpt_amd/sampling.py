@@ -56,6 +56,70 @@ class SamplingConfig:
         return cls(**given) if given else None
 
 
+@dataclass
+class Guidance:
+    """Classifier-free guidance of an action-conditioned model (genie_guidance in include/genie_hip.h, which states the arithmetic):
+    logits = scale * conditional + (1 - scale) * null, the null stream being the same tokens under ``null_action`` at every frame."""
+    scale: float          # w, finite: 1 = plain conditional sampling, 0 = the null stream alone, > 1 = guidance
+    null_action: int      # row of the action table that stands for "no action" (learned through action dropout: data.maskgit_collate)
+
+    def __post_init__(self):
+        self.validate()
+
+    def validate(self, action_vocab_size=None):
+        w, a = self.scale, self.null_action
+        if isinstance(w, bool) or not (isinstance(w, (int, float)) and math.isfinite(w)):
+            raise ValueError(f"guidance scale must be a finite number, got {w!r}")
+        if isinstance(a, bool) or not isinstance(a, int) or a < 0:
+            raise ValueError(f"null_action must be a non-negative integer, got {a!r}")
+        if action_vocab_size is not None:
+            if not action_vocab_size:
+                raise ValueError("guidance given to a model without actions (config.action_vocab_size == 0)")
+            if a >= action_vocab_size:
+                raise IndexError(f"null_action {a} out of range [0, {action_vocab_size})")
+        return self
+
+    def to_struct(self):
+        """The ctypes genie_guidance."""
+        from . import _lib
+        self.validate()
+        return _lib.Guidance(scale=float(self.scale), null_action=int(self.null_action))
+
+    @classmethod
+    def from_args(cls, args):
+        """From a namespace carrying guidance_scale / null_action; None when guidance_scale is absent or None."""
+        w = getattr(args, "guidance_scale", None)
+        if w is None:
+            return None
+        a = getattr(args, "null_action", None)
+        if a is None:
+            raise ValueError("--guidance_scale needs --null_action (the action-table row trained as 'no action')")
+        return cls(float(w), int(a))
+
+
+def guidance_struct(guidance, action_vocab_size=None):
+    """None -> None (the unchanged entry points); a Guidance -> its genie_guidance, checked against the model's action table
+    (scale 1 -> None as well, once checked: the library would dispatch to the unguided entry point anyway)."""
+    if guidance is None:
+        return None
+    if not isinstance(guidance, Guidance):
+        raise ValueError(f"guidance must be a Guidance or None, got {type(guidance).__name__}")
+    guidance.validate(action_vocab_size)
+    if float(guidance.scale) == 1.0:   # g = c: the unguided entry points, sizes and launches
+        return None
+    return guidance.to_struct()
+
+
+def add_guidance_arguments(parser):
+    """--guidance_scale / --null_action for tools/generate.py and tools/bench_generate.py."""
+    parser.add_argument("--guidance_scale", type=float, default=None,
+                        help="Classifier-free guidance scale w of an action-conditioned model: logits = w * conditional + (1 - w) * null "
+                             "(1 = off, > 1 pushes away from the null-action stream). Needs --null_action.")
+    parser.add_argument("--null_action", type=int, default=None,
+                        help="Row of the action table trained as 'no action' (tools/train.py --action_dropout --null_action).")
+    return parser
+
+
 def as_struct(sampling):
     """None -> None (the unchanged entry points); a SamplingConfig -> its genie_sampling."""
     if sampling is None:

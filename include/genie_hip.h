@@ -156,7 +156,25 @@ typedef struct genie_sampling {
     float choice_temperature; /* c >= 0 */
 } genie_sampling;
 
+/* Classifier-free guidance of an action-conditioned model (ABI 3 addition; NULL = none).  null_action is a row id in [0, n_actions)
+ * of the action table: the "no action" row, which training learns by replacing a clip's actions with it some of the time (action
+ * dropout, 1xgpt_amd/data.py).  scale is w, finite: 1 = plain conditional sampling, 0 = the null stream alone, > 1 = guidance.  For every
+ * token, every factored vocabulary and every entry i, with c_i the logit under the clip's actions and u_i the logit of the same tokens
+ * with null_action at every frame, the guided logit is, in f32 with three separately rounded operations and no FMA contraction,
+ *     omw = 1.0f - w          (computed once on the host)
+ *     g_i = (w * c_i) + (omw * u_i)
+ * -- reproducible bit for bit in NumPy f32, and w = 1 gives g = c, w = 0 gives g = u, both up to the sign of a zero (which neither the
+ * ordering nor exp sees).  Everything after that is the genie_sampling law applied to g: z = g * (1 / tau), confidence from the tempered
+ * unfiltered softmax of z, top-k, top-p, the inverse-CDF draw, arg-max at temperature <= 1e-8, the confidence-mode key from the same
+ * launch.  A NULL genie_sampling under guidance is the all-off law.  Reference counterpart: none. */
+typedef struct genie_guidance {
+    float scale;         /* w, finite */
+    int32_t null_action; /* in [0, n_actions) */
+} genie_guidance;
+
 int genie_version(void);
+/* sizeof(genie_guidance) and the offsets of its two fields, in declaration order: writes min(n, 3) entries, returns 3. */
+int genie_guidance_layout(size_t* out_host, int n);
 /* sizeof(genie_sampling) and the offsets of its four fields, in declaration order: writes min(n, 5) entries, returns 5. */
 int genie_sampling_layout(size_t* out_host, int n);
 /* The compiler's view of the POD structs above, for bindings to check their own declarations against (tests/test_abi_and_host.py):
@@ -448,6 +466,17 @@ int genie_sample_ex(const genie_cfg* cfg, const float* logits, int layout, int B
                     int64_t* samples, float* conf, void* stream, const genie_sampling* sampling, float* keys_out,
                     const float* noise, float anneal);
 
+/* genie_sample_ex on guided logits (genie_guidance above): logits_cond / logits_null are the conditional and the null logits of the same
+ * B * S tokens, both in `layout`; the guided logit is formed as the kernel loads them (no extra pass, nothing materialised).
+ * scale == 1 is exactly genie_sample_ex on logits_cond (logits_null is not read); a non-finite scale returns GENIE_E_ARG before
+ * anything is enqueued.  Reference counterpart: none. */
+int genie_sample_guided(const genie_cfg* cfg, const float* logits_cond, const float* logits_null, int layout, int B, float temperature,
+                        const float* uniforms, int64_t* samples, float* conf, void* stream, const genie_sampling* sampling,
+                        float* keys_out, const float* noise, float anneal, float scale);
+/* out[i] = (scale * cond[i]) + ((1.0f - scale) * null[i]), i < n: the guided logits materialised (what the guided loops return as the
+ * step-0 logits).  out may alias cond or null. */
+int genie_guide_logits(const float* cond, const float* null_logits, float* out, size_t n, float scale, void* stream);
+
 /* MaskGIT mask half for one step (st_mask_git.py:192-223), one frame of B clips.
  *   keys (B,S) float32: caller's torch.rand draws ("random") or conf ("greedy"); ignored if last_step
  *   n: tokens to re-mask (ceil(cos(pi/2 (step+1)/steps) S)); unmasked (B,S) uint8 in/out;
@@ -477,6 +506,29 @@ int genie_maskgit_generate_ex(const genie_cfg* cfg, const genie_weights* w, int6
                               int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
                               void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond,
                               const genie_sampling* sampling);
+
+/* genie_maskgit_generate_ex / genie_generate_cached_ex under classifier-free guidance: the _ex arguments plus a trailing genie_guidance.
+ * NULL or scale == 1 is the _ex entry point itself (the null half does not run; cache and workspace as there).  Otherwise the library
+ * builds the doubled inputs itself on the stream -- tokens duplicated to 2B clips, actions [cond->ids ; null_action] of shape (2B, T) --,
+ * runs the passes of the _ex loop at batch 2B, samples B rows from rows b and b + B of the logits with the guided kernel
+ * (genie_sample_guided), runs genie_mask_step on B rows and mirrors the frame's current tokens into the second half before the next pass.
+ * noise, uniforms, gen_out / samples_out and logits0_out keep their shapes (per B); logits0_out carries the GUIDED step-0 logits;
+ * teacher_force_time and merge_commit keep their meaning, and a pass that 2B clips take out of the fragment-order kernels' coverage
+ * (genie_frames_pass) falls back as the unguided loop does at that batch.  Guidance needs a non-NULL cond with n_actions > 0, null_action
+ * in [0, n_actions) and a finite scale: GENIE_E_ARG otherwise, nothing enqueued.
+ * Sizes under guidance: cache = genie_prefix_cache_bytes(cfg, 2 * B); workspace = genie_generate_guided_workspace_bytes(cfg, B, P), which
+ * for any P in [1, T] is also enough for genie_maskgit_generate_guided.  Reference counterpart: none. */
+size_t genie_generate_guided_workspace_bytes(const genie_cfg* cfg, int B, int P);
+int genie_maskgit_generate_guided(const genie_cfg* cfg, const genie_weights* w, int64_t* prompt, int B, int out_t, int steps,
+                                  float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                                  int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
+                                  void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond,
+                                  const genie_sampling* sampling, const genie_guidance* guidance);
+int genie_generate_cached_guided(const genie_cfg* cfg, const genie_weights* w, const int64_t* ids, int B, int P, int n_new,
+                                 int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                                 int teacher_force_time, int merge_commit, int64_t* gen_out, float* logits0_out, float* cache,
+                                 size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
+                                 const genie_frame_cond* cond, const genie_sampling* sampling, const genie_guidance* guidance);
 
 /* ---- optional per-launch timing (bench.py's roofline leg) ------------------------------------------------
  * When enabled, every launch of a kernel whose class bit is set in `class_mask` is bracketed by a pair of

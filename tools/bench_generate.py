@@ -13,6 +13,41 @@ sys.path.insert(0, REPO)
 import torch  # noqa: E402
 
 
+def guidance_ab(a, m, cfg, extra):
+    """guided(B) against unguided(B) and unguided(2B) of the same library, one call per leg per round, legs interleaved: per leg the
+    median and the min-max spread over the rounds."""
+    synth = importlib.import_module("1xgpt_amd.synthetic")
+    G = importlib.import_module("1xgpt_amd.generate")
+    guide = importlib.import_module("1xgpt_amd.sampling").Guidance(a.guidance_scale, 0)
+    res = []
+    for B in a.batches:
+        for steps in a.steps:
+            legs = {}
+            for name, nb, g in (("unguided_B", B, None), ("unguided_2B", 2 * B, None), ("guided_B", B, guide)):
+                ex = torch.from_numpy(synth.make_clips(nb, cfg, seed=7)).cuda().view(nb, 16, 16, 16)
+                acts = torch.randint(1, cfg.action_vocab_size, (nb, cfg.T), generator=torch.Generator().manual_seed(nb)).cuda()
+                noise = torch.rand(8, max(steps - 1, 1), nb, cfg.S, device="cuda")
+                legs[name] = dict(args=(m, ex, 8, steps, a.temperature, False), kw=dict(noise=noise, action_ids=acts, guidance=g, **extra),
+                                  times=[], frames=8 * B)
+            for leg in legs.values():
+                for _ in range(2):
+                    G.generate_frames_cached(*leg["args"], **leg["kw"])
+            for _ in range(a.repeats):
+                for leg in legs.values():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    G.generate_frames_cached(*leg["args"], **leg["kw"])
+                    torch.cuda.synchronize()
+                    leg["times"].append(time.perf_counter() - t0)
+            for name, leg in legs.items():
+                t = sorted(leg["times"])
+                res.append({"leg": name, "batch": B, "maskgit_steps": steps, "guidance_scale": a.guidance_scale, "sampler": bool(a.sampler),
+                            "median_ms": 1e3 * t[len(t) // 2], "min_ms": 1e3 * t[0], "max_ms": 1e3 * t[-1],
+                            "ms_per_frame": 1e3 * t[len(t) // 2] / leg["frames"]})
+                print(res[-1], flush=True)
+    print(json.dumps({"workload": "generate 8->8 frames under guidance, " + a.model + " " + a.precision, "results": res}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--precision", default="f16x3")
@@ -27,6 +62,10 @@ def main():
     ap.add_argument("--top_k", type=int, default=50)
     ap.add_argument("--top_p", type=float, default=0.9)
     ap.add_argument("--unmask_mode", default="random", choices=["random", "greedy", "confidence"])
+    ap.add_argument("--guidance_scale", type=float, default=None,
+                    help="classifier-free guidance A/B on an action-conditioned variant of the model (8 actions, null action 0), KV-cache "
+                         "schedule: per batch B, interleaved in one process, unguided at B, unguided at 2B and guided at B with this scale")
+    ap.add_argument("--repeats", type=int, default=7, help="interleaved rounds of the guidance A/B")
     a = ap.parse_args()
     extra = {}
     if a.sampler:
@@ -39,7 +78,11 @@ def main():
     G = importlib.import_module("1xgpt_amd.generate")
     STMaskGIT = importlib.import_module("1xgpt_amd.st_mask_git").STMaskGIT
     cfg = cfgmod.c138() if a.model == "c138" else cfgmod.c35()
+    if a.guidance_scale is not None:
+        cfg.action_vocab_size = 8
     m = STMaskGIT(cfg, precision=a.precision).load_numpy_state_dict(synth.make_state_dict(cfg, seed=0)).to("cuda")
+    if a.guidance_scale is not None:
+        return guidance_ab(a, m, cfg, extra)
     res = []
     for B in a.batches:
         ex = torch.from_numpy(synth.make_clips(B, cfg, seed=7)).cuda().view(B, 16, 16, 16)

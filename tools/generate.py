@@ -5,7 +5,7 @@ written as [prompt | generated | ground truth] video.bin + metadata.json (readab
   python tools/generate.py --checkpoint_dir DIR --val_data_dir data/val_v1.1 --output_dir data/genie_generated
   python tools/generate.py --synthetic --model c35 --output_dir /tmp/gen
 An action-conditioned checkpoint (action_vocab_size > 0) generates with the example's actions from the dataset's actions.bin
-(refused without one)."""
+(refused without one); --guidance_scale W --null_action K decodes such a model under classifier-free guidance."""
 import argparse
 import importlib
 import os
@@ -30,6 +30,7 @@ def build_parser():
                     help="The reference's switch: 0 = arg-max, any value above 1e-8 = sample from the softmax. It does NOT temper "
                          "(0.7 and 1.0 draw from the same law); use --logit_temperature, --top_k, --top_p for that.")
     importlib.import_module("1xgpt_amd.sampling").add_cli_arguments(ap)
+    importlib.import_module("1xgpt_amd.sampling").add_guidance_arguments(ap)
     ap.add_argument("--precision", choices=["exact", "f16x3", "bf16"], default="f16x3")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--model", choices=["c138", "c35"], default="c35")
@@ -42,6 +43,7 @@ def build_parser():
 def main():
     args = build_parser().parse_args()
     sampling = importlib.import_module("1xgpt_amd.sampling").SamplingConfig.from_args(args)
+    guidance = importlib.import_module("1xgpt_amd.sampling").Guidance.from_args(args)
     actions = None
     G = importlib.import_module("1xgpt_amd.generate")
     STMaskGIT = importlib.import_module("1xgpt_amd.st_mask_git").STMaskGIT
@@ -67,7 +69,8 @@ def main():
     ex = example.to("cuda").view(1, args.window_size, model.h, model.w)
     fn = G.generate_frames_cached if args.schedule == "kv_cache" else G.generate_frames
     out = fn(model, ex, args.num_prompt_frames, args.maskgit_steps, args.temperature, args.teacher_force_time,
-             action_ids=None if actions is None else actions.to("cuda"), sampling=sampling, unmask_mode=args.unmask_mode)
+             action_ids=None if actions is None else actions.to("cuda"), sampling=sampling, unmask_mode=args.unmask_mode,
+             guidance=guidance)
     print(G.write_outputs(out, args.output_dir, meta, vars(args)))
 
 

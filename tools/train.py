@@ -55,6 +55,10 @@ def parse_args():
     p.add_argument("--mu_transfer", action="store_true")
     p.add_argument("--precision", choices=["exact", "f16x3", "bf16"], default="bf16",
                    help="bf16 = what the reference computes under --mixed_precision bf16; f16x3 keeps f32-class gradients")
+    p.add_argument("--action_dropout", type=float, default=0.0,
+                   help="share of the training clips whose actions are replaced by --null_action (trains the null action of "
+                        "classifier-free guidance; action-conditioned configs only)")
+    p.add_argument("--null_action", type=int, default=None, help="row of the action table that stands for 'no action'")
     p.add_argument("--synthetic", type=int, default=0, help="train on N synthetic clips (no dataset on disk)")
     p.add_argument("--model", choices=["c138", "c35", "tiny"], default="c35", help="shape when no --genie_config is given")
     return p.parse_args()
@@ -171,7 +175,9 @@ def main():
         perm = torch.randperm(n_train, generator=g)  # same permutation on every rank; rank r takes its slice
         for m in range(consumed % micro_per_epoch if epoch == consumed // micro_per_epoch else 0, micro_per_epoch):
             idx = perm[(m * world + rank) * B:(m * world + rank + 1) * B].tolist()
-            batch = datamod.maskgit_collate(get_train(idx).to(dev), cfg, action_ids=acts_of(get_train_acts, idx))
+            batch = datamod.maskgit_collate(get_train(idx).to(dev), cfg, action_ids=acts_of(get_train_acts, idx),
+                                            action_dropout=args.action_dropout if model.config.action_vocab_size else 0.0,
+                                            null_action=args.null_action)
             out = tr.train_step(batch)
             loss_info += torch.stack([out["loss"] * B, torch.tensor(float(B), device=dev, dtype=torch.float64)])
             if "lr" not in out:
