@@ -201,6 +201,12 @@ for _n in ("genie_maskgit_generate", "genie_generate_cached"):
 del _n
 SIGNATURES["genie_sample_guided"] = (C.c_int, SIGNATURES["genie_sample_ex"][1][:2] + [c_ptr] + SIGNATURES["genie_sample_ex"][1][2:]
                                      + [C.c_float])
+# the rollout past the window: (cfg, B, ctx_max, guided) and (cfg, w, frames, B, P, keep, cap, f0, f1, resume, steps, temperature, unmask_mode,
+# noise, uniforms, merge_commit, cache, cache_bytes, workspace, workspace_bytes, stream, cond, sampling, guidance)
+SIGNATURES["genie_rollout_workspace_bytes"] = (C.c_size_t, [C.POINTER(GenieCfg), C.c_int, C.c_int, C.c_int])
+SIGNATURES["genie_rollout_cached"] = (C.c_int, [C.POINTER(GenieCfg), C.POINTER(Weights), c_ptr] + [C.c_int] * 8 + [C.c_float, C.c_int, c_ptr,
+                                                c_ptr, C.c_int, c_ptr, C.c_size_t, c_ptr, C.c_size_t, c_ptr, C.POINTER(FrameCond),
+                                                C.POINTER(Sampling), C.POINTER(Guidance)])
 
 _lib = None
 

@@ -685,7 +685,7 @@ struct GenScratch {
     uint8_t* unmasked;
     size_t end;
 };
-static GenScratch carve_generate(const genie_cfg& c, int B, int NB, int P, char* base) {
+static GenScratch carve_generate(const genie_cfg& c, int B, int NB, int P, char* base, bool window_acts = false) {
     const size_t BS = (size_t)B * c.S, NBS = (size_t)NB * c.S, V = (size_t)c.factored_vocab * c.num_factored;
     size_t off = generate_scratch_offset(c, NB, P);
     auto take = [&](size_t bytes) { char* r = base ? base + off : nullptr; off += align_up(bytes, 256); return r; };
@@ -698,7 +698,7 @@ static GenScratch carve_generate(const genie_cfg& c, int B, int NB, int P, char*
     g.conf = (float*)take(BS * 4);
     g.unmasked = (uint8_t*)take(BS);
     g.logits = (float*)take(NBS * V * 4);
-    g.acts = NB != B ? (int64_t*)take((size_t)NB * c.T * 8) : nullptr;
+    g.acts = (NB != B || window_acts) ? (int64_t*)take((size_t)NB * c.T * 8) : nullptr;   // window_acts: the rollout's action window
     g.end = off;
     return g;
 }
@@ -751,6 +751,139 @@ int genie_generate_cached_cond(const genie_cfg* cfg, const genie_weights* wt, co
                                     nullptr);
 }
 
+// What one generate / rollout call decodes with: its checked arguments and the carved scratch, shared by every window of the call.
+// B clips are decoded, NB run through every pass.
+struct GenLoop {
+    const genie_cfg* cfg;
+    const genie_weights* wt;
+    int B, NB, copies, steps, unmask_mode, merge_commit;
+    float temperature;
+    const genie_sampling* law;
+    const genie_guidance* guidance;
+    bool guided;
+    const genie_frame_cond* cond;   // what the passes embed with: ids (NB, cfg->T)
+    float* cache;
+    size_t cache_bytes;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+    GenScratch g;
+};
+// the decode options every loop entry point takes, checked on the host before anything is enqueued
+static int check_decode(int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                        const genie_sampling* sampling, const char* where) {
+    GENIE_TRY(check_sampling(sampling, where));
+    GENIE_TRY(check_unmask(unmask_mode, unmask_mode != -1, steps, noise, where));
+    GENIE_CHECK_ARG(temperature <= 1e-8f || uniforms, "%s: temperature > 0 needs uniforms", where);
+    return GENIE_OK;
+}
+
+// `ctx` context frames into cache slots 0 .. ctx-1: one ctx-frame pass over idsP (NB, ctx, S, already filled) where the fragment-order
+// kernels cover it, else the clean pass with the cache's T-frame layout, else frame by frame from src (frame t of clip b at
+// src + b * src_stride + t * S)
+static int run_context(const GenLoop& L, int ctx, const int64_t* src, long src_stride) {
+    const genie_cfg& c = *L.cfg;
+    hipStream_t st = as_stream(L.stream);
+    int rc = GENIE_E_UNSUPPORTED;
+    if (ctx > 1) {
+        rc = genie_frames_pass_cond(L.cfg, L.wt, L.g.idsP, L.NB, 0, ctx, L.cache, L.cache_bytes, nullptr, L.workspace, L.workspace_bytes,
+                                    L.stream, L.cond);
+        if (rc == GENIE_E_UNSUPPORTED)
+            rc = genie_clean_pass_cond(L.cfg, L.wt, L.g.idsP, L.NB, ctx, c.T, L.cache, L.cache_bytes, L.workspace, L.workspace_bytes,
+                                       L.stream, L.cond);
+    }
+    if (rc != GENIE_E_UNSUPPORTED) return rc;
+    for (int t = 0; t < ctx; ++t) {
+        GENIE_TRY(put_frame_ids(src + (size_t)t * c.S, src_stride, L.g.fin, c.S, c.S, L.B, 0, st, L.copies));
+        GENIE_TRY(genie_frames_pass_cond(L.cfg, L.wt, L.g.fin, L.NB, t, 1, L.cache, L.cache_bytes, nullptr, L.workspace, L.workspace_bytes,
+                                         L.stream, L.cond));
+    }
+    return GENIE_OK;
+}
+
+// The window body: decodes cache slots t0 .. t0 + n - 1 one after the other (slots < t0 - 1 are committed; slot t0 - 1 too unless `pend`).
+// Slot t0 + k draws from noise / uniforms [k] and its final tokens go to out + k * S (clip stride out_stride); its step-0 logits to
+// logits0_out[:, k] of (B, n, S, V) when wanted.  Every slot but the LAST is committed -- from its final tokens, or from tf + k * S (clip
+// stride tf_stride) when tf is given (teacher forcing in time) --, merged with step 0 of the next slot where merge_commit is set and the
+// library covers it.  pend != NULL: slot t0 - 1 is still pending; its final tokens (pend, clip stride pend_stride) are committed first, by
+// the same rule.
+static int decode_slots(const GenLoop& L, int t0, int n, const float* noise, const float* uniforms, int64_t* out, long out_stride,
+                        float* logits0_out, const int64_t* tf, long tf_stride, const int64_t* pend, long pend_stride) {
+    const genie_cfg* cfg = L.cfg;
+    const genie_cfg& c = *cfg;
+    const genie_weights* wt = L.wt;
+    const int B = L.B, NB = L.NB, copies = L.copies, steps = L.steps, unmask_mode = L.unmask_mode, S = c.S;
+    const float temperature = L.temperature;
+    const bool guided = L.guided, by_conf = unmask_mode == GENIE_UNMASK_CONFIDENCE;
+    const genie_frame_cond* cond = L.cond;
+    float* cache = L.cache;
+    const size_t cache_bytes = L.cache_bytes, workspace_bytes = L.workspace_bytes;
+    void *workspace = L.workspace, *stream = L.stream;
+    hipStream_t st = as_stream(stream);
+    const size_t BS = (size_t)B * S, V = (size_t)c.factored_vocab * c.num_factored;
+    int64_t *two = L.g.two, *cur = L.g.cur, *fin = L.g.fin, *samples = L.g.samples;
+    float *conf = L.g.conf, *logits = L.g.logits;
+    uint8_t* unmasked = L.g.unmasked;
+    const float* logits_null = logits + BS * V;   // guided: rows B .. 2B - 1 of every pass's logits
+    bool opened = false, merge = L.merge_commit != 0;
+    // commit slot t from fsrc: in the pass that also carries MaskGIT step 0 of slot t + 1 (all-mask tokens), or on its own
+    auto commit = [&](int t, const int64_t* fsrc, long fstride) -> int {
+        if (merge) {
+            GENIE_TRY(put_frame_ids(fsrc, fstride, two, 2L * S, S, B, 0, st, copies));
+            GENIE_TRY(put_frame_ids(nullptr, 0, two + S, 2L * S, S, B, c.image_vocab_size, st, copies));
+            const int rc = genie_frames_pass_cond(cfg, wt, two, NB, t, 2, cache, cache_bytes, logits, workspace, workspace_bytes, stream, cond);
+            if (rc == GENIE_E_UNSUPPORTED) merge = false;
+            else { GENIE_TRY(rc); opened = true; }
+        }
+        if (!opened) {
+            GENIE_TRY(put_frame_ids(fsrc, fstride, fin, S, S, B, 0, st, copies));
+            GENIE_TRY(genie_frames_pass_cond(cfg, wt, fin, NB, t, 1, cache, cache_bytes, nullptr, workspace, workspace_bytes, stream, cond));
+        }
+        return GENIE_OK;
+    };
+    if (pend) GENIE_TRY(commit(t0 - 1, pend, pend_stride));
+    for (int k = 0; k < n; ++k) {
+        const int t = t0 + k;
+        GENIE_TRY(put_frame_ids(nullptr, 0, cur, S, S, B, c.image_vocab_size, st, copies));
+        if (hipMemsetAsync(unmasked, 0, BS, st) != hipSuccess) { set_error("memset failed"); return GENIE_E_LAUNCH; }
+        for (int step = 0; step < steps; ++step) {
+            if (!(step == 0 && opened))
+                GENIE_TRY(genie_frames_pass_cond(cfg, wt, cur, NB, t, 1, cache, cache_bytes, logits, workspace, workspace_bytes, stream, cond));
+            if (step == 0 && logits0_out) {   // orig_logits of the frame (st_mask_git.py:165,226): the step-0 logits, (B, n, S, V)
+                if (guided) {                 // ... the guided ones
+                    GENIE_TRY(launch_guide_logits(logits, logits_null, logits0_out + (size_t)k * S * V, B, (long)(S * V), (long)(S * V),
+                                                  (long)((size_t)n * S * V), L.guidance->scale, st));
+                } else if (hipMemcpy2DAsync(logits0_out + (size_t)k * S * V, (size_t)n * S * V * 4, logits, (size_t)S * V * 4,
+                                            (size_t)S * V * 4, (size_t)B, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+                    set_error("memcpy failed");
+                    return GENIE_E_LAUNCH;
+                }
+            }
+            const float* u = temperature > 1e-8f ? uniforms + ((size_t)k * steps + step) * c.num_factored * BS : nullptr;
+            const bool last = step == steps - 1;
+            const float* draws = (last || unmask_mode == GENIE_UNMASK_GREEDY) ? nullptr : noise + ((size_t)k * (steps - 1) + step) * BS;
+            // "confidence": the sample launch writes the keys over conf (nothing else reads conf in this loop)
+            const float anneal = 1.0f - (float)(step + 1) / (float)steps;
+            if (guided)
+                GENIE_TRY(launch_sample_guided(c, logits, logits_null, GENIE_LAYOUT_TOKEN_MAJOR, B, temperature, u, samples, conf, L.law,
+                                               (by_conf && !last) ? conf : nullptr, draws, anneal, L.guidance->scale, st));
+            else
+                GENIE_TRY(launch_sample_ex(c, logits, GENIE_LAYOUT_TOKEN_MAJOR, B, temperature, u, samples, conf, L.law,
+                                           (by_conf && !last) ? conf : nullptr, draws, anneal, st));
+            const float* keys = last ? nullptr : (unmask_mode == GENIE_UNMASK_RANDOM ? draws : conf);
+            GENIE_TRY(launch_mask_step(keys, last ? 0 : mask_count(step, steps, S), last, c.image_vocab_size, unmasked, samples, cur, S, B, S, st));
+            if (guided) GENIE_TRY(put_frame_ids(cur, S, cur + BS, S, S, B, 0, st));   // the null half sees the same tokens
+        }
+        GENIE_TRY(put_frame_ids(cur, S, out + (size_t)k * S, out_stride, S, B, 0, st));
+        opened = false;
+        if (k + 1 < n) {   // commit slot t: its final tokens, or the ground truth when teacher-forcing in time
+            if (tf) GENIE_TRY(commit(t, tf + (size_t)k * S, tf_stride));
+            else GENIE_TRY(commit(t, cur, S));
+        }
+    }
+    return GENIE_OK;
+}
+
 // genie_generate_cached_ex (guidance NULL or of scale 1) and genie_generate_cached_guided: one loop, B clips decoded, NB per pass
 static int generate_cached_loop(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int P, int n_new,
                                 int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
@@ -764,11 +897,8 @@ static int generate_cached_loop(const genie_cfg* cfg, const genie_weights* wt, c
     GENIE_TRY(check_guidance(guidance, cond, "generate_cached"));
     GENIE_CHECK_ARG(B >= 1 && P >= 1 && n_new >= 1 && P + n_new <= c.T && steps >= 1,
                     "generate_cached: B=%d, %d prompt + %d new frames of at most %d, steps %d", B, P, n_new, c.T, steps);
-    GENIE_TRY(check_sampling(sampling, "generate_cached"));
-    GENIE_TRY(check_unmask(unmask_mode, unmask_mode != -1, steps, noise, "generate_cached"));
-    GENIE_CHECK_ARG(temperature <= 1e-8f || uniforms, "generate_cached: temperature > 0 needs uniforms");
+    GENIE_TRY(check_decode(steps, temperature, unmask_mode, noise, uniforms, sampling, "generate_cached"));
     const bool by_conf = unmask_mode == GENIE_UNMASK_CONFIDENCE;
-    const genie_sampling* law = (by_conf && !sampling) ? &kDefaultSampling : sampling;
     // under guidance every pass runs 2 B clips, [conditional ; null]: rows b and b + B hold the same tokens, the second half's actions are
     // null_action at every frame; B rows are sampled, masked and written out
     const bool guided = guidance && guidance->scale != 1.0f;
@@ -778,92 +908,117 @@ static int generate_cached_loop(const genie_cfg* cfg, const genie_weights* wt, c
     GENIE_TRY(check_ws(c, NB, workspace, workspace_bytes));
     hipStream_t st = as_stream(stream);
     const int S = c.S, T = P + n_new;   // frames per clip in `ids` (the cache keeps the model's c.T slots per clip)
-    const size_t BS = (size_t)B * S, V = (size_t)c.factored_vocab * c.num_factored;
     // scratch of the loop behind the workspace of its largest pass (the prompt's P frames; two frames for the merged passes):
     // genie_generate_workspace_bytes / genie_generate_guided_workspace_bytes (cfg, B, P) is the size to allocate
-    const GenScratch g = carve_generate(c, B, NB, P, (char*)workspace);
-    GENIE_CHECK_ARG(g.end <= workspace_bytes, "generate_cached: workspace too small (%zu < %zu bytes: size it with %s)", workspace_bytes,
-                    g.end, guided ? "genie_generate_guided_workspace_bytes" : "genie_generate_workspace_bytes");
-    int64_t *idsP = g.idsP, *two = g.two, *cur = g.cur, *fin = g.fin, *samples = g.samples;
-    float *conf = g.conf, *logits = g.logits;
-    uint8_t* unmasked = g.unmasked;
+    GenLoop L = {cfg, wt, B, NB, copies, steps, unmask_mode, merge_commit, temperature, (by_conf && !sampling) ? &kDefaultSampling : sampling,
+                 guidance, guided, cond, cache, cache_bytes, workspace, workspace_bytes, stream, carve_generate(c, B, NB, P, (char*)workspace)};
+    GENIE_CHECK_ARG(L.g.end <= workspace_bytes, "generate_cached: workspace too small (%zu < %zu bytes: size it with %s)", workspace_bytes,
+                    L.g.end, guided ? "genie_generate_guided_workspace_bytes" : "genie_generate_workspace_bytes");
     genie_frame_cond cond2;
     if (guided) {
-        GENIE_TRY(put_guided_actions(*cond, *guidance, B, c.T, g.acts, st));
+        GENIE_TRY(put_guided_actions(*cond, *guidance, B, c.T, L.g.acts, st));
         cond2 = *cond;
-        cond2.ids = g.acts;
-        cond = &cond2;
+        cond2.ids = L.g.acts;
+        L.cond = &cond2;
     }
-    const float* logits_null = logits + BS * V;   // guided: rows B .. 2B - 1 of every pass's logits
-
-    // ---- the prompt fills cache slots 0 .. P-1: one P-frame pass where the fragment-order kernels cover it, else the clean pass
-    // with the cache's T-frame layout, else frame by frame
+    // ---- the prompt fills cache slots 0 .. P-1
     for (int t = 0; t < P; ++t)
-        GENIE_TRY(put_frame_ids(ids + (size_t)t * S, (long)T * S, idsP + (size_t)t * S, (long)P * S, S, B, 0, st, copies));
-    int rc = GENIE_E_UNSUPPORTED;
-    if (P > 1) {
-        rc = genie_frames_pass_cond(cfg, wt, idsP, NB, 0, P, cache, cache_bytes, nullptr, workspace, workspace_bytes, stream, cond);
-        if (rc == GENIE_E_UNSUPPORTED)
-            rc = genie_clean_pass_cond(cfg, wt, idsP, NB, P, c.T, cache, cache_bytes, workspace, workspace_bytes, stream, cond);
+        GENIE_TRY(put_frame_ids(ids + (size_t)t * S, (long)T * S, L.g.idsP + (size_t)t * S, (long)P * S, S, B, 0, st, copies));
+    GENIE_TRY(run_context(L, P, ids, (long)T * S));
+    return decode_slots(L, P, n_new, noise, uniforms, gen_out, (long)n_new * S, logits0_out,
+                        teacher_force_time ? ids + (size_t)P * S : nullptr, (long)T * S, nullptr, 0);
+}
+
+// What the passes of one rollout window read, gathered from the caller's (B, cap, *) buffers in one launch:
+//   ctx_out (B * copies, ctx, S): the tokens of absolute frames [start, start + ctx); rows b + B (copies == 2) repeat rows b
+//   act_out (B * copies, T) or NULL: slot i = the action of absolute frame start + i, 0 past cap (never embedded); rows b + B = null_action
+__global__ void rollout_window_kernel(const int64_t* __restrict__ frames, const int64_t* __restrict__ actions, int64_t* __restrict__ ctx_out,
+                                      int64_t* __restrict__ act_out, int B, int copies, int ctx, int S, int T, long cap, long start,
+                                      int64_t null_action) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long per = (long)ctx * S, ntok = (long)B * copies * per;
+    if (i < ntok) {
+        const long r = i / per, j = i - r * per, b = r % B;
+        ctx_out[i] = frames[(b * cap + start) * S + j];
+        return;
     }
-    if (rc == GENIE_E_UNSUPPORTED) {
-        for (int t = 0; t < P; ++t) {
-            GENIE_TRY(put_frame_ids(ids + (size_t)t * S, (long)T * S, fin, S, S, B, 0, st, copies));
-            GENIE_TRY(genie_frames_pass_cond(cfg, wt, fin, NB, t, 1, cache, cache_bytes, nullptr, workspace, workspace_bytes, stream, cond));
-        }
-    } else {
-        GENIE_TRY(rc);
+    const long a = i - ntok;
+    if (!act_out || a >= (long)B * copies * T) return;
+    const long r = a / T, f = start + (a - r * T);
+    act_out[a] = r >= B ? null_action : (f < cap ? actions[r * cap + f] : 0);
+}
+static int put_rollout_window(const int64_t* frames, const int64_t* actions, int64_t* ctx_out, int64_t* act_out, int B, int copies,
+                              int ctx, int S, int T, long cap, long start, int64_t null_action, hipStream_t st) {
+    const long n = (long)B * copies * ((long)ctx * S + (act_out ? T : 0));
+    if (n == 0) return GENIE_OK;
+    rollout_window_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(frames, actions, ctx_out, act_out, B, copies, ctx, S, T, cap, start,
+                                                                       null_action);
+    GENIE_LAUNCH_CHECK("rollout_window");
+    return GENIE_OK;
+}
+
+size_t genie_rollout_workspace_bytes(const genie_cfg* cfg, int B, int ctx_max, int guided) {
+    if (check_cfg(cfg) != GENIE_OK || B < 1 || B > 0x3fffffff || ctx_max < 1 || ctx_max > cfg->T - 1) return 0;
+    const int NB = guided ? 2 * B : B;
+    const size_t off = carve_generate(*cfg, B, NB, ctx_max, nullptr, true).end;
+    const size_t full = guided ? carve_guided_prompt(*cfg, NB, nullptr).end : carve(*cfg, B, nullptr).total;
+    return off > full ? off : full;
+}
+
+int genie_rollout_cached(const genie_cfg* cfg, const genie_weights* wt, int64_t* frames, int B, int P, int keep, int cap, int f0, int f1,
+                         int resume, int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                         int merge_commit, float* cache, size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
+                         const genie_frame_cond* cond, const genie_sampling* sampling, const genie_guidance* guidance) {
+    GENIE_TRY(check_cfg(cfg));
+    const genie_cfg& c = *cfg;
+    const int T = c.T, S = c.S;
+    GENIE_CHECK_ARG(B >= 1 && steps >= 1, "rollout_cached: B=%d, steps %d", B, steps);
+    GENIE_CHECK_ARG(P >= 1 && P <= T - 1, "rollout_cached: %d prompt frames outside [1, %d]", P, T - 1);
+    GENIE_CHECK_ARG(keep >= 1 && keep <= T - 1, "rollout_cached: keep %d outside [1, %d]", keep, T - 1);
+    GENIE_CHECK_ARG(P <= f0 && f0 < f1 && f1 <= cap, "rollout_cached: frames [%d, %d) must lie in [%d prompt frames, cap %d]", f0, f1, P, cap);
+    GENIE_CHECK_ARG(resume == 0 || resume == 1, "rollout_cached: resume %d must be 0 or 1", resume);
+    GENIE_TRY(check_frame_cond(cond, "rollout_cached"));
+    GENIE_TRY(check_guidance(guidance, cond, "rollout_cached"));
+    GENIE_TRY(check_decode(steps, temperature, unmask_mode, noise, uniforms, sampling, "rollout_cached"));
+    GENIE_CHECK_ARG(wt && wt->layers_host && frames && cache, "rollout_cached: NULL pointer");
+    const bool by_conf = unmask_mode == GENIE_UNMASK_CONFIDENCE, guided = guidance && guidance->scale != 1.0f;
+    GENIE_CHECK_ARG(!guided || B <= 0x3fffffff, "rollout_cached: B=%d too large for guidance", B);
+    const int NB = guided ? 2 * B : B, copies = guided ? 2 : 1, hop = T - keep;
+    GENIE_CHECK_ARG(cache_bytes >= genie_prefix_cache_bytes(cfg, NB), "rollout_cached: cache too small");
+    GENIE_TRY(check_ws(c, NB, workspace, workspace_bytes));
+    // window of frame f: j = 0 below T, else 1 + (f - T) / hop; it starts at absolute frame j * hop and ends before j * hop + T
+    auto start_of = [&](int f) { return f < T ? 0 : (1 + (f - T) / hop) * hop; };
+    auto opens = [&](int f) { return f == P || (f >= T && f - start_of(f) == keep); };
+    const int start0 = start_of(f0);
+    const bool fresh0 = !resume || opens(f0);
+    // the largest context this call runs sizes its scratch: that of f0 unless resumed mid-window, `keep` for every later window
+    int ctx_need = fresh0 ? f0 - start0 : 1;
+    if (f1 > start0 + T && keep > ctx_need) ctx_need = keep;
+    GenLoop L = {cfg, wt, B, NB, copies, steps, unmask_mode, merge_commit, temperature, (by_conf && !sampling) ? &kDefaultSampling : sampling,
+                 guidance, guided, cond, cache, cache_bytes, workspace, workspace_bytes, stream,
+                 carve_generate(c, B, NB, ctx_need, (char*)workspace, true)};
+    GENIE_CHECK_ARG(L.g.end <= workspace_bytes, "rollout_cached: workspace too small (%zu < %zu bytes: size it with "
+                    "genie_rollout_workspace_bytes for a context of %d frames)", workspace_bytes, L.g.end, ctx_need);
+    hipStream_t st = as_stream(stream);
+    const bool acts = cond && cond->n_actions > 0;
+    genie_frame_cond cond2;
+    if (acts) {   // the passes read the window's actions, (NB, T) with the clip stride they expect
+        cond2 = *cond;
+        cond2.ids = L.g.acts;
+        L.cond = &cond2;
     }
-    bool opened = false, merge = merge_commit != 0;
-    for (int k = 0; k < n_new; ++k) {
-        const int t = P + k;
-        GENIE_TRY(put_frame_ids(nullptr, 0, cur, S, S, B, c.image_vocab_size, st, copies));
-        if (hipMemsetAsync(unmasked, 0, BS, st) != hipSuccess) { set_error("memset failed"); return GENIE_E_LAUNCH; }
-        for (int step = 0; step < steps; ++step) {
-            if (!(step == 0 && opened))
-                GENIE_TRY(genie_frames_pass_cond(cfg, wt, cur, NB, t, 1, cache, cache_bytes, logits, workspace, workspace_bytes, stream, cond));
-            if (step == 0 && logits0_out) {   // orig_logits of the frame (st_mask_git.py:165,226): the step-0 logits, (B, n_new, S, V)
-                if (guided) {                 // ... the guided ones
-                    GENIE_TRY(launch_guide_logits(logits, logits_null, logits0_out + (size_t)k * S * V, B, (long)(S * V), (long)(S * V),
-                                                  (long)((size_t)n_new * S * V), guidance->scale, st));
-                } else if (hipMemcpy2DAsync(logits0_out + (size_t)k * S * V, (size_t)n_new * S * V * 4, logits, (size_t)S * V * 4,
-                                            (size_t)S * V * 4, (size_t)B, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-                    set_error("memcpy failed");
-                    return GENIE_E_LAUNCH;
-                }
-            }
-            const float* u = temperature > 1e-8f ? uniforms + ((size_t)k * steps + step) * c.num_factored * BS : nullptr;
-            const bool last = step == steps - 1;
-            const float* draws = (last || unmask_mode == GENIE_UNMASK_GREEDY) ? nullptr : noise + ((size_t)k * (steps - 1) + step) * BS;
-            // "confidence": the sample launch writes the keys over conf (nothing else reads conf in this loop)
-            const float anneal = 1.0f - (float)(step + 1) / (float)steps;
-            if (guided)
-                GENIE_TRY(launch_sample_guided(c, logits, logits_null, GENIE_LAYOUT_TOKEN_MAJOR, B, temperature, u, samples, conf, law,
-                                               (by_conf && !last) ? conf : nullptr, draws, anneal, guidance->scale, st));
-            else
-                GENIE_TRY(launch_sample_ex(c, logits, GENIE_LAYOUT_TOKEN_MAJOR, B, temperature, u, samples, conf, law,
-                                           (by_conf && !last) ? conf : nullptr, draws, anneal, st));
-            const float* keys = last ? nullptr : (unmask_mode == GENIE_UNMASK_RANDOM ? draws : conf);
-            GENIE_TRY(launch_mask_step(keys, last ? 0 : mask_count(step, steps, S), last, c.image_vocab_size, unmasked, samples, cur, S, B, S, st));
-            if (guided) GENIE_TRY(put_frame_ids(cur, S, cur + BS, S, S, B, 0, st));   // the null half sees the same tokens
-        }
-        GENIE_TRY(put_frame_ids(cur, S, gen_out + (size_t)k * S, (long)n_new * S, S, B, 0, st));
-        opened = false;
-        if (t + 1 < T) {   // commit frame t: its final tokens, or the ground truth when teacher-forcing in time
-            const int64_t* fsrc = teacher_force_time ? ids + (size_t)t * S : cur;
-            const long fstride = teacher_force_time ? (long)T * S : S;
-            if (merge) {   // ... in the pass that also carries MaskGIT step 0 of frame t + 1 (all-mask tokens)
-                GENIE_TRY(put_frame_ids(fsrc, fstride, two, 2L * S, S, B, 0, st, copies));
-                GENIE_TRY(put_frame_ids(nullptr, 0, two + S, 2L * S, S, B, c.image_vocab_size, st, copies));
-                rc = genie_frames_pass_cond(cfg, wt, two, NB, t, 2, cache, cache_bytes, logits, workspace, workspace_bytes, stream, cond);
-                if (rc == GENIE_E_UNSUPPORTED) merge = false;
-                else { GENIE_TRY(rc); opened = true; }
-            }
-            if (!opened) {
-                GENIE_TRY(put_frame_ids(fsrc, fstride, fin, S, S, B, 0, st, copies));
-                GENIE_TRY(genie_frames_pass_cond(cfg, wt, fin, NB, t, 1, cache, cache_bytes, nullptr, workspace, workspace_bytes, stream, cond));
-            }
-        }
+    const long stride = (long)cap * S;
+    for (int f = f0; f < f1;) {
+        const int start = start_of(f), end = start + T < f1 ? start + T : f1;
+        const bool fresh = f != f0 || fresh0;   // the window's context is run from `frames`; else frame f - 1 is pending in the cache
+        const int ctx = fresh ? f - start : 0;
+        GENIE_TRY(put_rollout_window(frames, acts ? cond->ids : nullptr, L.g.idsP, acts ? L.g.acts : nullptr, B, copies, ctx, S, T, cap, start,
+                                     guided ? guidance->null_action : 0, st));
+        if (fresh) GENIE_TRY(run_context(L, ctx, frames + (size_t)start * S, stride));
+        GENIE_TRY(decode_slots(L, f - start, end - f, noise ? noise + (size_t)(f - f0) * (steps - 1) * B * S : nullptr,
+                               uniforms ? uniforms + (size_t)(f - f0) * steps * c.num_factored * B * S : nullptr, frames + (size_t)f * S,
+                               stride, nullptr, nullptr, 0, fresh ? nullptr : frames + (size_t)(f - 1) * S, stride));
+        f = end;
     }
     return GENIE_OK;
 }

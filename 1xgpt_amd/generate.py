@@ -211,6 +211,207 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
     return torch.cat([outputs, ex[:, P:]], dim=1)
 
 
+def frame_window(f, P, keep, T):
+    """(j, start, slot) of the generated absolute frame f >= P: it is decoded in slot ``slot`` of window ``j``, which starts at absolute
+    frame ``start`` (include/genie_hip.h, "rollout past the context window"); its context is the frames [start, f)."""
+    hop = T - keep
+    j = 0 if f < T else 1 + (f - T) // hop
+    return j, j * hop, f - j * hop
+
+
+def window_schedule(P, keep, T, n_new):
+    """The windows of a rollout of n_new frames behind P prompt frames: a list of (j, start, f_begin, f_end), in order -- window j holds
+    the absolute frames [start, start + T) in its T slots, runs [start, f_begin) as its context and decodes [f_begin, f_end).  Window 0
+    decodes up to T - P frames, every later one up to hop = T - keep."""
+    if not (1 <= P <= T - 1 and 1 <= keep <= T - 1):
+        raise ValueError(f"rollout: prompt frames {P} and keep {keep} must lie in [1, {T - 1}]")
+    out, f, end = [], P, P + n_new
+    while f < end:
+        j, start, _ = frame_window(f, P, keep, T)
+        nxt = min(start + T, end)
+        out.append((j, start, f, nxt))
+        f = nxt
+    return out
+
+
+def _rollout_actions(model, action_ids, B, n, what="action_ids"):
+    """Checked (B, n) int64 device actions of a rollout, or None for a model without actions."""
+    A = model.config.action_vocab_size
+    if not A:
+        if action_ids is not None:
+            raise ValueError(f"{what} given to a model without actions (config.action_vocab_size == 0)")
+        return None
+    if action_ids is None:
+        raise ValueError(f"this model is action-conditioned (action_vocab_size={A}): pass {what} ({B}, {n})")
+    a = torch.as_tensor(action_ids)
+    if a.dtype.is_floating_point or a.dtype == torch.bool:
+        raise RuntimeError(f"{what} must be an integer tensor, got {a.dtype}")
+    if tuple(a.shape) != (B, n):
+        raise RuntimeError(f"expected {what} of shape ({B}, {n}), got {tuple(a.shape)}")
+    if a.numel() and (int(a.min()) < 0 or int(a.max()) >= A):
+        raise IndexError(f"action id out of range [0, {A}): min {int(a.min())}, max {int(a.max())}")
+    return a.to(device=model.pos_embed_TSC.device, dtype=torch.int64).contiguous()
+
+
+class _Decode:
+    """The decode options of a rollout, resolved once: MaskGIT steps, unmasking mode, sampling law, guidance."""
+
+    def __init__(self, model, maskgit_steps, temperature, unmask_mode, sampling, guidance, merge_commit):
+        from . import _lib
+        from .sampling import SamplingConfig, as_struct, unmask_code
+        self.steps, self.temperature, self.merge_commit = int(maskgit_steps), float(temperature), bool(merge_commit)
+        self.unmask_mode, self.mode, self.law = unmask_mode, unmask_code(unmask_mode), as_struct(sampling)
+        if self.mode == _lib.UNMASK_CONFIDENCE and self.law is None:
+            self.law = as_struct(SamplingConfig())
+        self.guide = model._guidance(guidance)
+
+    def draws(self, model, n, B, noise, uniforms, dev):
+        """The (n, steps - 1, B, S) unmasking draws and (n, steps, nv, B, S) sampling draws of n frames: the caller's, or torch.rand."""
+        S, nv, steps = model.config.S, model.config.num_factored_vocabs, self.steps
+        nz = uni = None
+        if steps > 1 and self.unmask_mode != "greedy":
+            nz = (torch.rand(n, steps - 1, B, S, device=dev) if noise is None
+                  else noise.to(dev).reshape(n, -1, B, S)[:, :steps - 1].float().contiguous())
+        if self.temperature > 1e-8:
+            uni = (torch.rand(n, steps, nv, B, S, device=dev) if uniforms is None
+                   else uniforms.to(device=dev, dtype=torch.float32).contiguous())
+            assert uni.numel() == n * steps * nv * B * S, "uniforms: (n frames, maskgit_steps, num_factored_vocabs, B, S)"
+        return nz, uni
+
+
+def rollout_call(model, frames_BcS, actions_Bc, P, keep, f0, f1, resume, cache, dec, nz, uni):
+    """ONE genie_rollout_cached call: generates the absolute frames [f0, f1) of frames_BcS (B, cap, S) int64 in place.  actions_Bc: (B, cap)
+    int64 or None; cache: uint8 tensor of genie_prefix_cache_bytes(cfg, NB); dec: the _Decode options; nz / uni: this call's draws."""
+    from . import _lib
+    lib = _lib.load()
+    cfg, w = model._weights()[:2]
+    B, cap, S = frames_BcS.shape
+    assert frames_BcS.dtype == torch.int64 and frames_BcS.is_contiguous()
+    T = model.config.T
+    cond = None
+    if actions_Bc is not None:
+        assert actions_Bc.shape == (B, cap) and actions_Bc.dtype == torch.int64 and actions_Bc.is_contiguous()
+        cond = _lib.FrameCond(table=model.action_embed.weight.data_ptr(), ids=actions_Bc.data_ptr(), n_actions=model.config.action_vocab_size)
+    # the largest context the call runs sizes its workspace: `keep` for every window it opens after its first, and for the first the frames
+    # before f0 -- unless the call resumes in mid-window, where it runs none
+    wins = [w for w in window_schedule(P, keep, T, f1 - P) if w[3] > f0]
+    ctx = [fb - start for _, start, fb, _ in wins[1:]]
+    ctx.append(f0 - wins[0][1] if (not resume or f0 == wins[0][2]) else 1)
+    ws = model._workspace(B, guided=dec.guide is not None, rollout_ctx=max(ctx))
+    _lib.check(lib.genie_rollout_cached(cfg, w, frames_BcS.data_ptr(), B, P, keep, cap, f0, f1, int(resume), dec.steps, dec.temperature,
+                                        dec.mode, 0 if nz is None else nz.data_ptr(), 0 if uni is None else uni.data_ptr(),
+                                        int(dec.merge_commit), cache.data_ptr(), cache.numel(), ws.data_ptr(), ws.numel(),
+                                        torch.cuda.current_stream().cuda_stream, cond, dec.law, dec.guide), "genie_rollout_cached")
+
+
+def _rollout_cache(model, B, dec, dev):
+    from . import _lib
+    cfg = model._weights()[0]
+    return torch.empty(_lib.load().genie_prefix_cache_bytes(cfg, B if dec.guide is None else 2 * B), dtype=torch.uint8, device=dev)
+
+
+@torch.no_grad()
+def rollout_frames(model, prompt_BPHW: torch.LongTensor, n_new, keep=None, maskgit_steps=2, temperature=0.0, unmask_mode="random",
+                   noise=None, uniforms=None, action_ids=None, sampling=None, guidance=None, merge_commit=True):
+    """Generate n_new frames behind the P prompt frames of prompt_BPHW (B, P, H, W), past the model's window T if need be, in ONE library
+    call (genie_rollout_cached) -> (B, P + n_new, H, W).  Window 0 decodes frames [P, T); after that the window slides: the last ``keep``
+    frames (default P; 1 <= keep <= T - 1) are re-run as the context of the next hop = T - keep frames (window_schedule; positions are
+    absolute, so the KV cache cannot be shifted).  keep is a quality / cost dial: keep = T - 1 is the true sliding window.  Equal, bit
+    for bit, to chaining generate_frames_cached window by window on the same draws.
+    noise: optional (n_new, maskgit_steps - 1, B, S); uniforms: optional (n_new, maskgit_steps, num_factored_vocabs, B, S); fresh
+    torch.rand draws otherwise.  action_ids: (B, P + n_new), the actions of the absolute frames.  The other options: generate_frames_cached."""
+    cfg = model.config
+    pr = prompt_BPHW.to(torch.int64)
+    B, P = pr.shape[0], pr.shape[1]
+    keep = P if keep is None else int(keep)
+    n_new = int(n_new)
+    if n_new < 1:
+        raise ValueError("rollout_frames: n_new must be >= 1")
+    window_schedule(P, keep, cfg.T, n_new)   # (checks P and keep)
+    dev = pr.device
+    dec = _Decode(model, maskgit_steps, temperature, unmask_mode, sampling, guidance, merge_commit)
+    acts = _rollout_actions(model, action_ids, B, P + n_new)
+    frames = torch.full((B, P + n_new, cfg.S), model.mask_token_id, dtype=torch.int64, device=dev)
+    frames[:, :P] = pr.reshape(B, P, cfg.S)
+    nz, uni = dec.draws(model, n_new, B, noise, uniforms, dev)
+    rollout_call(model, frames, acts, P, keep, P, P + n_new, 0, _rollout_cache(model, B, dec, dev), dec, nz, uni)
+    return frames.view(B, P + n_new, model.h, model.w)
+
+
+class Rollout:
+    """An open-ended rollout: ``step(action)`` returns the next frame, ``extend(n, action_ids)`` the next n, each ONE
+    genie_rollout_cached call that resumes the temporal KV cache of the call before it (the first runs the prompt).  Same frames as
+    rollout_frames on the same draws, however the calls are split.  The object owns the (B, cap, S) token and (B, cap) action buffers
+    and the cache; the buffers grow by doubling cap (a copy, which leaves the cache valid).
+    prompt_actions: (B, P) actions of the prompt frames of an action-conditioned model; keep and the decode options: rollout_frames."""
+
+    def __init__(self, model, prompt_BPHW, keep=None, prompt_actions=None, maskgit_steps=2, temperature=0.0, unmask_mode="random",
+                 sampling=None, guidance=None, merge_commit=True, capacity=None):
+        cfg = model.config
+        pr = prompt_BPHW.to(torch.int64)
+        self.model, self.B, self.P = model, pr.shape[0], pr.shape[1]
+        self.keep = self.P if keep is None else int(keep)
+        window_schedule(self.P, self.keep, cfg.T, 0)   # (checks P and keep)
+        self.dec = _Decode(model, maskgit_steps, temperature, unmask_mode, sampling, guidance, merge_commit)
+        self.n = self.P   # frames so far
+        cap = max(self.P + 1, 2 * cfg.T if capacity is None else int(capacity))
+        self._frames = torch.full((self.B, cap, cfg.S), model.mask_token_id, dtype=torch.int64, device=pr.device)
+        self._frames[:, :self.P] = pr.reshape(self.B, self.P, cfg.S)
+        acts = _rollout_actions(model, prompt_actions, self.B, self.P, "prompt_actions")
+        self._acts = None
+        if acts is not None:
+            self._acts = torch.zeros(self.B, cap, dtype=torch.int64, device=pr.device)
+            self._acts[:, :self.P] = acts
+        self._cache = _rollout_cache(model, self.B, self.dec, pr.device)
+        self._resume = 0
+
+    @property
+    def frames(self):
+        """(B, n_so_far, H, W): the prompt and every frame generated so far."""
+        return self._frames[:, :self.n].reshape(self.B, self.n, self.model.h, self.model.w)
+
+    @property
+    def window(self):
+        """(j, start, slot) of the NEXT frame (frame_window)."""
+        return frame_window(self.n, self.P, self.keep, self.model.config.T)
+
+    def _grow(self, need):
+        cap = self._frames.shape[1]
+        if need <= cap:
+            return
+        while cap < need:
+            cap *= 2
+        frames = torch.full((self.B, cap, self._frames.shape[2]), self.model.mask_token_id, dtype=torch.int64, device=self._frames.device)
+        frames[:, :self.n] = self._frames[:, :self.n]
+        self._frames = frames
+        if self._acts is not None:
+            acts = torch.zeros(self.B, cap, dtype=torch.int64, device=frames.device)
+            acts[:, :self.n] = self._acts[:, :self.n]
+            self._acts = acts
+
+    @torch.no_grad()
+    def extend(self, n, action_ids=None, noise=None, uniforms=None):
+        """Generate the next n frames -> (B, n, H, W).  action_ids: (B, n) actions of the new frames; noise (n, steps - 1, B, S) and
+        uniforms (n, steps, nv, B, S): this call's draws, or fresh torch.rand ones."""
+        n = int(n)
+        if n < 1:
+            raise ValueError("Rollout.extend: n must be >= 1")
+        acts = _rollout_actions(self.model, action_ids, self.B, n)
+        f0, f1 = self.n, self.n + n
+        self._grow(f1)
+        if acts is not None:
+            self._acts[:, f0:f1] = acts
+        nz, uni = self.dec.draws(self.model, n, self.B, noise, uniforms, self._frames.device)
+        rollout_call(self.model, self._frames, self._acts, self.P, self.keep, f0, f1, self._resume, self._cache, self.dec, nz, uni)
+        self.n, self._resume = f1, 1
+        return self._frames[:, f0:f1].reshape(self.B, n, self.model.h, self.model.w)
+
+    def step(self, action=None, noise=None, uniforms=None):
+        """Generate the next frame under ``action`` (B,) -> (B, H, W).  noise (steps - 1, B, S), uniforms (steps, nv, B, S): its draws."""
+        a = None if action is None else torch.as_tensor(action).reshape(self.B, 1)
+        return self.extend(1, a, None if noise is None else noise[None], None if uniforms is None else uniforms[None])[:, 0]
+
+
 def write_outputs(outputs_THW: torch.LongTensor, output_dir, dataset_metadata: dict, args: dict):
     """video.bin (token_dtype of the source dataset) + metadata.json with the reference's extra keys
     (generate.py:105-116).  outputs for ONE example: (1, n, H, W) or (n, H, W)."""

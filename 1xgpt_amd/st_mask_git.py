@@ -248,11 +248,14 @@ class STMaskGIT(nn.Module):
         self._wide = sorted(packed.wide) if packed is not None else []
         return self._table
 
-    def _workspace(self, B, generate_prompt_frames=0, guided=False):
+    def _workspace(self, B, generate_prompt_frames=0, guided=False, rollout_ctx=0):
         """The model's workspace for B clips; generate_prompt_frames = P > 0: large enough for genie_generate_cached with P prompt frames too;
-        guided: for the guided loops on B clips (their passes run 2 B)."""
+        guided: for the guided loops on B clips (their passes run 2 B); rollout_ctx > 0: for genie_rollout_cached with contexts up to
+        that many frames too."""
         cfg = self._weights()[0]
         need = _lib.load().genie_workspace_bytes(cfg, B)
+        if rollout_ctx:
+            need = max(need, _lib.load().genie_rollout_workspace_bytes(cfg, B, rollout_ctx, int(guided)))
         if guided:
             need = max(need, _lib.load().genie_generate_guided_workspace_bytes(cfg, B, generate_prompt_frames or 1))
         elif generate_prompt_frames:
@@ -556,6 +559,12 @@ class STMaskGIT(nn.Module):
             step0_logits.append(logits)
         tokens = canvas.view(B, -1)
         return (tokens, torch.stack(step0_logits, dim=3)) if return_logits else tokens
+
+    def rollout(self, prompt_BPHW, n_new, keep=None, **kwargs):
+        """n_new frames behind the prompt frames (B, P, H, W), past the window T if need be -> (B, P + n_new, H, W): generate.rollout_frames
+        (one library call; the window slides by T - keep frames, re-running the last `keep` as its context)."""
+        from .generate import rollout_frames
+        return rollout_frames(self, prompt_BPHW, n_new, keep=keep, **kwargs)
 
     # ------------------------------------------------------------------ weights
     def init_weights(self):

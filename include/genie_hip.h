@@ -530,6 +530,48 @@ int genie_generate_cached_guided(const genie_cfg* cfg, const genie_weights* w, c
                                  size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
                                  const genie_frame_cond* cond, const genie_sampling* sampling, const genie_guidance* guidance);
 
+/* ---- rollout past the context window (ABI 3 addition; reference counterpart: none -- generate.py:77-103 stops at the window) ----------
+ * Positions are absolute (x = token_embed + (pos_embed[t, s] + action_row), genie_frame_cond above), so a frame that moves from slot t to
+ * slot t - hop changes its K / V in every layer: the temporal KV cache cannot be shifted.  A slide therefore RE-RUNS the kept context in
+ * its new slots, with the prompt sequence of genie_generate_cached (one multi-frame pass, else the clean pass, else frame by frame), and
+ * nothing of the cache is reused across a slide.
+ * Schedule.  T = cfg->T, prompt 1 <= P <= T - 1, 1 <= keep <= T - 1, hop = T - keep.  Frames are numbered absolutely over the whole rollout;
+ * frames [0, P) are the prompt.  A generated frame f >= P belongs to window
+ *     j(f) = 0 if f < T, else 1 + (f - T) / hop   (integer division);    start_j = j * hop;    slot(f) = f - start_j
+ * (slot in [P, T) for j = 0, in [keep, T) for j >= 1) and is decoded in slot(f) of window j(f): its context is the absolute frames
+ * [start_j, f) in slots 0 .. slot(f) - 1, its position rows are pos_embed[slot], and its action and those of its context are the actions
+ * of the ABSOLUTE frames.  Inside a window everything is the loop of genie_generate_cached_guided: `steps` one-frame passes, sample and
+ * mask step per frame, the commit of slot t merged with step 0 of slot t + 1 where merge_commit is set and the library covers it, and the
+ * last slot of a window is never committed.  The first frame of a window (f == P, or f >= T with slot(f) == keep) first has its context
+ * run into slots 0 .. slot(f) - 1; its step 0 is then a one-frame pass.
+ * Consequence: a rollout of N frames equals, in tokens, bit for bit, in every precision, chaining genie_generate_cached_ex / _guided
+ * window by window -- first P prompt frames and min(T - P, N) new ones, then the last `keep` frames as the prompt of min(hop, remaining)
+ * new ones --, each call with its window's slice of actions, noise and uniforms.  Cost: `steps` passes per frame plus one keep-frame
+ * context pass per hop frames; keep = T - 1 is the true sliding window.
+ *   frames (B, cap, S) int64, clip stride cap * S, in/out: [0, P) holds the prompt on entry, [0, f0) must be final; the call generates the
+ *     absolute frames [f0, f1), P <= f0 < f1 <= cap, writes each one's final tokens in place and reads its context from the same buffer.
+ *   resume 0: the context of f0's window, [start_j(f0), f0), is run from `frames` before f0 is decoded -- always valid; equal to
+ *     genie_generate_cached_ex on that window with f0 - start_j prompt frames.  resume 1: `cache` is what a previous call that ended at f0
+ *     left behind (slots of [start_j, f0 - 1) committed, frame f0 - 1 pending: a call NEVER commits its last frame); the call then begins
+ *     with the commit of f0 - 1 from `frames`, merged with step 0 of f0 by the rule above, so split calls enqueue the passes of one call.
+ *     Where f0 is the first frame of a window, resume is ignored and the context is re-run.
+ *   steps, temperature, unmask_mode, merge_commit, sampling, guidance: as genie_generate_cached_guided, same argument checks.
+ *   noise (f1 - f0, steps - 1, B, S), uniforms (f1 - f0, steps, num_factored, B, S): the draws of the frames of THIS call.
+ *   cond: ids is (B, cap) with clip stride `cap` -- the ONE place where the stride is not cfg->T -- and holds the actions of the absolute
+ *     frames; entries of frames >= f1 may be read but are never embedded.  One launch per window gathers the window's context tokens and its (NB, T) actions
+ *     (slots past cap: action 0, never embedded; under guidance the null half) for the passes, so a whole rollout is enqueued without a
+ *     host synchronisation.  There is no teacher_force_time and no logits0_out: neither has a meaning past the window.
+ *   cache: genie_prefix_cache_bytes(cfg, NB), NB = 2 B under guidance of scale != 1, else B.
+ *   workspace: genie_rollout_workspace_bytes(cfg, B, ctx_max, guided) with ctx_max = the largest context the call runs: max(P, keep) for
+ *     rollouts from the prompt and for resumed calls, f0 - start_j for a resume == 0 call in mid-window; >= the generate size of that
+ *     context; 0 on bad arguments (ctx_max outside [1, T - 1]).
+ * Argument errors return GENIE_E_ARG before anything is enqueued.  Tests: tests/test_rollout_cpu.py, tests/test_hip_rollout.py. */
+size_t genie_rollout_workspace_bytes(const genie_cfg* cfg, int B, int ctx_max, int guided);
+int genie_rollout_cached(const genie_cfg* cfg, const genie_weights* w, int64_t* frames, int B, int P, int keep, int cap, int f0, int f1,
+                         int resume, int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                         int merge_commit, float* cache, size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
+                         const genie_frame_cond* cond, const genie_sampling* sampling, const genie_guidance* guidance);
+
 /* ---- optional per-launch timing (bench.py's roofline leg) ------------------------------------------------
  * When enabled, every launch of a kernel whose class bit is set in `class_mask` is bracketed by a pair of
  * HIP events recorded on the launch stream.  genie_profile_read synchronises those events and returns, for

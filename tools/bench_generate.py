@@ -48,6 +48,44 @@ def guidance_ab(a, m, cfg, extra):
     print(json.dumps({"workload": "generate 8->8 frames under guidance, " + a.model + " " + a.precision, "results": res}))
 
 
+def rollout_ab(a, m, cfg, extra):
+    """rollout_frames at N new frames against generate_frames_cached at T - P new frames (P = 8, keep = --keep), one call per leg per round,
+    legs interleaved: per leg the median and the min-max spread over the rounds, in ms per generated frame.  --rollout 0 runs the
+    in-window leg alone (the A/B of a library that lacks the rollout)."""
+    synth = importlib.import_module("1xgpt_amd.synthetic")
+    G = importlib.import_module("1xgpt_amd.generate")
+    P, T, N = 8, cfg.T, a.rollout
+    res = []
+    for B in a.batches:
+        ex = torch.from_numpy(synth.make_clips(B, cfg, seed=7)).cuda().view(B, T, 16, 16)
+        for steps in a.steps:
+            legs = {"in_window": dict(fn=lambda ex=ex, steps=steps, nz=torch.rand(T - P, max(steps - 1, 1), B, cfg.S, device="cuda"):
+                                      G.generate_frames_cached(m, ex, P, steps, a.temperature, False, noise=nz, **extra),
+                                      frames=T - P, times=[])}
+            if N:
+                legs["rollout"] = dict(fn=lambda ex=ex, steps=steps, nz=torch.rand(N, max(steps - 1, 1), B, cfg.S, device="cuda"):
+                                       G.rollout_frames(m, ex[:, :P], N, keep=a.keep, maskgit_steps=steps, temperature=a.temperature,
+                                                        noise=nz, **extra),
+                                       frames=N, times=[])
+            for leg in legs.values():
+                for _ in range(2):
+                    leg["fn"]()
+            for _ in range(a.repeats):
+                for leg in legs.values():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    leg["fn"]()
+                    torch.cuda.synchronize()
+                    leg["times"].append(time.perf_counter() - t0)
+            for name, leg in legs.items():
+                t = [1e3 * x / leg["frames"] for x in sorted(leg["times"])]
+                res.append({"leg": name, "batch": B, "maskgit_steps": steps, "prompt": P, "keep": a.keep or P, "new_frames": leg["frames"],
+                            "sampler": bool(a.sampler), "ms_per_frame_median": t[len(t) // 2], "ms_per_frame_min": t[0],
+                            "ms_per_frame_max": t[-1]})
+                print(res[-1], flush=True)
+    print(json.dumps({"workload": f"rollout {P}->{N} frames against generate {P}->{T - P}, " + a.model + " " + a.precision, "results": res}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--precision", default="f16x3")
@@ -65,7 +103,11 @@ def main():
     ap.add_argument("--guidance_scale", type=float, default=None,
                     help="classifier-free guidance A/B on an action-conditioned variant of the model (8 actions, null action 0), KV-cache "
                          "schedule: per batch B, interleaved in one process, unguided at B, unguided at 2B and guided at B with this scale")
-    ap.add_argument("--repeats", type=int, default=7, help="interleaved rounds of the guidance A/B")
+    ap.add_argument("--repeats", type=int, default=7, help="interleaved rounds of the guidance A/B and of the rollout leg")
+    ap.add_argument("--rollout", type=int, default=None,
+                    help="rollout leg: ms per generated frame of rollout_frames at this many new frames (prompt 8) against generate_frames_cached "
+                         "at T - 8, interleaved in one process; 0 = the in-window leg alone")
+    ap.add_argument("--keep", type=int, default=None, help="context frames the rollout re-runs per window (default: the prompt's 8)")
     a = ap.parse_args()
     extra = {}
     if a.sampler:
@@ -83,6 +125,8 @@ def main():
     m = STMaskGIT(cfg, precision=a.precision).load_numpy_state_dict(synth.make_state_dict(cfg, seed=0)).to("cuda")
     if a.guidance_scale is not None:
         return guidance_ab(a, m, cfg, extra)
+    if a.rollout is not None:
+        return rollout_ab(a, m, cfg, extra)
     res = []
     for B in a.batches:
         ex = torch.from_numpy(synth.make_clips(B, cfg, seed=7)).cuda().view(B, 16, 16, 16)

@@ -5,7 +5,9 @@ written as [prompt | generated | ground truth] video.bin + metadata.json (readab
   python tools/generate.py --checkpoint_dir DIR --val_data_dir data/val_v1.1 --output_dir data/genie_generated
   python tools/generate.py --synthetic --model c35 --output_dir /tmp/gen
 An action-conditioned checkpoint (action_vocab_size > 0) generates with the example's actions from the dataset's actions.bin
-(refused without one); --guidance_scale W --null_action K decodes such a model under classifier-free guidance."""
+(refused without one); --guidance_scale W --null_action K decodes such a model under classifier-free guidance.
+--num_new_frames N rolls out N frames behind the prompt, past the model's window if need be (the window slides by T - keep frames and
+re-runs the last --keep frames as its context); the output is then [prompt | N generated | whatever ground truth exists]."""
 import argparse
 import importlib
 import os
@@ -37,6 +39,12 @@ def build_parser():
     ap.add_argument("--schedule", choices=["kv_cache", "full_forward"], default="kv_cache",
                     help="kv_cache: one-frame passes against a temporal KV cache (same frames up to f32 accumulation order); "
                          "full_forward: the reference's schedule, a full 16-frame forward per MaskGIT step (generate.py:81-95)")
+    ap.add_argument("--num_new_frames", type=int, default=None,
+                    help="Roll out this many frames behind the prompt in one library call, past the model's window if need be "
+                         "(default: fill the window, as the reference does).")
+    ap.add_argument("--keep", type=int, default=None,
+                    help="With --num_new_frames: frames of context each later window re-runs, 1 .. T-1 (default: --num_prompt_frames); "
+                         "T-1 is the true sliding window, smaller is cheaper.")
     return ap
 
 
@@ -67,6 +75,17 @@ def main():
             actions = item["action_ids"][None]
     model = model.to("cuda")
     ex = example.to("cuda").view(1, args.window_size, model.h, model.w)
+    if args.num_new_frames is not None:
+        P, N = args.num_prompt_frames, args.num_new_frames
+        if args.teacher_force_time or args.schedule != "kv_cache":
+            sys.exit("generate.py: --num_new_frames runs on the KV cache and has no teacher forcing in time")
+        if actions is not None and actions.shape[1] < P + N:
+            sys.exit(f"generate.py: {P} + {N} frames need as many actions, the example has {actions.shape[1]}: raise --window_size")
+        out = G.rollout_frames(model, ex[:, :P], N, keep=args.keep, maskgit_steps=args.maskgit_steps, temperature=args.temperature,
+                               unmask_mode=args.unmask_mode, action_ids=None if actions is None else actions[:, :P + N].to("cuda"),
+                               sampling=sampling, guidance=guidance)
+        print(G.write_outputs(torch.cat([out, ex[:, P:]], dim=1), args.output_dir, meta, vars(args)))
+        return
     fn = G.generate_frames_cached if args.schedule == "kv_cache" else G.generate_frames
     out = fn(model, ex, args.num_prompt_frames, args.maskgit_steps, args.temperature, args.teacher_force_time,
              action_ids=None if actions is None else actions.to("cuda"), sampling=sampling, unmask_mode=args.unmask_mode,
