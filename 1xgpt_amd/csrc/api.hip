@@ -65,12 +65,6 @@ static Workspace carve(const genie_cfg& c, int B, void* base) {
     w.unmasked = (uint8_t*)take((size_t)B * c.S);
     w.aux = take(M * c.d_model * 4);
     w.total = off;
-    w.tqkv = nullptr;
-    w.tcache = nullptr;
-    w.fcache = nullptr;
-    w.frame_t = -1;
-    w.frame_T = 0;
-    w.model_T = c.T;
     return w;
 }
 
@@ -114,59 +108,61 @@ static int check_ws(const genie_cfg& c, int B, void* ws, size_t bytes) {
     return GENIE_OK;
 }
 
-// ---- one SelfAttention + residual: x += proj(attn(qkv(u)))  (attention.py:36-61, st_transformer.py:74,78)
-static int attention_block(const genie_cfg& c, const genie_attn_weights& aw, const float* u, float* x, Workspace& w,
-                           int B, bool temporal, hipStream_t st) {
-    const int d = c.d_model, M = B * c.T * c.S;
-    float* qkv = (temporal && w.tqkv) ? w.tqkv : (float*)w.big;
-    float* ao = (float*)w.xn;  // u may alias w.xn: it is dead once qkv is computed
+// ---- temporal attention behind the qkv GEMM, shared by the three drivers (kernels.hpp)
+int temporal_attention(const genie_cfg& c, const genie_attn_weights& aw, const BlockPass& p, const TemporalQkv& tq, float* out,
+                       uint16_t* out16, size_t plane, bool in16, Workspace& w, int B, hipStream_t st) {
+    const int d = c.d_model, H = c.num_heads, Dh = c.head_dim;
     const float* nw = c.qk_norm ? aw.norm_w : nullptr;
     const float* nb = c.qk_norm ? aw.norm_b : nullptr;
-    if (temporal && w.frame_t >= 0) {  // single-frame decode: qkv -> cache slot frame_t, attend slots 0..frame_t
-        float* slot = w.fcache + (size_t)w.frame_t * c.S * 3 * d;
-        GENIE_TRY(launch_gemm_f32(u, d, (long)c.S * d, aw.qkv_w, d, 0, c.qkv_bias ? aw.qkv_b : nullptr, slot, 3 * d,
-                                  (long)w.frame_T * c.S * 3 * d, c.S, 3 * d, d, B, 0, 1.0f, st));
-        GENIE_TRY(launch_attn_temporal_single(w.fcache, ao, B, w.frame_T, c.S, w.frame_t, d, c.num_heads, c.head_dim,
-                                              c.attn_scale, nw, nb, st));
-        return launch_gemm_f32(ao, d, 0, aw.proj_w, d, 0, c.proj_bias ? aw.proj_b : nullptr, x, d, 0, M, d, d, 1,
-                               GEMM_ACCUM, 1.0f, st);
-    }
-    const int Tq = (temporal && w.tqkv && w.tq_frames > c.T) ? w.tq_frames : c.T;  // frames per clip in qkv's layout
-    if (Tq != c.T && B > 1)  // a short clean pass into a longer cache: one GEMM batch entry per clip
-        GENIE_TRY(launch_gemm_f32(u, d, (long)c.T * c.S * d, aw.qkv_w, d, 0, c.qkv_bias ? aw.qkv_b : nullptr, qkv, 3 * d,
-                                  (long)Tq * c.S * 3 * d, c.T * c.S, 3 * d, d, B, 0, 1.0f, st));
-    else
-    GENIE_TRY(launch_gemm_f32(u, d, 0, aw.qkv_w, d, 0, c.qkv_bias ? aw.qkv_b : nullptr, qkv, 3 * d, 0, M, 3 * d, d, 1,
-                              0, 1.0f, st));
-    if (temporal && w.stop_after_tqkv) return GENIE_OK;
-    if (!temporal) {
-        int rc = launch_attn_spatial_f32_mfma(qkv, ao, c.S, (long)B * c.T, d, c.num_heads, c.head_dim, c.attn_scale,
-                                              nw, nb, st);
-        if (rc == GENIE_E_UNSUPPORTED)  // no MFMA instantiation for this geometry: generic kernel
-            rc = launch_attn_generic(qkv, ao, c.S, (long)B * c.T, 1, c.S, 0, 1, d, c.num_heads, c.head_dim,
-                                     c.attn_scale, 0, nw, nb, st);
-        GENIE_TRY(rc);
-    } else if (w.tcache) {
-        GENIE_TRY(launch_attn_temporal_prefix(qkv, w.tcache, ao, B, c.T, c.S, d, c.num_heads, c.head_dim, c.attn_scale,
-                                              nw, nb, st, nullptr, 0, w.tshift));
+    if (p.is_decode())  // the GEMM filled cache slot frame_t: attend slots 0..frame_t
+        return launch_attn_temporal_single(p.cache, out, B, p.frame_T, c.S, p.frame_t, d, H, Dh, c.attn_scale, nw, nb, st, out16, plane,
+                                           in16);
+    const float* qkv = tq.base;
+    float* tmp = out16 ? w.logits : out;  // where a kernel without a 16-bit epilogue writes its f32 rows
+    if (p.reads_cache()) {
+        const int rc = launch_attn_temporal_prefix(qkv, p.cache, out, B, c.T, c.S, d, H, Dh, c.attn_scale, nw, nb, st, out16, plane,
+                                                   p.tshift, in16);
+        if (rc != GENIE_E_UNSUPPORTED || !out16 || in16) return rc;
+        GENIE_TRY(launch_attn_temporal_prefix(qkv, p.cache, tmp, B, c.T, c.S, d, H, Dh, c.attn_scale, nw, nb, st, nullptr, 0, p.tshift));
     } else {
-        int rc = launch_attn_temporal_f32_mfma(qkv, ao, B, c.T, c.S, d, c.num_heads, c.head_dim, c.attn_scale, nw, nb,
-                                               st, nullptr, 0, Tq);
-        if (rc == GENIE_E_UNSUPPORTED && !(Tq == c.T || B == 1)) {
+        const int Tq = p.tq_stride(c.T);
+        const int rc = launch_attn_temporal_f32_mfma(qkv, out, B, c.T, c.S, d, H, Dh, c.attn_scale, nw, nb, st, out16, plane, Tq, in16);
+        if (rc != GENIE_E_UNSUPPORTED || in16) return rc;
+        if (Tq != c.T && B > 1) {  // no MFMA instantiation for this geometry, and the generic kernel reads dense clips only
             set_error("strided temporal qkv needs the MFMA temporal kernel (8 <= frames <= 16)");
-            return GENIE_E_UNSUPPORTED;
+            return out16 ? GENIE_E_ARG : GENIE_E_UNSUPPORTED;  // (the codes the 16-bit drivers and the exact one have always returned here)
         }
-        if (rc == GENIE_E_UNSUPPORTED)
-            rc = launch_attn_generic(qkv, ao, c.T, (long)B * c.S, c.S, (long)c.T * c.S, 1, c.S, d, c.num_heads,
-                                     c.head_dim, c.attn_scale, 1, nw, nb, st);
-        GENIE_TRY(rc);
+        GENIE_TRY(launch_attn_generic(qkv, tmp, c.T, (long)B * c.S, c.S, (long)c.T * c.S, 1, c.S, d, H, Dh, c.attn_scale, 1, nw, nb, st));
     }
-    GENIE_TRY(launch_gemm_f32(ao, d, 0, aw.proj_w, d, 0, c.proj_bias ? aw.proj_b : nullptr, x, d, 0, M, d, d, 1,
-                              GEMM_ACCUM, 1.0f, st));
-    return GENIE_OK;
+    return out16 ? launch_to_operand16(tmp, out16, plane, (size_t)B * c.T * c.S * d, st) : GENIE_OK;
 }
 
-int st_block_exact(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, int B, hipStream_t st) {
+// ---- one SelfAttention + residual: x += proj(attn(qkv(u)))  (attention.py:36-61, st_transformer.py:74,78)
+static int attention_block(const genie_cfg& c, const genie_attn_weights& aw, const float* u, float* x, Workspace& w, const BlockPass& p,
+                           int B, bool temporal, hipStream_t st) {
+    const int d = c.d_model, M = B * c.T * c.S;
+    float* ao = (float*)w.xn;  // u may alias w.xn: it is dead once qkv is computed
+    const float* bias = c.qkv_bias ? aw.qkv_b : nullptr;
+    if (temporal) {
+        const TemporalQkv tq = temporal_qkv_target(c, p, (float*)w.big, B);
+        GENIE_TRY(launch_gemm_f32(u, d, tq.strideA, aw.qkv_w, d, 0, bias, tq.base + tq.off, 3 * d, tq.strideC, tq.rows, 3 * d, d,
+                                  tq.batch, 0, 1.0f, st));
+        if (p.stop_after_tqkv) return GENIE_OK;
+        GENIE_TRY(temporal_attention(c, aw, p, tq, ao, nullptr, 0, false, w, B, st));
+    } else {
+        float* qkv = (float*)w.big;
+        const float* nw = c.qk_norm ? aw.norm_w : nullptr;
+        const float* nb = c.qk_norm ? aw.norm_b : nullptr;
+        GENIE_TRY(launch_gemm_f32(u, d, 0, aw.qkv_w, d, 0, bias, qkv, 3 * d, 0, M, 3 * d, d, 1, 0, 1.0f, st));
+        int rc = launch_attn_spatial_f32_mfma(qkv, ao, c.S, (long)B * c.T, d, c.num_heads, c.head_dim, c.attn_scale, nw, nb, st);
+        if (rc == GENIE_E_UNSUPPORTED)  // no MFMA instantiation for this geometry: generic kernel
+            rc = launch_attn_generic(qkv, ao, c.S, (long)B * c.T, 1, c.S, 0, 1, d, c.num_heads, c.head_dim, c.attn_scale, 0, nw, nb, st);
+        GENIE_TRY(rc);
+    }
+    return launch_gemm_f32(ao, d, 0, aw.proj_w, d, 0, c.proj_bias ? aw.proj_b : nullptr, x, d, 0, M, d, d, 1, GEMM_ACCUM, 1.0f, st);
+}
+
+int st_block_exact(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, const BlockPass& p, int B, hipStream_t st) {
     const int d = c.d_model, M = B * c.T * c.S;
     float* xn = (float*)w.xn;
     // spatial: x += SpAttn(norm1(x))  (st_transformer.py:73-74)
@@ -175,10 +171,10 @@ int st_block_exact(const genie_cfg& c, const genie_layer_weights& lw, float* x, 
         GENIE_TRY(launch_layer_norm(x, lw.norm1_w, lw.norm1_b, xn, M, d, 1e-5f, st));
         u = xn;
     }
-    GENIE_TRY(attention_block(c, lw.spatial, u, x, w, B, false, st));
+    GENIE_TRY(attention_block(c, lw.spatial, u, x, w, p, B, false, st));
     // temporal: x += TmpAttn(x, causal), no pre-norm  (st_transformer.py:77-78)
-    GENIE_TRY(attention_block(c, lw.temporal, x, x, w, B, true, st));
-    if (w.stop_after_tqkv) return GENIE_OK;
+    GENIE_TRY(attention_block(c, lw.temporal, x, x, w, p, B, true, st));
+    if (p.stop_after_tqkv) return GENIE_OK;
     // MLP: x += fc2(gelu(fc1(norm2(x))))  (st_transformer.py:81, 16-25)
     u = x;
     if (!c.qk_norm) {
@@ -193,38 +189,27 @@ int st_block_exact(const genie_cfg& c, const genie_layer_weights& lw, float* x, 
     return GENIE_OK;
 }
 
-int st_block_bf16(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, int B, hipStream_t st);
-int prepare_bf16(const genie_cfg& c, const float* x, Workspace& w, int B, hipStream_t st);
-int st_block_f16x3(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, int B, hipStream_t st);
-int prepare_f16x3(const genie_cfg& c, const float* x, Workspace& w, int B, hipStream_t st);
-int readout_f16x3(const genie_cfg& c, const genie_weights& wt, const float* x, Workspace& w, int B, int t0, int t1,
-                  int layout, float* logits, hipStream_t st);
-int launch_pack_split(const float* src, uint16_t* dst, size_t n, hipStream_t st);
-int launch_linear_lowp(int precision, const uint16_t* x16, const uint16_t* W16, const float* b, float* y, int M, int N,
-                       int K, int gelu, int accumulate, hipStream_t st);
-int readout_bf16(const genie_cfg& c, const genie_weights& wt, const float* x, Workspace& w, int B, int t0, int t1,
-                 int layout, float* logits, hipStream_t st);
-
-static int st_block(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, int B, hipStream_t st) {
-    if (c.precision == GENIE_PREC_BF16) return st_block_bf16(c, lw, x, w, B, st);
-    if (c.precision == GENIE_PREC_F16X3) return st_block_f16x3(c, lw, x, w, B, st);
-    return st_block_exact(c, lw, x, w, B, st);
+// The layer loop of every pass: what runs in front of the first block, then `n` blocks, block i as the pass `make(i, next)` says
+// (next = the block behind it, NULL after the last).  The hand-offs between consecutive blocks live and die here.
+template <class MakePass>
+static int run_layers(const genie_cfg& c, const genie_layer_weights* layers, int n, float* x, Workspace& w, int B, hipStream_t st,
+                      MakePass make) {
+    if (c.precision == GENIE_PREC_BF16) GENIE_TRY(prepare_bf16(c, x, w, B, st));
+    if (c.precision == GENIE_PREC_F16X3) GENIE_TRY(prepare_f16x3(c, x, w, B, st));
+    BlockCarry carry;
+    for (int i = 0; i < n; ++i) {
+        const BlockPass p = make(i, i + 1 < n ? &layers[i + 1] : nullptr);
+        GENIE_STUDY_LAYER(i);
+        if (c.precision == GENIE_PREC_BF16) GENIE_TRY(st_block_bf16(c, layers[i], x, w, p, carry, B, st));
+        else if (c.precision == GENIE_PREC_F16X3) GENIE_TRY(st_block_f16x3(c, layers[i], x, w, p, B, st));
+        else GENIE_TRY(st_block_exact(c, layers[i], x, w, p, B, st));
+    }
+    return GENIE_OK;
 }
 
 static int decoder(const genie_cfg& c, const genie_weights& wt, float* x, Workspace& w, int B, hipStream_t st) {
-    if (c.precision == GENIE_PREC_BF16) GENIE_TRY(prepare_bf16(c, x, w, B, st));
-    if (c.precision == GENIE_PREC_F16X3) GENIE_TRY(prepare_f16x3(c, x, w, B, st));
-    w.ln1_done = w.qkv_planes_done = false;   // (hand-offs between consecutive blocks of ONE pass; a failed pass must not leave them set)
-    for (int i = 0; i < c.num_layers; ++i) {
-        w.skip_shadow_mlp = !c.qk_norm && i + 1 < c.num_layers;
-        w.next_layer = i + 1 < c.num_layers ? &wt.layers_host[i + 1] : nullptr;
-        GENIE_STUDY_LAYER(i);
-        const int rc = st_block(c, wt.layers_host[i], x, w, B, st);
-        w.skip_shadow_mlp = false;
-        w.next_layer = nullptr;
-        GENIE_TRY(rc);
-    }
-    return GENIE_OK;
+    return run_layers(c, wt.layers_host, c.num_layers, x, w, B, st,
+                      [&](int, const genie_layer_weights* next) { return BlockPass::plain(c, next, c.T); });
 }
 
 // out_x_proj on frames [t0,t1): token-major (B,nt,S,V) or BCTHW (B,V,nt,S) via the operand-swapped GEMM
@@ -414,9 +399,8 @@ int genie_st_block_forward(const genie_cfg* cfg, const genie_layer_weights* lw_h
     GENIE_CHECK_ARG(lw_host && x, "st_block_forward: NULL pointer");
     GENIE_TRY(check_ws(*cfg, B, workspace, workspace_bytes));
     Workspace w = carve(*cfg, B, workspace);
-    if (cfg->precision == GENIE_PREC_BF16) GENIE_TRY(prepare_bf16(*cfg, x, w, B, as_stream(stream)));
-    if (cfg->precision == GENIE_PREC_F16X3) GENIE_TRY(prepare_f16x3(*cfg, x, w, B, as_stream(stream)));
-    return st_block(*cfg, *lw_host, x, w, B, as_stream(stream));
+    return run_layers(*cfg, lw_host, 1, x, w, B, as_stream(stream),
+                      [&](int, const genie_layer_weights* next) { return BlockPass::plain(*cfg, next, cfg->T); });
 }
 
 int genie_decoder_forward(const genie_cfg* cfg, const genie_weights* wt, float* x, int B, void* workspace,
@@ -467,33 +451,16 @@ size_t genie_prefix_cache_bytes(const genie_cfg* cfg, int B) {
     return (size_t)cfg->num_layers * B * cfg->T * cfg->S * 3 * cfg->d_model * sizeof(float);
 }
 
-static int prefix_forward(const genie_cfg& c, const genie_weights& wt, const int64_t* ids, int B, float* cache,
-                          bool clean, int tshift, Workspace& w, hipStream_t st, int cache_frames = 0,
-                          const EmbedAct* act = nullptr) {
+// model_T: T of the model's own config (c is the pass's private copy with fewer frames)
+static int prefix_forward(const genie_cfg& c, const genie_weights& wt, const int64_t* ids, int B, float* cache, bool clean, int tshift,
+                          int model_T, Workspace& w, hipStream_t st, int cache_frames = 0, const EmbedAct* act = nullptr) {
     if (cache_frames <= 0) cache_frames = c.T;  // frames per clip in the cache layout (L, B, cache_frames, S, 3d)
     const size_t per_layer = (size_t)B * cache_frames * c.S * 3 * c.d_model;
     GENIE_TRY(launch_embed(c, wt, ids, B, w.x, st, act));
-    if (c.precision == GENIE_PREC_BF16) GENIE_TRY(prepare_bf16(c, w.x, w, B, st));
-    if (c.precision == GENIE_PREC_F16X3) GENIE_TRY(prepare_f16x3(c, w.x, w, B, st));
-    w.ln1_done = w.qkv_planes_done = false;
-    for (int i = 0; i < c.num_layers; ++i) {
-        if (clean) { w.tqkv = cache + i * per_layer; w.tcache = nullptr; w.tq_frames = cache_frames; }
-        else { w.tqkv = nullptr; w.tcache = cache + i * per_layer; w.tshift = tshift; }
-        w.skip_shadow_mlp = !c.qk_norm && i + 1 < c.num_layers;
-        w.next_layer = i + 1 < c.num_layers ? &wt.layers_host[i + 1] : nullptr;
-        w.stop_after_tqkv = clean && i + 1 == c.num_layers;  // nothing reads the clean pass's final hidden state
-        GENIE_STUDY_LAYER(i);
-        int rc = st_block(c, wt.layers_host[i], w.x, w, B, st);
-        w.skip_shadow_mlp = false;
-        w.next_layer = nullptr;
-        w.stop_after_tqkv = false;
-        w.tqkv = nullptr;
-        w.tq_frames = 0;
-        w.tcache = nullptr;
-        w.tshift = 0;
-        GENIE_TRY(rc);
-    }
-    return GENIE_OK;
+    return run_layers(c, wt.layers_host, c.num_layers, w.x, w, B, st, [&](int i, const genie_layer_weights* next) {
+        float* slice = cache + i * per_layer;  // (a clean pass stops after its last temporal qkv: nothing reads its final hidden state)
+        return clean ? BlockPass::clean(c, next, model_T, slice, cache_frames) : BlockPass::prefix(c, next, model_T, slice, tshift);
+    });
 }
 
 // The prefix passes run on `nframes` <= T frame slots per clip: a private copy of the config with T = nframes (dense
@@ -536,9 +503,9 @@ int genie_clean_pass_cond(const genie_cfg* cfg, const genie_weights* wt, const i
         return GENIE_E_UNSUPPORTED;
     }
     Workspace w = carve(c2, B, workspace);
-    w.model_T = cfg->T;
     EmbedAct act;
-    return prefix_forward(c2, w2, ids, B, cache, true, 0, w, as_stream(stream), cache_frames, frame_act(cond, cfg->S, 0, cfg->T, act));
+    return prefix_forward(c2, w2, ids, B, cache, true, 0, cfg->T, w, as_stream(stream), cache_frames,
+                          frame_act(cond, cfg->S, 0, cfg->T, act));
 }
 
 int genie_masked_frames_logits(const genie_cfg* cfg, const genie_weights* wt, const int64_t* frames, int B, int frame0,
@@ -560,10 +527,9 @@ int genie_masked_frames_logits_cond(const genie_cfg* cfg, const genie_weights* w
     genie_weights w2;
     GENIE_TRY(prefix_view(cfg, wt, B, frame0, nframes, cache_bytes, c2, w2));
     Workspace w = carve(c2, B, workspace);
-    w.model_T = cfg->T;
     hipStream_t st = as_stream(stream);
     EmbedAct act;   // slot i is clip frame frame0 + i
-    GENIE_TRY(prefix_forward(c2, w2, frames, B, const_cast<float*>(cache), false, frame0, w, st, 0,
+    GENIE_TRY(prefix_forward(c2, w2, frames, B, const_cast<float*>(cache), false, frame0, cfg->T, w, st, 0,
                              frame_act(cond, cfg->S, frame0, cfg->T, act)));
     return readout(c2, w2, w.x, w, B, 0, nframes, GENIE_LAYOUT_TOKEN_MAJOR, logits, st);
 }
@@ -596,28 +562,21 @@ int genie_frames_pass_cond(const genie_cfg* cfg, const genie_weights* wt, const 
         return GENIE_E_UNSUPPORTED;
     }
     Workspace w = carve(c1, B, workspace);
-    w.model_T = cfg->T;
     hipStream_t st = as_stream(stream);
     genie_weights w1 = *wt;
     w1.pos_embed = wt->pos_embed + (size_t)t0 * cfg->S * cfg->d_model;  // pos_embed_TSC[0, t0 + i]
     EmbedAct act;   // ... and the action of clip frame t0 + i
     GENIE_TRY(launch_embed(c1, w1, frame_ids, B, w.x, st, frame_act(cond, cfg->S, t0, cfg->T, act)));
+    const size_t per_layer = (size_t)B * cfg->T * cfg->S * 3 * cfg->d_model;
+    auto make = [&](int i, const genie_layer_weights* next) { return BlockPass::decode(c1, next, cfg->T, cache + i * per_layer, t0); };
     if (!fr) {
-        if (c1.precision == GENIE_PREC_BF16) GENIE_TRY(prepare_bf16(c1, w.x, w, B, st));
-        if (c1.precision == GENIE_PREC_F16X3) GENIE_TRY(prepare_f16x3(c1, w.x, w, B, st));
+        GENIE_TRY(run_layers(c1, wt->layers_host, c1.num_layers, w.x, w, B, st, make));
     } else {
         GENIE_TRY(frame_prepare_f16x3(c1, w.x, w, B, nf, st));
-    }
-    const size_t per_layer = (size_t)B * cfg->T * cfg->S * 3 * cfg->d_model;
-    for (int i = 0; i < c1.num_layers; ++i) {
-        w.fcache = cache + i * per_layer;
-        w.frame_t = t0;
-        w.frame_T = cfg->T;
-        w.skip_shadow_mlp = !c1.qk_norm && i + 1 < c1.num_layers;
-        const int rc = fr ? st_block_frame_f16x3(c1, wt->layers_host[i], w.x, w, B, nf, logits && !w.skip_shadow_mlp, st)
-                          : st_block(c1, wt->layers_host[i], w.x, w, B, st);
-        w.skip_shadow_mlp = false;
-        GENIE_TRY(rc);
+        for (int i = 0; i < c1.num_layers; ++i) {
+            const BlockPass p = make(i, i + 1 < c1.num_layers ? &wt->layers_host[i + 1] : nullptr);
+            GENIE_TRY(st_block_frame_f16x3(c1, wt->layers_host[i], w.x, w, p, B, nf, logits && !p.next_is_ln, st));
+        }
     }
     if (!logits) return GENIE_OK;
     if (fr) return readout_frame_f16x3(c1, *wt, w, B, nf, nf - 1, logits, st);

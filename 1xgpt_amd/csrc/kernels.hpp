@@ -6,7 +6,8 @@ namespace genie {
 
 enum { GEMM_GELU = 1, GEMM_ACCUM = 2, GEMM_BIAS_ALONG_M = 4 };
 
-// Workspace carving shared by api.hip and the precision-specific layer drivers (see carve() in api.hip).
+// Workspace carving shared by api.hip and the precision-specific layer drivers (see carve() in api.hip): buffers only.  What kind of
+// pass a layer call belongs to is a BlockPass, what one block hands to the next a BlockCarry (both below).
 struct Workspace {
     float* x;          // (M, d)   residual stream, f32 in every precision; offset 0 of the workspace
     void* xn;          // (M, d) x 4 bytes: exact = LayerNorm / attention output (f32);
@@ -18,29 +19,59 @@ struct Workspace {
     uint8_t* unmasked; // (B, S)
     void* aux;         // (M, d) x 4 bytes: f16x3 = split planes of the LayerNorm / attention output
     size_t total;
-    // teacher-forced prefix reuse (set per layer by the prefix entry points, NULL otherwise):
-    int model_T = 0;     // T of the MODEL's config (the passes below run on private copies with fewer frames): decides, once per
-                         // model, whether GENIE_PREC_BF16 keeps its temporal qkv / KV cache in bf16 (temporal_qkv16)
-    float* tqkv;         // where the temporal qkv GEMM writes (clean pass: this layer's slice of the cache)
-    int tq_frames = 0;   // frames per clip in the layout of `tqkv` (0 = dense: cfg.T); > cfg.T when a short clean pass fills a
-                         // full-length cache (generate: prompt frames into the T-frame KV cache)
-    const float* tcache; // non-NULL: temporal attention takes keys j < i + tshift from this cached qkv (masked-frames pass)
-    int tshift = 0;      // clip-frame offset of the masked-frames buffers against the cache (0 or 1)
-    // single-frame decode (generate with a temporal KV cache): the block runs on ONE frame (cfg.T == 1, dense
-    // (B,S,*) buffers); its temporal qkv is written into slot `frame_t` of this layer's cache slice and the
-    // attention reads slots 0..frame_t.
-    float* fcache;
-    int frame_t;   // -1 = off
-    int frame_T;   // frames per clip in the cache layout
-    // 16-bit precisions: the block's last GEMM need not refresh the 16-bit shadow of x when the next consumer is a
-    // LayerNorm (set by the layer loops for every layer but the last when the block has pre-norms)
-    bool skip_shadow_mlp = false;
-    // clean pass, last layer: only the temporal qkv (the cache entry) is needed -- the block returns right after that GEMM
-    bool stop_after_tqkv = false;
-    // GENIE_PREC_BF16, fused MLP kernel: the block that follows (NULL after the last one).  Its norm1 is applied in this block's
-    // MLP epilogue and `ln1_done` tells that block to skip its own LayerNorm launch.
-    const genie_layer_weights* next_layer = nullptr;
-    bool ln1_done = false;
+};
+
+// What one layer call is: built once per layer by the constructor function of its kind, read-only from then on.
+//   PLAIN   a full forward; no cache
+//   CLEAN   teacher-forced prefix reuse, first half: the temporal qkv GEMM writes this layer's slice of the cache
+//   PREFIX  ... second half (masked-frames pass): temporal attention takes keys j < i + tshift from the cached qkv
+//   DECODE  single-frame decode (generate with a temporal KV cache): the block runs on dense (B, nf, S, *) buffers; its temporal qkv is
+//           written into slot `frame_t` of this layer's cache slice and the attention reads slots 0..frame_t
+struct BlockPass {
+    enum Kind { PLAIN, CLEAN, PREFIX, DECODE };
+    const Kind kind;
+    float* const cache;     // this layer's slice of the temporal KV cache (NULL in a PLAIN pass).  A PREFIX pass only reads it: the
+                            // pointer is non-const because the fused temporal kernels take one `kv` argument for both directions
+    const int tq_frames;    // CLEAN: frames per clip in the cache layout; > cfg.T when a short clean pass fills a full-length cache
+                            // (generate: prompt frames into the T-frame KV cache)
+    const int tshift;       // PREFIX: clip-frame offset of the masked-frames buffers against the cache (0 or 1)
+    const int frame_t;      // DECODE: the cache slot of the pass's first frame
+    const int frame_T;      // DECODE: frames per clip in the cache layout
+    const int model_T;      // T of the MODEL's config (cache passes run on private copies with fewer frames): decides, once per model,
+                            // whether GENIE_PREC_BF16 keeps its temporal qkv / KV cache in bf16 (temporal_qkv16)
+    const bool stop_after_tqkv;   // CLEAN, last layer: only the temporal qkv (the cache entry) is needed -- the block returns right after it
+    // the block that follows (NULL after the last one) and whether it opens with a LayerNorm: then this block's last GEMM need not
+    // refresh the 16-bit shadow of x, and the GENIE_PREC_BF16 fused MLP kernel can apply that norm1 in its epilogue (BlockCarry)
+    const genie_layer_weights* const next_layer;
+    const bool next_is_ln;
+
+    static BlockPass plain(const genie_cfg& c, const genie_layer_weights* next, int model_T) {
+        return {PLAIN, nullptr, 0, 0, -1, 0, model_T, false, next, next && !c.qk_norm};
+    }
+    static BlockPass clean(const genie_cfg& c, const genie_layer_weights* next, int model_T, float* slice, int cache_frames) {
+        return {CLEAN, slice, cache_frames, 0, -1, 0, model_T, /*stop_after_tqkv=*/next == nullptr, next, next && !c.qk_norm};
+    }
+    static BlockPass prefix(const genie_cfg& c, const genie_layer_weights* next, int model_T, const float* slice, int tshift) {
+        return {PREFIX, const_cast<float*>(slice), 0, tshift, -1, 0, model_T, false, next, next && !c.qk_norm};
+    }
+    static BlockPass decode(const genie_cfg& c, const genie_layer_weights* next, int model_T, float* slice, int frame_t) {
+        return {DECODE, slice, 0, 0, frame_t, model_T, model_T, false, next, next && !c.qk_norm};
+    }
+    bool is_plain() const { return kind == PLAIN; }
+    bool is_decode() const { return kind == DECODE; }
+    bool writes_cache() const { return kind == CLEAN; }   // (DECODE writes its slot too, through its own GEMM shape)
+    bool reads_cache() const { return kind == PREFIX; }
+    bool is_cache_pass() const { return kind == CLEAN || kind == PREFIX; }
+    // frames per clip in the layout the temporal qkv GEMM writes (T = the pass's own frame count)
+    int tq_stride(int T) const { return kind == CLEAN && tq_frames > T ? tq_frames : T; }
+    bool strided(int T) const { return tq_stride(T) != T; }
+    int fused_mode() const { return kind == CLEAN ? 1 : kind == PREFIX ? 2 : 0; }   // `mode` of the fused temporal kernels
+};
+
+// What one block of a pass leaves for the next one (GENIE_PREC_BF16, fused MLP kernel).  Owned by the layer loop, which starts every
+// pass with a fresh one.
+struct BlockCarry {
+    bool ln1_done = false;          // norm1 of the next block is already applied (in xn16): that block skips its LayerNorm launch
     bool qkv_planes_done = false;   // ... or even its spatial operand planes (in `big`): that block goes straight to its attention kernel
 };
 
@@ -281,14 +312,61 @@ int launch_gemm16_sm_ln(int npl, const float* x, long ldx, const float* ln_g, co
 int launch_pack_frame_w16(const float* src, uint16_t* dst, int N, int K, hipStream_t st);
 bool frame_path_takes(const genie_cfg& c, const genie_layer_weights& lw, long rows);
 int frame_prepare_f16x3(const genie_cfg& c, const float* x, Workspace& w, int B, int nf, hipStream_t st);
-int st_block_frame_f16x3(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, int B, int nf, bool want_xs,
-                         hipStream_t st);
+// p: the DECODE pass of this layer (cache slice, first slot, frames per clip of the cache)
+int st_block_frame_f16x3(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, const BlockPass& p, int B, int nf,
+                         bool want_xs, hipStream_t st);
 int launch_frame_linear(const uint16_t* A, const uint16_t* W, const float* bias, float* y, int M, int N, int K, int mode, hipStream_t st);
 int readout_frame_f16x3(const genie_cfg& c, const genie_weights& wt, Workspace& w, int B, int nf, int f_out, float* logits,
                         hipStream_t st);
 // kernels_attn_dma.hip: spatial attention over the operand planes written by launch_gemm16_pp(G16X_OUT16 | G16X_QKV)
 int launch_attn_spatial_dma(int npl, const uint16_t* qkv16, long n_seq, int d, int H, int Dh, uint16_t* out16, size_t out_plane,
                             hipStream_t st);
+// The layer drivers, one per precision (api.hip: exact; kernels_bf16.hip: the two 16-bit ones), what runs in front of the first layer
+// and behind the last one, and the 16-bit Linear entries of the C ABI.
+int st_block_exact(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, const BlockPass& p, int B, hipStream_t st);
+int st_block_bf16(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, const BlockPass& p, BlockCarry& carry, int B,
+                  hipStream_t st);
+int st_block_f16x3(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, const BlockPass& p, int B, hipStream_t st);
+int prepare_bf16(const genie_cfg& c, const float* x, Workspace& w, int B, hipStream_t st);
+int prepare_f16x3(const genie_cfg& c, const float* x, Workspace& w, int B, hipStream_t st);
+int readout_bf16(const genie_cfg& c, const genie_weights& wt, const float* x, Workspace& w, int B, int t0, int t1, int layout,
+                 float* logits, hipStream_t st);
+int readout_f16x3(const genie_cfg& c, const genie_weights& wt, const float* x, Workspace& w, int B, int t0, int t1, int layout,
+                  float* logits, hipStream_t st);
+int launch_pack_split(const float* src, uint16_t* dst, size_t n, hipStream_t st);
+int launch_linear_lowp(int precision, const uint16_t* x16, const uint16_t* W16, const float* b, float* y, int M, int N, int K, int gelu,
+                       int accumulate, hipStream_t st);
+
+// (One description of the GEMM in place of the three copies of its decode / strided / dense shape logic in the drivers.)
+// Where the temporal qkv GEMM of a pass writes and how it is batched: `base + off` (f32 elements; a bf16 qkv lives at the same element
+// offset of the same base), `rows` rows per batch entry, `batch` entries strideA / strideC elements apart.
+//   DECODE: slot frame_t of the cache slice, one entry per clip;  a short CLEAN pass into a longer cache at B > 1: one entry per clip;
+//   otherwise ONE dense (M, 3d) GEMM into the cache slice (CLEAN) or into `dense`
+struct TemporalQkv {
+    float* base;
+    size_t off;
+    int rows, batch;
+    long strideA, strideC;
+};
+inline TemporalQkv temporal_qkv_target(const genie_cfg& c, const BlockPass& p, float* dense, int B) {
+    const int d = c.d_model, Tq = p.tq_stride(c.T);
+    if (p.is_decode())
+        return {p.cache, (size_t)p.frame_t * c.S * 3 * d, c.S, B, (long)c.S * d, (long)p.frame_T * c.S * 3 * d};
+    float* base = p.writes_cache() ? p.cache : dense;
+    if (Tq != c.T && B > 1) return {base, 0, c.T * c.S, B, (long)c.T * c.S * d, (long)Tq * c.S * 3 * d};
+    return {base, 0, B * c.T * c.S, 1, 0, 0};
+}
+// f32 rows -> a 16-bit driver's operand form: f16 split planes (plane != 0: hi at out16, lo at out16 + plane) or bf16 (plane == 0) --
+// the (out16, plane) convention of the attention launchers above, which take the same pair
+inline int launch_to_operand16(const float* src, uint16_t* out16, size_t plane, size_t n, hipStream_t st) {
+    return plane ? launch_split_f16(src, out16, plane, n, st) : launch_pack_bf16(src, out16, n, st);
+}
+// Temporal attention behind that GEMM, for all three drivers: decode slot / prefix / f32-MFMA / generic kernel.  The result leaves as
+// f32 rows (out) or, out16 != NULL, 16-bit: bf16 (plane == 0) or f16 split planes (hi at out16, lo at out16 + plane); a kernel that
+// cannot write 16-bit writes f32 into w.logits and a convert follows.  in16: the qkv and the cache hold bf16 (temporal_qkv16).
+int temporal_attention(const genie_cfg& c, const genie_attn_weights& aw, const BlockPass& p, const TemporalQkv& tq, float* out,
+                       uint16_t* out16, size_t plane, bool in16, Workspace& w, int B, hipStream_t st);
+
 int launch_adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
                  float weight_decay, int step, float grad_mult, const double* sumsq, float max_norm, hipStream_t st);
 

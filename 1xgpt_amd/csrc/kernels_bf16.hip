@@ -781,7 +781,7 @@ int launch_gemm16_ex(int npl, const uint16_t* A, long lda, long planeA, const ui
 // ---- fc2 of the one-frame passes at 2,048-4,096 rows (generate at 8-16 clips): N = d = 512 gives 64-128 tiles of 128x128 for a
 // K = 2,048 contraction -- half of the CUs idle and a 64-step K chain.  Split K in two over the GEMM's batch index (256 workgroups,
 // 32 steps each) into two f32 slabs in the (idle) logits scratch, then x += bias + slab0 + slab1 in that fixed order
-// (profiles/r03_fc2_splitk_ab.txt).  Only in the one-frame passes of generate (w.frame_t >= 0) and only when the 16-bit shadow of x is
+// (profiles/r03_fc2_splitk_ab.txt).  Only in the one-frame passes of generate (a DECODE pass) and only when the 16-bit shadow of x is
 // not wanted (every layer but the last of a LayerNorm model): full forwards keep the single fused K chain at every batch size.
 __global__ __launch_bounds__(256) void splitk2_residual_kernel(float* __restrict__ x, const float* __restrict__ s0,
                                                                const float* __restrict__ s1, const float* __restrict__ bias,
@@ -799,13 +799,13 @@ __global__ __launch_bounds__(256) void splitk2_residual_kernel(float* __restrict
 // returns GENIE_E_UNSUPPORTED when the shape is not in that range (the caller then runs the fused-epilogue GEMM)
 template <int NPL>
 static int fc2_splitk2(const genie_cfg& c, const uint16_t* h16, long plane_h, const uint16_t* w16, long plane_w, const float* bias,
-                       float* x, Workspace& w, int M, hipStream_t st, bool wide = false) {
+                       float* x, Workspace& w, const BlockPass& p, int M, hipStream_t st, bool wide = false) {
     static const int on = study_env("GENIE_FC2_SPLITK", 1);
     const int d = c.d_model, K = c.hidden;
     const long tiles = (long)((M + 127) / 128) * ((d + 127) / 128);
     const size_t V = (size_t)c.factored_vocab * c.num_factored;
-    if (!on || w.frame_t < 0 /* one-frame passes only: a clip's fc2 sum order must not depend on the batch size of a full forward */ ||
-        !w.skip_shadow_mlp || !w.logits || K < 2048 || K % 256 || d % 4 || tiles > 128 || (long)M * d <= (1L << 19) ||
+    if (!on || !p.is_decode() /* one-frame passes only: a clip's fc2 sum order must not depend on the batch size of a full forward */ ||
+        !p.next_is_ln || !w.logits || K < 2048 || K % 256 || d % 4 || tiles > 128 || (long)M * d <= (1L << 19) ||
         V < 2 * (size_t)d || wide)
         return GENIE_E_UNSUPPORTED;
     float* slabs = w.logits;
@@ -862,12 +862,28 @@ static int spatial_attention_fused(int npl, const genie_cfg& c, const genie_laye
     return launch_attn_spatial_dma(npl, qkv16, n_seq, d, c.num_heads, c.head_dim, out16, out_plane, st);
 }
 
+// Spatial attention from the f32 qkv, for both 16-bit drivers: the split kernel writes the operand form itself; any other geometry goes
+// through the generic kernel (f32 rows in the logits scratch) and a convert
+static int spatial_attention_f32qkv(const genie_cfg& c, const genie_attn_weights& aw, const float* qkv, Workspace& w, int B,
+                                    uint16_t* out16, size_t plane, hipStream_t st) {
+    const int d = c.d_model;
+    const float* nw = c.qk_norm ? aw.norm_w : nullptr;
+    const float* nb = c.qk_norm ? aw.norm_b : nullptr;
+    const int rc = launch_attn_spatial_split(qkv, nullptr, c.S, (long)B * c.T, d, c.num_heads, c.head_dim, c.attn_scale, nw, nb, st,
+                                             out16, plane);
+    if (rc != GENIE_E_UNSUPPORTED) return rc;
+    GENIE_TRY(launch_attn_generic(qkv, w.logits, c.S, (long)B * c.T, 1, c.S, 0, 1, d, c.num_heads, c.head_dim, c.attn_scale, 0, nw, nb,
+                                  st));
+    return launch_to_operand16(w.logits, out16, plane, (size_t)B * c.T * c.S * d, st);
+}
+
 // bf16 precision contract (mirrored by oracle.genie_oracle.BF16_MFMA):
 //   * every nn.Linear operand is bf16 (weights packed once; activations rounded by their producer)
 //   * accumulation, bias, GELU, LayerNorm and the residual stream are f32
 //   * qkv leaves its GEMM as f32 and the attention core runs on the f32-MFMA kernels of the exact path (its
 //     output is rounded to bf16 for the out-projection) -- attention is ~6 % of the FLOPs.
-int st_block_bf16(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, int B, hipStream_t st) {
+int st_block_bf16(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, const BlockPass& p, BlockCarry& carry, int B,
+                  hipStream_t st) {
     const int d = c.d_model, M = B * c.T * c.S;
     uint16_t* x16 = (uint16_t*)w.xn;              // bf16 shadow of the residual stream
     uint16_t* xn16 = x16 + (size_t)M * d;         // LayerNorm output, then attention output
@@ -876,25 +892,23 @@ int st_block_bf16(const genie_cfg& c, const genie_layer_weights& lw, float* x, W
     GENIE_CHECK_ARG(lw.spatial.qkv_w16 && lw.spatial.proj_w16 && lw.temporal.qkv_w16 && lw.temporal.proj_w16 &&
                         lw.fc1_w16 && lw.fc2_w16,
                     "bf16 precision needs packed bf16 weights (genie_pack_bf16)");
-    const float* nws = c.qk_norm ? lw.spatial.norm_w : nullptr;
-    const float* nbs = c.qk_norm ? lw.spatial.norm_b : nullptr;
-    const float* nwt = c.qk_norm ? lw.temporal.norm_w : nullptr;
-    const float* nbt = c.qk_norm ? lw.temporal.norm_b : nullptr;
+    // t16: the temporal qkv (and the KV cache slices) hold bf16 -- the qkv GEMM stores 2 bytes per value instead of 4 and the attention
+    // kernels (HBM-bound) read half the bytes; softmax and both products stay f32 inside them
+    const bool t16 = temporal_qkv16(c, p.model_T);
+    const BlockCarry prev = carry;   // what the previous block's fused MLP kernel already did for this one; taken, so that it is read once
+    carry = BlockCarry();
     // Will the temporal sub-block run as the fused kernel?  Then it rounds its operands from the f32 rows itself and the spatial kernel in
     // front need not write the bf16 shadow of x (134 MB per layer at 64 clips it would write and the temporal kernel read).
     static const int no_shadow_env = study_env("GENIE_T_FROM_F32", 1);   // (a study-build knob: the shipping library reads no environment)
-    const bool fused_t = w.frame_t < 0 && !w.tqkv && !w.tcache && !w.stop_after_tqkv && temporal_qkv16(c, w.model_T) &&
-                         temporal_fused_takes(c, lw.temporal, B);
+    const bool fused_t = p.is_plain() && t16 && temporal_fused_takes(c, lw.temporal, B);
     // ... or, in the prefix-cache passes, as the fused kernel that keeps the K / V fragment images in the cache slice (kernels_fused_prefix.hip)
-    const bool frag_t = w.frame_t < 0 && (w.tqkv || w.tcache) && (!w.tqkv || w.tq_frames <= c.T) && temporal_qkv16(c, w.model_T) &&
-                        temporal_prefix_fused_takes(c, lw.temporal, B, w.model_T);
+    const bool frag_t = p.is_cache_pass() && !p.strided(c.T) && t16 && temporal_prefix_fused_takes(c, lw.temporal, B, p.model_T);
     const bool shadow16 = !((fused_t || frag_t) && no_shadow_env);
     // spatial
     const uint16_t* u = x16;
     int rc = GENIE_E_UNSUPPORTED;
     bool qkv_done = false, proj_done = false;
-    if (w.qkv_planes_done) {   // the previous block's fused MLP kernel left this block's operand planes in `big`
-        w.qkv_planes_done = false;
+    if (prev.qkv_planes_done) {   // the previous block's fused MLP kernel left this block's operand planes in `big`
         rc = launch_spatial_attn_proj_bf16(c, lw.spatial, (const uint16_t*)w.big, x, shadow16 ? x16 : nullptr, (long)B * c.T, st);
         if (rc == GENIE_OK) proj_done = true;
         else if (rc == GENIE_E_UNSUPPORTED)   // (fewer sequences than the fused kernel takes: the stand-alone attention kernel reads the same planes, proj GEMM below)
@@ -911,38 +925,25 @@ int st_block_bf16(const genie_cfg& c, const genie_layer_weights& lw, float* x, W
     }
     if (!qkv_done) {
         if (!c.qk_norm) {
-            if (!w.ln1_done)   // (else: the previous block's fused MLP kernel wrote norm1(x) into xn16)
+            if (!prev.ln1_done)   // (else: the previous block's fused MLP kernel wrote norm1(x) into xn16)
                 GENIE_TRY(launch_layer_norm_bf16(x, lw.norm1_w, lw.norm1_b, xn16, M, d, 1e-5f, st));
             u = xn16;
         }
         rc = spatial_attention_fused(1, c, lw, u, 0, 0, w, B, xn16, 0, st, x, x16, &proj_done, shadow16);
     }
-    w.ln1_done = false;
     if (rc == GENIE_E_UNSUPPORTED) {
-    if (!qkv_done)
-    GENIE_TRY(launch_gemm16<1>(u, d, 0, lw.spatial.qkv_w16, d, 0, c.qkv_bias ? lw.spatial.qkv_b : nullptr, qkv, nullptr,
-                               0, 3 * d, M, 3 * d, d, G16_OUTF32, 1.0f, st));
-    rc = launch_attn_spatial_split(qkv, nullptr, c.S, (long)B * c.T, d, c.num_heads, c.head_dim, c.attn_scale, nws,
-                                   nbs, st, xn16, 0);
-    if (rc == GENIE_E_UNSUPPORTED) {
-        GENIE_TRY(launch_attn_generic(qkv, w.logits, c.S, (long)B * c.T, 1, c.S, 0, 1, d, c.num_heads, c.head_dim,
-                                      c.attn_scale, 0, nws, nbs, st));
-        rc = launch_pack_bf16(w.logits, xn16, (size_t)M * d, st);
-    }
+        if (!qkv_done)
+            GENIE_TRY(launch_gemm16<1>(u, d, 0, lw.spatial.qkv_w16, d, 0, c.qkv_bias ? lw.spatial.qkv_b : nullptr, qkv, nullptr,
+                                       0, 3 * d, M, 3 * d, d, G16_OUTF32, 1.0f, st));
+        rc = spatial_attention_f32qkv(c, lw.spatial, qkv, w, B, xn16, 0, st);
     }
     GENIE_TRY(rc);
     if (!proj_done)
-    GENIE_TRY(launch_gemm16<1>(xn16, d, 0, lw.spatial.proj_w16, d, 0, c.proj_bias ? lw.spatial.proj_b : nullptr, x, x16,
-                               0, d, M, d, d, G16_ACCUM | G16_OUTF32 | G16_OUT16, 1.0f, st));
-    // temporal (no pre-norm): operand = bf16 shadow of x.  t16: the temporal qkv (and the KV cache slices) hold bf16 -- the qkv
-    // GEMM stores 2 bytes per value instead of 4 and the attention kernels (HBM-bound) read half the bytes; softmax and both
-    // products stay f32 inside them
-    const bool t16 = temporal_qkv16(c, w.model_T);
-    const int oflag = t16 ? G16_OUT16 : G16_OUTF32;
-    float* tq = w.tqkv ? w.tqkv : qkv;
-    uint16_t* tq16 = reinterpret_cast<uint16_t*>(tq);
+        GENIE_TRY(launch_gemm16<1>(xn16, d, 0, lw.spatial.proj_w16, d, 0, c.proj_bias ? lw.spatial.proj_b : nullptr, x, x16,
+                                   0, d, M, d, d, G16_ACCUM | G16_OUTF32 | G16_OUT16, 1.0f, st));
+    // temporal (no pre-norm): operand = bf16 shadow of x
     bool temporal_done = false;
-    if (w.frame_t < 0 && !w.tqkv && !w.tcache && !w.stop_after_tqkv && t16) {
+    if (p.is_plain() && t16) {
         // plain full-clip forward of the shipped geometry: qkv + attention + proj + residual in ONE kernel, the qkv never
         // leaves the registers (kernels_fused.hip); same rounding points as the launches below
         // (the bf16 shadow of x exists unless the fused spatial kernel ran and was told not to write it)
@@ -951,72 +952,40 @@ int st_block_bf16(const genie_cfg& c, const genie_layer_weights& lw, float* x, W
         else if (rc != GENIE_E_UNSUPPORTED) return rc;
     }
     if (frag_t) {   // prefix-cache passes of the shipped geometry: one kernel, the cache slice holds K / V fragment images
-        GENIE_TRY(launch_temporal_prefix_fused_bf16(c, lw.temporal, x, reinterpret_cast<uint16_t*>(w.tqkv ? w.tqkv : const_cast<float*>(w.tcache)),
-                                                    B, w.tqkv ? 1 : 2, w.tshift, w.model_T, st));
-        if (w.stop_after_tqkv) return GENIE_OK;
+        GENIE_TRY(launch_temporal_prefix_fused_bf16(c, lw.temporal, x, reinterpret_cast<uint16_t*>(p.cache), B, p.fused_mode(), p.tshift,
+                                                    p.model_T, st));
+        if (p.stop_after_tqkv) return GENIE_OK;
         temporal_done = true;
     }
     if (!temporal_done) {
-    if (w.frame_t >= 0) {  // single-frame decode: qkv -> cache slot frame_t, attend slots 0..frame_t
-        float* slot = w.fcache + (size_t)w.frame_t * c.S * 3 * d;
-        uint16_t* slot16 = reinterpret_cast<uint16_t*>(w.fcache) + (size_t)w.frame_t * c.S * 3 * d;
-        GENIE_TRY(launch_gemm16<1>(x16, d, 0, lw.temporal.qkv_w16, d, 0, c.qkv_bias ? lw.temporal.qkv_b : nullptr, t16 ? nullptr : slot,
-                                   t16 ? slot16 : nullptr, 0, 3 * d, c.S, 3 * d, d, oflag, 1.0f, st, B, (long)c.S * d,
-                                   (long)w.frame_T * c.S * 3 * d));
-        rc = launch_attn_temporal_single(w.fcache, nullptr, B, w.frame_T, c.S, w.frame_t, d, c.num_heads, c.head_dim,
-                                         c.attn_scale, nwt, nbt, st, xn16, 0, t16);
-    } else {
-    const int Tq = (w.tqkv && w.tq_frames > c.T) ? w.tq_frames : c.T;  // frames per clip in tq's layout
-    if (Tq != c.T && B > 1)  // a short clean pass into a longer cache: one GEMM batch entry per clip
-        GENIE_TRY(launch_gemm16<1>(x16, d, 0, lw.temporal.qkv_w16, d, 0, c.qkv_bias ? lw.temporal.qkv_b : nullptr, t16 ? nullptr : tq,
-                                   t16 ? tq16 : nullptr, 0, 3 * d, c.T * c.S, 3 * d, d, oflag, 1.0f, st, B, (long)c.T * c.S * d,
-                                   (long)Tq * c.S * 3 * d));
-    else
-    GENIE_TRY(launch_gemm16<1>(x16, d, 0, lw.temporal.qkv_w16, d, 0, c.qkv_bias ? lw.temporal.qkv_b : nullptr, t16 ? nullptr : tq,
-                               t16 ? tq16 : nullptr, 0, 3 * d, M, 3 * d, d, oflag, 1.0f, st));
-    if (w.stop_after_tqkv) return GENIE_OK;
-    if (w.tcache) {
-        rc = launch_attn_temporal_prefix(tq, w.tcache, nullptr, B, c.T, c.S, d, c.num_heads, c.head_dim, c.attn_scale,
-                                         nwt, nbt, st, xn16, 0, w.tshift, t16);
-        if (rc == GENIE_E_UNSUPPORTED && !t16) {
-            GENIE_TRY(launch_attn_temporal_prefix(tq, w.tcache, w.logits, B, c.T, c.S, d, c.num_heads, c.head_dim,
-                                                  c.attn_scale, nwt, nbt, st, nullptr, 0, w.tshift));
-            rc = launch_pack_bf16(w.logits, xn16, (size_t)M * d, st);
-        }
-    } else {
-        rc = launch_attn_temporal_f32_mfma(tq, nullptr, B, c.T, c.S, d, c.num_heads, c.head_dim, c.attn_scale, nwt, nbt,
-                                           st, xn16, 0, Tq, t16);
-        if (rc == GENIE_E_UNSUPPORTED && !t16) {
-            GENIE_CHECK_ARG(Tq == c.T || B == 1, "strided temporal qkv needs the MFMA temporal kernel (8 <= frames <= 16)");
-            GENIE_TRY(launch_attn_generic(tq, w.logits, c.T, (long)B * c.S, c.S, (long)c.T * c.S, 1, c.S, d, c.num_heads,
-                                          c.head_dim, c.attn_scale, 1, nwt, nbt, st));
-            rc = launch_pack_bf16(w.logits, xn16, (size_t)M * d, st);
-        }
-    }
-    }
-    GENIE_TRY(rc);
-    // the 16-bit shadow of x is only read by a Linear that has no LayerNorm in front: temporal qkv always, fc1 and the next
-    // block's spatial qkv only in the qk-norm variant, the readout after the last block
-    GENIE_TRY(launch_gemm16<1>(xn16, d, 0, lw.temporal.proj_w16, d, 0, c.proj_bias ? lw.temporal.proj_b : nullptr, x,
-                               x16, 0, d, M, d, d, G16_ACCUM | G16_OUTF32 | (c.qk_norm ? G16_OUT16 : 0), 1.0f, st));
+        const TemporalQkv tq = temporal_qkv_target(c, p, qkv, B);
+        GENIE_TRY(launch_gemm16<1>(x16, d, 0, lw.temporal.qkv_w16, d, 0, c.qkv_bias ? lw.temporal.qkv_b : nullptr,
+                                   t16 ? nullptr : tq.base + tq.off, t16 ? reinterpret_cast<uint16_t*>(tq.base) + tq.off : nullptr, 0,
+                                   3 * d, tq.rows, 3 * d, d, t16 ? G16_OUT16 : G16_OUTF32, 1.0f, st, tq.batch, tq.strideA, tq.strideC));
+        if (p.stop_after_tqkv) return GENIE_OK;
+        GENIE_TRY(temporal_attention(c, lw.temporal, p, tq, nullptr, xn16, 0, t16, w, B, st));
+        // the 16-bit shadow of x is only read by a Linear that has no LayerNorm in front: temporal qkv always, fc1 and the next
+        // block's spatial qkv only in the qk-norm variant, the readout after the last block
+        GENIE_TRY(launch_gemm16<1>(xn16, d, 0, lw.temporal.proj_w16, d, 0, c.proj_bias ? lw.temporal.proj_b : nullptr, x,
+                                   x16, 0, d, M, d, d, G16_ACCUM | G16_OUTF32 | (c.qk_norm ? G16_OUT16 : 0), 1.0f, st));
     }
     // MLP
-    if (w.frame_t < 0) {   // LayerNorm + fc1 + GELU + fc2 + residual in one kernel for the shipped geometry (kernels_fused.hip)
-        const genie_layer_weights* nx = w.next_layer;
-        if (nx && nx->norm1_w && nx->norm1_b && w.skip_shadow_mlp) {
+    if (!p.is_decode()) {   // LayerNorm + fc1 + GELU + fc2 + residual in one kernel for the shipped geometry (kernels_fused.hip)
+        const genie_layer_weights* nx = p.next_layer;
+        if (nx && nx->norm1_w && nx->norm1_b && p.next_is_ln) {
             rc = GENIE_E_UNSUPPORTED;
             if (nx->spatial.fused_w16 && (nx->spatial.w16_wide & GENIE_FUSED_QKV_STREAM)) {
                 // ... and the next block's spatial qkv Linear too: its operand planes (in `big`, where its qkv GEMM would put them)
                 rc = launch_mlp_fused_bf16(c, lw, x, nullptr, (long)M, st, nx->norm1_w, nx->norm1_b,
                                            nx->spatial.fused_w16 + GENIE_SPATIAL_PROJ_FUSED_ELEMS, (uint16_t*)w.big);
-                if (rc == GENIE_OK) w.qkv_planes_done = true;
+                if (rc == GENIE_OK) carry.qkv_planes_done = true;
             }
             if (rc == GENIE_E_UNSUPPORTED) {
                 rc = launch_mlp_fused_bf16(c, lw, x, xn16, (long)M, st, nx->norm1_w, nx->norm1_b);
-                if (rc == GENIE_OK) w.ln1_done = true;
+                if (rc == GENIE_OK) carry.ln1_done = true;
             }
         } else {
-            rc = launch_mlp_fused_bf16(c, lw, x, w.skip_shadow_mlp ? nullptr : x16, (long)M, st);
+            rc = launch_mlp_fused_bf16(c, lw, x, p.next_is_ln ? nullptr : x16, (long)M, st);
         }
         if (rc != GENIE_E_UNSUPPORTED) return rc;
     }
@@ -1029,20 +998,17 @@ int st_block_bf16(const genie_cfg& c, const genie_layer_weights& lw, float* x, W
         else if (r2 != GENIE_E_UNSUPPORTED) return r2;
     }
     if (!fc1_done) {
-    if (!c.qk_norm) {
-        GENIE_TRY(launch_layer_norm_bf16(x, lw.norm2_w, lw.norm2_b, xn16, M, d, 1e-5f, st));
-        u = xn16;
+        if (!c.qk_norm) {
+            GENIE_TRY(launch_layer_norm_bf16(x, lw.norm2_w, lw.norm2_b, xn16, M, d, 1e-5f, st));
+            u = xn16;
+        }
+        GENIE_TRY(launch_gemm16<1>(u, d, 0, lw.fc1_w16, d, 0, c.mlp_bias ? lw.fc1_b : nullptr, nullptr, big16, 0, c.hidden,
+                                   M, c.hidden, d, G16_GELU | G16_OUT16, 1.0f, st));
     }
-    GENIE_TRY(launch_gemm16<1>(u, d, 0, lw.fc1_w16, d, 0, c.mlp_bias ? lw.fc1_b : nullptr, nullptr, big16, 0, c.hidden,
-                               M, c.hidden, d, G16_GELU | G16_OUT16, 1.0f, st));
-    }
-    {
-        const int rs = fc2_splitk2<1>(c, big16, 0, lw.fc2_w16, 0, c.mlp_bias ? lw.fc2_b : nullptr, x, w, M, st);
-        if (rs != GENIE_E_UNSUPPORTED) return rs;
-    }
-    GENIE_TRY(launch_gemm16<1>(big16, c.hidden, 0, lw.fc2_w16, c.hidden, 0, c.mlp_bias ? lw.fc2_b : nullptr, x, x16, 0,
-                               d, M, d, c.hidden, G16_ACCUM | G16_OUTF32 | (w.skip_shadow_mlp ? 0 : G16_OUT16), 1.0f, st));
-    return GENIE_OK;
+    const int rs = fc2_splitk2<1>(c, big16, 0, lw.fc2_w16, 0, c.mlp_bias ? lw.fc2_b : nullptr, x, w, p, M, st);
+    if (rs != GENIE_E_UNSUPPORTED) return rs;
+    return launch_gemm16<1>(big16, c.hidden, 0, lw.fc2_w16, c.hidden, 0, c.mlp_bias ? lw.fc2_b : nullptr, x, x16, 0, d, M, d, c.hidden,
+                            G16_ACCUM | G16_OUTF32 | (p.next_is_ln ? 0 : G16_OUT16), 1.0f, st);
 }
 
 // The bf16 shadow of x must exist before the first layer when the block has no pre-norm (qk_norm configs).
@@ -1076,7 +1042,7 @@ int readout_bf16(const genie_cfg& c, const genie_weights& wt, const float* x, Wo
 // Buffers: w.xn  = split planes of the residual stream x (hi | lo), M*d each
 //          w.aux = split planes of the LayerNorm output, then of the attention output
 //          w.big = qkv as f32 (M*3d), later the split planes of the MLP hidden (M*hidden each)
-int st_block_f16x3(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, int B, hipStream_t st) {
+int st_block_f16x3(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, const BlockPass& p, int B, hipStream_t st) {
     const int d = c.d_model, M = B * c.T * c.S, hid = c.hidden;
     const size_t pd = (size_t)M * d, ph = (size_t)M * hid;
     uint16_t* xs = (uint16_t*)w.xn;
@@ -1091,10 +1057,6 @@ int st_block_f16x3(const genie_cfg& c, const genie_layer_weights& lw, float* x, 
     const int wsq = (lw.spatial.w16_wide & GENIE_WIDE_QKV) ? G16_WIDEW : 0, wsp = (lw.spatial.w16_wide & GENIE_WIDE_PROJ) ? G16_WIDEW : 0;
     const int wtq = (lw.temporal.w16_wide & GENIE_WIDE_QKV) ? G16_WIDEW : 0, wtp = (lw.temporal.w16_wide & GENIE_WIDE_PROJ) ? G16_WIDEW : 0;
     const int wf1 = (lw.w16_wide & GENIE_WIDE_FC1) ? G16_WIDEW : 0, wf2 = (lw.w16_wide & GENIE_WIDE_FC2) ? G16_WIDEW : 0;
-    const float* nws = c.qk_norm ? lw.spatial.norm_w : nullptr;
-    const float* nbs = c.qk_norm ? lw.spatial.norm_b : nullptr;
-    const float* nwt = c.qk_norm ? lw.temporal.norm_w : nullptr;
-    const float* nbt = c.qk_norm ? lw.temporal.norm_b : nullptr;
     // ---- spatial
     GENIE_STUDY_CLASS(0);
     const uint16_t* u = xs;
@@ -1115,72 +1077,31 @@ int st_block_f16x3(const genie_cfg& c, const genie_layer_weights& lw, float* x, 
         rc = spatial_attention_fused(2, c, lw, u, pd, pw_qkv, w, B, as, pd, st);
     }
     if (rc == GENIE_E_UNSUPPORTED) {
-    if (!qkv_done)
-    GENIE_TRY(launch_gemm16<2>(u, d, pd, lw.spatial.qkv_w16, d, pw_qkv, c.qkv_bias ? lw.spatial.qkv_b : nullptr, qkv,
-                               nullptr, 0, 3 * d, M, 3 * d, d, G16_OUTF32 | wsq, 1.0f, st));
-    rc = launch_attn_spatial_split(qkv, nullptr, c.S, (long)B * c.T, d, c.num_heads, c.head_dim, c.attn_scale, nws,
-                                   nbs, st, as, pd);
-    if (rc == GENIE_E_UNSUPPORTED) {  // generic kernel writes f32 into x-sized scratch (logits region), then split
-        float* tmp = w.logits;
-        GENIE_TRY(launch_attn_generic(qkv, tmp, c.S, (long)B * c.T, 1, c.S, 0, 1, d, c.num_heads, c.head_dim,
-                                      c.attn_scale, 0, nws, nbs, st));
-        rc = launch_split_f16(tmp, as, pd, pd, st);
-    }
+        if (!qkv_done)
+            GENIE_TRY(launch_gemm16<2>(u, d, pd, lw.spatial.qkv_w16, d, pw_qkv, c.qkv_bias ? lw.spatial.qkv_b : nullptr, qkv,
+                                       nullptr, 0, 3 * d, M, 3 * d, d, G16_OUTF32 | wsq, 1.0f, st));
+        rc = spatial_attention_f32qkv(c, lw.spatial, qkv, w, B, as, pd, st);
     }
     GENIE_TRY(rc);
     GENIE_STUDY_CLASS(2);
     // the shipped geometry: temporal qkv Linear + attention as one kernel on the f32 rows of x (kernels_fused_f16x3.hip) -- the spatial
     // out-projection then need not write the split planes of x; in the prefix-cache passes the cache slice holds that kernel's k, v accumulators
-    const bool fused_tq = w.frame_t < 0 && (!w.tqkv || w.tq_frames <= c.T) &&
-                          temporal_qkv_attn_f16x3_takes(c, lw.temporal, B, w.model_T, w.tqkv || w.tcache);
+    const bool fused_tq = !p.is_decode() && !p.strided(c.T) &&
+                          temporal_qkv_attn_f16x3_takes(c, lw.temporal, B, p.model_T, p.is_cache_pass());
     GENIE_TRY(launch_gemm16<2>(as, d, pd, lw.spatial.proj_w16, d, pw_proj, c.proj_bias ? lw.spatial.proj_b : nullptr, x,
                                xs, pd, d, M, d, d, G16_ACCUM | G16_OUTF32 | (fused_tq ? 0 : G16_OUT16) | wsp, 1.0f, st));
     // ---- temporal
     GENIE_STUDY_CLASS(1);
-    float* tq = w.tqkv ? w.tqkv : qkv;
     if (fused_tq) {
-        GENIE_TRY(launch_temporal_qkv_attn_f16x3(c, lw.temporal, x, as, (long)pd, w.tqkv ? w.tqkv : const_cast<float*>(w.tcache), B,
-                                                 w.tqkv ? 1 : (w.tcache ? 2 : 0), w.tshift, w.model_T, st));
-        if (w.stop_after_tqkv) return GENIE_OK;
-        rc = GENIE_OK;
-    } else if (w.frame_t >= 0) {  // single-frame decode: qkv -> cache slot frame_t, attend slots 0..frame_t
-        float* slot = w.fcache + (size_t)w.frame_t * c.S * 3 * d;
-        GENIE_TRY(launch_gemm16<2>(xs, d, pd, lw.temporal.qkv_w16, d, pw_qkv, c.qkv_bias ? lw.temporal.qkv_b : nullptr,
-                                   slot, nullptr, 0, 3 * d, c.S, 3 * d, d, G16_OUTF32 | wtq, 1.0f, st, B, (long)c.S * d,
-                                   (long)w.frame_T * c.S * 3 * d));
-        rc = launch_attn_temporal_single(w.fcache, nullptr, B, w.frame_T, c.S, w.frame_t, d, c.num_heads, c.head_dim,
-                                         c.attn_scale, nwt, nbt, st, as, pd);
+        GENIE_TRY(launch_temporal_qkv_attn_f16x3(c, lw.temporal, x, as, (long)pd, p.cache, B, p.fused_mode(), p.tshift, p.model_T, st));
+        if (p.stop_after_tqkv) return GENIE_OK;
     } else {
-    const int Tq = (w.tqkv && w.tq_frames > c.T) ? w.tq_frames : c.T;  // frames per clip in tq's layout
-    if (Tq != c.T && B > 1)  // a short clean pass into a longer cache: one GEMM batch entry per clip
-        GENIE_TRY(launch_gemm16<2>(xs, d, pd, lw.temporal.qkv_w16, d, pw_qkv, c.qkv_bias ? lw.temporal.qkv_b : nullptr, tq,
-                                   nullptr, 0, 3 * d, c.T * c.S, 3 * d, d, G16_OUTF32 | wtq, 1.0f, st, B, (long)c.T * c.S * d,
-                                   (long)Tq * c.S * 3 * d));
-    else
-    GENIE_TRY(launch_gemm16<2>(xs, d, pd, lw.temporal.qkv_w16, d, pw_qkv, c.qkv_bias ? lw.temporal.qkv_b : nullptr, tq,
-                               nullptr, 0, 3 * d, M, 3 * d, d, G16_OUTF32 | wtq, 1.0f, st));
-    if (w.stop_after_tqkv) return GENIE_OK;
-    if (w.tcache) {
-        rc = launch_attn_temporal_prefix(tq, w.tcache, nullptr, B, c.T, c.S, d, c.num_heads, c.head_dim, c.attn_scale,
-                                         nwt, nbt, st, as, pd, w.tshift);
-        if (rc == GENIE_E_UNSUPPORTED) {
-            GENIE_TRY(launch_attn_temporal_prefix(tq, w.tcache, w.logits, B, c.T, c.S, d, c.num_heads, c.head_dim,
-                                                  c.attn_scale, nwt, nbt, st, nullptr, 0, w.tshift));
-            rc = launch_split_f16(w.logits, as, pd, pd, st);
-        }
-    } else {
-        rc = launch_attn_temporal_f32_mfma(tq, nullptr, B, c.T, c.S, d, c.num_heads, c.head_dim, c.attn_scale, nwt, nbt,
-                                           st, as, pd, Tq);
-        if (rc == GENIE_E_UNSUPPORTED) {
-            GENIE_CHECK_ARG(Tq == c.T || B == 1, "strided temporal qkv needs the MFMA temporal kernel (8 <= frames <= 16)");
-            float* tmp = w.logits;
-            GENIE_TRY(launch_attn_generic(tq, tmp, c.T, (long)B * c.S, c.S, (long)c.T * c.S, 1, c.S, d, c.num_heads,
-                                          c.head_dim, c.attn_scale, 1, nwt, nbt, st));
-            rc = launch_split_f16(tmp, as, pd, pd, st);
-        }
+        const TemporalQkv tq = temporal_qkv_target(c, p, qkv, B);
+        GENIE_TRY(launch_gemm16<2>(xs, d, pd, lw.temporal.qkv_w16, d, pw_qkv, c.qkv_bias ? lw.temporal.qkv_b : nullptr, tq.base + tq.off,
+                                   nullptr, 0, 3 * d, tq.rows, 3 * d, d, G16_OUTF32 | wtq, 1.0f, st, tq.batch, tq.strideA, tq.strideC));
+        if (p.stop_after_tqkv) return GENIE_OK;
+        GENIE_TRY(temporal_attention(c, lw.temporal, p, tq, nullptr, as, pd, false, w, B, st));
     }
-    }
-    GENIE_TRY(rc);
     GENIE_STUDY_CLASS(3);
     GENIE_TRY(launch_gemm16<2>(as, d, pd, lw.temporal.proj_w16, d, pw_proj, c.proj_bias ? lw.temporal.proj_b : nullptr,
                                x, xs, pd, d, M, d, d, G16_ACCUM | G16_OUTF32 | (c.qk_norm ? G16_OUT16 : 0) | wtp, 1.0f, st));
@@ -1195,21 +1116,18 @@ int st_block_f16x3(const genie_cfg& c, const genie_layer_weights& lw, float* x, 
         else if (r2 != GENIE_E_UNSUPPORTED) return r2;
     }
     if (!fc1_done) {
-    if (!c.qk_norm) {
-        GENIE_TRY(launch_layer_norm_split(x, lw.norm2_w, lw.norm2_b, as, pd, M, d, 1e-5f, st));
-        u = as;
-    }
-    GENIE_TRY(launch_gemm16<2>(u, d, pd, lw.fc1_w16, d, pw_fc, c.mlp_bias ? lw.fc1_b : nullptr, nullptr, hs, ph, hid, M,
-                               hid, d, G16_GELU | G16_OUT16 | wf1, 1.0f, st));
+        if (!c.qk_norm) {
+            GENIE_TRY(launch_layer_norm_split(x, lw.norm2_w, lw.norm2_b, as, pd, M, d, 1e-5f, st));
+            u = as;
+        }
+        GENIE_TRY(launch_gemm16<2>(u, d, pd, lw.fc1_w16, d, pw_fc, c.mlp_bias ? lw.fc1_b : nullptr, nullptr, hs, ph, hid, M,
+                                   hid, d, G16_GELU | G16_OUT16 | wf1, 1.0f, st));
     }
     GENIE_STUDY_CLASS(5);
-    {
-        const int rs = fc2_splitk2<2>(c, hs, (long)ph, lw.fc2_w16, (long)pw_fc, c.mlp_bias ? lw.fc2_b : nullptr, x, w, M, st, wf2 != 0);
-        if (rs != GENIE_E_UNSUPPORTED) return rs;
-    }
-    GENIE_TRY(launch_gemm16<2>(hs, hid, ph, lw.fc2_w16, hid, pw_fc, c.mlp_bias ? lw.fc2_b : nullptr, x, xs, pd, d, M, d,
-                               hid, G16_ACCUM | G16_OUTF32 | (w.skip_shadow_mlp ? 0 : G16_OUT16) | wf2, 1.0f, st));
-    return GENIE_OK;
+    const int rs = fc2_splitk2<2>(c, hs, (long)ph, lw.fc2_w16, (long)pw_fc, c.mlp_bias ? lw.fc2_b : nullptr, x, w, p, M, st, wf2 != 0);
+    if (rs != GENIE_E_UNSUPPORTED) return rs;
+    return launch_gemm16<2>(hs, hid, ph, lw.fc2_w16, hid, pw_fc, c.mlp_bias ? lw.fc2_b : nullptr, x, xs, pd, d, M, d, hid,
+                            G16_ACCUM | G16_OUTF32 | (p.next_is_ln ? 0 : G16_OUT16) | wf2, 1.0f, st);
 }
 
 int prepare_f16x3(const genie_cfg& c, const float* x, Workspace& w, int B, hipStream_t st) {

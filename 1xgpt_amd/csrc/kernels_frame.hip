@@ -1078,8 +1078,8 @@ static long frm_min_rows() {
     return v;
 }
 
-int st_block_frame_f16x3(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, int B, int nf, bool want_xs,
-                         hipStream_t st) {
+int st_block_frame_f16x3(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, const BlockPass& p, int B, int nf,
+                         bool want_xs, hipStream_t st) {
     const int d = c.d_model, S = c.S, H = c.num_heads, hid = c.hidden;
     const int M = B * nf * S, nw = d / 64;
     const bool mid = M >= frm_min_rows() && M % 128 == 0 && d % 128 == 0;
@@ -1162,8 +1162,8 @@ int st_block_frame_f16x3(const genie_cfg& c, const genie_layer_weights& lw, floa
     {
         FrGemmArgs g = a;
         g.A = xs; g.W = wq_t; g.bias = c.qkv_bias ? lw.temporal.qkv_b : nullptr; g.N = 3 * d; g.K = d;
-        g.Cf = w.fcache + (size_t)w.frame_t * S * 3 * d; g.ldc = 3 * d; g.rows_per_batch = (long)nf * S;
-        g.strideC = (long)w.frame_T * S * 3 * d;
+        g.Cf = p.cache + (size_t)p.frame_t * S * 3 * d; g.ldc = 3 * d; g.rows_per_batch = (long)nf * S;
+        g.strideC = (long)p.frame_T * S * 3 * d;
         ProfScope prof(GENIE_KC_GEMM, 2.0 * M * 3.0 * d * d, 4.0 * M * d + 4.0 * 3 * d * d + 4.0 * M * 3 * d, st,
                        mid ? "gemm16_frm_kernel (temporal qkv -> cache)" : "gemm16_fr_kernel (temporal qkv -> cache)");
         if (mid) GENIE_TRY(launch_frm_any<FR_EPI_F32>(g, st));
@@ -1171,13 +1171,13 @@ int st_block_frame_f16x3(const genie_cfg& c, const genie_layer_weights& lw, floa
     }
     {
         const long n = (long)M * H;
-        ProfScope prof(GENIE_KC_ATTN_TEMPORAL, 4.0 * (w.frame_t + nf) * c.head_dim * (double)n, (double)n * c.head_dim * 4.0 * (2 * (w.frame_t + nf) + 2), st,
+        ProfScope prof(GENIE_KC_ATTN_TEMPORAL, 4.0 * (p.frame_t + nf) * c.head_dim * (double)n, (double)n * c.head_dim * 4.0 * (2 * (p.frame_t + nf) + 2), st,
                        "attn_temporal_fr_kernel");
         if (c.head_dim == 64)
-            attn_temporal_fr_kernel<64><<<(unsigned)((n + 3) / 4), 256, 0, st>>>(w.fcache, as, n, w.frame_T, S, w.frame_t, nf, d, H, c.attn_scale,
+            attn_temporal_fr_kernel<64><<<(unsigned)((n + 3) / 4), 256, 0, st>>>(p.cache, as, n, p.frame_T, S, p.frame_t, nf, d, H, c.attn_scale,
                                                                                  qkn ? lw.temporal.norm_w : nullptr, qkn ? lw.temporal.norm_b : nullptr);
         else
-            attn_temporal_fr_kernel<32><<<(unsigned)((n + 3) / 4), 256, 0, st>>>(w.fcache, as, n, w.frame_T, S, w.frame_t, nf, d, H, c.attn_scale,
+            attn_temporal_fr_kernel<32><<<(unsigned)((n + 3) / 4), 256, 0, st>>>(p.cache, as, n, p.frame_T, S, p.frame_t, nf, d, H, c.attn_scale,
                                                                                  qkn ? lw.temporal.norm_w : nullptr, qkn ? lw.temporal.norm_b : nullptr);
         GENIE_LAUNCH_CHECK("attn_temporal_fr");
     }

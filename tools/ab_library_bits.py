@@ -1,0 +1,248 @@
+#!/usr/bin/env python3
+"""Do two builds of libgenie_hip.so compute the same bits with the same launches?  (The check of a host-code-only change.)
+
+    python 1xgpt_amd/build.py --variant parent          # at the commit to compare against
+    python tools/ab_library_bits.py 1xgpt_amd/lib_ab_parent.so 1xgpt_amd/libgenie_hip.so
+
+One battery runs in two fresh child processes, one per library (GENIE_HIP_LIBRARY), each under its own time limit; the second is not
+started when the first fails.  Per case a child records the return code, the SHA-256 of every output tensor's bytes (equal digests =
+zero differing bits) and, per kernel class, the name / launch-count table of genie_profile_kernels.  The parent process compares the two
+records and exits non-zero on any difference.
+
+The battery: every pass kind (full forward, clean pass + masked-frames pass at frame0 0 and 1, a half-length clean pass into a full-length
+cache at 1 and 2 clips, one- and two-frame decode passes, the cached generate loop with 2 MaskGIT steps and the merged commit, one
+STBlock) in all three precisions, for a LayerNorm and a qk-norm model, at three geometries.  A case the library refuses (e.g. two frames
+per pass outside f16x3) counts through its return code.  WATCHED names the kernels whose dispatch depends on the pass kind: the battery
+as a whole must reach each of them in the first library, else the battery itself has failed.  Two kernels of that kind carry no name a
+table could show: the launches of attn_spatial_dma are profiled unnamed (they are counted, and compared, as "(unnamed)" of the spatial
+attention class behind the 16-bit gemm16_pp qkv GEMMs), and splitk2_residual_kernel is launched outside any profiler scope (the d 512
+bf16 decode passes at 8 clips are inside the shape window of fc2_splitk2; its two-slab GEMM in front is counted).  For both a proxy
+is printed with the watched lines, and the first one is required."""
+import argparse
+import ctypes
+import hashlib
+import importlib
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# (name, d_model, heads, T, S, clips of the main cases)
+GEOMETRIES = [("d64", 64, 2, 4, 16, 3),        # generic attention kernels, ragged GEMM tiles
+              ("d256", 256, 8, 16, 256, 8),    # the shipped geometry: 8 clips = every fused bf16 kernel, chip-filling GEMMs
+              ("d512", 512, 8, 16, 256, 8)]    # heads of 64
+PRECISIONS = ["exact", "bf16", "f16x3"]
+WATCHED = ["spatial_attn_proj_bf16_kernel", "temporal_fused_bf16_kernel", "mlp_fused_bf16_kernel", "temporal_prefix_fused_bf16_kernel",
+           "temporal_qkv_attn_f16x3_kernel", "gemm16_pp_kernel", "gemm16_sm_ln_kernel"]
+N_CLASSES = 6   # GENIE_KC_COUNT
+
+
+def child(out_path):
+    sys.path.insert(0, REPO)
+    import numpy as np
+    import torch
+    _lib = importlib.import_module("1xgpt_amd._lib")
+    G = importlib.import_module("1xgpt_amd.generate")
+    synth = importlib.import_module("1xgpt_amd.synthetic")
+    GenieConfig = importlib.import_module("1xgpt_amd.config").GenieConfig
+    STMaskGIT = importlib.import_module("1xgpt_amd.st_mask_git").STMaskGIT
+    lib = _lib.load()
+    record = {}
+
+    def digest(t):
+        a = t.detach().contiguous().cpu().numpy()
+        return [str(a.dtype), list(a.shape), hashlib.sha256(a.tobytes()).hexdigest()]
+
+    def case(name, fn):
+        """fn() -> (rc, {tensor name: tensor}); the launches of all classes between reset and read are the case's table"""
+        _lib.check(lib.genie_profile_enable((1 << N_CLASSES) - 1), "profile_enable")
+        lib.genie_profile_reset()
+        try:
+            rc, outs = fn()
+        except _lib.GenieHipError as e:
+            rc, outs = e.code, {}
+        torch.cuda.synchronize()
+        table = {}
+        buf = ctypes.create_string_buffer(1 << 16)
+        for kc in range(N_CLASSES):
+            _lib.check(lib.genie_profile_kernels(kc, buf, len(buf)), "profile_kernels")
+            for ln in buf.value.decode().splitlines():
+                table[f"{kc}:{ln.split(chr(9))[0]}"] = int(float(ln.split("\t")[1]))
+        lib.genie_profile_enable(0)
+        record[name] = {"rc": rc, "outs": {k: digest(v) for k, v in outs.items()} if rc == 0 else {}, "kernels": table}
+        print(name, "rc", rc, "launches", sum(table.values()), flush=True)
+
+    for gname, d, heads, T, S, B in GEOMETRIES:
+        for qk_norm in (False, True):
+            cfg = GenieConfig(num_layers=2, num_heads=heads, d_model=d, T=T, S=S, num_factored_vocabs=2, qk_norm=qk_norm, use_mup=False,
+                              qkv_bias=True)
+            sd = synth.make_state_dict(cfg, seed=5, law="conditioned")
+            g = np.random.default_rng(6)
+            for k in sd:   # the synthetic law leaves biases at zero: make every bias the kernels add count
+                if k.endswith(".bias") and "norm" not in k:
+                    sd[k] = (0.05 * g.standard_normal(sd[k].shape)).astype(np.float32)
+            hw = int(round(S ** 0.5))
+            V = cfg.factored_vocab_size * cfg.num_factored_vocabs
+            for prec in PRECISIONS:
+                tag = f"{gname}/{'qknorm' if qk_norm else 'ln'}/{prec}"
+                m = STMaskGIT(cfg, precision=prec).load_numpy_state_dict(sd).to("cuda")
+                c, w, layers = m._weights()[:3]
+                st = torch.cuda.current_stream().cuda_stream
+                ids = torch.from_numpy(synth.make_clips(B, cfg, seed=7)).cuda().view(B, T, S)
+                masked = ids.clone()
+                masked[:, T // 2:, ::3] = cfg.image_vocab_size
+                ws = m._workspace(B, generate_prompt_frames=T // 2)
+                nbytes = lib.genie_prefix_cache_bytes(c, B)
+
+                def full():
+                    logits = m.compute_logits_frames(masked.view(B, T, hw, hw), T - 2, T, "token")
+                    hidden = m.hidden_states(masked.view(B, T, hw, hw)).clone()
+                    return 0, {"logits": logits, "hidden": hidden}
+                case(tag + "/compute_logits", full)
+
+                n = T - 1
+                cache = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+
+                def clean():
+                    rc = lib.genie_clean_pass(c, w, ids[:, :n].contiguous().data_ptr(), B, n, n, cache.data_ptr(), nbytes, ws.data_ptr(),
+                                              ws.numel(), st)
+                    return rc, {"cache": cache}
+                case(tag + "/clean_pass", clean)
+                for frame0 in (0, 1):
+                    def masked_pass():
+                        lg = torch.zeros(B, n, S, V, dtype=torch.float32, device="cuda")
+                        rc = lib.genie_masked_frames_logits(c, w, masked[:, frame0:frame0 + n].contiguous().data_ptr(), B, frame0, n,
+                                                            cache.data_ptr(), nbytes, lg.data_ptr(), ws.data_ptr(), ws.numel(), st)
+                        return rc, {"logits": lg}
+                    case(f"{tag}/masked_frames_logits/frame0={frame0}", masked_pass)
+
+                P = T // 2
+                for Bx in (1, 2, B):   # a half-length clean pass into the full-length cache, then decode passes against it
+                    nb = lib.genie_prefix_cache_bytes(c, Bx)
+                    kv = torch.zeros(nb, dtype=torch.uint8, device="cuda")
+
+                    def strided():
+                        rc = lib.genie_clean_pass(c, w, ids[:Bx, :P].contiguous().data_ptr(), Bx, P, T, kv.data_ptr(), nb, ws.data_ptr(),
+                                                  ws.numel(), st)
+                        return rc, {"cache": kv}
+                    case(f"{tag}/clean_pass_into_full_cache/B={Bx}", strided)
+
+                    def frame():
+                        lg = torch.zeros(Bx, S, V, dtype=torch.float32, device="cuda")
+                        rc = lib.genie_frame_pass(c, w, masked[:Bx, P].contiguous().data_ptr(), Bx, P, kv.data_ptr(), nb, lg.data_ptr(),
+                                                  ws.data_ptr(), ws.numel(), st)
+                        return rc, {"logits": lg, "cache": kv}
+                    case(f"{tag}/frame_pass/B={Bx}", frame)
+
+                    def frames():
+                        lg = torch.zeros(Bx, S, V, dtype=torch.float32, device="cuda")
+                        rc = lib.genie_frames_pass(c, w, masked[:Bx, P:P + 2].contiguous().data_ptr(), Bx, P, 2, kv.data_ptr(), nb,
+                                                   lg.data_ptr(), ws.data_ptr(), ws.numel(), st)
+                        return rc, {"logits": lg, "cache": kv}
+                    case(f"{tag}/frames_pass_nf2/B={Bx}", frames)
+
+                noise = torch.rand(T - P, 1, B, S, generator=torch.Generator().manual_seed(3)).cuda()
+
+                def generate():
+                    out = G.generate_frames_cached(m, ids.view(B, T, hw, hw), P, 2, 0.0, False, noise=noise, merge_commit=True)
+                    return 0, {"tokens": out}
+                case(tag + "/generate_cached", generate)
+
+                def block():
+                    x = (0.5 * torch.randn(B, T, S, d, generator=torch.Generator().manual_seed(4))).cuda()
+                    rc = lib.genie_st_block_forward(c, layers[0], x.data_ptr(), B, ws.data_ptr(), ws.numel(), st)
+                    return rc, {"x": x}
+                case(tag + "/st_block_forward", block)
+                del m, ws, cache
+                torch.cuda.empty_cache()
+    with open(out_path, "w") as f:
+        json.dump(record, f)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("library_a", nargs="?", help="the library to compare against (its tables decide whether the battery reached WATCHED)")
+    ap.add_argument("library_b", nargs="?")
+    ap.add_argument("--timeout", type=int, default=420, help="time limit of each child process, seconds")
+    ap.add_argument("--child", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.child:
+        return child(a.child)
+    if not (a.library_a and a.library_b):
+        ap.error("two libraries")
+    records = []
+    with tempfile.TemporaryDirectory() as tmp:
+        for i, path in enumerate((a.library_a, a.library_b)):
+            out = os.path.join(tmp, f"record_{i}.json")
+            env = dict(os.environ, GENIE_HIP_LIBRARY=os.path.abspath(path))
+            try:
+                rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", out], env=env, timeout=a.timeout).returncode
+            except subprocess.TimeoutExpired:
+                rc = 124
+            if rc != 0:
+                print(f"FAIL: the battery on {path} ended with status {rc}; nothing more was started")
+                return 2
+            records.append(json.load(open(out)))
+    ra, rb = records
+    bad = 0
+    if sorted(ra) != sorted(rb):
+        print("FAIL: the two runs did not record the same cases")
+        return 2
+    n_tensors = 0
+    for name in ra:
+        ca, cb = ra[name], rb[name]
+        if ca["rc"] != cb["rc"]:
+            bad += 1
+            print(f"DIFF {name}: return code {ca['rc']} != {cb['rc']}")
+        for k in sorted(set(ca["outs"]) | set(cb["outs"])):
+            n_tensors += 1
+            if ca["outs"].get(k) != cb["outs"].get(k):
+                bad += 1
+                print(f"DIFF {name}: tensor {k}: {ca['outs'].get(k)} != {cb['outs'].get(k)}")
+        if ca["kernels"] != cb["kernels"]:
+            bad += 1
+            for k in sorted(set(ca["kernels"]) | set(cb["kernels"])):
+                if ca["kernels"].get(k) != cb["kernels"].get(k):
+                    print(f"DIFF {name}: launches of {k}: {ca['kernels'].get(k)} != {cb['kernels'].get(k)}")
+    seen = {}
+    for name, cs in ra.items():
+        for k, v in cs["kernels"].items():
+            for wk in WATCHED:
+                if wk in k:
+                    seen.setdefault(wk, {}).setdefault(name.split("/")[0], 0)
+                    seen[wk][name.split("/")[0]] += v
+    for wk in WATCHED:
+        print(f"watched {wk}: launches per geometry {seen.get(wk, {})}")
+    missing = [wk for wk in WATCHED if wk not in seen]
+    # proxies for the two kernels no table names.  attn_spatial_dma: the unnamed launches of the spatial attention class in the 16-bit
+    # cases of the S = 256 geometries (every launcher of that class the 16-bit drivers reach is profiled unnamed; the DMA kernel is the
+    # one behind a gemm16_pp qkv GEMM) -- each geometry must show some.  splitk2_residual: the GEMM table of the one case inside the
+    # shape window of fc2_splitk2 (its two-slab GEMM is one launch of the kernel the unsplit fc2 would run on, so this is printed, not
+    # required).
+    for gname in ("d256", "d512"):
+        per = {prec: sum(cs["kernels"].get("1:(unnamed)", 0) for n, cs in ra.items() if n.startswith(gname + "/") and f"/{prec}/" in n)
+               for prec in ("bf16", "f16x3")}
+        print(f"proxy attn_spatial_dma: unnamed spatial-attention launches at {gname}: {per}")
+        if not sum(per.values()):
+            missing.append(f"attn_spatial_dma (no unnamed spatial-attention launch in the 16-bit cases at {gname})")
+    sk = ra.get("d512/ln/bf16/frame_pass/B=8", {"kernels": {}})["kernels"]
+    print("proxy splitk2_residual: GEMM launches of d512/ln/bf16/frame_pass/B=8 (2,048 rows, hidden 2,048: inside the fc2_splitk2 window):",
+          {k: v for k, v in sk.items() if k.startswith("0:")})
+    refused = sorted(n for n in ra if ra[n]["rc"] != 0)
+    print(f"{len(ra)} cases ({len(refused)} refused by both libraries alike), {n_tensors} output tensors, "
+          f"{sum(sum(c['kernels'].values()) for c in ra.values())} profiled launches in the first library")
+    if missing:
+        print(f"FAIL (of the battery): never reached {missing}")
+        return 3
+    if bad:
+        print(f"FAIL: {bad} differences")
+        return 1
+    print("PASS: zero differing bits, identical return codes, identical kernel tables")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
