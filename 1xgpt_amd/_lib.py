@@ -60,6 +60,12 @@ class Guidance(C.Structure):
     _fields_ = [("scale", C.c_float), ("null_action", C.c_int32)]
 
 
+class ActionProj(C.Structure):
+    """genie_action_proj: the projection of continuous per-frame action vectors (weight (d, A), bias, input mean and 1/std; device pointers)."""
+    _fields_ = [("weight", c_ptr), ("bias", c_ptr), ("mean", c_ptr), ("inv_std", c_ptr), ("action_dim", C.c_int32)]
+
+
+ACTION_MAX_DIM = 256   # GENIE_ACTION_MAX_DIM
 WIDE_QKV, WIDE_PROJ, WIDE_FC1, WIDE_FC2 = 1, 2, 1, 2          # bits of the w16_wide fields (genie_hip.h)
 FUSED_QKV_STREAM = 4                                        # spatial attention: fused_w16 = [proj stream | qkv stream]
 TEMPORAL_QKV_F16X3_ELEMS = 393216   # f16 values of the f16x3 temporal qkv stream (csrc/kernels_fused_f16x3.hip)
@@ -73,6 +79,9 @@ SIGNATURES = {
     "genie_abi_layout": (C.c_int, [C.POINTER(C.c_size_t), C.c_int]),
     "genie_sampling_layout": (C.c_int, [C.POINTER(C.c_size_t), C.c_int]),
     "genie_guidance_layout": (C.c_int, [C.POINTER(C.c_size_t), C.c_int]),
+    "genie_action_proj_layout": (C.c_int, [C.POINTER(C.c_size_t), C.c_int]),
+    "genie_action_rows": (C.c_int, [C.POINTER(ActionProj), c_ptr, c_ptr, C.c_int64, C.c_int, c_ptr]),
+    "genie_action_rows_backward": (C.c_int, [C.POINTER(ActionProj), c_ptr, c_ptr, C.c_int64, C.c_int, c_ptr, c_ptr, C.c_int, c_ptr]),
     "genie_last_error": (C.c_char_p, []),
     "genie_check_config": (C.c_int, [C.POINTER(GenieCfg)]),
     "genie_workspace_bytes": (C.c_size_t, [C.POINTER(GenieCfg), C.c_int]),
@@ -236,10 +245,13 @@ def load():
             fn.restype, fn.argtypes = res, args
         if lib.genie_version() != ABI_VERSION:
             raise RuntimeError(f"libgenie_hip ABI version {lib.genie_version()} != {ABI_VERSION}")
-        lay = (C.c_size_t * 5)()
+        lay = (C.c_size_t * 6)()
+        mine = [C.sizeof(ActionProj)] + [getattr(ActionProj, n).offset for n, _ in ActionProj._fields_]
+        if lib.genie_action_proj_layout(lay, 6) != 6 or list(lay) != mine:
+            raise RuntimeError(f"genie_action_proj layout {list(lay)} != the ctypes declaration {mine}")
         mine = [C.sizeof(Sampling)] + [getattr(Sampling, n).offset for n, _ in Sampling._fields_]
-        if lib.genie_sampling_layout(lay, 5) != 5 or list(lay) != mine:
-            raise RuntimeError(f"genie_sampling layout {list(lay)} != the ctypes declaration {mine}")
+        if lib.genie_sampling_layout(lay, 5) != 5 or list(lay)[:5] != mine:
+            raise RuntimeError(f"genie_sampling layout {list(lay)[:5]} != the ctypes declaration {mine}")
         mine = [C.sizeof(Guidance)] + [getattr(Guidance, n).offset for n, _ in Guidance._fields_]
         if lib.genie_guidance_layout(lay, 3) != 3 or list(lay)[:3] != mine:
             raise RuntimeError(f"genie_guidance layout {list(lay)[:3]} != the ctypes declaration {mine}")

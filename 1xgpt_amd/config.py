@@ -45,16 +45,29 @@ class GenieConfig:
     # per-frame action conditioning (not in the reference): A > 0 adds a learned (A, d_model) table whose row
     # action_ids[b, t] joins the positional embedding of every token of frame t.  0 = unconditioned, today's model.
     action_vocab_size: int = 0
+    # ... or continuous actions (not in the reference either): A > 0 adds a learned Linear(A, d_model) and a learned "no action" row;
+    # every entry point then takes action_vectors (B, T, A) float32, projected once per call into per-frame rows.  Excludes action_vocab_size.
+    action_dim: int = 0
 
     def __post_init__(self):
         self.factored_vocab_size = nth_root(self.image_vocab_size, self.num_factored_vocabs)
+        if self.action_vocab_size and self.action_dim:
+            raise ValueError(f"action_vocab_size ({self.action_vocab_size}) and action_dim ({self.action_dim}) are mutually exclusive: "
+                             "a model is conditioned on action ids or on action vectors")
+        if self.action_dim < 0:
+            raise ValueError(f"action_dim must be >= 0, got {self.action_dim}")
+        if not self.action_dim:
+            # 0 lives on the class only: vars(config) -- what config.json, shallow_copy and the reference-compatible dump are built
+            # from -- then has exactly the fields it had before continuous actions existed; reads still give 0
+            self.__dict__.pop("action_dim", None)
 
     def to_json_dict(self) -> dict:
-        """What config.json holds: every field, except action_vocab_size when it is 0 -- the reference's from_pretrained is
-        cls(**config) and would refuse the unknown key, so unconditioned checkpoints stay loadable there (byte-identical)."""
+        """What config.json holds: every field, except action_vocab_size / action_dim when they are 0 -- the reference's from_pretrained
+        is cls(**config) and would refuse the unknown key, so unconditioned checkpoints stay loadable there (byte-identical)."""
         d = dict(vars(self))
-        if not d.get("action_vocab_size"):
-            d.pop("action_vocab_size", None)
+        for k in ("action_vocab_size", "action_dim"):
+            if not d.get(k):
+                d.pop(k, None)
         return d
 
     def save_pretrained(self, json_path):

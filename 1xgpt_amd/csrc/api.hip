@@ -299,6 +299,32 @@ int genie_guidance_layout(size_t* out_host, int n) {
     for (int i = 0; i < n && i < 3 && out_host; ++i) out_host[i] = v[i];
     return 3;
 }
+int genie_action_proj_layout(size_t* out_host, int n) {
+    const size_t v[6] = {sizeof(genie_action_proj), offsetof(genie_action_proj, weight), offsetof(genie_action_proj, bias),
+                         offsetof(genie_action_proj, mean), offsetof(genie_action_proj, inv_std), offsetof(genie_action_proj, action_dim)};
+    for (int i = 0; i < n && i < 6 && out_host; ++i) out_host[i] = v[i];
+    return 6;
+}
+static int check_action_proj(const genie_action_proj* p, int64_t n, int d_model, const char* where) {
+    GENIE_CHECK_ARG(p != nullptr, "%s: NULL genie_action_proj", where);
+    GENIE_CHECK_ARG(p->action_dim >= 1 && d_model >= 1 && n >= 0, "%s: action_dim %d, d_model %d, n %lld must be >= 1, >= 1, >= 0", where,
+                    p->action_dim, d_model, (long long)n);
+    GENIE_CHECK_SHAPE(p->action_dim <= GENIE_ACTION_MAX_DIM && d_model <= 1024, "%s: action_dim %d / d_model %d beyond %d / 1024", where,
+                      p->action_dim, d_model, GENIE_ACTION_MAX_DIM);
+    return GENIE_OK;
+}
+int genie_action_rows(const genie_action_proj* p, const float* vecs, float* rows, int64_t n, int d_model, void* stream) {
+    GENIE_TRY(check_action_proj(p, n, d_model, "genie_action_rows"));
+    GENIE_CHECK_ARG(p->weight && vecs && rows, "genie_action_rows: NULL pointer");
+    return launch_action_rows(*p, vecs, rows, (long)n, d_model, as_stream(stream));
+}
+int genie_action_rows_backward(const genie_action_proj* p, const float* vecs, const float* d_rows, int64_t n, int d_model,
+                               float* d_weight, float* d_bias, int accumulate, void* stream) {
+    GENIE_TRY(check_action_proj(p, n, d_model, "genie_action_rows_backward"));
+    GENIE_CHECK_ARG(vecs && d_rows && d_weight, "genie_action_rows_backward: NULL pointer");
+    if (n == 0) return GENIE_OK;
+    return launch_action_rows_backward(*p, vecs, d_rows, (long)n, d_model, d_weight, d_bias, accumulate, as_stream(stream));
+}
 const char* genie_last_error(void) { return g_err; }
 int genie_check_config(const genie_cfg* cfg) { return check_cfg(cfg); }
 

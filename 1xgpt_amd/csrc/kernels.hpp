@@ -213,6 +213,10 @@ int launch_sample_guided(const genie_cfg& c, const float* logits_c, const float*
                          const float* noise, float anneal, float scale, hipStream_t st);
 int launch_guide_logits(const float* cond, const float* null_, float* out, long rows, long len, long in_stride, long out_stride, float scale,
                         hipStream_t st);
+// continuous actions (kernels_action.hip; arithmetic: genie_action_proj in genie_hip.h)
+int launch_action_rows(const genie_action_proj& p, const float* vecs, float* rows, long n, int d, hipStream_t st);
+int launch_action_rows_backward(const genie_action_proj& p, const float* vecs, const float* d_rows, long n, int d, float* d_weight,
+                                float* d_bias, int accumulate, hipStream_t st);
 int launch_mask_step(const float* keys, int n, int last_step, int64_t mask_id, uint8_t* unmasked, int64_t* samples,
                      int64_t* prompt_frame, long clip_stride, int B, int S, hipStream_t st);
 int launch_check_masked(const int64_t* prompt, int B, int T, int S, int out_t, int64_t mask_id, int32_t* flag,

@@ -39,12 +39,13 @@ class GenieEvaluator:
         from .sampling import SamplingConfig
         return SamplingConfig.from_args(self.args), getattr(self.args, "unmask_mode", None) or "random"
 
-    def predict_zframe_logits(self, input_ids: torch.LongTensor, noise=None, return_logits=True, action_ids=None):
+    def predict_zframe_logits(self, input_ids: torch.LongTensor, noise=None, return_logits=True, action_ids=None, action_vectors=None):
         """input_ids (B, T*H*W) -> (samples (B,T-1,H,W), factored logits (B,512,2,T-1,H,W)).
 
         Total forward passes = (T-1) * maskgit_steps (evaluate.py:90).
         noise: optional (T-1, maskgit_steps-1, B, S) replay of the "random" unmasking draws.
-        action_ids: (B, T) per-frame actions of an action-conditioned model."""
+        action_ids: (B, T) per-frame actions of an action-conditioned model; action_vectors: (B, T, action_dim) float actions of a
+        model with config.action_dim > 0 (so in every method below)."""
         m, a = self.model, self.args
         T = m.config.T
         clips = input_ids.to(self.device).to(torch.int64).view(-1, T, a.latent_h, a.latent_w)
@@ -56,7 +57,8 @@ class GenieEvaluator:
             timeline[:, t:] = m.mask_token_id
             frame, lg = m.maskgit_generate(timeline, out_t=t, maskgit_steps=a.maskgit_steps, temperature=a.temperature,
                                            noise=None if noise is None else noise[t - 1], return_logits=return_logits,
-                                           check=False, action_ids=action_ids, sampling=sampling, unmask_mode=unmask_mode)
+                                           check=False, action_ids=action_ids, action_vectors=action_vectors, sampling=sampling,
+                                           unmask_mode=unmask_mode)
             frames.append(frame)
             logits.append(lg)
         return torch.stack(frames, dim=1), (torch.stack(logits, dim=3) if return_logits else None)
@@ -71,7 +73,7 @@ class GenieEvaluator:
     # ------------------------------------------------------------------ teacher-forced prefix reuse
     @torch.no_grad()
     def predict_zframe_logits_reuse(self, input_ids: torch.LongTensor, noise=None, return_logits=True,
-                                    unmask_mode=None, step0_hook=None, action_ids=None, uniforms=None):
+                                    unmask_mode=None, step0_hook=None, action_ids=None, uniforms=None, action_vectors=None):
         """Same contract and same per-row arithmetic as ``predict_zframe_logits`` in (1 + steps) passes over T-1 frames
         instead of 15 * steps forwards over T: the ground-truth frames < t of every timeline t are identical to one clean
         pass (temporal attention is causal, everything else per-frame), so they are computed once (frames 0..T-2: no
@@ -103,7 +105,7 @@ class GenieEvaluator:
         ids = input_ids.to(self.device).to(torch.int64).view(-1, T, S)
         B = ids.shape[0]
         dev = ids.device
-        cond = m._cond(action_ids, B)
+        cond = m._cond(action_ids, B, action_vectors=action_vectors)
         ws = m._workspace(B)
         nbytes = lib.genie_prefix_cache_bytes(cfg, B)
         if getattr(self, "_cache", None) is None or self._cache.numel() < nbytes or self._cache.device != dev:
@@ -166,7 +168,7 @@ class GenieEvaluator:
         return samples_THW, fl
 
     @torch.no_grad()
-    def evaluate_metric_sums_reuse(self, input_ids, labels=None, noise=None, action_ids=None):
+    def evaluate_metric_sums_reuse(self, input_ids, labels=None, noise=None, action_ids=None, action_vectors=None):
         """``evaluate_metric_sums`` on the prefix-reuse path (same six sums)."""
         lib = _lib.load()
         m = self.model
@@ -186,9 +188,9 @@ class GenieEvaluator:
                                              ce.data_ptr(), st), "genie_factored_ce")
 
         # the CE is taken from the step-0 logits on the stream BEFORE the next MaskGIT step overwrites them: no 2 GB copy
-        m._cond(action_ids, B)   # (argument errors before anything is enqueued)
+        m._check_cond(action_ids, B, action_vectors)   # (argument errors before anything is enqueued)
         samples, _ = self.predict_zframe_logits_reuse(ids, noise=noise, return_logits=False, step0_hook=ce_of_step0,
-                                                      action_ids=action_ids)
+                                                      action_ids=action_ids, action_vectors=action_vectors)
         # (ground truth frames 1..T-1 == samples).sum() and the vector's sizes, on the device (no torch arithmetic)
         _lib.check(lib.genie_metric_hits(ids.data_ptr() + S * 8, T * S, samples.data_ptr(), (T - 1) * S, B, (T - 1) * S,
                                          ce.data_ptr(), float(B * (T - 1) * S), float(B * (T - 1)), float(B), sums.data_ptr(), st),
@@ -196,7 +198,7 @@ class GenieEvaluator:
         return sums
 
     @torch.no_grad()
-    def evaluate_metric_sums(self, input_ids, labels=None, noise=None, action_ids=None):
+    def evaluate_metric_sums(self, input_ids, labels=None, noise=None, action_ids=None, action_vectors=None):
         """One batch of the metric loop (evaluate.py:167-179) as device-side sums, no logits materialised
         for the caller: returns float64 tensor [sum CE, n CE tokens, sum (gt == sample), n sampled tokens,
         n frames, n clips]."""
@@ -211,7 +213,7 @@ class GenieEvaluator:
         sums = torch.zeros(6, dtype=torch.float64, device=ids.device)
         stream = torch.cuda.current_stream().cuda_stream
         sizes = (float(B * (T - 1) * S), float(B * (T - 1)), float(B))
-        m._cond(action_ids, B)   # (argument errors before anything is enqueued)
+        m._check_cond(action_ids, B, action_vectors)   # (argument errors before anything is enqueued)
         sampling, unmask_mode = self._sampling()
         for k, t in enumerate(range(1, T)):
             p = ids.clone()
@@ -219,6 +221,7 @@ class GenieEvaluator:
             s, fl = m.maskgit_generate(p, out_t=t, maskgit_steps=self.args.maskgit_steps,
                                        temperature=self.args.temperature,
                                        noise=None if noise is None else noise[k], check=False, action_ids=action_ids,
+                                       action_vectors=action_vectors,
                                        sampling=sampling, unmask_mode=unmask_mode)
             # fl is a permuted view of the contiguous (B, V, H, W) step-0 logits of frame t
             lg = fl.permute(0, 2, 1, 3, 4)
@@ -235,7 +238,7 @@ class GenieEvaluator:
 
 @torch.no_grad()
 def evaluate_clips(evaluator: GenieEvaluator, clips: torch.LongTensor, batch_size=16, noise_seed=None,
-                   distributed=False, reuse=True, clip_offset=0, action_ids=None):
+                   distributed=False, reuse=True, clip_offset=0, action_ids=None, action_vectors=None):
     """Metric loop over ``clips`` (N, T*H*W) with the reference's AvgMetric weighting (eval_utils.py:16-25).
 
     With ``distributed=True`` every rank passes ITS shard of the clips; the six sums are all-reduced (SUM)
@@ -244,7 +247,8 @@ def evaluate_clips(evaluator: GenieEvaluator, clips: torch.LongTensor, batch_siz
     clip_offset: index of this shard's first clip in the whole job; the "random" unmasking draws of a batch are keyed by
     (noise_seed, global index of its first clip), so a job gives the same draws however it is sharded over ranks (given
     shard boundaries that are multiples of batch_size).
-    action_ids: (N, T) per-frame actions of the clips (an action-conditioned model), sharded like them."""
+    action_ids: (N, T) per-frame actions of the clips (an action-conditioned model), sharded like them; action_vectors: (N, T, action_dim)
+    float actions of a model with config.action_dim > 0, sharded alike."""
     dev = evaluator.device
     total = torch.zeros(6, dtype=torch.float64, device=dev)
     torch.cuda.synchronize()
@@ -258,7 +262,8 @@ def evaluate_clips(evaluator: GenieEvaluator, clips: torch.LongTensor, batch_siz
             noise = torch.rand(m.config.T - 1, evaluator.args.maskgit_steps - 1, batch.shape[0], m.config.S,
                                generator=g).to(dev)
         fn = evaluator.evaluate_metric_sums_reuse if reuse else evaluator.evaluate_metric_sums
-        total += fn(batch, noise=noise, action_ids=None if action_ids is None else action_ids[i:i + batch_size])
+        total += fn(batch, noise=noise, action_ids=None if action_ids is None else action_ids[i:i + batch_size],
+                    action_vectors=None if action_vectors is None else action_vectors[i:i + batch_size])
     torch.cuda.synchronize()
     seconds = time.perf_counter() - t0
     if distributed:

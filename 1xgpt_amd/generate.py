@@ -18,14 +18,15 @@ STRIDE = 15
 @torch.no_grad()
 def generate_frames(model, example_THW: torch.LongTensor, num_prompt_frames=8, maskgit_steps=2, temperature=0.0,
                     teacher_force_time=False, noise=None, action_ids=None, sampling=None, unmask_mode="random", uniforms=None,
-                    guidance=None):
+                    guidance=None, action_vectors=None):
     """example_THW (B, T, H, W) on the model's device -> outputs (B, T + (T - num_prompt_frames), H, W):
     [prompt frames | predicted frames | ground-truth frames] (generate.py:97-103).
     noise: optional (T - num_prompt_frames, maskgit_steps-1, B, S).
     action_ids: (B, T) per-frame actions of an action-conditioned model (config.action_vocab_size > 0).
     sampling: a SamplingConfig (1xgpt_amd/sampling.py) or None = the reference's law; unmask_mode: "random" (the reference's
     harness), "greedy" or "confidence"; uniforms: optional (T - num_prompt_frames, maskgit_steps, num_factored_vocabs, B, S).
-    guidance: a Guidance(scale, null_action) or None: classifier-free guidance of an action-conditioned model."""
+    guidance: a Guidance(scale, null_action) or None: classifier-free guidance of an action-conditioned model.
+    action_vectors: (B, T, action_dim) float actions of a model with config.action_dim > 0 (then Guidance(scale) suffices)."""
     window_size = example_THW.shape[1]
     assert num_prompt_frames <= window_size
     example_THW = example_THW.to(torch.int64).contiguous()
@@ -38,7 +39,7 @@ def generate_frames(model, example_THW: torch.LongTensor, num_prompt_frames=8, m
             prompt_THW[:, timestep:] = model.mask_token_id
         samples_HW, _ = model.maskgit_generate(prompt_THW, out_t=timestep, maskgit_steps=maskgit_steps,
                                                temperature=temperature, noise=None if noise is None else noise[k],
-                                               return_logits=False, action_ids=action_ids, sampling=sampling,
+                                               return_logits=False, action_ids=action_ids, action_vectors=action_vectors, sampling=sampling,
                                                unmask_mode=unmask_mode, uniforms=None if uniforms is None else uniforms[k],
                                                guidance=guidance)
         samples.append(samples_HW)
@@ -52,7 +53,7 @@ def generate_frames(model, example_THW: torch.LongTensor, num_prompt_frames=8, m
 @torch.no_grad()
 def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_frames=8, maskgit_steps=2, temperature=0.0,
                            teacher_force_time=False, noise=None, unmask_mode="random", merge_commit=True, host_loop=False,
-                           action_ids=None, sampling=None, uniforms=None, guidance=None):
+                           action_ids=None, sampling=None, uniforms=None, guidance=None, action_vectors=None):
     """``generate_frames`` with a temporal KV cache (genie_frame_pass): every pass runs ONE frame through the stack
     against the cached temporal keys/values of the earlier frames instead of the full 16-frame forward --
     one P-frame pass for the prompt + (T-P)*(steps+1) single-frame passes (= 2 full-pass equivalents at P=8, steps=2) instead of (T-P)*steps full
@@ -62,7 +63,8 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
     host_loop: False = the whole loop is ONE library call (genie_generate_cached: every pass, sampling and mask step enqueued
     without a host step in between); True = the same loop driven from Python (one C-ABI call per pass / sample / mask step).
     action_ids: (B, T) per-frame actions of an action-conditioned model (config.action_vocab_size > 0); every pass embeds
-    frame t with action_ids[:, t].
+    frame t with action_ids[:, t].  action_vectors: (B, T, action_dim) float actions of a model with config.action_dim > 0 instead:
+    one extra launch projects them into per-frame rows before the first pass, and every pass is the one the ids would run.
     sampling: a SamplingConfig or None = the reference's law; unmask_mode may be "confidence" (both as in maskgit_generate);
     uniforms: optional (T - num_prompt_frames, maskgit_steps, num_factored_vocabs, B, S) sampling draws to replay.
     guidance: a Guidance(scale, null_action) or None: classifier-free guidance.  Every pass then runs 2 B clips -- the clips under their
@@ -87,8 +89,8 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
     assert P <= T and P >= 1
     dev = ex.device
     ids = ex.view(B, T, S)
-    cond = model._cond(action_ids, B, n_frames=T)
     guide = model._guidance(guidance)
+    cond = model._cond(action_ids, B, n_frames=T, action_vectors=action_vectors)
     NB = B if guide is None else 2 * B   # clips per pass: [conditional ; null] under guidance
     ws = model._workspace(B, generate_prompt_frames=P, guided=guide is not None)
     nbytes = lib.genie_prefix_cache_bytes(cfg, NB)
@@ -115,7 +117,7 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
         return torch.cat([outputs, ex[:, P:]], dim=1)
 
     if guide is not None:   # the doubled inputs: tokens twice, actions [the clips' ; null_action]
-        cond = model._frame_cond(torch.cat([cond.keep, torch.full_like(cond.keep, guide.null_action)]).contiguous())
+        cond = model._frame_cond(torch.cat([cond.keep, torch.full_like(cond.keep, guide.null_action)]).contiguous(), like=cond)
         ids = torch.cat([ids, ids]).contiguous()
 
     def frame_pass(tokens_BS, t, logits=None):
@@ -253,6 +255,30 @@ def _rollout_actions(model, action_ids, B, n, what="action_ids"):
     return a.to(device=model.pos_embed_TSC.device, dtype=torch.int64).contiguous()
 
 
+def _rollout_vectors(model, action_vectors, B, n, what="action_vectors"):
+    """Checked (n, B, action_dim) float32 device vectors of n rollout frames, frame-major (the order of their rows)."""
+    v = model.check_action_vectors(action_vectors, (B, n, model.config.action_dim), what)
+    return v.transpose(0, 1).contiguous()
+
+
+def _rollout_row_ids(B, cap, dev):
+    """(B, cap) int64: frame f of clip b reads row 1 + f B + b -- frame-major behind the null row 0, so a growing rollout appends rows."""
+    return (1 + torch.arange(cap, device=dev)[None, :] * B + torch.arange(B, device=dev)[:, None]).to(torch.int64).contiguous()
+
+
+def _rollout_inputs(model, action_ids, action_vectors, B, n, what="action_ids"):
+    """(ids, vectors) of n rollout frames, one of them None -- or both for an unconditioned model; raises like STMaskGIT._cond."""
+    if action_ids is not None and action_vectors is not None:
+        raise ValueError("pass action_ids or action_vectors, not both")
+    if model.config.action_dim:
+        if action_ids is not None:
+            raise ValueError(f"{what} given to a model conditioned on action vectors (action_dim={model.config.action_dim})")
+        return None, _rollout_vectors(model, action_vectors, B, n)
+    if action_vectors is not None:
+        raise ValueError("action_vectors given to a model without continuous actions (config.action_dim == 0)")
+    return _rollout_actions(model, action_ids, B, n, what), None
+
+
 class _Decode:
     """The decode options of a rollout, resolved once: MaskGIT steps, unmasking mode, sampling law, guidance."""
 
@@ -279,9 +305,9 @@ class _Decode:
         return nz, uni
 
 
-def rollout_call(model, frames_BcS, actions_Bc, P, keep, f0, f1, resume, cache, dec, nz, uni):
+def rollout_call(model, frames_BcS, actions_Bc, P, keep, f0, f1, resume, cache, dec, nz, uni, rows=None):
     """ONE genie_rollout_cached call: generates the absolute frames [f0, f1) of frames_BcS (B, cap, S) int64 in place.  actions_Bc: (B, cap)
-    int64 or None; cache: uint8 tensor of genie_prefix_cache_bytes(cfg, NB); dec: the _Decode options; nz / uni: this call's draws."""
+    int64 or None -- rows of the model's action table, or of `rows` (a projected row table of a model conditioned on action vectors); cache: uint8 tensor of genie_prefix_cache_bytes(cfg, NB); dec: the _Decode options; nz / uni: this call's draws."""
     from . import _lib
     lib = _lib.load()
     cfg, w = model._weights()[:2]
@@ -291,7 +317,11 @@ def rollout_call(model, frames_BcS, actions_Bc, P, keep, f0, f1, resume, cache, 
     cond = None
     if actions_Bc is not None:
         assert actions_Bc.shape == (B, cap) and actions_Bc.dtype == torch.int64 and actions_Bc.is_contiguous()
-        cond = _lib.FrameCond(table=model.action_embed.weight.data_ptr(), ids=actions_Bc.data_ptr(), n_actions=model.config.action_vocab_size)
+        if rows is not None:
+            cond = _lib.FrameCond(table=rows.data_ptr(), ids=actions_Bc.data_ptr(), n_actions=rows.shape[0])
+        else:
+            cond = _lib.FrameCond(table=model.action_embed.weight.data_ptr(), ids=actions_Bc.data_ptr(),
+                                  n_actions=model.config.action_vocab_size)
     # the largest context the call runs sizes its workspace: `keep` for every window it opens after its first, and for the first the frames
     # before f0 -- unless the call resumes in mid-window, where it runs none
     wins = [w for w in window_schedule(P, keep, T, f1 - P) if w[3] > f0]
@@ -312,14 +342,15 @@ def _rollout_cache(model, B, dec, dev):
 
 @torch.no_grad()
 def rollout_frames(model, prompt_BPHW: torch.LongTensor, n_new, keep=None, maskgit_steps=2, temperature=0.0, unmask_mode="random",
-                   noise=None, uniforms=None, action_ids=None, sampling=None, guidance=None, merge_commit=True):
+                   noise=None, uniforms=None, action_ids=None, sampling=None, guidance=None, merge_commit=True, action_vectors=None):
     """Generate n_new frames behind the P prompt frames of prompt_BPHW (B, P, H, W), past the model's window T if need be, in ONE library
     call (genie_rollout_cached) -> (B, P + n_new, H, W).  Window 0 decodes frames [P, T); after that the window slides: the last ``keep``
     frames (default P; 1 <= keep <= T - 1) are re-run as the context of the next hop = T - keep frames (window_schedule; positions are
     absolute, so the KV cache cannot be shifted).  keep is a quality / cost dial: keep = T - 1 is the true sliding window.  Equal, bit
     for bit, to chaining generate_frames_cached window by window on the same draws.
     noise: optional (n_new, maskgit_steps - 1, B, S); uniforms: optional (n_new, maskgit_steps, num_factored_vocabs, B, S); fresh
-    torch.rand draws otherwise.  action_ids: (B, P + n_new), the actions of the absolute frames.  The other options: generate_frames_cached."""
+    torch.rand draws otherwise.  action_ids: (B, P + n_new), the actions of the absolute frames; action_vectors: (B, P + n_new, action_dim)
+    for a model with config.action_dim > 0 (one launch projects all of them before the call).  The other options: generate_frames_cached."""
     cfg = model.config
     pr = prompt_BPHW.to(torch.int64)
     B, P = pr.shape[0], pr.shape[1]
@@ -330,11 +361,16 @@ def rollout_frames(model, prompt_BPHW: torch.LongTensor, n_new, keep=None, maskg
     window_schedule(P, keep, cfg.T, n_new)   # (checks P and keep)
     dev = pr.device
     dec = _Decode(model, maskgit_steps, temperature, unmask_mode, sampling, guidance, merge_commit)
-    acts = _rollout_actions(model, action_ids, B, P + n_new)
+    acts, vecs = _rollout_inputs(model, action_ids, action_vectors, B, P + n_new)
+    rows = None
+    if vecs is not None:
+        rows = model.new_row_table((P + n_new) * B)
+        model.project_actions(vecs.view(-1, vecs.shape[-1]), rows[1:])
+        acts = _rollout_row_ids(B, P + n_new, dev)
     frames = torch.full((B, P + n_new, cfg.S), model.mask_token_id, dtype=torch.int64, device=dev)
     frames[:, :P] = pr.reshape(B, P, cfg.S)
     nz, uni = dec.draws(model, n_new, B, noise, uniforms, dev)
-    rollout_call(model, frames, acts, P, keep, P, P + n_new, 0, _rollout_cache(model, B, dec, dev), dec, nz, uni)
+    rollout_call(model, frames, acts, P, keep, P, P + n_new, 0, _rollout_cache(model, B, dec, dev), dec, nz, uni, rows=rows)
     return frames.view(B, P + n_new, model.h, model.w)
 
 
@@ -343,10 +379,12 @@ class Rollout:
     genie_rollout_cached call that resumes the temporal KV cache of the call before it (the first runs the prompt).  Same frames as
     rollout_frames on the same draws, however the calls are split.  The object owns the (B, cap, S) token and (B, cap) action buffers
     and the cache; the buffers grow by doubling cap (a copy, which leaves the cache valid).
-    prompt_actions: (B, P) actions of the prompt frames of an action-conditioned model; keep and the decode options: rollout_frames."""
+    prompt_actions: (B, P) actions of the prompt frames of an action-conditioned model; keep and the decode options: rollout_frames.
+    A model with config.action_dim > 0 takes prompt_vectors (B, P, action_dim) here and (B, action_dim) / (B, n, action_dim) floats in
+    step / extend: each call projects only its new frames' vectors (one launch) into rows appended to the object's row table."""
 
     def __init__(self, model, prompt_BPHW, keep=None, prompt_actions=None, maskgit_steps=2, temperature=0.0, unmask_mode="random",
-                 sampling=None, guidance=None, merge_commit=True, capacity=None):
+                 sampling=None, guidance=None, merge_commit=True, capacity=None, prompt_vectors=None):
         cfg = model.config
         pr = prompt_BPHW.to(torch.int64)
         self.model, self.B, self.P = model, pr.shape[0], pr.shape[1]
@@ -357,9 +395,13 @@ class Rollout:
         cap = max(self.P + 1, 2 * cfg.T if capacity is None else int(capacity))
         self._frames = torch.full((self.B, cap, cfg.S), model.mask_token_id, dtype=torch.int64, device=pr.device)
         self._frames[:, :self.P] = pr.reshape(self.B, self.P, cfg.S)
-        acts = _rollout_actions(model, prompt_actions, self.B, self.P, "prompt_actions")
-        self._acts = None
-        if acts is not None:
+        acts, vecs = _rollout_inputs(model, prompt_actions, prompt_vectors, self.B, self.P, "prompt_actions")
+        self._acts = self._rows = None
+        if vecs is not None:
+            self._rows = model.new_row_table(cap * self.B)
+            model.project_actions(vecs.view(-1, vecs.shape[-1]), self._rows[1:1 + self.P * self.B])
+            self._acts = _rollout_row_ids(self.B, cap, pr.device)
+        elif acts is not None:
             self._acts = torch.zeros(self.B, cap, dtype=torch.int64, device=pr.device)
             self._acts[:, :self.P] = acts
         self._cache = _rollout_cache(model, self.B, self.dec, pr.device)
@@ -384,32 +426,47 @@ class Rollout:
         frames = torch.full((self.B, cap, self._frames.shape[2]), self.model.mask_token_id, dtype=torch.int64, device=self._frames.device)
         frames[:, :self.n] = self._frames[:, :self.n]
         self._frames = frames
-        if self._acts is not None:
+        if self._rows is not None:
+            rows = self.model.new_row_table(cap * self.B)
+            rows[:1 + self.n * self.B] = self._rows[:1 + self.n * self.B]
+            self._rows, self._acts = rows, _rollout_row_ids(self.B, cap, frames.device)
+        elif self._acts is not None:
             acts = torch.zeros(self.B, cap, dtype=torch.int64, device=frames.device)
             acts[:, :self.n] = self._acts[:, :self.n]
             self._acts = acts
 
     @torch.no_grad()
-    def extend(self, n, action_ids=None, noise=None, uniforms=None):
-        """Generate the next n frames -> (B, n, H, W).  action_ids: (B, n) actions of the new frames; noise (n, steps - 1, B, S) and
+    def extend(self, n, action_ids=None, noise=None, uniforms=None, action_vectors=None):
+        """Generate the next n frames -> (B, n, H, W).  action_ids: (B, n) actions of the new frames (action_vectors: (B, n, action_dim)
+        for a model with config.action_dim > 0); noise (n, steps - 1, B, S) and
         uniforms (n, steps, nv, B, S): this call's draws, or fresh torch.rand ones."""
         n = int(n)
         if n < 1:
             raise ValueError("Rollout.extend: n must be >= 1")
-        acts = _rollout_actions(self.model, action_ids, self.B, n)
+        acts, vecs = _rollout_inputs(self.model, action_ids, action_vectors, self.B, n)
         f0, f1 = self.n, self.n + n
         self._grow(f1)
-        if acts is not None:
+        if vecs is not None:
+            self.model.project_actions(vecs.view(-1, vecs.shape[-1]), self._rows[1 + f0 * self.B:1 + f1 * self.B])
+        elif acts is not None:
             self._acts[:, f0:f1] = acts
         nz, uni = self.dec.draws(self.model, n, self.B, noise, uniforms, self._frames.device)
-        rollout_call(self.model, self._frames, self._acts, self.P, self.keep, f0, f1, self._resume, self._cache, self.dec, nz, uni)
+        rollout_call(self.model, self._frames, self._acts, self.P, self.keep, f0, f1, self._resume, self._cache, self.dec, nz, uni,
+                     rows=self._rows)
         self.n, self._resume = f1, 1
         return self._frames[:, f0:f1].reshape(self.B, n, self.model.h, self.model.w)
 
     def step(self, action=None, noise=None, uniforms=None):
-        """Generate the next frame under ``action`` (B,) -> (B, H, W).  noise (steps - 1, B, S), uniforms (steps, nv, B, S): its draws."""
+        """Generate the next frame under ``action`` (B,) -> (B, H, W); a model with config.action_dim > 0 takes the frame's (B, action_dim)
+        float vectors.  noise (steps - 1, B, S), uniforms (steps, nv, B, S): its draws."""
+        nz, uni = None if noise is None else noise[None], None if uniforms is None else uniforms[None]
+        if self.model.config.action_dim and action is not None:
+            v = torch.as_tensor(action)
+            if v.dim() != 2 or v.shape[0] != self.B:
+                raise RuntimeError(f"expected the frame's action vectors of shape ({self.B}, {self.model.config.action_dim}), got {tuple(v.shape)}")
+            return self.extend(1, None, nz, uni, action_vectors=v[:, None])[:, 0]
         a = None if action is None else torch.as_tensor(action).reshape(self.B, 1)
-        return self.extend(1, a, None if noise is None else noise[None], None if uniforms is None else uniforms[None])[:, 0]
+        return self.extend(1, a, nz, uni)[:, 0]
 
 
 def write_outputs(outputs_THW: torch.LongTensor, output_dir, dataset_metadata: dict, args: dict):

@@ -56,12 +56,24 @@ class SamplingConfig:
         return cls(**given) if given else None
 
 
+class _ModelNull:
+    """Default of Guidance.null_action: "the model's own null row" (a model conditioned on action vectors has exactly one)."""
+
+    def __repr__(self):
+        return "MODEL_NULL"
+
+
+MODEL_NULL = _ModelNull()
+
+
 @dataclass
 class Guidance:
     """Classifier-free guidance of an action-conditioned model (genie_guidance in include/genie_hip.h, which states the arithmetic):
     logits = scale * conditional + (1 - scale) * null, the null stream being the same tokens under ``null_action`` at every frame."""
     scale: float          # w, finite: 1 = plain conditional sampling, 0 = the null stream alone, > 1 = guidance
-    null_action: int      # row of the action table that stands for "no action" (learned through action dropout: data.maskgit_collate)
+    # row of the action table that stands for "no action" (learned through action dropout: data.maskgit_collate).  A model with
+    # config.action_dim > 0 (continuous actions) supplies the index of its learned null row itself: Guidance(scale) is enough there.
+    null_action: int = MODEL_NULL
 
     def __post_init__(self):
         self.validate()
@@ -70,11 +82,13 @@ class Guidance:
         w, a = self.scale, self.null_action
         if isinstance(w, bool) or not (isinstance(w, (int, float)) and math.isfinite(w)):
             raise ValueError(f"guidance scale must be a finite number, got {w!r}")
-        if isinstance(a, bool) or not isinstance(a, int) or a < 0:
+        if a is not MODEL_NULL and (isinstance(a, bool) or not isinstance(a, int) or a < 0):
             raise ValueError(f"null_action must be a non-negative integer, got {a!r}")
         if action_vocab_size is not None:
             if not action_vocab_size:
                 raise ValueError("guidance given to a model without actions (config.action_vocab_size == 0)")
+            if a is MODEL_NULL:
+                raise ValueError("guidance of a model conditioned on action ids needs null_action (the table row trained as 'no action')")
             if a >= action_vocab_size:
                 raise IndexError(f"null_action {a} out of range [0, {action_vocab_size})")
         return self
@@ -83,6 +97,8 @@ class Guidance:
         """The ctypes genie_guidance."""
         from . import _lib
         self.validate()
+        if self.null_action is MODEL_NULL:
+            raise ValueError("Guidance without null_action has no struct of its own: the model supplies the row (guidance_struct)")
         return _lib.Guidance(scale=float(self.scale), null_action=int(self.null_action))
 
     @classmethod
@@ -97,13 +113,22 @@ class Guidance:
         return cls(float(w), int(a))
 
 
-def guidance_struct(guidance, action_vocab_size=None):
+def guidance_struct(guidance, action_vocab_size=None, null_row=None):
     """None -> None (the unchanged entry points); a Guidance -> its genie_guidance, checked against the model's action table
-    (scale 1 -> None as well, once checked: the library would dispatch to the unguided entry point anyway)."""
+    (scale 1 -> None as well, once checked: the library would dispatch to the unguided entry point anyway).
+    null_row: the fixed index of the learned null row in the per-call row table of a model conditioned on action vectors
+    (config.action_dim > 0); the Guidance then needs no null_action, and one that names another row is refused."""
     if guidance is None:
         return None
     if not isinstance(guidance, Guidance):
         raise ValueError(f"guidance must be a Guidance or None, got {type(guidance).__name__}")
+    if null_row is not None:
+        from . import _lib
+        guidance.validate()
+        if guidance.null_action is not MODEL_NULL and guidance.null_action != null_row:
+            raise ValueError(f"this model is conditioned on action vectors: its null row is row {null_row} of the per-call table, "
+                             f"not null_action={guidance.null_action} (pass Guidance(scale))")
+        return None if float(guidance.scale) == 1.0 else _lib.Guidance(scale=float(guidance.scale), null_action=int(null_row))
     guidance.validate(action_vocab_size)
     if float(guidance.scale) == 1.0:   # g = c: the unguided entry points, sizes and launches
         return None

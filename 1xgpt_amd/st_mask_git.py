@@ -15,6 +15,10 @@ Differences that are deliberate and visible:
   * per-frame action conditioning (not in the reference): with ``config.action_vocab_size = A > 0`` the model has an
     ``action_embed`` table (A, d_model) and every entry point takes ``action_ids`` (B, T): row ``action_ids[b, t]`` is
     added to every token of frame t of clip b, next to the positional embedding.
+  * continuous per-frame actions (not in the reference): with ``config.action_dim = A > 0`` the model has a learned
+    ``action_proj`` Linear(A, d_model), a learned ``action_null`` row and the buffers ``action_mean`` / ``action_std``; every entry
+    point takes ``action_vectors`` (B, T, A) float32, projected once per call (genie_action_rows) into a row table that the same
+    per-frame conditioning then addresses by index.
   * classifier-free guidance (not in the reference): ``maskgit_generate`` / ``generate`` take ``guidance=Guidance(scale, null_action)``.
 """
 import json
@@ -180,6 +184,15 @@ class STMaskGIT(nn.Module):
         self.out_x_proj = nn.Linear(config.d_model, config.factored_vocab_size * config.num_factored_vocabs)
         if config.action_vocab_size:
             self.action_embed = nn.Embedding(config.action_vocab_size, config.d_model)
+        if config.action_dim:
+            if config.action_dim > _lib.ACTION_MAX_DIM:
+                raise ValueError(f"action_dim {config.action_dim} > {_lib.ACTION_MAX_DIM} (GENIE_ACTION_MAX_DIM)")
+            self.action_proj = nn.Linear(config.action_dim, config.d_model)
+            self.action_null = nn.Parameter(torch.zeros(config.d_model))   # the learned "no action" row (guidance, action dropout)
+            self.register_buffer("action_mean", torch.zeros(config.action_dim))
+            self.register_buffer("action_std", torch.ones(config.action_dim))
+        self._inv_std = self._rows = None
+        self._row_ids = {}
         self.config = config
         self._table = None
         self._wide = []
@@ -198,11 +211,13 @@ class STMaskGIT(nn.Module):
 
     def _apply(self, fn, *a, **k):  # .to()/.cuda()/.float() move parameters: cached pointers are stale
         self._invalidate()
-        self._ws = None
+        self._ws = self._inv_std = self._rows = None
+        self._row_ids = {}
         return super()._apply(fn, *a, **k)
 
     def load_state_dict(self, *a, **k):
         self._invalidate()
+        self._inv_std = None
         return super().load_state_dict(*a, **k)
 
     def _device(self):
@@ -219,6 +234,7 @@ class STMaskGIT(nn.Module):
         """Forget the cached pointer table (packed copies, fused streams and range flags go with it)."""
         self._table = None
         self._wide = []
+        self._null_row_set = False   # row 0 of the cached action-row table is a copy of action_null
 
     def _weights(self):
         if self._table is not None:
@@ -269,11 +285,20 @@ class STMaskGIT(nn.Module):
     def _stream():
         return torch.cuda.current_stream().cuda_stream
 
-    def _cond(self, action_ids, B, n_frames=None):
+    def _cond(self, action_ids, B, n_frames=None, action_vectors=None):
         """The genie_frame_cond of a call on B clips (None for an unconditioned model), checked on the host before anything
         is enqueued.  action_ids: (B, T) integers in [0, A); (B, n_frames) with n_frames < T is padded to T (frames the
-        call never embeds)."""
+        call never embeds).  action_vectors: (B, T, action_dim) floats of a model with config.action_dim > 0, padded alike."""
         A, T = self.config.action_vocab_size, self.config.T
+        if action_ids is not None and action_vectors is not None:
+            raise ValueError("pass action_ids or action_vectors, not both")
+        if self.config.action_dim:
+            if action_ids is not None:
+                raise ValueError(f"action_ids given to a model conditioned on action vectors (action_dim={self.config.action_dim}): "
+                                 "pass action_vectors")
+            return self._cond_vectors(action_vectors, B, n_frames)
+        if action_vectors is not None:
+            raise ValueError("action_vectors given to a model without continuous actions (config.action_dim == 0)")
         if not A:
             if action_ids is not None:
                 raise ValueError("action_ids given to a model without actions (config.action_vocab_size == 0)")
@@ -294,15 +319,112 @@ class STMaskGIT(nn.Module):
         a = a.contiguous()
         return self._frame_cond(a)
 
-    def _frame_cond(self, a):
-        """genie_frame_cond of checked, contiguous int64 device ids (rows, T)."""
-        A = self.config.action_vocab_size
-        fc = _lib.FrameCond(table=self.action_embed.weight.data_ptr(), ids=a.data_ptr(), n_actions=A)
+    def _check_cond(self, action_ids, B, action_vectors=None, n_frames=None):
+        """The host-side checks of _cond alone: raises what _cond would raise, enqueues nothing."""
+        if self.config.action_dim and action_ids is None and action_vectors is not None:
+            T = self.config.T
+            self.check_action_vectors(action_vectors, (B, (T if n_frames is None else n_frames, T), self.config.action_dim))
+        else:
+            self._cond(action_ids, B, n_frames=n_frames, action_vectors=action_vectors)
+
+    def _frame_cond(self, a, like=None):
+        """genie_frame_cond of checked, contiguous int64 device ids (rows, T): over the model's action table, or over the
+        table of the genie_frame_cond `like` (the per-call row table of a model conditioned on action vectors)."""
+        if like is not None:
+            fc = _lib.FrameCond(table=like.table, ids=a.data_ptr(), n_actions=like.n_actions)
+            fc.rows = getattr(like, "rows", None)
+        else:
+            fc = _lib.FrameCond(table=self.action_embed.weight.data_ptr(), ids=a.data_ptr(), n_actions=self.config.action_vocab_size)
         fc.keep = a   # the ids tensor lives as long as the struct
+        return fc
+
+    # ---- continuous actions: project once per call, then the discrete path (genie_action_proj in include/genie_hip.h)
+    NULL_ROW = 0   # index of the learned null row in every per-call row table
+
+    def set_action_stats(self, mean, std):
+        """The input normalisation z = (a - mean) / std of the action vectors: (action_dim,) each, std > 0."""
+        D = self.config.action_dim
+        if not D:
+            raise ValueError("set_action_stats: this model has no continuous actions (config.action_dim == 0)")
+        mean = torch.as_tensor(mean, dtype=torch.float32).reshape(-1).cpu()
+        std = torch.as_tensor(std, dtype=torch.float32).reshape(-1).cpu()
+        if mean.numel() != D or std.numel() != D:
+            raise ValueError(f"set_action_stats: expected {D} means and {D} stds, got {mean.numel()} and {std.numel()}")
+        if not (bool(torch.isfinite(mean).all()) and bool(torch.isfinite(std).all()) and bool((std > 0).all())):
+            raise ValueError("set_action_stats: mean must be finite and std finite and > 0")
+        with torch.no_grad():
+            self.action_mean.copy_(mean)
+            self.action_std.copy_(std)
+        self._inv_std = None
+        return self
+
+    def check_action_vectors(self, action_vectors, shape, what="action_vectors"):
+        """Host-side checks of a float action tensor against `shape` (its last entry is action_dim; an entry that is a tuple allows
+        any of its members) -> contiguous float32 on the model's device.  Nothing is enqueued before a check fails."""
+        if action_vectors is None:
+            raise ValueError(f"this model is conditioned on action vectors (action_dim={self.config.action_dim}): pass {what} "
+                             f"{tuple(shape)}")
+        v = torch.as_tensor(action_vectors)
+        if not v.dtype.is_floating_point:
+            raise RuntimeError(f"{what} must be a floating-point tensor, got {v.dtype}")
+        ok = v.dim() == len(shape) and all(g in e if isinstance(e, tuple) else g == e for g, e in zip(v.shape, shape))
+        if not ok:
+            raise RuntimeError(f"expected {what} of shape {tuple(shape)}, got {tuple(v.shape)}")
+        if not bool(torch.isfinite(v).all()):
+            raise ValueError(f"{what} holds a non-finite entry")
+        return v.to(device=self._device(), dtype=torch.float32).contiguous()
+
+    def _action_proj_struct(self):
+        """The genie_action_proj over the parameters as they are now (pointers are read per call: a trainer re-points them)."""
+        if self._inv_std is None:   # 1 / std in f32 on the host (one read-back per set_action_stats / load / move)
+            import numpy as np
+            std = self.action_std.detach().cpu().numpy().astype(np.float32)
+            self._inv_std = torch.from_numpy(np.float32(1.0) / std).to(self._device())
+        p = _lib.ActionProj(weight=self.action_proj.weight.data_ptr(), bias=self.action_proj.bias.data_ptr(),
+                            mean=self.action_mean.data_ptr(), inv_std=self._inv_std.data_ptr(), action_dim=self.config.action_dim)
+        return p
+
+    def project_actions(self, vecs_nA, rows_nd):
+        """rows_nd (n, d_model) <- the projection of vecs_nA (n, action_dim), both contiguous f32 on the device: ONE launch."""
+        n = vecs_nA.shape[0]
+        assert vecs_nA.is_contiguous() and rows_nd.is_contiguous() and rows_nd.shape == (n, self.config.d_model)
+        for nm, t in (("action_proj.weight", self.action_proj.weight), ("action_proj.bias", self.action_proj.bias)):
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise RuntimeError(f"parameter {nm} must be contiguous float32 (got {t.dtype})")
+        _lib.check(_lib.load().genie_action_rows(self._action_proj_struct(), vecs_nA.data_ptr(), rows_nd.data_ptr(), n,
+                                                 self.config.d_model, self._stream()), "genie_action_rows")
+
+    def new_row_table(self, n_rows):
+        """A (1 + n_rows, d_model) row table whose row NULL_ROW is a copy of action_null (the others are the caller's to project)."""
+        t = torch.empty(1 + n_rows, self.config.d_model, dtype=torch.float32, device=self._device())
+        t[self.NULL_ROW].copy_(self.action_null.detach())
+        return t
+
+    def _cond_vectors(self, action_vectors, B, n_frames=None):
+        """genie_frame_cond of (B, T, action_dim) vectors: ONE genie_action_rows launch into the cached (1 + B T, d) table -- row 0
+        the null row, row 1 + b T + t frame (b, t) -- and the ids that address it."""
+        T, D = self.config.T, self.config.action_dim
+        n = T if n_frames is None else n_frames
+        v = self.check_action_vectors(action_vectors, (B, (n, T), D))
+        if v.shape[1] < T:   # frames the call never embeds
+            v = torch.cat([v, v.new_zeros(B, T - v.shape[1], D)], dim=1).contiguous()
+        if self._rows is None or self._rows.shape[0] < 1 + B * T or self._rows.device != v.device:
+            self._rows, self._null_row_set = self.new_row_table(B * T), True
+        elif not self._null_row_set:
+            self._rows[self.NULL_ROW].copy_(self.action_null.detach())
+            self._null_row_set = True
+        self.project_actions(v.view(B * T, D), self._rows[1:1 + B * T])
+        ids = self._row_ids.get(B)
+        if ids is None or ids.device != v.device:
+            ids = self._row_ids[B] = torch.arange(1, 1 + B * T, dtype=torch.int64, device=v.device).view(B, T)
+        fc = _lib.FrameCond(table=self._rows.data_ptr(), ids=ids.data_ptr(), n_actions=1 + B * T)
+        fc.keep, fc.rows, fc.vectors = ids, self._rows, v
         return fc
 
     def _guidance(self, guidance):
         """The genie_guidance of a call (None = unguided), checked on the host: a model without actions raises, like action_ids does."""
+        if self.config.action_dim:   # the model supplies the null row's index
+            return guidance_struct(guidance, null_row=self.NULL_ROW)
         return guidance_struct(guidance, self.config.action_vocab_size)
 
     def _ids(self, t, whole_clips=False):
@@ -316,26 +438,26 @@ class STMaskGIT(nn.Module):
         return t.to(torch.int64).contiguous()
 
     # ------------------------------------------------------------------ forward pieces
-    def hidden_states(self, x_THW: torch.LongTensor, action_ids=None):
+    def hidden_states(self, x_THW: torch.LongTensor, action_ids=None, action_vectors=None):
         """Run embed + decoder; the (B,T,S,d) result stays at offset 0 of the workspace (returned as a view)."""
         lib = _lib.load()
         cfg, w = self._weights()[:2]
         ids = self._ids(x_THW, whole_clips=True)
         B = ids.shape[0]
-        cond = self._cond(action_ids, B)
+        cond = self._cond(action_ids, B, action_vectors=action_vectors)
         ws = self._workspace(B)
         _lib.check(_lib.call_cond(lib, "genie_compute_logits", cond, cfg, w, ids.data_ptr(), B, 0, 0, 0, ws.data_ptr(),
                                   ws.data_ptr(), ws.numel(), self._stream()), "genie_compute_logits(hidden)")
         n = B * self.config.T * self.config.S * self.config.d_model
         return ws[: n * 4].view(torch.float32).view(B, self.config.T, self.config.S, self.config.d_model)
 
-    def compute_logits_frames(self, x_THW, t0, t1, layout="bcthw", action_ids=None):
+    def compute_logits_frames(self, x_THW, t0, t1, layout="bcthw", action_ids=None, action_vectors=None):
         """Logits of frames [t0,t1): (B, V, t1-t0, H, W) for layout='bcthw', (B, t1-t0, S, V) for 'token'."""
         lib = _lib.load()
         cfg, w = self._weights()[:2]
         ids = self._ids(x_THW, whole_clips=True)
         B = ids.shape[0]
-        cond = self._cond(action_ids, B)
+        cond = self._cond(action_ids, B, action_vectors=action_vectors)
         ws = self._workspace(B)
         nt, V = t1 - t0, self.config.factored_vocab_size * self.config.num_factored_vocabs
         if layout == "bcthw":
@@ -348,11 +470,11 @@ class STMaskGIT(nn.Module):
                                   ws.data_ptr(), ws.numel(), self._stream()), "genie_compute_logits")
         return out
 
-    def compute_logits(self, x_THW, action_ids=None):
+    def compute_logits(self, x_THW, action_ids=None, action_vectors=None):
         """ids (B,T,H,W) -> logits (B, V, T, H, W), channels [vocab0(512) | vocab1(512)]  (reference :255-265)."""
-        return self.compute_logits_frames(x_THW, 0, self.config.T, "bcthw", action_ids=action_ids)
+        return self.compute_logits_frames(x_THW, 0, self.config.T, "bcthw", action_ids=action_ids, action_vectors=action_vectors)
 
-    def ce_sums(self, x_THW, labels_THW, t0=1, t1=None, masked_only=True, action_ids=None):
+    def ce_sums(self, x_THW, labels_THW, t0=1, t1=None, masked_only=True, action_ids=None, action_vectors=None):
         """Fused forward + readout + factored CE: returns a (3,) float64 device tensor
         [sum CE, sum all-factors-correct, n counted] over frames [t0,t1); no logits leave the workspace."""
         lib = _lib.load()
@@ -360,9 +482,9 @@ class STMaskGIT(nn.Module):
         ids, lab = self._ids(x_THW, whole_clips=True), self._ids(labels_THW, whole_clips=True)
         B = ids.shape[0]
         t1 = self.config.T if t1 is None else t1
-        self._cond(action_ids, B)   # (argument errors before anything is enqueued)
+        self._check_cond(action_ids, B, action_vectors)   # (argument errors before anything is enqueued)
         ws = self._workspace(B)
-        self.hidden_states(ids, action_ids=action_ids)
+        self.hidden_states(ids, action_ids=action_ids, action_vectors=action_vectors)
         sums = torch.zeros(3, dtype=torch.float64, device=ids.device)
         _lib.check(lib.genie_readout_ce(cfg, w, ws.data_ptr(), lab.data_ptr(), ids.data_ptr() if masked_only else 0,
                                         B, t0, t1, sums.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
@@ -383,15 +505,15 @@ class STMaskGIT(nn.Module):
                                          sums.data_ptr(), self._stream()), "genie_factored_ce")
         return (sums[0] / sums[2]).float(), (sums[1] / sums[2]).float()  # 0/0 -> nan like the reference
 
-    def forward(self, input_ids, labels, action_ids=None):
+    def forward(self, input_ids, labels, action_ids=None, action_vectors=None):
         """(B, T*H*W) ids + labels -> GenieOutput(loss, acc, logits (B,V,T,H,W))  (reference :267-279)."""
         T, H, W = self.config.T, self.h, self.w
         x_THW = self._ids(input_ids).view(-1, T, H, W)
         lab = self._ids(labels).view(-1, T, H, W)
         if lab.shape != x_THW.shape:
             raise RuntimeError(f"labels {tuple(labels.shape)} do not match input_ids {tuple(input_ids.shape)}")
-        self._cond(action_ids, x_THW.shape[0])
-        logits = self.compute_logits(x_THW, action_ids=action_ids)  # leaves the hidden state in the workspace
+        self._check_cond(action_ids, x_THW.shape[0], action_vectors)
+        logits = self.compute_logits(x_THW, action_ids=action_ids, action_vectors=action_vectors)  # leaves the hidden state in the workspace
         lib = _lib.load()
         cfg, w = self._weights()[:2]
         B = x_THW.shape[0]
@@ -411,7 +533,8 @@ class STMaskGIT(nn.Module):
 
     @torch.no_grad()
     def maskgit_generate(self, prompt_THW, out_t, maskgit_steps=1, temperature=0.0, unmask_mode="random",
-                         noise=None, uniforms=None, return_logits=True, check=True, action_ids=None, sampling=None, guidance=None):
+                         noise=None, uniforms=None, return_logits=True, check=True, action_ids=None, sampling=None, guidance=None,
+                         action_vectors=None):
         """MaskGIT decode of frame ``out_t`` (reference :123-229): the whole loop runs on the device.
 
         Mutates ``prompt_THW[:, out_t]`` in place (reference :223) and returns
@@ -419,6 +542,8 @@ class STMaskGIT(nn.Module):
         noise: optional (maskgit_steps-1, B, S) float32 draws for "random" unmasking (default: torch.rand).
         uniforms: (maskgit_steps, num_factored_vocabs, B, S) for temperature > 1e-8 (default: torch.rand).
         action_ids: (B, T) actions of an action-conditioned model (config.action_vocab_size > 0), else None.
+        action_vectors: (B, T, action_dim) float actions of a model with config.action_dim > 0, else None; there ``Guidance(scale)``
+        needs no null_action (the model's learned null row is used).
         sampling: a ``SamplingConfig`` (logit temperature, top-k, top-p; 1xgpt_amd/sampling.py) or None = the reference's law.
         unmask_mode "confidence" (no reference counterpart) re-masks by confidence plus annealed Gumbel noise, drawn from ``noise``.
         guidance: a ``Guidance(scale, null_action)`` (1xgpt_amd/sampling.py) or None: classifier-free guidance of an action-conditioned
@@ -442,7 +567,7 @@ class STMaskGIT(nn.Module):
             raise RuntimeError(f"maskgit_generate expects a (B, T={self.config.T}, H, W) prompt, got {tuple(prompt_THW.shape)}")
         S, V = self.config.S, self.config.factored_vocab_size * self.config.num_factored_vocabs
         dev = prompt.device
-        cond = self._cond(action_ids, B)
+        cond = self._cond(action_ids, B, action_vectors=action_vectors)
         ws = self._workspace(B, guided=guide is not None)
         if unmask_mode != "greedy" and maskgit_steps > 1:
             if noise is None:
@@ -481,7 +606,7 @@ class STMaskGIT(nn.Module):
 
     def generate(self, input_ids, attention_mask=None, max_new_tokens=None, min_new_tokens=None, return_logits=False,
                  maskgit_steps=1, temperature=0.0, noise=None, kv_cache=True, action_ids=None, sampling=None,
-                 unmask_mode="random", uniforms=None, guidance=None):
+                 unmask_mode="random", uniforms=None, guidance=None, action_vectors=None):
         """Autoregressive frame generation behind the reference's Llama-style signature (st_mask_git.py:65-113):
         ``input_ids`` (B, n_prompt_frames * S) holds the prompt frames; ``max_new_tokens // S`` further frames are decoded one
         after the other with ``maskgit_generate``, each seeing every frame before it.  Returns the (B, (n_prompt + n_new) * S)
@@ -491,6 +616,7 @@ class STMaskGIT(nn.Module):
         kv_cache: True (default) = the frames are decoded by one-frame passes against a temporal KV cache; False = the reference's
         own schedule, a full forward over the canvas per MaskGIT step (same frames up to f32 accumulation order).
         action_ids: (B, T) -- or (B, n_prompt + n_new), padded to T -- actions of an action-conditioned model.
+        action_vectors: (B, T, action_dim) -- or (B, n_prompt + n_new, action_dim) -- float actions of a model with config.action_dim > 0.
         sampling / unmask_mode: as in ``maskgit_generate`` (the reference's generate always unmasks at random).
         uniforms: optional (n_new_frames, maskgit_steps, num_factored_vocabs, B, S) sampling draws to replay (temperature > 1e-8).
         guidance: as in ``maskgit_generate``; with ``return_logits`` the step-0 logits are the guided ones."""
@@ -507,7 +633,7 @@ class STMaskGIT(nn.Module):
         ids = self._ids(input_ids)
         B, n_new = ids.size(0), max_new_tokens // S
         n_prompt = ids.numel() // (B * S)
-        cond = self._cond(action_ids, B, n_frames=n_prompt + n_new)
+        cond = self._cond(action_ids, B, n_frames=n_prompt + n_new, action_vectors=action_vectors)
         if kv_cache and n_new >= 1 and n_prompt >= 1 and n_prompt + n_new <= self.config.T:
             # the same frames on the temporal KV cache, the whole loop one library call (genie_generate_cached): every MaskGIT step
             # runs the rows of the frame being decoded instead of a full forward over the canvas (causal in time: the all-MASK
@@ -552,7 +678,8 @@ class STMaskGIT(nn.Module):
         for k in range(n_new):
             frame, logits = self.maskgit_generate(canvas, n_prompt + k, maskgit_steps=maskgit_steps, temperature=temperature,
                                                   noise=None if noise is None else noise[k], return_logits=return_logits,
-                                                  action_ids=None if cond is None else cond.keep, sampling=sampling,
+                                                  action_ids=None if cond is None or self.config.action_dim else cond.keep,
+                                                  action_vectors=cond.vectors if self.config.action_dim else None, sampling=sampling,
                                                   unmask_mode=unmask_mode, uniforms=None if uniforms is None else uniforms[k],
                                                   guidance=guidance)
             canvas[:, n_prompt + k] = frame
@@ -596,10 +723,12 @@ class STMaskGIT(nn.Module):
                   os.path.join(save_directory, "model.safetensors"))
 
     @classmethod
-    def from_pretrained(cls, pretrained_model_name_or_path, precision="exact", action_vocab_size=None, **kwargs):
+    def from_pretrained(cls, pretrained_model_name_or_path, precision="exact", action_vocab_size=None, action_dim=None, **kwargs):
         """Load a local HF-style checkpoint directory (hub ids need a network and are not supported offline).
         action_vocab_size=A > 0 on an unconditioned checkpoint: a warm start -- every stored tensor loads strictly and the new
-        action table is zero, so the model computes exactly what the checkpoint does until the table is trained."""
+        action table is zero, so the model computes exactly what the checkpoint does until the table is trained.
+        action_dim=A > 0 on an unconditioned checkpoint: the same warm start for continuous actions -- zero projection weight, bias
+        and null row, mean 0 and std 1."""
         from safetensors.torch import load_file
         d = str(pretrained_model_name_or_path)
         if not os.path.isdir(d):
@@ -618,14 +747,27 @@ class STMaskGIT(nn.Module):
         sd = load_file(os.path.join(d, "model.safetensors"))
         warm = False
         if action_vocab_size is not None and action_vocab_size != config.action_vocab_size:
-            if config.action_vocab_size:
-                raise ValueError(f"checkpoint has action_vocab_size={config.action_vocab_size}, asked for {action_vocab_size}")
+            if config.action_vocab_size or config.action_dim:
+                raise ValueError(f"checkpoint has action_vocab_size={config.action_vocab_size}, action_dim={config.action_dim}; "
+                                 f"asked for action_vocab_size={action_vocab_size}")
             config.action_vocab_size = int(action_vocab_size)
             warm = config.action_vocab_size > 0
+        warm_vec = False
+        if action_dim is not None and action_dim != config.action_dim:
+            if config.action_dim or config.action_vocab_size:
+                raise ValueError(f"checkpoint has action_dim={config.action_dim}, action_vocab_size={config.action_vocab_size}; "
+                                 f"asked for action_dim={action_dim}")
+            config = GenieConfig(**{**vars(config), "action_dim": int(action_dim)})   # (runs the exclusivity check)
+            warm_vec = config.action_dim > 0
         model = cls(config, precision=precision)
         if warm:
             sd = dict(sd)
             sd["action_embed.weight"] = torch.zeros(config.action_vocab_size, config.d_model)
+        if warm_vec:
+            sd = dict(sd)
+            sd.update({"action_proj.weight": torch.zeros(config.d_model, config.action_dim), "action_proj.bias": torch.zeros(config.d_model),
+                       "action_null": torch.zeros(config.d_model), "action_mean": torch.zeros(config.action_dim),
+                       "action_std": torch.ones(config.action_dim)})
         model.load_state_dict(sd, strict=True)
         model.eval()
         return model

@@ -55,6 +55,9 @@ def state_dict_spec(cfg: GenieConfig):
     spec.append(("out_x_proj.bias", (V,), "bias", 1))
     if cfg.action_vocab_size:
         spec.append(("action_embed.weight", (cfg.action_vocab_size, d), "emb", 1))
+    if cfg.action_dim:   # continuous actions: the projection of O(1) inputs lands at the scale of an action-table row
+        spec += [("action_proj.weight", (d, cfg.action_dim), "act_lin", cfg.action_dim), ("action_proj.bias", (d,), "bias", 1),
+                 ("action_null", (d,), "emb", 1), ("action_mean", (cfg.action_dim,), "zeros", 1), ("action_std", (cfg.action_dim,), "ones", 1)]
     return spec
 
 
@@ -69,8 +72,10 @@ def make_state_dict(cfg: GenieConfig, seed: int = 0, law: str = "conditioned") -
     for key, shape, kind, fan_in in state_dict_spec(cfg):
         g = _rng(seed, key)
         z = g.standard_normal(shape, dtype=np.float32)
-        if law == "init":
-            if kind in ("lin", "lin_res", "readout", "emb", "pos"):
+        if kind in ("zeros", "ones"):   # the action statistics' defaults (buffers, not learned)
+            w = np.zeros(shape, np.float32) if kind == "zeros" else np.ones(shape, np.float32)
+        elif law == "init":
+            if kind in ("lin", "lin_res", "readout", "emb", "pos", "act_lin"):
                 w = z * np.float32(0.02)
             elif kind == "gamma":
                 w = np.ones(shape, np.float32)
@@ -85,6 +90,8 @@ def make_state_dict(cfg: GenieConfig, seed: int = 0, law: str = "conditioned") -
                 w = z * np.float32(1.0 / np.sqrt(fan_in))
             elif kind == "emb":
                 w = z * np.float32(0.7)
+            elif kind == "act_lin":
+                w = z * np.float32(0.7 / np.sqrt(fan_in))
             elif kind == "pos":
                 w = z * np.float32(0.5)
             elif kind == "gamma":

@@ -49,8 +49,9 @@ def lr_factor_linear(warmup_steps, max_steps):
 
 def decays(name: str) -> bool:
     """train.py:427-437: names containing "bias" or "layer_norm.weight" are excluded from weight decay.  No GENIE
-    parameter is called layer_norm.* (they are norm1/norm2/norm), so LayerNorm weights DO decay, as in the reference."""
-    return not ("bias" in name or "layer_norm.weight" in name)
+    parameter is called layer_norm.* (they are norm1/norm2/norm), so LayerNorm weights DO decay, as in the reference.
+    The learned null row of a model conditioned on action vectors (no reference counterpart) is a bias-like row and does not decay."""
+    return not ("bias" in name or "layer_norm.weight" in name or name == "action_null")
 
 
 # ------------------------------------------------------------------ pointer tables
@@ -99,13 +100,14 @@ def weights_table(config, tensors, w16=None):
 
 
 def _embedding_side(name):
-    return name.startswith("token_embed.") or name in ("pos_embed_TSC", "action_embed.weight")
+    return name.startswith("token_embed.") or name in ("pos_embed_TSC", "action_embed.weight", "action_proj.weight", "action_proj.bias",
+                                                        "action_null")
 
 
 def ready_order(config, names):
     """Parameter names in the order their gradients are final during the backward: readout, layers L-1..0 (within a
     layer: decaying tensors first, so each layer is two AdamW ranges), then the embedding side (with the action table of an
-    action-conditioned model last)."""
+    action-conditioned model last -- or the projection weight, bias and null row of one conditioned on action vectors)."""
     names = list(names)
     head = [n for n in names if n.startswith("out_x_proj.")]
     emb = [n for n in names if _embedding_side(n)]
@@ -248,6 +250,7 @@ class GenieTrainer:
         self.scratch = torch.zeros(1024, dtype=torch.float64, device=dev)
         self._acts = self._ws = None
         self._B = 0
+        self._d_rows = None   # (1 + B T, d) scratch: d loss / d rows of a model conditioned on action vectors, overwritten per call
 
     def pack_weights(self):
         """Refresh the 16-bit weight copies from the f32 parameters (no-op in the exact precision).  Call this (or
@@ -281,17 +284,35 @@ class GenieTrainer:
         return torch.cuda.current_stream().cuda_stream
 
     # ------------------------------------------------------------------ forward / backward (train.py:611-617)
-    def forward_backward(self, input_ids, labels, accumulate=False, reduce=True, action_ids=None):
+    def forward_backward(self, input_ids, labels, accumulate=False, reduce=True, action_ids=None, action_vectors=None, action_drop=None):
         """One micro-batch: loss/acc of STMaskGIT.forward and gradients into the flat buffer (added when
         `accumulate`).  Returns (loss, acc) as 0-dim float64 CUDA tensors (no host sync).
-        action_ids: (B, T) per-frame actions of an action-conditioned model (config.action_vocab_size > 0)."""
+        action_ids: (B, T) per-frame actions of an action-conditioned model (config.action_vocab_size > 0).
+        action_vectors: (B, T, action_dim) float actions of a model with config.action_dim > 0: projected into per-frame rows (one launch),
+        the existing forward and backward run on those rows, and d loss / d rows -- a (1 + B T, d) scratch, row 0 the null row's -- becomes
+        the gradients of action_proj (genie_action_rows_backward, one launch) and of action_null.
+        action_drop: (B,) bool with action_vectors (action dropout, data.maskgit_collate): a dropped clip's frames read the null row, so
+        their projected rows get a zero gradient and the null row theirs."""
         if not (input_ids.is_cuda and labels.is_cuda):
             raise RuntimeError("1xgpt_amd runs on the GPU only (no CPU fallback): move the batch to cuda")
         ids = input_ids.to(torch.int64).contiguous()
         lab = labels.to(torch.int64).contiguous()
         B = ids.shape[0]
         assert ids.shape == lab.shape == (B, self.config.T * self.config.S), ids.shape
-        cond = self.model._cond(action_ids, B)
+        vec = self.config.action_dim > 0
+        if action_drop is not None and not vec:
+            raise ValueError("action_drop needs a model conditioned on action vectors (config.action_dim > 0)")
+        drop = None
+        if action_drop is not None:
+            drop = torch.as_tensor(action_drop)
+            if drop.dtype != torch.bool or tuple(drop.shape) != (B,):
+                raise RuntimeError(f"expected action_drop of shape ({B},) and dtype bool, got {tuple(drop.shape)} {drop.dtype}")
+        cond = self.model._cond(action_ids, B, action_vectors=action_vectors)
+        if drop is not None:
+            vectors = cond.vectors
+            rows_ids = torch.where(drop.to(cond.keep.device)[:, None], self.model.NULL_ROW, cond.keep).contiguous()
+            cond = self.model._frame_cond(rows_ids, like=cond)
+            cond.vectors = vectors
         acts, ws = self._buffers(B)
         lib, cfg, st = self.lib, self.cfg, self._stream()
         acc_flag = 1 if accumulate else 0
@@ -313,6 +334,21 @@ class GenieTrainer:
         if cond is None:
             _lib.check(lib.genie_train_backward_embed(cfg, self.g_table, ids.data_ptr(), B, ws.data_ptr(), ws.numel(),
                                                       acc_flag, st), "genie_train_backward_embed")
+        elif vec:
+            n, d = B * self.config.T, self.config.d_model
+            if self._d_rows is None or self._d_rows.shape[0] != 1 + n:
+                self._d_rows = torch.empty(1 + n, d, dtype=torch.float32, device=self.params.device)
+            if accumulate:   # the table gradient shares the embeddings' accumulate flag: start the scratch from zero instead
+                self._d_rows.zero_()
+            _lib.check(lib.genie_train_backward_embed_cond(cfg, self.g_table, ids.data_ptr(), B, ws.data_ptr(), ws.numel(),
+                                                           acc_flag, st, self._d_rows.data_ptr(), cond),
+                       "genie_train_backward_embed_cond")
+            _lib.check(lib.genie_action_rows_backward(self.model._action_proj_struct(), cond.vectors.data_ptr(),
+                                                      self._d_rows[1:].data_ptr(), n, d, self.g_views["action_proj.weight"].data_ptr(),
+                                                      self.g_views["action_proj.bias"].data_ptr(), acc_flag, st),
+                       "genie_action_rows_backward")
+            g_null = self.g_views["action_null"]
+            g_null.add_(self._d_rows[0]) if accumulate else g_null.copy_(self._d_rows[0])
         else:
             _lib.check(lib.genie_train_backward_embed_cond(cfg, self.g_table, ids.data_ptr(), B, ws.data_ptr(), ws.numel(),
                                                            acc_flag, st, self.g_views["action_embed.weight"].data_ptr(), cond),
@@ -356,7 +392,8 @@ class GenieTrainer:
         `gradient_accumulation_steps` calls.  Returns device scalars (no host sync)."""
         is_update = (self._micro + 1) % self.accum == 0
         loss, acc = self.forward_backward(batch["input_ids"], batch["labels"], accumulate=self._micro % self.accum != 0,
-                                          reduce=is_update and self.accum == 1, action_ids=batch.get("action_ids"))
+                                          reduce=is_update and self.accum == 1, action_ids=batch.get("action_ids"),
+                                          action_vectors=batch.get("action_vectors"), action_drop=batch.get("action_drop"))
         self._micro += 1
         out = {"loss": loss, "acc": acc}
         if is_update:

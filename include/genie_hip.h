@@ -730,6 +730,38 @@ int genie_adamw_step(float* params, const float* grads, float* exp_avg, float* e
                      float beta2, float eps, float weight_decay, int step, float grad_mult, const double* grad_sumsq,
                      float max_grad_norm, void* stream);
 
+/* Continuous per-frame actions (ABI 3 addition; nothing above changes).  A model conditioned on float action vectors of A values per
+ * frame projects them, once per call, into the rows that genie_frame_cond addresses: the caller builds a table of one learned "no
+ * action" row plus one projected row per frame of the call, points cond->table at it and cond->ids at "row of frame (b, t)", and every
+ * *_cond / *_ex / *_guided / rollout entry point and genie_guidance.null_action then work by index, unchanged.  Reference counterpart:
+ * none (its README announces raw actions; its data.py leaves them commented out).
+ * The arithmetic, in f32 with every operation rounded on its own and no FMA contraction, reproducible bit for bit in NumPy f32:
+ *     z_j   = (a_j - mean_j) * inv_std_j          -- a NULL mean skips the subtraction, a NULL inv_std the product (not "with 0 or 1")
+ *     row_c = bias_c (0.0f when bias is NULL); then for j = 0 .. A-1 ascending:  row_c = row_c + (W[c,j] * z_j)
+ * and for the gradients, given d_rows = d loss / d rows (n, d_model), both sums starting from 0.0f and walking n = 0 .. n-1 ascending,
+ * strictly in sequence (one level, no chunks, no atomics: the same bytes run to run):
+ *     d_bias[c]     = sum_n d_rows[n,c]
+ *     d_weight[c,j] = sum_n (d_rows[n,c] * z[n,j])
+ * accumulate = 0 stores the finished sum; accumulate = 1 stores old + sum (one add).
+ * Sizes: 1 <= A <= GENIE_ACTION_MAX_DIM, 1 <= d_model <= 1024 (GENIE_E_SHAPE beyond).  A NULL p / vecs / rows / d_rows / d_weight / p->weight
+ * (forward), A < 1, d_model < 1 or n < 0: GENIE_E_ARG, nothing enqueued.  n == 0: success, nothing enqueued, nothing written.  d_bias may
+ * be NULL (no bias gradient).  The struct is read on the host during the call; its pointers are device pointers. */
+#define GENIE_ACTION_MAX_DIM 256
+typedef struct genie_action_proj {
+    const float* weight;   /* (d_model, A) f32, nn.Linear layout */
+    const float* bias;     /* (d_model) or NULL */
+    const float* mean;     /* (A) or NULL: input normalisation */
+    const float* inv_std;  /* (A) or NULL; 1/std computed by the caller in f32 */
+    int32_t action_dim;    /* A >= 1 */
+} genie_action_proj;
+/* sizeof(genie_action_proj) and the offsets of its five fields, in declaration order: writes min(n, 6) entries, returns 6. */
+int genie_action_proj_layout(size_t* out_host, int n);
+/* rows (n, d_model) <- the projection of vecs (n, A): one launch. */
+int genie_action_rows(const genie_action_proj* p, const float* vecs, float* rows, int64_t n, int d_model, void* stream);
+/* d_weight (d_model, A) and d_bias (d_model) from d_rows (n, d_model) and the same vecs (n, A): one launch; p->weight is not read. */
+int genie_action_rows_backward(const genie_action_proj* p, const float* vecs, const float* d_rows, int64_t n, int d_model,
+                               float* d_weight, float* d_bias, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,9 @@ def main():
     ap.add_argument("--guidance_scale", type=float, default=None,
                     help="classifier-free guidance A/B on an action-conditioned variant of the model (8 actions, null action 0), KV-cache "
                          "schedule: per batch B, interleaved in one process, unguided at B, unguided at 2B and guided at B with this scale")
+    ap.add_argument("--action_dim", type=int, default=0,
+                    help="plain run on a variant of the model conditioned on continuous action vectors of this many values per frame")
+    ap.add_argument("--action_vocab_size", type=int, default=0, help="plain run on an action-conditioned variant with this many action ids")
     ap.add_argument("--repeats", type=int, default=7, help="interleaved rounds of the guidance A/B and of the rollout leg")
     ap.add_argument("--rollout", type=int, default=None,
                     help="rollout leg: ms per generated frame of rollout_frames at this many new frames (prompt 8) against generate_frames_cached "
@@ -122,6 +125,10 @@ def main():
     cfg = cfgmod.c138() if a.model == "c138" else cfgmod.c35()
     if a.guidance_scale is not None:
         cfg.action_vocab_size = 8
+    elif a.action_dim:
+        cfg = cfgmod.GenieConfig(**{**vars(cfg), "action_dim": a.action_dim})
+    elif a.action_vocab_size:
+        cfg.action_vocab_size = a.action_vocab_size
     m = STMaskGIT(cfg, precision=a.precision).load_numpy_state_dict(synth.make_state_dict(cfg, seed=0)).to("cuda")
     if a.guidance_scale is not None:
         return guidance_ab(a, m, cfg, extra)
@@ -132,6 +139,10 @@ def main():
         ex = torch.from_numpy(synth.make_clips(B, cfg, seed=7)).cuda().view(B, 16, 16, 16)
         for steps in a.steps:
             noise = torch.rand(8, max(steps - 1, 1), B, cfg.S, device="cuda")
+            if cfg.action_dim:
+                extra["action_vectors"] = torch.randn(B, cfg.T, cfg.action_dim, generator=torch.Generator().manual_seed(B)).cuda()
+            elif cfg.action_vocab_size:
+                extra["action_ids"] = torch.randint(0, cfg.action_vocab_size, (B, cfg.T), generator=torch.Generator().manual_seed(B)).cuda()
             for name, fn in (("full_forward", G.generate_frames), ("kv_cache", G.generate_frames_cached)):
                 if name not in a.schedules or (name == "full_forward" and B * steps > 64):
                     continue
@@ -144,7 +155,8 @@ def main():
                     out = fn(m, ex, 8, steps, a.temperature, False, noise=noise, **extra)
                 torch.cuda.synchronize()
                 dt = (time.perf_counter() - t0) / reps
-                res.append({"schedule": name, "batch": B, "maskgit_steps": steps, "sampler": bool(a.sampler),
+                res.append({"schedule": name, "batch": B, "maskgit_steps": steps, "sampler": bool(a.sampler), "action_dim": cfg.action_dim,
+                            "action_vocab_size": cfg.action_vocab_size,
                             "temperature": a.temperature, "seconds": dt,
                             "frames_per_sec": 8 * B / dt, "s_per_frame": dt / (8 * B)})
                 print(res[-1], flush=True)

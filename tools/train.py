@@ -58,6 +58,9 @@ def parse_args():
     p.add_argument("--action_dropout", type=float, default=0.0,
                    help="share of the training clips whose actions are replaced by --null_action (trains the null action of "
                         "classifier-free guidance; action-conditioned configs only)")
+    p.add_argument("--action_dim", type=int, default=0,
+                   help="condition the model on continuous per-frame action vectors of this many values (the datasets' states.bin; "
+                        "random vectors under --synthetic); with --action_dropout a dropped clip reads the model's learned null row")
     p.add_argument("--null_action", type=int, default=None, help="row of the action table that stands for 'no action'")
     p.add_argument("--synthetic", type=int, default=0, help="train on N synthetic clips (no dataset on disk)")
     p.add_argument("--model", choices=["c138", "c35", "tiny"], default="c35", help="shape when no --genie_config is given")
@@ -86,6 +89,8 @@ def main():
                {"c138": cfgmod.c138, "c35": cfgmod.c35,
                 "tiny": lambda: cfgmod.GenieConfig(num_layers=2, num_heads=2, d_model=64, T=4, S=16, num_factored_vocabs=2,
                                                    qk_norm=False, num_prompt_frames=2)}[args.model]())
+        if args.action_dim:
+            cfg = cfgmod.GenieConfig(**{**vars(cfg), "action_dim": args.action_dim})
         train_clips = torch.from_numpy(synth.make_clips(args.synthetic, cfg, seed=1))
         eval_clips = train_clips[: max(1, args.synthetic // 8)]
         get_train = lambda idx: train_clips[idx]  # noqa: E731
@@ -96,6 +101,10 @@ def main():
             train_acts = torch.randint(0, cfg.action_vocab_size, (len(train_clips), cfg.T), generator=g)
             get_train_acts = lambda idx: train_acts[idx]  # noqa: E731
             get_eval_acts = lambda idx: train_acts[: len(eval_clips)][idx]  # noqa: E731
+        if cfg.action_dim:   # synthetic per-frame action vectors
+            train_vecs = torch.randn(len(train_clips), cfg.T, cfg.action_dim, generator=torch.Generator().manual_seed(2))
+            get_train_acts = lambda idx: train_vecs[idx]  # noqa: E731
+            get_eval_acts = lambda idx: train_vecs[: len(eval_clips)][idx]  # noqa: E731
     else:
         tds = datamod.RawTokenDataset(args.train_data_dir, window_size=args.window_size, stride=args.stride,
                                       filter_overlaps=args.filter_overlaps)
@@ -105,7 +114,15 @@ def main():
         cfg = cfgmod.GenieConfig.from_pretrained(args.genie_config)
         cfg.image_vocab_size, cfg.T, cfg.S = tds.metadata["vocab_size"], args.window_size, tds.metadata["s"] ** 2
         cfg.__post_init__()
+        if args.action_dim:
+            cfg = cfgmod.GenieConfig(**{**vars(cfg), "action_dim": args.action_dim})
         get_train, get_eval, n_train, n_eval = tds.batch, eds.batch, len(tds), len(eds)
+        if cfg.action_dim:
+            for name, ds in (("train", tds), ("val", eds)):
+                if ds.action_vectors is None or ds.action_vectors.shape[1] != cfg.action_dim:
+                    sys.exit(f"train.py: the config takes action vectors (action_dim {cfg.action_dim}) but the {name} dataset has no "
+                             f"states.bin of that width")
+            get_train_acts, get_eval_acts = tds.action_vector_batch, eds.action_vector_batch
         if cfg.action_vocab_size:
             for name, ds in (("train", tds), ("val", eds)):
                 if ds.actions is None:
@@ -115,9 +132,13 @@ def main():
 
     load_from = args.resume_from_checkpoint or args.warmstart_path
     warm_actions = cfg.action_vocab_size if (args.warmstart_path and not args.resume_from_checkpoint) else None
-    model = (STMaskGIT.from_pretrained(load_from, precision=args.precision, action_vocab_size=warm_actions or None) if load_from
+    warm_dim = cfg.action_dim if (args.warmstart_path and not args.resume_from_checkpoint) else None
+    model = (STMaskGIT.from_pretrained(load_from, precision=args.precision, action_vocab_size=warm_actions or None,
+                                       action_dim=warm_dim or None) if load_from
              else STMaskGIT(cfg, precision=args.precision))
-    acts_of = (lambda get, idx: get(idx).to(dev)) if model.config.action_vocab_size else (lambda get, idx: None)
+    conditioned = model.config.action_vocab_size or model.config.action_dim
+    acts_of = (lambda get, idx: get(idx).to(dev)) if conditioned else (lambda get, idx: None)
+    act_key = "action_vectors" if model.config.action_dim else "action_ids"   # the collator's and the model's keyword
     if model.config.action_vocab_size and not cfg.action_vocab_size:
         sys.exit("train.py: the checkpoint is action-conditioned: give a --genie_config with its action_vocab_size")
     if not load_from and args.mu_transfer:
@@ -157,8 +178,8 @@ def main():
         eb = args.per_device_eval_batch_size
         for k, s0 in enumerate(range(rank * eb, n_eval - eb * world + 1, eb * world)):
             batch = datamod.maskgit_collate(get_eval(range(s0, s0 + eb)).to(dev), cfg,
-                                            action_ids=acts_of(get_eval_acts, range(s0, s0 + eb)))
-            out = model(batch["input_ids"], batch["labels"], action_ids=batch.get("action_ids"))
+                                            **{act_key: acts_of(get_eval_acts, range(s0, s0 + eb))})
+            out = model(batch["input_ids"], batch["labels"], **{act_key: batch.get(act_key)})
             sums += torch.stack([out.loss.double() * eb, out.acc.double() * eb, torch.tensor(float(eb), device=dev).double()])
             if k + 1 >= args.max_eval_steps:
                 break
@@ -175,8 +196,8 @@ def main():
         perm = torch.randperm(n_train, generator=g)  # same permutation on every rank; rank r takes its slice
         for m in range(consumed % micro_per_epoch if epoch == consumed // micro_per_epoch else 0, micro_per_epoch):
             idx = perm[(m * world + rank) * B:(m * world + rank + 1) * B].tolist()
-            batch = datamod.maskgit_collate(get_train(idx).to(dev), cfg, action_ids=acts_of(get_train_acts, idx),
-                                            action_dropout=args.action_dropout if model.config.action_vocab_size else 0.0,
+            batch = datamod.maskgit_collate(get_train(idx).to(dev), cfg, **{act_key: acts_of(get_train_acts, idx)},
+                                            action_dropout=args.action_dropout if conditioned else 0.0,
                                             null_action=args.null_action)
             out = tr.train_step(batch)
             loss_info += torch.stack([out["loss"] * B, torch.tensor(float(B), device=dev, dtype=torch.float64)])
