@@ -281,8 +281,16 @@ int launch_action_embed_bwd(const genie_cfg& c, const float* dx, const int64_t* 
 int launch_sumsq(const float* x, size_t n, double* out, double* scratch, hipStream_t st);
 // 16-bit operand copies (kernels_train16.hip); npl = 1 bf16, 2 = f16 split planes [hi | lo]
 // colpart != NULL: also the column sums of the (post-gelu') values: slabs [rows/64][cols] for launch_slab_reduce
+// scale16 (npl == 2 only): the split copies hold in * scale16, saturated at +-65504 (the column sums and the MODE 1 write-back
+// are unscaled); the consumer folds 1 / scale16 into its alpha
 int launch_cast_transpose16(int npl, float* in, long ld, const float* z, uint16_t* out16, uint16_t* out16T, int rows,
-                            int cols, hipStream_t st, float* colpart = nullptr);
+                            int cols, hipStream_t st, float* colpart = nullptr, float scale16 = 1.0f);
+// f16x3 training: every gradient operand (d logits, dY, dz) is split as hi + lo/2048 of 2^12 times its value.  A loss averaged
+// over n tokens has gradients of order 1/n and below; under 2^-14 an f16 hi is flushed to zero (split_f16), the value then lives in
+// lo alone and the three-product GEMM (hi.hi + hi.lo + lo.hi, no lo.lo) multiplies it with the hi half of the other operand only:
+// 11 bits of the weight or activation instead of 22, 1e-4 of a gradient tensor's largest element at a few hundred tokens.  Scaled
+// by 2^12 values down to 1.5e-8 keep a normal hi; values of 16 and above saturate at the f16 range instead of overflowing.
+constexpr float GRAD_SCALE16 = 4096.0f;
 int launch_transpose16(int npl, const uint16_t* in, uint16_t* outT, int rows, int cols, hipStream_t st);
 // bf16 copy in the same orientation (+ gelu'(z)) and the [rows/64][cols] column-sum partials; no transposed copy
 int launch_cast_rows16(const float* in, long ld, const float* z, uint16_t* out16, int rows, int cols, hipStream_t st,

@@ -14,6 +14,8 @@ __device__ __forceinline__ void to16(float v, uint16_t& hi, uint16_t& lo) {
 }
 
 // MODE 0: v = in;  MODE 1: v = in * gelu'(z), also written back to `in` (f32 dz for the bias gradient)
+// NPL == 2: the split copies hold v * scale16 (a power of two, saturated at the f16 range), see GRAD_SCALE16 in kernels.hpp;
+// the f32 write-back and the column sums are of v itself
 __device__ __forceinline__ float gelu_grad16(float z) {
     const float cdf = 0.5f * (1.0f + erff(z * 0.70710678118654752440f));
     const float pdf = expf(-0.5f * z * z) * 0.39894228040143267794f;
@@ -24,7 +26,7 @@ __device__ __forceinline__ float gelu_grad16(float z) {
 template <int NPL, int MODE>
 __global__ __launch_bounds__(256) void cast_transpose_kernel(float* __restrict__ in, long ld, const float* __restrict__ z,
                                                              uint16_t* __restrict__ out16, uint16_t* __restrict__ out16T,
-                                                             int rows, int cols, float* __restrict__ colpart) {
+                                                             int rows, int cols, float* __restrict__ colpart, float scale16) {
     __shared__ uint16_t tile[NPL][64][66];
     __shared__ float csum[4][64];
     float cs = 0.f;  // column c0+tx over this thread's 16 rows (bias gradient partial)
@@ -42,6 +44,10 @@ __global__ __launch_bounds__(256) void cast_transpose_kernel(float* __restrict__
         }
         cs += v;
         uint16_t hi, lo;
+        if constexpr (NPL == 2) {   // saturate at the f16 range; comparisons, not fminf / fmaxf: a NaN stays a NaN
+            v *= scale16;
+            v = v > 65504.0f ? 65504.0f : (v < -65504.0f ? -65504.0f : v);
+        }
         to16<NPL>(v, hi, lo);
         tile[0][rl][tx] = hi;
         if constexpr (NPL == 2) tile[1][rl][tx] = lo;
@@ -151,17 +157,17 @@ static int check64(int rows, int cols, const char* what) {
 
 // mode 0: plain cast; mode 1: in *= gelu'(z) first (in place).  out16 may be NULL.
 int launch_cast_transpose16(int npl, float* in, long ld, const float* z, uint16_t* out16, uint16_t* out16T, int rows,
-                            int cols, hipStream_t st, float* colpart) {
+                            int cols, hipStream_t st, float* colpart, float scale16) {
     GENIE_TRY(check64(rows, cols, "cast_transpose16"));
     if (!rows || !cols) return GENIE_OK;
     dim3 grid(cols / 64, rows / 64);
     ProfScope prof(GENIE_KC_OTHER, 0.0, (double)rows * cols * (4.0 + (z ? 8.0 : 0.0) + 2.0 * npl * (out16 ? 2 : 1)), st);
     if (npl == 1) {
-        if (z) cast_transpose_kernel<1, 1><<<grid, 256, 0, st>>>(in, ld, z, out16, out16T, rows, cols, colpart);
-        else cast_transpose_kernel<1, 0><<<grid, 256, 0, st>>>(in, ld, nullptr, out16, out16T, rows, cols, colpart);
+        if (z) cast_transpose_kernel<1, 1><<<grid, 256, 0, st>>>(in, ld, z, out16, out16T, rows, cols, colpart, scale16);
+        else cast_transpose_kernel<1, 0><<<grid, 256, 0, st>>>(in, ld, nullptr, out16, out16T, rows, cols, colpart, scale16);
     } else {
-        if (z) cast_transpose_kernel<2, 1><<<grid, 256, 0, st>>>(in, ld, z, out16, out16T, rows, cols, colpart);
-        else cast_transpose_kernel<2, 0><<<grid, 256, 0, st>>>(in, ld, nullptr, out16, out16T, rows, cols, colpart);
+        if (z) cast_transpose_kernel<2, 1><<<grid, 256, 0, st>>>(in, ld, z, out16, out16T, rows, cols, colpart, scale16);
+        else cast_transpose_kernel<2, 0><<<grid, 256, 0, st>>>(in, ld, nullptr, out16, out16T, rows, cols, colpart, scale16);
     }
     GENIE_LAUNCH_CHECK("cast_transpose16");
     return GENIE_OK;

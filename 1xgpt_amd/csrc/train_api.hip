@@ -82,6 +82,10 @@ static int train_check(const genie_cfg* c, int B) {
                           "training step (16-bit): d_model, hidden, T*S and the vocabulary rows must be multiples of 64");
     GENIE_CHECK_SHAPE(c->S % 16 == 0 && c->head_dim % 16 == 0 && c->d_model % 16 == 0 && c->hidden % 16 == 0 && c->T <= 16,
                       "training step: S, head_dim, d_model, hidden must be multiples of 16 and T <= 16");
+    // the temporal attention backward and the qk-norm kernels of the backward exist for head_dim 32 / 64 only: refuse here,
+    // before any forward is launched for a step that cannot finish
+    GENIE_CHECK_SHAPE(c->head_dim == 32 || c->head_dim == 64, "training step: head_dim %d is not supported (32 or 64)",
+                      c->head_dim);
     return GENIE_OK;
 }
 
@@ -221,6 +225,10 @@ static TrainWs16 train_ws16(const genie_cfg& c, int B, int npl, void* base, size
     w.dy16 = (uint16_t*)(b + o1); w.dy16T = (uint16_t*)(b + o2); w.xT16 = (uint16_t*)(b + o3);
     return w;
 }
+// f16x3: the gradient copies made by cast_t_bias hold GRAD_SCALE16 times the gradient (kernels.hpp); every product that reads
+// them (wgrad_any, the dgrad lin16 calls on h.dy16) takes galpha(npl, alpha) = alpha / GRAD_SCALE16, exact in f32.  bf16: 1.
+static inline float grad_scale16(int npl) { return npl == 2 ? GRAD_SCALE16 : 1.0f; }
+static inline float galpha(int npl, float alpha) { return alpha / grad_scale16(npl); }
 // bf16: the weight gradient runs on the TN kernel (kernels_gemm_tn.hip) from row-major operands when the shapes allow, and then
 // neither the gradient nor the saved activation needs a transposed copy (GENIE_WGRAD_TN=0: the transposed-copy path, for A/B)
 static bool use_tn(int npl, int M, int N, int K) {
@@ -234,7 +242,8 @@ static int cast_t_bias(int npl, float* in, int cols, const float* z, TrainWs16& 
     if (use_tn(npl, M, cols, Kw))
         GENIE_TRY(launch_cast_rows16(in, cols, z, h.dy16, M, cols, st, dbias ? w.colpart : nullptr));
     else
-        GENIE_TRY(launch_cast_transpose16(npl, in, cols, z, h.dy16, h.dy16T, M, cols, st, dbias ? w.colpart : nullptr));
+        GENIE_TRY(launch_cast_transpose16(npl, in, cols, z, h.dy16, h.dy16T, M, cols, st, dbias ? w.colpart : nullptr,
+                                          grad_scale16(npl)));
     return dbias ? launch_slab_reduce(w.colpart, M / 64, (size_t)cols, dbias, beta, st) : GENIE_OK;
 }
 static inline int npl_of(const genie_cfg& c) { return c.precision == GENIE_PREC_BF16 ? 1 : 2; }
@@ -269,6 +278,7 @@ static int wgrad16(int npl, const uint16_t* dYT, const uint16_t* XT, float* dW, 
 // weight gradient from the gradient copies in `h` and the saved row-major 16-bit activation X16 (Mtok, K)
 static int wgrad_any(int npl, TrainWs16& h, const uint16_t* X16, float* dW, int Mtok, int N, int K, float alpha, float beta,
                      TrainWs& w, hipStream_t st) {
+    alpha = galpha(npl, alpha);
     if (use_tn(npl, Mtok, N, K)) {
         const int rc = launch_wgrad16_tn(h.dy16, N, X16, K, dW, Mtok, N, K, alpha, beta, w.slabs, w.slab_floats, st);
         GENIE_CHECK_SHAPE(rc != GENIE_E_UNSUPPORTED, "wgrad: TN kernel refused N=%d K=%d after its operand was prepared", N, K);
@@ -379,7 +389,7 @@ static int train_backward_head16(const genie_cfg& c, const genie_weights* wt, co
     float* dl = (float*)(acts + a.logits);
     GENIE_TRY(cast_t_bias(npl, dl, V, nullptr, h, M, (float*)grads->out_b, beta, w, st, d));
     GENIE_TRY(wgrad_any(npl, h, (const uint16_t*)(acts + a.xL16), (float*)grads->out_w, M, V, d, c.readout_mult, beta, w, st));
-    return lin16(npl, h.dy16, (size_t)M * V, wT->out_w16, nullptr, nullptr, w.dx, nullptr, M, d, V, c.readout_mult, st);
+    return lin16(npl, h.dy16, (size_t)M * V, wT->out_w16, nullptr, nullptr, w.dx, nullptr, M, d, V, galpha(npl, c.readout_mult), st);
 }
 
 static int train_backward_layer16(const genie_cfg& c, const genie_weights* wt, const genie_weights* wT,
@@ -401,13 +411,13 @@ static int train_backward_layer16(const genie_cfg& c, const genie_weights* wt, c
     // ---- MLP
     GENIE_TRY(cast_t_bias(npl, dx, d, nullptr, h, M, c.mlp_bias ? (float*)g.fc2_b : nullptr, beta, w, st, hid));
     GENIE_TRY(wgrad_any(npl, h, H16(a.h), (float*)g.fc2_w, M, d, hid, 1.0f, beta, w, st));
-    GENIE_TRY(lin16(npl, h.dy16, pd, lt.fc2_w16, nullptr, nullptr, w.g, nullptr, M, hid, d, 1.0f, st));         // dh
+    GENIE_TRY(lin16(npl, h.dy16, pd, lt.fc2_w16, nullptr, nullptr, w.g, nullptr, M, hid, d, galpha(npl, 1.0f), st));         // dh
     GENIE_TRY(cast_t_bias(npl, w.g, hid, F(a.z), h, M, c.mlp_bias ? (float*)g.fc1_b : nullptr, beta, w, st, d));  // dz
     GENIE_TRY(wgrad_any(npl, h, H16(a.u2), (float*)g.fc1_w, M, hid, d, 1.0f, beta, w, st));
     if (c.qk_norm) {
-        GENIE_TRY(lin16(npl, h.dy16, ph, lt.fc1_w16, nullptr, dx, dx, nullptr, M, d, hid, 1.0f, st));
+        GENIE_TRY(lin16(npl, h.dy16, ph, lt.fc1_w16, nullptr, dx, dx, nullptr, M, d, hid, galpha(npl, 1.0f), st));
     } else {
-        GENIE_TRY(lin16(npl, h.dy16, ph, lt.fc1_w16, nullptr, nullptr, w.d1, nullptr, M, d, hid, 1.0f, st));
+        GENIE_TRY(lin16(npl, h.dy16, ph, lt.fc1_w16, nullptr, nullptr, w.d1, nullptr, M, d, hid, galpha(npl, 1.0f), st));
         GENIE_TRY(launch_ln_bwd(F(a.x2), lw.norm2_w, w.d1, dx, (float*)g.norm2_w, (float*)g.norm2_b, M, d, 1e-5f, beta,
                                 w.lnpart, st));
     }
@@ -415,26 +425,26 @@ static int train_backward_layer16(const genie_cfg& c, const genie_weights* wt, c
     // ---- temporal
     GENIE_TRY(cast_t_bias(npl, dx, d, nullptr, h, M, c.proj_bias ? (float*)g.temporal.proj_b : nullptr, beta, w, st, d));
     GENIE_TRY(wgrad_any(npl, h, H16(a.aot), (float*)g.temporal.proj_w, M, d, d, 1.0f, beta, w, st));
-    GENIE_TRY(lin16(npl, h.dy16, pd, lt.temporal.proj_w16, nullptr, nullptr, w.d1, nullptr, M, d, d, 1.0f, st));
+    GENIE_TRY(lin16(npl, h.dy16, pd, lt.temporal.proj_w16, nullptr, nullptr, w.d1, nullptr, M, d, d, galpha(npl, 1.0f), st));
     GENIE_TRY(qk_source(c, lw.temporal, F(a.qkvt), w, B, &qk, st));
     GENIE_TRY(launch_attn_temporal_bwd(F(a.qkvt), qk.p, qk.ld, w.d1, w.g, B, c.T, c.S, d, c.num_heads, c.head_dim,
                                        c.attn_scale, st));
     GENIE_TRY(qk_norm_backward(c, lw.temporal, g.temporal, F(a.qkvt), w.g, w, B, beta, st));
     GENIE_TRY(cast_t_bias(npl, w.g, 3 * d, nullptr, h, M, c.qkv_bias ? (float*)g.temporal.qkv_b : nullptr, beta, w, st, d));
     GENIE_TRY(wgrad_any(npl, h, H16(a.x1h), (float*)g.temporal.qkv_w, M, 3 * d, d, 1.0f, beta, w, st));
-    GENIE_TRY(lin16(npl, h.dy16, p3, lt.temporal.qkv_w16, nullptr, dx, dx, nullptr, M, d, 3 * d, 1.0f, st));
+    GENIE_TRY(lin16(npl, h.dy16, p3, lt.temporal.qkv_w16, nullptr, dx, dx, nullptr, M, d, 3 * d, galpha(npl, 1.0f), st));
 
     // ---- spatial
     GENIE_TRY(cast_t_bias(npl, dx, d, nullptr, h, M, c.proj_bias ? (float*)g.spatial.proj_b : nullptr, beta, w, st, d));
     GENIE_TRY(wgrad_any(npl, h, H16(a.aos), (float*)g.spatial.proj_w, M, d, d, 1.0f, beta, w, st));
-    GENIE_TRY(lin16(npl, h.dy16, pd, lt.spatial.proj_w16, nullptr, nullptr, w.d1, nullptr, M, d, d, 1.0f, st));
+    GENIE_TRY(lin16(npl, h.dy16, pd, lt.spatial.proj_w16, nullptr, nullptr, w.d1, nullptr, M, d, d, galpha(npl, 1.0f), st));
     GENIE_TRY(qk_source(c, lw.spatial, F(a.qkvs), w, B, &qk, st));
     GENIE_TRY(spatial_attn_bwd(c, F(a.qkvs), qk, w.d1, w.g, w, B, st));
     GENIE_TRY(qk_norm_backward(c, lw.spatial, g.spatial, F(a.qkvs), w.g, w, B, beta, st));
     GENIE_TRY(cast_t_bias(npl, w.g, 3 * d, nullptr, h, M, c.qkv_bias ? (float*)g.spatial.qkv_b : nullptr, beta, w, st, d));
     GENIE_TRY(wgrad_any(npl, h, H16(a.u1), (float*)g.spatial.qkv_w, M, 3 * d, d, 1.0f, beta, w, st));
-    if (c.qk_norm) return lin16(npl, h.dy16, p3, lt.spatial.qkv_w16, nullptr, dx, dx, nullptr, M, d, 3 * d, 1.0f, st);
-    GENIE_TRY(lin16(npl, h.dy16, p3, lt.spatial.qkv_w16, nullptr, nullptr, w.d1, nullptr, M, d, 3 * d, 1.0f, st));
+    if (c.qk_norm) return lin16(npl, h.dy16, p3, lt.spatial.qkv_w16, nullptr, dx, dx, nullptr, M, d, 3 * d, galpha(npl, 1.0f), st);
+    GENIE_TRY(lin16(npl, h.dy16, p3, lt.spatial.qkv_w16, nullptr, nullptr, w.d1, nullptr, M, d, 3 * d, galpha(npl, 1.0f), st));
     return launch_ln_bwd(F(a.x0), lw.norm1_w, w.d1, dx, (float*)g.norm1_w, (float*)g.norm1_b, M, d, 1e-5f, beta, w.lnpart, st);
 }
 
@@ -488,9 +498,11 @@ int genie_train_forward(const genie_cfg* cfg, const genie_weights* wt, const int
 int genie_train_forward_cond(const genie_cfg* cfg, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels,
                              int B, float* acts, size_t acts_bytes, double* sums, void* stream,
                              const genie_frame_cond* cond) {
-    GENIE_TRY(train_check(cfg, B));
-    GENIE_CHECK_ARG(wt && input_ids && labels && acts && sums, "genie_train_forward: NULL argument");
+    // argument errors (GENIE_E_ARG) are reported before geometry errors (GENIE_E_SHAPE), as they were before train_check
+    // learnt to refuse a geometry that check_cfg admits
+    GENIE_CHECK_ARG(cfg && wt && input_ids && labels && acts && sums, "genie_train_forward: NULL argument");
     GENIE_TRY(check_frame_cond(cond, "genie_train_forward"));
+    GENIE_TRY(train_check(cfg, B));
     const genie_cfg& c = *cfg;
     EmbedAct ea;
     const EmbedAct* act = frame_act(cond, c.S, 0, c.T, ea);
@@ -642,11 +654,11 @@ int genie_train_backward_embed(const genie_cfg* cfg, const genie_weights* grads,
 int genie_train_backward_embed_cond(const genie_cfg* cfg, const genie_weights* grads, const int64_t* input_ids, int B,
                                     void* workspace, size_t workspace_bytes, int accumulate, void* stream,
                                     float* d_table, const genie_frame_cond* cond) {
-    GENIE_TRY(train_check(cfg, B));
-    GENIE_CHECK_ARG(grads && input_ids && workspace, "genie_train_backward_embed: NULL argument");
+    GENIE_CHECK_ARG(cfg && grads && input_ids && workspace, "genie_train_backward_embed: NULL argument");
     GENIE_TRY(check_frame_cond(cond, "genie_train_backward_embed"));
     const bool act = cond && cond->n_actions > 0;
     GENIE_CHECK_ARG(!act || d_table, "genie_train_backward_embed: actions without d_table");
+    GENIE_TRY(train_check(cfg, B));
     TrainWs w = train_ws(*cfg, B, workspace);
     GENIE_CHECK_ARG(workspace_bytes >= w.total, "training workspace too small: %zu < %zu", workspace_bytes, w.total);
     float* tables[4] = {nullptr, nullptr, nullptr, nullptr};

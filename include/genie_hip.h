@@ -673,7 +673,13 @@ int genie_rescale_u8_nhwc_bf16(const uint16_t* x, uint8_t* out, int n, int HW, i
  * again after every optimizer step); parameters, gradients and optimizer state are always f32.  Gradients travel in a second genie_weights table whose pointers address the caller's
  * gradient buffers (same shapes as the parameters; the *_w16 members are ignored).  `accumulate` = 0 overwrites the
  * gradients (optimizer.zero_grad() + backward), 1 adds to them (gradient accumulation, train.py:607-617).
- * Every reduction feeding a gradient has a fixed order: results are bit-reproducible run to run. */
+ * GENIE_PREC_F16X3 splits the gradient operands of those products as 2^12 times their value (undone in the accumulator's scale), so
+ * that gradients far below the f16 normal range keep all 22 bits; a gradient element of magnitude 16 or more saturates there.
+ * Every reduction feeding a gradient has a fixed order: results are bit-reproducible run to run.
+ * Geometry the step admits (checked by every entry point before anything is enqueued, GENIE_E_SHAPE otherwise): head_dim 32
+ * or 64 (head_dim 16 is inference only: the temporal attention backward and the qk-norm backward have no such kernel), T <= 16,
+ * S, d_model and hidden multiples of 16; the 16-bit precisions also need d_model, hidden, T * S and the vocabulary rows to be
+ * multiples of 64. */
 
 /* Bytes of the saved-activation buffer / of the backward scratch for B clips. */
 size_t genie_train_activation_bytes(const genie_cfg* cfg, int B);

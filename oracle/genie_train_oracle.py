@@ -442,7 +442,11 @@ class TrainNumerics:
 
 # bf16 training (GENIE_PREC_BF16): every point above
 BF16_TRAIN = TrainNumerics("BF16_TRAIN", go.round_bf16, TrainNumerics.POINTS, attn_bwd16=True)
-# split-f16 training (GENIE_PREC_F16X3): the Linear operands as hi + lo/2048 pairs, the erf-form GELU, f32 attention backward
+# split-f16 training (GENIE_PREC_F16X3): the Linear operands as hi + lo/2048 pairs, the erf-form GELU, f32 attention backward.
+# What this model does NOT restate, in either direction: the GEMM's three products (hi.hi + hi.lo + lo.hi, no lo.lo: the model
+# multiplies the rounded operands exactly), and the 2^12 scaling of the gradient operands (dlogits, dy, dz) in front of their
+# split (csrc/kernels.hpp GRAD_SCALE16: without it a gradient below 2^-14 lost its hi half and with it the lo half of whatever it
+# was multiplied with).  With the scaling the step sits ~1e-6 from the float64 oracle, closer than this model (1e-5 .. 7e-5).
 F16X3_TRAIN = TrainNumerics("F16X3_TRAIN", go.round_f16_split,
                             ("act", "attn_out", "hidden", "weight", "dlogits", "dy", "dz"))
 

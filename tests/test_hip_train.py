@@ -181,10 +181,10 @@ def test_gradients_vs_oracle_f16x3(H, d, B, qk_norm, T, use_mup):
     """The same cases in f16x3 at the same bar as exact ("f32-class gradients"): at d >= 128 the
     split-f16 copies go through the multi-tile cast_transpose / token-slab wgrad path that the d = 64 fixtures never reach.
 
-    Measured on an MI355X: 1.6e-6 .. 4.0e-5, except the two tight cases, H8 d512 muP 7.0e-5 and H4 d256 B2 5.3e-5 (the
-    margins under GRAD_TOL are 1.4x and 1.9x).  There the split-f16 contract itself accounts for much of it:
-    oracle.F16X3_TRAIN is 3.5e-5 and 1.8e-5 from the f32 oracle.  f16x3 has no bf16 rounding to flip, so its distance does
-    not drift chaotically with accumulation order the way bf16's does (test_hip_train_bf16.py)."""
+    Measured on an MI355X: 6.2e-7 .. 1.4e-6, the f32 oracle's own noise.  Before the gradient operands were scaled ahead of
+    their split (csrc/kernels.hpp GRAD_SCALE16; found by tests/test_hip_train_geometry.py) these read 1.6e-6 .. 4.0e-5, with H8
+    d512 muP at 7.0e-5 and H4 d256 B2 at 5.3e-5.  f16x3 has no bf16 rounding to flip, so its distance does not drift
+    chaotically with accumulation order the way bf16's does (test_hip_train_bf16.py)."""
     gradients_vs_oracle(H, d, B, qk_norm, T, use_mup, "f16x3")
 
 
