@@ -1,42 +1,55 @@
 // C ABI of the training step (include/genie_hip.h, "training" section): forward with saved activations, masked
 // factored CE, backward layer by layer (so the caller can overlap the gradient all-reduce of finished layers with
-// the backward of earlier ones), AdamW.  Two variants: GENIE_PREC_EXACT (this first part: f32 storage, every contraction on
-// the f32 matrix instruction) and the 16-bit matrix-core variant for GENIE_PREC_BF16 / _F16X3 further down.
+// the backward of earlier ones), AdamW.
 //
-// HBM layout of the saved activations, exact variant (floats; M = B*T*S tokens, token-major rows):
-//   per layer l at l*per_layer:  x0 (M,d) layer input | u1 (M,d) norm1(x0) | qkv_s (M,3d) | ao_s (M,d) spatial attention
-//   output before proj | x1 (M,d) | qkv_t (M,3d) | ao_t (M,d) | x2 (M,d) | u2 (M,d) norm2(x2) | z (M,hid) fc1 pre-activation
-//   | h (M,hid) gelu(z);  after the layers: xL (M,d) | logits (M,V) (replaced in place by d loss / d logits)
-// 21*d floats per token and layer: 5.6 GB per clip for the C138 shape -- sized for 288 GB, nothing is recomputed
-// except the attention probabilities (rebuilt inside the fused attention backward kernels; for S != 256 the spatial scores are
-// materialised per layer in the workspace, never saved).
+// The STBlock is stated once for the forward (train_forward) and once for the backward (train_backward_layer), as templates over
+// a backend that says how a Linear product runs and in which form its operands are saved:
+//   ExactOps (GENIE_PREC_EXACT): f32 storage, every contraction on the f32 matrix instruction (launch_gemm_f32_gen);
+//   Ops16 (GENIE_PREC_BF16 / _F16X3): every Linear product -- forward, dgrad, wgrad -- on the NT 16-bit GEMM of kernels_bf16.hip
+//     (bf16 weight gradients on the TN kernel where the shapes allow) from 16-bit operand copies: bf16, or two f16 planes [hi | lo].
+// LayerNorm, softmax, both attention cores (forward and backward; bf16: the spatial backward's products on the bf16 matrix cores,
+// kernels_attn_bwd16.hip), GELU, the residual stream, CE and all gradient reductions are f32 in both.
+//
+// HBM layout of the saved activations (train_acts; M = B*T*S tokens, token-major rows).  Per layer l at l*per_layer, f32 unless
+// marked [op] = saved in operand form (exact: f32; 16-bit: NPL planes of 16 bits, and every slot rounded up to 256 bytes):
+//   x0 (M,d) layer input | u1 [op] (M,d) norm1(x0) | qkv_s (M,3d) | ao_s [op] (M,d) spatial attention output before proj | x1 (M,d)
+//   | x1h [op] (M,d) x1 again (16-bit only; exact reads x1) | qkv_t (M,3d) | ao_t [op] (M,d) | x2 (M,d) | u2 [op] (M,d) norm2(x2)
+//   | z (M,hid) fc1 pre-activation | h [op] (M,hid) gelu(z);
+// after the layers: xL (M,d) | xL16 [op] (M,d) (16-bit only) | logits (M,V) (replaced in place by d loss / d logits).
+// qk_norm: norm1 / norm2 are Identity, so u1 / u2 are x0 / x2 in operand form (exact: the f32 slots themselves, the u1 / u2 slots
+// stay unused).  Exact: 21*d floats per token and layer, 5.6 GB per clip for the C138 shape; 16-bit: 52 d + 18 d NPL bytes -- sized
+// for 288 GB, nothing is recomputed except the attention probabilities (rebuilt inside the fused attention backward kernels; for
+// S != 256 the spatial scores are materialised per layer in the workspace, never saved).
 #include "kernels.hpp"
 
 namespace genie {
 
-struct TrainActs {
-    size_t per_layer, o_x0, o_u1, o_qkvs, o_aos, o_x1, o_qkvt, o_aot, o_x2, o_u2, o_z, o_h, o_xL, o_logits, total;
+constexpr float LN_EPS = 1e-5f;
+static inline int npl_of(const genie_cfg& c) { return c.precision == GENIE_PREC_BF16 ? 1 : 2; }
+static inline long PL(int npl, size_t n) { return npl == 2 ? (long)n : 0; }
+
+struct TrainActs {                               // byte offsets
+    size_t per_layer;
+    size_t x0, qkvs, x1, qkvt, x2, z;            // inside a layer, f32
+    size_t u1, aos, x1h, aot, u2, h;             // inside a layer, the operand the next Linear reads
+    size_t xL, xL16, logits, total;              // in the buffer (xL16: operand)
 };
 static TrainActs train_acts(const genie_cfg& c, int B) {
+    const bool exact = c.precision == GENIE_PREC_EXACT;
     const size_t M = (size_t)B * c.T * c.S, d = c.d_model, hid = c.hidden;
     const size_t V = (size_t)c.factored_vocab * c.num_factored;
+    const size_t op = exact ? 4 : 2 * npl_of(c), align = exact ? 1 : 256;   // bytes of an operand element; slot alignment
     TrainActs a;
     size_t o = 0;
-    a.o_x0 = o; o += M * d;
-    a.o_u1 = o; o += M * d;
-    a.o_qkvs = o; o += M * 3 * d;
-    a.o_aos = o; o += M * d;
-    a.o_x1 = o; o += M * d;
-    a.o_qkvt = o; o += M * 3 * d;
-    a.o_aot = o; o += M * d;
-    a.o_x2 = o; o += M * d;
-    a.o_u2 = o; o += M * d;
-    a.o_z = o; o += M * hid;
-    a.o_h = o; o += M * hid;
+    auto take = [&](size_t bytes) { size_t at = o; o += (bytes + align - 1) / align * align; return at; };
+    a.x0 = take(M * d * 4); a.u1 = take(M * d * op); a.qkvs = take(M * 3 * d * 4); a.aos = take(M * d * op);
+    a.x1 = take(M * d * 4); a.x1h = exact ? a.x1 : take(M * d * op); a.qkvt = take(M * 3 * d * 4); a.aot = take(M * d * op);
+    a.x2 = take(M * d * 4); a.u2 = take(M * d * op); a.z = take(M * hid * 4); a.h = take(M * hid * op);
     a.per_layer = o;
-    a.o_xL = a.per_layer * c.num_layers;
-    a.o_logits = a.o_xL + M * d;
-    a.total = a.o_logits + M * V;
+    if (exact && c.qk_norm) { a.u1 = a.x0; a.u2 = a.x2; }   // Identity norms: the f32 residual stream is the operand
+    o = a.per_layer * c.num_layers;
+    a.xL = take(M * d * 4); a.xL16 = exact ? a.xL : take(M * d * op); a.logits = take(M * V * 4);
+    a.total = o;
     return a;
 }
 
@@ -89,39 +102,66 @@ static int train_check(const genie_cfg* c, int B) {
     return GENIE_OK;
 }
 
-// y = x . W^T + b (+ R) on the general GEMM
-static int lin(const float* x, long ldx, const float* W, const float* b, const float* R, float* y, long ldy, int M, int N,
-               int K, float alpha, hipStream_t st) {
-    return launch_gemm_f32_gen(false, false, x, ldx, 0, 0, W, K, 0, 0, b, R, y, ldy, 0, 0, M, N, K, 1, 1, 1, 0, alpha, st);
+// one Linear y = x . W^T + b, W (N,K): the weight in every form a backend reads (wT16: the transposed 16-bit copy the 16-bit dgrad
+// multiplies with), its bias (NULL: none) and, in the backward, where its gradients go
+struct Lin {
+    const float* w; const uint16_t *w16, *wT16; const float* b;
+    float *dw, *db;
+    int N, K;
+};
+struct LayerLins { Lin qkv_s, proj_s, qkv_t, proj_t, fc1, fc2; };
+// w: the layer's weights; t: their transposed 16-bit copies (NULL: forward, exact); g: its gradients (NULL: forward)
+static LayerLins layer_lins(const genie_cfg& c, const genie_layer_weights& w, const genie_layer_weights* t,
+                            const genie_layer_weights* g) {
+    static const genie_layer_weights none{};
+    const genie_layer_weights &T = t ? *t : none, &G = g ? *g : none;
+    const int d = c.d_model, hid = c.hidden;
+    auto lin = [](const float* W, const uint16_t* W16, const uint16_t* WT16, bool bias, const float* b, const float* dW,
+                  const float* db, int N, int K) {
+        return Lin{W, W16, WT16, bias ? b : nullptr, (float*)dW, bias ? (float*)db : nullptr, N, K};
+    };
+    auto qkv = [&](const genie_attn_weights& a, const genie_attn_weights& at, const genie_attn_weights& ag) {
+        return lin(a.qkv_w, a.qkv_w16, at.qkv_w16, c.qkv_bias, a.qkv_b, ag.qkv_w, ag.qkv_b, 3 * d, d);
+    };
+    auto proj = [&](const genie_attn_weights& a, const genie_attn_weights& at, const genie_attn_weights& ag) {
+        return lin(a.proj_w, a.proj_w16, at.proj_w16, c.proj_bias, a.proj_b, ag.proj_w, ag.proj_b, d, d);
+    };
+    return LayerLins{qkv(w.spatial, T.spatial, G.spatial), proj(w.spatial, T.spatial, G.spatial),
+                     qkv(w.temporal, T.temporal, G.temporal), proj(w.temporal, T.temporal, G.temporal),
+                     lin(w.fc1_w, w.fc1_w16, T.fc1_w16, c.mlp_bias, w.fc1_b, G.fc1_w, G.fc1_b, hid, d),
+                     lin(w.fc2_w, w.fc2_w16, T.fc2_w16, c.mlp_bias, w.fc2_b, G.fc2_w, G.fc2_b, d, hid)};
 }
-// dx = alpha * dy . W (+ R), W (N,K) row-major read k-major
-static int dgrad(const float* dy, const float* W, const float* R, float* dx, int M, int N, int K, float alpha,
-                 hipStream_t st) {
-    return launch_gemm_f32_gen(false, true, dy, N, 0, 0, W, K, 0, 0, nullptr, R, dx, K, 0, 0, M, K, N, 1, 1, 1, 0, alpha,
-                               st);
+static Lin readout_lin(const genie_cfg& c, const genie_weights* w, const genie_weights* t, const genie_weights* g) {
+    return Lin{w->out_w, w->out_w16, t ? t->out_w16 : nullptr, w->out_b, g ? (float*)g->out_w : nullptr,
+               g ? (float*)g->out_b : nullptr, c.factored_vocab * c.num_factored, c.d_model};
 }
 
-static int spatial_attn_fwd(const genie_cfg& c, const genie_attn_weights& aw, const float* qkv, float* ao, int B,
-                            hipStream_t st) {
+// attention over saved qkv rows into the operand of the projection: f32 rows in `out`, or (out16) 16-bit planes, for which the
+// generic kernel goes through the f32 scratch `out`
+static int attn_fwd(const genie_cfg& c, const genie_attn_weights& aw, const float* qkv, bool temporal, float* out,
+                    uint16_t* out16, int npl, int B, hipStream_t st) {
     const float* nw = c.qk_norm ? aw.norm_w : nullptr;
     const float* nb = c.qk_norm ? aw.norm_b : nullptr;
-    int rc = launch_attn_spatial_f32_mfma(qkv, ao, c.S, (long)B * c.T, c.d_model, c.num_heads, c.head_dim, c.attn_scale,
-                                          nw, nb, st);
-    if (rc == GENIE_E_UNSUPPORTED)
-        rc = launch_attn_generic(qkv, ao, c.S, (long)B * c.T, 1, c.S, 0, 1, c.d_model, c.num_heads, c.head_dim,
-                                 c.attn_scale, 0, nw, nb, st);
-    return rc;
-}
-static int temporal_attn_fwd(const genie_cfg& c, const genie_attn_weights& aw, const float* qkv, float* ao, int B,
-                             hipStream_t st) {
-    const float* nw = c.qk_norm ? aw.norm_w : nullptr;
-    const float* nb = c.qk_norm ? aw.norm_b : nullptr;
-    int rc = launch_attn_temporal_f32_mfma(qkv, ao, B, c.T, c.S, c.d_model, c.num_heads, c.head_dim, c.attn_scale, nw, nb,
-                                           st);
-    if (rc == GENIE_E_UNSUPPORTED)
-        rc = launch_attn_generic(qkv, ao, c.T, (long)B * c.S, c.S, (long)c.T * c.S, 1, c.S, c.d_model, c.num_heads,
-                                 c.head_dim, c.attn_scale, 1, nw, nb, st);
-    return rc;
+    const size_t pd = (size_t)B * c.T * c.S * c.d_model, plane = out16 ? PL(npl, pd) : 0;
+    float* direct = out16 ? nullptr : out;
+    int rc;
+    if (temporal)
+        rc = launch_attn_temporal_f32_mfma(qkv, direct, B, c.T, c.S, c.d_model, c.num_heads, c.head_dim, c.attn_scale, nw, nb,
+                                           st, out16, plane);
+    else if (out16)
+        rc = launch_attn_spatial_split(qkv, nullptr, c.S, (long)B * c.T, c.d_model, c.num_heads, c.head_dim, c.attn_scale, nw,
+                                       nb, st, out16, plane);
+    else
+        rc = launch_attn_spatial_f32_mfma(qkv, out, c.S, (long)B * c.T, c.d_model, c.num_heads, c.head_dim, c.attn_scale, nw,
+                                          nb, st);
+    if (rc != GENIE_E_UNSUPPORTED) return rc;
+    if (temporal)
+        GENIE_TRY(launch_attn_generic(qkv, out, c.T, (long)B * c.S, c.S, (long)c.T * c.S, 1, c.S, c.d_model, c.num_heads,
+                                      c.head_dim, c.attn_scale, 1, nw, nb, st));
+    else
+        GENIE_TRY(launch_attn_generic(qkv, out, c.S, (long)B * c.T, 1, c.S, 0, 1, c.d_model, c.num_heads, c.head_dim,
+                                      c.attn_scale, 0, nw, nb, st));
+    return out16 ? launch_cast16(npl, out, out16, pd, st) : GENIE_OK;
 }
 // where the backward reads q and k: the saved qkv itself, or (qk_norm) their LayerNorm'd copies in w.qkn
 struct QkSrc { const float* p; long ld; };
@@ -175,42 +215,11 @@ static int spatial_attn_bwd(const genie_cfg& c, const float* qkv, QkSrc qk, cons
     return GENIE_OK;
 }
 
-
-// ================================================================================================
-// 16-bit matrix-core variant (GENIE_PREC_BF16 / GENIE_PREC_F16X3): every Linear product -- forward, dgrad, wgrad --
-// runs on the NT 16-bit GEMM of kernels_bf16.hip; LayerNorm, softmax, both attention cores (forward and backward; bf16:
-// the spatial backward's products on the bf16 matrix cores, kernels_attn_bwd16.hip),
-// GELU, the residual stream, CE and all gradient reductions stay f32 exactly as in the exact variant.
-// Saved per layer (bytes/token: 52 d f32 + 18 d NPL 16-bit): f32 x0, qkv_s, x1, qkv_t, x2, z;  16-bit GEMM operands
-// u1 = norm1(x0), ao_s, x1, ao_t, u2 = norm2(x2), h = gelu(z).
-// ================================================================================================
-struct TrainActs16 {
-    size_t per_layer;                            // bytes
-    size_t x0, qkvs, x1, qkvt, x2, z;            // byte offsets inside a layer (f32)
-    size_t u1, aos, x1h, aot, u2, h;             // byte offsets inside a layer (16-bit, NPL planes)
-    size_t xL, xL16, logits, total;              // byte offsets in the buffer
-};
-static TrainActs16 train_acts16(const genie_cfg& c, int B, int npl) {
-    const size_t M = (size_t)B * c.T * c.S, d = c.d_model, hid = c.hidden;
-    const size_t V = (size_t)c.factored_vocab * c.num_factored;
-    TrainActs16 a;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
-    a.x0 = take(M * d * 4); a.qkvs = take(M * 3 * d * 4); a.x1 = take(M * d * 4); a.qkvt = take(M * 3 * d * 4);
-    a.x2 = take(M * d * 4); a.z = take(M * hid * 4);
-    a.u1 = take(M * d * 2 * npl); a.aos = take(M * d * 2 * npl); a.x1h = take(M * d * 2 * npl);
-    a.aot = take(M * d * 2 * npl); a.u2 = take(M * d * 2 * npl); a.h = take(M * hid * 2 * npl);
-    a.per_layer = o;
-    o = a.per_layer * c.num_layers;
-    a.xL = take(M * d * 4); a.xL16 = take(M * d * 2 * npl); a.logits = take(M * V * 4);
-    a.total = o;
-    return a;
-}
 struct TrainWs16 {
     uint16_t *dy16, *dy16T, *xT16;
     size_t total;
 };
-// appended behind the exact workspace
+// the 16-bit backend's gradient copies, appended behind the exact workspace
 static TrainWs16 train_ws16(const genie_cfg& c, int B, int npl, void* base, size_t exact_total) {
     const size_t M = (size_t)B * c.T * c.S, d = c.d_model;
     const size_t V = (size_t)c.factored_vocab * c.num_factored;
@@ -225,39 +234,20 @@ static TrainWs16 train_ws16(const genie_cfg& c, int B, int npl, void* base, size
     w.dy16 = (uint16_t*)(b + o1); w.dy16T = (uint16_t*)(b + o2); w.xT16 = (uint16_t*)(b + o3);
     return w;
 }
-// f16x3: the gradient copies made by cast_t_bias hold GRAD_SCALE16 times the gradient (kernels.hpp); every product that reads
-// them (wgrad_any, the dgrad lin16 calls on h.dy16) takes galpha(npl, alpha) = alpha / GRAD_SCALE16, exact in f32.  bf16: 1.
-static inline float grad_scale16(int npl) { return npl == 2 ? GRAD_SCALE16 : 1.0f; }
-static inline float galpha(int npl, float alpha) { return alpha / grad_scale16(npl); }
 // bf16: the weight gradient runs on the TN kernel (kernels_gemm_tn.hip) from row-major operands when the shapes allow, and then
 // neither the gradient nor the saved activation needs a transposed copy (GENIE_WGRAD_TN=0: the transposed-copy path, for A/B)
 static bool use_tn(int npl, int M, int N, int K) {
     static const int tn = study_env("GENIE_WGRAD_TN", 1);
     return tn && npl == 1 && M % 64 == 0 && N % 256 == 0 && K % 128 == 0;
 }
-// 16-bit copies of a gradient matrix (row-major, and transposed unless its weight gradient takes the TN kernel: Kw = the K of
-// that weight gradient) and, in the same pass, its column sums (= the bias gradient)
-static int cast_t_bias(int npl, float* in, int cols, const float* z, TrainWs16& h, int M, float* dbias, float beta,
-                       TrainWs& w, hipStream_t st, int Kw) {
-    if (use_tn(npl, M, cols, Kw))
-        GENIE_TRY(launch_cast_rows16(in, cols, z, h.dy16, M, cols, st, dbias ? w.colpart : nullptr));
-    else
-        GENIE_TRY(launch_cast_transpose16(npl, in, cols, z, h.dy16, h.dy16T, M, cols, st, dbias ? w.colpart : nullptr,
-                                          grad_scale16(npl)));
-    return dbias ? launch_slab_reduce(w.colpart, M / 64, (size_t)cols, dbias, beta, st) : GENIE_OK;
-}
-static inline int npl_of(const genie_cfg& c) { return c.precision == GENIE_PREC_BF16 ? 1 : 2; }
-static inline long PL(int npl, size_t n) { return npl == 2 ? (long)n : 0; }
-
-// y(f32) / y16 = x16 . W16^T (+b) (+R)
-static int lin16(int npl, const uint16_t* x16, size_t nx, const uint16_t* W16, const float* b, const float* R, float* y,
-                 uint16_t* y16, int M, int N, int K, float alpha, hipStream_t st) {
-    int flags = 0;
+// y(f32) / y16 = alpha * x16 . W16^T (+b) (+R), x16 (M,K), W16 (N,K)
+static int lin16(int npl, const uint16_t* x16, const uint16_t* W16, const float* b, const float* R, float* y, uint16_t* y16,
+                 int M, int N, int K, float alpha, hipStream_t st, int flags = 0) {
     if (y) flags |= G16X_OUTF32;
     if (y16) flags |= G16X_OUT16;
     if (R) flags |= G16X_ACCUM;
-    return launch_gemm16_ex(npl, x16, K, PL(npl, nx), W16, K, PL(npl, (size_t)N * K), b, (R && R != y) ? R : nullptr, y, y16,
-                            PL(npl, (size_t)M * N), N, M, N, K, flags, alpha, st, 1, 0, 0, 0);
+    return launch_gemm16_ex(npl, x16, K, PL(npl, (size_t)M * K), W16, K, PL(npl, (size_t)N * K), b, (R && R != y) ? R : nullptr,
+                            y, y16, PL(npl, (size_t)M * N), N, M, N, K, flags, alpha, st, 1, 0, 0, 0);
 }
 // dW[N,K] (beta*dW +)= alpha * dY^T . X from the TRANSPOSED 16-bit copies dYT (N, Mtok), XT (K, Mtok)
 static int wgrad16(int npl, const uint16_t* dYT, const uint16_t* XT, float* dW, int Mtok, int N, int K, float alpha,
@@ -275,46 +265,8 @@ static int wgrad16(int npl, const uint16_t* dYT, const uint16_t* XT, float* dW, 
     return launch_slab_reduce(slabs, ns, (size_t)N * K, dW, beta, st);
 }
 
-// weight gradient from the gradient copies in `h` and the saved row-major 16-bit activation X16 (Mtok, K)
-static int wgrad_any(int npl, TrainWs16& h, const uint16_t* X16, float* dW, int Mtok, int N, int K, float alpha, float beta,
-                     TrainWs& w, hipStream_t st) {
-    alpha = galpha(npl, alpha);
-    if (use_tn(npl, Mtok, N, K)) {
-        const int rc = launch_wgrad16_tn(h.dy16, N, X16, K, dW, Mtok, N, K, alpha, beta, w.slabs, w.slab_floats, st);
-        GENIE_CHECK_SHAPE(rc != GENIE_E_UNSUPPORTED, "wgrad: TN kernel refused N=%d K=%d after its operand was prepared", N, K);
-        return rc;
-    }
-    GENIE_TRY(launch_transpose16(npl, X16, h.xT16, Mtok, K, st));
-    return wgrad16(npl, h.dy16T, h.xT16, dW, Mtok, N, K, alpha, beta, w.slabs, w.slab_floats, st);
-}
-
-static int attn_fwd16(const genie_cfg& c, const genie_attn_weights& aw, const float* qkv, bool temporal, uint16_t* out16,
-                      float* tmp, int B, int npl, hipStream_t st) {
-    const float* nw = c.qk_norm ? aw.norm_w : nullptr;
-    const float* nb = c.qk_norm ? aw.norm_b : nullptr;
-    const size_t pd = (size_t)B * c.T * c.S * c.d_model;
-    int rc;
-    if (!temporal) {
-        rc = launch_attn_spatial_split(qkv, nullptr, c.S, (long)B * c.T, c.d_model, c.num_heads, c.head_dim, c.attn_scale,
-                                       nw, nb, st, out16, PL(npl, pd));
-        if (rc == GENIE_E_UNSUPPORTED) {
-            GENIE_TRY(launch_attn_generic(qkv, tmp, c.S, (long)B * c.T, 1, c.S, 0, 1, c.d_model, c.num_heads, c.head_dim,
-                                          c.attn_scale, 0, nw, nb, st));
-            rc = launch_cast16(npl, tmp, out16, pd, st);
-        }
-    } else {
-        rc = launch_attn_temporal_f32_mfma(qkv, nullptr, B, c.T, c.S, c.d_model, c.num_heads, c.head_dim, c.attn_scale, nw,
-                                           nb, st, out16, PL(npl, pd));
-        if (rc == GENIE_E_UNSUPPORTED) {
-            GENIE_TRY(launch_attn_generic(qkv, tmp, c.T, (long)B * c.S, c.S, (long)c.T * c.S, 1, c.S, c.d_model,
-                                          c.num_heads, c.head_dim, c.attn_scale, 1, nw, nb, st));
-            rc = launch_cast16(npl, tmp, out16, pd, st);
-        }
-    }
-    return rc;
-}
-
 static int need16(const genie_weights* wt, const genie_cfg& c, const char* what) {
+    if (c.precision == GENIE_PREC_EXACT) return GENIE_OK;
     GENIE_CHECK_ARG(wt && wt->out_w16, "%s: 16-bit weight copies missing (genie_train_pack_weights)", what);
     for (int l = 0; l < c.num_layers; ++l) {
         const genie_layer_weights& lw = wt->layers_host[l];
@@ -325,127 +277,197 @@ static int need16(const genie_weights* wt, const genie_cfg& c, const char* what)
     return GENIE_OK;
 }
 
-static int train_forward16(const genie_cfg& c, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels,
-                           int B, char* acts, size_t acts_bytes, double* sums, hipStream_t st, const EmbedAct* act) {
-    const int npl = npl_of(c);
-    GENIE_TRY(need16(wt, c, "genie_train_forward"));
-    const TrainActs16 a = train_acts16(c, B, npl);
-    GENIE_CHECK_ARG(acts_bytes >= a.total, "genie_train_forward: activation buffer too small: %zu < %zu", acts_bytes, a.total);
-    const int d = c.d_model, hid = c.hidden, M = B * c.T * c.S, V = c.factored_vocab * c.num_factored;
-    GENIE_CHECK_SHAPE(V >= d, "training step (16-bit): vocabulary rows %d < d_model %d", V, d);
-    const size_t pd = (size_t)M * d, ph = (size_t)M * hid;
-    float* tmp = (float*)(acts + a.logits);  // free until the readout
+// ================================================================================================
+// The two backends.  Same members: Operand (the element type of a saved Linear input), cast / norm / attention (produce an
+// operand), linear, linear_backward.  M tokens; beta 1 accumulates into the gradients; w is unused by the forward.
+// ================================================================================================
+struct ExactOps {
+    using Operand = float;
+    const genie_cfg& c;
+    int B, M;
+    hipStream_t st;
+    TrainWs w;
+    float beta;
+
+    int cast(const float*, Operand*, size_t) { return GENIE_OK; }   // train_acts: the f32 rows are the operand
+    int norm(const float* x, const float* g, const float* b, Operand* u) {
+        return launch_layer_norm(x, g, b, u, M, c.d_model, LN_EPS, st);
+    }
+    int attention(bool temporal, const genie_attn_weights& aw, const float* qkv, Operand* ao) {
+        return attn_fwd(c, aw, qkv, temporal, ao, nullptr, 0, B, st);
+    }
+    // y = alpha * x . W^T + b (+ R); gelu: also gelu(y) as the next operand.  y_op (y again, in operand form) is y itself here.
+    int linear(const Operand* x, const Lin& l, const float* R, float* y, Operand* /*y_op*/, Operand* gelu, float alpha = 1.0f) {
+        GENIE_TRY(launch_gemm_f32_gen(false, false, x, l.K, 0, 0, l.w, l.K, 0, 0, l.b, R, y, l.N, 0, 0, M, l.N, l.K, 1, 1, 1, 0,
+                                      alpha, st));
+        return gelu ? launch_gelu_fwd(y, gelu, (size_t)M * l.N, st) : GENIE_OK;
+    }
+    // from dy (M,N) (z: d gelu(z), turned into dz in place first) and the saved input x (M,K): l.dw, l.db and
+    // dx = alpha * dy . W (+ R), W (N,K) read k-major
+    int linear_backward(float* dy, const Operand* x, const Lin& l, const float* z, const float* R, float* dx, float alpha = 1.0f) {
+        if (z) GENIE_TRY(launch_gelu_bwd(z, dy, (size_t)M * l.N, st));
+        GENIE_TRY(launch_wgrad_f32(dy, l.N, x, l.K, l.dw, M, l.N, l.K, alpha, beta, w.slabs, w.slab_floats, st));
+        if (l.db) GENIE_TRY(launch_colsum(dy, l.N, M, l.N, l.db, beta, w.colpart, st));
+        return launch_gemm_f32_gen(false, true, dy, l.N, 0, 0, l.w, l.K, 0, 0, nullptr, R, dx, l.K, 0, 0, M, l.K, l.N, 1, 1, 1, 0,
+                                   alpha, st);
+    }
+};
+
+struct Ops16 {
+    using Operand = uint16_t;
+    const genie_cfg& c;
+    int B, M;
+    hipStream_t st;
+    TrainWs w;
+    float beta;
+    int npl;
+    TrainWs16 h;   // backward only
+    float* tmp;    // forward only: (M,d) f32 behind the generic attention kernels (the logits region, free until the readout)
+
+    int cast(const float* x, Operand* u, size_t n) { return launch_cast16(npl, x, u, n, st); }
+    int norm(const float* x, const float* g, const float* b, Operand* u) {
+        if (npl == 1) return launch_layer_norm_bf16(x, g, b, u, M, c.d_model, LN_EPS, st);
+        return launch_layer_norm_split(x, g, b, u, (size_t)M * c.d_model, M, c.d_model, LN_EPS, st);
+    }
+    int attention(bool temporal, const genie_attn_weights& aw, const float* qkv, Operand* ao) {
+        return attn_fwd(c, aw, qkv, temporal, tmp, ao, npl, B, st);
+    }
+    // one GEMM: the epilogue writes y, y_op (y in operand form) or gelu (gelu(y) in operand form: the f32 pre-activation is kept for gelu')
+    int linear(const Operand* x, const Lin& l, const float* R, float* y, Operand* y_op, Operand* gelu, float alpha = 1.0f) {
+        return lin16(npl, x, l.w16, l.b, R, y, gelu ? gelu : y_op, M, l.N, l.K, alpha, st, gelu ? G16X_GELU16 : 0);
+    }
+
+    // f16x3: the gradient copies made by cast_t_bias hold GRAD_SCALE16 times the gradient (kernels.hpp); the two products of
+    // linear_backward that read them take alpha / grad_scale16(), exact in f32.  bf16: 1.
+    float grad_scale16() const { return npl == 2 ? GRAD_SCALE16 : 1.0f; }
+    // 16-bit copies of a gradient matrix (row-major, and transposed unless its weight gradient takes the TN kernel: Kw = the K of
+    // that weight gradient), with gelu'(z) applied when z, and, in the same pass, its column sums (= the bias gradient)
+    int cast_t_bias(float* in, int cols, const float* z, float* dbias, int Kw) {
+        if (use_tn(npl, M, cols, Kw))
+            GENIE_TRY(launch_cast_rows16(in, cols, z, h.dy16, M, cols, st, dbias ? w.colpart : nullptr));
+        else
+            GENIE_TRY(launch_cast_transpose16(npl, in, cols, z, h.dy16, h.dy16T, M, cols, st, dbias ? w.colpart : nullptr,
+                                              grad_scale16()));
+        return dbias ? launch_slab_reduce(w.colpart, M / 64, (size_t)cols, dbias, beta, st) : GENIE_OK;
+    }
+    // weight gradient from the gradient copies in `h` and the saved row-major 16-bit activation X16 (M, K)
+    int wgrad_any(const Operand* X16, float* dW, int N, int K, float alpha) {
+        if (use_tn(npl, M, N, K)) {
+            const int rc = launch_wgrad16_tn(h.dy16, N, X16, K, dW, M, N, K, alpha, beta, w.slabs, w.slab_floats, st);
+            GENIE_CHECK_SHAPE(rc != GENIE_E_UNSUPPORTED, "wgrad: TN kernel refused N=%d K=%d after its operand was prepared", N, K);
+            return rc;
+        }
+        GENIE_TRY(launch_transpose16(npl, X16, h.xT16, M, K, st));
+        return wgrad16(npl, h.dy16T, h.xT16, dW, M, N, K, alpha, beta, w.slabs, w.slab_floats, st);
+    }
+    int linear_backward(float* dy, const Operand* x, const Lin& l, const float* z, const float* R, float* dx, float alpha = 1.0f) {
+        const float ga = alpha / grad_scale16();
+        GENIE_TRY(cast_t_bias(dy, l.N, z, l.db, l.K));
+        GENIE_TRY(wgrad_any(x, l.dw, l.N, l.K, ga));
+        return lin16(npl, h.dy16, l.wT16, nullptr, R, dx, nullptr, M, l.K, l.N, ga, st);
+    }
+};
+
+// ================================================================================================
+// The step, once for both backends
+// ================================================================================================
+template <class Ops>
+static int train_forward(Ops& o, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels, char* acts,
+                         const TrainActs& a, double* sums, const EmbedAct* act) {
+    using Operand = typename Ops::Operand;
+    const genie_cfg& c = o.c;
+    const size_t pd = (size_t)o.M * c.d_model;
     auto F = [&](int l, size_t off) { return (float*)(acts + a.per_layer * l + off); };
-    auto H16 = [&](int l, size_t off) { return (uint16_t*)(acts + a.per_layer * l + off); };
-    GENIE_TRY(launch_embed(c, *wt, input_ids, B, F(0, a.x0), st, act));
-    if (c.qk_norm) GENIE_TRY(launch_cast16(npl, F(0, a.x0), H16(0, a.u1), pd, st));
+    auto X = [&](int l, size_t off) { return (Operand*)(acts + a.per_layer * l + off); };
+    float *xL = (float*)(acts + a.xL), *logits = (float*)(acts + a.logits);
+    Operand* xL_op = (Operand*)(acts + a.xL16);
+    GENIE_TRY(launch_embed(c, *wt, input_ids, o.B, F(0, a.x0), o.st, act));
+    // qk_norm: norm1 / norm2 are Identity (st_transformer.py:44,67), so the operand of qkv_s / fc1 is the residual stream itself:
+    // the Linear that produces it hands it over in operand form (y_op); layer 0 gets its from a cast.  Else norm1 / norm2 produce
+    // the operand, and the readout's comes from a cast.
+    const bool idn = c.qk_norm;
+    if (idn) GENIE_TRY(o.cast(F(0, a.x0), X(0, a.u1), pd));
     for (int l = 0; l < c.num_layers; ++l) {
         const genie_layer_weights& lw = wt->layers_host[l];
+        const LayerLins n = layer_lins(c, lw, nullptr, nullptr);
         const bool last = l + 1 == c.num_layers;
-        float* xnext = last ? (float*)(acts + a.xL) : F(l + 1, a.x0);
-        uint16_t* xnext16 = last ? (uint16_t*)(acts + a.xL16) : H16(l + 1, a.u1);
-        if (!c.qk_norm) {
-            if (npl == 1) GENIE_TRY(launch_layer_norm_bf16(F(l, a.x0), lw.norm1_w, lw.norm1_b, H16(l, a.u1), M, d, 1e-5f, st));
-            else GENIE_TRY(launch_layer_norm_split(F(l, a.x0), lw.norm1_w, lw.norm1_b, H16(l, a.u1), pd, M, d, 1e-5f, st));
-        }
-        GENIE_TRY(lin16(npl, H16(l, a.u1), pd, lw.spatial.qkv_w16, c.qkv_bias ? lw.spatial.qkv_b : nullptr, nullptr,
-                        F(l, a.qkvs), nullptr, M, 3 * d, d, 1.0f, st));
-        GENIE_TRY(attn_fwd16(c, lw.spatial, F(l, a.qkvs), false, H16(l, a.aos), tmp, B, npl, st));
-        GENIE_TRY(lin16(npl, H16(l, a.aos), pd, lw.spatial.proj_w16, c.proj_bias ? lw.spatial.proj_b : nullptr, F(l, a.x0),
-                        F(l, a.x1), H16(l, a.x1h), M, d, d, 1.0f, st));
-        GENIE_TRY(lin16(npl, H16(l, a.x1h), pd, lw.temporal.qkv_w16, c.qkv_bias ? lw.temporal.qkv_b : nullptr, nullptr,
-                        F(l, a.qkvt), nullptr, M, 3 * d, d, 1.0f, st));
-        GENIE_TRY(attn_fwd16(c, lw.temporal, F(l, a.qkvt), true, H16(l, a.aot), tmp, B, npl, st));
-        GENIE_TRY(lin16(npl, H16(l, a.aot), pd, lw.temporal.proj_w16, c.proj_bias ? lw.temporal.proj_b : nullptr,
-                        F(l, a.x1), F(l, a.x2), c.qk_norm ? H16(l, a.u2) : nullptr, M, d, d, 1.0f, st));
-        if (!c.qk_norm) {
-            if (npl == 1) GENIE_TRY(launch_layer_norm_bf16(F(l, a.x2), lw.norm2_w, lw.norm2_b, H16(l, a.u2), M, d, 1e-5f, st));
-            else GENIE_TRY(launch_layer_norm_split(F(l, a.x2), lw.norm2_w, lw.norm2_b, H16(l, a.u2), pd, M, d, 1e-5f, st));
-        }
-        // fc1: the f32 pre-activation is kept for gelu'; the 16-bit operand of fc2 gets gelu applied in the epilogue
-        GENIE_TRY(launch_gemm16_ex(npl, H16(l, a.u2), d, PL(npl, pd), lw.fc1_w16, d, PL(npl, (size_t)hid * d),
-                                   c.mlp_bias ? lw.fc1_b : nullptr, nullptr, F(l, a.z), H16(l, a.h), PL(npl, ph), hid, M, hid,
-                                   d, G16X_OUTF32 | G16X_OUT16 | G16X_GELU16, 1.0f, st, 1, 0, 0, 0));
-        GENIE_TRY(lin16(npl, H16(l, a.h), ph, lw.fc2_w16, c.mlp_bias ? lw.fc2_b : nullptr, F(l, a.x2), xnext,
-                        c.qk_norm ? xnext16 : nullptr, M, d, hid, 1.0f, st));
+        float* xnext = last ? xL : F(l + 1, a.x0);
+        Operand* xnext_op = last ? xL_op : X(l + 1, a.u1);
+        // spatial sub-block (st_transformer.py:73-74)
+        if (!idn) GENIE_TRY(o.norm(F(l, a.x0), lw.norm1_w, lw.norm1_b, X(l, a.u1)));
+        GENIE_TRY(o.linear(X(l, a.u1), n.qkv_s, nullptr, F(l, a.qkvs), nullptr, nullptr));
+        GENIE_TRY(o.attention(false, lw.spatial, F(l, a.qkvs), X(l, a.aos)));
+        GENIE_TRY(o.linear(X(l, a.aos), n.proj_s, F(l, a.x0), F(l, a.x1), X(l, a.x1h), nullptr));
+        // temporal sub-block (st_transformer.py:77-78)
+        GENIE_TRY(o.linear(X(l, a.x1h), n.qkv_t, nullptr, F(l, a.qkvt), nullptr, nullptr));
+        GENIE_TRY(o.attention(true, lw.temporal, F(l, a.qkvt), X(l, a.aot)));
+        GENIE_TRY(o.linear(X(l, a.aot), n.proj_t, F(l, a.x1), F(l, a.x2), idn ? X(l, a.u2) : nullptr, nullptr));
+        // MLP sub-block (st_transformer.py:81, 16-25)
+        if (!idn) GENIE_TRY(o.norm(F(l, a.x2), lw.norm2_w, lw.norm2_b, X(l, a.u2)));
+        GENIE_TRY(o.linear(X(l, a.u2), n.fc1, nullptr, F(l, a.z), nullptr, X(l, a.h)));
+        GENIE_TRY(o.linear(X(l, a.h), n.fc2, F(l, a.x2), xnext, idn ? xnext_op : nullptr, nullptr));
     }
-    if (!c.qk_norm) GENIE_TRY(launch_cast16(npl, (float*)(acts + a.xL), (uint16_t*)(acts + a.xL16), pd, st));
-    GENIE_TRY(lin16(npl, (uint16_t*)(acts + a.xL16), pd, wt->out_w16, wt->out_b, nullptr, (float*)(acts + a.logits), nullptr,
-                    M, V, d, c.readout_mult, st));
-    if (hipMemsetAsync(sums, 0, 3 * sizeof(double), st) != hipSuccess) {
+    if (!idn) GENIE_TRY(o.cast(xL, xL_op, pd));
+    GENIE_TRY(o.linear(xL_op, readout_lin(c, wt, nullptr, nullptr), nullptr, logits, nullptr, nullptr, c.readout_mult));
+    if (hipMemsetAsync(sums, 0, 3 * sizeof(double), o.st) != hipSuccess) {
         set_error("genie_train_forward: hipMemsetAsync failed");
         return GENIE_E_LAUNCH;
     }
-    return launch_ce_fwd_bwd(c, (float*)(acts + a.logits), input_ids, labels, B, sums, st);
+    return launch_ce_fwd_bwd(c, logits, input_ids, labels, o.B, sums, o.st);
 }
 
-static int train_backward_head16(const genie_cfg& c, const genie_weights* wt, const genie_weights* wT,
-                                 const genie_weights* grads, int B, char* acts, TrainWs& w, TrainWs16& h, float beta,
-                                 hipStream_t st) {
-    const int npl = npl_of(c);
-    GENIE_TRY(need16(wT, c, "genie_train_backward_head (transposed copies)"));
-    const TrainActs16 a = train_acts16(c, B, npl);
-    const int d = c.d_model, M = B * c.T * c.S, V = c.factored_vocab * c.num_factored;
-    float* dl = (float*)(acts + a.logits);
-    GENIE_TRY(cast_t_bias(npl, dl, V, nullptr, h, M, (float*)grads->out_b, beta, w, st, d));
-    GENIE_TRY(wgrad_any(npl, h, (const uint16_t*)(acts + a.xL16), (float*)grads->out_w, M, V, d, c.readout_mult, beta, w, st));
-    return lin16(npl, h.dy16, (size_t)M * V, wT->out_w16, nullptr, nullptr, w.dx, nullptr, M, d, V, galpha(npl, c.readout_mult), st);
+// d loss / d logits (in the logits slot) -> the readout's gradients and d xL in w.dx
+template <class Ops>
+static int train_backward_head(Ops& o, const genie_weights* wt, const genie_weights* wT, const genie_weights* grads, char* acts,
+                               const TrainActs& a) {
+    return o.linear_backward((float*)(acts + a.logits), (const typename Ops::Operand*)(acts + a.xL16),
+                             readout_lin(o.c, wt, wT, grads), nullptr, nullptr, o.w.dx, o.c.readout_mult);
 }
 
-static int train_backward_layer16(const genie_cfg& c, const genie_weights* wt, const genie_weights* wT,
-                                  const genie_weights* grads, int layer, int B, char* acts, TrainWs& w, TrainWs16& h,
-                                  float beta, hipStream_t st) {
-    const int npl = npl_of(c);
-    const TrainActs16 a = train_acts16(c, B, npl);
-    const int d = c.d_model, hid = c.hidden, M = B * c.T * c.S;
-    const size_t pd = (size_t)M * d, ph = (size_t)M * hid, p3 = (size_t)M * 3 * d;
+// w.dx: d loss / d (the layer's output) -> d loss / d (its input), and the layer's gradients
+template <class Ops>
+static int train_backward_layer(Ops& o, const genie_weights* wt, const genie_weights* wT, const genie_weights* grads, int layer,
+                                char* acts, const TrainActs& a) {
+    const genie_cfg& c = o.c;
+    const int d = c.d_model, M = o.M, B = o.B;
+    const float beta = o.beta;
+    hipStream_t st = o.st;
+    TrainWs& w = o.w;
     const genie_layer_weights& lw = wt->layers_host[layer];
-    const genie_layer_weights& lt = wT->layers_host[layer];
     const genie_layer_weights& g = grads->layers_host[layer];
+    const LayerLins n = layer_lins(c, lw, wT ? &wT->layers_host[layer] : nullptr, &g);
     char* L = acts + a.per_layer * layer;
     auto F = [&](size_t off) { return (float*)(L + off); };
-    auto H16 = [&](size_t off) { return (const uint16_t*)(L + off); };
+    auto X = [&](size_t off) { return (const typename Ops::Operand*)(L + off); };
     float* dx = w.dx;
     QkSrc qk;
 
-    // ---- MLP
-    GENIE_TRY(cast_t_bias(npl, dx, d, nullptr, h, M, c.mlp_bias ? (float*)g.fc2_b : nullptr, beta, w, st, hid));
-    GENIE_TRY(wgrad_any(npl, h, H16(a.h), (float*)g.fc2_w, M, d, hid, 1.0f, beta, w, st));
-    GENIE_TRY(lin16(npl, h.dy16, pd, lt.fc2_w16, nullptr, nullptr, w.g, nullptr, M, hid, d, galpha(npl, 1.0f), st));         // dh
-    GENIE_TRY(cast_t_bias(npl, w.g, hid, F(a.z), h, M, c.mlp_bias ? (float*)g.fc1_b : nullptr, beta, w, st, d));  // dz
-    GENIE_TRY(wgrad_any(npl, h, H16(a.u2), (float*)g.fc1_w, M, hid, d, 1.0f, beta, w, st));
+    // ---- MLP: x3 = x2 + fc2(gelu(fc1(norm2(x2))))  (st_transformer.py:81, 16-25)
+    GENIE_TRY(o.linear_backward(dx, X(a.h), n.fc2, nullptr, nullptr, w.g));                 // dh
     if (c.qk_norm) {
-        GENIE_TRY(lin16(npl, h.dy16, ph, lt.fc1_w16, nullptr, dx, dx, nullptr, M, d, hid, galpha(npl, 1.0f), st));
+        GENIE_TRY(o.linear_backward(w.g, X(a.u2), n.fc1, F(a.z), dx, dx));                  // Identity norm: dx += dz . W1
     } else {
-        GENIE_TRY(lin16(npl, h.dy16, ph, lt.fc1_w16, nullptr, nullptr, w.d1, nullptr, M, d, hid, galpha(npl, 1.0f), st));
-        GENIE_TRY(launch_ln_bwd(F(a.x2), lw.norm2_w, w.d1, dx, (float*)g.norm2_w, (float*)g.norm2_b, M, d, 1e-5f, beta,
+        GENIE_TRY(o.linear_backward(w.g, X(a.u2), n.fc1, F(a.z), nullptr, w.d1));           // d norm2 output
+        GENIE_TRY(launch_ln_bwd(F(a.x2), lw.norm2_w, w.d1, dx, (float*)g.norm2_w, (float*)g.norm2_b, M, d, LN_EPS, beta,
                                 w.lnpart, st));
     }
 
-    // ---- temporal
-    GENIE_TRY(cast_t_bias(npl, dx, d, nullptr, h, M, c.proj_bias ? (float*)g.temporal.proj_b : nullptr, beta, w, st, d));
-    GENIE_TRY(wgrad_any(npl, h, H16(a.aot), (float*)g.temporal.proj_w, M, d, d, 1.0f, beta, w, st));
-    GENIE_TRY(lin16(npl, h.dy16, pd, lt.temporal.proj_w16, nullptr, nullptr, w.d1, nullptr, M, d, d, galpha(npl, 1.0f), st));
+    // ---- temporal: x2 = x1 + proj(attn(qkv(x1))), no pre-norm  (st_transformer.py:77-78)
+    GENIE_TRY(o.linear_backward(dx, X(a.aot), n.proj_t, nullptr, nullptr, w.d1));           // d attention output
     GENIE_TRY(qk_source(c, lw.temporal, F(a.qkvt), w, B, &qk, st));
     GENIE_TRY(launch_attn_temporal_bwd(F(a.qkvt), qk.p, qk.ld, w.d1, w.g, B, c.T, c.S, d, c.num_heads, c.head_dim,
                                        c.attn_scale, st));
     GENIE_TRY(qk_norm_backward(c, lw.temporal, g.temporal, F(a.qkvt), w.g, w, B, beta, st));
-    GENIE_TRY(cast_t_bias(npl, w.g, 3 * d, nullptr, h, M, c.qkv_bias ? (float*)g.temporal.qkv_b : nullptr, beta, w, st, d));
-    GENIE_TRY(wgrad_any(npl, h, H16(a.x1h), (float*)g.temporal.qkv_w, M, 3 * d, d, 1.0f, beta, w, st));
-    GENIE_TRY(lin16(npl, h.dy16, p3, lt.temporal.qkv_w16, nullptr, dx, dx, nullptr, M, d, 3 * d, galpha(npl, 1.0f), st));
+    GENIE_TRY(o.linear_backward(w.g, X(a.x1h), n.qkv_t, nullptr, dx, dx));                  // dx += dqkv . Wqkv
 
-    // ---- spatial
-    GENIE_TRY(cast_t_bias(npl, dx, d, nullptr, h, M, c.proj_bias ? (float*)g.spatial.proj_b : nullptr, beta, w, st, d));
-    GENIE_TRY(wgrad_any(npl, h, H16(a.aos), (float*)g.spatial.proj_w, M, d, d, 1.0f, beta, w, st));
-    GENIE_TRY(lin16(npl, h.dy16, pd, lt.spatial.proj_w16, nullptr, nullptr, w.d1, nullptr, M, d, d, galpha(npl, 1.0f), st));
+    // ---- spatial: x1 = x0 + proj(attn(qkv(norm1(x0))))  (st_transformer.py:73-74)
+    GENIE_TRY(o.linear_backward(dx, X(a.aos), n.proj_s, nullptr, nullptr, w.d1));
     GENIE_TRY(qk_source(c, lw.spatial, F(a.qkvs), w, B, &qk, st));
     GENIE_TRY(spatial_attn_bwd(c, F(a.qkvs), qk, w.d1, w.g, w, B, st));
     GENIE_TRY(qk_norm_backward(c, lw.spatial, g.spatial, F(a.qkvs), w.g, w, B, beta, st));
-    GENIE_TRY(cast_t_bias(npl, w.g, 3 * d, nullptr, h, M, c.qkv_bias ? (float*)g.spatial.qkv_b : nullptr, beta, w, st, d));
-    GENIE_TRY(wgrad_any(npl, h, H16(a.u1), (float*)g.spatial.qkv_w, M, 3 * d, d, 1.0f, beta, w, st));
-    if (c.qk_norm) return lin16(npl, h.dy16, p3, lt.spatial.qkv_w16, nullptr, dx, dx, nullptr, M, d, 3 * d, galpha(npl, 1.0f), st);
-    GENIE_TRY(lin16(npl, h.dy16, p3, lt.spatial.qkv_w16, nullptr, nullptr, w.d1, nullptr, M, d, 3 * d, galpha(npl, 1.0f), st));
-    return launch_ln_bwd(F(a.x0), lw.norm1_w, w.d1, dx, (float*)g.norm1_w, (float*)g.norm1_b, M, d, 1e-5f, beta, w.lnpart, st);
+    if (c.qk_norm) return o.linear_backward(w.g, X(a.u1), n.qkv_s, nullptr, dx, dx);
+    GENIE_TRY(o.linear_backward(w.g, X(a.u1), n.qkv_s, nullptr, nullptr, w.d1));            // d norm1 output
+    return launch_ln_bwd(F(a.x0), lw.norm1_w, w.d1, dx, (float*)g.norm1_w, (float*)g.norm1_b, M, d, LN_EPS, beta, w.lnpart, st);
 }
 
 }  // namespace genie
@@ -456,8 +478,7 @@ extern "C" {
 
 size_t genie_train_activation_bytes(const genie_cfg* cfg, int B) {
     if (!cfg || B <= 0) return 0;
-    if (cfg->precision != GENIE_PREC_EXACT) return train_acts16(*cfg, B, npl_of(*cfg)).total;
-    return train_acts(*cfg, B).total * sizeof(float);
+    return train_acts(*cfg, B).total;
 }
 size_t genie_train_workspace_bytes(const genie_cfg* cfg, int B) {
     if (!cfg || B <= 0) return 0;
@@ -506,46 +527,19 @@ int genie_train_forward_cond(const genie_cfg* cfg, const genie_weights* wt, cons
     const genie_cfg& c = *cfg;
     EmbedAct ea;
     const EmbedAct* act = frame_act(cond, c.S, 0, c.T, ea);
-    if (c.precision != GENIE_PREC_EXACT)
-        return train_forward16(c, wt, input_ids, labels, B, (char*)acts, acts_bytes, sums, (hipStream_t)stream, act);
+    GENIE_TRY(need16(wt, c, "genie_train_forward"));
     const TrainActs a = train_acts(c, B);
-    GENIE_CHECK_ARG(acts_bytes >= a.total * sizeof(float), "genie_train_forward: activation buffer too small: %zu < %zu",
-                    acts_bytes, a.total * sizeof(float));
+    GENIE_CHECK_ARG(acts_bytes >= a.total, "genie_train_forward: activation buffer too small: %zu < %zu", acts_bytes, a.total);
+    const int M = B * c.T * c.S, V = c.factored_vocab * c.num_factored;
     hipStream_t st = (hipStream_t)stream;
-    const int d = c.d_model, hid = c.hidden, M = B * c.T * c.S;
-    GENIE_TRY(launch_embed(c, *wt, input_ids, B, acts + a.o_x0, st, act));
-    for (int l = 0; l < c.num_layers; ++l) {
-        const genie_layer_weights& lw = wt->layers_host[l];
-        float* L = acts + a.per_layer * l;
-        float* xnext = (l + 1 < c.num_layers) ? acts + a.per_layer * (l + 1) + a.o_x0 : acts + a.o_xL;
-        // qk_norm: norm1/norm2 are Identity (st_transformer.py:44,67) and the u1/u2 slots stay unused
-        const float* u1 = c.qk_norm ? L + a.o_x0 : L + a.o_u1;
-        const float* u2 = c.qk_norm ? L + a.o_x2 : L + a.o_u2;
-        if (!c.qk_norm) GENIE_TRY(launch_layer_norm(L + a.o_x0, lw.norm1_w, lw.norm1_b, L + a.o_u1, M, d, 1e-5f, st));
-        GENIE_TRY(lin(u1, d, lw.spatial.qkv_w, c.qkv_bias ? lw.spatial.qkv_b : nullptr, nullptr, L + a.o_qkvs,
-                      3 * d, M, 3 * d, d, 1.0f, st));
-        GENIE_TRY(spatial_attn_fwd(c, lw.spatial, L + a.o_qkvs, L + a.o_aos, B, st));
-        GENIE_TRY(lin(L + a.o_aos, d, lw.spatial.proj_w, c.proj_bias ? lw.spatial.proj_b : nullptr, L + a.o_x0,
-                      L + a.o_x1, d, M, d, d, 1.0f, st));
-        GENIE_TRY(lin(L + a.o_x1, d, lw.temporal.qkv_w, c.qkv_bias ? lw.temporal.qkv_b : nullptr, nullptr, L + a.o_qkvt,
-                      3 * d, M, 3 * d, d, 1.0f, st));
-        GENIE_TRY(temporal_attn_fwd(c, lw.temporal, L + a.o_qkvt, L + a.o_aot, B, st));
-        GENIE_TRY(lin(L + a.o_aot, d, lw.temporal.proj_w, c.proj_bias ? lw.temporal.proj_b : nullptr, L + a.o_x1,
-                      L + a.o_x2, d, M, d, d, 1.0f, st));
-        if (!c.qk_norm) GENIE_TRY(launch_layer_norm(L + a.o_x2, lw.norm2_w, lw.norm2_b, L + a.o_u2, M, d, 1e-5f, st));
-        GENIE_TRY(lin(u2, d, lw.fc1_w, c.mlp_bias ? lw.fc1_b : nullptr, nullptr, L + a.o_z, hid, M, hid, d, 1.0f,
-                      st));
-        GENIE_TRY(launch_gelu_fwd(L + a.o_z, L + a.o_h, (size_t)M * hid, st));
-        GENIE_TRY(lin(L + a.o_h, hid, lw.fc2_w, c.mlp_bias ? lw.fc2_b : nullptr, L + a.o_x2, xnext, d, M, d, hid, 1.0f,
-                      st));
+    char* base = (char*)acts;
+    if (c.precision == GENIE_PREC_EXACT) {
+        ExactOps o{c, B, M, st, TrainWs{}, 0.0f};
+        return train_forward(o, wt, input_ids, labels, base, a, sums, act);
     }
-    const int V = c.factored_vocab * c.num_factored;
-    GENIE_TRY(lin(acts + a.o_xL, d, wt->out_w, wt->out_b, nullptr, acts + a.o_logits, V, M, V, d, c.readout_mult, st));
-    if (hipMemsetAsync(sums, 0, 3 * sizeof(double), st) != hipSuccess) {
-        set_error("genie_train_forward: hipMemsetAsync failed");
-        return GENIE_E_LAUNCH;
-    }
-    return launch_ce_fwd_bwd(c, acts + a.o_logits, input_ids, labels, B, sums, st);
+    GENIE_CHECK_SHAPE(V >= c.d_model, "training step (16-bit): vocabulary rows %d < d_model %d", V, c.d_model);
+    Ops16 o{c, B, M, st, TrainWs{}, 0.0f, npl_of(c), TrainWs16{}, (float*)(base + a.logits)};
+    return train_forward(o, wt, input_ids, labels, base, a, sums, act);
 }
 
 int genie_train_backward_head(const genie_cfg* cfg, const genie_weights* wt, const genie_weights* wT,
@@ -554,22 +548,21 @@ int genie_train_backward_head(const genie_cfg* cfg, const genie_weights* wt, con
     GENIE_TRY(train_check(cfg, B));
     GENIE_CHECK_ARG(wt && grads && acts && workspace, "genie_train_backward_head: NULL argument");
     const genie_cfg& c = *cfg;
-    TrainWs w = train_ws(c, B, workspace);
-    hipStream_t st = (hipStream_t)stream;
-    if (c.precision != GENIE_PREC_EXACT) {
-        TrainWs16 h = train_ws16(c, B, npl_of(c), workspace, w.total);
-        GENIE_CHECK_ARG(workspace_bytes >= h.total, "training workspace too small: %zu < %zu", workspace_bytes, h.total);
-        return train_backward_head16(c, wt, wT, grads, B, (char*)acts, w, h, accumulate ? 1.0f : 0.0f, st);
-    }
+    const TrainWs w = train_ws(c, B, workspace);
     const TrainActs a = train_acts(c, B);
-    GENIE_CHECK_ARG(workspace_bytes >= w.total, "training workspace too small: %zu < %zu", workspace_bytes, w.total);
-    const int d = c.d_model, M = B * c.T * c.S, V = c.factored_vocab * c.num_factored;
+    const int M = B * c.T * c.S;
     const float beta = accumulate ? 1.0f : 0.0f;
-    const float* dl = acts + a.o_logits;
-    GENIE_TRY(launch_wgrad_f32(dl, V, acts + a.o_xL, d, (float*)grads->out_w, M, V, d, c.readout_mult, beta, w.slabs,
-                               w.slab_floats, st));
-    GENIE_TRY(launch_colsum(dl, V, M, V, (float*)grads->out_b, beta, w.colpart, st));
-    return dgrad(dl, wt->out_w, nullptr, w.dx, M, V, d, c.readout_mult, st);
+    hipStream_t st = (hipStream_t)stream;
+    if (c.precision == GENIE_PREC_EXACT) {
+        GENIE_CHECK_ARG(workspace_bytes >= w.total, "training workspace too small: %zu < %zu", workspace_bytes, w.total);
+        ExactOps o{c, B, M, st, w, beta};
+        return train_backward_head(o, wt, wT, grads, (char*)acts, a);
+    }
+    const TrainWs16 h = train_ws16(c, B, npl_of(c), workspace, w.total);
+    GENIE_CHECK_ARG(workspace_bytes >= h.total, "training workspace too small: %zu < %zu", workspace_bytes, h.total);
+    GENIE_TRY(need16(wT, c, "genie_train_backward_head (transposed copies)"));
+    Ops16 o{c, B, M, st, w, beta, npl_of(c), h, nullptr};
+    return train_backward_head(o, wt, wT, grads, (char*)acts, a);
 }
 
 int genie_train_backward_layer(const genie_cfg* cfg, const genie_weights* wt, const genie_weights* wT,
@@ -579,70 +572,21 @@ int genie_train_backward_layer(const genie_cfg* cfg, const genie_weights* wt, co
     GENIE_CHECK_ARG(wt && grads && acts && workspace, "genie_train_backward_layer: NULL argument");
     GENIE_CHECK_ARG(layer >= 0 && layer < cfg->num_layers, "genie_train_backward_layer: layer %d out of range", layer);
     const genie_cfg& c = *cfg;
-    TrainWs w = train_ws(c, B, workspace);
-    hipStream_t st = (hipStream_t)stream;
-    if (c.precision != GENIE_PREC_EXACT) {
-        GENIE_TRY(need16(wT, c, "genie_train_backward_layer (transposed copies)"));
-        TrainWs16 h = train_ws16(c, B, npl_of(c), workspace, w.total);
-        GENIE_CHECK_ARG(workspace_bytes >= h.total, "training workspace too small: %zu < %zu", workspace_bytes, h.total);
-        return train_backward_layer16(c, wt, wT, grads, layer, B, (char*)acts, w, h, accumulate ? 1.0f : 0.0f, st);
-    }
+    const TrainWs w = train_ws(c, B, workspace);
     const TrainActs a = train_acts(c, B);
-    GENIE_CHECK_ARG(workspace_bytes >= w.total, "training workspace too small: %zu < %zu", workspace_bytes, w.total);
-    const int d = c.d_model, hid = c.hidden, M = B * c.T * c.S;
+    const int M = B * c.T * c.S;
     const float beta = accumulate ? 1.0f : 0.0f;
-    const genie_layer_weights& lw = wt->layers_host[layer];
-    const genie_layer_weights& g = grads->layers_host[layer];
-    const float* L = acts + a.per_layer * layer;
-    float* dx = w.dx;
-    const float* u1 = c.qk_norm ? L + a.o_x0 : L + a.o_u1;
-    const float* u2 = c.qk_norm ? L + a.o_x2 : L + a.o_u2;
-    QkSrc qk;
-
-    // ---- MLP: x3 = x2 + fc2(gelu(fc1(norm2(x2))))  (st_transformer.py:81, 16-25)
-    GENIE_TRY(launch_wgrad_f32(dx, d, L + a.o_h, hid, (float*)g.fc2_w, M, d, hid, 1.0f, beta, w.slabs, w.slab_floats, st));
-    if (c.mlp_bias) GENIE_TRY(launch_colsum(dx, d, M, d, (float*)g.fc2_b, beta, w.colpart, st));
-    GENIE_TRY(dgrad(dx, lw.fc2_w, nullptr, w.g, M, d, hid, 1.0f, st));          // dh
-    GENIE_TRY(launch_gelu_bwd(L + a.o_z, w.g, (size_t)M * hid, st));            // dz
-    GENIE_TRY(launch_wgrad_f32(w.g, hid, u2, d, (float*)g.fc1_w, M, hid, d, 1.0f, beta, w.slabs, w.slab_floats, st));
-    if (c.mlp_bias) GENIE_TRY(launch_colsum(w.g, hid, M, hid, (float*)g.fc1_b, beta, w.colpart, st));
-    if (c.qk_norm) {
-        GENIE_TRY(dgrad(w.g, lw.fc1_w, dx, dx, M, hid, d, 1.0f, st));           // Identity norm: dx += dz . W1
-    } else {
-        GENIE_TRY(dgrad(w.g, lw.fc1_w, nullptr, w.d1, M, hid, d, 1.0f, st));    // d norm2 output
-        GENIE_TRY(launch_ln_bwd(L + a.o_x2, lw.norm2_w, w.d1, dx, (float*)g.norm2_w, (float*)g.norm2_b, M, d, 1e-5f, beta,
-                                w.lnpart, st));
+    hipStream_t st = (hipStream_t)stream;
+    if (c.precision == GENIE_PREC_EXACT) {
+        GENIE_CHECK_ARG(workspace_bytes >= w.total, "training workspace too small: %zu < %zu", workspace_bytes, w.total);
+        ExactOps o{c, B, M, st, w, beta};
+        return train_backward_layer(o, wt, wT, grads, layer, (char*)acts, a);
     }
-
-    // ---- temporal: x2 = x1 + proj(attn(qkv(x1))), no pre-norm  (st_transformer.py:77-78)
-    GENIE_TRY(launch_wgrad_f32(dx, d, L + a.o_aot, d, (float*)g.temporal.proj_w, M, d, d, 1.0f, beta, w.slabs,
-                               w.slab_floats, st));
-    if (c.proj_bias) GENIE_TRY(launch_colsum(dx, d, M, d, (float*)g.temporal.proj_b, beta, w.colpart, st));
-    GENIE_TRY(dgrad(dx, lw.temporal.proj_w, nullptr, w.d1, M, d, d, 1.0f, st));  // d attention output
-    GENIE_TRY(qk_source(c, lw.temporal, L + a.o_qkvt, w, B, &qk, st));
-    GENIE_TRY(launch_attn_temporal_bwd(L + a.o_qkvt, qk.p, qk.ld, w.d1, w.g, B, c.T, c.S, d, c.num_heads, c.head_dim,
-                                       c.attn_scale, st));
-    GENIE_TRY(qk_norm_backward(c, lw.temporal, g.temporal, L + a.o_qkvt, w.g, w, B, beta, st));
-    GENIE_TRY(launch_wgrad_f32(w.g, 3 * d, L + a.o_x1, d, (float*)g.temporal.qkv_w, M, 3 * d, d, 1.0f, beta, w.slabs,
-                               w.slab_floats, st));
-    if (c.qkv_bias) GENIE_TRY(launch_colsum(w.g, 3 * d, M, 3 * d, (float*)g.temporal.qkv_b, beta, w.colpart, st));
-    GENIE_TRY(dgrad(w.g, lw.temporal.qkv_w, dx, dx, M, 3 * d, d, 1.0f, st));     // dx += dqkv . Wqkv
-
-    // ---- spatial: x1 = x0 + proj(attn(qkv(norm1(x0))))  (st_transformer.py:73-74)
-    GENIE_TRY(launch_wgrad_f32(dx, d, L + a.o_aos, d, (float*)g.spatial.proj_w, M, d, d, 1.0f, beta, w.slabs, w.slab_floats,
-                               st));
-    if (c.proj_bias) GENIE_TRY(launch_colsum(dx, d, M, d, (float*)g.spatial.proj_b, beta, w.colpart, st));
-    GENIE_TRY(dgrad(dx, lw.spatial.proj_w, nullptr, w.d1, M, d, d, 1.0f, st));
-    GENIE_TRY(qk_source(c, lw.spatial, L + a.o_qkvs, w, B, &qk, st));
-    GENIE_TRY(spatial_attn_bwd(c, L + a.o_qkvs, qk, w.d1, w.g, w, B, st));
-    GENIE_TRY(qk_norm_backward(c, lw.spatial, g.spatial, L + a.o_qkvs, w.g, w, B, beta, st));
-    GENIE_TRY(launch_wgrad_f32(w.g, 3 * d, u1, d, (float*)g.spatial.qkv_w, M, 3 * d, d, 1.0f, beta, w.slabs,
-                               w.slab_floats, st));
-    if (c.qkv_bias) GENIE_TRY(launch_colsum(w.g, 3 * d, M, 3 * d, (float*)g.spatial.qkv_b, beta, w.colpart, st));
-    if (c.qk_norm) return dgrad(w.g, lw.spatial.qkv_w, dx, dx, M, 3 * d, d, 1.0f, st);
-    GENIE_TRY(dgrad(w.g, lw.spatial.qkv_w, nullptr, w.d1, M, 3 * d, d, 1.0f, st));  // d norm1 output
-    return launch_ln_bwd(L + a.o_x0, lw.norm1_w, w.d1, dx, (float*)g.norm1_w, (float*)g.norm1_b, M, d, 1e-5f, beta, w.lnpart,
-                         st);
+    GENIE_TRY(need16(wT, c, "genie_train_backward_layer (transposed copies)"));
+    const TrainWs16 h = train_ws16(c, B, npl_of(c), workspace, w.total);
+    GENIE_CHECK_ARG(workspace_bytes >= h.total, "training workspace too small: %zu < %zu", workspace_bytes, h.total);
+    Ops16 o{c, B, M, st, w, beta, npl_of(c), h, nullptr};
+    return train_backward_layer(o, wt, wT, grads, layer, (char*)acts, a);
 }
 
 int genie_train_backward_embed(const genie_cfg* cfg, const genie_weights* grads, const int64_t* input_ids, int B,

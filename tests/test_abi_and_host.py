@@ -109,6 +109,39 @@ def test_workspace_holds_the_16bit_scratch_when_the_vocabulary_is_narrower_than_
         assert ws(d_model=d, image_vocab_size=4 * d, num_factored_vocabs=1)[0] == narrow + M * 3 * d * 4   # V = 4d: M * V floats
 
 
+# (genie_train_activation_bytes, genie_train_workspace_bytes) in exact, bf16, f16x3.  Read from the library of the commit before the
+# training step's layer was stated once for the three precisions (one layout function for the saved activations): the buffers are
+# opaque to the caller, their sizes are not.
+TRAIN_BUFFER_BYTES = {
+    "d64": [(966656, 18211328), (860160, 18604544), (1015808, 18997760)],                    # tests/test_hip_train_bf16.py
+    "s144qk": [(15040512, 38822912), (13123584, 42361856), (15925248, 45900800)],             # tests/test_hip_train_geometry.py
+    "t8s256": [(31457280, 49816576), (28311552, 62399488), (33554432, 74982400)],
+    "c35/B1": [(2839543808, 161490944), (2371878912, 186656768), (2977955840, 211822592)],
+    "c35/B8": [(22716350464, 808462336), (18975031296, 1009788928), (23823646720, 1211115520)],
+    "c138/B1": [(5662310400, 390082560), (4726980608, 440414208), (5939134464, 490745856)],
+    "c138/B8": [(45298483200, 1214263296), (37815844864, 1616916480), (47513075712, 2019569664)],
+}
+
+
+def test_training_buffer_sizes_are_unchanged():
+    lib_mod = pkg("_lib")
+    L = lib_mod.load()
+    C = pkg("config")
+
+    def small(H, d, T, S, qk_norm, layers):
+        return C.GenieConfig(num_layers=layers, num_heads=H, d_model=d, T=T, S=S, num_factored_vocabs=2, qk_norm=qk_norm,
+                             num_prompt_frames=max(1, T // 2), use_mup=False)
+    cases = {"d64": (small(2, 64, 4, 16, False, 2), 1), "s144qk": (small(2, 128, 4, 144, True, 2), 1),
+             "t8s256": (small(2, 128, 8, 256, False, 1), 1), "c35/B1": (C.c35(), 1), "c35/B8": (C.c35(), 8),
+             "c138/B1": (C.c138(), 1), "c138/B8": (C.c138(), 8)}
+    assert sorted(cases) == sorted(TRAIN_BUFFER_BYTES)
+    for name, (cfg, B) in cases.items():
+        for prec, want in zip((lib_mod.PREC_EXACT, lib_mod.PREC_BF16, lib_mod.PREC_F16X3), TRAIN_BUFFER_BYTES[name]):
+            c = lib_mod.make_cfg(cfg, prec)
+            got = (L.genie_train_activation_bytes(c, B), L.genie_train_workspace_bytes(c, B))
+            assert got == want, (name, prec, got, want)
+
+
 def test_config_roundtrip_and_derived(tmp_path):
     C = pkg("config")
     c = C.c35()

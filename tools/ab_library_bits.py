@@ -17,7 +17,13 @@ as a whole must reach each of them in the first library, else the battery itself
 table could show: the launches of attn_spatial_dma are profiled unnamed (they are counted, and compared, as "(unnamed)" of the spatial
 attention class behind the 16-bit gemm16_pp qkv GEMMs), and splitk2_residual_kernel is launched outside any profiler scope (the d 512
 bf16 decode passes at 8 clips are inside the shape window of fc2_splitk2; its two-slab GEMM in front is counted).  For both a proxy
-is printed with the watched lines, and the first one is required."""
+is printed with the watched lines, and the first one is required.
+
+The training battery (--battery train; the default runs both, each in its own pair of child processes): per case a GenieTrainer, one
+forward_backward, a second one with accumulate=True, one optimizer_step.  Recorded: the loss sums and every gradient tensor after each
+call, the flat parameters after the step, genie_train_activation_bytes / genie_train_workspace_bytes, and the kernel tables around the
+whole case (the trainer's weight packing included).  TRAIN_CASES are geometries tests/test_hip_train*.py pin, in all three precisions;
+s144 (T*S = 288) is refused by the 16-bit step and counts through its return code."""
 import argparse
 import ctypes
 import hashlib
@@ -38,9 +44,18 @@ PRECISIONS = ["exact", "bf16", "f16x3"]
 WATCHED = ["spatial_attn_proj_bf16_kernel", "temporal_fused_bf16_kernel", "mlp_fused_bf16_kernel", "temporal_prefix_fused_bf16_kernel",
            "temporal_qkv_attn_f16x3_kernel", "gemm16_pp_kernel", "gemm16_sm_ln_kernel"]
 N_CLASSES = 6   # GENIE_KC_COUNT
+# training battery: (name, heads, d_model, T, S, clips, qk_norm, layers, action_vocab_size)
+TRAIN_CASES = [("d64", 2, 64, 4, 16, 1, False, 2, 0),         # transposed-copy wgrad with ns = 1; materialised spatial backward
+               ("t8s64qk", 2, 64, 8, 64, 1, True, 2, 0),      # qk-norm epilogue hand-offs; short-window temporal forward; generic temporal backward
+               ("d128", 2, 128, 4, 256, 2, False, 2, 0),      # fused spatial backward (exact / f16x3); attn_bwd16 + TN wgrad with slabs (bf16)
+               ("d256qk", 8, 256, 4, 256, 2, True, 2, 0),     # every weight on TN (bf16); wgrad16 ns > 1 (f16x3)
+               ("d384t16", 6, 384, 16, 64, 1, False, 1, 0),   # T = 16 MFMA temporal backward; TN and transposed-copy mixed in one layer
+               ("s144", 1, 64, 2, 144, 1, False, 2, 0),       # exact only: the 16-bit step refuses T*S = 288
+               ("d64act", 2, 64, 4, 16, 1, False, 2, 5)]      # the _cond forward and the embed backward with a table gradient
+TRAIN_WATCHED = ["gemm_f32_gen_kernel", "attn_spatial_bwd_fused_kernel", "wgrad16_tn_kernel", "attn_bwd16_"]
 
 
-def child(out_path):
+def child(out_path, battery):
     sys.path.insert(0, REPO)
     import numpy as np
     import torch
@@ -51,6 +66,12 @@ def child(out_path):
     STMaskGIT = importlib.import_module("1xgpt_amd.st_mask_git").STMaskGIT
     lib = _lib.load()
     record = {}
+
+    def nonzero_biases(sd, seed):   # the synthetic law leaves biases at zero: make every bias the kernels add count
+        g = np.random.default_rng(seed)
+        for k in sd:
+            if k.endswith(".bias") and "norm" not in k:
+                sd[k] = (0.05 * g.standard_normal(sd[k].shape)).astype(np.float32)
 
     def digest(t):
         a = t.detach().contiguous().cpu().numpy()
@@ -75,15 +96,46 @@ def child(out_path):
         record[name] = {"rc": rc, "outs": {k: digest(v) for k, v in outs.items()} if rc == 0 else {}, "kernels": table}
         print(name, "rc", rc, "launches", sum(table.values()), flush=True)
 
+    if battery == "train":
+        TO = importlib.import_module("oracle.genie_train_oracle")   # its collator draws from NumPy: the same batch in both children
+        GenieTrainer = importlib.import_module("1xgpt_amd.train").GenieTrainer
+        for name, heads, d, T, S, B, qk_norm, layers, n_act in TRAIN_CASES:
+            cfg = GenieConfig(num_layers=layers, num_heads=heads, d_model=d, T=T, S=S, num_factored_vocabs=2, qk_norm=qk_norm,
+                              use_mup=False, qkv_bias=True, num_prompt_frames=max(1, T // 2), action_vocab_size=n_act)
+            sd = synth.make_state_dict(cfg, seed=5, law="conditioned")
+            nonzero_biases(sd, 6)
+            batches = [TO.maskgit_collate(synth.make_clips(B, cfg, seed=7 + i), cfg, TO.NumpyDraws(9 + i)) for i in range(2)]
+            kw = [{"action_ids": torch.from_numpy(np.random.default_rng(11 + i).integers(0, n_act, (B, T))).cuda()} if n_act else {}
+                  for i in range(2)]
+            for prec in PRECISIONS:
+                sizes = []
+
+                def step():
+                    tr = GenieTrainer(STMaskGIT(cfg, precision=prec).load_numpy_state_dict(sd).to("cuda"), lr=1e-3)
+                    sizes[:] = [lib.genie_train_activation_bytes(tr.cfg, B), lib.genie_train_workspace_bytes(tr.cfg, B)]
+                    outs = {}
+                    for i, b in enumerate(batches):
+                        tr.forward_backward(torch.from_numpy(b["input_ids"]).cuda(), torch.from_numpy(b["labels"]).cuda(),
+                                            accumulate=i == 1, **kw[i])
+                        outs[f"call{i}/sums"] = tr.sums.clone()
+                        outs.update({f"call{i}/grad/{k}": g.clone() for k, g in tr.gradients().items()})
+                    tr.optimizer_step()
+                    outs["params"] = tr.params
+                    return 0, outs
+                case(f"{name}/{prec}", step)
+                record[f"{name}/{prec}"]["sizes"] = list(sizes)
+                print(f"{name}/{prec} activation / workspace bytes {sizes}", flush=True)
+                torch.cuda.empty_cache()
+        with open(out_path, "w") as f:
+            json.dump(record, f)
+        return
+
     for gname, d, heads, T, S, B in GEOMETRIES:
         for qk_norm in (False, True):
             cfg = GenieConfig(num_layers=2, num_heads=heads, d_model=d, T=T, S=S, num_factored_vocabs=2, qk_norm=qk_norm, use_mup=False,
                               qkv_bias=True)
             sd = synth.make_state_dict(cfg, seed=5, law="conditioned")
-            g = np.random.default_rng(6)
-            for k in sd:   # the synthetic law leaves biases at zero: make every bias the kernels add count
-                if k.endswith(".bias") and "norm" not in k:
-                    sd[k] = (0.05 * g.standard_normal(sd[k].shape)).astype(np.float32)
+            nonzero_biases(sd, 6)
             hw = int(round(S ** 0.5))
             V = cfg.factored_vocab_size * cfg.num_factored_vocabs
             for prec in PRECISIONS:
@@ -162,28 +214,21 @@ def child(out_path):
         json.dump(record, f)
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("library_a", nargs="?", help="the library to compare against (its tables decide whether the battery reached WATCHED)")
-    ap.add_argument("library_b", nargs="?")
-    ap.add_argument("--timeout", type=int, default=420, help="time limit of each child process, seconds")
-    ap.add_argument("--child", help=argparse.SUPPRESS)
-    a = ap.parse_args()
-    if a.child:
-        return child(a.child)
-    if not (a.library_a and a.library_b):
-        ap.error("two libraries")
+def run_battery(a, battery):
+    """Both children of one battery and the comparison of their records -> 0, or the exit status of the failure"""
+    watched = TRAIN_WATCHED if battery == "train" else WATCHED
     records = []
     with tempfile.TemporaryDirectory() as tmp:
         for i, path in enumerate((a.library_a, a.library_b)):
             out = os.path.join(tmp, f"record_{i}.json")
             env = dict(os.environ, GENIE_HIP_LIBRARY=os.path.abspath(path))
             try:
-                rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", out], env=env, timeout=a.timeout).returncode
+                rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", out, "--battery", battery], env=env,
+                                    timeout=a.timeout).returncode
             except subprocess.TimeoutExpired:
                 rc = 124
             if rc != 0:
-                print(f"FAIL: the battery on {path} ended with status {rc}; nothing more was started")
+                print(f"FAIL: the {battery} battery on {path} ended with status {rc}; nothing more was started")
                 return 2
             records.append(json.load(open(out)))
     ra, rb = records
@@ -197,6 +242,9 @@ def main():
         if ca["rc"] != cb["rc"]:
             bad += 1
             print(f"DIFF {name}: return code {ca['rc']} != {cb['rc']}")
+        if ca.get("sizes") != cb.get("sizes"):
+            bad += 1
+            print(f"DIFF {name}: activation / workspace bytes {ca.get('sizes')} != {cb.get('sizes')}")
         for k in sorted(set(ca["outs"]) | set(cb["outs"])):
             n_tensors += 1
             if ca["outs"].get(k) != cb["outs"].get(k):
@@ -210,18 +258,34 @@ def main():
     seen = {}
     for name, cs in ra.items():
         for k, v in cs["kernels"].items():
-            for wk in WATCHED:
+            for wk in watched:
                 if wk in k:
                     seen.setdefault(wk, {}).setdefault(name.split("/")[0], 0)
                     seen[wk][name.split("/")[0]] += v
-    for wk in WATCHED:
+    for wk in watched:
         print(f"watched {wk}: launches per geometry {seen.get(wk, {})}")
-    missing = [wk for wk in WATCHED if wk not in seen]
-    # proxies for the two kernels no table names.  attn_spatial_dma: the unnamed launches of the spatial attention class in the 16-bit
-    # cases of the S = 256 geometries (every launcher of that class the 16-bit drivers reach is profiled unnamed; the DMA kernel is the
-    # one behind a gemm16_pp qkv GEMM) -- each geometry must show some.  splitk2_residual: the GEMM table of the one case inside the
-    # shape window of fc2_splitk2 (its two-slab GEMM is one launch of the kernel the unsplit fc2 would run on, so this is printed, not
-    # required).
+    missing = [wk for wk in watched if wk not in seen]
+    if battery == "inference":
+        missing += inference_proxies(ra)
+    refused = sorted(n for n in ra if ra[n]["rc"] != 0)
+    print(f"{battery} battery: {len(ra)} cases ({len(refused)} refused by both libraries alike), {n_tensors} output tensors, "
+          f"{sum(sum(c['kernels'].values()) for c in ra.values())} profiled launches in the first library")
+    if missing:
+        print(f"FAIL (of the {battery} battery): never reached {missing}")
+        return 3
+    if bad:
+        print(f"FAIL: {bad} differences in the {battery} battery")
+        return 1
+    return 0
+
+
+def inference_proxies(ra):
+    """Proxies for the two kernels no table names -> what is missing.  attn_spatial_dma: the unnamed launches of the spatial attention
+    class in the 16-bit cases of the S = 256 geometries (every launcher of that class the 16-bit drivers reach is profiled unnamed; the
+    DMA kernel is the one behind a gemm16_pp qkv GEMM) -- each geometry must show some.  splitk2_residual: the GEMM table of the one
+    case inside the shape window of fc2_splitk2 (its two-slab GEMM is one launch of the kernel the unsplit fc2 would run on, so this is
+    printed, not required)."""
+    missing = []
     for gname in ("d256", "d512"):
         per = {prec: sum(cs["kernels"].get("1:(unnamed)", 0) for n, cs in ra.items() if n.startswith(gname + "/") and f"/{prec}/" in n)
                for prec in ("bf16", "f16x3")}
@@ -231,15 +295,26 @@ def main():
     sk = ra.get("d512/ln/bf16/frame_pass/B=8", {"kernels": {}})["kernels"]
     print("proxy splitk2_residual: GEMM launches of d512/ln/bf16/frame_pass/B=8 (2,048 rows, hidden 2,048: inside the fc2_splitk2 window):",
           {k: v for k, v in sk.items() if k.startswith("0:")})
-    refused = sorted(n for n in ra if ra[n]["rc"] != 0)
-    print(f"{len(ra)} cases ({len(refused)} refused by both libraries alike), {n_tensors} output tensors, "
-          f"{sum(sum(c['kernels'].values()) for c in ra.values())} profiled launches in the first library")
-    if missing:
-        print(f"FAIL (of the battery): never reached {missing}")
-        return 3
-    if bad:
-        print(f"FAIL: {bad} differences")
-        return 1
+    return missing
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("library_a", nargs="?", help="the library to compare against (its tables decide whether the battery reached WATCHED)")
+    ap.add_argument("library_b", nargs="?")
+    ap.add_argument("--timeout", type=int, default=420, help="time limit of each child process, seconds")
+    ap.add_argument("--battery", default="all", choices=["all", "inference", "train"],
+                    help="each battery runs in its own pair of child processes; a failing one ends the run")
+    ap.add_argument("--child", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.child:
+        return child(a.child, a.battery)
+    if not (a.library_a and a.library_b):
+        ap.error("two libraries")
+    for battery in (["inference", "train"] if a.battery == "all" else [a.battery]):
+        status = run_battery(a, battery)
+        if status:
+            return status
     print("PASS: zero differing bits, identical return codes, identical kernel tables")
     return 0
 
