@@ -141,6 +141,8 @@ SIGNATURES = {
                                              C.c_int, c_ptr]),
     "genie_train_backward_embed_cond": (C.c_int, [C.POINTER(GenieCfg), C.POINTER(Weights), c_ptr, C.c_int, c_ptr, C.c_size_t,
                                                   C.c_int, c_ptr, c_ptr, C.POINTER(FrameCond)]),
+    "genie_temporal_attention_backward": (C.c_int, [c_ptr, c_ptr, C.c_int64, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                    C.c_int, C.c_int, C.c_float, c_ptr]),
     "genie_sumsq": (C.c_int, [c_ptr, C.c_size_t, c_ptr, c_ptr, c_ptr]),
     "genie_adamw_step": (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float,
                                    C.c_float, C.c_int, C.c_float, c_ptr, C.c_float, c_ptr]),

@@ -754,11 +754,218 @@ __global__ __launch_bounds__(256) void attn_temporal_bwd_mfma_kernel(const float
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The same backward for T = 16 NT frames, NT = 2 / 4 (T = 32 / 64), head_dim 32 / 64: still one wave per (b, s, head) and no
+// LDS; the T x T scores are the lower triangle of NT x NT tiles of 16 x 16, each computed exactly as above (both layouts,
+// the same operand fragments and feature permutation).  Tile row I (queries 16I .. 16I+15) is the outer loop:
+//   S and dP of its I+1 tiles in both layouts stay in registers (<= 64 VGPRs); only the diagonal tile J = I is masked;
+//   max, 1/sum and D_i run over the whole tile row in the T layout (in-lane over tiles and e, then the two cross-group
+//   shuffles) and are fetched by lane index for the N layout;
+//   dQ_I = scale sum_J dS_IJ K_J is complete when the row ends and is stored once;
+//   dK_J += dS_IJ^T Q_I and dV_J += P_IJ^T dO_I accumulate in NT x 2 x NV register quads (128 VGPRs at T = 64, head_dim 64),
+//   in increasing I, and are stored once after the last row.
+// Nothing is kept between tiles but those: the K / V fragments of tile J are read again for every I >= J (L2 hits: a head's
+// rows are DH contiguous floats per frame, at most 3 x 16 KB per wave).  Every loop is unrolled (register arrays).
+// ------------------------------------------------------------------------------------------------
+template <int NV>
+__device__ __forceinline__ void load_nv(const float* __restrict__ p, float (&o)[NV]) {
+    if constexpr (NV == 4) {
+        const float4 a = *reinterpret_cast<const float4*>(p);
+        o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
+    } else {
+        const float2 a = *reinterpret_cast<const float2*>(p);
+        o[0] = a.x; o[1] = a.y;
+    }
+}
+template <int NV>
+__device__ __forceinline__ void store_nv(float* __restrict__ p, const f32x4 (&x)[NV], int e, float mul) {
+    if constexpr (NV == 4)
+        *reinterpret_cast<float4*>(p) = make_float4(x[0][e] * mul, x[1][e] * mul, x[2][e] * mul, x[3][e] * mul);
+    else
+        *reinterpret_cast<float2*>(p) = make_float2(x[0][e] * mul, x[1][e] * mul);
+}
+
+template <int DH, int NT>
+__global__ __launch_bounds__(256) void attn_temporal_bwd_tiled_kernel(const float* __restrict__ qkv,
+                                                                      const float* __restrict__ qk, long qk_ld,
+                                                                      const float* __restrict__ dO,
+                                                                      float* __restrict__ dqkv, long n_bs, int S, int d,
+                                                                      int H, float scale) {
+    constexpr int T = 16 * NT, PER = DH / 4, NV = DH / 16;
+    const int lane = threadIdx.x & 63;
+    const int r = lane & 15, g = lane >> 4;
+    const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long bs = wave / H;
+    const int head = (int)(wave - bs * H);
+    if (bs >= n_bs) return;
+    const long b = bs / S, s = bs - b * S;
+    const size_t row0 = (size_t)(b * T) * S + s;  // token row of frame 0; frame t is row0 + t*S
+    const float* qb = qk + row0 * qk_ld + head * DH;          // q at column 0, k at column d
+    const float* vb = qkv + row0 * 3 * d + 2 * d + head * DH;
+    const float* ob = dO + row0 * d + head * DH;
+    float* outb = dqkv + row0 * 3 * d + head * DH + NV * r;   // D map: lane (r,g) holds rows 4g+e, features NV*r + c
+    const long qs = (long)S * qk_ld, vs = (long)S * 3 * d, os = (long)S * d;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    f32x4 dk[NT][NV], dv[NT][NV];
+#pragma unroll
+    for (int J = 0; J < NT; ++J)
+#pragma unroll
+        for (int c = 0; c < NV; ++c) { dk[J][c] = zero; dv[J][c] = zero; }
+#pragma unroll
+    for (int I = 0; I < NT; ++I) {
+        // ---- row operands of the tile row: lane (r,g) holds features g*PER .. of frame 16I + r
+        float q[PER], go[PER];
+        {
+            const size_t t = (size_t)(16 * I + r);
+#pragma unroll
+            for (int c = 0; c < PER; c += 4) {
+                const float4 a = *reinterpret_cast<const float4*>(qb + t * qs + g * PER + c);
+                const float4 dd = *reinterpret_cast<const float4*>(ob + t * os + g * PER + c);
+                q[c] = a.x * scale; q[c + 1] = a.y * scale; q[c + 2] = a.z * scale; q[c + 3] = a.w * scale;
+                go[c] = dd.x; go[c + 1] = dd.y; go[c + 2] = dd.z; go[c + 3] = dd.w;
+            }
+        }
+        f32x4 sT[NT], pT[NT], sN[NT], pN[NT];
+#pragma unroll
+        for (int J = 0; J < NT; ++J) {
+            if (J > I) continue;
+            const size_t t = (size_t)(16 * J + r);
+            float k[PER], v[PER];
+#pragma unroll
+            for (int c = 0; c < PER; c += 4) {
+                const float4 bb = *reinterpret_cast<const float4*>(qb + t * qs + d + g * PER + c);
+                const float4 cc = *reinterpret_cast<const float4*>(vb + t * vs + g * PER + c);
+                k[c] = bb.x; k[c + 1] = bb.y; k[c + 2] = bb.z; k[c + 3] = bb.w;
+                v[c] = cc.x; v[c + 1] = cc.y; v[c + 2] = cc.z; v[c + 3] = cc.w;
+            }
+            // two accumulator chains per product (even / odd c), added at the end: half the chain length -- with sharp softmax rows
+            // (|s| ~ 16) the rounding of a DH/4-long f32 chain in the scores was the largest error of the whole backward
+            f32x4 a[2][4];
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int m = 0; m < 4; ++m) a[h][m] = zero;
+#pragma unroll
+            for (int c = 0; c < PER; ++c) {
+                a[c & 1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(k[c], q[c], a[c & 1][0], 0, 0, 0);   // S[i=r][j=4g+e]
+                a[c & 1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[c], go[c], a[c & 1][1], 0, 0, 0);  // dP[i=r][j=4g+e]
+                a[c & 1][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(q[c], k[c], a[c & 1][2], 0, 0, 0);   // S[i=4g+e][j=r]
+                a[c & 1][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(go[c], v[c], a[c & 1][3], 0, 0, 0);  // dP[i=4g+e][j=r]
+            }
+            sT[J] = a[0][0] + a[1][0]; pT[J] = a[0][1] + a[1][1]; sN[J] = a[0][2] + a[1][2]; pN[J] = a[0][3] + a[1][3];
+            // keep the next tile's operand loads behind this tile: hoisted across the unrolled tiles they cost more registers than
+            // one wave has (T = 64, head_dim 64)
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // ---- softmax statistics of row i = 16I + r in the T layout (causal: only the diagonal tile has j > i)
+        float mx = -INFINITY;
+#pragma unroll
+        for (int J = 0; J < NT; ++J) {
+            if (J > I) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (J == I && 4 * g + e > r) sT[J][e] = -INFINITY;
+                mx = fmaxf(mx, sT[J][e]);
+            }
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 16));
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        float sum = 0.f;
+#pragma unroll
+        for (int J = 0; J < NT; ++J) {
+            if (J > I) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { sT[J][e] = expf(sT[J][e] - mx); sum += sT[J][e]; }
+        }
+        sum += __shfl_xor(sum, 16);
+        sum += __shfl_xor(sum, 32);
+        const float inv = 1.0f / sum;
+        float dsum = 0.f;
+#pragma unroll
+        for (int J = 0; J < NT; ++J) {
+            if (J > I) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { sT[J][e] *= inv; dsum += sT[J][e] * pT[J][e]; }
+        }
+        dsum += __shfl_xor(dsum, 16);
+        dsum += __shfl_xor(dsum, 32);
+        // ---- statistics of row 16I + 4g+e for the N layout come from lane 4g+e (any group holds them)
+        float mi[4], ii[4], di[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            mi[e] = __shfl(mx, 4 * g + e); ii[e] = __shfl(inv, 4 * g + e); di[e] = __shfl(dsum, 4 * g + e);
+        }
+        // ---- B operands of the tile row's frames 16I + 4g+e, features NV*r .. NV*r+NV-1
+        float qq[4][NV], dd[4][NV];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const size_t t = (size_t)(16 * I + 4 * g + e);
+            load_nv<NV>(qb + t * qs + NV * r, qq[e]);
+            load_nv<NV>(ob + t * os + NV * r, dd[e]);
+        }
+        f32x4 dq[NV];
+#pragma unroll
+        for (int c = 0; c < NV; ++c) dq[c] = zero;
+#pragma unroll
+        for (int J = 0; J < NT; ++J) {
+            if (J > I) continue;
+            f32x4 dsT, dsN, prN;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                dsT[e] = sT[J][e] * (pT[J][e] - dsum);  // masked entries: P = 0
+                const float p = (J < I || r <= 4 * g + e) ? expf(sN[J][e] - mi[e]) * ii[e] : 0.f;
+                prN[e] = p;
+                dsN[e] = p * (pN[J][e] - di[e]);
+            }
+            float kk[4][NV];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) load_nv<NV>(qb + (size_t)(16 * J + 4 * g + e) * qs + d + NV * r, kk[e]);
+#pragma unroll
+            for (int c = 0; c < NV; ++c) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    dq[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(dsT[e], kk[e][c], dq[c], 0, 0, 0);
+                    dk[J][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(dsN[e], qq[e][c], dk[J][c], 0, 0, 0);
+                    dv[J][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(prN[e], dd[e][c], dv[J][c], 0, 0, 0);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) store_nv<NV>(outb + (size_t)(16 * I + 4 * g + e) * vs, dq, e, scale);
+    }
+    // qq holds the UNSCALED q (the scores used scale*q), so dK takes the scale here, as dQ does
+#pragma unroll
+    for (int J = 0; J < NT; ++J) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float* o = outb + (size_t)(16 * J + 4 * g + e) * vs;
+            store_nv<NV>(o + d, dk[J], e, scale);
+            store_nv<NV>(o + 2 * d, dv[J], e, 1.0f);
+        }
+    }
+}
+
 int launch_attn_temporal_bwd(const float* qkv, const float* qk, long qk_ld, const float* dO, float* dqkv, int B, int T,
                              int S, int d, int H, int Dh, float scale, hipStream_t st) {
-    GENIE_CHECK_SHAPE(T <= 16, "temporal attention backward: T=%d > 16", T);
+    GENIE_CHECK_SHAPE(T <= 64, "temporal attention backward: T=%d > 64", T);
+    GENIE_CHECK_SHAPE(T <= 16 || ((T == 32 || T == 64) && (Dh == 32 || Dh == 64)),
+                      "temporal attention backward: T=%d > 16 needs T in {32, 64} and head_dim in {32, 64}, not %d", T, Dh);
     const long n_grp = (long)B * S * H;
     if (n_grp <= 0) return GENIE_OK;
+    if (T > 16) {
+        ProfScope prof(GENIE_KC_ATTN_TEMPORAL, 10.0 * n_grp * T * T * Dh, 4.0 * n_grp * T * Dh * 7, st);
+        const unsigned wblocks = (unsigned)((n_grp + 3) / 4);
+#define TT_LAUNCH(DH_, NT_) \
+    attn_temporal_bwd_tiled_kernel<DH_, NT_><<<wblocks, 256, 0, st>>>(qkv, qk, qk_ld, dO, dqkv, (long)B * S, S, d, H, scale)
+        if (Dh == 64 && T == 64) TT_LAUNCH(64, 4);
+        else if (Dh == 64) TT_LAUNCH(64, 2);
+        else if (T == 64) TT_LAUNCH(32, 4);
+        else TT_LAUNCH(32, 2);
+#undef TT_LAUNCH
+        GENIE_LAUNCH_CHECK("attn_temporal_bwd_tiled");
+        return GENIE_OK;
+    }
     if (T == 16 && (Dh == 64 || Dh == 32)) {
         ProfScope prof(GENIE_KC_ATTN_TEMPORAL, 10.0 * n_grp * T * T * Dh, 4.0 * n_grp * T * Dh * 7, st);
         const unsigned wblocks = (unsigned)((n_grp + 3) / 4);

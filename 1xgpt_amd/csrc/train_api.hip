@@ -93,8 +93,8 @@ static int train_check(const genie_cfg* c, int B) {
         GENIE_CHECK_SHAPE(c->d_model % 64 == 0 && c->hidden % 64 == 0 && (c->T * c->S) % 64 == 0 &&
                               (c->factored_vocab * c->num_factored) % 64 == 0,
                           "training step (16-bit): d_model, hidden, T*S and the vocabulary rows must be multiples of 64");
-    GENIE_CHECK_SHAPE(c->S % 16 == 0 && c->head_dim % 16 == 0 && c->d_model % 16 == 0 && c->hidden % 16 == 0 && c->T <= 16,
-                      "training step: S, head_dim, d_model, hidden must be multiples of 16 and T <= 16");
+    GENIE_CHECK_SHAPE(c->S % 16 == 0 && c->head_dim % 16 == 0 && c->d_model % 16 == 0 && c->hidden % 16 == 0 && c->T <= 64,
+                      "training step: S, head_dim, d_model, hidden must be multiples of 16 and T <= 64");
     // the temporal attention backward and the qk-norm kernels of the backward exist for head_dim 32 / 64 only: refuse here,
     // before any forward is launched for a step that cannot finish
     GENIE_CHECK_SHAPE(c->head_dim == 32 || c->head_dim == 64, "training step: head_dim %d is not supported (32 or 64)",
@@ -614,6 +614,21 @@ int genie_train_backward_embed_cond(const genie_cfg* cfg, const genie_weights* g
     if (!act) return GENIE_OK;
     // per-frame sums of dx in w.d1 ((M, d) floats, dead after the last layer's backward; B*T rows needed)
     return launch_action_embed_bwd(*cfg, w.dx, cond->ids, cond->n_actions, B, d_table, beta, w.d1, st);
+}
+
+int genie_temporal_attention_backward(const float* qkv, const float* qk, int64_t qk_ld, const float* d_out,
+                                      float* d_qkv, int B, int T, int S, int d_model, int num_heads, int head_dim,
+                                      float scale, void* stream) {
+    GENIE_CHECK_ARG(qkv && qk && d_out && d_qkv && B > 0, "genie_temporal_attention_backward: NULL argument or B <= 0");
+    GENIE_CHECK_ARG(T > 0 && S > 0 && d_model > 0 && num_heads > 0 && head_dim > 0,
+                    "genie_temporal_attention_backward: T, S, d_model, num_heads, head_dim must be positive");
+    GENIE_CHECK_SHAPE(T <= 64 && (T & (T - 1)) == 0, "genie_temporal_attention_backward: T=%d is not a power of two <= 64", T);
+    GENIE_CHECK_SHAPE((long)head_dim * num_heads == d_model, "genie_temporal_attention_backward: head_dim %d * num_heads %d != d_model %d",
+                      head_dim, num_heads, d_model);
+    GENIE_CHECK_SHAPE(qk_ld == 2L * d_model || qk_ld == 3L * d_model,
+                      "genie_temporal_attention_backward: qk_ld %ld is neither 2*d_model nor 3*d_model", (long)qk_ld);
+    return launch_attn_temporal_bwd(qkv, qk, (long)qk_ld, d_out, d_qkv, B, T, S, d_model, num_heads, head_dim, scale,
+                                    (hipStream_t)stream);
 }
 
 int genie_sumsq(const float* x, size_t n, double* out, double* scratch, void* stream) {

@@ -677,8 +677,8 @@ int genie_rescale_u8_nhwc_bf16(const uint16_t* x, uint8_t* out, int n, int HW, i
  * that gradients far below the f16 normal range keep all 22 bits; a gradient element of magnitude 16 or more saturates there.
  * Every reduction feeding a gradient has a fixed order: results are bit-reproducible run to run.
  * Geometry the step admits (checked by every entry point before anything is enqueued, GENIE_E_SHAPE otherwise): head_dim 32
- * or 64 (head_dim 16 is inference only: the temporal attention backward and the qk-norm backward have no such kernel), T <= 16,
- * S, d_model and hidden multiples of 16; the 16-bit precisions also need d_model, hidden, T * S and the vocabulary rows to be
+ * or 64 (head_dim 16 is inference only: the temporal attention backward and the qk-norm backward have no such kernel), T <= 64
+ * (a power of two, by genie_check_config), S, d_model and hidden multiples of 16; the 16-bit precisions also need d_model, hidden, T * S and the vocabulary rows to be
  * multiples of 64. */
 
 /* Bytes of the saved-activation buffer / of the backward scratch for B clips. */
@@ -722,6 +722,20 @@ int genie_train_backward_embed(const genie_cfg* cfg, const genie_weights* grads,
 int genie_train_backward_embed_cond(const genie_cfg* cfg, const genie_weights* grads, const int64_t* input_ids, int B,
                                     void* workspace, size_t workspace_bytes, int accumulate, void* stream,
                                     float* d_table, const genie_frame_cond* cond);
+
+/* The temporal (causal, over the T frames of one spatial position) attention backward of the step, alone -- the counterpart of
+ * genie_attention_core for the backward; f32 in every precision.  qkv (B,T,S,3*d_model) is the saved q | k | v; qk holds the q | k the
+ * scores were made from, q at column 0 and k at column d_model of rows of qk_ld floats: qkv itself (qk_ld = 3*d_model) or the
+ * qk-norm copies (qk_ld = 2*d_model); d_out (B,T,S,d_model) is d loss / d (attention output).  d_qkv (B,T,S,3*d_model) is
+ * OVERWRITTEN with dq | dk | dv (with qk-norm: the gradients of the normalised q, k):
+ *     p = softmax_j(scale q_i.k_j), j <= i;  dp = d_out_i.v_j;  ds = p (dp - sum_j p dp);
+ *     dq = scale ds K;  dk = scale ds^T Q;  dv = p^T d_out
+ * in a fixed summation order, no atomics: the same bytes run to run.  T <= 64 and a power of two; T = 32 / 64 need head_dim 32
+ * or 64, T <= 16 also admits 128.  NULL pointers or B <= 0: GENIE_E_ARG; T > 64 or not a power of two, head_dim * num_heads !=
+ * d_model, qk_ld not 2*d_model or 3*d_model: GENIE_E_SHAPE -- both before the device or the stream is touched. */
+int genie_temporal_attention_backward(const float* qkv, const float* qk, int64_t qk_ld, const float* d_out,
+                                      float* d_qkv, int B, int T, int S, int d_model, int num_heads, int head_dim,
+                                      float scale, void* stream);
 
 /* *out += sum x[i]^2 in f64, two-stage with a fixed order (scratch: 1024 doubles).  The global gradient norm of
  * clip_grad_norm_ (train.py:628-629) is sqrt of this summed over all gradient buffers. */

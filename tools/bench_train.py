@@ -18,6 +18,7 @@ def main():
     ap.add_argument("--config", default="c138", choices=["c35", "c138"])
     ap.add_argument("--layers", type=int, default=0)
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--T", type=int, default=0, help="frames per clip (default: the config's own 16); 32 and 64 train too")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--breakdown", action="store_true")
@@ -28,6 +29,8 @@ def main():
     cfg.qk_norm = False
     if a.layers:
         cfg.num_layers = a.layers
+    if a.T:
+        cfg.T = a.T
     sd = syn.make_state_dict(cfg, seed=0, law="init")
     model = pkg("st_mask_git").STMaskGIT(cfg, precision=a.precision).load_numpy_state_dict(sd).to("cuda")
     tr = pkg("train").GenieTrainer(model, lr=1e-4, max_grad_norm=1.0)
@@ -52,7 +55,7 @@ def main():
     tokens = a.batch * cfg.T * cfg.S
     n_params = sum(p.numel() for p in model.parameters())
     flops = 6.0 * n_params * tokens  # the reference's own estimate (train.py:543)
-    print(f"{a.config} L={cfg.num_layers} B={a.batch}: {dt*1e3:.1f} ms/step, {tokens/dt:.0f} tokens/s, "
+    print(f"{a.config} L={cfg.num_layers} T={cfg.T} B={a.batch}: {dt*1e3:.1f} ms/step, {tokens/dt:.0f} tokens/s, "
           f"{flops/dt/1e12:.1f} TFLOP/s (6ND), loss {float(out['loss']):.4f}, |g| {float(out['grad_norm']):.4f}, "
           f"acts {tr._acts.numel()/2**30:.1f} GiB, ws {tr._ws.numel()/2**30:.1f} GiB")
     if a.breakdown:

@@ -27,7 +27,8 @@ def parse_args():
     p = argparse.ArgumentParser(description="Train a GENIE spatio-temporal MaskGIT model (MI355X path).")
     p.add_argument("--train_data_dir", type=str, default="data/train_v1.1")
     p.add_argument("--val_data_dir", type=str, default="data/val_v1.1")
-    p.add_argument("--window_size", type=int, default=16)
+    p.add_argument("--window_size", type=int, default=None,
+                   help="frames per clip (default 16); a power of two up to 64.  With --synthetic: overrides the T of the model shape when given")
     p.add_argument("--stride", type=int, default=15)
     p.add_argument("--filter_overlaps", action="store_true")
     p.add_argument("--genie_config", type=str, help="GenieConfig json")
@@ -89,6 +90,8 @@ def main():
                {"c138": cfgmod.c138, "c35": cfgmod.c35,
                 "tiny": lambda: cfgmod.GenieConfig(num_layers=2, num_heads=2, d_model=64, T=4, S=16, num_factored_vocabs=2,
                                                    qk_norm=False, num_prompt_frames=2)}[args.model]())
+        if args.window_size is not None:
+            cfg = cfgmod.GenieConfig(**{**vars(cfg), "T": args.window_size})
         if args.action_dim:
             cfg = cfgmod.GenieConfig(**{**vars(cfg), "action_dim": args.action_dim})
         train_clips = torch.from_numpy(synth.make_clips(args.synthetic, cfg, seed=1))
@@ -106,6 +109,8 @@ def main():
             get_train_acts = lambda idx: train_vecs[idx]  # noqa: E731
             get_eval_acts = lambda idx: train_vecs[: len(eval_clips)][idx]  # noqa: E731
     else:
+        if args.window_size is None:
+            args.window_size = 16
         tds = datamod.RawTokenDataset(args.train_data_dir, window_size=args.window_size, stride=args.stride,
                                       filter_overlaps=args.filter_overlaps)
         eds = datamod.RawTokenDataset(args.val_data_dir, window_size=args.window_size, stride=args.stride,

@@ -7,6 +7,9 @@ p50 / p95 / max over the seeds of the worst-tensor median / max / Frobenius erro
 distance that switching off the spatial-backward rounding points (bwd_*) alone makes on the spatial-attention tensors.
 
     python tools/train_bf16_floor.py [--seeds 100] [--jobs 8] [case ...]
+
+A case is an id of tests/test_hip_train_bf16.py (all of them when none is named), train_shape_dh64, or an id of
+tests/test_hip_train_long_window.py (T = 32 / 64; only when named).
 """
 import argparse
 import os
@@ -26,6 +29,9 @@ METRICS = ("median", "max", "fro", "loss", "norm")
 
 def load(name):
     import test_hip_train_bf16 as T
+    import test_hip_train_long_window as LW
+    if name in LW.CASES:
+        return (T,) + LW.make_case(name)
     if name == "train_shape_dh64":
         from conftest import load_golden
         z, cfg, sd = load_golden(name)
@@ -76,7 +82,7 @@ def main():
             for i, m in enumerate(METRICS):
                 q = np.percentile(d[:, i], [50, 95, 100])
                 print(f"  {m:7s} {q[0]:.2e} / {q[1]:.2e} / {q[2]:.2e}")
-            if T.CASES.get(name, ((0, 0, 0, 256),))[0][3] == 256:
+            if load(name)[1].S == 256:
                 f = bwd16_points(name)
                 print(f"  bwd_* points off, spatial-attention Frobenius: {min(f.values()):.2e} .. {max(f.values()):.2e}")
             sys.stdout.flush()
