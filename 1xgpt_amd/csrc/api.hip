@@ -1,5 +1,5 @@
 // C ABI of libgenie_hip.so (include/genie_hip.h): argument checking, workspace carving and the
-// launch sequences of STBlock / decoder / readout / MaskGIT.  All work is enqueued on the caller's
+// launch sequences of decoder / MaskGIT / generate (the layer itself and the readout: st_block.hip).  All work is enqueued on the caller's
 // stream; nothing here allocates, synchronises or touches the host-side of any tensor.
 #include <math.h>
 #include <stdarg.h>
@@ -58,7 +58,7 @@ static Workspace carve(const genie_cfg& c, int B, void* base) {
     w.x = (float*)take(M * c.d_model * 4);
     w.xn = take(M * c.d_model * 4);
     w.big = take(M * wide * 4);
-    // w.logits doubles as the (M, d) f32 scratch of the 16-bit blocks' generic attention path (kernels_bf16.hip): V < d happens
+    // w.logits doubles as the (M, d) f32 scratch of the 16-bit blocks' generic attention path (st_block.hip): V < d happens
     w.logits = (float*)take(M * (V > (size_t)c.d_model ? V : (size_t)c.d_model) * 4);
     w.samples = (int64_t*)take((size_t)B * c.S * 8);
     w.conf = (float*)take((size_t)B * c.S * 4);
@@ -108,101 +108,19 @@ static int check_ws(const genie_cfg& c, int B, void* ws, size_t bytes) {
     return GENIE_OK;
 }
 
-// ---- temporal attention behind the qkv GEMM, shared by the three drivers (kernels.hpp)
-int temporal_attention(const genie_cfg& c, const genie_attn_weights& aw, const BlockPass& p, const TemporalQkv& tq, float* out,
-                       uint16_t* out16, size_t plane, bool in16, Workspace& w, int B, hipStream_t st) {
-    const int d = c.d_model, H = c.num_heads, Dh = c.head_dim;
-    const float* nw = c.qk_norm ? aw.norm_w : nullptr;
-    const float* nb = c.qk_norm ? aw.norm_b : nullptr;
-    if (p.is_decode())  // the GEMM filled cache slot frame_t: attend slots 0..frame_t
-        return launch_attn_temporal_single(p.cache, out, B, p.frame_T, c.S, p.frame_t, d, H, Dh, c.attn_scale, nw, nb, st, out16, plane,
-                                           in16);
-    const float* qkv = tq.base;
-    float* tmp = out16 ? w.logits : out;  // where a kernel without a 16-bit epilogue writes its f32 rows
-    if (p.reads_cache()) {
-        const int rc = launch_attn_temporal_prefix(qkv, p.cache, out, B, c.T, c.S, d, H, Dh, c.attn_scale, nw, nb, st, out16, plane,
-                                                   p.tshift, in16);
-        if (rc != GENIE_E_UNSUPPORTED || !out16 || in16) return rc;
-        GENIE_TRY(launch_attn_temporal_prefix(qkv, p.cache, tmp, B, c.T, c.S, d, H, Dh, c.attn_scale, nw, nb, st, nullptr, 0, p.tshift));
-    } else {
-        const int Tq = p.tq_stride(c.T);
-        const int rc = launch_attn_temporal_f32_mfma(qkv, out, B, c.T, c.S, d, H, Dh, c.attn_scale, nw, nb, st, out16, plane, Tq, in16);
-        if (rc != GENIE_E_UNSUPPORTED || in16) return rc;
-        if (Tq != c.T && B > 1) {  // no MFMA instantiation for this geometry, and the generic kernel reads dense clips only
-            set_error("strided temporal qkv needs the MFMA temporal kernel (8 <= frames <= 16)");
-            return out16 ? GENIE_E_ARG : GENIE_E_UNSUPPORTED;  // (the codes the 16-bit drivers and the exact one have always returned here)
-        }
-        GENIE_TRY(launch_attn_generic(qkv, tmp, c.T, (long)B * c.S, c.S, (long)c.T * c.S, 1, c.S, d, H, Dh, c.attn_scale, 1, nw, nb, st));
-    }
-    return out16 ? launch_to_operand16(tmp, out16, plane, (size_t)B * c.T * c.S * d, st) : GENIE_OK;
-}
-
-// ---- one SelfAttention + residual: x += proj(attn(qkv(u)))  (attention.py:36-61, st_transformer.py:74,78)
-static int attention_block(const genie_cfg& c, const genie_attn_weights& aw, const float* u, float* x, Workspace& w, const BlockPass& p,
-                           int B, bool temporal, hipStream_t st) {
-    const int d = c.d_model, M = B * c.T * c.S;
-    float* ao = (float*)w.xn;  // u may alias w.xn: it is dead once qkv is computed
-    const float* bias = c.qkv_bias ? aw.qkv_b : nullptr;
-    if (temporal) {
-        const TemporalQkv tq = temporal_qkv_target(c, p, (float*)w.big, B);
-        GENIE_TRY(launch_gemm_f32(u, d, tq.strideA, aw.qkv_w, d, 0, bias, tq.base + tq.off, 3 * d, tq.strideC, tq.rows, 3 * d, d,
-                                  tq.batch, 0, 1.0f, st));
-        if (p.stop_after_tqkv) return GENIE_OK;
-        GENIE_TRY(temporal_attention(c, aw, p, tq, ao, nullptr, 0, false, w, B, st));
-    } else {
-        float* qkv = (float*)w.big;
-        const float* nw = c.qk_norm ? aw.norm_w : nullptr;
-        const float* nb = c.qk_norm ? aw.norm_b : nullptr;
-        GENIE_TRY(launch_gemm_f32(u, d, 0, aw.qkv_w, d, 0, bias, qkv, 3 * d, 0, M, 3 * d, d, 1, 0, 1.0f, st));
-        int rc = launch_attn_spatial_f32_mfma(qkv, ao, c.S, (long)B * c.T, d, c.num_heads, c.head_dim, c.attn_scale, nw, nb, st);
-        if (rc == GENIE_E_UNSUPPORTED)  // no MFMA instantiation for this geometry: generic kernel
-            rc = launch_attn_generic(qkv, ao, c.S, (long)B * c.T, 1, c.S, 0, 1, d, c.num_heads, c.head_dim, c.attn_scale, 0, nw, nb, st);
-        GENIE_TRY(rc);
-    }
-    return launch_gemm_f32(ao, d, 0, aw.proj_w, d, 0, c.proj_bias ? aw.proj_b : nullptr, x, d, 0, M, d, d, 1, GEMM_ACCUM, 1.0f, st);
-}
-
-int st_block_exact(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, const BlockPass& p, int B, hipStream_t st) {
-    const int d = c.d_model, M = B * c.T * c.S;
-    float* xn = (float*)w.xn;
-    // spatial: x += SpAttn(norm1(x))  (st_transformer.py:73-74)
-    const float* u = x;
-    if (!c.qk_norm) {
-        GENIE_TRY(launch_layer_norm(x, lw.norm1_w, lw.norm1_b, xn, M, d, 1e-5f, st));
-        u = xn;
-    }
-    GENIE_TRY(attention_block(c, lw.spatial, u, x, w, p, B, false, st));
-    // temporal: x += TmpAttn(x, causal), no pre-norm  (st_transformer.py:77-78)
-    GENIE_TRY(attention_block(c, lw.temporal, x, x, w, p, B, true, st));
-    if (p.stop_after_tqkv) return GENIE_OK;
-    // MLP: x += fc2(gelu(fc1(norm2(x))))  (st_transformer.py:81, 16-25)
-    u = x;
-    if (!c.qk_norm) {
-        GENIE_TRY(launch_layer_norm(x, lw.norm2_w, lw.norm2_b, xn, M, d, 1e-5f, st));
-        u = xn;
-    }
-    float* hid = (float*)w.big;
-    GENIE_TRY(launch_gemm_f32(u, d, 0, lw.fc1_w, d, 0, c.mlp_bias ? lw.fc1_b : nullptr, hid, c.hidden, 0, M, c.hidden,
-                              d, 1, GEMM_GELU, 1.0f, st));
-    GENIE_TRY(launch_gemm_f32(hid, c.hidden, 0, lw.fc2_w, c.hidden, 0, c.mlp_bias ? lw.fc2_b : nullptr, x, d, 0, M, d,
-                              c.hidden, 1, GEMM_ACCUM, 1.0f, st));
-    return GENIE_OK;
-}
-
 // The layer loop of every pass: what runs in front of the first block, then `n` blocks, block i as the pass `make(i, next)` says
 // (next = the block behind it, NULL after the last).  The hand-offs between consecutive blocks live and die here.
 template <class MakePass>
 static int run_layers(const genie_cfg& c, const genie_layer_weights* layers, int n, float* x, Workspace& w, int B, hipStream_t st,
                       MakePass make) {
-    if (c.precision == GENIE_PREC_BF16) GENIE_TRY(prepare_bf16(c, x, w, B, st));
-    if (c.precision == GENIE_PREC_F16X3) GENIE_TRY(prepare_f16x3(c, x, w, B, st));
+    const bool exact = c.precision == GENIE_PREC_EXACT;   // else a 16-bit precision: one driver for both (st_block.hip)
+    if (!exact) GENIE_TRY(prepare16(c, x, w, B, st));
     BlockCarry carry;
     for (int i = 0; i < n; ++i) {
         const BlockPass p = make(i, i + 1 < n ? &layers[i + 1] : nullptr);
         GENIE_STUDY_LAYER(i);
-        if (c.precision == GENIE_PREC_BF16) GENIE_TRY(st_block_bf16(c, layers[i], x, w, p, carry, B, st));
-        else if (c.precision == GENIE_PREC_F16X3) GENIE_TRY(st_block_f16x3(c, layers[i], x, w, p, B, st));
-        else GENIE_TRY(st_block_exact(c, layers[i], x, w, p, B, st));
+        if (exact) GENIE_TRY(st_block_exact(c, layers[i], x, w, p, B, st));
+        else GENIE_TRY(st_block16(c, layers[i], x, w, p, carry, B, st));
     }
     return GENIE_OK;
 }
@@ -210,23 +128,6 @@ static int run_layers(const genie_cfg& c, const genie_layer_weights* layers, int
 static int decoder(const genie_cfg& c, const genie_weights& wt, float* x, Workspace& w, int B, hipStream_t st) {
     return run_layers(c, wt.layers_host, c.num_layers, x, w, B, st,
                       [&](int, const genie_layer_weights* next) { return BlockPass::plain(c, next, c.T); });
-}
-
-// out_x_proj on frames [t0,t1): token-major (B,nt,S,V) or BCTHW (B,V,nt,S) via the operand-swapped GEMM
-static int readout(const genie_cfg& c, const genie_weights& wt, const float* x, Workspace& w, int B, int t0, int t1,
-                   int layout, float* logits, hipStream_t st) {
-    if (c.precision == GENIE_PREC_BF16) return readout_bf16(c, wt, x, w, B, t0, t1, layout, logits, st);
-    if (c.precision == GENIE_PREC_F16X3) return readout_f16x3(c, wt, x, w, B, t0, t1, layout, logits, st);
-    const int d = c.d_model, nt = t1 - t0, V = c.factored_vocab * c.num_factored;
-    const long rows = (long)nt * c.S;
-    const float* xa = x + (size_t)t0 * c.S * d;
-    const long strideX = (long)c.T * c.S * d;
-    if (layout == GENIE_LAYOUT_TOKEN_MAJOR) {
-        return launch_gemm_f32(xa, d, strideX, wt.out_w, d, 0, wt.out_b, logits, V, rows * V, (int)rows, V, d, B, 0,
-                               c.readout_mult, st);
-    }
-    return launch_gemm_f32(wt.out_w, d, 0, xa, d, strideX, wt.out_b, logits, rows, rows * V, V, (int)rows, d, B,
-                           GEMM_BIAS_ALONG_M, c.readout_mult, st);
 }
 
 static int mask_count(int step, int steps, int S) {

@@ -1,4 +1,5 @@
-// Host-side launchers of the gfx950 kernels (implemented in kernels_exact.hip / kernels_bf16.hip).
+// Host-side launchers of the gfx950 kernels (one block of declarations per kernels_*.hip file) and the pass / workspace types of the
+// layer drivers (st_block.hip, kernels_frame.hip), which api.hip's entry points and loops call.
 #pragma once
 #include "common.hpp"
 
@@ -6,7 +7,7 @@ namespace genie {
 
 enum { GEMM_GELU = 1, GEMM_ACCUM = 2, GEMM_BIAS_ALONG_M = 4 };
 
-// Workspace carving shared by api.hip and the precision-specific layer drivers (see carve() in api.hip): buffers only.  What kind of
+// Workspace carving shared by api.hip and the layer drivers (see carve() in api.hip): buffers only.  What kind of
 // pass a layer call belongs to is a BlockPass, what one block hands to the next a BlockCarry (both below).
 struct Workspace {
     float* x;          // (M, d)   residual stream, f32 in every precision; offset 0 of the workspace
@@ -299,9 +300,17 @@ int launch_cast_rows16(const float* in, long ld, const float* z, uint16_t* out16
 int launch_wgrad16_tn(const uint16_t* dY, long ldy, const uint16_t* X, long ldx, float* dW, int Mtok, int N, int K, float alpha,
                       float beta, float* slabs, size_t slab_floats, hipStream_t st);
 int launch_cast16(int npl, const float* src, uint16_t* dst, size_t n, hipStream_t st);
-enum { G16X_GELU = 1, G16X_ACCUM = 2, G16X_OUT16 = 4, G16X_OUTF32 = 8, G16X_GELU16 = 16, G16X_NT = 32,
+// The flags of the 16-bit GEMMs (launch_gemm16_ex and the launchers behind it), the one vocabulary of kernels and drivers
+enum { G16X_GELU = 1, G16X_ACCUM = 2, G16X_OUT16 = 4, G16X_OUTF32 = 8,
+       G16X_GELU16 = 16 /* GELU on the 16-bit output only (bf16: gelu16_2 polynomial): Cf keeps the pre-activation (training forward) */,
+       G16X_NT = 32 /* non-temporal output stores: the output is larger than the on-die caches (set by the launchers) */,
        G16X_QKV = 64 /* gemm16_pp only: the spatial-attention operand layout, see launch_gemm16_pp */,
-       G16X_QKNORM = 128 /* with G16X_QKV: q and k leave through the per-head LayerNorm (qn_g, qn_b; attention.py:31-34, 42-47) */ };  // = the G16_* flags of kernels_bf16.hip
+       G16X_QKNORM = 128 /* with G16X_QKV: q and k leave through the per-head LayerNorm (qn_g, qn_b; attention.py:31-34, 42-47) */,
+       // launch_gemm16_ex only: read and stripped there, they never reach a kernel
+       G16X_WIDEW = 1024 /* f16x3: W is not a |w| < 32 weight matrix (a `w16_wide` tensor of genie_hip.h, or an activation / gradient
+                            operand of the training step): keep it off the 2^11-scaling single-accumulator kernel (gemm16_pp) */,
+       G16X_NOSM = 2048 /* not the in-workgroup split-K kernel of small problems (gemm16_sm): the caller splits K itself, or promises a
+                           sum order that does not depend on the problem size */ };
 int launch_gemm16_ex(int npl, const uint16_t* A, long lda, long planeA, const uint16_t* W, long ldw, long planeW,
                      const float* bias, const float* Rf, float* Cf, uint16_t* C16, long plane16, long ldc, int M, int N,
                      int K, int flags, float alpha, hipStream_t st, int batch, long strideA, long strideW, long strideC);
@@ -333,18 +342,17 @@ int readout_frame_f16x3(const genie_cfg& c, const genie_weights& wt, Workspace& 
 // kernels_attn_dma.hip: spatial attention over the operand planes written by launch_gemm16_pp(G16X_OUT16 | G16X_QKV)
 int launch_attn_spatial_dma(int npl, const uint16_t* qkv16, long n_seq, int d, int H, int Dh, uint16_t* out16, size_t out_plane,
                             hipStream_t st);
-// The layer drivers, one per precision (api.hip: exact; kernels_bf16.hip: the two 16-bit ones), what runs in front of the first layer
-// and behind the last one, and the 16-bit Linear entries of the C ABI.
+// st_block.hip: the layer drivers (exact; 16-bit = GENIE_PREC_BF16 or GENIE_PREC_F16X3 by c.precision), what runs in front of the first
+// 16-bit layer and the readout behind the last one (all three precisions)
 int st_block_exact(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, const BlockPass& p, int B, hipStream_t st);
-int st_block_bf16(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, const BlockPass& p, BlockCarry& carry, int B,
-                  hipStream_t st);
-int st_block_f16x3(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, const BlockPass& p, int B, hipStream_t st);
-int prepare_bf16(const genie_cfg& c, const float* x, Workspace& w, int B, hipStream_t st);
-int prepare_f16x3(const genie_cfg& c, const float* x, Workspace& w, int B, hipStream_t st);
-int readout_bf16(const genie_cfg& c, const genie_weights& wt, const float* x, Workspace& w, int B, int t0, int t1, int layout,
-                 float* logits, hipStream_t st);
-int readout_f16x3(const genie_cfg& c, const genie_weights& wt, const float* x, Workspace& w, int B, int t0, int t1, int layout,
-                  float* logits, hipStream_t st);
+int st_block16(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, const BlockPass& p, BlockCarry& carry, int B,
+               hipStream_t st);
+int prepare16(const genie_cfg& c, const float* x, Workspace& w, int B, hipStream_t st);
+int readout(const genie_cfg& c, const genie_weights& wt, const float* x, Workspace& w, int B, int t0, int t1, int layout, float* logits,
+            hipStream_t st);
+// kernels_bf16.hip: elementwise steps of those drivers, and the 16-bit Linear entries of the C ABI
+int launch_splitk2_residual(float* x, const float* s0, const float* s1, const float* bias, size_t n4, int N, hipStream_t st);
+int launch_shadow_bf16(const float* src, uint16_t* dst, size_t n, hipStream_t st);
 int launch_pack_split(const float* src, uint16_t* dst, size_t n, hipStream_t st);
 int launch_linear_lowp(int precision, const uint16_t* x16, const uint16_t* W16, const float* b, float* y, int M, int N, int K, int gelu,
                        int accumulate, hipStream_t st);
@@ -373,7 +381,7 @@ inline TemporalQkv temporal_qkv_target(const genie_cfg& c, const BlockPass& p, f
 inline int launch_to_operand16(const float* src, uint16_t* out16, size_t plane, size_t n, hipStream_t st) {
     return plane ? launch_split_f16(src, out16, plane, n, st) : launch_pack_bf16(src, out16, n, st);
 }
-// Temporal attention behind that GEMM, for all three drivers: decode slot / prefix / f32-MFMA / generic kernel.  The result leaves as
+// Temporal attention behind that GEMM (st_block.hip), for all drivers: decode slot / prefix / f32-MFMA / generic kernel.  The result leaves as
 // f32 rows (out) or, out16 != NULL, 16-bit: bf16 (plane == 0) or f16 split planes (hi at out16, lo at out16 + plane); a kernel that
 // cannot write 16-bit writes f32 into w.logits and a convert follows.  in16: the qkv and the cache hold bf16 (temporal_qkv16).
 int temporal_attention(const genie_cfg& c, const genie_attn_weights& aw, const BlockPass& p, const TemporalQkv& tq, float* out,

@@ -1,4 +1,5 @@
-// 16-bit matrix-core path of the GENIE forward for gfx950.
+// The 16-bit GEMM of the 128x128 / 256x128 tiles for gfx950 and its launcher (launch_gemm16: the dispatch over this file's kernels,
+// gemm16_pp and gemm16_sm), plus the 16-bit Linear entries of the C ABI.  The layer drivers that call it: st_block.hip, train_api.hip.
 //
 // gemm16_nt_kernel<NPL, BK>:  C[M,N] (+)= epilogue( alpha * A[M,K] . W[N,K]^T + bias ) on v_mfma_f32_32x32x16
 //   NPL = 1  operands are bf16 (one product)                     -> GENIE_PREC_BF16, the throughput mode
@@ -22,12 +23,6 @@ namespace genie {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-enum { G16_GELU = 1, G16_ACCUM = 2, G16_OUT16 = 4, G16_OUTF32 = 8,
-       G16_GELU16 = 16, /* GELU on the 16-bit output only (bf16: gelu16_2 polynomial): Cf keeps the pre-activation (training forward) */
-       G16_NT = 32,     /* non-temporal output stores: the output is larger than the on-die caches (launcher) */
-       G16_WIDEW = 1024 /* launcher only (never reaches a kernel): the f16x3 weight's hi plane reaches |w| >= 32 -> not the
-                           2^11-scaling single-accumulator kernel (the `w16_wide` flags of genie_hip.h) */ };
 
 constexpr float SPLIT_INV = 1.0f / 2048.0f;
 
@@ -81,7 +76,7 @@ __global__ __launch_bounds__(256, 2) void gemm16_nt_kernel(const uint16_t* __res
     W += (size_t)blockIdx.y * strideW;
     if (Cf) Cf += (size_t)blockIdx.y * strideC;
     if (C16) C16 += (size_t)blockIdx.y * strideC;
-    // residual source of G16_ACCUM: Cf itself (in place) unless the caller keeps the input (training: Rf != Cf)
+    // residual source of G16X_ACCUM: Cf itself (in place) unless the caller keeps the input (training: Rf != Cf)
     const float* Rsrc = Rf ? Rf + (size_t)blockIdx.y * strideC : Cf;
 
     // ---- staging addresses: wave w moves chunks w*NCHUNK/4 .. of every plane tile
@@ -197,8 +192,8 @@ __global__ __launch_bounds__(256, 2) void gemm16_nt_kernel(const uint16_t* __res
                 if constexpr (NPL == 2) v += corr[i][j][e] * SPLIT_INV;
                 ct[(i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h) * 64 + j * 32 + r] = v;
             }
-    const bool do_gelu = flags & G16_GELU, do_acc = flags & G16_ACCUM;
-    const bool out16 = flags & G16_OUT16, outf = flags & G16_OUTF32;
+    const bool do_gelu = flags & G16X_GELU, do_acc = flags & G16X_ACCUM;
+    const bool out16 = flags & G16X_OUT16, outf = flags & G16X_OUTF32;
     const bool vec = ((N | (int)ldc) & 3) == 0;
     const int c4 = (lane & 15) << 2;
     const int col = n0 + wn * 64 + c4;
@@ -224,7 +219,7 @@ __global__ __launch_bounds__(256, 2) void gemm16_nt_kernel(const uint16_t* __res
     auto store_row = [&](int row, float4 v) {
         const size_t idx = (size_t)row * ldc + col;
         if (outf) {
-            if (flags & G16_NT) {
+            if (flags & G16X_NT) {
                 ef4 t = {v.x, v.y, v.z, v.w};
                 __builtin_nontemporal_store(t, reinterpret_cast<ef4*>(Cf + idx));
             } else {
@@ -232,7 +227,7 @@ __global__ __launch_bounds__(256, 2) void gemm16_nt_kernel(const uint16_t* __res
             }
         }
         if (out16) {
-            if (flags & G16_GELU16) {   // bf16: the polynomial form, as in gemm16_pp (the hidden must not depend on the tile kernel)
+            if (flags & G16X_GELU16) {   // bf16: the polynomial form, as in gemm16_pp (the hidden must not depend on the tile kernel)
                 const genie_f2 g0 = gelu16_2<NPL == 1>(genie_f2{v.x, v.y}), g1 = gelu16_2<NPL == 1>(genie_f2{v.z, v.w});
                 v.x = g0[0]; v.y = g0[1]; v.z = g1[0]; v.w = g1[1];
             }
@@ -290,7 +285,7 @@ __global__ __launch_bounds__(256, 2) void gemm16_nt_kernel(const uint16_t* __res
                 const size_t idx = (size_t)row * ldc + col + c;
                 if (do_acc) v += Rsrc[idx];
                 if (outf) Cf[idx] = v;
-                if (out16) store16<NPL>(C16, (size_t)plane16, idx, (flags & G16_GELU16) ? gelu16_1<NPL == 1>(v) : v);
+                if (out16) store16<NPL>(C16, (size_t)plane16, idx, (flags & G16X_GELU16) ? gelu16_1<NPL == 1>(v) : v);
             }
         }
     }
@@ -351,7 +346,7 @@ __global__ __launch_bounds__(256 * NWN, 1) void gemm16_v2_kernel(const uint16_t*
     W += (size_t)blockIdx.y * strideW;
     if (Cf) Cf += (size_t)blockIdx.y * strideC;
     if (C16) C16 += (size_t)blockIdx.y * strideC;
-    // residual source of G16_ACCUM: Cf itself (in place) unless the caller keeps the input (training: Rf != Cf)
+    // residual source of G16X_ACCUM: Cf itself (in place) unless the caller keeps the input (training: Rf != Cf)
     const float* Rsrc = Rf ? Rf + (size_t)blockIdx.y * strideC : Cf;
 
     // ---- staging: chunk c = wid + 8*i of the stage image [A pl0 .. | W pl0 ..]
@@ -515,8 +510,8 @@ __global__ __launch_bounds__(256 * NWN, 1) void gemm16_v2_kernel(const uint16_t*
     // store and the 16-bit operand store.
     __syncthreads();  // every wave is done with the stage buffers (and has drained its loads)
     float* ct = reinterpret_cast<float*>(smem) + wid * (RR * WN_COLS);
-    const bool do_gelu = flags & G16_GELU, do_acc = flags & G16_ACCUM;
-    const bool out16 = flags & G16_OUT16, outf = flags & G16_OUTF32;
+    const bool do_gelu = flags & G16X_GELU, do_acc = flags & G16X_ACCUM;
+    const bool out16 = flags & G16X_OUT16, outf = flags & G16X_OUTF32;
     constexpr int LPR = WN_COLS / 4;  // lanes per row (float4 each)
     constexpr int RPI = 64 / LPR;     // rows per wave-instruction
     const int c4 = (lane % LPR) << 2;
@@ -559,7 +554,7 @@ __global__ __launch_bounds__(256 * NWN, 1) void gemm16_v2_kernel(const uint16_t*
     auto store_row = [&](int row, float4 v) {
         const size_t idx = (size_t)row * ldc + col;
         if (outf) {
-            if (flags & G16_NT) {
+            if (flags & G16X_NT) {
                 typedef float nt4 __attribute__((ext_vector_type(4)));
                 nt4 t = {v.x, v.y, v.z, v.w};
                 __builtin_nontemporal_store(t, reinterpret_cast<nt4*>(Cf + idx));
@@ -568,7 +563,7 @@ __global__ __launch_bounds__(256 * NWN, 1) void gemm16_v2_kernel(const uint16_t*
             }
         }
         if (out16) {
-            if (flags & G16_GELU16) {   // bf16: the polynomial form, as in gemm16_pp (the hidden must not depend on the tile kernel)
+            if (flags & G16X_GELU16) {   // bf16: the polynomial form, as in gemm16_pp (the hidden must not depend on the tile kernel)
                 const genie_f2 g0 = gelu16_2<NPL == 1>(genie_f2{v.x, v.y}), g1 = gelu16_2<NPL == 1>(genie_f2{v.z, v.w});
                 v.x = g0[0]; v.y = g0[1]; v.z = g1[0]; v.w = g1[1];
             }
@@ -576,15 +571,15 @@ __global__ __launch_bounds__(256 * NWN, 1) void gemm16_v2_kernel(const uint16_t*
                 uint2 pk;
                 pk.x = (uint32_t)f32_to_bf16(v.x) | ((uint32_t)f32_to_bf16(v.y) << 16);
                 pk.y = (uint32_t)f32_to_bf16(v.z) | ((uint32_t)f32_to_bf16(v.w) << 16);
-                store_u2(C16 + idx, pk, flags & G16_NT);
+                store_u2(C16 + idx, pk, flags & G16X_NT);
             } else {
                 uint16_t h0, l0, h1, l1, h2, l2, h3, l3;
                 split_f16(v.x, h0, l0); split_f16(v.y, h1, l1); split_f16(v.z, h2, l2); split_f16(v.w, h3, l3);
                 uint2 ph, pl;
                 ph.x = (uint32_t)h0 | ((uint32_t)h1 << 16); ph.y = (uint32_t)h2 | ((uint32_t)h3 << 16);
                 pl.x = (uint32_t)l0 | ((uint32_t)l1 << 16); pl.y = (uint32_t)l2 | ((uint32_t)l3 << 16);
-                store_u2(C16 + idx, ph, flags & G16_NT);
-                store_u2(C16 + (size_t)plane16 + idx, pl, flags & G16_NT);
+                store_u2(C16 + idx, ph, flags & G16X_NT);
+                store_u2(C16 + (size_t)plane16 + idx, pl, flags & G16X_NT);
             }
         }
     };
@@ -636,7 +631,7 @@ __global__ __launch_bounds__(256 * NWN, 1) void gemm16_v2_kernel(const uint16_t*
 
 // Weight tensors whose packed hi plane reaches |w| >= 32 (the `w16_wide` flags of the weight structs, genie_hip.h): the
 // single-accumulator split GEMM (gemm16_pp) multiplies the hi plane by 2^11 in f16, exact below 32 only, so the layer drivers pass
-// weights_on_w = false for these and they run on the two-accumulator kernels (gemm16_v2 / gemm16_nt / gemm16_sm: hi.hi and the
+// G16X_WIDEW for these and they run on the two-accumulator kernels (gemm16_v2 / gemm16_nt / gemm16_sm: hi.hi and the
 // cross terms in separate accumulators, no operand scaling; limit = the f16 range).
 
 #ifdef GENIE_STUDY
@@ -657,18 +652,20 @@ template <int NPL>
 static int launch_gemm16(const uint16_t* A, long lda, long planeA, const uint16_t* W, long ldw, long planeW,
                          const float* bias, float* Cf, uint16_t* C16, long plane16, long ldc, int M, int N, int K,
                          int flags, float alpha, hipStream_t st, int batch = 1, long strideA = 0, long strideC = 0,
-                         const float* Rf = nullptr, long strideW = 0, bool weights_on_w = true, bool allow_sm = true) {
+                         const float* Rf = nullptr, long strideW = 0) {
     constexpr int BK = NPL == 1 ? 64 : 32;
     GENIE_CHECK_SHAPE(K % BK == 0 && K > 0, "gemm16: K=%d must be a positive multiple of %d", K, BK);
     GENIE_CHECK_SHAPE(lda % 8 == 0 && ldw % 8 == 0, "gemm16: leading dims must be multiples of 8 elements");
     if (M <= 0 || N <= 0) return GENIE_OK;
-    if (flags & G16_WIDEW) { weights_on_w = false; flags &= ~G16_WIDEW; }
+    // the launcher-only flags never reach a kernel
+    const bool weights_on_w = !(flags & G16X_WIDEW), allow_sm = !(flags & G16X_NOSM);
+    flags &= ~(G16X_WIDEW | G16X_NOSM);
     const double mn = (double)M * N * batch;
     {   // outputs that cannot stay in the 256 MB Infinity Cache anyway are stored non-temporally: +10..18 % on the
         // K = 512 GEMMs at >= 8 clips (they no longer evict the A panel / weights they share the L2 with)
         static const int nt_mode = study_env("GENIE_GEMM16_NT", -1);
-        const double out_bytes = mn * ((flags & G16_OUTF32 ? 4 : 0) + (flags & G16_OUT16 ? 2 * NPL : 0));
-        if (nt_mode == 1 || (nt_mode < 0 && out_bytes >= 192e6)) flags |= G16_NT;
+        const double out_bytes = mn * ((flags & G16X_OUTF32 ? 4 : 0) + (flags & G16X_OUT16 ? 2 * NPL : 0));
+        if (nt_mode == 1 || (nt_mode < 0 && out_bytes >= 192e6)) flags |= G16X_NT;
     }
     {   // the 256x256 phase-scheduled kernel (kernels_gemm_pp.hip) takes every problem that fills the chip with its tiles.
         // Its split-f16 form multiplies the W operand's hi plane by 2^11 in registers, so W must be a weight matrix
@@ -701,8 +698,8 @@ static int launch_gemm16(const uint16_t* A, long lda, long planeA, const uint16_
         const size_t lds2 = 3 * 48 * 1024;
         ProfScope prof(GENIE_KC_GEMM, 2.0 * mn * K,
                        2.0 * NPL * ((double)M * K * batch + (double)N * K) +
-                           mn * ((flags & G16_ACCUM ? 4 : 0) + (flags & G16_OUTF32 ? 4 : 0) +
-                                 (flags & G16_OUT16 ? 2 * NPL : 0)),
+                           mn * ((flags & G16X_ACCUM ? 4 : 0) + (flags & G16X_OUTF32 ? 4 : 0) +
+                                 (flags & G16X_OUT16 ? 2 * NPL : 0)),
                        st, NPL == 2 ? "gemm16_v2_kernel<2,...> (256x128 tile, f16x3 two-accumulator form)" : "gemm16_v2_kernel<1,...> (256x128 / 256x256 tile, bf16)");
         static const int nwn = study_env("GENIE_GEMM16_NWN", 4);
         static const int big = study_env("GENIE_GEMM16_BN256", 1);
@@ -742,7 +739,7 @@ static int launch_gemm16(const uint16_t* A, long lda, long planeA, const uint16_
     const size_t lds = (size_t)2 * 2 * NPL * 128 * BK * 2;
     ProfScope prof(GENIE_KC_GEMM, 2.0 * mn * K,
                    2.0 * NPL * ((double)M * K * batch + (double)N * K) +
-                       mn * ((flags & G16_ACCUM ? 4 : 0) + (flags & G16_OUTF32 ? 4 : 0) + (flags & G16_OUT16 ? 2 * NPL : 0)),
+                       mn * ((flags & G16X_ACCUM ? 4 : 0) + (flags & G16X_OUTF32 ? 4 : 0) + (flags & G16X_OUT16 ? 2 * NPL : 0)),
                    st, NPL == 2 ? "gemm16_nt_kernel<2,...> (128x128 tile, f16x3)" : "gemm16_nt_kernel<1,...> (128x128 tile, bf16)");
     // Problems this small (batch-1 generate: a GEMM is 21..36 us) are bound by the serial chain of K-steps -- each one a
     // barrier plus an L2 round trip -- not by throughput, and fewer workgroups than CUs are resident anyway: double the
@@ -765,8 +762,8 @@ static int launch_gemm16(const uint16_t* A, long lda, long planeA, const uint16_
     return GENIE_OK;
 }
 
-// Non-template entry for the training step (kernels_train16.hip): npl = 1 bf16, 2 = f16 split planes.
-//   Rf: residual source when it must differ from Cf (G16_ACCUM);  batch > 1 strides A, W and C (split-K slabs:
+// Non-template entry for the layer drivers (st_block.hip, train_api.hip): npl = 1 bf16, 2 = f16 split planes.
+//   Rf: residual source when it must differ from Cf (G16X_ACCUM);  batch > 1 strides A, W and C (split-K slabs:
 //   strideA = strideW = K elements of one slab, strideC = M*N)
 int launch_gemm16_ex(int npl, const uint16_t* A, long lda, long planeA, const uint16_t* W, long ldw, long planeW,
                      const float* bias, const float* Rf, float* Cf, uint16_t* C16, long plane16, long ldc, int M, int N,
@@ -775,14 +772,10 @@ int launch_gemm16_ex(int npl, const uint16_t* A, long lda, long planeA, const ui
         return launch_gemm16<1>(A, lda, planeA, W, ldw, planeW, bias, Cf, C16, plane16, ldc, M, N, K, flags, alpha, st,
                                 batch, strideA, strideC, Rf, strideW);
     return launch_gemm16<2>(A, lda, planeA, W, ldw, planeW, bias, Cf, C16, plane16, ldc, M, N, K, flags, alpha, st, batch,
-                            strideA, strideC, Rf, strideW, /*weights_on_w=*/false);
+                            strideA, strideC, Rf, strideW);
 }
 
-// ---- fc2 of the one-frame passes at 2,048-4,096 rows (generate at 8-16 clips): N = d = 512 gives 64-128 tiles of 128x128 for a
-// K = 2,048 contraction -- half of the CUs idle and a 64-step K chain.  Split K in two over the GEMM's batch index (256 workgroups,
-// 32 steps each) into two f32 slabs in the (idle) logits scratch, then x += bias + slab0 + slab1 in that fixed order
-// (profiles/r03_fc2_splitk_ab.txt).  Only in the one-frame passes of generate (a DECODE pass) and only when the 16-bit shadow of x is
-// not wanted (every layer but the last of a LayerNorm model): full forwards keep the single fused K chain at every batch size.
+// x += bias + s0 + s1 in that fixed order: the residual step behind a two-slab split-K fc2 (fc2_splitk2, st_block.hip)
 __global__ __launch_bounds__(256) void splitk2_residual_kernel(float* __restrict__ x, const float* __restrict__ s0,
                                                                const float* __restrict__ s1, const float* __restrict__ bias,
                                                                size_t n4, int N) {
@@ -796,23 +789,8 @@ __global__ __launch_bounds__(256) void splitk2_residual_kernel(float* __restrict
     v = v + ((a + bv) + b);
     reinterpret_cast<sk4*>(x)[i] = v;
 }
-// returns GENIE_E_UNSUPPORTED when the shape is not in that range (the caller then runs the fused-epilogue GEMM)
-template <int NPL>
-static int fc2_splitk2(const genie_cfg& c, const uint16_t* h16, long plane_h, const uint16_t* w16, long plane_w, const float* bias,
-                       float* x, Workspace& w, const BlockPass& p, int M, hipStream_t st, bool wide = false) {
-    static const int on = study_env("GENIE_FC2_SPLITK", 1);
-    const int d = c.d_model, K = c.hidden;
-    const long tiles = (long)((M + 127) / 128) * ((d + 127) / 128);
-    const size_t V = (size_t)c.factored_vocab * c.num_factored;
-    if (!on || !p.is_decode() /* one-frame passes only: a clip's fc2 sum order must not depend on the batch size of a full forward */ ||
-        !p.next_is_ln || !w.logits || K < 2048 || K % 256 || d % 4 || tiles > 128 || (long)M * d <= (1L << 19) ||
-        V < 2 * (size_t)d || wide)
-        return GENIE_E_UNSUPPORTED;
-    float* slabs = w.logits;
-    GENIE_TRY(launch_gemm16<NPL>(h16, K, plane_h, w16, K, plane_w, nullptr, slabs, nullptr, 0, d, M, d, K / 2, G16_OUTF32, 1.0f, st,
-                                 2, (long)(K / 2), (long)M * d, nullptr, (long)(K / 2), true, false));
-    const size_t n4 = (size_t)M * d / 4;
-    splitk2_residual_kernel<<<(unsigned)((n4 + 255) / 256), 256, 0, st>>>(x, slabs, slabs + (size_t)M * d, bias, n4, d);
+int launch_splitk2_residual(float* x, const float* s0, const float* s1, const float* bias, size_t n4, int N, hipStream_t st) {
+    splitk2_residual_kernel<<<(unsigned)((n4 + 255) / 256), 256, 0, st>>>(x, s0, s1, bias, n4, N);
     GENIE_LAUNCH_CHECK("splitk2_residual");
     return GENIE_OK;
 }
@@ -823,332 +801,9 @@ __global__ void cast16_kernel(const float* __restrict__ src, uint16_t* __restric
     if (i < n) dst[i] = f32_to_bf16(src[i]);
 }
 
-
-// Spatial attention on the fused operand path: the QKV GEMM writes [Q * scale * log2e | K | V^T] as 16-bit planes in the
-// attention kernel's own layout (kernels_gemm_pp.hip, G16X_QKV) and kernels_attn_dma.hip streams them through LDS -- no f32
-// qkv round trip, no operand split / transpose inside the attention kernel.  Covers the shipped geometry (S = 256, head_dim
-// 32 / 64, d % 256 == 0, LayerNorm or qk-norm blocks, chip-filling batches); anything else returns GENIE_E_UNSUPPORTED and the caller
-// runs the f32-qkv path below.
-// x / x16 / proj_done (bf16 only): when given and the geometry allows, the attention AND the out-projection + residual run as
-// kernels_fused.hip's spatial_attn_proj kernel (x, x16 updated, *proj_done = true: the caller skips its proj GEMM)
-static int spatial_attention_fused(int npl, const genie_cfg& c, const genie_layer_weights& lw, const uint16_t* u, size_t planeA,
-                                   size_t planeW, Workspace& w, int B, uint16_t* out16, size_t out_plane, hipStream_t st,
-                                   float* x = nullptr, uint16_t* x16 = nullptr, bool* proj_done = nullptr, bool shadow16 = true) {
-    static const int on = study_env("GENIE_ATTN_DMA", 1);
-    const int d = c.d_model;
-#ifdef GENIE_STUDY
-    if (npl == 2 && study_terms() != 3) return GENIE_E_UNSUPPORTED;
-#endif
-    if (npl == 2 && (lw.spatial.w16_wide & GENIE_WIDE_QKV)) return GENIE_E_UNSUPPORTED;  // |w| >= 32: two-accumulator GEMM + f32-qkv attention
-    // (qk_norm: the per-head LayerNorm of q and k is the QKV GEMM's epilogue -- G16X_QKNORM -- so the planes hold normalised, scaled
-    // operands and the attention kernels below are the same in both variants)
-    if (!on || c.S != 256 || (c.head_dim != 64 && c.head_dim != 32) || d % 256 || d != c.num_heads * c.head_dim ||
-        (c.qk_norm && !(lw.spatial.norm_w && lw.spatial.norm_b)))
-        return GENIE_E_UNSUPPORTED;
-    const long n_seq = (long)B * c.T;
-    const int M = (int)(n_seq * c.S);
-    uint16_t* qkv16 = (uint16_t*)w.big;  // 3 * npl planes of M * d 16-bit values <= the (M, 3d) f32 buffer
-    const int rc = launch_gemm16_pp(npl, 3, npl == 2, u, d, (long)planeA, lw.spatial.qkv_w16, d, (long)planeW,
-                                    c.qkv_bias ? lw.spatial.qkv_b : nullptr, nullptr, nullptr, qkv16, (long)M * d, d, M, 3 * d, d,
-                                    G16X_OUT16 | G16X_QKV | (c.qk_norm ? G16X_QKNORM : 0), 1.0f, st, 1, 0, 0, 0,
-                                    c.attn_scale * 1.4426950408889634f, c.head_dim, c.qk_norm ? lw.spatial.norm_w : nullptr,
-                                    c.qk_norm ? lw.spatial.norm_b : nullptr);
-    if (rc != GENIE_OK) return rc;
-    if (npl == 1 && x && x16 && proj_done) {   // shipped geometry, bf16: attention over all heads + out-projection + residual in one kernel
-        const int rf = launch_spatial_attn_proj_bf16(c, lw.spatial, qkv16, x, shadow16 ? x16 : nullptr, n_seq, st);
-        if (rf == GENIE_OK) { *proj_done = true; return GENIE_OK; }
-        if (rf != GENIE_E_UNSUPPORTED) return rf;
-    }
-    return launch_attn_spatial_dma(npl, qkv16, n_seq, d, c.num_heads, c.head_dim, out16, out_plane, st);
-}
-
-// Spatial attention from the f32 qkv, for both 16-bit drivers: the split kernel writes the operand form itself; any other geometry goes
-// through the generic kernel (f32 rows in the logits scratch) and a convert
-static int spatial_attention_f32qkv(const genie_cfg& c, const genie_attn_weights& aw, const float* qkv, Workspace& w, int B,
-                                    uint16_t* out16, size_t plane, hipStream_t st) {
-    const int d = c.d_model;
-    const float* nw = c.qk_norm ? aw.norm_w : nullptr;
-    const float* nb = c.qk_norm ? aw.norm_b : nullptr;
-    const int rc = launch_attn_spatial_split(qkv, nullptr, c.S, (long)B * c.T, d, c.num_heads, c.head_dim, c.attn_scale, nw, nb, st,
-                                             out16, plane);
-    if (rc != GENIE_E_UNSUPPORTED) return rc;
-    GENIE_TRY(launch_attn_generic(qkv, w.logits, c.S, (long)B * c.T, 1, c.S, 0, 1, d, c.num_heads, c.head_dim, c.attn_scale, 0, nw, nb,
-                                  st));
-    return launch_to_operand16(w.logits, out16, plane, (size_t)B * c.T * c.S * d, st);
-}
-
-// bf16 precision contract (mirrored by oracle.genie_oracle.BF16_MFMA):
-//   * every nn.Linear operand is bf16 (weights packed once; activations rounded by their producer)
-//   * accumulation, bias, GELU, LayerNorm and the residual stream are f32
-//   * qkv leaves its GEMM as f32 and the attention core runs on the f32-MFMA kernels of the exact path (its
-//     output is rounded to bf16 for the out-projection) -- attention is ~6 % of the FLOPs.
-int st_block_bf16(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, const BlockPass& p, BlockCarry& carry, int B,
-                  hipStream_t st) {
-    const int d = c.d_model, M = B * c.T * c.S;
-    uint16_t* x16 = (uint16_t*)w.xn;              // bf16 shadow of the residual stream
-    uint16_t* xn16 = x16 + (size_t)M * d;         // LayerNorm output, then attention output
-    float* qkv = (float*)w.big;                   // f32 qkv
-    uint16_t* big16 = (uint16_t*)w.big;           // later: bf16 MLP hidden
-    GENIE_CHECK_ARG(lw.spatial.qkv_w16 && lw.spatial.proj_w16 && lw.temporal.qkv_w16 && lw.temporal.proj_w16 &&
-                        lw.fc1_w16 && lw.fc2_w16,
-                    "bf16 precision needs packed bf16 weights (genie_pack_bf16)");
-    // t16: the temporal qkv (and the KV cache slices) hold bf16 -- the qkv GEMM stores 2 bytes per value instead of 4 and the attention
-    // kernels (HBM-bound) read half the bytes; softmax and both products stay f32 inside them
-    const bool t16 = temporal_qkv16(c, p.model_T);
-    const BlockCarry prev = carry;   // what the previous block's fused MLP kernel already did for this one; taken, so that it is read once
-    carry = BlockCarry();
-    // Will the temporal sub-block run as the fused kernel?  Then it rounds its operands from the f32 rows itself and the spatial kernel in
-    // front need not write the bf16 shadow of x (134 MB per layer at 64 clips it would write and the temporal kernel read).
-    static const int no_shadow_env = study_env("GENIE_T_FROM_F32", 1);   // (a study-build knob: the shipping library reads no environment)
-    const bool fused_t = p.is_plain() && t16 && temporal_fused_takes(c, lw.temporal, B);
-    // ... or, in the prefix-cache passes, as the fused kernel that keeps the K / V fragment images in the cache slice (kernels_fused_prefix.hip)
-    const bool frag_t = p.is_cache_pass() && !p.strided(c.T) && t16 && temporal_prefix_fused_takes(c, lw.temporal, B, p.model_T);
-    const bool shadow16 = !((fused_t || frag_t) && no_shadow_env);
-    // spatial
-    const uint16_t* u = x16;
-    int rc = GENIE_E_UNSUPPORTED;
-    bool qkv_done = false, proj_done = false;
-    if (prev.qkv_planes_done) {   // the previous block's fused MLP kernel left this block's operand planes in `big`
-        rc = launch_spatial_attn_proj_bf16(c, lw.spatial, (const uint16_t*)w.big, x, shadow16 ? x16 : nullptr, (long)B * c.T, st);
-        if (rc == GENIE_OK) proj_done = true;
-        else if (rc == GENIE_E_UNSUPPORTED)   // (fewer sequences than the fused kernel takes: the stand-alone attention kernel reads the same planes, proj GEMM below)
-            rc = launch_attn_spatial_dma(1, (uint16_t*)w.big, (long)B * c.T, d, c.num_heads, c.head_dim, xn16, 0, st);
-        GENIE_TRY(rc);
-        qkv_done = true;
-    }
-    if (!qkv_done && !c.qk_norm) {  // one-frame passes: LayerNorm inside the small GEMM's fragment path (no LayerNorm launch)
-        const int r2 = launch_gemm16_sm_ln(1, x, d, lw.norm1_w, lw.norm1_b, 1e-5f, lw.spatial.qkv_w16, d, 0,
-                                           c.qkv_bias ? lw.spatial.qkv_b : nullptr, nullptr, qkv, nullptr, 0, 3 * d, M, 3 * d, d,
-                                           G16_OUTF32, 1.0f, st);
-        if (r2 == GENIE_OK) qkv_done = true;
-        else if (r2 != GENIE_E_UNSUPPORTED) return r2;
-    }
-    if (!qkv_done) {
-        if (!c.qk_norm) {
-            if (!prev.ln1_done)   // (else: the previous block's fused MLP kernel wrote norm1(x) into xn16)
-                GENIE_TRY(launch_layer_norm_bf16(x, lw.norm1_w, lw.norm1_b, xn16, M, d, 1e-5f, st));
-            u = xn16;
-        }
-        rc = spatial_attention_fused(1, c, lw, u, 0, 0, w, B, xn16, 0, st, x, x16, &proj_done, shadow16);
-    }
-    if (rc == GENIE_E_UNSUPPORTED) {
-        if (!qkv_done)
-            GENIE_TRY(launch_gemm16<1>(u, d, 0, lw.spatial.qkv_w16, d, 0, c.qkv_bias ? lw.spatial.qkv_b : nullptr, qkv, nullptr,
-                                       0, 3 * d, M, 3 * d, d, G16_OUTF32, 1.0f, st));
-        rc = spatial_attention_f32qkv(c, lw.spatial, qkv, w, B, xn16, 0, st);
-    }
-    GENIE_TRY(rc);
-    if (!proj_done)
-        GENIE_TRY(launch_gemm16<1>(xn16, d, 0, lw.spatial.proj_w16, d, 0, c.proj_bias ? lw.spatial.proj_b : nullptr, x, x16,
-                                   0, d, M, d, d, G16_ACCUM | G16_OUTF32 | G16_OUT16, 1.0f, st));
-    // temporal (no pre-norm): operand = bf16 shadow of x
-    bool temporal_done = false;
-    if (p.is_plain() && t16) {
-        // plain full-clip forward of the shipped geometry: qkv + attention + proj + residual in ONE kernel, the qkv never
-        // leaves the registers (kernels_fused.hip); same rounding points as the launches below
-        // (the bf16 shadow of x exists unless the fused spatial kernel ran and was told not to write it)
-        rc = launch_temporal_fused_bf16(c, lw.temporal, (proj_done && !shadow16) ? nullptr : x16, x, B, st);
-        if (rc == GENIE_OK) temporal_done = true;
-        else if (rc != GENIE_E_UNSUPPORTED) return rc;
-    }
-    if (frag_t) {   // prefix-cache passes of the shipped geometry: one kernel, the cache slice holds K / V fragment images
-        GENIE_TRY(launch_temporal_prefix_fused_bf16(c, lw.temporal, x, reinterpret_cast<uint16_t*>(p.cache), B, p.fused_mode(), p.tshift,
-                                                    p.model_T, st));
-        if (p.stop_after_tqkv) return GENIE_OK;
-        temporal_done = true;
-    }
-    if (!temporal_done) {
-        const TemporalQkv tq = temporal_qkv_target(c, p, qkv, B);
-        GENIE_TRY(launch_gemm16<1>(x16, d, 0, lw.temporal.qkv_w16, d, 0, c.qkv_bias ? lw.temporal.qkv_b : nullptr,
-                                   t16 ? nullptr : tq.base + tq.off, t16 ? reinterpret_cast<uint16_t*>(tq.base) + tq.off : nullptr, 0,
-                                   3 * d, tq.rows, 3 * d, d, t16 ? G16_OUT16 : G16_OUTF32, 1.0f, st, tq.batch, tq.strideA, tq.strideC));
-        if (p.stop_after_tqkv) return GENIE_OK;
-        GENIE_TRY(temporal_attention(c, lw.temporal, p, tq, nullptr, xn16, 0, t16, w, B, st));
-        // the 16-bit shadow of x is only read by a Linear that has no LayerNorm in front: temporal qkv always, fc1 and the next
-        // block's spatial qkv only in the qk-norm variant, the readout after the last block
-        GENIE_TRY(launch_gemm16<1>(xn16, d, 0, lw.temporal.proj_w16, d, 0, c.proj_bias ? lw.temporal.proj_b : nullptr, x,
-                                   x16, 0, d, M, d, d, G16_ACCUM | G16_OUTF32 | (c.qk_norm ? G16_OUT16 : 0), 1.0f, st));
-    }
-    // MLP
-    if (!p.is_decode()) {   // LayerNorm + fc1 + GELU + fc2 + residual in one kernel for the shipped geometry (kernels_fused.hip)
-        const genie_layer_weights* nx = p.next_layer;
-        if (nx && nx->norm1_w && nx->norm1_b && p.next_is_ln) {
-            rc = GENIE_E_UNSUPPORTED;
-            if (nx->spatial.fused_w16 && (nx->spatial.w16_wide & GENIE_FUSED_QKV_STREAM)) {
-                // ... and the next block's spatial qkv Linear too: its operand planes (in `big`, where its qkv GEMM would put them)
-                rc = launch_mlp_fused_bf16(c, lw, x, nullptr, (long)M, st, nx->norm1_w, nx->norm1_b,
-                                           nx->spatial.fused_w16 + GENIE_SPATIAL_PROJ_FUSED_ELEMS, (uint16_t*)w.big);
-                if (rc == GENIE_OK) carry.qkv_planes_done = true;
-            }
-            if (rc == GENIE_E_UNSUPPORTED) {
-                rc = launch_mlp_fused_bf16(c, lw, x, xn16, (long)M, st, nx->norm1_w, nx->norm1_b);
-                if (rc == GENIE_OK) carry.ln1_done = true;
-            }
-        } else {
-            rc = launch_mlp_fused_bf16(c, lw, x, p.next_is_ln ? nullptr : x16, (long)M, st);
-        }
-        if (rc != GENIE_E_UNSUPPORTED) return rc;
-    }
-    u = x16;
-    bool fc1_done = false;
-    if (!c.qk_norm) {
-        const int r2 = launch_gemm16_sm_ln(1, x, d, lw.norm2_w, lw.norm2_b, 1e-5f, lw.fc1_w16, d, 0, c.mlp_bias ? lw.fc1_b : nullptr,
-                                           nullptr, nullptr, big16, 0, c.hidden, M, c.hidden, d, G16_GELU | G16_OUT16, 1.0f, st);
-        if (r2 == GENIE_OK) fc1_done = true;
-        else if (r2 != GENIE_E_UNSUPPORTED) return r2;
-    }
-    if (!fc1_done) {
-        if (!c.qk_norm) {
-            GENIE_TRY(launch_layer_norm_bf16(x, lw.norm2_w, lw.norm2_b, xn16, M, d, 1e-5f, st));
-            u = xn16;
-        }
-        GENIE_TRY(launch_gemm16<1>(u, d, 0, lw.fc1_w16, d, 0, c.mlp_bias ? lw.fc1_b : nullptr, nullptr, big16, 0, c.hidden,
-                                   M, c.hidden, d, G16_GELU | G16_OUT16, 1.0f, st));
-    }
-    const int rs = fc2_splitk2<1>(c, big16, 0, lw.fc2_w16, 0, c.mlp_bias ? lw.fc2_b : nullptr, x, w, p, M, st);
-    if (rs != GENIE_E_UNSUPPORTED) return rs;
-    return launch_gemm16<1>(big16, c.hidden, 0, lw.fc2_w16, c.hidden, 0, c.mlp_bias ? lw.fc2_b : nullptr, x, x16, 0, d, M, d, c.hidden,
-                            G16_ACCUM | G16_OUTF32 | (p.next_is_ln ? 0 : G16_OUT16), 1.0f, st);
-}
-
-// The bf16 shadow of x must exist before the first layer when the block has no pre-norm (qk_norm configs).
-int prepare_bf16(const genie_cfg& c, const float* x, Workspace& w, int B, hipStream_t st) {
-    // LayerNorm blocks read the f32 x (norm1) first and their spatial out-projection writes the shadow before anything reads it
-    if (!c.qk_norm) return GENIE_OK;
-    const size_t n = (size_t)B * c.T * c.S * c.d_model;
-    cast16_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(x, (uint16_t*)w.xn, n);
+int launch_shadow_bf16(const float* src, uint16_t* dst, size_t n, hipStream_t st) {
+    cast16_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(src, dst, n);
     GENIE_LAUNCH_CHECK("cast16");
-    return GENIE_OK;
-}
-
-// out_x_proj on frames [t0,t1) from the bf16 shadow; logits f32.  BCTHW goes through the token-major scratch.
-int readout_bf16(const genie_cfg& c, const genie_weights& wt, const float* x, Workspace& w, int B, int t0, int t1,
-                 int layout, float* logits, hipStream_t st) {
-    GENIE_CHECK_ARG(wt.out_w16, "bf16 precision needs packed bf16 weights (genie_pack_bf16)");
-    const int d = c.d_model, nt = t1 - t0, V = c.factored_vocab * c.num_factored;
-    const long rows = (long)nt * c.S;
-    GENIE_CHECK_ARG((const void*)x == (const void*)w.x, "bf16 readout reads the workspace's own hidden state");
-    const uint16_t* x16 = (const uint16_t*)w.xn;
-    float* dst = (layout == GENIE_LAYOUT_TOKEN_MAJOR) ? logits : w.logits;
-    GENIE_TRY(launch_gemm16<1>(x16 + (size_t)t0 * c.S * d, d, 0, wt.out_w16, d, 0, wt.out_b, dst, nullptr, 0, V,
-                               (int)rows, V, d, G16_OUTF32, c.readout_mult, st, B, (long)c.T * c.S * d, rows * V));
-    if (layout != GENIE_LAYOUT_TOKEN_MAJOR) GENIE_TRY(launch_transpose(w.logits, logits, B, (int)rows, V, st));
-    return GENIE_OK;
-}
-
-// ---- GENIE_PREC_F16X3 ---------------------------------------------------------------------------
-// Every Linear runs on the f16 matrix cores with split operands (3 MFMAs per K-step); everything else is
-// the exact path: f32 qkv -> f32-MFMA attention kernels -> outputs re-split for the next Linear.
-// Buffers: w.xn  = split planes of the residual stream x (hi | lo), M*d each
-//          w.aux = split planes of the LayerNorm output, then of the attention output
-//          w.big = qkv as f32 (M*3d), later the split planes of the MLP hidden (M*hidden each)
-int st_block_f16x3(const genie_cfg& c, const genie_layer_weights& lw, float* x, Workspace& w, const BlockPass& p, int B, hipStream_t st) {
-    const int d = c.d_model, M = B * c.T * c.S, hid = c.hidden;
-    const size_t pd = (size_t)M * d, ph = (size_t)M * hid;
-    uint16_t* xs = (uint16_t*)w.xn;
-    uint16_t* as = (uint16_t*)w.aux;
-    float* qkv = (float*)w.big;
-    uint16_t* hs = (uint16_t*)w.big;
-    GENIE_CHECK_ARG(lw.spatial.qkv_w16 && lw.spatial.proj_w16 && lw.temporal.qkv_w16 && lw.temporal.proj_w16 &&
-                        lw.fc1_w16 && lw.fc2_w16,
-                    "f16x3 precision needs split-f16 weights (genie_pack_split_f16)");
-    const size_t pw_qkv = (size_t)3 * d * d, pw_proj = (size_t)d * d, pw_fc = (size_t)hid * d;
-    // |w| >= 32 range flags of the packed tensors (genie_hip.h): those Linears stay off the 2^11-scaling kernel
-    const int wsq = (lw.spatial.w16_wide & GENIE_WIDE_QKV) ? G16_WIDEW : 0, wsp = (lw.spatial.w16_wide & GENIE_WIDE_PROJ) ? G16_WIDEW : 0;
-    const int wtq = (lw.temporal.w16_wide & GENIE_WIDE_QKV) ? G16_WIDEW : 0, wtp = (lw.temporal.w16_wide & GENIE_WIDE_PROJ) ? G16_WIDEW : 0;
-    const int wf1 = (lw.w16_wide & GENIE_WIDE_FC1) ? G16_WIDEW : 0, wf2 = (lw.w16_wide & GENIE_WIDE_FC2) ? G16_WIDEW : 0;
-    // ---- spatial
-    GENIE_STUDY_CLASS(0);
-    const uint16_t* u = xs;
-    int rc = GENIE_E_UNSUPPORTED;
-    bool qkv_done = false;
-    if (!c.qk_norm) {  // one-frame passes: LayerNorm inside the small GEMM's fragment path (no LayerNorm launch)
-        const int r2 = launch_gemm16_sm_ln(2, x, d, lw.norm1_w, lw.norm1_b, 1e-5f, lw.spatial.qkv_w16, d, pw_qkv,
-                                           c.qkv_bias ? lw.spatial.qkv_b : nullptr, nullptr, qkv, nullptr, 0, 3 * d, M, 3 * d, d,
-                                           G16_OUTF32, 1.0f, st);
-        if (r2 == GENIE_OK) qkv_done = true;
-        else if (r2 != GENIE_E_UNSUPPORTED) return r2;
-    }
-    if (!qkv_done) {
-        if (!c.qk_norm) {
-            GENIE_TRY(launch_layer_norm_split(x, lw.norm1_w, lw.norm1_b, as, pd, M, d, 1e-5f, st));
-            u = as;
-        }
-        rc = spatial_attention_fused(2, c, lw, u, pd, pw_qkv, w, B, as, pd, st);
-    }
-    if (rc == GENIE_E_UNSUPPORTED) {
-        if (!qkv_done)
-            GENIE_TRY(launch_gemm16<2>(u, d, pd, lw.spatial.qkv_w16, d, pw_qkv, c.qkv_bias ? lw.spatial.qkv_b : nullptr, qkv,
-                                       nullptr, 0, 3 * d, M, 3 * d, d, G16_OUTF32 | wsq, 1.0f, st));
-        rc = spatial_attention_f32qkv(c, lw.spatial, qkv, w, B, as, pd, st);
-    }
-    GENIE_TRY(rc);
-    GENIE_STUDY_CLASS(2);
-    // the shipped geometry: temporal qkv Linear + attention as one kernel on the f32 rows of x (kernels_fused_f16x3.hip) -- the spatial
-    // out-projection then need not write the split planes of x; in the prefix-cache passes the cache slice holds that kernel's k, v accumulators
-    const bool fused_tq = !p.is_decode() && !p.strided(c.T) &&
-                          temporal_qkv_attn_f16x3_takes(c, lw.temporal, B, p.model_T, p.is_cache_pass());
-    GENIE_TRY(launch_gemm16<2>(as, d, pd, lw.spatial.proj_w16, d, pw_proj, c.proj_bias ? lw.spatial.proj_b : nullptr, x,
-                               xs, pd, d, M, d, d, G16_ACCUM | G16_OUTF32 | (fused_tq ? 0 : G16_OUT16) | wsp, 1.0f, st));
-    // ---- temporal
-    GENIE_STUDY_CLASS(1);
-    if (fused_tq) {
-        GENIE_TRY(launch_temporal_qkv_attn_f16x3(c, lw.temporal, x, as, (long)pd, p.cache, B, p.fused_mode(), p.tshift, p.model_T, st));
-        if (p.stop_after_tqkv) return GENIE_OK;
-    } else {
-        const TemporalQkv tq = temporal_qkv_target(c, p, qkv, B);
-        GENIE_TRY(launch_gemm16<2>(xs, d, pd, lw.temporal.qkv_w16, d, pw_qkv, c.qkv_bias ? lw.temporal.qkv_b : nullptr, tq.base + tq.off,
-                                   nullptr, 0, 3 * d, tq.rows, 3 * d, d, G16_OUTF32 | wtq, 1.0f, st, tq.batch, tq.strideA, tq.strideC));
-        if (p.stop_after_tqkv) return GENIE_OK;
-        GENIE_TRY(temporal_attention(c, lw.temporal, p, tq, nullptr, as, pd, false, w, B, st));
-    }
-    GENIE_STUDY_CLASS(3);
-    GENIE_TRY(launch_gemm16<2>(as, d, pd, lw.temporal.proj_w16, d, pw_proj, c.proj_bias ? lw.temporal.proj_b : nullptr,
-                               x, xs, pd, d, M, d, d, G16_ACCUM | G16_OUTF32 | (c.qk_norm ? G16_OUT16 : 0) | wtp, 1.0f, st));
-    // ---- MLP
-    GENIE_STUDY_CLASS(4);
-    u = xs;
-    bool fc1_done = false;
-    if (!c.qk_norm) {
-        const int r2 = launch_gemm16_sm_ln(2, x, d, lw.norm2_w, lw.norm2_b, 1e-5f, lw.fc1_w16, d, pw_fc, c.mlp_bias ? lw.fc1_b : nullptr,
-                                           nullptr, nullptr, hs, ph, hid, M, hid, d, G16_GELU | G16_OUT16, 1.0f, st);
-        if (r2 == GENIE_OK) fc1_done = true;
-        else if (r2 != GENIE_E_UNSUPPORTED) return r2;
-    }
-    if (!fc1_done) {
-        if (!c.qk_norm) {
-            GENIE_TRY(launch_layer_norm_split(x, lw.norm2_w, lw.norm2_b, as, pd, M, d, 1e-5f, st));
-            u = as;
-        }
-        GENIE_TRY(launch_gemm16<2>(u, d, pd, lw.fc1_w16, d, pw_fc, c.mlp_bias ? lw.fc1_b : nullptr, nullptr, hs, ph, hid, M,
-                                   hid, d, G16_GELU | G16_OUT16 | wf1, 1.0f, st));
-    }
-    GENIE_STUDY_CLASS(5);
-    const int rs = fc2_splitk2<2>(c, hs, (long)ph, lw.fc2_w16, (long)pw_fc, c.mlp_bias ? lw.fc2_b : nullptr, x, w, p, M, st, wf2 != 0);
-    if (rs != GENIE_E_UNSUPPORTED) return rs;
-    return launch_gemm16<2>(hs, hid, ph, lw.fc2_w16, hid, pw_fc, c.mlp_bias ? lw.fc2_b : nullptr, x, xs, pd, d, M, d, hid,
-                            G16_ACCUM | G16_OUTF32 | (p.next_is_ln ? 0 : G16_OUT16) | wf2, 1.0f, st);
-}
-
-int prepare_f16x3(const genie_cfg& c, const float* x, Workspace& w, int B, hipStream_t st) {
-    if (!c.qk_norm) return GENIE_OK;   // (as prepare_bf16: nothing reads the split planes of x before the first out-projection rewrites them)
-    const size_t n = (size_t)B * c.T * c.S * c.d_model;
-    return launch_split_f16(x, (uint16_t*)w.xn, n, n, st);
-}
-
-int readout_f16x3(const genie_cfg& c, const genie_weights& wt, const float* x, Workspace& w, int B, int t0, int t1,
-                  int layout, float* logits, hipStream_t st) {
-    GENIE_CHECK_ARG(wt.out_w16, "f16x3 precision needs split-f16 weights (genie_pack_split_f16)");
-    const int d = c.d_model, nt = t1 - t0, V = c.factored_vocab * c.num_factored;
-    const long rows = (long)nt * c.S;
-    GENIE_CHECK_ARG((const void*)x == (const void*)w.x, "f16x3 readout reads the workspace's own hidden state");
-    const size_t pd = (size_t)B * c.T * c.S * d;
-    const uint16_t* xs = (const uint16_t*)w.xn;
-    float* dst = (layout == GENIE_LAYOUT_TOKEN_MAJOR) ? logits : w.logits;
-    GENIE_STUDY_CLASS(6);
-    GENIE_TRY(launch_gemm16<2>(xs + (size_t)t0 * c.S * d, d, pd, wt.out_w16, d, (size_t)V * d, wt.out_b, dst, nullptr, 0,
-                               V, (int)rows, V, d, G16_OUTF32 | (wt.out_w16_wide ? G16_WIDEW : 0), c.readout_mult, st, B, (long)c.T * c.S * d, rows * V));
-    if (layout != GENIE_LAYOUT_TOKEN_MAJOR) GENIE_TRY(launch_transpose(w.logits, logits, B, (int)rows, V, st));
     return GENIE_OK;
 }
 
@@ -1156,7 +811,7 @@ int launch_pack_split(const float* src, uint16_t* dst, size_t n, hipStream_t st)
 
 int launch_linear_lowp(int precision, const uint16_t* x16, const uint16_t* W16, const float* b, float* y, int M, int N,
                        int K, int gelu, int accumulate, hipStream_t st) {
-    const int flags = G16_OUTF32 | (gelu ? G16_GELU : 0) | (accumulate ? G16_ACCUM : 0);
+    const int flags = G16X_OUTF32 | (gelu ? G16X_GELU : 0) | (accumulate ? G16X_ACCUM : 0);
 #ifdef GENIE_STUDY
     {   // leading-dimension study (tools/bench_gemm.py --pad-a / --pad-c allocate the padded buffers): does a power-of-two
         // row stride of the activation planes / of the output cost memory-channel conflicts?
@@ -1183,8 +838,7 @@ int launch_gemm_bf16_out16(const uint16_t* A16, const uint16_t* W16, const float
                            hipStream_t st) {
     // (no split-K kernel here: the MAGVIT2 stacks promise the same bytes for an image whatever else is in the batch, so the
     // accumulation order must not depend on the problem size)
-    return launch_gemm16<1>(A16, K, 0, W16, K, 0, bias, nullptr, C16, 0, N, M, N, K, G16_OUT16, 1.0f, st, 1, 0, 0, nullptr, 0, true,
-                            /*allow_sm=*/false);
+    return launch_gemm16<1>(A16, K, 0, W16, K, 0, bias, nullptr, C16, 0, N, M, N, K, G16X_OUT16 | G16X_NOSM, 1.0f, st);
 }
 
 }  // namespace genie

@@ -32,7 +32,7 @@
 //     ds_read_b128, one workgroup barrier per stage, and each fragment feeds G matrix instructions.
 //   * 4 waves per workgroup (128 tokens per block), 2 workgroups per CU (<= 256 registers per lane): one workgroup's
 //     HBM phases (operand load, residual read-modify-write) run under the other's matrix work.
-// Numerics = the bf16 contract of kernels_bf16.hip / oracle BF16_MFMA: Linear operands bf16 (q, k, v rounded to bf16 as the
+// Numerics = the bf16 contract of st_block.hip / oracle BF16_MFMA: Linear operands bf16 (q, k, v rounded to bf16 as the
 // stored temporal qkv is), f32 accumulation, f32 softmax; P is split into two bf16 terms (hi + lo, 16 mantissa bits) so the
 // P.V product is f32-class as in the unfused f32 attention kernel.
 #include <stdio.h>

@@ -8,7 +8,7 @@
 //     (lane: token l & 15, k-group l >> 4, 8 consecutive k; hi and lo' planes of the split, made here from the f32 rows of x) are the B
 //     operand of the swapped products D[feature][token] = W . X^T (q, k) and the A operand of the plain one (v).
 //   * every Linear product is three v_mfma_f32_16x16x32_f16: acc_m += Whi . xhi, acc_c += Whi . xlo' + Wlo' . xhi, value =
-//     acc_m + acc_c / 2048 (+ bias) -- the f16x3 contract of kernels_bf16.hip / kernels_frame.hip (22-bit operands, f32 accumulation).
+//     acc_m + acc_c / 2048 (+ bias) -- the f16x3 contract of st_block.hip / kernels_frame.hip (22-bit operands, f32 accumulation).
 //   * the attention is f32 on v_mfma_f32_16x16x4_f32, as attn_temporal_f32_mfma_kernel: the accumulator layout of q, k (lane = token,
 //     features 4 g + e) is both operands' layout of S^T = K Q^T contracted in the order (g, e); S^T's (lane = query, keys 4 g + e) is the
 //     B operand and v's (lane = feature, tokens 4 g + e) the A operand of O^T = V^T P.  Nothing is re-laid and nothing is rounded.

@@ -246,6 +246,7 @@ static int lin16(int npl, const uint16_t* x16, const uint16_t* W16, const float*
     if (y) flags |= G16X_OUTF32;
     if (y16) flags |= G16X_OUT16;
     if (R) flags |= G16X_ACCUM;
+    if (npl == 2) flags |= G16X_WIDEW;   // (as the wgrad products below: the step's f16x3 GEMMs all run on the two-accumulator kernels)
     return launch_gemm16_ex(npl, x16, K, PL(npl, (size_t)M * K), W16, K, PL(npl, (size_t)N * K), b, (R && R != y) ? R : nullptr,
                             y, y16, PL(npl, (size_t)M * N), N, M, N, K, flags, alpha, st, 1, 0, 0, 0);
 }
@@ -256,12 +257,13 @@ static int wgrad16(int npl, const uint16_t* dYT, const uint16_t* XT, float* dW, 
     int ns = 1;
     while (ns < 64 && tiles * ns < 256 && Mtok % (64 * ns * 2) == 0 && (size_t)(ns * 2) * N * K <= slab_floats) ns *= 2;
     const long pa = PL(npl, (size_t)N * Mtok), pw = PL(npl, (size_t)K * Mtok);
+    const int wide = npl == 2 ? G16X_WIDEW : 0;   // the W operand is an activation, not a |w| < 32 weight matrix
     if (ns == 1)
         return launch_gemm16_ex(npl, dYT, Mtok, pa, XT, Mtok, pw, nullptr, nullptr, dW, nullptr, 0, K, N, K, Mtok,
-                                G16X_OUTF32 | (beta != 0.f ? G16X_ACCUM : 0), alpha, st, 1, 0, 0, 0);
+                                G16X_OUTF32 | (beta != 0.f ? G16X_ACCUM : 0) | wide, alpha, st, 1, 0, 0, 0);
     const int kc = Mtok / ns;
     GENIE_TRY(launch_gemm16_ex(npl, dYT, Mtok, pa, XT, Mtok, pw, nullptr, nullptr, slabs, nullptr, 0, K, N, K, kc,
-                               G16X_OUTF32, alpha, st, ns, kc, kc, (long)N * K));
+                               G16X_OUTF32 | wide, alpha, st, ns, kc, kc, (long)N * K));
     return launch_slab_reduce(slabs, ns, (size_t)N * K, dW, beta, st);
 }
 

@@ -11,7 +11,8 @@ records and exits non-zero on any difference.
 
 The battery: every pass kind (full forward, clean pass + masked-frames pass at frame0 0 and 1, a half-length clean pass into a full-length
 cache at 1 and 2 clips, one- and two-frame decode passes, the cached generate loop with 2 MaskGIT steps and the merged commit, one
-STBlock) in all three precisions, for a LayerNorm and a qk-norm model, at three geometries.  A case the library refuses (e.g. two frames
+STBlock) in all three precisions, for a LayerNorm and a qk-norm model, at four geometries; then BRANCH_CASES, one model each for the
+branches of the 16-bit layer driver (csrc/st_block.hip) that those models do not reach.  A case the library refuses (e.g. two frames
 per pass outside f16x3) counts through its return code.  WATCHED names the kernels whose dispatch depends on the pass kind: the battery
 as a whole must reach each of them in the first library, else the battery itself has failed.  Two kernels of that kind carry no name a
 table could show: the launches of attn_spatial_dma are profiled unnamed (they are counted, and compared, as "(unnamed)" of the spatial
@@ -39,7 +40,24 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (name, d_model, heads, T, S, clips of the main cases)
 GEOMETRIES = [("d64", 64, 2, 4, 16, 3),        # generic attention kernels, ragged GEMM tiles
               ("d256", 256, 8, 16, 256, 8),    # the shipped geometry: 8 clips = every fused bf16 kernel, chip-filling GEMMs
-              ("d512", 512, 8, 16, 256, 8)]    # heads of 64
+              ("d512", 512, 8, 16, 256, 8),    # heads of 64
+              ("d64h16", 64, 4, 4, 16, 3)]     # heads of 16: the bf16 temporal qkv and KV cache stay f32 (temporal_qkv16 false)
+# Branches of the 16-bit layer driver that no model above reaches: (tag, precision, clips, the cases to run, (d, heads, T, S, qk_norm,
+# qkv_bias), edit of the weights / of how they are packed)
+BRANCH_CASES = [
+    # |w| >= 32 in a row of every Linear: each leaves gemm16_pp for a two-accumulator kernel (8 clips: gemm16_pp would take them all) and
+    # the spatial sub-block its fused qkv + DMA attention for the f32 qkv
+    ("d256wide/ln/f16x3", "f16x3", 8, ("compute_logits", "clean_pass", "masked_frames_logits"), (256, 8, 16, 256, False, True), "wide"),
+    # ... at d 512, where no fused kernel takes the temporal qkv Linear
+    ("d512wide/ln/f16x3", "f16x3", 8, ("compute_logits",), (512, 8, 16, 256, False, True), "wide"),
+    # no qkv bias: the fused MLP kernel of block 0 also writes block 1's spatial operand planes (BlockCarry::qkv_planes_done); block 1 reads
+    # them with the fused attention + out-projection kernel at 128 sequences (8 clips), with the stand-alone attention kernel at 32 (2 clips)
+    ("d256nobias/ln/bf16", "bf16", 8, ("compute_logits",), (256, 8, 16, 256, False, False), None),
+    ("d256nobias2/ln/bf16", "bf16", 2, ("compute_logits",), (256, 8, 16, 256, False, False), None),
+    # fc2_splitk2 on split planes: a one-frame pass of 2,048 rows at hidden 2,048 that the fragment-order frame kernels do not take
+    ("d512noframe/ln/f16x3", "f16x3", 8, ("clean_pass_into_full_cache", "frame_pass"), (512, 8, 16, 256, False, True), "no_frame_streams")]
+WIDE_TENSORS = [f"decoder.layers.0.{t}.weight" for t in ("spatial_attn.qkv", "spatial_attn.proj", "temporal_attn.qkv", "temporal_attn.proj",
+                                                         "mlp.fc1", "mlp.fc2")] + ["out_x_proj.weight"]
 PRECISIONS = ["exact", "bf16", "f16x3"]
 WATCHED = ["spatial_attn_proj_bf16_kernel", "temporal_fused_bf16_kernel", "mlp_fused_bf16_kernel", "temporal_prefix_fused_bf16_kernel",
            "temporal_qkv_attn_f16x3_kernel", "gemm16_pp_kernel", "gemm16_sm_ln_kernel"]
@@ -77,7 +95,7 @@ def child(out_path, battery):
         a = t.detach().contiguous().cpu().numpy()
         return [str(a.dtype), list(a.shape), hashlib.sha256(a.tobytes()).hexdigest()]
 
-    def case(name, fn):
+    def record_case(name, fn):
         """fn() -> (rc, {tensor name: tensor}); the launches of all classes between reset and read are the case's table"""
         _lib.check(lib.genie_profile_enable((1 << N_CLASSES) - 1), "profile_enable")
         lib.genie_profile_reset()
@@ -122,7 +140,7 @@ def child(out_path, battery):
                     tr.optimizer_step()
                     outs["params"] = tr.params
                     return 0, outs
-                case(f"{name}/{prec}", step)
+                record_case(f"{name}/{prec}", step)
                 record[f"{name}/{prec}"]["sizes"] = list(sizes)
                 print(f"{name}/{prec} activation / workspace bytes {sizes}", flush=True)
                 torch.cuda.empty_cache()
@@ -130,86 +148,115 @@ def child(out_path, battery):
             json.dump(record, f)
         return
 
+    def model_cases(tag, cfg, sd, prec, B, only=None):
+        """Every pass kind on one model (`only`: the case names to run, None = all of them)"""
+        d, T, S = cfg.d_model, cfg.T, cfg.S
+        hw = int(round(S ** 0.5))
+        V = cfg.factored_vocab_size * cfg.num_factored_vocabs
+
+        def case(name, fn):
+            if only is None or name[len(tag) + 1:].split("/")[0] in only:
+                record_case(name, fn)
+        m = STMaskGIT(cfg, precision=prec).load_numpy_state_dict(sd).to("cuda")
+        c, w, layers = m._weights()[:3]
+        st = torch.cuda.current_stream().cuda_stream
+        ids = torch.from_numpy(synth.make_clips(B, cfg, seed=7)).cuda().view(B, T, S)
+        masked = ids.clone()
+        masked[:, T // 2:, ::3] = cfg.image_vocab_size
+        ws = m._workspace(B, generate_prompt_frames=T // 2)
+        nbytes = lib.genie_prefix_cache_bytes(c, B)
+
+        def full():
+            logits = m.compute_logits_frames(masked.view(B, T, hw, hw), T - 2, T, "token")
+            bcthw = m.compute_logits_frames(masked.view(B, T, hw, hw), T - 1, T, "bcthw")   # the readout's other layout
+            hidden = m.hidden_states(masked.view(B, T, hw, hw)).clone()
+            assert bool(torch.isfinite(logits).all()), tag   # (equal digests of NaNs would compare nothing)
+            return 0, {"logits": logits, "logits_bcthw": bcthw, "hidden": hidden}
+        case(tag + "/compute_logits", full)
+
+        n = T - 1
+        cache = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+
+        def clean():
+            rc = lib.genie_clean_pass(c, w, ids[:, :n].contiguous().data_ptr(), B, n, n, cache.data_ptr(), nbytes, ws.data_ptr(),
+                                      ws.numel(), st)
+            return rc, {"cache": cache}
+        case(tag + "/clean_pass", clean)
+        for frame0 in (0, 1):
+            def masked_pass():
+                lg = torch.zeros(B, n, S, V, dtype=torch.float32, device="cuda")
+                rc = lib.genie_masked_frames_logits(c, w, masked[:, frame0:frame0 + n].contiguous().data_ptr(), B, frame0, n,
+                                                    cache.data_ptr(), nbytes, lg.data_ptr(), ws.data_ptr(), ws.numel(), st)
+                return rc, {"logits": lg}
+            case(f"{tag}/masked_frames_logits/frame0={frame0}", masked_pass)
+
+        P = T // 2
+        for Bx in (1, 2, B):   # a half-length clean pass into the full-length cache, then decode passes against it
+            nb = lib.genie_prefix_cache_bytes(c, Bx)
+            kv = torch.zeros(nb, dtype=torch.uint8, device="cuda")
+
+            def strided():
+                rc = lib.genie_clean_pass(c, w, ids[:Bx, :P].contiguous().data_ptr(), Bx, P, T, kv.data_ptr(), nb, ws.data_ptr(),
+                                          ws.numel(), st)
+                return rc, {"cache": kv}
+            case(f"{tag}/clean_pass_into_full_cache/B={Bx}", strided)
+
+            def frame():
+                lg = torch.zeros(Bx, S, V, dtype=torch.float32, device="cuda")
+                rc = lib.genie_frame_pass(c, w, masked[:Bx, P].contiguous().data_ptr(), Bx, P, kv.data_ptr(), nb, lg.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), st)
+                return rc, {"logits": lg, "cache": kv}
+            case(f"{tag}/frame_pass/B={Bx}", frame)
+
+            def frames():
+                lg = torch.zeros(Bx, S, V, dtype=torch.float32, device="cuda")
+                rc = lib.genie_frames_pass(c, w, masked[:Bx, P:P + 2].contiguous().data_ptr(), Bx, P, 2, kv.data_ptr(), nb,
+                                           lg.data_ptr(), ws.data_ptr(), ws.numel(), st)
+                return rc, {"logits": lg, "cache": kv}
+            case(f"{tag}/frames_pass_nf2/B={Bx}", frames)
+
+        noise = torch.rand(T - P, 1, B, S, generator=torch.Generator().manual_seed(3)).cuda()
+
+        def generate():
+            out = G.generate_frames_cached(m, ids.view(B, T, hw, hw), P, 2, 0.0, False, noise=noise, merge_commit=True)
+            return 0, {"tokens": out}
+        case(tag + "/generate_cached", generate)
+
+        def block():
+            x = (0.5 * torch.randn(B, T, S, d, generator=torch.Generator().manual_seed(4))).cuda()
+            rc = lib.genie_st_block_forward(c, layers[0], x.data_ptr(), B, ws.data_ptr(), ws.numel(), st)
+            return rc, {"x": x}
+        case(tag + "/st_block_forward", block)
+        del m, ws, cache
+        torch.cuda.empty_cache()
+
+    def make_cfg(d, heads, T, S, qk_norm, qkv_bias=True):
+        return GenieConfig(num_layers=2, num_heads=heads, d_model=d, T=T, S=S, num_factored_vocabs=2, qk_norm=qk_norm, use_mup=False,
+                           qkv_bias=qkv_bias)
+
     for gname, d, heads, T, S, B in GEOMETRIES:
         for qk_norm in (False, True):
-            cfg = GenieConfig(num_layers=2, num_heads=heads, d_model=d, T=T, S=S, num_factored_vocabs=2, qk_norm=qk_norm, use_mup=False,
-                              qkv_bias=True)
+            cfg = make_cfg(d, heads, T, S, qk_norm)
             sd = synth.make_state_dict(cfg, seed=5, law="conditioned")
             nonzero_biases(sd, 6)
-            hw = int(round(S ** 0.5))
-            V = cfg.factored_vocab_size * cfg.num_factored_vocabs
             for prec in PRECISIONS:
-                tag = f"{gname}/{'qknorm' if qk_norm else 'ln'}/{prec}"
-                m = STMaskGIT(cfg, precision=prec).load_numpy_state_dict(sd).to("cuda")
-                c, w, layers = m._weights()[:3]
-                st = torch.cuda.current_stream().cuda_stream
-                ids = torch.from_numpy(synth.make_clips(B, cfg, seed=7)).cuda().view(B, T, S)
-                masked = ids.clone()
-                masked[:, T // 2:, ::3] = cfg.image_vocab_size
-                ws = m._workspace(B, generate_prompt_frames=T // 2)
-                nbytes = lib.genie_prefix_cache_bytes(c, B)
-
-                def full():
-                    logits = m.compute_logits_frames(masked.view(B, T, hw, hw), T - 2, T, "token")
-                    hidden = m.hidden_states(masked.view(B, T, hw, hw)).clone()
-                    return 0, {"logits": logits, "hidden": hidden}
-                case(tag + "/compute_logits", full)
-
-                n = T - 1
-                cache = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
-
-                def clean():
-                    rc = lib.genie_clean_pass(c, w, ids[:, :n].contiguous().data_ptr(), B, n, n, cache.data_ptr(), nbytes, ws.data_ptr(),
-                                              ws.numel(), st)
-                    return rc, {"cache": cache}
-                case(tag + "/clean_pass", clean)
-                for frame0 in (0, 1):
-                    def masked_pass():
-                        lg = torch.zeros(B, n, S, V, dtype=torch.float32, device="cuda")
-                        rc = lib.genie_masked_frames_logits(c, w, masked[:, frame0:frame0 + n].contiguous().data_ptr(), B, frame0, n,
-                                                            cache.data_ptr(), nbytes, lg.data_ptr(), ws.data_ptr(), ws.numel(), st)
-                        return rc, {"logits": lg}
-                    case(f"{tag}/masked_frames_logits/frame0={frame0}", masked_pass)
-
-                P = T // 2
-                for Bx in (1, 2, B):   # a half-length clean pass into the full-length cache, then decode passes against it
-                    nb = lib.genie_prefix_cache_bytes(c, Bx)
-                    kv = torch.zeros(nb, dtype=torch.uint8, device="cuda")
-
-                    def strided():
-                        rc = lib.genie_clean_pass(c, w, ids[:Bx, :P].contiguous().data_ptr(), Bx, P, T, kv.data_ptr(), nb, ws.data_ptr(),
-                                                  ws.numel(), st)
-                        return rc, {"cache": kv}
-                    case(f"{tag}/clean_pass_into_full_cache/B={Bx}", strided)
-
-                    def frame():
-                        lg = torch.zeros(Bx, S, V, dtype=torch.float32, device="cuda")
-                        rc = lib.genie_frame_pass(c, w, masked[:Bx, P].contiguous().data_ptr(), Bx, P, kv.data_ptr(), nb, lg.data_ptr(),
-                                                  ws.data_ptr(), ws.numel(), st)
-                        return rc, {"logits": lg, "cache": kv}
-                    case(f"{tag}/frame_pass/B={Bx}", frame)
-
-                    def frames():
-                        lg = torch.zeros(Bx, S, V, dtype=torch.float32, device="cuda")
-                        rc = lib.genie_frames_pass(c, w, masked[:Bx, P:P + 2].contiguous().data_ptr(), Bx, P, 2, kv.data_ptr(), nb,
-                                                   lg.data_ptr(), ws.data_ptr(), ws.numel(), st)
-                        return rc, {"logits": lg, "cache": kv}
-                    case(f"{tag}/frames_pass_nf2/B={Bx}", frames)
-
-                noise = torch.rand(T - P, 1, B, S, generator=torch.Generator().manual_seed(3)).cuda()
-
-                def generate():
-                    out = G.generate_frames_cached(m, ids.view(B, T, hw, hw), P, 2, 0.0, False, noise=noise, merge_commit=True)
-                    return 0, {"tokens": out}
-                case(tag + "/generate_cached", generate)
-
-                def block():
-                    x = (0.5 * torch.randn(B, T, S, d, generator=torch.Generator().manual_seed(4))).cuda()
-                    rc = lib.genie_st_block_forward(c, layers[0], x.data_ptr(), B, ws.data_ptr(), ws.numel(), st)
-                    return rc, {"x": x}
-                case(tag + "/st_block_forward", block)
-                del m, ws, cache
-                torch.cuda.empty_cache()
+                model_cases(f"{gname}/{'qknorm' if qk_norm else 'ln'}/{prec}", cfg, sd, prec, B)
+    for tag, prec, B, only, geometry, edit in BRANCH_CASES:
+        cfg = make_cfg(*geometry)
+        sd = synth.make_state_dict(cfg, seed=5, law="conditioned")
+        nonzero_biases(sd, 6)
+        env = {}
+        if edit == "wide":   # one row of every Linear of the block and of the readout reaches |w| >= 32 (tests/test_hip_configs.py)
+            for k in WIDE_TENSORS:
+                sd[k][5] *= 40.0 / np.abs(sd[k][5]).max()
+        elif edit == "no_frame_streams":
+            env = {"GENIE_NO_FRAME_KERNELS": "1"}   # (read by the weight packer: no fragment-order streams -> the layer loop runs the pass)
+        os.environ.update(env)
+        try:
+            model_cases(tag, cfg, sd, prec, B, only)
+        finally:
+            for k in env:
+                del os.environ[k]
     with open(out_path, "w") as f:
         json.dump(record, f)
 
@@ -295,6 +342,13 @@ def inference_proxies(ra):
     sk = ra.get("d512/ln/bf16/frame_pass/B=8", {"kernels": {}})["kernels"]
     print("proxy splitk2_residual: GEMM launches of d512/ln/bf16/frame_pass/B=8 (2,048 rows, hidden 2,048: inside the fc2_splitk2 window):",
           {k: v for k, v in sk.items() if k.startswith("0:")})
+    for name in ("d512/ln/f16x3/frame_pass/B=8", "d512noframe/ln/f16x3/frame_pass/B=8"):   # the same pass on the frame kernels / in the layer loop
+        print(f"proxy splitk2_residual on split planes: GEMM launches of {name}:",
+              {k: v for k, v in ra.get(name, {"kernels": {}})["kernels"].items() if k.startswith("0:")})
+    for name in ("d256nobias/ln/bf16/compute_logits", "d256nobias2/ln/bf16/compute_logits"):
+        # qkv_planes_done: three forwards of two blocks run 6 spatial sub-blocks on 3 qkv GEMMs; below 128 sequences block 1 shows an unnamed
+        # spatial attention launch in place of spatial_attn_proj
+        print(f"proxy qkv_planes_done: launches of {name}:", ra.get(name, {"kernels": {}})["kernels"])
     return missing
 
 
