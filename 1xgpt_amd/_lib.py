@@ -219,6 +219,17 @@ SIGNATURES["genie_rollout_cached"] = (C.c_int, [C.POINTER(GenieCfg), C.POINTER(W
                                                 c_ptr, C.c_int, c_ptr, C.c_size_t, c_ptr, C.c_size_t, c_ptr, C.POINTER(FrameCond),
                                                 C.POINTER(Sampling), C.POINTER(Guidance)])
 
+# fan-out generation: (cfg, NB, K, n_new), (cfg, B, K, P, guided) and (cfg, w, ids, B, K, P, n_new, steps, temperature, unmask_mode, noise,
+# uniforms, merge_commit, gen_out, trunk, trunk_bytes, branch, branch_bytes, workspace, workspace_bytes, stream, cond, sampling, guidance);
+# the decode attention alone: (cfg, aw, trunk_slice, branch_slice, out, NBK, K, P0, Tb, t, in16, stream)
+SIGNATURES["genie_fanout_branch_bytes"] = (C.c_size_t, [C.POINTER(GenieCfg), C.c_int, C.c_int, C.c_int])
+SIGNATURES["genie_fanout_workspace_bytes"] = (C.c_size_t, [C.POINTER(GenieCfg), C.c_int, C.c_int, C.c_int, C.c_int])
+SIGNATURES["genie_generate_fanout"] = (C.c_int, [C.POINTER(GenieCfg), C.POINTER(Weights), c_ptr] + [C.c_int] * 5 + [C.c_float, C.c_int, c_ptr,
+                                                 c_ptr, C.c_int, c_ptr, c_ptr, C.c_size_t, c_ptr, C.c_size_t, c_ptr, C.c_size_t, c_ptr,
+                                                 C.POINTER(FrameCond), C.POINTER(Sampling), C.POINTER(Guidance)])
+SIGNATURES["genie_temporal_attention_decode_fanout"] = (C.c_int, [C.POINTER(GenieCfg), C.POINTER(AttnWeights), c_ptr, c_ptr, c_ptr] + [C.c_int] * 6
+                                                        + [c_ptr])
+
 _lib = None
 
 
@@ -242,7 +253,12 @@ def load():
         # "no ROCm-capable device is detected" on the GPU box.
         import torch  # noqa: F401
         lib = C.CDLL(LIB_PATH)
+        other = bool(os.environ.get("GENIE_HIP_LIBRARY"))
+        missing = []
         for name, (res, args) in SIGNATURES.items():
+            if other and not hasattr(lib, name):   # an A/B against an older build of this ABI: entry points added since stay unbound
+                missing.append(name)
+                continue
             fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         if lib.genie_version() != ABI_VERSION:
@@ -259,8 +275,8 @@ def load():
             raise RuntimeError(f"genie_guidance layout {list(lay)[:3]} != the ctypes declaration {mine}")
         if os.environ.get("GENIE_HIP_LIBRARY") or lib.genie_study_build():
             import sys
-            print(f"1xgpt_amd: using {LIB_PATH} (study build: {bool(lib.genie_study_build())}) -- not the shipping library",
-                  file=sys.stderr)
+            print(f"1xgpt_amd: using {LIB_PATH} (study build: {bool(lib.genie_study_build())}) -- not the shipping library"
+                  + (f"; it lacks {', '.join(missing)}" if missing else ""), file=sys.stderr)
         _lib = lib
     return _lib
 

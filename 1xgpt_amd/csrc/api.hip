@@ -467,17 +467,38 @@ int genie_frames_pass(const genie_cfg* cfg, const genie_weights* wt, const int64
                                   nullptr);
 }
 
-int genie_frames_pass_cond(const genie_cfg* cfg, const genie_weights* wt, const int64_t* frame_ids, int B, int t0, int nf,
-                           float* cache, size_t cache_bytes, float* logits, void* workspace, size_t workspace_bytes,
-                           void* stream, const genie_frame_cond* cond) {
+// The split cache of a fan-out call (genie_generate_fanout): the B clips of a decode pass are K branches each of B / K parent clips.
+// Slots [0, P0) live in `trunk`, a T-slot cache of B / K clips that the context pass filled and no decode pass writes; slot j >= P0 is
+// slot j - P0 of the pass's own cache, (L, B, Tb, S, 3d).
+struct FanOut {
+    const float* trunk;
+    int K, P0, Tb;
+};
+static size_t fanout_branch_bytes(const genie_cfg& c, size_t NBK, int Tb) {
+    return (size_t)c.num_layers * NBK * Tb * c.S * 3 * c.d_model * sizeof(float);
+}
+
+// genie_frames_pass_cond, and with fan != NULL the decode pass of a fan-out call: `cache` is then the branch cache, and every such pass
+// has t0 >= P0 -- nothing writes the trunk after the context pass
+static int frames_pass(const genie_cfg* cfg, const genie_weights* wt, const int64_t* frame_ids, int B, int t0, int nf, float* cache,
+                       size_t cache_bytes, float* logits, void* workspace, size_t workspace_bytes, void* stream,
+                       const genie_frame_cond* cond, const FanOut* fan) {
     GENIE_TRY(check_cfg(cfg));
     GENIE_CHECK_ARG(wt && wt->layers_host && frame_ids && cache, "frames_pass: NULL pointer");
     GENIE_TRY(check_frame_cond(cond, "frames_pass"));
     GENIE_CHECK_ARG(nf >= 1 && t0 >= 0 && t0 + nf <= cfg->T, "frames_pass: frames [%d, %d) out of range", t0, t0 + nf);
-    GENIE_CHECK_ARG(cache_bytes >= genie_prefix_cache_bytes(cfg, B), "frames_pass: cache too small");
-    GENIE_TRY(check_ws(*cfg, B, workspace, workspace_bytes));
     genie_cfg c1 = *cfg;
     c1.T = nf;  // every buffer of this pass is a dense (B, nf, S, *) tensor
+    if (fan) {   // (the call sized its workspace for its own passes, not for B * K clips of T frames)
+        GENIE_CHECK_ARG(B >= 1 && fan->K >= 1 && B % fan->K == 0 && fan->trunk, "frames_pass: %d clips in branches of %d", B, fan->K);
+        GENIE_CHECK_ARG(t0 >= fan->P0 && t0 + nf <= fan->P0 + fan->Tb, "frames_pass: frames [%d, %d) outside the branch slots [%d, %d)", t0,
+                        t0 + nf, fan->P0, fan->P0 + fan->Tb);
+        GENIE_CHECK_ARG(cache_bytes >= fanout_branch_bytes(*cfg, (size_t)B, fan->Tb), "frames_pass: branch cache too small");
+        GENIE_CHECK_ARG(workspace && workspace_bytes >= carve(c1, B, nullptr).total, "frames_pass: workspace too small");
+    } else {
+        GENIE_CHECK_ARG(cache_bytes >= genie_prefix_cache_bytes(cfg, B), "frames_pass: cache too small");
+        GENIE_TRY(check_ws(*cfg, B, workspace, workspace_bytes));
+    }
     // the fragment-order kernels (kernels_frame.hip) take the pass when they cover every layer; several frames per pass exist
     // only there
     // (the decode attention kernel holds 16 cache slots; the readout Linear writes 64-column tiles with no tail handling)
@@ -494,8 +515,13 @@ int genie_frames_pass_cond(const genie_cfg* cfg, const genie_weights* wt, const 
     w1.pos_embed = wt->pos_embed + (size_t)t0 * cfg->S * cfg->d_model;  // pos_embed_TSC[0, t0 + i]
     EmbedAct act;   // ... and the action of clip frame t0 + i
     GENIE_TRY(launch_embed(c1, w1, frame_ids, B, w.x, st, frame_act(cond, cfg->S, t0, cfg->T, act)));
-    const size_t per_layer = (size_t)B * cfg->T * cfg->S * 3 * cfg->d_model;
-    auto make = [&](int i, const genie_layer_weights* next) { return BlockPass::decode(c1, next, cfg->T, cache + i * per_layer, t0); };
+    const size_t slot = (size_t)cfg->S * 3 * cfg->d_model;
+    const size_t per_layer = (size_t)B * (fan ? fan->Tb : cfg->T) * slot, per_trunk = fan ? (size_t)(B / fan->K) * cfg->T * slot : 0;
+    auto make = [&](int i, const genie_layer_weights* next) {
+        if (fan)
+            return BlockPass::decode_fanout(c1, next, cfg->T, cache + i * per_layer, t0, fan->trunk + i * per_trunk, fan->P0, fan->K, fan->Tb);
+        return BlockPass::decode(c1, next, cfg->T, cache + i * per_layer, t0);
+    };
     if (!fr) {
         GENIE_TRY(run_layers(c1, wt->layers_host, c1.num_layers, w.x, w, B, st, make));
     } else {
@@ -508,6 +534,12 @@ int genie_frames_pass_cond(const genie_cfg* cfg, const genie_weights* wt, const 
     if (!logits) return GENIE_OK;
     if (fr) return readout_frame_f16x3(c1, *wt, w, B, nf, nf - 1, logits, st);
     return readout(c1, *wt, w.x, w, B, 0, 1, GENIE_LAYOUT_TOKEN_MAJOR, logits, st);
+}
+
+int genie_frames_pass_cond(const genie_cfg* cfg, const genie_weights* wt, const int64_t* frame_ids, int B, int t0, int nf,
+                           float* cache, size_t cache_bytes, float* logits, void* workspace, size_t workspace_bytes,
+                           void* stream, const genie_frame_cond* cond) {
+    return frames_pass(cfg, wt, frame_ids, B, t0, nf, cache, cache_bytes, logits, workspace, workspace_bytes, stream, cond, nullptr);
 }
 
 int genie_frame_pass(const genie_cfg* cfg, const genie_weights* wt, const int64_t* frame_ids, int B, int t, float* cache,
@@ -565,18 +597,20 @@ static size_t generate_scratch_offset(const genie_cfg& c, int B, int P) {
 
 // The loop scratch of genie_generate_cached_*: B clips are decoded, NB clips run through every pass (NB == B, or 2 B under guidance:
 // [conditional ; null]).  The size functions and the loop both carve here (base == NULL: sizes only).
+// A fan-out call (genie_generate_fanout) carves the same buffers: its context runs NBctx = NB / K clips, and it keeps their (NBctx, T)
+// actions beside the branches' (NB, T).
 struct GenScratch {
-    int64_t *idsP, *two, *cur, *fin, *samples, *acts;
+    int64_t *idsP, *two, *cur, *fin, *samples, *acts, *acts_ctx;
     float *conf, *logits;
     uint8_t* unmasked;
     size_t end;
 };
-static GenScratch carve_generate(const genie_cfg& c, int B, int NB, int P, char* base, bool window_acts = false) {
+// off: where the scratch starts; NBctx: clips of the context pass (idsP)
+static GenScratch carve_loop(const genie_cfg& c, int B, int NB, int NBctx, int P, size_t off, char* base, bool acts) {
     const size_t BS = (size_t)B * c.S, NBS = (size_t)NB * c.S, V = (size_t)c.factored_vocab * c.num_factored;
-    size_t off = generate_scratch_offset(c, NB, P);
     auto take = [&](size_t bytes) { char* r = base ? base + off : nullptr; off += align_up(bytes, 256); return r; };
     GenScratch g;
-    g.idsP = (int64_t*)take(NBS * P * 8);
+    g.idsP = (int64_t*)take((size_t)NBctx * c.S * P * 8);
     g.two = (int64_t*)take(NBS * 2 * 8);
     g.cur = (int64_t*)take(NBS * 8);
     g.fin = (int64_t*)take(NBS * 8);
@@ -584,9 +618,23 @@ static GenScratch carve_generate(const genie_cfg& c, int B, int NB, int P, char*
     g.conf = (float*)take(BS * 4);
     g.unmasked = (uint8_t*)take(BS);
     g.logits = (float*)take(NBS * V * 4);
-    g.acts = (NB != B || window_acts) ? (int64_t*)take((size_t)NB * c.T * 8) : nullptr;   // window_acts: the rollout's action window
+    g.acts = acts ? (int64_t*)take((size_t)NB * c.T * 8) : nullptr;
+    g.acts_ctx = NBctx != NB ? (int64_t*)take((size_t)NBctx * c.T * 8) : nullptr;
     g.end = off;
     return g;
+}
+static GenScratch carve_generate(const genie_cfg& c, int B, int NB, int P, char* base, bool window_acts = false) {
+    return carve_loop(c, B, NB, NB, P, generate_scratch_offset(c, NB, P), base, NB != B || window_acts);   // window_acts: the rollout's action window
+}
+// ... of genie_generate_fanout: B * K clips are decoded, NB * K run through every decode pass, NB through the context pass.  The scratch
+// starts behind the larger of the context pass (NB clips, P frames) and a two-frame pass of NB * K clips.
+static GenScratch carve_fanout(const genie_cfg& c, int B, int NB, int K, int P, char* base) {
+    genie_cfg cm = c;
+    cm.T = P;
+    const size_t ctx = carve(cm, NB, nullptr).total;
+    cm.T = 2;
+    const size_t two = carve(cm, NB * K, nullptr).total;
+    return carve_loop(c, B * K, NB * K, NB, P, ctx > two ? ctx : two, base, true);
 }
 // ... of genie_maskgit_generate_guided behind the model's workspace for 2 B clips: the doubled prompt and the (2B, T) actions
 struct GuidedPrompt {
@@ -654,6 +702,7 @@ struct GenLoop {
     size_t workspace_bytes;
     void* stream;
     GenScratch g;
+    const FanOut* fan = nullptr;    // a fan-out call's decode passes: `cache` is the branch cache (the context ran into fan->trunk)
 };
 // the decode options every loop entry point takes, checked on the host before anything is enqueued
 static int check_decode(int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
@@ -712,18 +761,21 @@ static int decode_slots(const GenLoop& L, int t0, int n, const float* noise, con
     uint8_t* unmasked = L.g.unmasked;
     const float* logits_null = logits + BS * V;   // guided: rows B .. 2B - 1 of every pass's logits
     bool opened = false, merge = L.merge_commit != 0;
+    auto pass = [&](const int64_t* frame_ids, int t, int nf, float* lg) {
+        return frames_pass(cfg, wt, frame_ids, NB, t, nf, cache, cache_bytes, lg, workspace, workspace_bytes, stream, cond, L.fan);
+    };
     // commit slot t from fsrc: in the pass that also carries MaskGIT step 0 of slot t + 1 (all-mask tokens), or on its own
     auto commit = [&](int t, const int64_t* fsrc, long fstride) -> int {
         if (merge) {
             GENIE_TRY(put_frame_ids(fsrc, fstride, two, 2L * S, S, B, 0, st, copies));
             GENIE_TRY(put_frame_ids(nullptr, 0, two + S, 2L * S, S, B, c.image_vocab_size, st, copies));
-            const int rc = genie_frames_pass_cond(cfg, wt, two, NB, t, 2, cache, cache_bytes, logits, workspace, workspace_bytes, stream, cond);
+            const int rc = pass(two, t, 2, logits);
             if (rc == GENIE_E_UNSUPPORTED) merge = false;
             else { GENIE_TRY(rc); opened = true; }
         }
         if (!opened) {
             GENIE_TRY(put_frame_ids(fsrc, fstride, fin, S, S, B, 0, st, copies));
-            GENIE_TRY(genie_frames_pass_cond(cfg, wt, fin, NB, t, 1, cache, cache_bytes, nullptr, workspace, workspace_bytes, stream, cond));
+            GENIE_TRY(pass(fin, t, 1, nullptr));
         }
         return GENIE_OK;
     };
@@ -734,7 +786,7 @@ static int decode_slots(const GenLoop& L, int t0, int n, const float* noise, con
         if (hipMemsetAsync(unmasked, 0, BS, st) != hipSuccess) { set_error("memset failed"); return GENIE_E_LAUNCH; }
         for (int step = 0; step < steps; ++step) {
             if (!(step == 0 && opened))
-                GENIE_TRY(genie_frames_pass_cond(cfg, wt, cur, NB, t, 1, cache, cache_bytes, logits, workspace, workspace_bytes, stream, cond));
+                GENIE_TRY(pass(cur, t, 1, logits));
             if (step == 0 && logits0_out) {   // orig_logits of the frame (st_mask_git.py:165,226): the step-0 logits, (B, n, S, V)
                 if (guided) {                 // ... the guided ones
                     GENIE_TRY(launch_guide_logits(logits, logits_null, logits0_out + (size_t)k * S * V, B, (long)(S * V), (long)(S * V),
@@ -925,6 +977,109 @@ int genie_generate_cached_guided(const genie_cfg* cfg, const genie_weights* wt, 
                                  const genie_frame_cond* cond, const genie_sampling* sampling, const genie_guidance* guidance) {
     return generate_cached_loop(cfg, wt, ids, B, P, n_new, steps, temperature, unmask_mode, noise, uniforms, teacher_force_time, merge_commit,
                                 gen_out, logits0_out, cache, cache_bytes, workspace, workspace_bytes, stream, cond, sampling, guidance);
+}
+
+// ---- fan-out generation: K futures per clip over one shared context cache ------------------------------------------------
+// The (NB, T) actions of the context pass and the (NB * K, T) actions of the decode passes from the caller's (B * K, T) ids, null halves
+// included: parent b reads its context actions from its branch 0 (row b * K; frames < P of the other branches are never read).
+__global__ void fanout_actions_kernel(const int64_t* __restrict__ ids, int64_t* __restrict__ ctx_out, int64_t* __restrict__ br_out, int B, int K,
+                                      int NB, int T, int P, int64_t null_action) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long nctx = (long)NB * T, BK = (long)B * K;
+    if (i < nctx) {
+        const long r = i / T, f = i - r * T;
+        ctx_out[i] = r >= B ? null_action : ids[r * K * T + f];
+        return;
+    }
+    const long a = i - nctx;
+    if (a >= nctx * K) return;
+    const long r = a / T, f = a - r * T;
+    br_out[a] = r >= BK ? null_action : ids[(f < P ? r / K * K : r) * T + f];
+}
+
+// NB * K as an int the passes can take, or 0
+static int fanout_clips(int B, int K, bool guided) {
+    if (B < 1 || K < 1) return 0;
+    const long n = (long)B * K * (guided ? 2 : 1);
+    return n <= 0x3fffffff ? (int)n : 0;
+}
+
+size_t genie_fanout_branch_bytes(const genie_cfg* cfg, int NB, int K, int n_new) {
+    if (check_cfg(cfg) != GENIE_OK || !fanout_clips(NB, K, false) || n_new < 1 || n_new > cfg->T - 1) return 0;
+    return fanout_branch_bytes(*cfg, (size_t)NB * K, n_new);
+}
+
+size_t genie_fanout_workspace_bytes(const genie_cfg* cfg, int B, int K, int P, int guided) {
+    if (check_cfg(cfg) != GENIE_OK || !fanout_clips(B, K, guided != 0) || P < 1 || P > cfg->T - 1) return 0;
+    const int NB = guided ? 2 * B : B;
+    const size_t off = carve_fanout(*cfg, B, NB, K, P, nullptr).end;
+    const size_t full = carve(*cfg, NB, nullptr).total;   // (the context passes check against the model's own workspace size)
+    return off > full ? off : full;
+}
+
+int genie_generate_fanout(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int K, int P, int n_new, int steps,
+                          float temperature, int unmask_mode, const float* noise, const float* uniforms, int merge_commit, int64_t* gen_out,
+                          float* trunk, size_t trunk_bytes, float* branch, size_t branch_bytes, void* workspace, size_t workspace_bytes,
+                          void* stream, const genie_frame_cond* cond, const genie_sampling* sampling, const genie_guidance* guidance) {
+    GENIE_TRY(check_cfg(cfg));
+    const genie_cfg& c = *cfg;
+    GENIE_TRY(check_frame_cond(cond, "generate_fanout"));
+    GENIE_TRY(check_guidance(guidance, cond, "generate_fanout"));
+    GENIE_CHECK_ARG(B >= 1 && K >= 1 && P >= 1 && n_new >= 1 && P + n_new <= c.T && steps >= 1,
+                    "generate_fanout: B=%d, K=%d, %d prompt + %d new frames of at most %d, steps %d", B, K, P, n_new, c.T, steps);
+    GENIE_TRY(check_decode(steps, temperature, unmask_mode, noise, uniforms, sampling, "generate_fanout"));
+    const bool by_conf = unmask_mode == GENIE_UNMASK_CONFIDENCE, guided = guidance && guidance->scale != 1.0f;
+    const int NBK = fanout_clips(B, K, guided);
+    GENIE_CHECK_ARG(NBK > 0, "generate_fanout: B=%d x K=%d%s clips per pass are too many", B, K, guided ? " x 2" : "");
+    const int NB = guided ? 2 * B : B, copies = guided ? 2 : 1, BK = B * K;
+    GENIE_CHECK_ARG(wt && wt->layers_host && ids && gen_out && trunk && branch && workspace, "generate_fanout: NULL pointer");
+    GENIE_CHECK_ARG(trunk_bytes >= genie_prefix_cache_bytes(cfg, NB), "generate_fanout: trunk cache too small (genie_prefix_cache_bytes of %d clips)", NB);
+    GENIE_CHECK_ARG(branch_bytes >= fanout_branch_bytes(c, (size_t)NBK, n_new), "generate_fanout: branch cache too small (genie_fanout_branch_bytes)");
+    const GenScratch g = carve_fanout(c, B, NB, K, P, (char*)workspace);
+    const size_t full = carve(c, NB, nullptr).total;
+    GENIE_CHECK_ARG(workspace_bytes >= g.end && workspace_bytes >= full, "generate_fanout: workspace too small (%zu < %zu bytes: size it with "
+                    "genie_fanout_workspace_bytes)", workspace_bytes, g.end > full ? g.end : full);
+    hipStream_t st = as_stream(stream);
+    const int S = c.S;
+    const genie_sampling* law = (by_conf && !sampling) ? &kDefaultSampling : sampling;
+    // the context of the NB clips runs once, into the trunk; its actions and the branches' come from one launch
+    genie_frame_cond cond_ctx, cond_br;
+    const bool acts = cond && cond->n_actions > 0;
+    if (acts) {
+        const long n = (long)NB * c.T * (1 + K);
+        fanout_actions_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(cond->ids, g.acts_ctx ? g.acts_ctx : g.acts, g.acts, B, K, NB, c.T, P,
+                                                                           guided ? guidance->null_action : 0);
+        GENIE_LAUNCH_CHECK("fanout_actions");
+        cond_ctx = cond_br = *cond;
+        cond_ctx.ids = g.acts_ctx ? g.acts_ctx : g.acts;   // (K == 1: one table serves both)
+        cond_br.ids = g.acts;
+    }
+    GenLoop Lc = {cfg, wt, B, NB, copies, steps, unmask_mode, merge_commit, temperature, law, guidance, guided, acts ? &cond_ctx : cond,
+                  trunk, trunk_bytes, workspace, workspace_bytes, stream, g};
+    GENIE_TRY(put_frame_ids(ids, (long)P * S, g.idsP, (long)P * S, P * S, B, 0, st, copies));
+    GENIE_TRY(run_context(Lc, P, ids, (long)P * S));
+    // ... then the loop of genie_generate_cached decodes B * K clips over the split cache, starting at slot P with nothing pending
+    const FanOut fan = {trunk, K, P, n_new};
+    const GenLoop Lb = {cfg, wt, BK, NBK, copies, steps, unmask_mode, merge_commit, temperature, law, guidance, guided, acts ? &cond_br : cond,
+                        branch, branch_bytes, workspace, workspace_bytes, stream, g, &fan};
+    return decode_slots(Lb, P, n_new, noise, uniforms, gen_out, (long)n_new * S, nullptr, nullptr, 0, nullptr, 0);
+}
+
+int genie_temporal_attention_decode_fanout(const genie_cfg* cfg, const genie_attn_weights* aw, const float* trunk_slice,
+                                           const float* branch_slice, float* out, int NBK, int K, int P0, int Tb, int t, int in16,
+                                           void* stream) {
+    GENIE_CHECK_ARG(cfg && aw && branch_slice && out, "temporal_attention_decode_fanout: NULL pointer");
+    const genie_cfg& c = *cfg;   // (only the attention geometry is read: head_dim 8 is not a model's, but it is this kernel's)
+    GENIE_CHECK_SHAPE(c.num_heads >= 1 && c.d_model == c.num_heads * c.head_dim && c.S >= 1 && c.T >= 1 && c.T <= 64,
+                      "temporal_attention_decode_fanout: d_model %d, %d heads of %d, S=%d, T=%d", c.d_model, c.num_heads, c.head_dim, c.S, c.T);
+    GENIE_CHECK_ARG(NBK >= 1 && K >= 1 && NBK % K == 0, "temporal_attention_decode_fanout: %d clips in branches of %d", NBK, K);
+    GENIE_CHECK_ARG(P0 >= 0 && P0 <= t && t < c.T && Tb >= 1 && t - P0 < Tb, "temporal_attention_decode_fanout: slot %d, trunk slots [0, %d) of %d, "
+                    "%d branch slots", t, P0, c.T, Tb);
+    GENIE_CHECK_ARG(trunk_slice || P0 == 0, "temporal_attention_decode_fanout: NULL trunk with P0 = %d", P0);
+    GENIE_CHECK_ARG(!c.qk_norm || (aw->norm_w && aw->norm_b), "temporal_attention_decode_fanout: qk_norm without norm_w / norm_b");
+    return launch_attn_temporal_single_fanout(branch_slice, out, NBK, Tb, c.S, t, c.d_model, c.num_heads, c.head_dim, c.attn_scale,
+                                              c.qk_norm ? aw->norm_w : nullptr, c.qk_norm ? aw->norm_b : nullptr, as_stream(stream), nullptr, 0,
+                                              in16 != 0, FanSplit<true>{trunk_slice ? trunk_slice : branch_slice, c.T, P0, K});
 }
 
 int genie_pack_frame_w16(const float* src, uint16_t* dst, int N, int K, void* stream) {

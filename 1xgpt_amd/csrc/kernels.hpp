@@ -28,6 +28,9 @@ struct Workspace {
 //   PREFIX  ... second half (masked-frames pass): temporal attention takes keys j < i + tshift from the cached qkv
 //   DECODE  single-frame decode (generate with a temporal KV cache): the block runs on dense (B, nf, S, *) buffers; its temporal qkv is
 //           written into slot `frame_t` of this layer's cache slice and the attention reads slots 0..frame_t
+//           fan-out flavour (decode_fanout): the B clips of the pass are K branches each of B / K parents.  Slots < fan_P0 are read from the
+//           parent's clip of `trunk` (an ordinary model_T-slot slice of B / K clips, never written here); slot j >= fan_P0 is slot
+//           j - fan_P0 of the clip's own `cache`, a slice of frame_T = Tb slots per clip
 struct BlockPass {
     enum Kind { PLAIN, CLEAN, PREFIX, DECODE };
     const Kind kind;
@@ -45,6 +48,9 @@ struct BlockPass {
     // refresh the 16-bit shadow of x, and the GENIE_PREC_BF16 fused MLP kernel can apply that norm1 in its epilogue (BlockCarry)
     const genie_layer_weights* const next_layer;
     const bool next_is_ln;
+    const float* const trunk = nullptr;   // DECODE, fan-out: this layer's slice of the shared context cache (NULL: an ordinary decode pass)
+    const int fan_P0 = 0;                 // ... its slots [0, fan_P0) are the ones read; 0 in an ordinary decode pass
+    const int fan_K = 1;                  // ... branches per parent clip
 
     static BlockPass plain(const genie_cfg& c, const genie_layer_weights* next, int model_T) {
         return {PLAIN, nullptr, 0, 0, -1, 0, model_T, false, next, next && !c.qk_norm};
@@ -58,7 +64,12 @@ struct BlockPass {
     static BlockPass decode(const genie_cfg& c, const genie_layer_weights* next, int model_T, float* slice, int frame_t) {
         return {DECODE, slice, 0, 0, frame_t, model_T, model_T, false, next, next && !c.qk_norm};
     }
+    static BlockPass decode_fanout(const genie_cfg& c, const genie_layer_weights* next, int model_T, float* branch_slice, int frame_t,
+                                   const float* trunk_slice, int P0, int K, int Tb) {
+        return {DECODE, branch_slice, 0, 0, frame_t, Tb, model_T, false, next, next && !c.qk_norm, trunk_slice, P0, K};
+    }
     bool is_plain() const { return kind == PLAIN; }
+    bool is_fanout() const { return trunk != nullptr; }
     bool is_decode() const { return kind == DECODE; }
     bool writes_cache() const { return kind == CLEAN; }   // (DECODE writes its slot too, through its own GEMM shape)
     bool reads_cache() const { return kind == PREFIX; }
@@ -189,6 +200,20 @@ int launch_attn_spatial_split(const float* qkv, float* out, int S, long n_seq, i
 int launch_attn_temporal_single(const float* cache, float* out, int B, int T, int S, int t, int d, int H, int Dh,
                                 float scale, const float* nw, const float* nb, hipStream_t st,
                                 uint16_t* out16 = nullptr, size_t plane = 0, bool in16 = false);
+// The split cache of a fan-out decode pass as the decode attention kernels see it (BlockPass::decode_fanout): clip i reads slots
+// j < P0 at trunk + ((i / K) * T + j) * S * 3d and slots j >= P0 at branch + (i * Tb + (j - P0)) * S * 3d.  The ordinary flavour carries
+// nothing: its instantiations are the kernels without the split.
+template <bool FAN>
+struct FanSplit {};
+template <>
+struct FanSplit<true> {
+    const void* trunk;   // same element type as the branch slice
+    int T, P0, K;        // slots per clip of the trunk; first branch slot; branches per parent
+};
+// launch_attn_temporal_single over that split cache: `cache` is the branch slice and T its slots per clip (Tb); t >= fan.P0
+int launch_attn_temporal_single_fanout(const float* cache, float* out, int B, int T, int S, int t, int d, int H, int Dh, float scale,
+                                       const float* nw, const float* nb, hipStream_t st, uint16_t* out16, size_t plane, bool in16,
+                                       const FanSplit<true>& fan);
 int launch_attn_temporal_prefix(const float* cur, const float* cache, float* out, int B, int T, int S, int d, int H,
                                 int Dh, float scale, const float* nw, const float* nb, hipStream_t st,
                                 uint16_t* out16 = nullptr, size_t plane = 0, int sh = 0, bool in16 = false);
@@ -360,7 +385,7 @@ int launch_linear_lowp(int precision, const uint16_t* x16, const uint16_t* W16, 
 // (One description of the GEMM in place of the three copies of its decode / strided / dense shape logic in the drivers.)
 // Where the temporal qkv GEMM of a pass writes and how it is batched: `base + off` (f32 elements; a bf16 qkv lives at the same element
 // offset of the same base), `rows` rows per batch entry, `batch` entries strideA / strideC elements apart.
-//   DECODE: slot frame_t of the cache slice, one entry per clip;  a short CLEAN pass into a longer cache at B > 1: one entry per clip;
+//   DECODE: slot frame_t of the cache slice (fan-out: slot frame_t - fan_P0 of the branch slice), one entry per clip;  a short CLEAN pass into a longer cache at B > 1: one entry per clip;
 //   otherwise ONE dense (M, 3d) GEMM into the cache slice (CLEAN) or into `dense`
 struct TemporalQkv {
     float* base;
@@ -371,7 +396,7 @@ struct TemporalQkv {
 inline TemporalQkv temporal_qkv_target(const genie_cfg& c, const BlockPass& p, float* dense, int B) {
     const int d = c.d_model, Tq = p.tq_stride(c.T);
     if (p.is_decode())
-        return {p.cache, (size_t)p.frame_t * c.S * 3 * d, c.S, B, (long)c.S * d, (long)p.frame_T * c.S * 3 * d};
+        return {p.cache, (size_t)(p.frame_t - p.fan_P0) * c.S * 3 * d, c.S, B, (long)c.S * d, (long)p.frame_T * c.S * 3 * d};
     float* base = p.writes_cache() ? p.cache : dense;
     if (Tq != c.T && B > 1) return {base, 0, c.T * c.S, B, (long)c.T * c.S * d, (long)Tq * c.S * 3 * d};
     return {base, 0, B * c.T * c.S, 1, 0, 0};

@@ -1958,14 +1958,29 @@ int launch_attn_temporal_prefix(const float* cur, const float* cache, float* out
 // written into slot t): the decode step of the temporal KV cache used by generate().  One wavefront per
 // (b, s, head), lane = feature; T <= 64 scores live in registers of lane 0..t after wave reductions.
 // out: dense (B, S, d) f32 / bf16 / split-f16.
+// FAN: the split cache of a fan-out decode pass (FanSplit, kernels.hpp) -- `cache` is the branch slice with T = Tb slots per clip,
+// slots below fan.P0 come from the parent's clip of the trunk; the base pointer is chosen per frame, after the clamp.  Same
+// arithmetic in the same order as the ordinary flavour (FAN = false: the kernel without the split), and no score array: with
+// t >= 16 score j stays in lane j instead of an indexed (scratch) array.
 // ------------------------------------------------------------------------------------------------
-template <int DH, typename TI>
+// cache slot j of one (clip, position, head): `own` + j slots, or (FAN) the trunk below P0 and slot j - P0 of the branch from P0 on
+template <bool FAN, typename TI>
+__device__ __forceinline__ const TI* fan_slot(const TI* own, const TI* trunk, int j, int P0, size_t tok) {
+    if constexpr (FAN) {
+        const bool lo = j < P0;
+        return (lo ? trunk : own) + (size_t)(lo ? j : j - P0) * tok;
+    } else {
+        return own + (size_t)j * tok;
+    }
+}
+
+template <int DH, typename TI, bool FAN>
 __global__ __launch_bounds__(256) void attn_temporal_single_kernel(const TI* __restrict__ cache,
                                                                    float* __restrict__ out, long n_items, int T, int S,
                                                                    int t, int d, int H, float scale,
                                                                    const float* __restrict__ nw,
                                                                    const float* __restrict__ nb,
-                                                                   uint16_t* __restrict__ out16, size_t plane) {
+                                                                   uint16_t* __restrict__ out16, size_t plane, FanSplit<FAN> fan) {
     const int lane = threadIdx.x & 63;
     const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (item >= n_items) return;
@@ -1975,6 +1990,12 @@ __global__ __launch_bounds__(256) void attn_temporal_single_kernel(const TI* __r
     const bool act = lane < DH;
     const size_t tok_stride = (size_t)S * 3 * d;
     const TI* base = cache + ((size_t)(b * T) * S + s) * 3 * d + head * DH + (act ? lane : 0);
+    const TI* tbase = nullptr;   // FAN: the same (position, head, lane) of the parent's clip of the trunk
+    int P0 = 0;
+    if constexpr (FAN) {
+        tbase = static_cast<const TI*>(fan.trunk) + ((size_t)((b / fan.K) * fan.T) * S + s) * 3 * d + head * DH + (act ? lane : 0);
+        P0 = fan.P0;
+    }
     auto norm = [&](float v) {  // qk-norm over the DH active lanes
         if (!nw) return v;
         const float mu = wave_sum(act ? v : 0.f) / DH;
@@ -1992,12 +2013,14 @@ __global__ __launch_bounds__(256) void attn_temporal_single_kernel(const TI* __r
             constexpr int CH = DH / 4;
             const int j = lane >> 2, c4 = lane & 3;
             const TI* hb = cache + ((size_t)(b * T) * S + s) * 3 * d + head * DH;
+            const TI* thb = nullptr;
+            if constexpr (FAN) thb = static_cast<const TI*>(fan.trunk) + ((size_t)((b / fan.K) * fan.T) * S + s) * 3 * d + head * DH;
             float qv[CH], kv[CH], vj[16];
-            load_vals<CH>(hb + (size_t)t * tok_stride + c4 * CH, qv);
-            load_vals<CH>(hb + (size_t)(j <= t ? j : t) * tok_stride + d + c4 * CH, kv);
+            load_vals<CH>(fan_slot<FAN>(hb, thb, t, P0, tok_stride) + c4 * CH, qv);
+            load_vals<CH>(fan_slot<FAN>(hb, thb, j <= t ? j : t, P0, tok_stride) + d + c4 * CH, kv);
 #pragma unroll
             for (int jj = 0; jj < 16; ++jj)   // (frames past t re-read frame t, branch-free: their probability is 0)
-                vj[jj] = load_val(hb + (size_t)(jj <= t ? jj : t) * tok_stride + 2 * d + (act ? lane : 0));
+                vj[jj] = load_val(fan_slot<FAN>(hb, thb, jj <= t ? jj : t, P0, tok_stride) + 2 * d + (act ? lane : 0));
             // (ties the score arithmetic behind the issue of the value loads: one memory round trip, not two)
             asm volatile("" : "+v"(qv[0]), "+v"(kv[0]) :: "memory");
             float part = 0.f;
@@ -2025,7 +2048,7 @@ __global__ __launch_bounds__(256) void attn_temporal_single_kernel(const TI* __r
             return;
         }
     }
-    float q = norm(load_val(base + (size_t)t * tok_stride)) * scale;
+    float q = norm(load_val(fan_slot<FAN>(base, tbase, t, P0, tok_stride))) * scale;
     if (!act) q = 0.f;
     if (t < 16) {
         // the shipped window (T = 16): every cached key / value of the (position, head) is fetched up front -- 2 (t + 1)
@@ -2035,7 +2058,7 @@ __global__ __launch_bounds__(256) void attn_temporal_single_kernel(const TI* __r
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             kj[j] = 0.f; vj[j] = 0.f;
-            if (j <= t) { kj[j] = load_val(base + (size_t)j * tok_stride + d); vj[j] = load_val(base + (size_t)j * tok_stride + 2 * d); }
+            if (j <= t) { kj[j] = load_val(fan_slot<FAN>(base, tbase, j, P0, tok_stride) + d); vj[j] = load_val(fan_slot<FAN>(base, tbase, j, P0, tok_stride) + 2 * d); }
         }
         float mx16 = -INFINITY;
 #pragma unroll
@@ -2062,6 +2085,29 @@ __global__ __launch_bounds__(256) void attn_temporal_single_kernel(const TI* __r
         else out16[oi16] = f32_to_bf16(o16);
         return;
     }
+    if constexpr (FAN) {
+        // every lane holds the same wave_sum, so lane j keeps score j; exp runs once per lane, and the sum and P.V read lane j's value
+        // in the order j = 0 .. t of the array loops below
+        float mine = 0.f, mxf = -INFINITY;
+        for (int j = 0; j <= t; ++j) {
+            const float kj = norm(load_val(fan_slot<FAN>(base, tbase, j, P0, tok_stride) + d));
+            const float a = wave_sum(act ? q * kj : 0.f);
+            mine = lane == j ? a : mine;
+            mxf = fmaxf(mxf, a);
+        }
+        mine = expf(mine - mxf);
+        float sumf = 0.f;
+        for (int j = 0; j <= t; ++j) sumf += __shfl(mine, j);
+        const float invf = 1.0f / sumf;
+        float of = 0.f;
+        for (int j = 0; j <= t; ++j) of = fmaf(__shfl(mine, j) * invf, load_val(fan_slot<FAN>(base, tbase, j, P0, tok_stride) + 2 * d), of);
+        if (!act) return;
+        const size_t oif = (size_t)bs * d + head * DH + lane;
+        if (!out16) out[oif] = of;
+        else if (plane) { uint16_t hi, lo; split_f16(of, hi, lo); out16[oif] = hi; out16[plane + oif] = lo; }
+        else out16[oif] = f32_to_bf16(of);
+        return;
+    }
     float sc[64];
     float mx = -INFINITY;
     for (int j = 0; j <= t; ++j) {
@@ -2082,18 +2128,21 @@ __global__ __launch_bounds__(256) void attn_temporal_single_kernel(const TI* __r
     else out16[oi] = f32_to_bf16(o);
 }
 
-int launch_attn_temporal_single(const float* cache, float* out, int B, int T, int S, int t, int d, int H, int Dh,
-                                float scale, const float* nw, const float* nb, hipStream_t st, uint16_t* out16,
-                                size_t plane, bool in16) {
-    GENIE_CHECK_SHAPE(T <= 64 && t >= 0 && t < T, "temporal_single: bad frame %d of %d", t, T);
+// fan != NULL: the fan-out flavour (launch_attn_temporal_single_fanout)
+static int attn_temporal_single_launch(const float* cache, float* out, int B, int T, int S, int t, int d, int H, int Dh, float scale,
+                                       const float* nw, const float* nb, hipStream_t st, uint16_t* out16, size_t plane, bool in16,
+                                       const FanSplit<true>* fan) {
     const long n = (long)B * S * H;
     ProfScope prof(GENIE_KC_ATTN_TEMPORAL, 4.0 * (t + 1) * Dh * (double)n, (double)n * Dh * (in16 ? 2.0 : 4.0) * (2 * t + 4), st);
     const unsigned blocks = (unsigned)((n + 3) / 4);
     const uint16_t* c16 = reinterpret_cast<const uint16_t*>(cache);
+    const FanSplit<false> none;
 #define SINGLE(DH_)                                                                                                          \
     case DH_:                                                                                                                \
-        if (in16) attn_temporal_single_kernel<DH_, uint16_t><<<blocks, 256, 0, st>>>(c16, out, n, T, S, t, d, H, scale, nw, nb, out16, plane); \
-        else attn_temporal_single_kernel<DH_, float><<<blocks, 256, 0, st>>>(cache, out, n, T, S, t, d, H, scale, nw, nb, out16, plane);     \
+        if (fan && in16) attn_temporal_single_kernel<DH_, uint16_t, true><<<blocks, 256, 0, st>>>(c16, out, n, T, S, t, d, H, scale, nw, nb, out16, plane, *fan); \
+        else if (fan) attn_temporal_single_kernel<DH_, float, true><<<blocks, 256, 0, st>>>(cache, out, n, T, S, t, d, H, scale, nw, nb, out16, plane, *fan);     \
+        else if (in16) attn_temporal_single_kernel<DH_, uint16_t, false><<<blocks, 256, 0, st>>>(c16, out, n, T, S, t, d, H, scale, nw, nb, out16, plane, none); \
+        else attn_temporal_single_kernel<DH_, float, false><<<blocks, 256, 0, st>>>(cache, out, n, T, S, t, d, H, scale, nw, nb, out16, plane, none);     \
         break;
     switch (Dh) {
         SINGLE(8) SINGLE(16) SINGLE(32) SINGLE(64)
@@ -2102,6 +2151,22 @@ int launch_attn_temporal_single(const float* cache, float* out, int B, int T, in
 #undef SINGLE
     GENIE_LAUNCH_CHECK("attn_temporal_single");
     return GENIE_OK;
+}
+
+int launch_attn_temporal_single(const float* cache, float* out, int B, int T, int S, int t, int d, int H, int Dh,
+                                float scale, const float* nw, const float* nb, hipStream_t st, uint16_t* out16,
+                                size_t plane, bool in16) {
+    GENIE_CHECK_SHAPE(T <= 64 && t >= 0 && t < T, "temporal_single: bad frame %d of %d", t, T);
+    return attn_temporal_single_launch(cache, out, B, T, S, t, d, H, Dh, scale, nw, nb, st, out16, plane, in16, nullptr);
+}
+
+int launch_attn_temporal_single_fanout(const float* cache, float* out, int B, int T, int S, int t, int d, int H, int Dh, float scale,
+                                       const float* nw, const float* nb, hipStream_t st, uint16_t* out16, size_t plane, bool in16,
+                                       const FanSplit<true>& fan) {
+    GENIE_CHECK_SHAPE(fan.T <= 64 && fan.K >= 1 && B % fan.K == 0 && fan.P0 >= 0 && fan.P0 <= t && t - fan.P0 < T && t < fan.T,
+                      "temporal_single (fan-out): frame %d, trunk slots [0, %d) of %d, %d branch slots, %d clips in branches of %d", t, fan.P0,
+                      fan.T, T, B, fan.K);
+    return attn_temporal_single_launch(cache, out, B, T, S, t, d, H, Dh, scale, nw, nb, st, out16, plane, in16, &fan);
 }
 
 }  // namespace genie

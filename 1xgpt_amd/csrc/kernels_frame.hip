@@ -822,11 +822,15 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 // V are 16 / FPI loads each; scores are 4-feature partial dot products reduced over the LPF lanes of a frame, the softmax runs over
 // the register copies and the lane groups, P.V reduces over the groups.  head_dim 64 / 32, T <= 16; qk-norm (qn_g != NULL): the raw cached q / k
 // slices go through the per-head LayerNorm on read (head_layer_norm: a frame's head slice = the LPF lanes of its group).
+// FAN: the split cache of a fan-out decode pass (FanSplit, kernels.hpp) -- `cache` is the branch slice with T = Tb slots per clip,
+// slots below fan.P0 come from the parent's clip of the trunk.  The FPI frames of one load instruction may lie on both sides of P0:
+// every lane group chooses its own base pointer, after the clamp.  FAN = false is the kernel without the split.
 // ------------------------------------------------------------------------------------------------------------------------------
-template <int DH>
+template <int DH, bool FAN>
 __global__ __launch_bounds__(256) void attn_temporal_fr_kernel(const float* __restrict__ cache, uint16_t* __restrict__ out16,
                                                                long n_items, int T, int S, int t0, int nf, int d, int H, float scale,
-                                                               const float* __restrict__ qn_g, const float* __restrict__ qn_b) {
+                                                               const float* __restrict__ qn_g, const float* __restrict__ qn_b,
+                                                               FanSplit<FAN> fan) {
     constexpr int LPF = DH / 4, FPI = 64 / LPF, NI = 16 / FPI;     // lanes per frame, frames per instruction, instructions
     const int lane = threadIdx.x & 63;
     const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -840,14 +844,29 @@ __global__ __launch_bounds__(256) void attn_temporal_fr_kernel(const float* __re
     const int g = lane / LPF, c = lane % LPF;
     const size_t tok = (size_t)S * 3 * d;
     const float* hb = cache + ((size_t)(b * T) * S + s) * 3 * d + head * DH + 4 * c;
-    f32x4 qv = *reinterpret_cast<const f32x4*>(hb + (size_t)t * tok);
+    const float* tb = nullptr;   // FAN: the same (position, head, features) of the parent's clip of the trunk
+    int P0 = 0;
+    if constexpr (FAN) {
+        tb = static_cast<const float*>(fan.trunk) + ((size_t)((b / fan.K) * fan.T) * S + s) * 3 * d + head * DH + 4 * c;
+        P0 = fan.P0;
+    }
+    // cache slot j of the lane's (clip, position, head, features): (FAN) the trunk below P0, slot j - P0 of the branch from P0 on
+    auto slot = [&](int j) {
+        if constexpr (FAN) {
+            const bool lo = j < P0;
+            return (lo ? tb : hb) + (size_t)(lo ? j : j - P0) * tok;
+        } else {
+            return hb + (size_t)j * tok;
+        }
+    };
+    f32x4 qv = *reinterpret_cast<const f32x4*>(slot(t));
     f32x4 kv[NI], vv[NI];
     f32x4 qg = f32x4{0.f, 0.f, 0.f, 0.f}, qb = qg;
     if (qn_g) { qg = *reinterpret_cast<const f32x4*>(qn_g + 4 * c); qb = *reinterpret_cast<const f32x4*>(qn_b + 4 * c); }
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
         const int j = FPI * i + g;
-        const float* src = hb + (size_t)(j <= t ? j : t) * tok;    // (frames past t re-read frame t: their probability is 0)
+        const float* src = slot(j <= t ? j : t);    // (frames past t re-read frame t: their probability is 0)
         kv[i] = *reinterpret_cast<const f32x4*>(src + d);
         vv[i] = *reinterpret_cast<const f32x4*>(src + 2 * d);
     }
@@ -1162,7 +1181,8 @@ int st_block_frame_f16x3(const genie_cfg& c, const genie_layer_weights& lw, floa
     {
         FrGemmArgs g = a;
         g.A = xs; g.W = wq_t; g.bias = c.qkv_bias ? lw.temporal.qkv_b : nullptr; g.N = 3 * d; g.K = d;
-        g.Cf = p.cache + (size_t)p.frame_t * S * 3 * d; g.ldc = 3 * d; g.rows_per_batch = (long)nf * S;
+        // (fan-out: slot frame_t - fan_P0 of the branch slice, frame_T = Tb slots per clip; fan_P0 = 0 in an ordinary decode pass)
+        g.Cf = p.cache + (size_t)(p.frame_t - p.fan_P0) * S * 3 * d; g.ldc = 3 * d; g.rows_per_batch = (long)nf * S;
         g.strideC = (long)p.frame_T * S * 3 * d;
         ProfScope prof(GENIE_KC_GEMM, 2.0 * M * 3.0 * d * d, 4.0 * M * d + 4.0 * 3 * d * d + 4.0 * M * 3 * d, st,
                        mid ? "gemm16_frm_kernel (temporal qkv -> cache)" : "gemm16_fr_kernel (temporal qkv -> cache)");
@@ -1173,12 +1193,18 @@ int st_block_frame_f16x3(const genie_cfg& c, const genie_layer_weights& lw, floa
         const long n = (long)M * H;
         ProfScope prof(GENIE_KC_ATTN_TEMPORAL, 4.0 * (p.frame_t + nf) * c.head_dim * (double)n, (double)n * c.head_dim * 4.0 * (2 * (p.frame_t + nf) + 2), st,
                        "attn_temporal_fr_kernel");
-        if (c.head_dim == 64)
-            attn_temporal_fr_kernel<64><<<(unsigned)((n + 3) / 4), 256, 0, st>>>(p.cache, as, n, p.frame_T, S, p.frame_t, nf, d, H, c.attn_scale,
-                                                                                 qkn ? lw.temporal.norm_w : nullptr, qkn ? lw.temporal.norm_b : nullptr);
+        const float *tn_g = qkn ? lw.temporal.norm_w : nullptr, *tn_b = qkn ? lw.temporal.norm_b : nullptr;
+        const unsigned blocks = (unsigned)((n + 3) / 4);
+        const FanSplit<true> fan = {p.trunk, p.model_T, p.fan_P0, p.fan_K};
+        const FanSplit<false> none;
+        if (p.is_fanout() && c.head_dim == 64)
+            attn_temporal_fr_kernel<64, true><<<blocks, 256, 0, st>>>(p.cache, as, n, p.frame_T, S, p.frame_t, nf, d, H, c.attn_scale, tn_g, tn_b, fan);
+        else if (p.is_fanout())
+            attn_temporal_fr_kernel<32, true><<<blocks, 256, 0, st>>>(p.cache, as, n, p.frame_T, S, p.frame_t, nf, d, H, c.attn_scale, tn_g, tn_b, fan);
+        else if (c.head_dim == 64)
+            attn_temporal_fr_kernel<64, false><<<blocks, 256, 0, st>>>(p.cache, as, n, p.frame_T, S, p.frame_t, nf, d, H, c.attn_scale, tn_g, tn_b, none);
         else
-            attn_temporal_fr_kernel<32><<<(unsigned)((n + 3) / 4), 256, 0, st>>>(p.cache, as, n, p.frame_T, S, p.frame_t, nf, d, H, c.attn_scale,
-                                                                                 qkn ? lw.temporal.norm_w : nullptr, qkn ? lw.temporal.norm_b : nullptr);
+            attn_temporal_fr_kernel<32, false><<<blocks, 256, 0, st>>>(p.cache, as, n, p.frame_T, S, p.frame_t, nf, d, H, c.attn_scale, tn_g, tn_b, none);
         GENIE_LAUNCH_CHECK("attn_temporal_fr");
     }
     {

@@ -15,9 +15,13 @@ int temporal_attention(const genie_cfg& c, const genie_attn_weights& aw, const B
     const int d = c.d_model, H = c.num_heads, Dh = c.head_dim;
     const float* nw = c.qk_norm ? aw.norm_w : nullptr;
     const float* nb = c.qk_norm ? aw.norm_b : nullptr;
-    if (p.is_decode())  // the GEMM filled cache slot frame_t: attend slots 0..frame_t
+    if (p.is_decode()) {  // the GEMM filled cache slot frame_t: attend slots 0..frame_t
+        if (p.is_fanout())  // ... slots below fan_P0 from the parent's clip of the trunk, the rest from the branch slice
+            return launch_attn_temporal_single_fanout(p.cache, out, B, p.frame_T, c.S, p.frame_t, d, H, Dh, c.attn_scale, nw, nb, st, out16,
+                                                      plane, in16, FanSplit<true>{p.trunk, p.model_T, p.fan_P0, p.fan_K});
         return launch_attn_temporal_single(p.cache, out, B, p.frame_T, c.S, p.frame_t, d, H, Dh, c.attn_scale, nw, nb, st, out16, plane,
                                            in16);
+    }
     const float* qkv = tq.base;
     float* tmp = out16 ? w.logits : out;  // where a kernel without a 16-bit epilogue writes its f32 rows
     if (p.reads_cache()) {

@@ -374,6 +374,118 @@ def rollout_frames(model, prompt_BPHW: torch.LongTensor, n_new, keep=None, maskg
     return frames.view(B, P + n_new, model.h, model.w)
 
 
+def _fanout_inputs(model, prompt_BPHW, n_new, K, action_ids, action_vectors, prompt_actions, prompt_action_vectors):
+    """The checked inputs of fanout_frames, before the library is touched -> (B, P, K, prompt ids (B, P) or None, branch ids (B K, n_new)
+    or None, prompt vectors (B, P, A) or None, branch vectors (B K, n_new, A) or None); raises in the style of _rollout_inputs."""
+    cfg = model.config
+    if prompt_BPHW.dim() != 4 or prompt_BPHW.shape[2] * prompt_BPHW.shape[3] != cfg.S:
+        raise RuntimeError(f"expected prompt frames (B, P, H, W) of {cfg.S} tokens each, got {tuple(prompt_BPHW.shape)}")
+    B, P, n_new = prompt_BPHW.shape[0], prompt_BPHW.shape[1], int(n_new)
+    if n_new < 1 or P < 1 or P + n_new > cfg.T:
+        raise ValueError(f"fanout_frames: {P} prompt + {n_new} new frames must lie inside the window of {cfg.T} (in-window generation; "
+                         "a longer horizon continues with rollout_frames on the B * K results)")
+    if action_ids is not None and action_vectors is not None:
+        raise ValueError("pass action_ids or action_vectors, not both")
+    given = action_ids if action_ids is not None else action_vectors
+    want = 3 if action_ids is not None else 4
+    if given is not None:
+        g = torch.as_tensor(given)
+        if g.dim() != want or g.shape[0] != B or g.shape[2] != n_new:
+            what = "action_ids" if action_ids is not None else "action_vectors"
+            shape = f"({B}, K, {n_new})" if action_ids is not None else f"({B}, K, {n_new}, {cfg.action_dim})"
+            raise RuntimeError(f"expected {what} of shape {shape}, got {tuple(g.shape)}")
+        if K is not None and int(K) != g.shape[1]:
+            raise ValueError(f"K = {K} but the actions hold {g.shape[1]} branches per clip")
+        K = g.shape[1]
+    if K is None:
+        raise ValueError("fanout_frames: pass K (branches per clip), or per-branch actions that carry it")
+    K = int(K)
+    if K < 1:
+        raise ValueError(f"fanout_frames: K = {K} must be >= 1")
+    if cfg.action_dim:
+        if action_ids is not None or prompt_actions is not None:
+            raise ValueError(f"action ids given to a model conditioned on action vectors (action_dim={cfg.action_dim})")
+        pv = model.check_action_vectors(prompt_action_vectors, (B, P, cfg.action_dim), "prompt_action_vectors")
+        bv = model.check_action_vectors(action_vectors, (B, K, n_new, cfg.action_dim))
+        return B, P, K, None, None, pv, bv.view(B * K, n_new, cfg.action_dim)
+    if action_vectors is not None or prompt_action_vectors is not None:
+        raise ValueError("action vectors given to a model without continuous actions (config.action_dim == 0)")
+    pa = _rollout_actions(model, prompt_actions, B, P, "prompt_actions")
+    ba = _rollout_actions(model, None if action_ids is None else torch.as_tensor(action_ids).reshape(B * K, n_new), B * K, n_new)
+    return B, P, K, pa, ba, None, None
+
+
+@torch.no_grad()
+def fanout_frames(model, prompt_BPHW: torch.LongTensor, n_new, K=None, action_ids=None, action_vectors=None, prompt_actions=None,
+                  prompt_action_vectors=None, maskgit_steps=2, temperature=0.0, unmask_mode="random", sampling=None, guidance=None,
+                  merge_commit=True, noise=None, uniforms=None):
+    """K candidate futures of n_new frames for each of the B prompts (B, P, H, W) -> (B, K, n_new, H, W), in ONE library call
+    (genie_generate_fanout): the context runs once per clip into a shared trunk cache, and the decode passes run B * K clips that read the
+    trunk's slots [0, P) and keep only their own n_new slots.  In-window: P + n_new <= T.  Branch k of clip b equals clip b * K + k of
+    generate_frames_cached on the K-times replicated batch with that branch's actions and draws.
+    action_ids: (B, K, n_new) actions of the new frames, with prompt_actions (B, P) for the prompt; a model with config.action_dim > 0
+    takes action_vectors (B, K, n_new, action_dim) and prompt_action_vectors (B, P, action_dim) instead (one launch each projects them into
+    one row table; row 0 is action_null).  K is taken from them; an unconditioned model takes K explicitly, and its branches differ by
+    their draws only.  noise: optional (n_new, maskgit_steps - 1, B * K, S); uniforms: optional (n_new, maskgit_steps, num_factored_vocabs,
+    B * K, S); fresh torch.rand draws otherwise.  The other options: generate_frames_cached.
+    A longer horizon continues by handing the (B * K) results, behind their prompts, to rollout_frames as prompts."""
+    B, P, K, pa, ba, pv, bv = _fanout_inputs(model, prompt_BPHW, n_new, K, action_ids, action_vectors, prompt_actions, prompt_action_vectors)
+    n_new = int(n_new)
+    dec = _Decode(model, maskgit_steps, temperature, unmask_mode, sampling, guidance, merge_commit)
+    pr = prompt_BPHW.to(torch.int64).reshape(B, P, model.config.S).contiguous()
+    cond = fanout_cond(model, B, P, K, n_new, pa, ba, pv, bv, pr.device)
+    nz, uni = dec.draws(model, n_new, B * K, noise, uniforms, pr.device)
+    return fanout_call(model, pr, K, n_new, cond, dec, nz, uni).view(B, K, n_new, model.h, model.w)
+
+
+def fanout_cond(model, B, P, K, n_new, prompt_ids, branch_ids, prompt_vectors, branch_vectors, dev):
+    """The genie_frame_cond of a fan-out call from checked inputs (_fanout_inputs), None for an unconditioned model: ids (B K, T),
+    branch-major -- the prompt's actions in every branch, then the branch's own, 0 past P + n_new (never embedded).  Vectors are projected
+    into one row table (one launch for the prompt's, one for the branches'); row 0 is action_null."""
+    from . import _lib
+    if branch_ids is None and branch_vectors is None:
+        return None
+    ids = torch.zeros(B, K, model.config.T, dtype=torch.int64, device=dev)
+    if branch_vectors is not None:
+        rows = model.new_row_table(B * P + B * K * n_new)
+        model.project_actions(prompt_vectors.view(B * P, -1), rows[1:1 + B * P])
+        model.project_actions(branch_vectors.view(B * K * n_new, -1), rows[1 + B * P:])
+        ids[:, :, :P] = (1 + torch.arange(B * P, device=dev)).view(B, 1, P)
+        ids[:, :, P:P + n_new] = (1 + B * P + torch.arange(B * K * n_new, device=dev)).view(B, K, n_new)
+        cond = _lib.FrameCond(table=rows.data_ptr(), ids=ids.data_ptr(), n_actions=rows.shape[0])
+        cond.rows = rows
+    else:
+        ids[:, :, :P] = prompt_ids[:, None]
+        ids[:, :, P:P + n_new] = branch_ids.view(B, K, n_new)
+        cond = _lib.FrameCond(table=model.action_embed.weight.data_ptr(), ids=ids.data_ptr(), n_actions=model.config.action_vocab_size)
+    cond.keep = ids   # the ids tensor lives as long as the struct
+    return cond
+
+
+def fanout_call(model, prompt_BPS, K, n_new, cond, dec, nz, uni, trunk=None, branch=None):
+    """ONE genie_generate_fanout call -> gen (B, K, n_new, S) int64.  prompt_BPS: (B, P, S) int64, contiguous; cond: fanout_cond; dec: the
+    _Decode options; nz / uni: the call's draws over B K rows.  trunk / branch: uint8 tensors of genie_prefix_cache_bytes(cfg, NB) and
+    genie_fanout_branch_bytes(cfg, NB, K, n_new) to keep what the call leaves in them (allocated here otherwise)."""
+    from . import _lib
+    lib = _lib.load()
+    cfg, w = model._weights()[:2]
+    B, P, S = prompt_BPS.shape
+    assert prompt_BPS.dtype == torch.int64 and prompt_BPS.is_contiguous()
+    dev = prompt_BPS.device
+    NB = B if dec.guide is None else 2 * B
+    if trunk is None:
+        trunk = torch.empty(lib.genie_prefix_cache_bytes(cfg, NB), dtype=torch.uint8, device=dev)
+    if branch is None:
+        branch = torch.empty(lib.genie_fanout_branch_bytes(cfg, NB, K, n_new), dtype=torch.uint8, device=dev)
+    ws = torch.empty(lib.genie_fanout_workspace_bytes(cfg, B, K, P, int(dec.guide is not None)), dtype=torch.uint8, device=dev)
+    gen = torch.empty(B, K, n_new, S, dtype=torch.int64, device=dev)
+    _lib.check(lib.genie_generate_fanout(cfg, w, prompt_BPS.data_ptr(), B, K, P, n_new, dec.steps, dec.temperature, dec.mode,
+                                         0 if nz is None else nz.data_ptr(), 0 if uni is None else uni.data_ptr(), int(dec.merge_commit),
+                                         gen.data_ptr(), trunk.data_ptr(), trunk.numel(), branch.data_ptr(), branch.numel(), ws.data_ptr(),
+                                         ws.numel(), torch.cuda.current_stream().cuda_stream, cond, dec.law, dec.guide), "genie_generate_fanout")
+    return gen
+
+
 class Rollout:
     """An open-ended rollout: ``step(action)`` returns the next frame, ``extend(n, action_ids)`` the next n, each ONE
     genie_rollout_cached call that resumes the temporal KV cache of the call before it (the first runs the prompt).  Same frames as

@@ -693,6 +693,12 @@ class STMaskGIT(nn.Module):
         from .generate import rollout_frames
         return rollout_frames(self, prompt_BPHW, n_new, keep=keep, **kwargs)
 
+    def fanout(self, prompt_BPHW, n_new, K=None, **kwargs):
+        """K candidate futures of n_new frames per prompt (B, P, H, W) -> (B, K, n_new, H, W) over one shared context cache:
+        generate.fanout_frames (one library call, in-window: P + n_new <= T)."""
+        from .generate import fanout_frames
+        return fanout_frames(self, prompt_BPHW, n_new, K=K, **kwargs)
+
     # ------------------------------------------------------------------ weights
     def init_weights(self):
         """N(0, 0.02) Linear/Embedding weights, zero biases (reference :281-296; the muP branch of the

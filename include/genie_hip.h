@@ -572,6 +572,46 @@ int genie_rollout_cached(const genie_cfg* cfg, const genie_weights* w, int64_t* 
                          int merge_commit, float* cache, size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
                          const genie_frame_cond* cond, const genie_sampling* sampling, const genie_guidance* guidance);
 
+/* ---- fan-out generation: K futures per clip over one shared context cache (ABI 3 addition; reference counterpart: none) ---------------
+ * A world model's user holds an observed context and asks what happens under action sequence 1, 2, ... K.  As K extra clips of a batch
+ * that costs the context pass K times on identical tokens and K full T-slot caches whose first P slots hold the same bytes.  Here the
+ * context of the B clips (NB = 2 B under guidance of scale != 1, else B) runs ONCE into `trunk`, an ordinary cache of NB clips, and the
+ * loop of genie_generate_cached_guided then decodes B * K clips, NBK = NB * K per pass, clip i being branch i % K of parent i / K, over a
+ * split cache:
+ *     slot j <  P  of clip i:   trunk  + ((i / K) * T  +  j     ) * S * 3d      (per layer; read only -- every decode pass has t0 >= P)
+ *     slot j >= P  of clip i:   branch + ( i      * Tb + (j - P)) * S * 3d      branch: (L, NBK, Tb, S, 3d) f32, Tb = n_new
+ * GENIE_PREC_BF16 with a 16-bit cache keeps its rule in both: 16-bit values in the first half of each layer's slice, slices at the f32
+ * strides.  Everything else is that loop: `steps` passes per frame, the commit of slot t merged with step 0 of slot t + 1 where
+ * merge_commit is set and the library covers NBK clips (the 16,384-row cut is taken at the pass's own row count), the sampling law, the
+ * three unmask modes, guidance (trunk [cond ; null] of 2 B clips, branches [cond B K ; null B K], parent i / K in both halves), no host
+ * synchronisation.  In-window only: P + n_new <= T; there is no teacher_force_time and no logits0_out.  K = 1 enqueues the launches of
+ * genie_generate_cached_guided with other addresses: same tokens, bit for bit.  In general the tokens equal those of the K-times
+ * replicated batch (clip b * K + k = clip b under branch k's actions and draws) through the one-pass loop at NBK clips per pass.
+ *   ids (B, P, S): the prompts only.  gen_out (B, K, n_new, S).  noise (n_new, steps - 1, B * K, S), uniforms (n_new, steps, num_factored,
+ *   B * K, S): rows of clip b * K + k.
+ *   cond->ids (B * K, T), branch-major: row b * K + k, clip stride cfg->T.  The context reads frames < P from row b * K (branch 0); frames
+ *   < P of the other branches are never read.  One launch builds the (NB, T) and (NBK, T) ids the passes embed with, null halves included.
+ *   trunk: genie_prefix_cache_bytes(cfg, NB); the caller may read the context's K / V there afterwards.
+ *   branch: genie_fanout_branch_bytes(cfg, NB, K, n_new) = L * NB * K * n_new * S * 3d * 4; 0 on bad arguments.
+ *   workspace: genie_fanout_workspace_bytes(cfg, B, K, P, guided): the larger of the context pass (NB clips, P frames) and a two-frame
+ *   pass of NBK clips, plus the loop's scratch; 0 on bad arguments.
+ * Argument errors (NULL pointers, K < 1, P + n_new > T, a buffer too small, NB * K beyond 2^30 - 1) return GENIE_E_ARG before anything is
+ * enqueued.  A longer horizon continues by handing the B * K results as prompts to genie_rollout_cached.
+ * Tests: tests/test_fanout_cpu.py, tests/test_hip_fanout.py. */
+size_t genie_fanout_branch_bytes(const genie_cfg* cfg, int NB, int K, int n_new);
+size_t genie_fanout_workspace_bytes(const genie_cfg* cfg, int B, int K, int P, int guided);
+int genie_generate_fanout(const genie_cfg* cfg, const genie_weights* w, const int64_t* ids, int B, int K, int P, int n_new, int steps,
+                          float temperature, int unmask_mode, const float* noise, const float* uniforms, int merge_commit, int64_t* gen_out,
+                          float* trunk, size_t trunk_bytes, float* branch, size_t branch_bytes, void* workspace, size_t workspace_bytes,
+                          void* stream, const genie_frame_cond* cond, const genie_sampling* sampling, const genie_guidance* guidance);
+/* The decode attention of one layer over that split cache, alone (the `single` kernel family; the fragment-order passes have their own
+ * flavour of it): query slot t >= P0 of NBK clips against slots 0..t, out (NBK, S, d) f32 rows.  trunk_slice: (NBK / K, cfg->T, S, 3d),
+ * branch_slice: (NBK, Tb, S, 3d); in16 != 0: both hold bf16 values.  K = 1, P0 = 0, Tb = cfg->T reads branch_slice as an ordinary cache
+ * (trunk_slice may then be NULL).  Reads only the attention geometry of cfg (heads of 8 are admitted here) and aw->norm_w / norm_b. */
+int genie_temporal_attention_decode_fanout(const genie_cfg* cfg, const genie_attn_weights* aw, const float* trunk_slice,
+                                           const float* branch_slice, float* out, int NBK, int K, int P0, int Tb, int t, int in16,
+                                           void* stream);
+
 /* ---- optional per-launch timing (bench.py's roofline leg) ------------------------------------------------
  * When enabled, every launch of a kernel whose class bit is set in `class_mask` is bracketed by a pair of
  * HIP events recorded on the launch stream.  genie_profile_read synchronises those events and returns, for

@@ -86,6 +86,45 @@ def rollout_ab(a, m, cfg, extra):
     print(json.dumps({"workload": f"rollout {P}->{N} frames against generate {P}->{T - P}, " + a.model + " " + a.precision, "results": res}))
 
 
+def fanout_ab(a, m, cfg, extra):
+    """fanout_frames at (B, K) against generate_frames_cached on the K-times replicated batch (prompt 8, 8 new frames), one call per leg
+    per round, legs interleaved: per leg the median and the min-max spread over the rounds, and the peak cache bytes of each."""
+    synth = importlib.import_module("1xgpt_amd.synthetic")
+    G = importlib.import_module("1xgpt_amd.generate")
+    L = importlib.import_module("1xgpt_amd._lib")
+    lib, c = L.load(), m._weights()[0]
+    P, T, K = 8, cfg.T, a.fanout
+    N = T - P
+    res = []
+    for B in a.batches:
+        ex = torch.from_numpy(synth.make_clips(B, cfg, seed=7)).cuda().view(B, T, 16, 16)
+        rep = ex.repeat_interleave(K, dim=0).contiguous()
+        for steps in a.steps:
+            nz = torch.rand(N, max(steps - 1, 1), B * K, cfg.S, device="cuda")
+            legs = {"fanout": dict(fn=lambda steps=steps, nz=nz: G.fanout_frames(m, ex[:, :P], N, K=K, maskgit_steps=steps,
+                                                                                 temperature=a.temperature, noise=nz, **extra),
+                                   cache=lib.genie_prefix_cache_bytes(c, B) + lib.genie_fanout_branch_bytes(c, B, K, N), times=[]),
+                    "replicated": dict(fn=lambda steps=steps, nz=nz: G.generate_frames_cached(m, rep, P, steps, a.temperature, False, noise=nz,
+                                                                                              **extra),
+                                       cache=lib.genie_prefix_cache_bytes(c, B * K), times=[])}
+            for leg in legs.values():
+                for _ in range(2):
+                    leg["fn"]()
+            for _ in range(a.repeats):
+                for leg in legs.values():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    leg["fn"]()
+                    torch.cuda.synchronize()
+                    leg["times"].append(time.perf_counter() - t0)
+            for name, leg in legs.items():
+                t = sorted(leg["times"])
+                res.append({"leg": name, "batch": B, "K": K, "maskgit_steps": steps, "prompt": P, "new_frames": N, "sampler": bool(a.sampler),
+                            "median_ms": 1e3 * t[len(t) // 2], "min_ms": 1e3 * t[0], "max_ms": 1e3 * t[-1], "cache_bytes": leg["cache"]})
+                print(res[-1], flush=True)
+    print(json.dumps({"workload": f"fan-out {P}->{N} frames x K={K} against the replicated batch, " + a.model + " " + a.precision, "results": res}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--precision", default="f16x3")
@@ -110,6 +149,9 @@ def main():
     ap.add_argument("--rollout", type=int, default=None,
                     help="rollout leg: ms per generated frame of rollout_frames at this many new frames (prompt 8) against generate_frames_cached "
                          "at T - 8, interleaved in one process; 0 = the in-window leg alone")
+    ap.add_argument("--fanout", type=int, default=None,
+                    help="fan-out leg: per batch B, fanout_frames at (B, K) against generate_frames_cached on the K-times replicated batch "
+                         "(prompt 8, 8 new frames), interleaved in one process, with the cache bytes of each")
     ap.add_argument("--keep", type=int, default=None, help="context frames the rollout re-runs per window (default: the prompt's 8)")
     a = ap.parse_args()
     extra = {}
@@ -134,6 +176,8 @@ def main():
         return guidance_ab(a, m, cfg, extra)
     if a.rollout is not None:
         return rollout_ab(a, m, cfg, extra)
+    if a.fanout is not None:
+        return fanout_ab(a, m, cfg, extra)
     res = []
     for B in a.batches:
         ex = torch.from_numpy(synth.make_clips(B, cfg, seed=7)).cuda().view(B, 16, 16, 16)

@@ -7,7 +7,9 @@ written as [prompt | generated | ground truth] video.bin + metadata.json (readab
 An action-conditioned checkpoint (action_vocab_size > 0) generates with the example's actions from the dataset's actions.bin
 (refused without one); --guidance_scale W --null_action K decodes such a model under classifier-free guidance.
 --num_new_frames N rolls out N frames behind the prompt, past the model's window if need be (the window slides by T - keep frames and
-re-runs the last --keep frames as its context); the output is then [prompt | N generated | whatever ground truth exists]."""
+re-runs the last --keep frames as its context); the output is then [prompt | N generated | whatever ground truth exists].
+--fanout K generates K candidate futures of the example over one shared context cache (in-window; branches differ by their sampling
+draws and, for an action-conditioned model, by the (K, n_new) action ids of --fanout_actions); branch k is written to OUTPUT_DIR/branch_k."""
 import argparse
 import importlib
 import os
@@ -45,7 +47,35 @@ def build_parser():
     ap.add_argument("--keep", type=int, default=None,
                     help="With --num_new_frames: frames of context each later window re-runs, 1 .. T-1 (default: --num_prompt_frames); "
                          "T-1 is the true sliding window, smaller is cheaper.")
+    ap.add_argument("--fanout", type=int, default=None,
+                    help="Generate this many candidate futures of the example in one library call (fanout_frames): the context runs once, "
+                         "every branch keeps only its new frames' cache slots. In-window: fills the window, or --num_new_frames of it.")
+    ap.add_argument("--fanout_actions", type=str, default=None,
+                    help="With --fanout on an action-conditioned model: a text file of K rows of n_new action ids, one row per branch "
+                         "(the prompt frames keep the example's actions).")
     return ap
+
+
+def fanout_main(args, model, ex, actions, meta, sampling, guidance, G):
+    """--fanout K: [prompt | branch k's frames | ground truth] per branch, in OUTPUT_DIR/branch_k."""
+    import numpy as np
+    P, K = args.num_prompt_frames, args.fanout
+    N = args.window_size - P if args.num_new_frames is None else args.num_new_frames
+    if args.teacher_force_time or args.schedule != "kv_cache":
+        sys.exit("generate.py: --fanout runs on the KV cache and has no teacher forcing in time")
+    kw = {}
+    if model.config.action_vocab_size:
+        if args.fanout_actions is None:
+            sys.exit("generate.py: --fanout on an action-conditioned model needs --fanout_actions (K rows of n_new ids)")
+        ids = np.loadtxt(args.fanout_actions, dtype=np.int64, ndmin=2)
+        if ids.shape != (K, N):
+            sys.exit(f"generate.py: --fanout_actions holds {ids.shape} ids, expected ({K}, {N})")
+        kw = dict(action_ids=torch.from_numpy(ids)[None].to("cuda"), prompt_actions=actions[:, :P].to("cuda"))
+    out = G.fanout_frames(model, ex[:, :P], N, K=K, maskgit_steps=args.maskgit_steps, temperature=args.temperature,
+                          unmask_mode=args.unmask_mode, sampling=sampling, guidance=guidance, **kw)
+    for k in range(K):
+        frames = torch.cat([ex[:, :P], out[:, k], ex[:, P:]], dim=1)
+        print(G.write_outputs(frames, os.path.join(args.output_dir, f"branch_{k}"), meta, vars(args)))
 
 
 def main():
@@ -75,6 +105,8 @@ def main():
             actions = item["action_ids"][None]
     model = model.to("cuda")
     ex = example.to("cuda").view(1, args.window_size, model.h, model.w)
+    if args.fanout is not None:
+        return fanout_main(args, model, ex, actions, meta, sampling, guidance, G)
     if args.num_new_frames is not None:
         P, N = args.num_prompt_frames, args.num_new_frames
         if args.teacher_force_time or args.schedule != "kv_cache":

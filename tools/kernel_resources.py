@@ -17,7 +17,7 @@ for line in out.splitlines():
     m = re.search(r"(TotalSGPRs|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\]): (\d+)", line)
     if m and cur is not None:
         cur[m.group(1).split(" [")[0]] = int(m.group(2))
-print(f"{'kernel':100s} {'vgpr':>5s} {'agpr':>5s} {'sgpr':>5s} {'scratch':>7s} {'vspill':>6s} {'occ':>4s}")
+print(f"{'kernel':100s} {'vgpr':>5s} {'agpr':>5s} {'sgpr':>5s} {'scratch':>7s} {'vspill':>6s} {'occ':>4s} {'lds':>6s}")
 for r in rows:
     print(f"{r['name'][:100]:100s} {r.get('VGPRs', -1):5d} {r.get('AGPRs', -1):5d} {r.get('TotalSGPRs', -1):5d} {r.get('ScratchSize', -1):7d} "
-          f"{r.get('VGPRs Spill', -1):6d} {r.get('Occupancy', -1):4d}")
+          f"{r.get('VGPRs Spill', -1):6d} {r.get('Occupancy', -1):4d} {r.get('LDS Size', -1):6d}")
