@@ -229,6 +229,14 @@ SIGNATURES["genie_generate_fanout"] = (C.c_int, [C.POINTER(GenieCfg), C.POINTER(
                                                  C.POINTER(FrameCond), C.POINTER(Sampling), C.POINTER(Guidance)])
 SIGNATURES["genie_temporal_attention_decode_fanout"] = (C.c_int, [C.POINTER(GenieCfg), C.POINTER(AttnWeights), c_ptr, c_ptr, c_ptr] + [C.c_int] * 6
                                                         + [c_ptr])
+# scoring observed futures: (cfg, logits, targets, target_clip_stride, K, N, nll, nll_stride, hits, token_nll, token_stride, stream),
+# (cfg, B, K, P) and (cfg, w, ids, B, K, P, n, merge_commit, nll, hits, token_nll, trunk, trunk_bytes, branch, branch_bytes, workspace,
+# workspace_bytes, stream, cond)
+SIGNATURES["genie_score_logits"] = (C.c_int, [C.POINTER(GenieCfg), c_ptr, c_ptr, C.c_int64, C.c_int, C.c_int64, c_ptr, C.c_int64, c_ptr, c_ptr,
+                                              C.c_int64, c_ptr])
+SIGNATURES["genie_score_workspace_bytes"] = (C.c_size_t, [C.POINTER(GenieCfg), C.c_int, C.c_int, C.c_int])
+SIGNATURES["genie_score_fanout"] = (C.c_int, [C.POINTER(GenieCfg), C.POINTER(Weights), c_ptr] + [C.c_int] * 5 + [c_ptr, c_ptr, c_ptr, c_ptr,
+                                              C.c_size_t, c_ptr, C.c_size_t, c_ptr, C.c_size_t, c_ptr, C.POINTER(FrameCond)])
 
 _lib = None
 

@@ -1065,6 +1065,118 @@ int genie_generate_fanout(const genie_cfg* cfg, const genie_weights* wt, const i
     return decode_slots(Lb, P, n_new, noise, uniforms, gen_out, (long)n_new * S, nullptr, nullptr, 0, nullptr, 0);
 }
 
+// ---- scoring observed futures: per-(clip, branch, frame) NLL over the fan-out cache ----------------------------------------
+int genie_score_logits(const genie_cfg* cfg, const float* logits, const int64_t* targets, int64_t target_clip_stride, int K, int64_t N,
+                       double* nll, int64_t nll_stride, double* hits, float* token_nll, int64_t token_stride, void* stream) {
+    GENIE_TRY(check_cfg(cfg));
+    GENIE_CHECK_ARG(logits && targets && nll, "score_logits: NULL pointer");
+    GENIE_CHECK_ARG(K >= 1 && N >= 1 && N <= 0x7fffffffLL, "score_logits: %lld rows in branches of %d", (long long)N, K);
+    GENIE_CHECK_ARG(target_clip_stride >= 0 && nll_stride >= 1, "score_logits: target stride %lld, nll stride %lld", (long long)target_clip_stride,
+                    (long long)nll_stride);
+    GENIE_CHECK_ARG(!token_nll || token_stride >= cfg->S, "score_logits: token_nll stride %lld below S = %d", (long long)token_stride, cfg->S);
+    GENIE_CHECK_ARG(((uintptr_t)logits & 15) == 0, "score_logits: logits must be 16-byte aligned");
+    return launch_score_rows(*cfg, logits, targets, (long)target_clip_stride, K, (long)N, nll, (long)nll_stride, hits, token_nll,
+                             (long)token_stride, as_stream(stream));
+}
+
+size_t genie_score_workspace_bytes(const genie_cfg* cfg, int B, int K, int P) { return genie_fanout_workspace_bytes(cfg, B, K, P, 0); }
+
+// rows of S token ids for the B * K clips of a fan-out pass from their B parents: dst[i][0..S) = src[i / K][0..S) (strides in elements)
+__global__ void branch_frame_ids_kernel(const int64_t* __restrict__ src, long src_stride, int64_t* __restrict__ dst, long dst_stride, int S,
+                                        long BK, int K) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= BK * S) return;
+    const long r = i / S, s = i - r * S;
+    dst[r * dst_stride + s] = src[(r / K) * src_stride + s];
+}
+
+// decode_slots' sibling for OBSERVED frames: per slot t0 + j the all-mask pass (riding the commit of slot t0 + j - 1 by decode_slots' own
+// rule), launch_score_rows on its logits against frame j of obs (parent clip i / K of row i, clip stride obs_stride), then the commit of
+// the observed tokens; the last slot is not committed.  nll / hits (L.B, n), token_nll (L.B, n, S).  No sample or mask-step launches,
+// no draws, no host synchronisation.
+static int score_slots(const GenLoop& L, int t0, int n, const int64_t* obs, long obs_stride, int K, double* nll, double* hits,
+                       float* token_nll) {
+    const genie_cfg& c = *L.cfg;
+    const int BK = L.B, S = c.S;
+    hipStream_t st = as_stream(L.stream);
+    int64_t *two = L.g.two, *cur = L.g.cur, *fin = L.g.fin;
+    float* logits = L.g.logits;
+    bool opened = false, merge = L.merge_commit != 0;
+    auto pass = [&](const int64_t* frame_ids, int t, int nf, float* lg) {
+        return frames_pass(L.cfg, L.wt, frame_ids, L.NB, t, nf, L.cache, L.cache_bytes, lg, L.workspace, L.workspace_bytes, L.stream, L.cond,
+                           L.fan);
+    };
+    auto put_observed = [&](const int64_t* src, int64_t* dst, long dst_stride) {
+        branch_frame_ids_kernel<<<(unsigned)(((long)BK * S + 255) / 256), 256, 0, st>>>(src, obs_stride, dst, dst_stride, S, (long)BK, K);
+        GENIE_LAUNCH_CHECK("branch_frame_ids");
+        return GENIE_OK;
+    };
+    for (int j = 0; j < n; ++j) {
+        const int t = t0 + j;
+        if (!opened) {
+            GENIE_TRY(put_frame_ids(nullptr, 0, cur, S, S, BK, c.image_vocab_size, st));
+            GENIE_TRY(pass(cur, t, 1, logits));
+        }
+        GENIE_TRY(launch_score_rows(c, logits, obs + (size_t)j * S, obs_stride, K, BK, nll + j, n, hits ? hits + j : nullptr,
+                                    token_nll ? token_nll + (size_t)j * S : nullptr, (long)n * S, st));
+        opened = false;
+        if (j + 1 == n) break;
+        if (merge) {   // commit slot t in the pass that also carries the all-mask slot t + 1
+            GENIE_TRY(put_observed(obs + (size_t)j * S, two, 2L * S));
+            GENIE_TRY(put_frame_ids(nullptr, 0, two + S, 2L * S, S, BK, c.image_vocab_size, st));
+            const int rc = pass(two, t, 2, logits);
+            if (rc == GENIE_E_UNSUPPORTED) merge = false;
+            else { GENIE_TRY(rc); opened = true; }
+        }
+        if (!opened) {
+            GENIE_TRY(put_observed(obs + (size_t)j * S, fin, S));
+            GENIE_TRY(pass(fin, t, 1, nullptr));
+        }
+    }
+    return GENIE_OK;
+}
+
+int genie_score_fanout(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int K, int P, int n, int merge_commit,
+                       double* nll, double* hits, float* token_nll, float* trunk, size_t trunk_bytes, float* branch, size_t branch_bytes,
+                       void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond) {
+    GENIE_TRY(check_cfg(cfg));
+    const genie_cfg& c = *cfg;
+    GENIE_TRY(check_frame_cond(cond, "score_fanout"));
+    GENIE_CHECK_ARG(B >= 1 && K >= 1 && P >= 1 && n >= 1 && P + n <= c.T, "score_fanout: B=%d, K=%d, %d prompt + %d scored frames of at most %d",
+                    B, K, P, n, c.T);
+    const int BK = fanout_clips(B, K, false);
+    GENIE_CHECK_ARG(BK > 0, "score_fanout: B=%d x K=%d clips per pass are too many", B, K);
+    GENIE_CHECK_ARG(wt && wt->layers_host && ids && nll && trunk && branch && workspace, "score_fanout: NULL pointer");
+    GENIE_CHECK_ARG(trunk_bytes >= genie_prefix_cache_bytes(cfg, B), "score_fanout: trunk cache too small (genie_prefix_cache_bytes of %d clips)", B);
+    GENIE_CHECK_ARG(branch_bytes >= fanout_branch_bytes(c, (size_t)BK, n), "score_fanout: branch cache too small (genie_fanout_branch_bytes)");
+    const GenScratch g = carve_fanout(c, B, B, K, P, (char*)workspace);
+    const size_t full = carve(c, B, nullptr).total;
+    GENIE_CHECK_ARG(workspace_bytes >= g.end && workspace_bytes >= full, "score_fanout: workspace too small (%zu < %zu bytes: size it with "
+                    "genie_score_workspace_bytes)", workspace_bytes, g.end > full ? g.end : full);
+    hipStream_t st = as_stream(stream);
+    const int S = c.S;
+    const long clip = (long)(P + n) * S;   // ids (B, P + n, S)
+    genie_frame_cond cond_ctx, cond_br;
+    const bool acts = cond && cond->n_actions > 0;
+    if (acts) {
+        const long na = (long)B * c.T * (1 + K);
+        fanout_actions_kernel<<<(unsigned)((na + 255) / 256), 256, 0, st>>>(cond->ids, g.acts_ctx ? g.acts_ctx : g.acts, g.acts, B, K, B, c.T, P, 0);
+        GENIE_LAUNCH_CHECK("fanout_actions");
+        cond_ctx = cond_br = *cond;
+        cond_ctx.ids = g.acts_ctx ? g.acts_ctx : g.acts;
+        cond_br.ids = g.acts;
+    }
+    // the context of the B clips runs once, into the trunk, as in genie_generate_fanout
+    GenLoop Lc = {cfg, wt, B, B, 1, 1, GENIE_UNMASK_GREEDY, merge_commit, 0.0f, nullptr, nullptr, false, acts ? &cond_ctx : cond,
+                  trunk, trunk_bytes, workspace, workspace_bytes, stream, g};
+    GENIE_TRY(put_frame_ids(ids, clip, g.idsP, (long)P * S, P * S, B, 0, st));
+    GENIE_TRY(run_context(Lc, P, ids, clip));
+    const FanOut fan = {trunk, K, P, n};
+    const GenLoop Lb = {cfg, wt, BK, BK, 1, 1, GENIE_UNMASK_GREEDY, merge_commit, 0.0f, nullptr, nullptr, false, acts ? &cond_br : cond,
+                        branch, branch_bytes, workspace, workspace_bytes, stream, g, &fan};
+    return score_slots(Lb, P, n, ids + (size_t)P * S, clip, K, nll, hits, token_nll);
+}
+
 int genie_temporal_attention_decode_fanout(const genie_cfg* cfg, const genie_attn_weights* aw, const float* trunk_slice,
                                            const float* branch_slice, float* out, int NBK, int K, int P0, int Tb, int t, int in16,
                                            void* stream) {

@@ -225,6 +225,11 @@ int launch_count_equal(const int64_t* a, long sa, const int64_t* b, long sb, int
                        double n_tokens, double n_frames, double n_clips, hipStream_t st);
 int launch_factored_ce(const genie_cfg& c, const float* logits, int layout, const int64_t* targets,
                        const int64_t* weight_ids, int B, int t0, int t1, double* sums, hipStream_t st);
+// per-row NLL of one frame's token-major (N, S, V) logits: row i against the S targets at targets + (i / K) * target_clip_stride.
+// nll / hits: f64, row i at [i * nll_stride] (hits may be NULL); token_nll: NULL or f32, row i at [i * token_stride + s].  Fixed-order
+// f64 reduction inside the workgroup, no atomics.
+int launch_score_rows(const genie_cfg& c, const float* logits, const int64_t* targets, long target_clip_stride, int K, long N, double* nll,
+                      long nll_stride, double* hits, float* token_nll, long token_stride, hipStream_t st);
 int launch_sample(const genie_cfg& c, const float* logits, int layout, int B, float temperature,
                   const float* uniforms, int64_t* samples, float* conf, hipStream_t st);
 // kernels_sample.hip: the tempered / top-k / top-p filtered law (genie_sampling); NULL or all-off without keys_out = launch_sample

@@ -1064,6 +1064,110 @@ int launch_factored_ce(const genie_cfg& c, const float* logits, int layout, cons
 }
 
 // ------------------------------------------------------------------------------------------------
+// Per-row negative log-likelihood of observed tokens (genie_score_logits / genie_score_fanout): the per-token loss of
+// ce_token_major_kernel, kept apart per row instead of summed over the batch.  Row i of the token-major (N, S, V) logits of ONE frame
+// is scored against the S targets at targets + (i / K) * target_clip_stride: the K branches of a clip share their parent's tokens.
+// One workgroup per row, one wave per token; wave w takes tokens w, w + nw, ... and keeps its own f64 partial, and thread 0 adds the nw
+// partials in wave order -- a fixed order and no atomics, so two launches give the same bits.
+// The token's arithmetic is ce_token_major_kernel's, restated here so that kernel's code stays as it is.
+// ------------------------------------------------------------------------------------------------
+#define GENIE_SCORE_MAX_WAVES 16
+__device__ __forceinline__ float score_token(const float* __restrict__ lp, uint64_t tgt, int vf, int nfac, int lane, bool& all_ok) {
+    float loss = 0.f;
+    all_ok = true;
+    if (vf == 512 && nfac == 2) {
+        // 2 x 512: a lane owns 8 consecutive logits of each factor; the four 16-byte loads are in flight before the first use
+        typedef float sc4 __attribute__((ext_vector_type(4)));
+        sc4 v[2][2];
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) v[f][q] = *reinterpret_cast<const sc4*>(lp + f * 512 + lane * 8 + q * 4);
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+            const int tf = (int)(tgt % 512);
+            tgt /= 512;
+            float mx = -INFINITY;
+            int mi = 0;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const float x = v[f][q >> 2][q & 3];
+                if (x > mx) { mx = x; mi = lane * 8 + q; }
+            }
+            wave_argmax(mx, mi);
+            float se = 0.f;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) se += expf(v[f][q >> 2][q & 3] - mx);
+            se = wave_sum(se);
+            float tv = 0.f;   // the target's logit sits in lane tf / 8, slot tf % 8
+#pragma unroll
+            for (int q = 0; q < 8; ++q) tv = (tf & 7) == q ? v[f][q >> 2][q & 3] : tv;
+            tv = __shfl(tv, tf >> 3);
+            loss += (logf(se) + mx) - tv;
+            all_ok = all_ok && (mi == tf);
+        }
+        return loss;
+    }
+    for (int f = 0; f < nfac; ++f) {
+        const int tf = (int)(tgt % (uint64_t)vf);
+        tgt /= (uint64_t)vf;
+        float mx = -INFINITY;
+        int mi = 0;
+        for (int k = lane; k < vf; k += 64) {
+            const float v = lp[f * vf + k];
+            if (v > mx) { mx = v; mi = k; }
+        }
+        wave_argmax(mx, mi);
+        float se = 0.f;
+        for (int k = lane; k < vf; k += 64) se += expf(lp[f * vf + k] - mx);
+        se = wave_sum(se);
+        loss += (logf(se) + mx) - lp[f * vf + tf];
+        all_ok = all_ok && (mi == tf);
+    }
+    return loss;
+}
+
+__global__ __launch_bounds__(64 * GENIE_SCORE_MAX_WAVES) void score_rows_kernel(const float* __restrict__ logits,
+                                                                                const int64_t* __restrict__ targets, long target_clip_stride,
+                                                                                int K, int S, int vf, int nfac, double* __restrict__ nll,
+                                                                                long nll_stride, double* __restrict__ hits,
+                                                                                float* __restrict__ token_nll, long token_stride) {
+    __shared__ double red[2][GENIE_SCORE_MAX_WAVES];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const long row = blockIdx.x;
+    const int64_t* tg = targets + (row / K) * target_clip_stride;
+    const float* lrow = logits + (size_t)row * S * vf * nfac;
+    double acc = 0, hit = 0;
+    for (int s = wid; s < S; s += nw) {
+        bool ok;
+        const float loss = score_token(lrow + (size_t)s * vf * nfac, (uint64_t)tg[s], vf, nfac, lane, ok);
+        acc += (double)loss;
+        hit += ok ? 1.0 : 0.0;
+        if (token_nll && lane == 0) token_nll[row * token_stride + s] = loss;
+    }
+    if (lane == 0) { red[0][wid] = acc; red[1][wid] = hit; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double a = 0, h = 0;
+        for (int w = 0; w < nw; ++w) { a += red[0][w]; h += red[1][w]; }
+        nll[row * nll_stride] = a;
+        if (hits) hits[row * nll_stride] = h;
+    }
+}
+
+int launch_score_rows(const genie_cfg& c, const float* logits, const int64_t* targets, long target_clip_stride, int K, long N, double* nll,
+                      long nll_stride, double* hits, float* token_nll, long token_stride, hipStream_t st) {
+    if (N <= 0) return GENIE_OK;
+    GENIE_CHECK_SHAPE(N <= 0x7fffffffL, "score_rows: %ld rows", N);
+    int nw = c.S / 4;   // four tokens per wave at the least: S = 16 runs 4 waves, S >= 64 all 16
+    nw = nw < 1 ? 1 : (nw > GENIE_SCORE_MAX_WAVES ? GENIE_SCORE_MAX_WAVES : nw);
+    score_rows_kernel<<<(unsigned)N, 64 * nw, 0, st>>>(logits, targets, target_clip_stride, K, c.S, c.factored_vocab, c.num_factored, nll,
+                                                       nll_stride, hits, token_nll, token_stride);
+    GENIE_LAUNCH_CHECK("score_rows");
+    return GENIE_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // a13  MaskGIT sampling half (st_mask_git.py:171-190): per factor (most significant first) softmax,
 // argmax (first max wins) or inverse-CDF sample, sample = hi*Vf + lo, conf = prod p[sample].
 // One wavefront per token; strides make it layout-agnostic (vstride = 1 token-major, S for (B,V,S)).

@@ -486,6 +486,91 @@ def fanout_call(model, prompt_BPS, K, n_new, cond, dec, nz, uni, trunk=None, bra
     return gen
 
 
+class Score:
+    """What score_frames returns: nll (B, K, n) float64, the negative log-likelihood of each observed frame under each branch; hits
+    (B, K, n) float64, the count of tokens whose argmax equals the observed token in every factor; token_nll (B, K, n, H, W) float32, or
+    None unless per_token was asked for."""
+
+    def __init__(self, nll, hits, token_nll=None):
+        self.nll, self.hits, self.token_nll = nll, hits, token_nll
+
+    def __repr__(self):
+        return f"Score(nll={tuple(self.nll.shape)}, per_token={self.token_nll is not None})"
+
+
+def _score_inputs(model, clip_BTHW, num_prompt_frames, K, action_ids, action_vectors, prompt_actions, prompt_action_vectors):
+    """The checked inputs of score_frames, before the library is touched -> (B, P, n, K, prompt ids, branch ids, prompt vectors, branch
+    vectors) with the last four as _fanout_inputs returns them; raises in its style."""
+    cfg = model.config
+    clip = torch.as_tensor(clip_BTHW)
+    if clip.dim() != 4 or clip.shape[2] * clip.shape[3] != cfg.S:
+        raise RuntimeError(f"expected an observed clip (B, P + n, H, W) of {cfg.S} tokens per frame, got {tuple(clip.shape)}")
+    if clip.dtype.is_floating_point or clip.dtype == torch.bool:
+        raise RuntimeError(f"the clip must be an integer tensor of token ids, got {clip.dtype}")
+    P, n = int(num_prompt_frames), clip.shape[1] - int(num_prompt_frames)
+    if P < 1 or n < 1 or P + n > cfg.T:
+        raise ValueError(f"score_frames: {P} prompt + {n} scored frames must lie inside the window of {cfg.T}, with at least one of each")
+    if clip.numel() and (int(clip.min()) < 0 or int(clip.max()) >= cfg.image_vocab_size):
+        raise IndexError(f"token id out of range [0, {cfg.image_vocab_size}): min {int(clip.min())}, max {int(clip.max())} (an observed "
+                         "clip holds no mask tokens)")
+    if K is None and action_ids is None and action_vectors is None:
+        raise ValueError("score_frames: pass K (hypotheses per clip; 1 scores the clip itself), or per-branch actions that carry it")
+    B, P, K, pa, ba, pv, bv = _fanout_inputs(model, clip[:, :P], n, K, action_ids, action_vectors, prompt_actions, prompt_action_vectors)
+    return B, P, n, K, pa, ba, pv, bv
+
+
+def score_call(model, clip_BTS, P, K, cond, merge_commit=True, per_token=False, trunk=None, branch=None):
+    """ONE genie_score_fanout call -> (nll (B, K, n) float64, hits (B, K, n) float64, token_nll (B, K, n, S) float32 or None).  clip_BTS:
+    (B, P + n, S) int64, contiguous, the observed tokens; cond: fanout_cond.  trunk / branch: uint8 tensors of genie_prefix_cache_bytes(cfg,
+    B) and genie_fanout_branch_bytes(cfg, B, K, n) to keep what the call leaves in them (allocated here otherwise)."""
+    from . import _lib
+    lib = _lib.load()
+    cfg, w = model._weights()[:2]
+    B, Tc, S = clip_BTS.shape
+    n = Tc - P
+    assert clip_BTS.dtype == torch.int64 and clip_BTS.is_contiguous()
+    dev = clip_BTS.device
+    if trunk is None:
+        trunk = torch.empty(lib.genie_prefix_cache_bytes(cfg, B), dtype=torch.uint8, device=dev)
+    if branch is None:
+        branch = torch.empty(lib.genie_fanout_branch_bytes(cfg, B, K, n), dtype=torch.uint8, device=dev)
+    ws = torch.empty(lib.genie_score_workspace_bytes(cfg, B, K, P), dtype=torch.uint8, device=dev)
+    nll = torch.empty(B, K, n, dtype=torch.float64, device=dev)
+    hits = torch.empty(B, K, n, dtype=torch.float64, device=dev)
+    tok = torch.empty(B, K, n, S, dtype=torch.float32, device=dev) if per_token else None
+    _lib.check(lib.genie_score_fanout(cfg, w, clip_BTS.data_ptr(), B, K, P, n, int(bool(merge_commit)), nll.data_ptr(), hits.data_ptr(),
+                                      0 if tok is None else tok.data_ptr(), trunk.data_ptr(), trunk.numel(), branch.data_ptr(), branch.numel(),
+                                      ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream, cond), "genie_score_fanout")
+    return nll, hits, tok
+
+
+@torch.no_grad()
+def score_frames(model, clip_BTHW: torch.LongTensor, num_prompt_frames, K=None, action_ids=None, action_vectors=None, prompt_actions=None,
+                 prompt_action_vectors=None, per_token=False, merge_commit=True):
+    """How likely is what DID happen under each of K action hypotheses?  clip_BTHW (B, P + n, H, W): the observed tokens, P =
+    num_prompt_frames of them context.  -> Score with nll[b, k, j] = - sum over the frame's tokens and factors of log softmax(logits)[observed
+    token], the logits being MaskGIT step 0 of frame P + j (all-mask) behind the observed frames before it, under branch k's actions --
+    what generate_frames_cached(teacher_force_time=True) reports as its step-0 logits.  ONE library call (genie_score_fanout): the context
+    runs once per clip, the B * K hypotheses read it through the fan-out cache, and no logits leave the library.  In-window: P + n <= T.
+    action_ids (B, K, n) with prompt_actions (B, P), or action_vectors (B, K, n, action_dim) with prompt_action_vectors (B, P, action_dim),
+    as in fanout_frames; K is taken from them.  An unconditioned model takes K explicitly (K = 1: per-clip, per-frame scoring).
+    per_token: also return token_nll (B, K, n, H, W)."""
+    B, P, n, K, pa, ba, pv, bv = _score_inputs(model, clip_BTHW, num_prompt_frames, K, action_ids, action_vectors, prompt_actions,
+                                               prompt_action_vectors)
+    clip = torch.as_tensor(clip_BTHW).to(device=model._device(), dtype=torch.int64).reshape(B, P + n, model.config.S).contiguous()
+    cond = fanout_cond(model, B, P, K, n, pa, ba, pv, bv, clip.device)
+    nll, hits, tok = score_call(model, clip, P, K, cond, merge_commit=merge_commit, per_token=per_token)
+    return Score(nll, hits, None if tok is None else tok.view(B, K, n, model.h, model.w))
+
+
+def infer_actions(model, clip_BTHW, num_prompt_frames, **kwargs):
+    """Inverse dynamics by likelihood: which of the K action sequences explains the observed frames best?  -> (best (B,) int64, the argmin
+    over k of nll.sum(-1); nll (B, K, n) float64).  Arguments: score_frames.  The model does not promise that this recovers the actions a
+    future was generated with."""
+    nll = score_frames(model, clip_BTHW, num_prompt_frames, **kwargs).nll
+    return nll.sum(-1).argmin(dim=1), nll
+
+
 class Rollout:
     """An open-ended rollout: ``step(action)`` returns the next frame, ``extend(n, action_ids)`` the next n, each ONE
     genie_rollout_cached call that resumes the temporal KV cache of the call before it (the first runs the prompt).  Same frames as

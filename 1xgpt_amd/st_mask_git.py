@@ -699,6 +699,12 @@ class STMaskGIT(nn.Module):
         from .generate import fanout_frames
         return fanout_frames(self, prompt_BPHW, n_new, K=K, **kwargs)
 
+    def score(self, clip_BTHW, num_prompt_frames, K=None, **kwargs):
+        """Per-frame negative log-likelihood of the observed frames behind the prompt under K action hypotheses per clip -> a Score with
+        nll (B, K, n) float64: generate.score_frames (one library call, in-window)."""
+        from .generate import score_frames
+        return score_frames(self, clip_BTHW, num_prompt_frames, K=K, **kwargs)
+
     # ------------------------------------------------------------------ weights
     def init_weights(self):
         """N(0, 0.02) Linear/Embedding weights, zero biases (reference :281-296; the muP branch of the

@@ -612,6 +612,37 @@ int genie_temporal_attention_decode_fanout(const genie_cfg* cfg, const genie_att
                                            const float* branch_slice, float* out, int NBK, int K, int P0, int Tb, int t, int in16,
                                            void* stream);
 
+/* ---- scoring observed futures: per-branch NLL over the fan-out cache (ABI 3 addition; reference counterpart: none) ---------------------
+ * The reverse question of genie_generate_fanout: this is what DID happen -- how likely was it under each of K action hypotheses?
+ *     nll[b, k, j] = - sum over the S tokens and the factors of  log softmax(logits_j)[observed token]
+ * where logits_j are the MaskGIT step-0 logits of slot P + j with that slot all-mask, slots < P + j holding the OBSERVED tokens, and the
+ * actions of branch k: the logits genie_generate_cached_ex(teacher_force_time = 1) returns as logits0_out, and the per-token loss of
+ * genie_factored_ce.  Unguided, in-window (P + n <= T).  K = 1 scores each clip of an unconditioned or conditioned model per frame.
+ *
+ * genie_score_logits: the kernel alone, on token-major logits (N, S, V) of ONE frame (16-byte aligned).  Row i is scored against the S
+ *   int64 targets at targets + (i / K) * target_clip_stride (the K branches of a clip share its tokens; targets must lie in
+ *   [0, image_vocab_size)).  nll[i * nll_stride] (f64) = the row's NLL; hits[i * nll_stride] (f64, may be NULL) = the number of tokens
+ *   whose first-max-wins argmax equals the target in every factor; token_nll[i * token_stride + s] (f32, may be NULL) = each token's
+ *   loss.  One wave per token, ce_token_major_kernel's arithmetic (per factor: max, sum of expf(v - max), (logf(sum) + max) - target
+ *   logit); the row's sum is taken in f64 in a fixed order inside one workgroup, without atomics: two launches give identical bits.
+ * genie_score_fanout: ids (B, P + n, S), the observed clips.  Their P context frames run ONCE into `trunk` as in genie_generate_fanout;
+ *   then per slot t = P + j: the all-mask pass of B * K clips over the split cache (riding the commit of slot t - 1 as one two-frame pass
+ *   where merge_commit is set and the library covers it, by the rule of genie_generate_cached), the score launch against ids[:, P + j]
+ *   of the parent clip, and the commit of the observed tokens (not for the last slot).  No sample or mask-step launches, no draws, no
+ *   host synchronisation.  nll, hits (may be NULL): (B, K, n) f64; token_nll (may be NULL): (B, K, n, S) f32.
+ *   cond->ids (B * K, T), branch-major, as in genie_generate_fanout.  trunk: genie_prefix_cache_bytes(cfg, B); branch:
+ *   genie_fanout_branch_bytes(cfg, B, K, n); workspace: genie_score_workspace_bytes(cfg, B, K, P) (0 on bad arguments).
+ *   K = 1 gives, bit for bit, genie_score_logits of the logits0_out of the teacher-forced genie_generate_cached_ex; K > 1 the K = 1
+ *   scores of the K-times replicated batch.
+ * Argument errors (NULL pointers, K < 1, P < 1, n < 1, P + n > T, a buffer too small) return GENIE_E_ARG before anything is enqueued.
+ * Tests: tests/test_score_cpu.py, tests/test_hip_score.py. */
+int genie_score_logits(const genie_cfg* cfg, const float* logits, const int64_t* targets, int64_t target_clip_stride, int K, int64_t N,
+                       double* nll, int64_t nll_stride, double* hits, float* token_nll, int64_t token_stride, void* stream);
+size_t genie_score_workspace_bytes(const genie_cfg* cfg, int B, int K, int P);
+int genie_score_fanout(const genie_cfg* cfg, const genie_weights* w, const int64_t* ids, int B, int K, int P, int n, int merge_commit,
+                       double* nll, double* hits, float* token_nll, float* trunk, size_t trunk_bytes, float* branch, size_t branch_bytes,
+                       void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond);
+
 /* ---- optional per-launch timing (bench.py's roofline leg) ------------------------------------------------
  * When enabled, every launch of a kernel whose class bit is set in `class_mask` is bracketed by a pair of
  * HIP events recorded on the launch stream.  genie_profile_read synchronises those events and returns, for

@@ -125,6 +125,77 @@ def fanout_ab(a, m, cfg, extra):
     print(json.dumps({"workload": f"fan-out {P}->{N} frames x K={K} against the replicated batch, " + a.model + " " + a.precision, "results": res}))
 
 
+def teacher_forced_logits0(m, ex, P, cond=None):
+    """The step-0 logits (B, n, S, V) of genie_generate_cached_ex teacher-forced in time at one MaskGIT step: the route to per-frame
+    likelihoods without genie_score_fanout."""
+    L = importlib.import_module("1xgpt_amd._lib")
+    lib = L.load()
+    cfg, w = m._weights()[:2]
+    c = m.config
+    B, T = ex.shape[:2]
+    ids = ex.reshape(B, T, c.S).contiguous()
+    V = c.factored_vocab_size * c.num_factored_vocabs
+    gen = torch.empty(B, T - P, c.S, dtype=torch.int64, device="cuda")
+    lg = torch.empty(B, T - P, c.S, V, dtype=torch.float32, device="cuda")
+    ws = m._workspace(B, generate_prompt_frames=P)
+    nbytes = lib.genie_prefix_cache_bytes(cfg, B)
+    cache = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    L.check(L.call_guided(lib, "genie_generate_cached", cond, None, None, cfg, w, ids.data_ptr(), B, P, T - P, 1, 0.0, L.UNMASK_GREEDY, 0, 0, 1, 1,
+                          gen.data_ptr(), lg.data_ptr(), cache.data_ptr(), nbytes, ws.data_ptr(), ws.numel(),
+                          torch.cuda.current_stream().cuda_stream), "genie_generate_cached")
+    return lg
+
+
+def score_ab(a, m, cfg, extra):
+    """score_frames at (B, K) (prompt 8, 8 scored frames) against (1) the teacher-forced cached loop at one MaskGIT step on the K-times
+    replicated batch with its step-0 logits written out and the NLL taken in torch, and (2) fanout_frames at two steps on the same shape;
+    one call per leg per round, legs interleaved: per leg the median and the min-max spread, and the cache and logits bytes of each."""
+    synth = importlib.import_module("1xgpt_amd.synthetic")
+    G = importlib.import_module("1xgpt_amd.generate")
+    L = importlib.import_module("1xgpt_amd._lib")
+    lib, c = L.load(), m._weights()[0]
+    P, T, K = 8, cfg.T, a.score
+    N = T - P
+    V, nf, vf = cfg.factored_vocab_size * cfg.num_factored_vocabs, cfg.num_factored_vocabs, cfg.factored_vocab_size
+    res = []
+
+    def torch_nll(rep):
+        lg = teacher_forced_logits0(m, rep, P)                                       # (B K, N, S, V)
+        tg = rep[:, P:].reshape(-1, N, cfg.S)
+        nll = torch.zeros(tg.shape, dtype=torch.float32, device="cuda")
+        for f in range(nf):
+            lp = torch.log_softmax(lg[..., f * vf:(f + 1) * vf], dim=-1)
+            nll -= lp.gather(-1, ((tg // vf ** f) % vf)[..., None])[..., 0]
+        return nll.double().sum(-1)
+
+    for B in a.batches:
+        ex = torch.from_numpy(synth.make_clips(B, cfg, seed=7)).cuda().view(B, T, 16, 16)
+        rep = ex.repeat_interleave(K, dim=0).contiguous()
+        nz = torch.rand(N, 1, B * K, cfg.S, device="cuda")
+        split = lib.genie_prefix_cache_bytes(c, B) + lib.genie_fanout_branch_bytes(c, B, K, N)
+        legs = {"score": dict(fn=lambda: G.score_frames(m, ex, P, K=K), cache=split, logits=B * K * cfg.S * V * 4, times=[]),
+                "replicated_logits0_torch_ce": dict(fn=lambda: torch_nll(rep), cache=lib.genie_prefix_cache_bytes(c, B * K),
+                                                    logits=B * K * (N + 1) * cfg.S * V * 4, times=[]),
+                "fanout_steps2": dict(fn=lambda: G.fanout_frames(m, ex[:, :P], N, K=K, maskgit_steps=2, temperature=a.temperature, noise=nz,
+                                                                 **extra), cache=split, logits=B * K * cfg.S * V * 4, times=[])}
+        for leg in legs.values():
+            for _ in range(2):
+                leg["fn"]()
+        for _ in range(a.repeats):
+            for leg in legs.values():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                leg["fn"]()
+                torch.cuda.synchronize()
+                leg["times"].append(time.perf_counter() - t0)
+        for name, leg in legs.items():
+            t = sorted(leg["times"])
+            res.append({"leg": name, "batch": B, "K": K, "prompt": P, "frames": N, "median_ms": 1e3 * t[len(t) // 2], "min_ms": 1e3 * t[0],
+                        "max_ms": 1e3 * t[-1], "cache_bytes": leg["cache"], "logits_bytes": leg["logits"]})
+            print(res[-1], flush=True)
+    print(json.dumps({"workload": f"score {N} observed frames behind {P} x K={K}, " + a.model + " " + a.precision, "results": res}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--precision", default="f16x3")
@@ -152,6 +223,9 @@ def main():
     ap.add_argument("--fanout", type=int, default=None,
                     help="fan-out leg: per batch B, fanout_frames at (B, K) against generate_frames_cached on the K-times replicated batch "
                          "(prompt 8, 8 new frames), interleaved in one process, with the cache bytes of each")
+    ap.add_argument("--score", type=int, default=None,
+                    help="scoring leg: per batch B, score_frames at (B, K) against the teacher-forced cached loop with its step-0 logits and a "
+                         "torch CE on the K-times replicated batch, and against fanout_frames at two steps (prompt 8, 8 frames), interleaved")
     ap.add_argument("--keep", type=int, default=None, help="context frames the rollout re-runs per window (default: the prompt's 8)")
     a = ap.parse_args()
     extra = {}
@@ -178,6 +252,8 @@ def main():
         return rollout_ab(a, m, cfg, extra)
     if a.fanout is not None:
         return fanout_ab(a, m, cfg, extra)
+    if a.score is not None:
+        return score_ab(a, m, cfg, extra)
     res = []
     for B in a.batches:
         ex = torch.from_numpy(synth.make_clips(B, cfg, seed=7)).cuda().view(B, 16, 16, 16)

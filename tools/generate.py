@@ -9,7 +9,9 @@ An action-conditioned checkpoint (action_vocab_size > 0) generates with the exam
 --num_new_frames N rolls out N frames behind the prompt, past the model's window if need be (the window slides by T - keep frames and
 re-runs the last --keep frames as its context); the output is then [prompt | N generated | whatever ground truth exists].
 --fanout K generates K candidate futures of the example over one shared context cache (in-window; branches differ by their sampling
-draws and, for an action-conditioned model, by the (K, n_new) action ids of --fanout_actions); branch k is written to OUTPUT_DIR/branch_k."""
+draws and, for an action-conditioned model, by the (K, n_new) action ids of --fanout_actions); branch k is written to OUTPUT_DIR/branch_k.
+--score generates nothing: it prints the negative log-likelihood of each observed frame behind the prompt (score_frames), one row per
+action hypothesis of --fanout_actions (or the example's own actions)."""
 import argparse
 import importlib
 import os
@@ -53,7 +55,30 @@ def build_parser():
     ap.add_argument("--fanout_actions", type=str, default=None,
                     help="With --fanout on an action-conditioned model: a text file of K rows of n_new action ids, one row per branch "
                          "(the prompt frames keep the example's actions).")
+    ap.add_argument("--score", action="store_true",
+                    help="Generate nothing: print the per-frame negative log-likelihood of the example's observed frames behind the prompt "
+                         "(score_frames). On an action-conditioned model --fanout_actions scores K hypotheses (K rows of ids) and names the "
+                         "likeliest; without it the example's own actions are scored.")
     return ap
+
+
+def score_main(args, model, ex, actions, G):
+    """--score: one line per hypothesis, the NLL of each observed frame in nats and their sum."""
+    import numpy as np
+    P = args.num_prompt_frames
+    N = args.window_size - P if args.num_new_frames is None else args.num_new_frames
+    kw = dict(K=1)
+    if model.config.action_vocab_size:
+        ids = actions[:, P:P + N].numpy()
+        if args.fanout_actions is not None:
+            ids = np.loadtxt(args.fanout_actions, dtype=np.int64, ndmin=2)
+            if ids.shape[1] != N:
+                sys.exit(f"generate.py: --fanout_actions holds {ids.shape} ids, expected (K, {N})")
+        kw = dict(action_ids=torch.from_numpy(np.ascontiguousarray(ids))[None].to("cuda"), prompt_actions=actions[:, :P].to("cuda"))
+    best, nll = G.infer_actions(model, ex[:, :P + N], P, **kw)
+    for k, row in enumerate(nll[0].tolist()):
+        print(f"hypothesis {k}: nll per frame [" + ", ".join(f"{v:.3f}" for v in row) + f"] sum {sum(row):.3f}")
+    print(f"likeliest hypothesis: {int(best[0])}")
 
 
 def fanout_main(args, model, ex, actions, meta, sampling, guidance, G):
@@ -105,6 +130,8 @@ def main():
             actions = item["action_ids"][None]
     model = model.to("cuda")
     ex = example.to("cuda").view(1, args.window_size, model.h, model.w)
+    if args.score:
+        return score_main(args, model, ex, actions, G)
     if args.fanout is not None:
         return fanout_main(args, model, ex, actions, meta, sampling, guidance, G)
     if args.num_new_frames is not None:
