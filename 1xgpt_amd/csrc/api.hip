@@ -1,6 +1,6 @@
 // C ABI of libgenie_hip.so (include/genie_hip.h): argument checking, workspace carving and the
-// launch sequences of decoder / MaskGIT / generate (the layer itself and the readout: st_block.hip).  All work is enqueued on the caller's
-// stream; nothing here allocates, synchronises or touches the host-side of any tensor.
+// launch sequences of the single passes (the layer itself and the readout: st_block.hip; the generate loops over these passes:
+// generate_api.hip).  All work is enqueued on the caller's stream; nothing here allocates, synchronises or touches the host-side of any tensor.
 #include <math.h>
 #include <stdarg.h>
 #include <stddef.h>
@@ -43,7 +43,7 @@ ProfScope::~ProfScope() {
 }
 
 // Workspace carving (struct Workspace: kernels.hpp).  All offsets 256-byte aligned.
-static Workspace carve(const genie_cfg& c, int B, void* base) {
+Workspace carve(const genie_cfg& c, int B, void* base) {
     Workspace w;
     const size_t M = (size_t)B * c.T * c.S;
     const size_t wide = (size_t)(3 * c.d_model > c.hidden ? 3 * c.d_model : c.hidden);
@@ -68,7 +68,7 @@ static Workspace carve(const genie_cfg& c, int B, void* base) {
     return w;
 }
 
-static int check_cfg(const genie_cfg* c) {
+int check_cfg(const genie_cfg* c) {
     GENIE_CHECK_ARG(c != nullptr, "cfg is NULL");
     GENIE_CHECK_SHAPE(c->num_layers >= 1 && c->num_heads >= 1, "num_layers/num_heads must be >= 1");
     GENIE_CHECK_SHAPE(c->d_model == c->num_heads * c->head_dim, "d_model %d != num_heads %d * head_dim %d", c->d_model,
@@ -100,7 +100,7 @@ static int check_cfg(const genie_cfg* c) {
     return GENIE_OK;
 }
 
-static int check_ws(const genie_cfg& c, int B, void* ws, size_t bytes) {
+int check_ws(const genie_cfg& c, int B, void* ws, size_t bytes) {
     GENIE_CHECK_ARG(B >= 1, "B=%d must be >= 1", B);
     GENIE_CHECK_ARG(ws != nullptr, "workspace is NULL");
     size_t need = carve(c, B, nullptr).total;
@@ -125,23 +125,19 @@ static int run_layers(const genie_cfg& c, const genie_layer_weights* layers, int
     return GENIE_OK;
 }
 
-static int decoder(const genie_cfg& c, const genie_weights& wt, float* x, Workspace& w, int B, hipStream_t st) {
+int decoder(const genie_cfg& c, const genie_weights& wt, float* x, Workspace& w, int B, hipStream_t st) {
     return run_layers(c, wt.layers_host, c.num_layers, x, w, B, st,
                       [&](int, const genie_layer_weights* next) { return BlockPass::plain(c, next, c.T); });
 }
 
-static int mask_count(int step, int steps, int S) {
+int mask_count(int step, int steps, int S) {
     // n = ceil(cos(pi/2 * (step+1)/steps) * S), python float math (st_mask_git.py:17-26,199)
     double u = (double)(step + 1) / (double)steps;
     return (int)ceil(cos(u * M_PI / 2.0) * (double)S);
 }
 
-}  // namespace genie
-
-using namespace genie;
-
 // a genie_sampling law (NULL = none), checked on the host before anything is enqueued
-static int check_sampling(const genie_sampling* sp, const char* where) {
+int check_sampling(const genie_sampling* sp, const char* where) {
     if (!sp) return GENIE_OK;
     GENIE_CHECK_ARG(sp->logit_temperature > 0.f && sp->logit_temperature <= 3.0e38f,
                     "%s: sampling: logit_temperature %g must be positive and finite", where, (double)sp->logit_temperature);
@@ -152,7 +148,7 @@ static int check_sampling(const genie_sampling* sp, const char* where) {
     return GENIE_OK;
 }
 // unmask_mode and the draws it needs; GENIE_UNMASK_CONFIDENCE only through the *_ex entry points (ex)
-static int check_unmask(int unmask_mode, bool ex, int steps, const float* noise, const char* where) {
+int check_unmask(int unmask_mode, bool ex, int steps, const float* noise, const char* where) {
     const bool known = unmask_mode == GENIE_UNMASK_RANDOM || unmask_mode == GENIE_UNMASK_GREEDY ||
                        (ex && unmask_mode == GENIE_UNMASK_CONFIDENCE);
     if (!known) {
@@ -166,7 +162,7 @@ static int check_unmask(int unmask_mode, bool ex, int steps, const float* noise,
     return GENIE_OK;
 }
 // a genie_guidance (NULL = none) and the condition it needs, checked on the host before anything is enqueued
-static int check_guidance(const genie_guidance* g, const genie_frame_cond* cond, const char* where) {
+int check_guidance(const genie_guidance* g, const genie_frame_cond* cond, const char* where) {
     if (!g) return GENIE_OK;
     GENIE_CHECK_ARG(isfinite(g->scale), "%s: guidance: scale %g must be finite", where, (double)g->scale);
     GENIE_CHECK_ARG(cond && cond->n_actions > 0, "%s: guidance needs an action condition (cond with n_actions > 0)", where);
@@ -175,7 +171,11 @@ static int check_guidance(const genie_guidance* g, const genie_frame_cond* cond,
     return GENIE_OK;
 }
 // the confidence mode's scale when the caller gave no law: the documented default of choice_temperature
-static const genie_sampling kDefaultSampling = {1.0f, 0, 1.0f, 4.5f};
+const genie_sampling kDefaultSampling = {1.0f, 0, 1.0f, 4.5f};
+
+}  // namespace genie
+
+using namespace genie;
 
 extern "C" {
 
@@ -467,20 +467,11 @@ int genie_frames_pass(const genie_cfg* cfg, const genie_weights* wt, const int64
                                   nullptr);
 }
 
-// The split cache of a fan-out call (genie_generate_fanout): the B clips of a decode pass are K branches each of B / K parent clips.
-// Slots [0, P0) live in `trunk`, a T-slot cache of B / K clips that the context pass filled and no decode pass writes; slot j >= P0 is
-// slot j - P0 of the pass's own cache, (L, B, Tb, S, 3d).
-struct FanOut {
-    const float* trunk;
-    int K, P0, Tb;
-};
-static size_t fanout_branch_bytes(const genie_cfg& c, size_t NBK, int Tb) {
-    return (size_t)c.num_layers * NBK * Tb * c.S * 3 * c.d_model * sizeof(float);
-}
+}  // extern "C"
 
-// genie_frames_pass_cond, and with fan != NULL the decode pass of a fan-out call: `cache` is then the branch cache, and every such pass
-// has t0 >= P0 -- nothing writes the trunk after the context pass
-static int frames_pass(const genie_cfg* cfg, const genie_weights* wt, const int64_t* frame_ids, int B, int t0, int nf, float* cache,
+// genie_frames_pass_cond, and with fan != NULL the decode pass of a fan-out call (generate_api.hip): `cache` is then the branch cache, and
+// every such pass has t0 >= P0 -- nothing writes the trunk after the context pass
+int genie::frames_pass(const genie_cfg* cfg, const genie_weights* wt, const int64_t* frame_ids, int B, int t0, int nf, float* cache,
                        size_t cache_bytes, float* logits, void* workspace, size_t workspace_bytes, void* stream,
                        const genie_frame_cond* cond, const FanOut* fan) {
     GENIE_TRY(check_cfg(cfg));
@@ -536,6 +527,8 @@ static int frames_pass(const genie_cfg* cfg, const genie_weights* wt, const int6
     return readout(c1, *wt, w.x, w, B, 0, 1, GENIE_LAYOUT_TOKEN_MAJOR, logits, st);
 }
 
+extern "C" {
+
 int genie_frames_pass_cond(const genie_cfg* cfg, const genie_weights* wt, const int64_t* frame_ids, int B, int t0, int nf,
                            float* cache, size_t cache_bytes, float* logits, void* workspace, size_t workspace_bytes,
                            void* stream, const genie_frame_cond* cond) {
@@ -559,513 +552,6 @@ int genie_frame_linear(const uint16_t* a_fr, const uint16_t* w_fr, const float* 
     return launch_frame_linear(a_fr, w_fr, bias, y, M, N, K, mode, as_stream(stream));
 }
 
-// rows of S token ids: dst[b][0..S) = src[b][0..S) (clip strides in elements) or, src == NULL, the fill value; `copies` > 1 repeats the
-// B rows at dst rows B .. 2B - 1, ... (the doubled batch of the guided loops)
-__global__ void frame_ids_kernel(const int64_t* __restrict__ src, long src_stride, int64_t* __restrict__ dst, long dst_stride, int S, int B,
-                                 int64_t fill, int copies) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long per = (long)B * S;
-    if (i >= per * copies) return;
-    const long r = i / per, j = i - r * per;
-    const long b = j / S, s = j - b * S;
-    dst[(r * B + b) * dst_stride + s] = src ? src[b * src_stride + s] : fill;
-}
-static int put_frame_ids(const int64_t* src, long src_stride, int64_t* dst, long dst_stride, int S, int B, int64_t fill, hipStream_t st,
-                         int copies = 1) {
-    frame_ids_kernel<<<(unsigned)(((long)B * S * copies + 255) / 256), 256, 0, st>>>(src, src_stride, dst, dst_stride, S, B, fill, copies);
-    GENIE_LAUNCH_CHECK("frame_ids");
-    return GENIE_OK;
-}
-// the (2B, T) actions of a guided pass: the clips' own ids, then null_action at every frame
-__global__ void guided_actions_kernel(const int64_t* __restrict__ ids, int64_t* __restrict__ out, long n, int64_t null_action) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < 2 * n) out[i] = i < n ? ids[i] : null_action;
-}
-static int put_guided_actions(const genie_frame_cond& cond, const genie_guidance& g, int B, int T, int64_t* out, hipStream_t st) {
-    const long n = (long)B * T;
-    guided_actions_kernel<<<(unsigned)((2 * n + 255) / 256), 256, 0, st>>>(cond.ids, out, n, g.null_action);
-    GENIE_LAUNCH_CHECK("guided_actions");
-    return GENIE_OK;
-}
-
-// where the loop scratch of genie_generate_cached starts: behind the workspace of its largest pass
-static size_t generate_scratch_offset(const genie_cfg& c, int B, int P) {
-    genie_cfg cm = c;
-    cm.T = P > 2 ? P : 2;
-    return carve(cm, B, nullptr).total;
-}
-
-// The loop scratch of genie_generate_cached_*: B clips are decoded, NB clips run through every pass (NB == B, or 2 B under guidance:
-// [conditional ; null]).  The size functions and the loop both carve here (base == NULL: sizes only).
-// A fan-out call (genie_generate_fanout) carves the same buffers: its context runs NBctx = NB / K clips, and it keeps their (NBctx, T)
-// actions beside the branches' (NB, T).
-struct GenScratch {
-    int64_t *idsP, *two, *cur, *fin, *samples, *acts, *acts_ctx;
-    float *conf, *logits;
-    uint8_t* unmasked;
-    size_t end;
-};
-// off: where the scratch starts; NBctx: clips of the context pass (idsP)
-static GenScratch carve_loop(const genie_cfg& c, int B, int NB, int NBctx, int P, size_t off, char* base, bool acts) {
-    const size_t BS = (size_t)B * c.S, NBS = (size_t)NB * c.S, V = (size_t)c.factored_vocab * c.num_factored;
-    auto take = [&](size_t bytes) { char* r = base ? base + off : nullptr; off += align_up(bytes, 256); return r; };
-    GenScratch g;
-    g.idsP = (int64_t*)take((size_t)NBctx * c.S * P * 8);
-    g.two = (int64_t*)take(NBS * 2 * 8);
-    g.cur = (int64_t*)take(NBS * 8);
-    g.fin = (int64_t*)take(NBS * 8);
-    g.samples = (int64_t*)take(BS * 8);
-    g.conf = (float*)take(BS * 4);
-    g.unmasked = (uint8_t*)take(BS);
-    g.logits = (float*)take(NBS * V * 4);
-    g.acts = acts ? (int64_t*)take((size_t)NB * c.T * 8) : nullptr;
-    g.acts_ctx = NBctx != NB ? (int64_t*)take((size_t)NBctx * c.T * 8) : nullptr;
-    g.end = off;
-    return g;
-}
-static GenScratch carve_generate(const genie_cfg& c, int B, int NB, int P, char* base, bool window_acts = false) {
-    return carve_loop(c, B, NB, NB, P, generate_scratch_offset(c, NB, P), base, NB != B || window_acts);   // window_acts: the rollout's action window
-}
-// ... of genie_generate_fanout: B * K clips are decoded, NB * K run through every decode pass, NB through the context pass.  The scratch
-// starts behind the larger of the context pass (NB clips, P frames) and a two-frame pass of NB * K clips.
-static GenScratch carve_fanout(const genie_cfg& c, int B, int NB, int K, int P, char* base) {
-    genie_cfg cm = c;
-    cm.T = P;
-    const size_t ctx = carve(cm, NB, nullptr).total;
-    cm.T = 2;
-    const size_t two = carve(cm, NB * K, nullptr).total;
-    return carve_loop(c, B * K, NB * K, NB, P, ctx > two ? ctx : two, base, true);
-}
-// ... of genie_maskgit_generate_guided behind the model's workspace for 2 B clips: the doubled prompt and the (2B, T) actions
-struct GuidedPrompt {
-    int64_t *prompt2, *acts;
-    size_t end;
-};
-static GuidedPrompt carve_guided_prompt(const genie_cfg& c, int NB, char* base) {
-    size_t off = carve(c, NB, nullptr).total;
-    auto take = [&](size_t bytes) { char* r = base ? base + off : nullptr; off += align_up(bytes, 256); return r; };
-    GuidedPrompt g;
-    g.prompt2 = (int64_t*)take((size_t)NB * c.T * c.S * 8);
-    g.acts = (int64_t*)take((size_t)NB * c.T * 8);
-    g.end = off;
-    return g;
-}
-
-size_t genie_generate_workspace_bytes(const genie_cfg* cfg, int B, int P) {
-    if (check_cfg(cfg) != GENIE_OK || B < 1 || P < 1 || P > cfg->T) return 0;
-    const size_t off = carve_generate(*cfg, B, B, P, nullptr).end;
-    const size_t full = carve(*cfg, B, nullptr).total;   // (the passes themselves check against the model's own workspace size)
-    return off > full ? off : full;
-}
-
-size_t genie_generate_guided_workspace_bytes(const genie_cfg* cfg, int B, int P) {
-    if (check_cfg(cfg) != GENIE_OK || B < 1 || B > 0x3fffffff || P < 1 || P > cfg->T) return 0;
-    const size_t off = carve_generate(*cfg, B, 2 * B, P, nullptr).end;
-    const size_t full = carve_guided_prompt(*cfg, 2 * B, nullptr).end;   // (>= the model's own workspace for 2 B clips)
-    return off > full ? off : full;
-}
-
-int genie_generate_cached(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int P, int n_new, int steps,
-                          float temperature, int unmask_mode, const float* noise, const float* uniforms, int teacher_force_time,
-                          int merge_commit, int64_t* gen_out, float* logits0_out, float* cache, size_t cache_bytes, void* workspace,
-                          size_t workspace_bytes, void* stream) {
-    return genie_generate_cached_cond(cfg, wt, ids, B, P, n_new, steps, temperature, unmask_mode, noise, uniforms, teacher_force_time,
-                                      merge_commit, gen_out, logits0_out, cache, cache_bytes, workspace, workspace_bytes, stream,
-                                      nullptr);
-}
-
-int genie_generate_cached_cond(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int P, int n_new,
-                               int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
-                               int teacher_force_time, int merge_commit, int64_t* gen_out, float* logits0_out, float* cache,
-                               size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
-                               const genie_frame_cond* cond) {
-    if (unmask_mode == GENIE_UNMASK_CONFIDENCE) unmask_mode = -1;   // (only genie_generate_cached_ex knows that mode)
-    return genie_generate_cached_ex(cfg, wt, ids, B, P, n_new, steps, temperature, unmask_mode, noise, uniforms, teacher_force_time,
-                                    merge_commit, gen_out, logits0_out, cache, cache_bytes, workspace, workspace_bytes, stream, cond,
-                                    nullptr);
-}
-
-// What one generate / rollout call decodes with: its checked arguments and the carved scratch, shared by every window of the call.
-// B clips are decoded, NB run through every pass.
-struct GenLoop {
-    const genie_cfg* cfg;
-    const genie_weights* wt;
-    int B, NB, copies, steps, unmask_mode, merge_commit;
-    float temperature;
-    const genie_sampling* law;
-    const genie_guidance* guidance;
-    bool guided;
-    const genie_frame_cond* cond;   // what the passes embed with: ids (NB, cfg->T)
-    float* cache;
-    size_t cache_bytes;
-    void* workspace;
-    size_t workspace_bytes;
-    void* stream;
-    GenScratch g;
-    const FanOut* fan = nullptr;    // a fan-out call's decode passes: `cache` is the branch cache (the context ran into fan->trunk)
-};
-// the decode options every loop entry point takes, checked on the host before anything is enqueued
-static int check_decode(int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
-                        const genie_sampling* sampling, const char* where) {
-    GENIE_TRY(check_sampling(sampling, where));
-    GENIE_TRY(check_unmask(unmask_mode, unmask_mode != -1, steps, noise, where));
-    GENIE_CHECK_ARG(temperature <= 1e-8f || uniforms, "%s: temperature > 0 needs uniforms", where);
-    return GENIE_OK;
-}
-
-// `ctx` context frames into cache slots 0 .. ctx-1: one ctx-frame pass over idsP (NB, ctx, S, already filled) where the fragment-order
-// kernels cover it, else the clean pass with the cache's T-frame layout, else frame by frame from src (frame t of clip b at
-// src + b * src_stride + t * S)
-static int run_context(const GenLoop& L, int ctx, const int64_t* src, long src_stride) {
-    const genie_cfg& c = *L.cfg;
-    hipStream_t st = as_stream(L.stream);
-    int rc = GENIE_E_UNSUPPORTED;
-    if (ctx > 1) {
-        rc = genie_frames_pass_cond(L.cfg, L.wt, L.g.idsP, L.NB, 0, ctx, L.cache, L.cache_bytes, nullptr, L.workspace, L.workspace_bytes,
-                                    L.stream, L.cond);
-        if (rc == GENIE_E_UNSUPPORTED)
-            rc = genie_clean_pass_cond(L.cfg, L.wt, L.g.idsP, L.NB, ctx, c.T, L.cache, L.cache_bytes, L.workspace, L.workspace_bytes,
-                                       L.stream, L.cond);
-    }
-    if (rc != GENIE_E_UNSUPPORTED) return rc;
-    for (int t = 0; t < ctx; ++t) {
-        GENIE_TRY(put_frame_ids(src + (size_t)t * c.S, src_stride, L.g.fin, c.S, c.S, L.B, 0, st, L.copies));
-        GENIE_TRY(genie_frames_pass_cond(L.cfg, L.wt, L.g.fin, L.NB, t, 1, L.cache, L.cache_bytes, nullptr, L.workspace, L.workspace_bytes,
-                                         L.stream, L.cond));
-    }
-    return GENIE_OK;
-}
-
-// The window body: decodes cache slots t0 .. t0 + n - 1 one after the other (slots < t0 - 1 are committed; slot t0 - 1 too unless `pend`).
-// Slot t0 + k draws from noise / uniforms [k] and its final tokens go to out + k * S (clip stride out_stride); its step-0 logits to
-// logits0_out[:, k] of (B, n, S, V) when wanted.  Every slot but the LAST is committed -- from its final tokens, or from tf + k * S (clip
-// stride tf_stride) when tf is given (teacher forcing in time) --, merged with step 0 of the next slot where merge_commit is set and the
-// library covers it.  pend != NULL: slot t0 - 1 is still pending; its final tokens (pend, clip stride pend_stride) are committed first, by
-// the same rule.
-static int decode_slots(const GenLoop& L, int t0, int n, const float* noise, const float* uniforms, int64_t* out, long out_stride,
-                        float* logits0_out, const int64_t* tf, long tf_stride, const int64_t* pend, long pend_stride) {
-    const genie_cfg* cfg = L.cfg;
-    const genie_cfg& c = *cfg;
-    const genie_weights* wt = L.wt;
-    const int B = L.B, NB = L.NB, copies = L.copies, steps = L.steps, unmask_mode = L.unmask_mode, S = c.S;
-    const float temperature = L.temperature;
-    const bool guided = L.guided, by_conf = unmask_mode == GENIE_UNMASK_CONFIDENCE;
-    const genie_frame_cond* cond = L.cond;
-    float* cache = L.cache;
-    const size_t cache_bytes = L.cache_bytes, workspace_bytes = L.workspace_bytes;
-    void *workspace = L.workspace, *stream = L.stream;
-    hipStream_t st = as_stream(stream);
-    const size_t BS = (size_t)B * S, V = (size_t)c.factored_vocab * c.num_factored;
-    int64_t *two = L.g.two, *cur = L.g.cur, *fin = L.g.fin, *samples = L.g.samples;
-    float *conf = L.g.conf, *logits = L.g.logits;
-    uint8_t* unmasked = L.g.unmasked;
-    const float* logits_null = logits + BS * V;   // guided: rows B .. 2B - 1 of every pass's logits
-    bool opened = false, merge = L.merge_commit != 0;
-    auto pass = [&](const int64_t* frame_ids, int t, int nf, float* lg) {
-        return frames_pass(cfg, wt, frame_ids, NB, t, nf, cache, cache_bytes, lg, workspace, workspace_bytes, stream, cond, L.fan);
-    };
-    // commit slot t from fsrc: in the pass that also carries MaskGIT step 0 of slot t + 1 (all-mask tokens), or on its own
-    auto commit = [&](int t, const int64_t* fsrc, long fstride) -> int {
-        if (merge) {
-            GENIE_TRY(put_frame_ids(fsrc, fstride, two, 2L * S, S, B, 0, st, copies));
-            GENIE_TRY(put_frame_ids(nullptr, 0, two + S, 2L * S, S, B, c.image_vocab_size, st, copies));
-            const int rc = pass(two, t, 2, logits);
-            if (rc == GENIE_E_UNSUPPORTED) merge = false;
-            else { GENIE_TRY(rc); opened = true; }
-        }
-        if (!opened) {
-            GENIE_TRY(put_frame_ids(fsrc, fstride, fin, S, S, B, 0, st, copies));
-            GENIE_TRY(pass(fin, t, 1, nullptr));
-        }
-        return GENIE_OK;
-    };
-    if (pend) GENIE_TRY(commit(t0 - 1, pend, pend_stride));
-    for (int k = 0; k < n; ++k) {
-        const int t = t0 + k;
-        GENIE_TRY(put_frame_ids(nullptr, 0, cur, S, S, B, c.image_vocab_size, st, copies));
-        if (hipMemsetAsync(unmasked, 0, BS, st) != hipSuccess) { set_error("memset failed"); return GENIE_E_LAUNCH; }
-        for (int step = 0; step < steps; ++step) {
-            if (!(step == 0 && opened))
-                GENIE_TRY(pass(cur, t, 1, logits));
-            if (step == 0 && logits0_out) {   // orig_logits of the frame (st_mask_git.py:165,226): the step-0 logits, (B, n, S, V)
-                if (guided) {                 // ... the guided ones
-                    GENIE_TRY(launch_guide_logits(logits, logits_null, logits0_out + (size_t)k * S * V, B, (long)(S * V), (long)(S * V),
-                                                  (long)((size_t)n * S * V), L.guidance->scale, st));
-                } else if (hipMemcpy2DAsync(logits0_out + (size_t)k * S * V, (size_t)n * S * V * 4, logits, (size_t)S * V * 4,
-                                            (size_t)S * V * 4, (size_t)B, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-                    set_error("memcpy failed");
-                    return GENIE_E_LAUNCH;
-                }
-            }
-            const float* u = temperature > 1e-8f ? uniforms + ((size_t)k * steps + step) * c.num_factored * BS : nullptr;
-            const bool last = step == steps - 1;
-            const float* draws = (last || unmask_mode == GENIE_UNMASK_GREEDY) ? nullptr : noise + ((size_t)k * (steps - 1) + step) * BS;
-            // "confidence": the sample launch writes the keys over conf (nothing else reads conf in this loop)
-            const float anneal = 1.0f - (float)(step + 1) / (float)steps;
-            if (guided)
-                GENIE_TRY(launch_sample_guided(c, logits, logits_null, GENIE_LAYOUT_TOKEN_MAJOR, B, temperature, u, samples, conf, L.law,
-                                               (by_conf && !last) ? conf : nullptr, draws, anneal, L.guidance->scale, st));
-            else
-                GENIE_TRY(launch_sample_ex(c, logits, GENIE_LAYOUT_TOKEN_MAJOR, B, temperature, u, samples, conf, L.law,
-                                           (by_conf && !last) ? conf : nullptr, draws, anneal, st));
-            const float* keys = last ? nullptr : (unmask_mode == GENIE_UNMASK_RANDOM ? draws : conf);
-            GENIE_TRY(launch_mask_step(keys, last ? 0 : mask_count(step, steps, S), last, c.image_vocab_size, unmasked, samples, cur, S, B, S, st));
-            if (guided) GENIE_TRY(put_frame_ids(cur, S, cur + BS, S, S, B, 0, st));   // the null half sees the same tokens
-        }
-        GENIE_TRY(put_frame_ids(cur, S, out + (size_t)k * S, out_stride, S, B, 0, st));
-        opened = false;
-        if (k + 1 < n) {   // commit slot t: its final tokens, or the ground truth when teacher-forcing in time
-            if (tf) GENIE_TRY(commit(t, tf + (size_t)k * S, tf_stride));
-            else GENIE_TRY(commit(t, cur, S));
-        }
-    }
-    return GENIE_OK;
-}
-
-// genie_generate_cached_ex (guidance NULL or of scale 1) and genie_generate_cached_guided: one loop, B clips decoded, NB per pass
-static int generate_cached_loop(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int P, int n_new,
-                                int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
-                                int teacher_force_time, int merge_commit, int64_t* gen_out, float* logits0_out, float* cache,
-                                size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
-                                const genie_frame_cond* cond, const genie_sampling* sampling, const genie_guidance* guidance) {
-    GENIE_TRY(check_cfg(cfg));
-    const genie_cfg& c = *cfg;
-    GENIE_CHECK_ARG(wt && wt->layers_host && ids && gen_out && cache, "generate_cached: NULL pointer");
-    GENIE_TRY(check_frame_cond(cond, "generate_cached"));
-    GENIE_TRY(check_guidance(guidance, cond, "generate_cached"));
-    GENIE_CHECK_ARG(B >= 1 && P >= 1 && n_new >= 1 && P + n_new <= c.T && steps >= 1,
-                    "generate_cached: B=%d, %d prompt + %d new frames of at most %d, steps %d", B, P, n_new, c.T, steps);
-    GENIE_TRY(check_decode(steps, temperature, unmask_mode, noise, uniforms, sampling, "generate_cached"));
-    const bool by_conf = unmask_mode == GENIE_UNMASK_CONFIDENCE;
-    // under guidance every pass runs 2 B clips, [conditional ; null]: rows b and b + B hold the same tokens, the second half's actions are
-    // null_action at every frame; B rows are sampled, masked and written out
-    const bool guided = guidance && guidance->scale != 1.0f;
-    GENIE_CHECK_ARG(!guided || B <= 0x3fffffff, "generate_cached: B=%d too large for guidance", B);
-    const int NB = guided ? 2 * B : B, copies = guided ? 2 : 1;
-    GENIE_CHECK_ARG(cache_bytes >= genie_prefix_cache_bytes(cfg, NB), "generate_cached: cache too small");
-    GENIE_TRY(check_ws(c, NB, workspace, workspace_bytes));
-    hipStream_t st = as_stream(stream);
-    const int S = c.S, T = P + n_new;   // frames per clip in `ids` (the cache keeps the model's c.T slots per clip)
-    // scratch of the loop behind the workspace of its largest pass (the prompt's P frames; two frames for the merged passes):
-    // genie_generate_workspace_bytes / genie_generate_guided_workspace_bytes (cfg, B, P) is the size to allocate
-    GenLoop L = {cfg, wt, B, NB, copies, steps, unmask_mode, merge_commit, temperature, (by_conf && !sampling) ? &kDefaultSampling : sampling,
-                 guidance, guided, cond, cache, cache_bytes, workspace, workspace_bytes, stream, carve_generate(c, B, NB, P, (char*)workspace)};
-    GENIE_CHECK_ARG(L.g.end <= workspace_bytes, "generate_cached: workspace too small (%zu < %zu bytes: size it with %s)", workspace_bytes,
-                    L.g.end, guided ? "genie_generate_guided_workspace_bytes" : "genie_generate_workspace_bytes");
-    genie_frame_cond cond2;
-    if (guided) {
-        GENIE_TRY(put_guided_actions(*cond, *guidance, B, c.T, L.g.acts, st));
-        cond2 = *cond;
-        cond2.ids = L.g.acts;
-        L.cond = &cond2;
-    }
-    // ---- the prompt fills cache slots 0 .. P-1
-    for (int t = 0; t < P; ++t)
-        GENIE_TRY(put_frame_ids(ids + (size_t)t * S, (long)T * S, L.g.idsP + (size_t)t * S, (long)P * S, S, B, 0, st, copies));
-    GENIE_TRY(run_context(L, P, ids, (long)T * S));
-    return decode_slots(L, P, n_new, noise, uniforms, gen_out, (long)n_new * S, logits0_out,
-                        teacher_force_time ? ids + (size_t)P * S : nullptr, (long)T * S, nullptr, 0);
-}
-
-// What the passes of one rollout window read, gathered from the caller's (B, cap, *) buffers in one launch:
-//   ctx_out (B * copies, ctx, S): the tokens of absolute frames [start, start + ctx); rows b + B (copies == 2) repeat rows b
-//   act_out (B * copies, T) or NULL: slot i = the action of absolute frame start + i, 0 past cap (never embedded); rows b + B = null_action
-__global__ void rollout_window_kernel(const int64_t* __restrict__ frames, const int64_t* __restrict__ actions, int64_t* __restrict__ ctx_out,
-                                      int64_t* __restrict__ act_out, int B, int copies, int ctx, int S, int T, long cap, long start,
-                                      int64_t null_action) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long per = (long)ctx * S, ntok = (long)B * copies * per;
-    if (i < ntok) {
-        const long r = i / per, j = i - r * per, b = r % B;
-        ctx_out[i] = frames[(b * cap + start) * S + j];
-        return;
-    }
-    const long a = i - ntok;
-    if (!act_out || a >= (long)B * copies * T) return;
-    const long r = a / T, f = start + (a - r * T);
-    act_out[a] = r >= B ? null_action : (f < cap ? actions[r * cap + f] : 0);
-}
-static int put_rollout_window(const int64_t* frames, const int64_t* actions, int64_t* ctx_out, int64_t* act_out, int B, int copies,
-                              int ctx, int S, int T, long cap, long start, int64_t null_action, hipStream_t st) {
-    const long n = (long)B * copies * ((long)ctx * S + (act_out ? T : 0));
-    if (n == 0) return GENIE_OK;
-    rollout_window_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(frames, actions, ctx_out, act_out, B, copies, ctx, S, T, cap, start,
-                                                                       null_action);
-    GENIE_LAUNCH_CHECK("rollout_window");
-    return GENIE_OK;
-}
-
-size_t genie_rollout_workspace_bytes(const genie_cfg* cfg, int B, int ctx_max, int guided) {
-    if (check_cfg(cfg) != GENIE_OK || B < 1 || B > 0x3fffffff || ctx_max < 1 || ctx_max > cfg->T - 1) return 0;
-    const int NB = guided ? 2 * B : B;
-    const size_t off = carve_generate(*cfg, B, NB, ctx_max, nullptr, true).end;
-    const size_t full = guided ? carve_guided_prompt(*cfg, NB, nullptr).end : carve(*cfg, B, nullptr).total;
-    return off > full ? off : full;
-}
-
-int genie_rollout_cached(const genie_cfg* cfg, const genie_weights* wt, int64_t* frames, int B, int P, int keep, int cap, int f0, int f1,
-                         int resume, int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
-                         int merge_commit, float* cache, size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
-                         const genie_frame_cond* cond, const genie_sampling* sampling, const genie_guidance* guidance) {
-    GENIE_TRY(check_cfg(cfg));
-    const genie_cfg& c = *cfg;
-    const int T = c.T, S = c.S;
-    GENIE_CHECK_ARG(B >= 1 && steps >= 1, "rollout_cached: B=%d, steps %d", B, steps);
-    GENIE_CHECK_ARG(P >= 1 && P <= T - 1, "rollout_cached: %d prompt frames outside [1, %d]", P, T - 1);
-    GENIE_CHECK_ARG(keep >= 1 && keep <= T - 1, "rollout_cached: keep %d outside [1, %d]", keep, T - 1);
-    GENIE_CHECK_ARG(P <= f0 && f0 < f1 && f1 <= cap, "rollout_cached: frames [%d, %d) must lie in [%d prompt frames, cap %d]", f0, f1, P, cap);
-    GENIE_CHECK_ARG(resume == 0 || resume == 1, "rollout_cached: resume %d must be 0 or 1", resume);
-    GENIE_TRY(check_frame_cond(cond, "rollout_cached"));
-    GENIE_TRY(check_guidance(guidance, cond, "rollout_cached"));
-    GENIE_TRY(check_decode(steps, temperature, unmask_mode, noise, uniforms, sampling, "rollout_cached"));
-    GENIE_CHECK_ARG(wt && wt->layers_host && frames && cache, "rollout_cached: NULL pointer");
-    const bool by_conf = unmask_mode == GENIE_UNMASK_CONFIDENCE, guided = guidance && guidance->scale != 1.0f;
-    GENIE_CHECK_ARG(!guided || B <= 0x3fffffff, "rollout_cached: B=%d too large for guidance", B);
-    const int NB = guided ? 2 * B : B, copies = guided ? 2 : 1, hop = T - keep;
-    GENIE_CHECK_ARG(cache_bytes >= genie_prefix_cache_bytes(cfg, NB), "rollout_cached: cache too small");
-    GENIE_TRY(check_ws(c, NB, workspace, workspace_bytes));
-    // window of frame f: j = 0 below T, else 1 + (f - T) / hop; it starts at absolute frame j * hop and ends before j * hop + T
-    auto start_of = [&](int f) { return f < T ? 0 : (1 + (f - T) / hop) * hop; };
-    auto opens = [&](int f) { return f == P || (f >= T && f - start_of(f) == keep); };
-    const int start0 = start_of(f0);
-    const bool fresh0 = !resume || opens(f0);
-    // the largest context this call runs sizes its scratch: that of f0 unless resumed mid-window, `keep` for every later window
-    int ctx_need = fresh0 ? f0 - start0 : 1;
-    if (f1 > start0 + T && keep > ctx_need) ctx_need = keep;
-    GenLoop L = {cfg, wt, B, NB, copies, steps, unmask_mode, merge_commit, temperature, (by_conf && !sampling) ? &kDefaultSampling : sampling,
-                 guidance, guided, cond, cache, cache_bytes, workspace, workspace_bytes, stream,
-                 carve_generate(c, B, NB, ctx_need, (char*)workspace, true)};
-    GENIE_CHECK_ARG(L.g.end <= workspace_bytes, "rollout_cached: workspace too small (%zu < %zu bytes: size it with "
-                    "genie_rollout_workspace_bytes for a context of %d frames)", workspace_bytes, L.g.end, ctx_need);
-    hipStream_t st = as_stream(stream);
-    const bool acts = cond && cond->n_actions > 0;
-    genie_frame_cond cond2;
-    if (acts) {   // the passes read the window's actions, (NB, T) with the clip stride they expect
-        cond2 = *cond;
-        cond2.ids = L.g.acts;
-        L.cond = &cond2;
-    }
-    const long stride = (long)cap * S;
-    for (int f = f0; f < f1;) {
-        const int start = start_of(f), end = start + T < f1 ? start + T : f1;
-        const bool fresh = f != f0 || fresh0;   // the window's context is run from `frames`; else frame f - 1 is pending in the cache
-        const int ctx = fresh ? f - start : 0;
-        GENIE_TRY(put_rollout_window(frames, acts ? cond->ids : nullptr, L.g.idsP, acts ? L.g.acts : nullptr, B, copies, ctx, S, T, cap, start,
-                                     guided ? guidance->null_action : 0, st));
-        if (fresh) GENIE_TRY(run_context(L, ctx, frames + (size_t)start * S, stride));
-        GENIE_TRY(decode_slots(L, f - start, end - f, noise ? noise + (size_t)(f - f0) * (steps - 1) * B * S : nullptr,
-                               uniforms ? uniforms + (size_t)(f - f0) * steps * c.num_factored * B * S : nullptr, frames + (size_t)f * S,
-                               stride, nullptr, nullptr, 0, fresh ? nullptr : frames + (size_t)(f - 1) * S, stride));
-        f = end;
-    }
-    return GENIE_OK;
-}
-
-int genie_generate_cached_ex(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int P, int n_new,
-                             int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
-                             int teacher_force_time, int merge_commit, int64_t* gen_out, float* logits0_out, float* cache,
-                             size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
-                             const genie_frame_cond* cond, const genie_sampling* sampling) {
-    return generate_cached_loop(cfg, wt, ids, B, P, n_new, steps, temperature, unmask_mode, noise, uniforms, teacher_force_time, merge_commit,
-                                gen_out, logits0_out, cache, cache_bytes, workspace, workspace_bytes, stream, cond, sampling, nullptr);
-}
-
-int genie_generate_cached_guided(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int P, int n_new,
-                                 int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
-                                 int teacher_force_time, int merge_commit, int64_t* gen_out, float* logits0_out, float* cache,
-                                 size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
-                                 const genie_frame_cond* cond, const genie_sampling* sampling, const genie_guidance* guidance) {
-    return generate_cached_loop(cfg, wt, ids, B, P, n_new, steps, temperature, unmask_mode, noise, uniforms, teacher_force_time, merge_commit,
-                                gen_out, logits0_out, cache, cache_bytes, workspace, workspace_bytes, stream, cond, sampling, guidance);
-}
-
-// ---- fan-out generation: K futures per clip over one shared context cache ------------------------------------------------
-// The (NB, T) actions of the context pass and the (NB * K, T) actions of the decode passes from the caller's (B * K, T) ids, null halves
-// included: parent b reads its context actions from its branch 0 (row b * K; frames < P of the other branches are never read).
-__global__ void fanout_actions_kernel(const int64_t* __restrict__ ids, int64_t* __restrict__ ctx_out, int64_t* __restrict__ br_out, int B, int K,
-                                      int NB, int T, int P, int64_t null_action) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long nctx = (long)NB * T, BK = (long)B * K;
-    if (i < nctx) {
-        const long r = i / T, f = i - r * T;
-        ctx_out[i] = r >= B ? null_action : ids[r * K * T + f];
-        return;
-    }
-    const long a = i - nctx;
-    if (a >= nctx * K) return;
-    const long r = a / T, f = a - r * T;
-    br_out[a] = r >= BK ? null_action : ids[(f < P ? r / K * K : r) * T + f];
-}
-
-// NB * K as an int the passes can take, or 0
-static int fanout_clips(int B, int K, bool guided) {
-    if (B < 1 || K < 1) return 0;
-    const long n = (long)B * K * (guided ? 2 : 1);
-    return n <= 0x3fffffff ? (int)n : 0;
-}
-
-size_t genie_fanout_branch_bytes(const genie_cfg* cfg, int NB, int K, int n_new) {
-    if (check_cfg(cfg) != GENIE_OK || !fanout_clips(NB, K, false) || n_new < 1 || n_new > cfg->T - 1) return 0;
-    return fanout_branch_bytes(*cfg, (size_t)NB * K, n_new);
-}
-
-size_t genie_fanout_workspace_bytes(const genie_cfg* cfg, int B, int K, int P, int guided) {
-    if (check_cfg(cfg) != GENIE_OK || !fanout_clips(B, K, guided != 0) || P < 1 || P > cfg->T - 1) return 0;
-    const int NB = guided ? 2 * B : B;
-    const size_t off = carve_fanout(*cfg, B, NB, K, P, nullptr).end;
-    const size_t full = carve(*cfg, NB, nullptr).total;   // (the context passes check against the model's own workspace size)
-    return off > full ? off : full;
-}
-
-int genie_generate_fanout(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int K, int P, int n_new, int steps,
-                          float temperature, int unmask_mode, const float* noise, const float* uniforms, int merge_commit, int64_t* gen_out,
-                          float* trunk, size_t trunk_bytes, float* branch, size_t branch_bytes, void* workspace, size_t workspace_bytes,
-                          void* stream, const genie_frame_cond* cond, const genie_sampling* sampling, const genie_guidance* guidance) {
-    GENIE_TRY(check_cfg(cfg));
-    const genie_cfg& c = *cfg;
-    GENIE_TRY(check_frame_cond(cond, "generate_fanout"));
-    GENIE_TRY(check_guidance(guidance, cond, "generate_fanout"));
-    GENIE_CHECK_ARG(B >= 1 && K >= 1 && P >= 1 && n_new >= 1 && P + n_new <= c.T && steps >= 1,
-                    "generate_fanout: B=%d, K=%d, %d prompt + %d new frames of at most %d, steps %d", B, K, P, n_new, c.T, steps);
-    GENIE_TRY(check_decode(steps, temperature, unmask_mode, noise, uniforms, sampling, "generate_fanout"));
-    const bool by_conf = unmask_mode == GENIE_UNMASK_CONFIDENCE, guided = guidance && guidance->scale != 1.0f;
-    const int NBK = fanout_clips(B, K, guided);
-    GENIE_CHECK_ARG(NBK > 0, "generate_fanout: B=%d x K=%d%s clips per pass are too many", B, K, guided ? " x 2" : "");
-    const int NB = guided ? 2 * B : B, copies = guided ? 2 : 1, BK = B * K;
-    GENIE_CHECK_ARG(wt && wt->layers_host && ids && gen_out && trunk && branch && workspace, "generate_fanout: NULL pointer");
-    GENIE_CHECK_ARG(trunk_bytes >= genie_prefix_cache_bytes(cfg, NB), "generate_fanout: trunk cache too small (genie_prefix_cache_bytes of %d clips)", NB);
-    GENIE_CHECK_ARG(branch_bytes >= fanout_branch_bytes(c, (size_t)NBK, n_new), "generate_fanout: branch cache too small (genie_fanout_branch_bytes)");
-    const GenScratch g = carve_fanout(c, B, NB, K, P, (char*)workspace);
-    const size_t full = carve(c, NB, nullptr).total;
-    GENIE_CHECK_ARG(workspace_bytes >= g.end && workspace_bytes >= full, "generate_fanout: workspace too small (%zu < %zu bytes: size it with "
-                    "genie_fanout_workspace_bytes)", workspace_bytes, g.end > full ? g.end : full);
-    hipStream_t st = as_stream(stream);
-    const int S = c.S;
-    const genie_sampling* law = (by_conf && !sampling) ? &kDefaultSampling : sampling;
-    // the context of the NB clips runs once, into the trunk; its actions and the branches' come from one launch
-    genie_frame_cond cond_ctx, cond_br;
-    const bool acts = cond && cond->n_actions > 0;
-    if (acts) {
-        const long n = (long)NB * c.T * (1 + K);
-        fanout_actions_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(cond->ids, g.acts_ctx ? g.acts_ctx : g.acts, g.acts, B, K, NB, c.T, P,
-                                                                           guided ? guidance->null_action : 0);
-        GENIE_LAUNCH_CHECK("fanout_actions");
-        cond_ctx = cond_br = *cond;
-        cond_ctx.ids = g.acts_ctx ? g.acts_ctx : g.acts;   // (K == 1: one table serves both)
-        cond_br.ids = g.acts;
-    }
-    GenLoop Lc = {cfg, wt, B, NB, copies, steps, unmask_mode, merge_commit, temperature, law, guidance, guided, acts ? &cond_ctx : cond,
-                  trunk, trunk_bytes, workspace, workspace_bytes, stream, g};
-    GENIE_TRY(put_frame_ids(ids, (long)P * S, g.idsP, (long)P * S, P * S, B, 0, st, copies));
-    GENIE_TRY(run_context(Lc, P, ids, (long)P * S));
-    // ... then the loop of genie_generate_cached decodes B * K clips over the split cache, starting at slot P with nothing pending
-    const FanOut fan = {trunk, K, P, n_new};
-    const GenLoop Lb = {cfg, wt, BK, NBK, copies, steps, unmask_mode, merge_commit, temperature, law, guidance, guided, acts ? &cond_br : cond,
-                        branch, branch_bytes, workspace, workspace_bytes, stream, g, &fan};
-    return decode_slots(Lb, P, n_new, noise, uniforms, gen_out, (long)n_new * S, nullptr, nullptr, 0, nullptr, 0);
-}
-
-// ---- scoring observed futures: per-(clip, branch, frame) NLL over the fan-out cache ----------------------------------------
 int genie_score_logits(const genie_cfg* cfg, const float* logits, const int64_t* targets, int64_t target_clip_stride, int K, int64_t N,
                        double* nll, int64_t nll_stride, double* hits, float* token_nll, int64_t token_stride, void* stream) {
     GENIE_TRY(check_cfg(cfg));
@@ -1077,104 +563,6 @@ int genie_score_logits(const genie_cfg* cfg, const float* logits, const int64_t*
     GENIE_CHECK_ARG(((uintptr_t)logits & 15) == 0, "score_logits: logits must be 16-byte aligned");
     return launch_score_rows(*cfg, logits, targets, (long)target_clip_stride, K, (long)N, nll, (long)nll_stride, hits, token_nll,
                              (long)token_stride, as_stream(stream));
-}
-
-size_t genie_score_workspace_bytes(const genie_cfg* cfg, int B, int K, int P) { return genie_fanout_workspace_bytes(cfg, B, K, P, 0); }
-
-// rows of S token ids for the B * K clips of a fan-out pass from their B parents: dst[i][0..S) = src[i / K][0..S) (strides in elements)
-__global__ void branch_frame_ids_kernel(const int64_t* __restrict__ src, long src_stride, int64_t* __restrict__ dst, long dst_stride, int S,
-                                        long BK, int K) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= BK * S) return;
-    const long r = i / S, s = i - r * S;
-    dst[r * dst_stride + s] = src[(r / K) * src_stride + s];
-}
-
-// decode_slots' sibling for OBSERVED frames: per slot t0 + j the all-mask pass (riding the commit of slot t0 + j - 1 by decode_slots' own
-// rule), launch_score_rows on its logits against frame j of obs (parent clip i / K of row i, clip stride obs_stride), then the commit of
-// the observed tokens; the last slot is not committed.  nll / hits (L.B, n), token_nll (L.B, n, S).  No sample or mask-step launches,
-// no draws, no host synchronisation.
-static int score_slots(const GenLoop& L, int t0, int n, const int64_t* obs, long obs_stride, int K, double* nll, double* hits,
-                       float* token_nll) {
-    const genie_cfg& c = *L.cfg;
-    const int BK = L.B, S = c.S;
-    hipStream_t st = as_stream(L.stream);
-    int64_t *two = L.g.two, *cur = L.g.cur, *fin = L.g.fin;
-    float* logits = L.g.logits;
-    bool opened = false, merge = L.merge_commit != 0;
-    auto pass = [&](const int64_t* frame_ids, int t, int nf, float* lg) {
-        return frames_pass(L.cfg, L.wt, frame_ids, L.NB, t, nf, L.cache, L.cache_bytes, lg, L.workspace, L.workspace_bytes, L.stream, L.cond,
-                           L.fan);
-    };
-    auto put_observed = [&](const int64_t* src, int64_t* dst, long dst_stride) {
-        branch_frame_ids_kernel<<<(unsigned)(((long)BK * S + 255) / 256), 256, 0, st>>>(src, obs_stride, dst, dst_stride, S, (long)BK, K);
-        GENIE_LAUNCH_CHECK("branch_frame_ids");
-        return GENIE_OK;
-    };
-    for (int j = 0; j < n; ++j) {
-        const int t = t0 + j;
-        if (!opened) {
-            GENIE_TRY(put_frame_ids(nullptr, 0, cur, S, S, BK, c.image_vocab_size, st));
-            GENIE_TRY(pass(cur, t, 1, logits));
-        }
-        GENIE_TRY(launch_score_rows(c, logits, obs + (size_t)j * S, obs_stride, K, BK, nll + j, n, hits ? hits + j : nullptr,
-                                    token_nll ? token_nll + (size_t)j * S : nullptr, (long)n * S, st));
-        opened = false;
-        if (j + 1 == n) break;
-        if (merge) {   // commit slot t in the pass that also carries the all-mask slot t + 1
-            GENIE_TRY(put_observed(obs + (size_t)j * S, two, 2L * S));
-            GENIE_TRY(put_frame_ids(nullptr, 0, two + S, 2L * S, S, BK, c.image_vocab_size, st));
-            const int rc = pass(two, t, 2, logits);
-            if (rc == GENIE_E_UNSUPPORTED) merge = false;
-            else { GENIE_TRY(rc); opened = true; }
-        }
-        if (!opened) {
-            GENIE_TRY(put_observed(obs + (size_t)j * S, fin, S));
-            GENIE_TRY(pass(fin, t, 1, nullptr));
-        }
-    }
-    return GENIE_OK;
-}
-
-int genie_score_fanout(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int K, int P, int n, int merge_commit,
-                       double* nll, double* hits, float* token_nll, float* trunk, size_t trunk_bytes, float* branch, size_t branch_bytes,
-                       void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond) {
-    GENIE_TRY(check_cfg(cfg));
-    const genie_cfg& c = *cfg;
-    GENIE_TRY(check_frame_cond(cond, "score_fanout"));
-    GENIE_CHECK_ARG(B >= 1 && K >= 1 && P >= 1 && n >= 1 && P + n <= c.T, "score_fanout: B=%d, K=%d, %d prompt + %d scored frames of at most %d",
-                    B, K, P, n, c.T);
-    const int BK = fanout_clips(B, K, false);
-    GENIE_CHECK_ARG(BK > 0, "score_fanout: B=%d x K=%d clips per pass are too many", B, K);
-    GENIE_CHECK_ARG(wt && wt->layers_host && ids && nll && trunk && branch && workspace, "score_fanout: NULL pointer");
-    GENIE_CHECK_ARG(trunk_bytes >= genie_prefix_cache_bytes(cfg, B), "score_fanout: trunk cache too small (genie_prefix_cache_bytes of %d clips)", B);
-    GENIE_CHECK_ARG(branch_bytes >= fanout_branch_bytes(c, (size_t)BK, n), "score_fanout: branch cache too small (genie_fanout_branch_bytes)");
-    const GenScratch g = carve_fanout(c, B, B, K, P, (char*)workspace);
-    const size_t full = carve(c, B, nullptr).total;
-    GENIE_CHECK_ARG(workspace_bytes >= g.end && workspace_bytes >= full, "score_fanout: workspace too small (%zu < %zu bytes: size it with "
-                    "genie_score_workspace_bytes)", workspace_bytes, g.end > full ? g.end : full);
-    hipStream_t st = as_stream(stream);
-    const int S = c.S;
-    const long clip = (long)(P + n) * S;   // ids (B, P + n, S)
-    genie_frame_cond cond_ctx, cond_br;
-    const bool acts = cond && cond->n_actions > 0;
-    if (acts) {
-        const long na = (long)B * c.T * (1 + K);
-        fanout_actions_kernel<<<(unsigned)((na + 255) / 256), 256, 0, st>>>(cond->ids, g.acts_ctx ? g.acts_ctx : g.acts, g.acts, B, K, B, c.T, P, 0);
-        GENIE_LAUNCH_CHECK("fanout_actions");
-        cond_ctx = cond_br = *cond;
-        cond_ctx.ids = g.acts_ctx ? g.acts_ctx : g.acts;
-        cond_br.ids = g.acts;
-    }
-    // the context of the B clips runs once, into the trunk, as in genie_generate_fanout
-    GenLoop Lc = {cfg, wt, B, B, 1, 1, GENIE_UNMASK_GREEDY, merge_commit, 0.0f, nullptr, nullptr, false, acts ? &cond_ctx : cond,
-                  trunk, trunk_bytes, workspace, workspace_bytes, stream, g};
-    GENIE_TRY(put_frame_ids(ids, clip, g.idsP, (long)P * S, P * S, B, 0, st));
-    GENIE_TRY(run_context(Lc, P, ids, clip));
-    const FanOut fan = {trunk, K, P, n};
-    const GenLoop Lb = {cfg, wt, BK, BK, 1, 1, GENIE_UNMASK_GREEDY, merge_commit, 0.0f, nullptr, nullptr, false, acts ? &cond_br : cond,
-                        branch, branch_bytes, workspace, workspace_bytes, stream, g, &fan};
-    return score_slots(Lb, P, n, ids + (size_t)P * S, clip, K, nll, hits, token_nll);
 }
 
 int genie_temporal_attention_decode_fanout(const genie_cfg* cfg, const genie_attn_weights* aw, const float* trunk_slice,
@@ -1279,138 +667,6 @@ int genie_mask_step(const float* keys, int n, int last_step, int64_t mask_id, ui
     GENIE_CHECK_ARG(last_step || (n >= 0 && n <= S), "mask_step: n=%d out of range", n);
     return launch_mask_step(keys, n, last_step, mask_id, unmasked, samples, prompt_frame, (long)prompt_clip_stride, B,
                             S, as_stream(stream));
-}
-
-int genie_maskgit_generate(const genie_cfg* cfg, const genie_weights* wt, int64_t* prompt, int B, int out_t, int steps,
-                           float temperature, int unmask_mode, const float* noise, const float* uniforms,
-                           int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
-                           void* workspace, size_t workspace_bytes, void* stream) {
-    return genie_maskgit_generate_cond(cfg, wt, prompt, B, out_t, steps, temperature, unmask_mode, noise, uniforms, samples_out,
-                                       logits0_out, layout, status_flag, workspace, workspace_bytes, stream, nullptr);
-}
-
-int genie_maskgit_generate_cond(const genie_cfg* cfg, const genie_weights* wt, int64_t* prompt, int B, int out_t, int steps,
-                                float temperature, int unmask_mode, const float* noise, const float* uniforms,
-                                int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
-                                void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond) {
-    if (unmask_mode == GENIE_UNMASK_CONFIDENCE) unmask_mode = -1;   // (only genie_maskgit_generate_ex knows that mode)
-    return genie_maskgit_generate_ex(cfg, wt, prompt, B, out_t, steps, temperature, unmask_mode, noise, uniforms, samples_out,
-                                     logits0_out, layout, status_flag, workspace, workspace_bytes, stream, cond, nullptr);
-}
-
-// genie_maskgit_generate_ex (guidance NULL or of scale 1) and genie_maskgit_generate_guided: one loop, B clips decoded, NB per forward
-static int maskgit_generate_loop(const genie_cfg* cfg, const genie_weights* wt, int64_t* prompt, int B, int out_t, int steps,
-                                 float temperature, int unmask_mode, const float* noise, const float* uniforms,
-                                 int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
-                                 void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond,
-                                 const genie_sampling* sampling, const genie_guidance* guidance) {
-    GENIE_TRY(check_cfg(cfg));
-    const genie_cfg& c = *cfg;
-    GENIE_CHECK_ARG(wt && wt->layers_host && prompt && samples_out, "maskgit_generate: NULL pointer");
-    GENIE_TRY(check_frame_cond(cond, "maskgit_generate"));
-    GENIE_TRY(check_guidance(guidance, cond, "maskgit_generate"));
-    if (!(out_t >= 1 && out_t < c.T)) {  // assert out_t  (st_mask_git.py:154)
-        set_error("maskgit_generate requires 0 < out_t < T (got %d)", out_t);
-        return GENIE_E_ASSERT;
-    }
-    GENIE_CHECK_ARG(steps >= 1, "maskgit_generate: steps=%d must be >= 1", steps);
-    GENIE_TRY(check_sampling(sampling, "maskgit_generate"));
-    GENIE_TRY(check_unmask(unmask_mode, unmask_mode != -1, steps, noise, "maskgit_generate"));
-    GENIE_CHECK_ARG(temperature <= 1e-8f || uniforms, "maskgit_generate: temperature > 0 needs uniforms");
-    const bool by_conf = unmask_mode == GENIE_UNMASK_CONFIDENCE;
-    const genie_sampling* law = (by_conf && !sampling) ? &kDefaultSampling : sampling;
-    // under guidance every forward runs 2 B clips, [conditional ; null], on a doubled copy of the prompt behind the workspace
-    const bool guided = guidance && guidance->scale != 1.0f;
-    GENIE_CHECK_ARG(!guided || B <= 0x3fffffff, "maskgit_generate: B=%d too large for guidance", B);
-    const int NB = guided ? 2 * B : B;
-    GENIE_TRY(check_ws(c, NB, workspace, workspace_bytes));
-    Workspace w = carve(c, NB, workspace);
-    hipStream_t st = as_stream(stream);
-    const size_t BS = (size_t)B * c.S;
-    const long V = (long)c.factored_vocab * c.num_factored;
-    const long clip = (long)c.T * c.S;
-    const int64_t* tokens = prompt;   // what every forward embeds
-    genie_frame_cond cond2;
-    if (guided) {
-        const GuidedPrompt gp = carve_guided_prompt(c, NB, (char*)workspace);
-        GENIE_CHECK_ARG(gp.end <= workspace_bytes, "maskgit_generate: workspace too small (%zu < %zu bytes: size it with "
-                        "genie_generate_guided_workspace_bytes)", workspace_bytes, gp.end);
-        GENIE_TRY(put_guided_actions(*cond, *guidance, B, c.T, gp.acts, st));
-        cond2 = *cond;
-        cond2.ids = gp.acts;
-        cond = &cond2;
-        GENIE_TRY(put_frame_ids(prompt, clip, gp.prompt2, clip, (int)clip, B, 0, st, 2));
-        tokens = gp.prompt2;
-    }
-    // guided: the null half of the frame's logits, and room behind both halves for the guided step-0 logits (w.logits holds T >= 2 frames)
-    const float* logits_null = w.logits + BS * V;
-    float* logits_g = w.logits + 2 * BS * V;
-
-    GENIE_TRY(launch_check_masked(prompt, B, c.T, c.S, out_t, c.image_vocab_size, status_flag, st));
-    if (hipMemsetAsync(w.unmasked, 0, BS, st) != hipSuccess) { set_error("memset failed"); return GENIE_E_LAUNCH; }
-    EmbedAct act;
-    const EmbedAct* pact = frame_act(cond, c.S, 0, c.T, act);
-    for (int step = 0; step < steps; ++step) {
-        GENIE_TRY(launch_embed(c, *wt, tokens, NB, w.x, st, pact));
-        GENIE_TRY(decoder(c, *wt, w.x, w, NB, st));
-        GENIE_TRY(readout(c, *wt, w.x, w, NB, out_t, out_t + 1, GENIE_LAYOUT_TOKEN_MAJOR, w.logits, st));
-        if (step == 0 && logits0_out) {  // orig_logits_CHW: step-0 logits are what is returned (:165,226); the guided ones under guidance
-            const bool tm = layout == GENIE_LAYOUT_TOKEN_MAJOR;
-            if (guided) GENIE_TRY(launch_guide_logits(w.logits, logits_null, tm ? logits0_out : logits_g, 1, (long)(BS * V), 0, 0, guidance->scale, st));
-            if (tm) {
-                if (!guided && hipMemcpyAsync(logits0_out, w.logits, BS * V * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-                    set_error("memcpy failed");
-                    return GENIE_E_LAUNCH;
-                }
-            } else {
-                GENIE_TRY(launch_transpose(guided ? logits_g : w.logits, logits0_out, B, c.S, (int)V, st));
-            }
-        }
-        const float* u = (temperature > 1e-8f) ? uniforms + (size_t)step * c.num_factored * BS : nullptr;
-        const int last = (step == steps - 1);
-        const float* draws = (last || unmask_mode == GENIE_UNMASK_GREEDY) ? nullptr : noise + (size_t)step * BS;
-        // "confidence": the sample launch writes the keys over conf (nothing else reads conf in this loop)
-        const float anneal = 1.0f - (float)(step + 1) / (float)steps;
-        if (guided)
-            GENIE_TRY(launch_sample_guided(c, w.logits, logits_null, GENIE_LAYOUT_TOKEN_MAJOR, B, temperature, u, w.samples, w.conf, law,
-                                           (by_conf && !last) ? w.conf : nullptr, draws, anneal, guidance->scale, st));
-        else
-            GENIE_TRY(launch_sample_ex(c, w.logits, GENIE_LAYOUT_TOKEN_MAJOR, B, temperature, u, w.samples, w.conf, law,
-                                       (by_conf && !last) ? w.conf : nullptr, draws, anneal, st));
-        const float* keys = nullptr;
-        int n = 0;
-        if (!last) {
-            n = mask_count(step, steps, c.S);
-            keys = (unmask_mode == GENIE_UNMASK_RANDOM) ? draws : w.conf;
-        }
-        GENIE_TRY(launch_mask_step(keys, n, last, c.image_vocab_size, w.unmasked, w.samples,
-                                   prompt + (size_t)out_t * c.S, clip, B, c.S, st));
-        if (guided && !last)   // both halves of the next forward see the frame's current tokens
-            GENIE_TRY(put_frame_ids(prompt + (size_t)out_t * c.S, clip, const_cast<int64_t*>(tokens) + (size_t)out_t * c.S, clip, c.S, B, 0, st, 2));
-    }
-    if (hipMemcpyAsync(samples_out, w.samples, BS * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        set_error("memcpy failed");
-        return GENIE_E_LAUNCH;
-    }
-    return GENIE_OK;
-}
-
-int genie_maskgit_generate_ex(const genie_cfg* cfg, const genie_weights* wt, int64_t* prompt, int B, int out_t, int steps,
-                              float temperature, int unmask_mode, const float* noise, const float* uniforms,
-                              int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
-                              void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond,
-                              const genie_sampling* sampling) {
-    return maskgit_generate_loop(cfg, wt, prompt, B, out_t, steps, temperature, unmask_mode, noise, uniforms, samples_out, logits0_out, layout,
-                                 status_flag, workspace, workspace_bytes, stream, cond, sampling, nullptr);
-}
-
-int genie_maskgit_generate_guided(const genie_cfg* cfg, const genie_weights* wt, int64_t* prompt, int B, int out_t, int steps,
-                                  float temperature, int unmask_mode, const float* noise, const float* uniforms,
-                                  int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
-                                  void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond,
-                                  const genie_sampling* sampling, const genie_guidance* guidance) {
-    return maskgit_generate_loop(cfg, wt, prompt, B, out_t, steps, temperature, unmask_mode, noise, uniforms, samples_out, logits0_out, layout,
-                                 status_flag, workspace, workspace_bytes, stream, cond, sampling, guidance);
 }
 
 int genie_profile_enable(int class_mask) {

@@ -1,5 +1,5 @@
 // Host-side launchers of the gfx950 kernels (one block of declarations per kernels_*.hip file) and the pass / workspace types of the
-// layer drivers (st_block.hip, kernels_frame.hip), which api.hip's entry points and loops call.
+// layer drivers (st_block.hip, kernels_frame.hip), which api.hip's entry points and the loops of generate_api.hip call.
 #pragma once
 #include "common.hpp"
 
@@ -419,5 +419,31 @@ int temporal_attention(const genie_cfg& c, const genie_attn_weights& aw, const B
 
 int launch_adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
                  float weight_decay, int step, float grad_mult, const double* sumsq, float max_norm, hipStream_t st);
+
+// api.hip: the host helpers its entry points share with the generate loops (generate_api.hip)
+Workspace carve(const genie_cfg& c, int B, void* base);   // base == NULL: sizes only
+int check_cfg(const genie_cfg* c);
+int check_ws(const genie_cfg& c, int B, void* ws, size_t bytes);
+int decoder(const genie_cfg& c, const genie_weights& wt, float* x, Workspace& w, int B, hipStream_t st);
+int mask_count(int step, int steps, int S);
+// what a caller's decode options must satisfy, checked on the host before anything is enqueued (NULL = none; where: the entry point)
+int check_sampling(const genie_sampling* sp, const char* where);
+int check_unmask(int unmask_mode, bool ex, int steps, const float* noise, const char* where);
+int check_guidance(const genie_guidance* g, const genie_frame_cond* cond, const char* where);
+extern const genie_sampling kDefaultSampling;
+// The split cache of a fan-out call (genie_generate_fanout): the B clips of a decode pass are K branches each of B / K parent clips.
+// Slots [0, P0) live in `trunk`, a T-slot cache of B / K clips that the context pass filled and no decode pass writes; slot j >= P0 is
+// slot j - P0 of the pass's own cache, (L, B, Tb, S, 3d).
+struct FanOut {
+    const float* trunk;
+    int K, P0, Tb;
+};
+inline size_t fanout_branch_bytes(const genie_cfg& c, size_t NBK, int Tb) {
+    return (size_t)c.num_layers * NBK * Tb * c.S * 3 * c.d_model * sizeof(float);
+}
+// genie_frames_pass_cond, and with fan != NULL the decode pass of a fan-out call
+int frames_pass(const genie_cfg* cfg, const genie_weights* wt, const int64_t* frame_ids, int B, int t0, int nf, float* cache,
+                size_t cache_bytes, float* logits, void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond,
+                const FanOut* fan);
 
 }  // namespace genie

@@ -142,6 +142,122 @@ def test_training_buffer_sizes_are_unchanged():
             assert got == want, (name, prec, got, want)
 
 
+def loop_workspace_sizes(L, c, T):
+    """The size functions of the generate loops on the grid B x P (x guided) (x K), in one fixed order:
+    [generate, generate_guided, rollout, fanout, fanout_branch]"""
+    Bs, Ks, Ps = (1, 3, 16), (1, 3, 64), (1, T // 2, T - 1)
+    return [[L.genie_generate_workspace_bytes(c, B, P) for B in Bs for P in Ps],
+            [L.genie_generate_guided_workspace_bytes(c, B, P) for B in Bs for P in Ps],
+            [L.genie_rollout_workspace_bytes(c, B, P, g) for g in (0, 1) for B in Bs for P in Ps],
+            [L.genie_fanout_workspace_bytes(c, B, K, P, g) for g in (0, 1) for B in Bs for K in Ks for P in Ps],
+            [L.genie_fanout_branch_bytes(c, B, K, P) for B in Bs for K in Ks for P in Ps]]
+
+
+# loop_workspace_sizes of four configs, the same in exact, bf16 and f16x3.  Read from the library of the commit before the generate loops
+# moved into a driver file of their own (one Decode, one PassCtx, one MaskGIT step, one commit rule): what a caller allocates stays.
+LOOP_WORKSPACE_BYTES = {
+    "d64": [
+        [377600, 377600, 377600, 1131520, 1131520, 1131520, 6032640, 6032640, 6032640],
+        [755712, 755712, 755712, 2265856, 2265856, 2265856, 12082688, 12082688, 12082688],
+        [377600, 377600, 377600, 1131520, 1131520, 1131520, 6032640, 6032640, 6032640, 755712, 755712, 755712, 2265856, 2265856,
+         2265856, 12082688, 12082688, 12082688],
+        [377600, 377600, 377600, 766464, 766464, 766720, 16314880, 16314880, 16315136, 1131520, 1131520, 1131520, 2296320, 2296576,
+         2297088, 48943872, 48944128, 48944640, 6032640, 6032640, 6032640, 12238336, 12240384, 12242432, 261032448, 261034496,
+         261036544, 754432, 754432, 754432, 1530112, 1530368, 1530624, 32615936, 32616192, 32616448, 2262528, 2262528, 2262528,
+         4588544, 4589312, 4590080, 97847296, 97848064, 97848832, 12065280, 12065280, 12065280, 24466688, 24470784, 24474880,
+         521851904, 521856000, 521860096],
+        [24576, 49152, 73728, 73728, 147456, 221184, 1572864, 3145728, 4718592, 73728, 147456, 221184, 221184, 442368, 663552,
+         4718592, 9437184, 14155776, 393216, 786432, 1179648, 1179648, 2359296, 3538944, 25165824, 50331648, 75497472],
+    ],
+    "d256": [
+        [46140672, 46140672, 46140672, 138422016, 138422016, 138422016, 738250752, 738250752, 738250752],
+        [92347136, 92347136, 92347136, 277041408, 277041408, 277041408, 1477554176, 1477554176, 1477554176],
+        [46140672, 46140672, 46140672, 138422016, 138422016, 138422016, 738250752, 738250752, 738250752, 92347136, 92347136,
+         92347136, 277041408, 277041408, 277041408, 1477554176, 1477554176, 1477554176],
+        [46140672, 46140672, 46140672, 46140672, 46140672, 46468864, 437168384, 437182720, 437197056, 138422016, 138422016,
+         138422016, 138422016, 138422016, 139406080, 1311504896, 1311547904, 1311590912, 738250752, 738250752, 738250752,
+         738250752, 738250752, 743497728, 6994692096, 6994921472, 6995150848, 92281344, 92281344, 92281344, 92281344, 92281344,
+         92927232, 874123520, 874152192, 874180864, 276844032, 276844032, 276844032, 276844032, 276844032, 278781696, 2622370560,
+         2622456576, 2622542592, 1476501504, 1476501504, 1476501504, 1476501504, 1476501504, 1486835712, 13985976320, 13986435072,
+         13986893824],
+        [1572864, 12582912, 23592960, 4718592, 37748736, 70778880, 100663296, 805306368, 1509949440, 4718592, 37748736, 70778880,
+         14155776, 113246208, 212336640, 301989888, 2415919104, 4529848320, 25165824, 201326592, 377487360, 75497472, 603979776,
+         1132462080, 1610612736, 12884901888, 24159191040],
+    ],
+    "d512": [
+        [75500800, 75500800, 75500800, 226502400, 226502400, 226502400, 1208012800, 1208012800, 1208012800],
+        [151067392, 151067392, 151067392, 453202176, 453202176, 453202176, 2417078272, 2417078272, 2417078272],
+        [75500800, 75500800, 75500800, 226502400, 226502400, 226502400, 1208012800, 1208012800, 1208012800, 151067392, 151067392,
+         151067392, 453202176, 453202176, 453202176, 2417078272, 2417078272, 2417078272],
+        [75500800, 75500800, 75500800, 75500800, 75500800, 75500800, 672049408, 672063744, 672078080, 226502400, 226502400,
+         226502400, 226502400, 226502400, 226502400, 2016147968, 2016190976, 2016233984, 1208012800, 1208012800, 1208012800,
+         1208012800, 1208012800, 1208012800, 10752788480, 10753017856, 10753247232, 151001600, 151001600, 151001600, 151001600,
+         151001600, 151001600, 1343885568, 1343914240, 1343942912, 453004800, 453004800, 453004800, 453004800, 453004800,
+         453004800, 4031656704, 4031742720, 4031828736, 2416025600, 2416025600, 2416025600, 2416025600, 2416025600, 2416025600,
+         21502169088, 21502627840, 21503086592],
+        [3145728, 25165824, 47185920, 9437184, 75497472, 141557760, 201326592, 1610612736, 3019898880, 9437184, 75497472,
+         141557760, 28311552, 226492416, 424673280, 603979776, 4831838208, 9059696640, 50331648, 402653184, 754974720, 150994944,
+         1207959552, 2264924160, 3221225472, 25769803776, 48318382080],
+    ],
+    "v3x64": [
+        [164608, 164608, 164608, 492544, 492544, 492544, 2624768, 2624768, 2624768],
+        [329728, 329728, 329728, 987904, 987904, 987904, 5266944, 5266944, 5266944],
+        [164608, 164608, 164608, 492544, 492544, 492544, 2624768, 2624768, 2624768, 329728, 329728, 329728, 987904, 987904, 987904,
+         5266944, 5266944, 5266944],
+        [164608, 164608, 164608, 287232, 287232, 287488, 6091264, 6091264, 6091520, 492544, 492544, 492544, 858624, 858880, 859392,
+         18273024, 18273280, 18273792, 2624768, 2624768, 2624768, 4570624, 4572672, 4574720, 97454592, 97456640, 97458688, 328448,
+         328448, 328448, 571648, 571904, 572160, 12168704, 12168960, 12169216, 984576, 984576, 984576, 1713152, 1713920, 1714688,
+         36505600, 36506368, 36507136, 5249536, 5249536, 5249536, 9131264, 9135360, 9139456, 194696192, 194700288, 194704384],
+        [24576, 49152, 73728, 73728, 147456, 221184, 1572864, 3145728, 4718592, 73728, 147456, 221184, 221184, 442368, 663552,
+         4718592, 9437184, 14155776, 393216, 786432, 1179648, 1179648, 2359296, 3538944, 25165824, 50331648, 75497472],
+    ],
+}
+
+
+def test_loop_workspace_sizes_are_unchanged():
+    lib_mod = pkg("_lib")
+    L = lib_mod.load()
+    C = pkg("config")
+
+    def model(H, d, T, S, **kw):
+        return C.GenieConfig(num_layers=2, num_heads=H, d_model=d, T=T, S=S, qk_norm=False, use_mup=False, **kw)
+    cases = {"d64": model(2, 64, 4, 16, num_factored_vocabs=2), "d256": model(8, 256, 16, 256, num_factored_vocabs=2),
+             "d512": model(8, 512, 16, 256, num_factored_vocabs=2),
+             "v3x64": model(2, 64, 4, 16, image_vocab_size=64 ** 3, num_factored_vocabs=3)}
+    assert sorted(cases) == sorted(LOOP_WORKSPACE_BYTES)
+    names = ["generate", "generate_guided", "rollout", "fanout", "fanout_branch"]
+    for name, cfg in cases.items():
+        T = cfg.T
+        for prec in (lib_mod.PREC_EXACT, lib_mod.PREC_BF16, lib_mod.PREC_F16X3):
+            c = lib_mod.make_cfg(cfg, prec)
+            for fn, got, want in zip(names, loop_workspace_sizes(L, c, T), LOOP_WORKSPACE_BYTES[name]):
+                assert got == want, (name, prec, fn, got, want)
+            # scoring allocates what an unguided fan-out call does
+            for B, K, P in [(1, 1, 1), (3, 3, T // 2), (16, 64, T - 1), (1, 64, T - 1)]:
+                assert L.genie_score_workspace_bytes(c, B, K, P) == L.genie_fanout_workspace_bytes(c, B, K, P, 0) > 0
+            # ... and every size function answers a bad argument with 0
+            big = 0x40000000   # clips no guided pass (2 B) or fan-out pass (B * K) can count
+            zero = [L.genie_generate_workspace_bytes(None, 1, 1), L.genie_generate_workspace_bytes(c, 0, 1),
+                    L.genie_generate_workspace_bytes(c, 1, 0), L.genie_generate_workspace_bytes(c, 1, T + 1),
+                    L.genie_generate_guided_workspace_bytes(None, 1, 1), L.genie_generate_guided_workspace_bytes(c, 0, 1),
+                    L.genie_generate_guided_workspace_bytes(c, big, 1), L.genie_generate_guided_workspace_bytes(c, 1, 0),
+                    L.genie_generate_guided_workspace_bytes(c, 1, T + 1),
+                    L.genie_rollout_workspace_bytes(None, 1, 1, 0), L.genie_rollout_workspace_bytes(c, 0, 1, 0),
+                    L.genie_rollout_workspace_bytes(c, big, 1, 1), L.genie_rollout_workspace_bytes(c, 1, 0, 0),
+                    L.genie_rollout_workspace_bytes(c, 1, T, 1),
+                    L.genie_fanout_workspace_bytes(None, 1, 1, 1, 0), L.genie_fanout_workspace_bytes(c, 0, 1, 1, 0),
+                    L.genie_fanout_workspace_bytes(c, 1, 0, 1, 0), L.genie_fanout_workspace_bytes(c, big // 2, 2, 1, 0),
+                    L.genie_fanout_workspace_bytes(c, big // 4, 2, 1, 1), L.genie_fanout_workspace_bytes(c, 1, 1, 0, 0),
+                    L.genie_fanout_workspace_bytes(c, 1, 1, T, 1),
+                    L.genie_score_workspace_bytes(None, 1, 1, 1), L.genie_score_workspace_bytes(c, 0, 1, 1),
+                    L.genie_score_workspace_bytes(c, 1, 0, 1), L.genie_score_workspace_bytes(c, big // 2, 2, 1),
+                    L.genie_score_workspace_bytes(c, 1, 1, 0), L.genie_score_workspace_bytes(c, 1, 1, T),
+                    L.genie_fanout_branch_bytes(None, 1, 1, 1), L.genie_fanout_branch_bytes(c, 0, 1, 1),
+                    L.genie_fanout_branch_bytes(c, 1, 0, 1), L.genie_fanout_branch_bytes(c, big // 2, 2, 1),
+                    L.genie_fanout_branch_bytes(c, 1, 1, 0), L.genie_fanout_branch_bytes(c, 1, 1, T)]
+            assert zero == [0] * len(zero), (name, prec, zero)
+
+
 def test_config_roundtrip_and_derived(tmp_path):
     C = pkg("config")
     c = C.c35()

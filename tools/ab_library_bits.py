@@ -24,7 +24,18 @@ The training battery (--battery train; the default runs both, each in its own pa
 forward_backward, a second one with accumulate=True, one optimizer_step.  Recorded: the loss sums and every gradient tensor after each
 call, the flat parameters after the step, genie_train_activation_bytes / genie_train_workspace_bytes, and the kernel tables around the
 whole case (the trainer's weight packing included).  TRAIN_CASES are geometries tests/test_hip_train*.py pin, in all three precisions;
-s144 (T*S = 288) is refused by the 16-bit step and counts through its return code."""
+s144 (T*S = 288) is refused by the 16-bit step and counts through its return code.
+
+The loops battery (--battery loops): the generate loops of csrc/generate_api.hip, called through ctypes on LOOP_MODELS.  Per model and
+clip count: genie_maskgit_generate_ex / _guided (3 steps; random, greedy and confidence unmasking at temperature 0 and under a
+(0.7, 50, 0.9) law; the step-0 logits in both layouts; guidance of scale 3 and of scale 1), genie_generate_cached_ex / _guided (merged and
+unmerged commits, teacher forcing in time, step-0 logits, a law, actions), genie_rollout_cached over three windows (in one call, and split
+in mid-window with resume = 1; plain, with actions, guided), genie_generate_fanout (K = 1 and 3; P = 1, T / 2 and T - 1; per-branch
+actions; guided) and genie_score_fanout (K = 1 and 3; merged and unmerged; with and without hits / token_nll / actions); then the calls
+each entry point refuses (NULL pointer, frames past T, a workspace or cache one byte short, temperature > 0 without uniforms, guidance
+without actions, ...).  Every output tensor starts sentinel-filled and every cache zeroed, and all are digested whether the call was
+refused or not: a refused call must leave them as they were.  Before a record is kept, float outputs are checked finite and generated
+tokens checked not to be one id."""
 import argparse
 import ctypes
 import hashlib
@@ -71,6 +82,13 @@ TRAIN_CASES = [("d64", 2, 64, 4, 16, 1, False, 2, 0),         # transposed-copy 
                ("s144", 1, 64, 2, 144, 1, False, 2, 0),       # exact only: the 16-bit step refuses T*S = 288
                ("d64act", 2, 64, 4, 16, 1, False, 2, 5)]      # the _cond forward and the embed backward with a table gradient
 TRAIN_WATCHED = ["gemm_f32_gen_kernel", "attn_spatial_bwd_fused_kernel", "wgrad16_tn_kernel", "attn_bwd16_"]
+# loops battery: (name, d_model, heads, T, S, precisions, clip counts), a LayerNorm and a qk-norm model each.  d64: the generic kernels --
+# every merged commit is refused and the loops fall back, the context runs frame by frame; d256 / d512 in f16x3: the fragment-order
+# passes with merged commits and the multi-frame context pass; 9 clips of 8 context frames are past its 16,384-row cut (the clean pass runs)
+LOOP_MODELS = [("d64", 64, 2, 4, 16, PRECISIONS, (3,)),
+               ("d256", 256, 8, 16, 256, ["f16x3"], (1, 2)),
+               ("d512", 512, 8, 16, 256, ["f16x3"], (1, 2, 9))]
+LOOPS_WATCHED = ["gemm16_fr(m)_kernel (readout)"]   # the fragment-order passes: without them no merged commit and no multi-frame context
 
 
 def child(out_path, battery):
@@ -95,8 +113,9 @@ def child(out_path, battery):
         a = t.detach().contiguous().cpu().numpy()
         return [str(a.dtype), list(a.shape), hashlib.sha256(a.tobytes()).hexdigest()]
 
-    def record_case(name, fn):
-        """fn() -> (rc, {tensor name: tensor}); the launches of all classes between reset and read are the case's table"""
+    def record_case(name, fn, keep_refused=False):
+        """fn() -> (rc, {tensor name: tensor}); the launches of all classes between reset and read are the case's table.  keep_refused:
+        the outputs of a refused call are digested too (sentinel-filled by the case: a refused call must not have touched them)"""
         _lib.check(lib.genie_profile_enable((1 << N_CLASSES) - 1), "profile_enable")
         lib.genie_profile_reset()
         try:
@@ -111,7 +130,7 @@ def child(out_path, battery):
             for ln in buf.value.decode().splitlines():
                 table[f"{kc}:{ln.split(chr(9))[0]}"] = int(float(ln.split("\t")[1]))
         lib.genie_profile_enable(0)
-        record[name] = {"rc": rc, "outs": {k: digest(v) for k, v in outs.items()} if rc == 0 else {}, "kernels": table}
+        record[name] = {"rc": rc, "outs": {k: digest(v) for k, v in outs.items()} if rc == 0 or keep_refused else {}, "kernels": table}
         print(name, "rc", rc, "launches", sum(table.values()), flush=True)
 
     if battery == "train":
@@ -144,6 +163,252 @@ def child(out_path, battery):
                 record[f"{name}/{prec}"]["sizes"] = list(sizes)
                 print(f"{name}/{prec} activation / workspace bytes {sizes}", flush=True)
                 torch.cuda.empty_cache()
+        with open(out_path, "w") as f:
+            json.dump(record, f)
+        return
+
+    def loop_cases(tag, m, B):
+        """Every loop entry point of csrc/generate_api.hip on one model (action_vocab_size 5; cond = None runs it unconditioned), called
+        through ctypes on buffers of this function's own: every output starts sentinel-filled, every cache zeroed"""
+        cfg = m.config
+        T, S, nv = cfg.T, cfg.S, cfg.num_factored_vocabs
+        V = cfg.factored_vocab_size * nv
+        c, w = m._weights()[:2]
+        st = torch.cuda.current_stream().cuda_stream
+        clip = torch.from_numpy(synth.make_clips(B, cfg, seed=7)).cuda().view(B, T, S)
+        table = m.action_embed.weight
+        law = _lib.Sampling(0.7, 50, 0.9, 4.5)
+        RANDOM, GREEDY, CONF = _lib.UNMASK_RANDOM, _lib.UNMASK_GREEDY, _lib.UNMASK_CONFIDENCE
+        ws = torch.zeros(max([lib.genie_generate_guided_workspace_bytes(c, B, P) for P in (1, T // 2, T - 1)]
+                             + [lib.genie_rollout_workspace_bytes(c, B, T - 1, 1)]
+                             + [lib.genie_fanout_workspace_bytes(c, B, 3, P, 1) for P in (1, T // 2, T - 1)]), dtype=torch.uint8, device="cuda")
+
+        def rand(seed, *shape):
+            return torch.rand(*shape, generator=torch.Generator().manual_seed(seed)).cuda()
+
+        def sent(dtype, *shape):
+            return torch.full(shape, -7 if dtype == torch.int64 else 12345.0, dtype=dtype, device="cuda")
+
+        def ptr(t):
+            return 0 if t is None else t.data_ptr()
+
+        def acts(seed, rows, cols):
+            a = torch.from_numpy(np.random.default_rng(seed).integers(1, 5, (rows, cols))).cuda()
+            fc = _lib.FrameCond(table=table.data_ptr(), ids=a.data_ptr(), n_actions=5)
+            fc.keep = a
+            return fc
+
+        def guide(scale):
+            return _lib.Guidance(scale, 0)
+
+        def draws(temperature, steps, n, rows, seed=3):
+            """(noise (n, steps - 1, rows, S), uniforms (n, steps, nv, rows, S) or None at temperature 0)"""
+            return rand(seed, n, max(steps - 1, 1), rows, S), rand(seed + 1, n, steps, nv, rows, S) if temperature > 0 else None
+
+        def case(name, fn, tokens=()):
+            def checked():
+                rc, outs = fn()
+                if rc == 0:
+                    torch.cuda.synchronize()
+                    for k, v in outs.items():   # (equal digests of NaNs, or of a constant frame, would compare nothing)
+                        assert not v.is_floating_point() or bool(torch.isfinite(v).all()), (tag, name, k)
+                    for k in tokens:
+                        assert int(outs[k].min()) != int(outs[k].max()), (tag, name, k, "every generated token is one id")
+                return rc, outs
+            record_case(f"{tag}/{name}", checked, keep_refused=True)
+
+        # ---- genie_maskgit_generate_ex / _guided: (cond, sampling, guidance, then the keyword edits of a refused call)
+        def maskgit(mode=RANDOM, temperature=0.0, sampling=None, guidance=None, cond=None, layout=_lib.LAYOUT_TOKEN_MAJOR, steps=3,
+                    out_t=T // 2, want_logits=True, null_prompt=False, short=0, no_uniforms=False):
+            def fn():
+                prompt = clip.clone()
+                prompt[:, out_t if 0 < out_t < T else 1:] = cfg.image_vocab_size
+                nz, uni = draws(temperature, steps, 1, B)
+                samples, flag = sent(torch.int64, B, S), torch.zeros(1, dtype=torch.int32, device="cuda")
+                lg = sent(torch.float32, B * S * V) if want_logits else None
+                guided = guidance is not None
+                need = lib.genie_generate_guided_workspace_bytes(c, B, 1) if guided else lib.genie_workspace_bytes(c, B)
+                args = [c, w, 0 if null_prompt else prompt.data_ptr(), B, out_t, steps, temperature, mode, ptr(nz), 0 if no_uniforms else ptr(uni),
+                        samples.data_ptr(), ptr(lg), layout, flag.data_ptr(), ws.data_ptr(), need - short, st, cond, sampling]
+                rc = lib.genie_maskgit_generate_guided(*args, guidance) if guided else lib.genie_maskgit_generate_ex(*args)
+                outs = {"tokens": samples, "prompt": prompt, "status": flag}
+                if want_logits:
+                    outs["logits0"] = lg
+                return rc, outs
+            return fn
+        for mode, mname in ((RANDOM, "random"), (GREEDY, "greedy"), (CONF, "confidence")):
+            case(f"maskgit/{mname}/t0", maskgit(mode, layout=_lib.LAYOUT_TOKEN_MAJOR), tokens=("tokens",))
+            case(f"maskgit/{mname}/law", maskgit(mode, 1.0, law, layout=_lib.LAYOUT_BCTHW), tokens=("tokens",))
+        case("maskgit/conf_default_law", maskgit(CONF, 1.0, None, want_logits=False), tokens=("tokens",))
+        case("maskgit/actions", maskgit(cond=acts(11, B, T)), tokens=("tokens",))
+        case("maskgit/guided3", maskgit(CONF, 1.0, law, guide(3.0), acts(11, B, T)), tokens=("tokens",))
+        case("maskgit/guided3/bcthw", maskgit(RANDOM, 0.0, None, guide(3.0), acts(11, B, T), layout=_lib.LAYOUT_BCTHW), tokens=("tokens",))
+        case("maskgit/guided1", maskgit(RANDOM, 0.0, None, guide(1.0), acts(11, B, T)), tokens=("tokens",))
+        case("maskgit/refused/null", maskgit(null_prompt=True))
+        case("maskgit/refused/out_t", maskgit(out_t=T))
+        case("maskgit/refused/out_t_and_guidance", maskgit(out_t=0, guidance=guide(3.0)))
+        case("maskgit/refused/steps", maskgit(steps=0))
+        case("maskgit/refused/mode", maskgit(mode=7))
+        case("maskgit/refused/workspace", maskgit(short=1))
+        case("maskgit/refused/workspace_guided", maskgit(guidance=guide(3.0), cond=acts(11, B, T), short=1))
+        case("maskgit/refused/uniforms", maskgit(temperature=1.0, no_uniforms=True))
+        case("maskgit/refused/guidance", maskgit(guidance=guide(3.0)))
+        case("maskgit/refused/null_action", maskgit(guidance=_lib.Guidance(3.0, 5), cond=acts(11, B, T)))
+
+        # ---- genie_generate_cached_ex / _guided
+        Pc, nc = T // 2, min(T - T // 2, 3)
+
+        def cached(mode=RANDOM, temperature=0.0, sampling=None, guidance=None, cond=None, tf=0, merge=1, want_logits=False, steps=2, P=Pc,
+                   n=nc, null_ids=False, short=0, no_uniforms=False):
+            def fn():
+                ids = clip[:, :min(P + n, T)].contiguous()
+                nz, uni = draws(temperature, steps, n, B)
+                NB = 2 * B if guidance is not None and guidance.scale != 1.0 else B
+                gen = sent(torch.int64, B, n, S)
+                lg = sent(torch.float32, B, n, S, V) if want_logits else None
+                cache = torch.zeros(lib.genie_prefix_cache_bytes(c, NB), dtype=torch.uint8, device="cuda")
+                need = (lib.genie_generate_guided_workspace_bytes if NB != B else lib.genie_generate_workspace_bytes)(c, B, min(P, T))
+                args = [c, w, 0 if null_ids else ids.data_ptr(), B, P, n, steps, temperature, mode, ptr(nz), 0 if no_uniforms else ptr(uni), tf,
+                        merge, gen.data_ptr(), ptr(lg), cache.data_ptr(), cache.numel(), ws.data_ptr(), need - short, st, cond, sampling]
+                rc = lib.genie_generate_cached_guided(*args, guidance) if guidance is not None else lib.genie_generate_cached_ex(*args)
+                outs = {"tokens": gen, "cache": cache}
+                if want_logits:
+                    outs["logits0"] = lg
+                return rc, outs
+            return fn
+        case("cached/merged", cached(), tokens=("tokens",))
+        case("cached/unmerged/logits0", cached(merge=0, want_logits=True), tokens=("tokens",))
+        case("cached/tf/logits0", cached(GREEDY, tf=1, want_logits=True), tokens=("tokens",))
+        case("cached/law", cached(CONF, 1.0, law), tokens=("tokens",))
+        case("cached/actions/steps1", cached(cond=acts(12, B, T), steps=1), tokens=("tokens",))
+        case("cached/guided3", cached(RANDOM, 1.0, law, guide(3.0), acts(12, B, T), want_logits=True), tokens=("tokens",))
+        case("cached/guided3/unmerged/tf", cached(CONF, 0.0, None, guide(3.0), acts(12, B, T), tf=1, merge=0), tokens=("tokens",))
+        case("cached/guided1", cached(guidance=guide(1.0), cond=acts(12, B, T)), tokens=("tokens",))
+        case("cached/refused/null", cached(null_ids=True))
+        case("cached/refused/frames", cached(P=T - 1, n=2))
+        case("cached/refused/workspace", cached(short=1))
+        case("cached/refused/uniforms", cached(temperature=1.0, no_uniforms=True))
+        case("cached/refused/guidance", cached(guidance=guide(3.0)))
+        case("cached/refused/mode", cached(mode=7))
+
+        # ---- genie_rollout_cached past the window: 3 windows; in one call, and split in mid-window with resume = 1
+        if T == 4:
+            rolls = [("keep2", 2, 2, 5)]
+        else:
+            rolls = [("keep8", T - 2, 8, 4), ("keep15", T - 2, T - 1, 4)]
+
+        def rollout(P, keep, n, split, guidance=None, cond_seed=None, temperature=0.0, mode=RANDOM, sampling=None, steps=2, null_frames=False,
+                    short=0, no_uniforms=False, f1_over=0):
+            def fn():
+                cap = P + n
+                frames = torch.full((B, cap, S), cfg.image_vocab_size, dtype=torch.int64, device="cuda")
+                frames[:, :P] = clip[:, :P]
+                cond = acts(cond_seed, B, cap) if cond_seed else None
+                guided = guidance is not None and guidance.scale != 1.0
+                nz, uni = draws(temperature, steps, n, B)
+                cache = torch.zeros(lib.genie_prefix_cache_bytes(c, 2 * B if guided else B), dtype=torch.uint8, device="cuda")
+                need = lib.genie_rollout_workspace_bytes(c, B, max(P, min(keep, T - 1)), int(guided))   # the largest context of the call(s)
+                rc = 0
+                for f0, f1, resume in ([(P, P + 1, 0), (P + 1, cap, 1)] if split else [(P, cap + f1_over, 0)]):
+                    if rc == 0:
+                        rc = lib.genie_rollout_cached(c, w, 0 if null_frames else frames.data_ptr(), B, P, keep, cap, f0, f1, resume, steps,
+                                                      temperature, mode, nz[f0 - P:].data_ptr(), 0 if uni is None or no_uniforms else uni[f0 - P:].data_ptr(),
+                                                      1, cache.data_ptr(), cache.numel(), ws.data_ptr(), need - short, st, cond, sampling, guidance)
+                return rc, {"tokens": frames, "cache": cache}
+            return fn
+        for rname, P, keep, n in rolls:
+            for split in (0, 1):
+                case(f"rollout/{rname}/split{split}", rollout(P, keep, n, split), tokens=("tokens",))
+                case(f"rollout/{rname}/split{split}/guided3", rollout(P, keep, n, split, guide(3.0), 13, 1.0, CONF, law), tokens=("tokens",))
+            case(f"rollout/{rname}/actions", rollout(P, keep, n, 0, None, 13), tokens=("tokens",))
+        rname, P, keep, n = rolls[0]
+        case("rollout/refused/null", rollout(P, keep, n, 0, null_frames=True))
+        case("rollout/refused/frames", rollout(P, keep, n, 0, f1_over=1))
+        case("rollout/refused/keep", rollout(P, T, n, 0))
+        case("rollout/refused/workspace", rollout(P, keep, n, 0, short=1))
+        case("rollout/refused/uniforms", rollout(P, keep, n, 0, temperature=1.0, no_uniforms=True))
+        case("rollout/refused/guidance", rollout(P, keep, n, 0, guide(3.0)))
+
+        # ---- genie_generate_fanout and genie_score_fanout over one trunk
+        def fanout(K, P, n, guidance=None, cond_seed=None, temperature=0.0, mode=RANDOM, sampling=None, steps=2, merge=1, null_ids=False, short=0,
+                   no_uniforms=False, short_branch=0):
+            def fn():
+                guided = guidance is not None and guidance.scale != 1.0
+                NB = 2 * B if guided else B
+                ids = clip[:, :min(P, T)].contiguous()
+                cond = acts(cond_seed, B * K, T) if cond_seed else None
+                nz, uni = draws(temperature, steps, n, B * K)
+                gen = sent(torch.int64, B, K, n, S)
+                trunk = torch.zeros(lib.genie_prefix_cache_bytes(c, NB), dtype=torch.uint8, device="cuda")
+                branch = torch.zeros(max(lib.genie_fanout_branch_bytes(c, NB, K, min(n, T - 1)), 256), dtype=torch.uint8, device="cuda")
+                need = lib.genie_fanout_workspace_bytes(c, B, K, min(P, T - 1), int(guided))
+                rc = lib.genie_generate_fanout(c, w, 0 if null_ids else ids.data_ptr(), B, K, P, n, steps, temperature, mode, ptr(nz),
+                                               0 if no_uniforms else ptr(uni), merge, gen.data_ptr(), trunk.data_ptr(), trunk.numel(), branch.data_ptr(),
+                                               branch.numel() - short_branch, ws.data_ptr(), need - short, st, cond, sampling, guidance)
+                return rc, {"tokens": gen, "trunk": trunk, "branch": branch}
+            return fn
+        nf = min(T - 1, 3)
+        for K in (1, 3):
+            case(f"fanout/K{K}/P1", fanout(K, 1, nf, temperature=1.0, sampling=law), tokens=("tokens",))
+            case(f"fanout/K{K}/Plast/actions", fanout(K, T - 1, 1, cond_seed=14), tokens=("tokens",))
+            case(f"fanout/K{K}/P1/actions/unmerged", fanout(K, 1, nf, cond_seed=14, mode=CONF, merge=0), tokens=("tokens",))
+            case(f"fanout/K{K}/P1/guided3", fanout(K, 1, nf, guide(3.0), 14, 1.0, GREEDY, law), tokens=("tokens",))
+            case(f"fanout/K{K}/Phalf/guided3", fanout(K, T // 2, T - T // 2 if T == 4 else 2, guide(3.0), 14), tokens=("tokens",))
+        case("fanout/refused/null", fanout(3, 1, nf, null_ids=True))
+        case("fanout/refused/frames", fanout(3, T - 1, 2))
+        case("fanout/refused/workspace", fanout(3, 1, nf, short=1))
+        case("fanout/refused/branch", fanout(3, 1, nf, short_branch=1))
+        case("fanout/refused/uniforms", fanout(3, 1, nf, temperature=1.0, no_uniforms=True))
+        case("fanout/refused/guidance", fanout(3, 1, nf, guide(3.0)))
+        case("fanout/refused/K", fanout(0, 1, nf))
+
+        def score(K, P, n, merge=1, cond_seed=None, per_token=True, want_hits=True, null_ids=False, short=0, short_trunk=0):
+            def fn():
+                ids = clip[:, :min(P + n, T)].contiguous()
+                cond = acts(cond_seed, B * K, T) if cond_seed else None
+                nll = sent(torch.float64, B, max(K, 1), n)
+                hits = sent(torch.float64, B, max(K, 1), n) if want_hits else None
+                tok = sent(torch.float32, B, max(K, 1), n, S) if per_token else None
+                trunk = torch.zeros(lib.genie_prefix_cache_bytes(c, B), dtype=torch.uint8, device="cuda")
+                branch = torch.zeros(max(lib.genie_fanout_branch_bytes(c, B, K, min(n, T - 1)), 256), dtype=torch.uint8, device="cuda")
+                need = lib.genie_score_workspace_bytes(c, B, K, min(P, T - 1))
+                rc = lib.genie_score_fanout(c, w, 0 if null_ids else ids.data_ptr(), B, K, P, n, merge, nll.data_ptr(), ptr(hits), ptr(tok),
+                                            trunk.data_ptr(), trunk.numel() - short_trunk, branch.data_ptr(), branch.numel(), ws.data_ptr(),
+                                            need - short, st, cond)
+                outs = {"nll": nll, "trunk": trunk, "branch": branch}
+                if want_hits:
+                    outs["hits"] = hits
+                if per_token:
+                    outs["token_nll"] = tok
+                return rc, outs
+            return fn
+        ns = T - T // 2 if T == 4 else 3
+        for K in (1, 3):
+            case(f"score/K{K}/merged", score(K, T // 2, ns))
+            case(f"score/K{K}/unmerged/actions", score(K, T // 2, ns, merge=0, cond_seed=15, per_token=False))
+            case(f"score/K{K}/P1/actions/nll_only", score(K, 1, 2, cond_seed=15, per_token=False, want_hits=False))
+        case("score/refused/null", score(3, T // 2, ns, null_ids=True))
+        case("score/refused/frames", score(3, T - 1, 2))
+        case("score/refused/workspace", score(3, T // 2, ns, short=1))
+        case("score/refused/trunk", score(3, T // 2, ns, short_trunk=1))
+        case("score/refused/K", score(0, T // 2, ns))
+        del ws
+        torch.cuda.empty_cache()
+
+    if battery == "loops":
+        for gname, d, heads, T, S, precs, clips in LOOP_MODELS:
+            for qk_norm in (False, True):
+                cfg = GenieConfig(num_layers=2, num_heads=heads, d_model=d, T=T, S=S, num_factored_vocabs=2, qk_norm=qk_norm, use_mup=False,
+                                  qkv_bias=True, action_vocab_size=5)
+                sd = synth.make_state_dict(cfg, seed=5, law="conditioned")
+                nonzero_biases(sd, 6)
+                sd["action_embed.weight"] = (0.5 * np.random.default_rng(8).standard_normal(sd["action_embed.weight"].shape)).astype(np.float32)
+                for prec in precs:
+                    m = STMaskGIT(cfg, precision=prec).load_numpy_state_dict(sd).to("cuda")
+                    for B in clips:
+                        loop_cases(f"{gname}/{'qknorm' if qk_norm else 'ln'}/{prec}/B{B}", m, B)
+                    del m
+                    torch.cuda.empty_cache()
         with open(out_path, "w") as f:
             json.dump(record, f)
         return
@@ -263,7 +528,7 @@ def child(out_path, battery):
 
 def run_battery(a, battery):
     """Both children of one battery and the comparison of their records -> 0, or the exit status of the failure"""
-    watched = TRAIN_WATCHED if battery == "train" else WATCHED
+    watched = {"train": TRAIN_WATCHED, "loops": LOOPS_WATCHED}.get(battery, WATCHED)
     records = []
     with tempfile.TemporaryDirectory() as tmp:
         for i, path in enumerate((a.library_a, a.library_b)):
@@ -357,7 +622,7 @@ def main():
     ap.add_argument("library_a", nargs="?", help="the library to compare against (its tables decide whether the battery reached WATCHED)")
     ap.add_argument("library_b", nargs="?")
     ap.add_argument("--timeout", type=int, default=420, help="time limit of each child process, seconds")
-    ap.add_argument("--battery", default="all", choices=["all", "inference", "train"],
+    ap.add_argument("--battery", default="all", choices=["all", "inference", "train", "loops"],
                     help="each battery runs in its own pair of child processes; a failing one ends the run")
     ap.add_argument("--child", help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -365,7 +630,7 @@ def main():
         return child(a.child, a.battery)
     if not (a.library_a and a.library_b):
         ap.error("two libraries")
-    for battery in (["inference", "train"] if a.battery == "all" else [a.battery]):
+    for battery in (["inference", "train", "loops"] if a.battery == "all" else [a.battery]):
         status = run_battery(a, battery)
         if status:
             return status
