@@ -199,6 +199,12 @@ for _n in ("genie_embed", "genie_compute_logits", "genie_maskgit_generate", "gen
            "genie_frame_pass", "genie_frames_pass", "genie_generate_cached", "genie_train_forward"):
     SIGNATURES[_n + "_cond"] = (SIGNATURES[_n][0], SIGNATURES[_n][1] + [C.POINTER(FrameCond)])
 del _n
+# the training step with activation recomputation: the arguments of the plain entry point (genie_train_forward: of its *_cond form)
+# + a trailing int recompute (0 = that entry point)
+for _n in ("genie_train_activation_bytes", "genie_train_workspace_bytes", "genie_train_forward_cond", "genie_train_backward_head",
+           "genie_train_backward_layer"):
+    SIGNATURES[_n.replace("_cond", "") + "_ex"] = (SIGNATURES[_n][0], SIGNATURES[_n][1] + [C.c_int])
+del _n
 # the *_ex variants: the *_cond arguments + a trailing genie_sampling* (NULL = the *_cond entry point); genie_sample_ex: genie_sample's
 # arguments + sampling, keys_out, noise, anneal
 for _n in ("genie_maskgit_generate", "genie_generate_cached"):
@@ -304,6 +310,15 @@ def call_cond(lib, name, cond, *args):
     if cond is None:
         return getattr(lib, name)(*args)
     return getattr(lib, name + "_cond")(*args, cond)
+
+
+def call_recompute(lib, name, recompute, *args, cond=False):
+    """lib.<name>(*args) when `recompute` is 0 (the saving training step's entry point, unchanged), else lib.<name>_ex(*args, recompute).
+    cond: False for an entry point without conditioning; for genie_train_forward, None or the genie_frame_cond of the call: call_cond
+    when `recompute` is 0, else lib.<name>_ex(*args, cond, recompute)."""
+    if cond is False:
+        return getattr(lib, name + "_ex")(*args, recompute) if recompute else getattr(lib, name)(*args)
+    return getattr(lib, name + "_ex")(*args, cond, recompute) if recompute else call_cond(lib, name, cond, *args)
 
 
 def call_ex(lib, name, cond, sampling, *args):

@@ -775,6 +775,35 @@ int launch_gemm16_ex(int npl, const uint16_t* A, long lda, long planeA, const ui
                             strideA, strideC, Rf, strideW);
 }
 
+// split_f16_x4 of n floats (n % 4 == 0) into [hi | lo] planes: the split of the gemm16_sm / gemm16_pp epilogues, which keep a hi below
+// the f16 normal range where split_f16 (split_f16_kernel, and the epilogues of the kernels above) writes 0 and moves the value to lo
+__global__ __launch_bounds__(256) void split_f16_x4_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst, size_t plane,
+                                                           size_t n4) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    const float4 v = reinterpret_cast<const float4*>(src)[i];
+    uint32_t h01, h23, l01, l23;
+    split_f16_x4(v.x, v.y, v.z, v.w, h01, h23, l01, l23);
+    *reinterpret_cast<uint2*>(dst + 4 * i) = make_uint2(h01, h23);
+    *reinterpret_cast<uint2*>(dst + plane + 4 * i) = make_uint2(l01, l23);
+}
+// The operand form of the (M, N) f32 matrix `src` as the G16X_OUT16 epilogue of launch_gemm16_ex(npl, ...) writes it for the problem
+// (M, N, K) with row-major operands and `flags`: the recomputing training step rebuilds with it, from the f32 output alone, the operand
+// that a Linear of the forward handed to the next layer.  bf16 rounds the same way in every kernel; the split-f16 kernels do not split
+// alike (above), so this follows launch_gemm16's choice between them.  f16x3 needs G16X_WIDEW (the training step's Linears: gemm16_pp,
+// whose acceptance is not restated here, is out of the choice) and answers GENIE_E_UNSUPPORTED without.
+int launch_cast16_like_gemm(int npl, const float* src, uint16_t* dst, int M, int N, int K, int flags, hipStream_t st) {
+    const size_t n = (size_t)M * N;
+    if (npl == 1) return launch_cast16(1, src, dst, n, st);
+    if (!(flags & G16X_WIDEW)) return GENIE_E_UNSUPPORTED;
+    const bool sm = !(flags & G16X_NOSM) &&
+                    gemm16_sm_takes(2, K, (long)M * K, K, (long)N * K, (long)n, N, M, N, K, flags & ~(G16X_WIDEW | G16X_NOSM), 1);
+    if (!sm) return launch_split_f16(src, dst, n, n, st);
+    split_f16_x4_kernel<<<(unsigned)((n / 4 + 255) / 256), 256, 0, st>>>(src, dst, n, n / 4);   // (gemm16_sm: N % 4 == 0)
+    GENIE_LAUNCH_CHECK("split_f16_x4");
+    return GENIE_OK;
+}
+
 // x += bias + s0 + s1 in that fixed order: the residual step behind a two-slab split-K fc2 (fc2_splitk2, st_block.hip)
 __global__ __launch_bounds__(256) void splitk2_residual_kernel(float* __restrict__ x, const float* __restrict__ s0,
                                                                const float* __restrict__ s1, const float* __restrict__ bias,

@@ -293,21 +293,26 @@ __global__ __launch_bounds__(NW * 64, 1) void gemm16_sm_kernel(const uint16_t* _
 
 // Returns GENIE_E_UNSUPPORTED when the problem is not "small" or does not fit the tiling; the caller (launch_gemm16 in
 // kernels_bf16.hip) then takes a throughput kernel.  npl = 1: bf16 operands; 2: split-f16 planes.
-int launch_gemm16_sm(int npl, const uint16_t* A, long lda, long planeA, const uint16_t* W, long ldw, long planeW,
-                     const float* bias, const float* Rf, float* Cf, uint16_t* C16, long plane16, long ldc, int M, int N, int K,
-                     int flags, float alpha, hipStream_t st, int batch, long strideA, long strideW, long strideC) {
+// (the test alone: gemm16_sm_takes, for a caller that must know which kernel's epilogue wrote an output -- launch_cast16_like_gemm)
+bool gemm16_sm_takes(int npl, long lda, long planeA, long ldw, long planeW, long plane16, long ldc, int M, int N, int K, int flags,
+                     int batch) {
     static const int on = study_env("GENIE_GEMM16_SM", 1);
     static const long max_out = study_env("GENIE_GEMM16_SM_MAX", (int)(1L << 20));
-    if (!on || (long)M * N * batch > max_out) return GENIE_E_UNSUPPORTED;
+    if (!on || (long)M * N * batch > max_out) return false;
     // long contractions (fc2, K = 2048) above 512 K outputs (2,048 rows x 512): the LDS-tiled 128x128 kernel is ahead -- every
     // workgroup here streams its operands from L2 itself, and at 32x32 tiles that is the bound (f16x3 63.4 -> 48.4 us, bf16
     // 25.4 -> 24.1; at 1,024 rows this kernel is 1.5-1.7x ahead, `profiles/r03_sm_threshold.txt`)
-    if (K > 512 && (long)M * N * batch > (1L << 19)) return GENIE_E_UNSUPPORTED;
-    if (N % 4 || ldc % 4 || lda % 8 || ldw % 8 || planeA % 8 || planeW % 8) return GENIE_E_UNSUPPORTED;
-    if (npl == 2 && (flags & G16X_OUT16) && plane16 == 0) return GENIE_E_UNSUPPORTED;
+    if (K > 512 && (long)M * N * batch > (1L << 19)) return false;
+    if (N % 4 || ldc % 4 || lda % 8 || ldw % 8 || planeA % 8 || planeW % 8) return false;
+    if (npl == 2 && (flags & G16X_OUT16) && plane16 == 0) return false;
     // 8 waves = 8 K-splits (every wave gets K/8 >= 64 k; at K = 512 the whole contraction is in flight at once); K = 256
     // (the 35M config's width) runs 4 waves of 64 k
-    if (K % 512 && K != 256) return GENIE_E_UNSUPPORTED;
+    return !(K % 512 && K != 256);
+}
+int launch_gemm16_sm(int npl, const uint16_t* A, long lda, long planeA, const uint16_t* W, long ldw, long planeW,
+                     const float* bias, const float* Rf, float* Cf, uint16_t* C16, long plane16, long ldc, int M, int N, int K,
+                     int flags, float alpha, hipStream_t st, int batch, long strideA, long strideW, long strideC) {
+    if (!gemm16_sm_takes(npl, lda, planeA, ldw, planeW, plane16, ldc, M, N, K, flags, batch)) return GENIE_E_UNSUPPORTED;
     const bool one = K == 512 || K == 256;   // one 64-k block per wave
     const double mn = (double)M * N * batch;
     ProfScope prof(GENIE_KC_GEMM, 2.0 * mn * K,

@@ -2,7 +2,8 @@
 // factored CE, backward layer by layer (so the caller can overlap the gradient all-reduce of finished layers with
 // the backward of earlier ones), AdamW.
 //
-// The STBlock is stated once for the forward (train_forward) and once for the backward (train_backward_layer), as templates over
+// The STBlock is stated once for the forward (layer_forward: train_forward's loop and the recomputation in front of a layer's
+// backward, which say where the layer's activations live with a LayerAt) and once for the backward (train_backward_layer), as templates over
 // a backend that says how a Linear product runs and in which form its operands are saved:
 //   ExactOps (GENIE_PREC_EXACT): f32 storage, every contraction on the f32 matrix instruction (launch_gemm_f32_gen);
 //   Ops16 (GENIE_PREC_BF16 / _F16X3): every Linear product -- forward, dgrad, wgrad -- on the NT 16-bit GEMM of kernels_bf16.hip
@@ -17,9 +18,21 @@
 //   | z (M,hid) fc1 pre-activation | h [op] (M,hid) gelu(z);
 // after the layers: xL (M,d) | xL16 [op] (M,d) (16-bit only) | logits (M,V) (replaced in place by d loss / d logits).
 // qk_norm: norm1 / norm2 are Identity, so u1 / u2 are x0 / x2 in operand form (exact: the f32 slots themselves, the u1 / u2 slots
-// stay unused).  Exact: 21*d floats per token and layer, 5.6 GB per clip for the C138 shape; 16-bit: 52 d + 18 d NPL bytes -- sized
-// for 288 GB, nothing is recomputed except the attention probabilities (rebuilt inside the fused attention backward kernels; for
-// S != 256 the spatial scores are materialised per layer in the workspace, never saved).
+// stay unused).  Exact: 21*d floats per token and layer, 5.6 GB per clip for the C138 shape; 16-bit: 52 d + 18 d NPL bytes.  In this
+// layout (recompute = 0) nothing is recomputed except the attention probabilities (rebuilt inside the fused attention backward
+// kernels; for S != 256 the spatial scores are materialised per layer in the workspace, never saved).
+//
+// recompute = 1 (the *_ex entry points) keeps one tensor per layer and rebuilds the rest in the backward:
+//   L checkpoints x0[l] (M,d) f32, each rounded up to 256 bytes | ONE layer's slots u1 .. h as above, shared by every layer
+//   | xL | xL16 | logits as above.
+// The forward runs every layer in the shared slots, reading checkpoint l and writing checkpoint l + 1 (or xL); the backward of
+// layer l first runs the same layer forward again from checkpoint l, without fc2 (its output is the next checkpoint, which no
+// backward reads, and with Identity norms its 16-bit epilogue would write the NEXT layer's operand over this layer's u1), so every
+// genie_train_backward_layer_ex call overwrites the shared slots.  With Identity norms in the 16-bit precisions layer l's u1 came
+// from the fc2 epilogue of layer l - 1 (layer 0's from a cast); the recomputation makes it from the checkpoint in the same bits
+// (Ops16::cast_like: in f16x3 the GEMM kernels do not all split a value below the f16 normal range alike).  The forward kernels are
+// bit-reproducible, so the gradients are the same bits as with recompute = 0.  Size: at most the recompute = 0 size of a one-layer
+// model plus the L checkpoints.
 #include "kernels.hpp"
 
 namespace genie {
@@ -29,25 +42,40 @@ static inline int npl_of(const genie_cfg& c) { return c.precision == GENIE_PREC_
 static inline long PL(int npl, size_t n) { return npl == 2 ? (long)n : 0; }
 
 struct TrainActs {                               // byte offsets
-    size_t per_layer;
-    size_t x0, qkvs, x1, qkvt, x2, z;            // inside a layer, f32
-    size_t u1, aos, x1h, aot, u2, h;             // inside a layer, the operand the next Linear reads
+    size_t x0_stride;                            // layer l's input x0 is at x0_stride * l
+    size_t slots, per_layer;                     // layer l's other slots start at slots + per_layer * l
+    size_t qkvs, x1, qkvt, x2, z;                // inside a layer's slots, f32
+    size_t u1, aos, x1h, aot, u2, h;             // inside a layer's slots, the operand the next Linear reads
     size_t xL, xL16, logits, total;              // in the buffer (xL16: operand)
+    bool x_is_op;                                // u1 is x0 itself (and u2 is x2)
+    bool recompute;
 };
-static TrainActs train_acts(const genie_cfg& c, int B) {
+// recompute 0: every layer keeps its input and its slots, x0 first (x0_stride = per_layer).  1: the strip of checkpoints, then one
+// layer's slots that every layer uses (per_layer = 0)
+static TrainActs train_acts(const genie_cfg& c, int B, int recompute) {
     const bool exact = c.precision == GENIE_PREC_EXACT;
     const size_t M = (size_t)B * c.T * c.S, d = c.d_model, hid = c.hidden;
     const size_t V = (size_t)c.factored_vocab * c.num_factored;
     const size_t op = exact ? 4 : 2 * npl_of(c), align = exact ? 1 : 256;   // bytes of an operand element; slot alignment
     TrainActs a;
+    a.recompute = recompute != 0;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t at = o; o += (bytes + align - 1) / align * align; return at; };
-    a.x0 = take(M * d * 4); a.u1 = take(M * d * op); a.qkvs = take(M * 3 * d * 4); a.aos = take(M * d * op);
+    a.x0_stride = (M * d * 4 + 255) / 256 * 256;
+    if (a.recompute) o = a.slots = a.x0_stride * c.num_layers;
+    else { a.slots = 0; take(M * d * 4); }
+    a.u1 = take(M * d * op); a.qkvs = take(M * 3 * d * 4); a.aos = take(M * d * op);
     a.x1 = take(M * d * 4); a.x1h = exact ? a.x1 : take(M * d * op); a.qkvt = take(M * 3 * d * 4); a.aot = take(M * d * op);
     a.x2 = take(M * d * 4); a.u2 = take(M * d * op); a.z = take(M * hid * 4); a.h = take(M * hid * op);
-    a.per_layer = o;
-    if (exact && c.qk_norm) { a.u1 = a.x0; a.u2 = a.x2; }   // Identity norms: the f32 residual stream is the operand
-    o = a.per_layer * c.num_layers;
+    if (a.recompute) {   // slot offsets count from a.slots
+        for (size_t* off : {&a.u1, &a.qkvs, &a.aos, &a.x1, &a.x1h, &a.qkvt, &a.aot, &a.x2, &a.u2, &a.z, &a.h}) *off -= a.slots;
+        a.per_layer = 0;
+    } else {
+        a.per_layer = a.x0_stride = o;
+        o = a.per_layer * c.num_layers;
+    }
+    a.x_is_op = exact && c.qk_norm;   // Identity norms: the f32 residual stream is the operand
+    if (a.x_is_op) a.u2 = a.x2;
     a.xL = take(M * d * 4); a.xL16 = exact ? a.xL : take(M * d * op); a.logits = take(M * V * 4);
     a.total = o;
     return a;
@@ -84,6 +112,13 @@ static TrainWs train_ws(const genie_cfg& c, int B, void* base) {
     w.colpart = (float*)(b + o_cp); w.dscratch = (double*)(b + o_ds);
     w.qkn = (float*)(b + o_qkn);
     return w;
+}
+
+// the activation layout of the *_ex entry points: 0 saves every layer, 1 recomputes them (see the top of this file)
+static inline bool mode_ok(int recompute) { return recompute == 0 || recompute == 1; }
+static int check_mode(int recompute, const char* fn) {
+    GENIE_CHECK_ARG(mode_ok(recompute), "%s: recompute %d is neither 0 (save) nor 1 (recompute per layer)", fn, recompute);
+    return GENIE_OK;
 }
 
 static int train_check(const genie_cfg* c, int B) {
@@ -241,12 +276,16 @@ static bool use_tn(int npl, int M, int N, int K) {
     return tn && npl == 1 && M % 64 == 0 && N % 256 == 0 && K % 128 == 0;
 }
 // y(f32) / y16 = alpha * x16 . W16^T (+b) (+R), x16 (M,K), W16 (N,K)
-static int lin16(int npl, const uint16_t* x16, const uint16_t* W16, const float* b, const float* R, float* y, uint16_t* y16,
-                 int M, int N, int K, float alpha, hipStream_t st, int flags = 0) {
+static int lin16_flags(int npl, bool y, bool y16, bool R, int flags) {
     if (y) flags |= G16X_OUTF32;
     if (y16) flags |= G16X_OUT16;
     if (R) flags |= G16X_ACCUM;
     if (npl == 2) flags |= G16X_WIDEW;   // (as the wgrad products below: the step's f16x3 GEMMs all run on the two-accumulator kernels)
+    return flags;
+}
+static int lin16(int npl, const uint16_t* x16, const uint16_t* W16, const float* b, const float* R, float* y, uint16_t* y16,
+                 int M, int N, int K, float alpha, hipStream_t st, int flags = 0) {
+    flags = lin16_flags(npl, y, y16, R, flags);
     return launch_gemm16_ex(npl, x16, K, PL(npl, (size_t)M * K), W16, K, PL(npl, (size_t)N * K), b, (R && R != y) ? R : nullptr,
                             y, y16, PL(npl, (size_t)M * N), N, M, N, K, flags, alpha, st, 1, 0, 0, 0);
 }
@@ -292,6 +331,7 @@ struct ExactOps {
     float beta;
 
     int cast(const float*, Operand*, size_t) { return GENIE_OK; }   // train_acts: the f32 rows are the operand
+    int cast_like(const float*, Operand*, const Lin&) { return GENIE_OK; }
     int norm(const float* x, const float* g, const float* b, Operand* u) {
         return launch_layer_norm(x, g, b, u, M, c.d_model, LN_EPS, st);
     }
@@ -324,9 +364,15 @@ struct Ops16 {
     float beta;
     int npl;
     TrainWs16 h;   // backward only
-    float* tmp;    // forward only: (M,d) f32 behind the generic attention kernels (the logits region, free until the readout)
+    float* tmp;    // (M,d) f32 behind the generic attention kernels.  Forward: the logits region, free until the readout;
+                   // recomputing backward: w.d1 (the logits region holds d logits until the head has run); else unused
 
     int cast(const float* x, Operand* u, size_t n) { return launch_cast16(npl, x, u, n, st); }
+    // y (M, l.N) -> the y_op that linear(x, l, R, y, y_op, nullptr) wrote beside it: the same bits, which in f16x3 depend on the kernel
+    // that took the product (launch_cast16_like_gemm)
+    int cast_like(const float* y, Operand* y_op, const Lin& l) {
+        return launch_cast16_like_gemm(npl, y, y_op, M, l.N, l.K, lin16_flags(npl, true, true, true, 0), st);
+    }
     int norm(const float* x, const float* g, const float* b, Operand* u) {
         if (npl == 1) return launch_layer_norm_bf16(x, g, b, u, M, c.d_model, LN_EPS, st);
         return launch_layer_norm_split(x, g, b, u, (size_t)M * c.d_model, M, c.d_model, LN_EPS, st);
@@ -373,41 +419,65 @@ struct Ops16 {
 // ================================================================================================
 // The step, once for both backends
 // ================================================================================================
+// where one layer's activations live: its input x0, its slots (base of the TrainActs offsets), its u1 (a slot, or x0 itself), and
+// where its output goes (the next layer's x0 and u1, or xL and xL16)
+template <class Operand>
+struct LayerAt {
+    float* x0; char* slots; Operand* u1;
+    float* xnext; Operand* xnext_op;
+    float* F(size_t off) const { return (float*)(slots + off); }
+    Operand* X(size_t off) const { return (Operand*)(slots + off); }
+};
+template <class Operand>
+static LayerAt<Operand> layer_at(const genie_cfg& c, char* acts, const TrainActs& a, int l) {
+    auto x0 = [&](int k) { return (float*)(acts + a.x0_stride * k); };
+    auto u1 = [&](int k) { return a.x_is_op ? (Operand*)x0(k) : (Operand*)(acts + a.slots + a.per_layer * k + a.u1); };
+    const bool last = l + 1 == c.num_layers;
+    return LayerAt<Operand>{x0(l), acts + a.slots + a.per_layer * l, u1(l), last ? (float*)(acts + a.xL) : x0(l + 1),
+                            last ? (Operand*)(acts + a.xL16) : u1(l + 1)};
+}
+
+// One STBlock from p.x0 (and, with Identity norms, its operand form p.u1) into the layer's slots; fc2: and its output into
+// p.xnext / p.xnext_op.  The forward runs it whole; the recomputation in front of a layer's backward stops before fc2, whose output
+// no backward reads.
+// qk_norm: norm1 / norm2 are Identity (st_transformer.py:44,67), so the operand of qkv_s / fc1 is the residual stream itself:
+// the Linear that produces it hands it over in operand form (y_op); layer 0 (and a recomputed layer) gets its from a cast.  Else
+// norm1 / norm2 produce the operand, and the readout's comes from a cast.
+template <class Ops>
+static int layer_forward(Ops& o, const genie_layer_weights& lw, const LayerLins& n, const TrainActs& a,
+                         const LayerAt<typename Ops::Operand>& p, bool fc2) {
+    const bool idn = o.c.qk_norm;
+    // spatial sub-block (st_transformer.py:73-74)
+    if (!idn) GENIE_TRY(o.norm(p.x0, lw.norm1_w, lw.norm1_b, p.u1));
+    GENIE_TRY(o.linear(p.u1, n.qkv_s, nullptr, p.F(a.qkvs), nullptr, nullptr));
+    GENIE_TRY(o.attention(false, lw.spatial, p.F(a.qkvs), p.X(a.aos)));
+    GENIE_TRY(o.linear(p.X(a.aos), n.proj_s, p.x0, p.F(a.x1), p.X(a.x1h), nullptr));
+    // temporal sub-block (st_transformer.py:77-78)
+    GENIE_TRY(o.linear(p.X(a.x1h), n.qkv_t, nullptr, p.F(a.qkvt), nullptr, nullptr));
+    GENIE_TRY(o.attention(true, lw.temporal, p.F(a.qkvt), p.X(a.aot)));
+    GENIE_TRY(o.linear(p.X(a.aot), n.proj_t, p.F(a.x1), p.F(a.x2), idn ? p.X(a.u2) : nullptr, nullptr));
+    // MLP sub-block (st_transformer.py:81, 16-25)
+    if (!idn) GENIE_TRY(o.norm(p.F(a.x2), lw.norm2_w, lw.norm2_b, p.X(a.u2)));
+    GENIE_TRY(o.linear(p.X(a.u2), n.fc1, nullptr, p.F(a.z), nullptr, p.X(a.h)));
+    if (!fc2) return GENIE_OK;
+    return o.linear(p.X(a.h), n.fc2, p.F(a.x2), p.xnext, idn ? p.xnext_op : nullptr, nullptr);
+}
+
 template <class Ops>
 static int train_forward(Ops& o, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels, char* acts,
                          const TrainActs& a, double* sums, const EmbedAct* act) {
     using Operand = typename Ops::Operand;
     const genie_cfg& c = o.c;
     const size_t pd = (size_t)o.M * c.d_model;
-    auto F = [&](int l, size_t off) { return (float*)(acts + a.per_layer * l + off); };
-    auto X = [&](int l, size_t off) { return (Operand*)(acts + a.per_layer * l + off); };
     float *xL = (float*)(acts + a.xL), *logits = (float*)(acts + a.logits);
     Operand* xL_op = (Operand*)(acts + a.xL16);
-    GENIE_TRY(launch_embed(c, *wt, input_ids, o.B, F(0, a.x0), o.st, act));
-    // qk_norm: norm1 / norm2 are Identity (st_transformer.py:44,67), so the operand of qkv_s / fc1 is the residual stream itself:
-    // the Linear that produces it hands it over in operand form (y_op); layer 0 gets its from a cast.  Else norm1 / norm2 produce
-    // the operand, and the readout's comes from a cast.
+    const LayerAt<Operand> first = layer_at<Operand>(c, acts, a, 0);
+    GENIE_TRY(launch_embed(c, *wt, input_ids, o.B, first.x0, o.st, act));
     const bool idn = c.qk_norm;
-    if (idn) GENIE_TRY(o.cast(F(0, a.x0), X(0, a.u1), pd));
+    if (idn) GENIE_TRY(o.cast(first.x0, first.u1, pd));
     for (int l = 0; l < c.num_layers; ++l) {
         const genie_layer_weights& lw = wt->layers_host[l];
-        const LayerLins n = layer_lins(c, lw, nullptr, nullptr);
-        const bool last = l + 1 == c.num_layers;
-        float* xnext = last ? xL : F(l + 1, a.x0);
-        Operand* xnext_op = last ? xL_op : X(l + 1, a.u1);
-        // spatial sub-block (st_transformer.py:73-74)
-        if (!idn) GENIE_TRY(o.norm(F(l, a.x0), lw.norm1_w, lw.norm1_b, X(l, a.u1)));
-        GENIE_TRY(o.linear(X(l, a.u1), n.qkv_s, nullptr, F(l, a.qkvs), nullptr, nullptr));
-        GENIE_TRY(o.attention(false, lw.spatial, F(l, a.qkvs), X(l, a.aos)));
-        GENIE_TRY(o.linear(X(l, a.aos), n.proj_s, F(l, a.x0), F(l, a.x1), X(l, a.x1h), nullptr));
-        // temporal sub-block (st_transformer.py:77-78)
-        GENIE_TRY(o.linear(X(l, a.x1h), n.qkv_t, nullptr, F(l, a.qkvt), nullptr, nullptr));
-        GENIE_TRY(o.attention(true, lw.temporal, F(l, a.qkvt), X(l, a.aot)));
-        GENIE_TRY(o.linear(X(l, a.aot), n.proj_t, F(l, a.x1), F(l, a.x2), idn ? X(l, a.u2) : nullptr, nullptr));
-        // MLP sub-block (st_transformer.py:81, 16-25)
-        if (!idn) GENIE_TRY(o.norm(F(l, a.x2), lw.norm2_w, lw.norm2_b, X(l, a.u2)));
-        GENIE_TRY(o.linear(X(l, a.u2), n.fc1, nullptr, F(l, a.z), nullptr, X(l, a.h)));
-        GENIE_TRY(o.linear(X(l, a.h), n.fc2, F(l, a.x2), xnext, idn ? xnext_op : nullptr, nullptr));
+        GENIE_TRY(layer_forward(o, lw, layer_lins(c, lw, nullptr, nullptr), a, layer_at<Operand>(c, acts, a, l), true));
     }
     if (!idn) GENIE_TRY(o.cast(xL, xL_op, pd));
     GENIE_TRY(o.linear(xL_op, readout_lin(c, wt, nullptr, nullptr), nullptr, logits, nullptr, nullptr, c.readout_mult));
@@ -438,11 +508,19 @@ static int train_backward_layer(Ops& o, const genie_weights* wt, const genie_wei
     const genie_layer_weights& lw = wt->layers_host[layer];
     const genie_layer_weights& g = grads->layers_host[layer];
     const LayerLins n = layer_lins(c, lw, wT ? &wT->layers_host[layer] : nullptr, &g);
-    char* L = acts + a.per_layer * layer;
-    auto F = [&](size_t off) { return (float*)(L + off); };
-    auto X = [&](size_t off) { return (const typename Ops::Operand*)(L + off); };
+    const LayerAt<typename Ops::Operand> p = layer_at<typename Ops::Operand>(c, acts, a, layer);
+    auto F = [&](size_t off) { return p.F(off); };
+    auto X = [&](size_t off) { return (const typename Ops::Operand*)p.X(off); };
     float* dx = w.dx;
     QkSrc qk;
+
+    // ---- recompute: the layer's slots again from its checkpoint, as the forward made them.  Identity norms: u1 in the bits the
+    // forward gave it -- layer 0's from a cast, a later layer's from the epilogue of the fc2 before it (every layer's fc2 has this
+    // layer's shape).  The 16-bit backend's attention scratch is w.d1, free until the MLP's backward below.
+    if (a.recompute) {
+        if (c.qk_norm) GENIE_TRY(layer == 0 ? o.cast(p.x0, p.u1, (size_t)M * d) : o.cast_like(p.x0, p.u1, n.fc2));
+        GENIE_TRY(layer_forward(o, lw, n, a, p, false));
+    }
 
     // ---- MLP: x3 = x2 + fc2(gelu(fc1(norm2(x2))))  (st_transformer.py:81, 16-25)
     GENIE_TRY(o.linear_backward(dx, X(a.h), n.fc2, nullptr, nullptr, w.g));                 // dh
@@ -467,9 +545,9 @@ static int train_backward_layer(Ops& o, const genie_weights* wt, const genie_wei
     GENIE_TRY(qk_source(c, lw.spatial, F(a.qkvs), w, B, &qk, st));
     GENIE_TRY(spatial_attn_bwd(c, F(a.qkvs), qk, w.d1, w.g, w, B, st));
     GENIE_TRY(qk_norm_backward(c, lw.spatial, g.spatial, F(a.qkvs), w.g, w, B, beta, st));
-    if (c.qk_norm) return o.linear_backward(w.g, X(a.u1), n.qkv_s, nullptr, dx, dx);
-    GENIE_TRY(o.linear_backward(w.g, X(a.u1), n.qkv_s, nullptr, nullptr, w.d1));            // d norm1 output
-    return launch_ln_bwd(F(a.x0), lw.norm1_w, w.d1, dx, (float*)g.norm1_w, (float*)g.norm1_b, M, d, LN_EPS, beta, w.lnpart, st);
+    if (c.qk_norm) return o.linear_backward(w.g, p.u1, n.qkv_s, nullptr, dx, dx);
+    GENIE_TRY(o.linear_backward(w.g, p.u1, n.qkv_s, nullptr, nullptr, w.d1));               // d norm1 output
+    return launch_ln_bwd(p.x0, lw.norm1_w, w.d1, dx, (float*)g.norm1_w, (float*)g.norm1_b, M, d, LN_EPS, beta, w.lnpart, st);
 }
 
 }  // namespace genie
@@ -478,12 +556,16 @@ using namespace genie;
 
 extern "C" {
 
-size_t genie_train_activation_bytes(const genie_cfg* cfg, int B) {
-    if (!cfg || B <= 0) return 0;
-    return train_acts(*cfg, B).total;
+size_t genie_train_activation_bytes(const genie_cfg* cfg, int B) { return genie_train_activation_bytes_ex(cfg, B, 0); }
+size_t genie_train_workspace_bytes(const genie_cfg* cfg, int B) { return genie_train_workspace_bytes_ex(cfg, B, 0); }
+
+size_t genie_train_activation_bytes_ex(const genie_cfg* cfg, int B, int recompute) {
+    if (!cfg || B <= 0 || !mode_ok(recompute)) return 0;
+    return train_acts(*cfg, B, recompute).total;
 }
-size_t genie_train_workspace_bytes(const genie_cfg* cfg, int B) {
-    if (!cfg || B <= 0) return 0;
+// the same in both modes: the recomputation's only scratch, behind the 16-bit backend's generic attention, is w.d1
+size_t genie_train_workspace_bytes_ex(const genie_cfg* cfg, int B, int recompute) {
+    if (!cfg || B <= 0 || !mode_ok(recompute)) return 0;
     const size_t exact = train_ws(*cfg, B, nullptr).total;
     if (cfg->precision != GENIE_PREC_EXACT) return train_ws16(*cfg, B, npl_of(*cfg), nullptr, exact).total;
     return exact;
@@ -515,12 +597,19 @@ int genie_train_pack_weights(const genie_cfg* cfg, const genie_weights* w, const
 
 int genie_train_forward(const genie_cfg* cfg, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels,
                         int B, float* acts, size_t acts_bytes, double* sums, void* stream) {
-    return genie_train_forward_cond(cfg, wt, input_ids, labels, B, acts, acts_bytes, sums, stream, nullptr);
+    return genie_train_forward_ex(cfg, wt, input_ids, labels, B, acts, acts_bytes, sums, stream, nullptr, 0);
 }
 
 int genie_train_forward_cond(const genie_cfg* cfg, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels,
                              int B, float* acts, size_t acts_bytes, double* sums, void* stream,
                              const genie_frame_cond* cond) {
+    return genie_train_forward_ex(cfg, wt, input_ids, labels, B, acts, acts_bytes, sums, stream, cond, 0);
+}
+
+int genie_train_forward_ex(const genie_cfg* cfg, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels,
+                           int B, float* acts, size_t acts_bytes, double* sums, void* stream, const genie_frame_cond* cond,
+                           int recompute) {
+    GENIE_TRY(check_mode(recompute, "genie_train_forward"));
     // argument errors (GENIE_E_ARG) are reported before geometry errors (GENIE_E_SHAPE), as they were before train_check
     // learnt to refuse a geometry that check_cfg admits
     GENIE_CHECK_ARG(cfg && wt && input_ids && labels && acts && sums, "genie_train_forward: NULL argument");
@@ -530,7 +619,7 @@ int genie_train_forward_cond(const genie_cfg* cfg, const genie_weights* wt, cons
     EmbedAct ea;
     const EmbedAct* act = frame_act(cond, c.S, 0, c.T, ea);
     GENIE_TRY(need16(wt, c, "genie_train_forward"));
-    const TrainActs a = train_acts(c, B);
+    const TrainActs a = train_acts(c, B, recompute);
     GENIE_CHECK_ARG(acts_bytes >= a.total, "genie_train_forward: activation buffer too small: %zu < %zu", acts_bytes, a.total);
     const int M = B * c.T * c.S, V = c.factored_vocab * c.num_factored;
     hipStream_t st = (hipStream_t)stream;
@@ -547,11 +636,18 @@ int genie_train_forward_cond(const genie_cfg* cfg, const genie_weights* wt, cons
 int genie_train_backward_head(const genie_cfg* cfg, const genie_weights* wt, const genie_weights* wT,
                               const genie_weights* grads, int B, float* acts, void* workspace, size_t workspace_bytes,
                               int accumulate, void* stream) {
+    return genie_train_backward_head_ex(cfg, wt, wT, grads, B, acts, workspace, workspace_bytes, accumulate, stream, 0);
+}
+
+int genie_train_backward_head_ex(const genie_cfg* cfg, const genie_weights* wt, const genie_weights* wT,
+                                 const genie_weights* grads, int B, float* acts, void* workspace, size_t workspace_bytes,
+                                 int accumulate, void* stream, int recompute) {
+    GENIE_TRY(check_mode(recompute, "genie_train_backward_head"));
     GENIE_TRY(train_check(cfg, B));
     GENIE_CHECK_ARG(wt && grads && acts && workspace, "genie_train_backward_head: NULL argument");
     const genie_cfg& c = *cfg;
     const TrainWs w = train_ws(c, B, workspace);
-    const TrainActs a = train_acts(c, B);
+    const TrainActs a = train_acts(c, B, recompute);
     const int M = B * c.T * c.S;
     const float beta = accumulate ? 1.0f : 0.0f;
     hipStream_t st = (hipStream_t)stream;
@@ -570,12 +666,19 @@ int genie_train_backward_head(const genie_cfg* cfg, const genie_weights* wt, con
 int genie_train_backward_layer(const genie_cfg* cfg, const genie_weights* wt, const genie_weights* wT,
                                const genie_weights* grads, int layer, int B, float* acts, void* workspace,
                                size_t workspace_bytes, int accumulate, void* stream) {
+    return genie_train_backward_layer_ex(cfg, wt, wT, grads, layer, B, acts, workspace, workspace_bytes, accumulate, stream, 0);
+}
+
+int genie_train_backward_layer_ex(const genie_cfg* cfg, const genie_weights* wt, const genie_weights* wT,
+                                  const genie_weights* grads, int layer, int B, float* acts, void* workspace,
+                                  size_t workspace_bytes, int accumulate, void* stream, int recompute) {
+    GENIE_TRY(check_mode(recompute, "genie_train_backward_layer"));
     GENIE_TRY(train_check(cfg, B));
     GENIE_CHECK_ARG(wt && grads && acts && workspace, "genie_train_backward_layer: NULL argument");
     GENIE_CHECK_ARG(layer >= 0 && layer < cfg->num_layers, "genie_train_backward_layer: layer %d out of range", layer);
     const genie_cfg& c = *cfg;
     const TrainWs w = train_ws(c, B, workspace);
-    const TrainActs a = train_acts(c, B);
+    const TrainActs a = train_acts(c, B, recompute);
     const int M = B * c.T * c.S;
     const float beta = accumulate ? 1.0f : 0.0f;
     hipStream_t st = (hipStream_t)stream;
@@ -587,7 +690,7 @@ int genie_train_backward_layer(const genie_cfg* cfg, const genie_weights* wt, co
     GENIE_TRY(need16(wT, c, "genie_train_backward_layer (transposed copies)"));
     const TrainWs16 h = train_ws16(c, B, npl_of(c), workspace, w.total);
     GENIE_CHECK_ARG(workspace_bytes >= h.total, "training workspace too small: %zu < %zu", workspace_bytes, h.total);
-    Ops16 o{c, B, M, st, w, beta, npl_of(c), h, nullptr};
+    Ops16 o{c, B, M, st, w, beta, npl_of(c), h, recompute ? w.d1 : nullptr};
     return train_backward_layer(o, wt, wT, grads, layer, (char*)acts, a);
 }
 

@@ -173,8 +173,12 @@ def bucket_bounds(segments, target_elems):
 
 class GenieTrainer:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0,
-                 gradient_accumulation_steps=1, lr_lambda=None, bucket_mb=64, group=None):
+                 gradient_accumulation_steps=1, lr_lambda=None, bucket_mb=64, group=None, recompute=False):
+        """recompute: keep only each layer's input from the forward and rebuild the layer's other activations in front of its
+        backward (include/genie_hip.h, "Activation recomputation"): the same loss and gradient bits from an activation buffer of
+        about one layer plus L checkpoints, for about one more layer forward per layer of time."""
         self.model, self.config = model, model.config
+        self.recompute = 1 if recompute else 0
         dev = model._device()  # raises on CPU: no fallback
         self.lib = _lib.load()
         self.precision = model.precision
@@ -270,8 +274,8 @@ class GenieTrainer:
     def _buffers(self, B):
         if B != self._B:
             self._acts = self._ws = None
-            na = self.lib.genie_train_activation_bytes(self.cfg, B)
-            nw = self.lib.genie_train_workspace_bytes(self.cfg, B)
+            na = _lib.call_recompute(self.lib, "genie_train_activation_bytes", self.recompute, self.cfg, B)
+            nw = _lib.call_recompute(self.lib, "genie_train_workspace_bytes", self.recompute, self.cfg, B)
             if na == 0 or nw == 0:
                 _lib.check(self.lib.genie_check_config(self.cfg), "genie_check_config")
             self._acts = torch.empty(na, dtype=torch.uint8, device=self.params.device)
@@ -316,18 +320,19 @@ class GenieTrainer:
         acts, ws = self._buffers(B)
         lib, cfg, st = self.lib, self.cfg, self._stream()
         acc_flag = 1 if accumulate else 0
-        _lib.check(_lib.call_cond(lib, "genie_train_forward", cond, cfg, self.w_table, ids.data_ptr(), lab.data_ptr(), B,
-                                  acts.data_ptr(), acts.numel(), self.sums.data_ptr(), st), "genie_train_forward")
+        _lib.check(_lib.call_recompute(lib, "genie_train_forward", self.recompute, cfg, self.w_table, ids.data_ptr(), lab.data_ptr(), B,
+                                       acts.data_ptr(), acts.numel(), self.sums.data_ptr(), st, cond=cond), "genie_train_forward")
         sums = self.sums.clone()
         self.reducer.reset()
-        _lib.check(lib.genie_train_backward_head(cfg, self.w_table, self.wT_table, self.g_table, B, acts.data_ptr(),
-                                                 ws.data_ptr(), ws.numel(), acc_flag, st), "genie_train_backward_head")
+        _lib.check(_lib.call_recompute(lib, "genie_train_backward_head", self.recompute, cfg, self.w_table, self.wT_table,
+                                       self.g_table, B, acts.data_ptr(), ws.data_ptr(), ws.numel(), acc_flag, st),
+                   "genie_train_backward_head")
         if reduce:
             self.reducer.ready(self.segments[0][1])
         L = self.config.num_layers
         for k, layer in enumerate(reversed(range(L))):
-            _lib.check(lib.genie_train_backward_layer(cfg, self.w_table, self.wT_table, self.g_table, layer, B,
-                                                      acts.data_ptr(), ws.data_ptr(), ws.numel(), acc_flag, st),
+            _lib.check(_lib.call_recompute(lib, "genie_train_backward_layer", self.recompute, cfg, self.w_table, self.wT_table,
+                                           self.g_table, layer, B, acts.data_ptr(), ws.data_ptr(), ws.numel(), acc_flag, st),
                        "genie_train_backward_layer")
             if reduce:
                 self.reducer.ready(self.segments[1 + k][1])
@@ -420,7 +425,7 @@ class GenieTrainer:
         return {"state": st, "completed_steps": self.completed_steps, "micro_step": self._micro,
                 "hyper": {"lr": self.base_lr, "betas": tuple(self.betas), "eps": self.eps,
                           "weight_decay": self.weight_decay, "max_grad_norm": self.max_grad_norm,
-                          "gradient_accumulation_steps": self.accum}}
+                          "gradient_accumulation_steps": self.accum, "recompute": bool(self.recompute)}}
 
     def load_state_dict(self, sd):
         """Inverse of `state_dict` (moments, step counters); hyper-parameters stay those of this trainer (a warning

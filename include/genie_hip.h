@@ -794,6 +794,30 @@ int genie_train_backward_embed_cond(const genie_cfg* cfg, const genie_weights* g
                                     void* workspace, size_t workspace_bytes, int accumulate, void* stream,
                                     float* d_table, const genie_frame_cond* cond);
 
+/* Activation recomputation (additions; nothing above changes).  The *_ex forms take `recompute`: 0 is the entry point of the same
+ * name without _ex (every intermediate of every layer is saved); 1 keeps only each layer's f32 input (L checkpoints of B*T*S*d_model
+ * floats), one layer's worth of intermediates that every layer reuses, and the tail (final x, logits), and
+ * genie_train_backward_layer_ex first rebuilds layer `layer`'s intermediates from its checkpoint with the forward's own kernels
+ * (all but the second MLP product, whose output no backward reads).  Those kernels are bit-reproducible: losses and every gradient
+ * are the same bits as with recompute = 0, for about one more layer forward (less fc2) per layer of time.  With recompute = 1
+ *     genie_train_activation_bytes_ex(cfg, B, 1) <= genie_train_activation_bytes(cfg with num_layers = 1, B)
+ *                                                   + num_layers * roundup256(B*T*S*d_model*4),
+ * the workspace size is that of recompute = 0, and EVERY genie_train_backward_layer_ex call overwrites the shared intermediates:
+ * the order stays forward, head, layers L-1 .. 0, embed, all with the same `recompute` and buffers sized for it.
+ * genie_train_backward_embed[_cond] does not read the activation buffer and serves both modes.  Any other `recompute`: the size
+ * functions return 0, the others GENIE_E_ARG before any other check. */
+size_t genie_train_activation_bytes_ex(const genie_cfg* cfg, int B, int recompute);
+size_t genie_train_workspace_bytes_ex(const genie_cfg* cfg, int B, int recompute);
+int genie_train_forward_ex(const genie_cfg* cfg, const genie_weights* w, const int64_t* input_ids, const int64_t* labels,
+                           int B, float* acts, size_t acts_bytes, double* sums_out, void* stream,
+                           const genie_frame_cond* cond, int recompute);
+int genie_train_backward_head_ex(const genie_cfg* cfg, const genie_weights* w, const genie_weights* wT,
+                                 const genie_weights* grads, int B, float* acts, void* workspace, size_t workspace_bytes,
+                                 int accumulate, void* stream, int recompute);
+int genie_train_backward_layer_ex(const genie_cfg* cfg, const genie_weights* w, const genie_weights* wT,
+                                  const genie_weights* grads, int layer, int B, float* acts, void* workspace,
+                                  size_t workspace_bytes, int accumulate, void* stream, int recompute);
+
 /* The temporal (causal, over the T frames of one spatial position) attention backward of the step, alone -- the counterpart of
  * genie_attention_core for the backward; f32 in every precision.  qkv (B,T,S,3*d_model) is the saved q | k | v; qk holds the q | k the
  * scores were made from, q at column 0 and k at column d_model of rows of qk_ld floats: qkv itself (qk_ld = 3*d_model) or the

@@ -23,6 +23,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--breakdown", action="store_true")
     ap.add_argument("--precision", default="exact", choices=["exact", "f16x3", "bf16"])
+    ap.add_argument("--recompute", action="store_true",
+                    help="keep one checkpoint per layer and rebuild each layer's activations in its backward (GenieTrainer(recompute=True))")
     a = ap.parse_args()
     cfgm, syn, _lib = pkg("config"), pkg("synthetic"), pkg("_lib")
     cfg = cfgm.c138() if a.config == "c138" else cfgm.c35()
@@ -33,7 +35,7 @@ def main():
         cfg.T = a.T
     sd = syn.make_state_dict(cfg, seed=0, law="init")
     model = pkg("st_mask_git").STMaskGIT(cfg, precision=a.precision).load_numpy_state_dict(sd).to("cuda")
-    tr = pkg("train").GenieTrainer(model, lr=1e-4, max_grad_norm=1.0)
+    tr = pkg("train").GenieTrainer(model, lr=1e-4, max_grad_norm=1.0, recompute=a.recompute)
     ids = torch.from_numpy(syn.make_clips(a.batch, cfg, seed=1)).cuda()
     collate = pkg("data").maskgit_collate
     torch.manual_seed(0)
@@ -55,9 +57,11 @@ def main():
     tokens = a.batch * cfg.T * cfg.S
     n_params = sum(p.numel() for p in model.parameters())
     flops = 6.0 * n_params * tokens  # the reference's own estimate (train.py:543)
-    print(f"{a.config} L={cfg.num_layers} T={cfg.T} B={a.batch}: {dt*1e3:.1f} ms/step, {tokens/dt:.0f} tokens/s, "
+    act_bytes = [lib.genie_train_activation_bytes_ex(tr.cfg, a.batch, m) for m in (0, 1)]
+    print(f"{a.config} L={cfg.num_layers} T={cfg.T} B={a.batch} recompute={int(a.recompute)}: {dt*1e3:.1f} ms/step, {tokens/dt:.0f} tokens/s, "
           f"{flops/dt/1e12:.1f} TFLOP/s (6ND), loss {float(out['loss']):.4f}, |g| {float(out['grad_norm']):.4f}, "
-          f"acts {tr._acts.numel()/2**30:.1f} GiB, ws {tr._ws.numel()/2**30:.1f} GiB")
+          f"acts {tr._acts.numel()/2**30:.1f} GiB, ws {tr._ws.numel()/2**30:.1f} GiB, "
+          f"activation bytes saved / recomputed {act_bytes[0]} / {act_bytes[1]}")
     if a.breakdown:
         import ctypes as C
         buf = (C.c_double * 4)()

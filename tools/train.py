@@ -39,6 +39,9 @@ def parse_args():
     p.add_argument("--per_device_train_batch_size", type=int, default=4)
     p.add_argument("--per_device_eval_batch_size", type=int, default=4)
     p.add_argument("--gradient_accumulation_steps", type=int, default=1)
+    p.add_argument("--recompute_activations", action="store_true",
+                   help="keep one checkpoint per layer and rebuild each layer's activations in its backward: the same numbers from "
+                        "about a tenth of the activation memory, for about one more forward of time")
     p.add_argument("--learning_rate", type=float, default=1e-4)
     p.add_argument("--weight_decay", type=float, default=0.0)
     p.add_argument("--num_train_epochs", type=int, default=1)
@@ -168,7 +171,7 @@ def main():
                  "custom_cosine": trainmod.lr_factor_custom_cosine(warm, max_steps)}[args.lr_scheduler_type]
     tr = trainmod.GenieTrainer(model, lr=args.learning_rate, betas=(args.adam_beta_1, args.adam_beta_2), eps=args.adam_eps,
                                weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm,
-                               gradient_accumulation_steps=accum, lr_lambda=lr_lambda)
+                               gradient_accumulation_steps=accum, lr_lambda=lr_lambda, recompute=args.recompute_activations)
     if args.resume_from_checkpoint:  # optimizer moments, step counters (train.py:560-590)
         tr.load_state_dict(torch.load(os.path.join(args.resume_from_checkpoint, "trainer_state.pt"), map_location=dev))
     n_params = sum(p.numel() for p in model.parameters())
