@@ -577,9 +577,15 @@ int genie_temporal_attention_decode_fanout(const genie_cfg* cfg, const genie_att
                     "%d branch slots", t, P0, c.T, Tb);
     GENIE_CHECK_ARG(trunk_slice || P0 == 0, "temporal_attention_decode_fanout: NULL trunk with P0 = %d", P0);
     GENIE_CHECK_ARG(!c.qk_norm || (aw->norm_w && aw->norm_b), "temporal_attention_decode_fanout: qk_norm without norm_w / norm_b");
-    return launch_attn_temporal_single_fanout(branch_slice, out, NBK, Tb, c.S, t, c.d_model, c.num_heads, c.head_dim, c.attn_scale,
-                                              c.qk_norm ? aw->norm_w : nullptr, c.qk_norm ? aw->norm_b : nullptr, as_stream(stream), nullptr, 0,
-                                              in16 != 0, FanSplit<true>{trunk_slice ? trunk_slice : branch_slice, c.T, P0, K});
+    const float* nw = c.qk_norm ? aw->norm_w : nullptr;
+    const float* nb = c.qk_norm ? aw->norm_b : nullptr;
+    // the dense form (no trunk, one branch per clip) is the ordinary decode kernel; that launcher refuses slices of more than 64 slots
+    if (!trunk_slice && K == 1 && P0 == 0 && Tb <= 64)
+        return launch_attn_temporal_single(branch_slice, out, NBK, Tb, c.S, t, c.d_model, c.num_heads, c.head_dim, c.attn_scale, nw, nb,
+                                           as_stream(stream), nullptr, 0, in16 != 0);
+    return launch_attn_temporal_single_fanout(branch_slice, out, NBK, Tb, c.S, t, c.d_model, c.num_heads, c.head_dim, c.attn_scale, nw, nb,
+                                              as_stream(stream), nullptr, 0, in16 != 0,
+                                              FanSplit<true>{trunk_slice ? trunk_slice : branch_slice, c.T, P0, K});
 }
 
 int genie_pack_frame_w16(const float* src, uint16_t* dst, int N, int K, void* stream) {

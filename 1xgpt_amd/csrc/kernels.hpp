@@ -191,12 +191,16 @@ int launch_attn_generic_bf16(const uint16_t* qkv, uint16_t* out, int N, long n_s
 int launch_attn_spatial_f32_mfma(const float* qkv, float* out, int S, long n_seq, int d, int H, int Dh, float scale,
                                  const float* nw, const float* nb, hipStream_t st, uint16_t* out16 = nullptr,
                                  size_t plane = 0);
-int launch_attn_temporal_f32_mfma(const float* qkv, float* out, int B, int T, int S, int d, int H, int Dh, float scale,
-                                  const float* nw, const float* nb, hipStream_t st, uint16_t* out16 = nullptr,
-                                  size_t plane = 0, int Tq = 0, bool in16 = false);
 int launch_attn_spatial_split(const float* qkv, float* out, int S, long n_seq, int d, int H, int Dh, float scale,
                               const float* nw, const float* nb, hipStream_t st, uint16_t* out16 = nullptr,
                               size_t plane = 0);
+// kernels_attn_temporal.hip: causal temporal attention (out16 / plane as above; in16: the qkv rows / the cache hold bf16, temporal_qkv16)
+int launch_attn_temporal_f32_mfma(const float* qkv, float* out, int B, int T, int S, int d, int H, int Dh, float scale,
+                                  const float* nw, const float* nb, hipStream_t st, uint16_t* out16 = nullptr,
+                                  size_t plane = 0, int Tq = 0, bool in16 = false);
+int launch_attn_temporal_prefix(const float* cur, const float* cache, float* out, int B, int T, int S, int d, int H,
+                                int Dh, float scale, const float* nw, const float* nb, hipStream_t st,
+                                uint16_t* out16 = nullptr, size_t plane = 0, int sh = 0, bool in16 = false);
 int launch_attn_temporal_single(const float* cache, float* out, int B, int T, int S, int t, int d, int H, int Dh,
                                 float scale, const float* nw, const float* nb, hipStream_t st,
                                 uint16_t* out16 = nullptr, size_t plane = 0, bool in16 = false);
@@ -210,13 +214,21 @@ struct FanSplit<true> {
     const void* trunk;   // same element type as the branch slice
     int T, P0, K;        // slots per clip of the trunk; first branch slot; branches per parent
 };
+// cache slot j of one (clip, position, head): `own` + j slots, or (FAN) the trunk below P0 and slot j - P0 of the branch from P0 on
+template <bool FAN, typename TI>
+__device__ __forceinline__ const TI* fan_slot(const TI* own, const TI* trunk, int j, int P0, size_t tok) {
+    if constexpr (FAN) {
+        const bool lo = j < P0;
+        return (lo ? trunk : own) + (size_t)(lo ? j : j - P0) * tok;
+    } else {
+        return own + (size_t)j * tok;
+    }
+}
 // launch_attn_temporal_single over that split cache: `cache` is the branch slice and T its slots per clip (Tb); t >= fan.P0
 int launch_attn_temporal_single_fanout(const float* cache, float* out, int B, int T, int S, int t, int d, int H, int Dh, float scale,
                                        const float* nw, const float* nb, hipStream_t st, uint16_t* out16, size_t plane, bool in16,
                                        const FanSplit<true>& fan);
-int launch_attn_temporal_prefix(const float* cur, const float* cache, float* out, int B, int T, int S, int d, int H,
-                                int Dh, float scale, const float* nw, const float* nb, hipStream_t st,
-                                uint16_t* out16 = nullptr, size_t plane = 0, int sh = 0, bool in16 = false);
+// kernels_exact.hip, continued
 int launch_layer_norm_split(const float* x, const float* g, const float* b, uint16_t* y, size_t plane, long rows, int C,
                             float eps, hipStream_t st);
 int launch_split_f16(const float* src, uint16_t* dst, size_t plane, size_t n, hipStream_t st);

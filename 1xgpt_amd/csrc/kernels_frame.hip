@@ -850,23 +850,14 @@ __global__ __launch_bounds__(256) void attn_temporal_fr_kernel(const float* __re
         tb = static_cast<const float*>(fan.trunk) + ((size_t)((b / fan.K) * fan.T) * S + s) * 3 * d + head * DH + 4 * c;
         P0 = fan.P0;
     }
-    // cache slot j of the lane's (clip, position, head, features): (FAN) the trunk below P0, slot j - P0 of the branch from P0 on
-    auto slot = [&](int j) {
-        if constexpr (FAN) {
-            const bool lo = j < P0;
-            return (lo ? tb : hb) + (size_t)(lo ? j : j - P0) * tok;
-        } else {
-            return hb + (size_t)j * tok;
-        }
-    };
-    f32x4 qv = *reinterpret_cast<const f32x4*>(slot(t));
+    f32x4 qv = *reinterpret_cast<const f32x4*>(fan_slot<FAN>(hb, tb, t, P0, tok));
     f32x4 kv[NI], vv[NI];
     f32x4 qg = f32x4{0.f, 0.f, 0.f, 0.f}, qb = qg;
     if (qn_g) { qg = *reinterpret_cast<const f32x4*>(qn_g + 4 * c); qb = *reinterpret_cast<const f32x4*>(qn_b + 4 * c); }
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
         const int j = FPI * i + g;
-        const float* src = slot(j <= t ? j : t);    // (frames past t re-read frame t: their probability is 0)
+        const float* src = fan_slot<FAN>(hb, tb, j <= t ? j : t, P0, tok);    // (frames past t re-read frame t: their probability is 0)
         kv[i] = *reinterpret_cast<const f32x4*>(src + d);
         vv[i] = *reinterpret_cast<const f32x4*>(src + 2 * d);
     }

@@ -1,6 +1,6 @@
 """CPU-only tests of fan-out generation (genie_generate_fanout, generate.fanout_frames): the C ABI additions (exported, bound, argument
-errors before any HIP call, the size functions), the Python shape checks, and the compiled fan-out flavours of the two decode attention
-kernels (no scratch, no LDS)."""
+errors before any HIP call, the size functions), the Python shape checks, and the compiled flavours of the two decode attention
+kernels (csrc/kernels_attn_temporal.hip, csrc/kernels_frame.hip: no scratch, no LDS)."""
 import os
 import subprocess
 import sys
@@ -182,8 +182,9 @@ def test_python_shape_checks_raise_before_the_library_is_called(monkeypatch):
 
 
 def test_fanout_kernel_flavours_use_no_scratch_and_no_lds():
-    """The built code object: every fan-out instantiation of the two decode attention kernels keeps its scores in registers (the ordinary
-    `single` kernel's t >= 16 path indexes a score array in scratch; the fan-out flavour keeps score j in lane j), and none uses LDS."""
+    """The built code object: every instantiation of the two decode attention kernels (csrc/kernels_attn_temporal.hip, csrc/kernels_frame.hip),
+    ordinary and fan-out, keeps its scores in registers (the `single` kernel's t >= 16 path keeps score j in lane j: no indexed array in
+    scratch), and none uses LDS."""
     LLVM = "/opt/rocm/lib/llvm/bin"
     if not (os.path.exists(f"{LLVM}/llvm-objdump") and os.path.exists(f"{LLVM}/clang-offload-bundler")):
         pytest.skip("no ROCm LLVM tools")
@@ -193,12 +194,13 @@ def test_fanout_kernel_flavours_use_no_scratch_and_no_lds():
     audit = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(audit)
     rows = {r[0]: r for r in audit.audit(lib_mod.LIB_PATH, all_kernels=True)}
-    single = {k: v for k, v in rows.items() if "attn_temporal_single_kernel<" in k and k.rstrip().endswith("true>")}
+    single = {k: v for k, v in rows.items() if "attn_temporal_single_kernel<" in k}
     fr = {k: v for k, v in rows.items() if "attn_temporal_fr_kernel<" in k and k.rstrip().endswith("true>")}
-    assert len(single) == 8 and len(fr) == 2, (sorted(single), sorted(fr))      # head_dim 8 / 16 / 32 / 64 x f32 / bf16; 64 / 32
+    assert len(single) == 16 and len(fr) == 2, (sorted(single), sorted(fr))     # head_dim 8 / 16 / 32 / 64 x f32 / bf16 x ordinary / fan-out; 64 / 32
+    assert sum(k.rstrip().endswith("true>") for k in single) == 8, sorted(single)
     for name, r in {**single, **fr}.items():
         assert r[6] == 0, f"{name}: {r[6]} bytes of scratch per lane"
-        assert r[7] <= 80, f"{name}: {r[7]} registers (the ordinary flavours take 79 at most)"
+        assert r[7] <= 80, f"{name}: {r[7]} registers (79 at most before the fan-out flavour existed)"
     # no LDS: the group segment size in the kernels' own metadata
     import re
     import tempfile
@@ -208,9 +210,9 @@ def test_fanout_kernel_flavours_use_no_scratch_and_no_lds():
     lds = {}
     for block in re.split(r"\n\s*- \.agpr_count:", meta):
         name, size = re.search(r"\.name:\s+(\S+)", block), re.search(r"\.group_segment_fixed_size:\s+(\d+)", block)
-        if name and size and re.search(r"attn_temporal_(single|fr)_kernel.*Lb1E", name.group(1)):
+        if name and size and re.search(r"attn_temporal_single_kernel|attn_temporal_fr_kernel.*Lb1E", name.group(1)):
             lds[name.group(1)] = int(size.group(1))
-    assert len(lds) == 10 and not any(lds.values()), lds
+    assert len(lds) == 18 and not any(lds.values()), lds
 
 
 def test_tools_list_the_fanout_flags():

@@ -65,7 +65,7 @@ def test_batched_forward_vs_oracle(precision, nm, tol, width, heads):
 @pytest.mark.parametrize("T,heads,width,qkn", [(8, 2, 128, False), (8, 4, 128, True), (8, 2, 64, False)])
 def test_short_window_temporal_mfma(T, heads, width, qkn):
     """Windows shorter than 16 frames (generate.py / RawTokenDataset window_size = 8; T must be a power of two) run the 16x16 MFMA temporal kernel
-    with padded rows (kernels_exact.hip attn_temporal_f32_mfma_kernel, 8 <= T <= 16): logits against the f64-accumulating oracle."""
+    with padded rows (kernels_attn_temporal.hip attn_temporal_f32_mfma_kernel, 8 <= T <= 16): logits against the f64-accumulating oracle."""
     cfg = pkg("config").GenieConfig(num_layers=2, num_heads=heads, d_model=width, T=T, S=16, num_factored_vocabs=2,
                                     qk_norm=qkn, use_mup=False)
     synth = pkg("synthetic")

@@ -269,9 +269,12 @@ def test_fragment_order_path(heads):
 
 # ------------------------------------------------------------------ 5: T = 32
 def test_long_window_general_path():
-    """T = 32 in exact, P = 18, n_new = 2: t >= 16, the general path of the `single` kernel, over a trunk longer than 16 slots."""
-    cfg, m, clips = shaped_model("exact", T=32)
-    fanout_vs_replicated(m, clips[:, :18], 3, 2, seed=13)
+    """T = 32 in exact, P = 18, n_new = 2: t >= 16, the general path of the `single` kernel, over a trunk longer than 16 slots -- without
+    qk-norm, and with it (trunk and branch slots normalised on read).  The replicated oracle runs the ordinary flavour of the kernel, the
+    fan-out call the other."""
+    for qk_norm in (False, True):
+        cfg, m, clips = shaped_model("exact", T=32, qk_norm=qk_norm)
+        fanout_vs_replicated(m, clips[:, :18], 3, 2, seed=13)
 
 
 # ------------------------------------------------------------------ 6: the kernel alone

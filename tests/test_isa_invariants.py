@@ -62,7 +62,8 @@ def test_exact_gemm_interior_path(rows):
 
 def test_attention_and_conv_kernels_have_no_scratch(rows):
     for sub in ("attn_spatial_dma_kernel<", "conv3x3_slab_kernel<", "conv3x3_igemm_kernel<", "wgrad16_tn_kernel",
-                "attn_temporal_f32_mfma_kernel<", "attn_temporal_prefix_f32_mfma_kernel<", "layer_norm_fast_kernel<"):
+                "attn_temporal_f32_mfma_kernel<", "attn_temporal_prefix_f32_mfma_kernel<", "attn_temporal_single_kernel<",
+                "layer_norm_fast_kernel<"):
         for name, r in pick(rows, sub).items():
             assert r[6] == 0, f"{name}: {r[6]} bytes of scratch per lane"
     # the slab kernel's compiler-inserted waits were ~25 before its epilogue was restructured

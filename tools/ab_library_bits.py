@@ -11,7 +11,7 @@ records and exits non-zero on any difference.
 
 The battery: every pass kind (full forward, clean pass + masked-frames pass at frame0 0 and 1, a half-length clean pass into a full-length
 cache at 1 and 2 clips, one- and two-frame decode passes, the cached generate loop with 2 MaskGIT steps and the merged commit, one
-STBlock) in all three precisions, for a LayerNorm and a qk-norm model, at four geometries; then BRANCH_CASES, one model each for the
+STBlock) in all three precisions, for a LayerNorm and a qk-norm model, at five geometries; then BRANCH_CASES, one model each for the
 branches of the 16-bit layer driver (csrc/st_block.hip) that those models do not reach.  A case the library refuses (e.g. two frames
 per pass outside f16x3) counts through its return code.  WATCHED names the kernels whose dispatch depends on the pass kind: the battery
 as a whole must reach each of them in the first library, else the battery itself has failed.  Two kernels of that kind carry no name a
@@ -52,7 +52,10 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GEOMETRIES = [("d64", 64, 2, 4, 16, 3),        # generic attention kernels, ragged GEMM tiles
               ("d256", 256, 8, 16, 256, 8),    # the shipped geometry: 8 clips = every fused bf16 kernel, chip-filling GEMMs
               ("d512", 512, 8, 16, 256, 8),    # heads of 64
-              ("d64h16", 64, 4, 4, 16, 3)]     # heads of 16: the bf16 temporal qkv and KV cache stay f32 (temporal_qkv16 false)
+              ("d64h16", 64, 4, 4, 16, 3),     # heads of 16: the bf16 temporal qkv and KV cache stay f32 (temporal_qkv16 false)
+              # T > 16: the generic prefix attention kernel, causal attn_generic, and the decode attention kernel's t >= 16 path (the
+              # frame passes start at slot T / 2 = 16)
+              ("d64t32", 64, 2, 32, 16, 2)]
 # Branches of the 16-bit layer driver that no model above reaches: (tag, precision, clips, the cases to run, (d, heads, T, S, qk_norm,
 # qkv_bias), edit of the weights / of how they are packed)
 BRANCH_CASES = [
