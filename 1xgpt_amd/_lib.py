@@ -65,6 +65,11 @@ class ActionProj(C.Structure):
     _fields_ = [("weight", c_ptr), ("bias", c_ptr), ("mean", c_ptr), ("inv_std", c_ptr), ("action_dim", C.c_int32)]
 
 
+class Dropout(C.Structure):
+    """genie_dropout: MLP dropout of one training micro-batch (drop probability, micro-batch counter, seed; 1xgpt_amd/train.py)."""
+    _fields_ = [("p", C.c_float), ("call", C.c_uint32), ("seed", C.c_uint64)]
+
+
 ACTION_MAX_DIM = 256   # GENIE_ACTION_MAX_DIM
 WIDE_QKV, WIDE_PROJ, WIDE_FC1, WIDE_FC2 = 1, 2, 1, 2          # bits of the w16_wide fields (genie_hip.h)
 FUSED_QKV_STREAM = 4                                        # spatial attention: fused_w16 = [proj stream | qkv stream]
@@ -244,6 +249,14 @@ SIGNATURES["genie_score_workspace_bytes"] = (C.c_size_t, [C.POINTER(GenieCfg), C
 SIGNATURES["genie_score_fanout"] = (C.c_int, [C.POINTER(GenieCfg), C.POINTER(Weights), c_ptr] + [C.c_int] * 5 + [c_ptr, c_ptr, c_ptr, c_ptr,
                                               C.c_size_t, c_ptr, C.c_size_t, c_ptr, C.c_size_t, c_ptr, C.POINTER(FrameCond)])
 
+# MLP dropout in the training step: the mask law alone, (dr, layer, site, n, keep, stream), and the *_ex arguments + a trailing
+# genie_dropout* (NULL or p = 0: the *_ex entry point)
+SIGNATURES["genie_dropout_layout"] = (C.c_int, [C.POINTER(C.c_size_t), C.c_int])
+SIGNATURES["genie_dropout_mask"] = (C.c_int, [C.POINTER(Dropout), C.c_int, C.c_int, C.c_int64, c_ptr, c_ptr])
+for _n in ("genie_train_forward", "genie_train_backward_layer"):
+    SIGNATURES[_n + "_drop"] = (SIGNATURES[_n + "_ex"][0], SIGNATURES[_n + "_ex"][1] + [C.POINTER(Dropout)])
+del _n
+
 _lib = None
 
 
@@ -287,6 +300,9 @@ def load():
         mine = [C.sizeof(Guidance)] + [getattr(Guidance, n).offset for n, _ in Guidance._fields_]
         if lib.genie_guidance_layout(lay, 3) != 3 or list(lay)[:3] != mine:
             raise RuntimeError(f"genie_guidance layout {list(lay)[:3]} != the ctypes declaration {mine}")
+        mine = [C.sizeof(Dropout)] + [getattr(Dropout, n).offset for n, _ in Dropout._fields_]
+        if "genie_dropout_layout" not in missing and (lib.genie_dropout_layout(lay, 4) != 4 or list(lay)[:4] != mine):
+            raise RuntimeError(f"genie_dropout layout {list(lay)[:4]} != the ctypes declaration {mine}")
         if os.environ.get("GENIE_HIP_LIBRARY") or lib.genie_study_build():
             import sys
             print(f"1xgpt_amd: using {LIB_PATH} (study build: {bool(lib.genie_study_build())}) -- not the shipping library"
@@ -319,6 +335,15 @@ def call_recompute(lib, name, recompute, *args, cond=False):
     if cond is False:
         return getattr(lib, name + "_ex")(*args, recompute) if recompute else getattr(lib, name)(*args)
     return getattr(lib, name + "_ex")(*args, cond, recompute) if recompute else call_cond(lib, name, cond, *args)
+
+
+def call_drop(lib, name, recompute, drop, *args, cond=False):
+    """call_recompute when `drop` is None (the entry points of before, unchanged), else lib.<name>_drop(*args, [cond,] recompute, drop)."""
+    if drop is None:
+        return call_recompute(lib, name, recompute, *args, cond=cond)
+    if cond is False:
+        return getattr(lib, name + "_drop")(*args, recompute, drop)
+    return getattr(lib, name + "_drop")(*args, cond, recompute, drop)
 
 
 def call_ex(lib, name, cond, sampling, *args):

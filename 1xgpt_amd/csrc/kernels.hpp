@@ -322,6 +322,16 @@ int launch_embed_bwd(const genie_cfg& c, const float* dx, const int64_t* ids, in
 int launch_action_embed_bwd(const genie_cfg& c, const float* dx, const int64_t* act_ids, int n_act, int B, float* d_table,
                             float beta, float* frame_sums, hipStream_t st);
 int launch_sumsq(const float* x, size_t n, double* out, double* scratch, hipStream_t st);
+// kernels_dropout.hip: MLP dropout of the training step.  DropKey: one mask of one call -- the Philox key (the seed), counter words 2
+// and 3 (stream = layer * 2 + site, the caller's micro-batch counter) and the keep threshold (element kept iff its word >= thr)
+struct DropKey { uint32_t k0, k1, stream, call, thr; };
+int launch_drop_gelu_fwd(const float* z, float* h, size_t n, const DropKey& k, hipStream_t st);   // h = m * gelu(z)
+int launch_drop_gelu_bwd(const float* z, float* g, size_t n, const DropKey& k, hipStream_t st);   // g = m * g * gelu'(z), in place
+// out = (add, NULL: 0) + m * (s * in), n f32 values (in == out, add == out allowed); npl_out 1 / 2: also out16 = launch_cast16(npl_out, out)
+int launch_drop_axpy(int npl_out, const float* in, const float* add, float* out, uint16_t* out16, size_t n, float s, const DropKey& k,
+                     hipStream_t st);
+int launch_drop_zero16(int npl, uint16_t* h16, size_t n, const DropKey& k, hipStream_t st);       // h16 = m * h16 in every plane, in place
+int launch_dropout_mask(uint8_t* keep, size_t n, const DropKey& k, hipStream_t st);              // the keep bytes (genie_dropout_mask)
 // 16-bit operand copies (kernels_train16.hip); npl = 1 bf16, 2 = f16 split planes [hi | lo]
 // colpart != NULL: also the column sums of the (post-gelu') values: slabs [rows/64][cols] for launch_slab_reduce
 // scale16 (npl == 2 only): the split copies hold in * scale16, saturated at +-65504 (the column sums and the MODE 1 write-back

@@ -33,6 +33,15 @@
 // (Ops16::cast_like: in f16x3 the GEMM kernels do not all split a value below the f16 normal range alike).  The forward kernels are
 // bit-reproducible, so the gradients are the same bits as with recompute = 0.  Size: at most the recompute = 0 size of a one-layer
 // model plus the L checkpoints.
+//
+// MLP dropout (the *_drop entry points, genie_dropout with p > 0; kernels_dropout.hip): h = m0 s gelu(z), x3 = x2 + m1 s (fc2(h) + b2),
+// keep masks recomputed from counters wherever they are applied, nothing stored.  Site 0: the h slot holds m0 gelu(z) -- zeroed, not
+// scaled -- and s rides in the alpha of fc2 and of fc2's two backward products, which touches neither the bias nor its gradient; z
+// keeps the pre-activation, and the backward zeroes dh with m0 before gelu'.  Site 1: the bias is inside the dropped term, so fc2
+// writes t = s h . W2^T + b2 into the output slot without the residual and one pass turns it into x2 + m1 s t in place (with Identity
+// norms in the 16-bit precisions it also writes the next layer's operand, in launch_cast16's rounding, which is what the recomputation
+// then rebuilds it with); the backward hands fc2 a masked, scaled copy of the running dx in w.d1, dead at that point, and the residual
+// branch keeps dx itself.  p = 0 launches exactly the step above.
 #include "kernels.hpp"
 
 namespace genie {
@@ -318,9 +327,28 @@ static int need16(const genie_weights* wt, const genie_cfg& c, const char* what)
     return GENIE_OK;
 }
 
+// MLP dropout of one call: off (p = 0, the default: no dropout kernel is launched), or the scale 1 / (1 - p) and the mask key
+struct Drop {
+    bool on = false;
+    float s = 1.0f;
+    DropKey k{};
+    DropKey key(int layer, int site) const { DropKey r = k; r.stream = (uint32_t)(layer * 2 + site); return r; }
+};
+static bool drop_p_ok(const genie_dropout* dr) { return !dr || (dr->p >= 0.0f && dr->p < 1.0f); }   // (NaN fails both)
+// the key of *dr's masks, `stream` still to be set; thr = floor((double)p * 2^32): 0 at p = 0, where every word passes
+static DropKey drop_key(const genie_dropout& dr) {
+    return DropKey{(uint32_t)dr.seed, (uint32_t)(dr.seed >> 32), 0u, dr.call, (uint32_t)((double)dr.p * 4294967296.0)};
+}
+static Drop make_drop(const genie_dropout* dr) {
+    if (!dr || dr->p == 0.0f) return Drop{};
+    return Drop{true, 1.0f / (1.0f - dr->p), drop_key(*dr)};
+}
+
 // ================================================================================================
 // The two backends.  Same members: Operand (the element type of a saved Linear input), cast / norm / attention (produce an
 // operand), linear, linear_backward.  M tokens; beta 1 accumulates into the gradients; w is unused by the forward.
+// With dropout (dr.on): hidden_drop = the fc1 call with the site 0 mask on its gelu operand, residual_drop = y = R + m s t (and y_op),
+// mask_dh = the site 0 mask on dh in front of fc1's linear_backward (kGeluInMask: it applied gelu' as well, so that call gets no z).
 // ================================================================================================
 struct ExactOps {
     using Operand = float;
@@ -329,6 +357,17 @@ struct ExactOps {
     hipStream_t st;
     TrainWs w;
     float beta;
+    Drop dr;
+    static constexpr bool kGeluInMask = true;
+
+    int hidden_drop(const Operand* x, const Lin& l, float* z, Operand* h, const DropKey& k) {
+        GENIE_TRY(linear(x, l, nullptr, z, nullptr, nullptr));
+        return launch_drop_gelu_fwd(z, h, (size_t)M * l.N, k, st);
+    }
+    int residual_drop(const float* t, const float* R, float* y, Operand* /*y_op*/, size_t n, const DropKey& k) {
+        return launch_drop_axpy(0, t, R, y, nullptr, n, dr.s, k, st);
+    }
+    int mask_dh(float* dh, const float* z, size_t n, const DropKey& k) { return launch_drop_gelu_bwd(z, dh, n, k, st); }
 
     int cast(const float*, Operand*, size_t) { return GENIE_OK; }   // train_acts: the f32 rows are the operand
     int cast_like(const float*, Operand*, const Lin&) { return GENIE_OK; }
@@ -366,6 +405,17 @@ struct Ops16 {
     TrainWs16 h;   // backward only
     float* tmp;    // (M,d) f32 behind the generic attention kernels.  Forward: the logits region, free until the readout;
                    // recomputing backward: w.d1 (the logits region holds d logits until the head has run); else unused
+    Drop dr;
+    static constexpr bool kGeluInMask = false;   // gelu' is part of cast_t_bias
+
+    int hidden_drop(const Operand* x, const Lin& l, float* z, Operand* h, const DropKey& k) {
+        GENIE_TRY(linear(x, l, nullptr, z, nullptr, h));
+        return launch_drop_zero16(npl, h, (size_t)M * l.N, k, st);
+    }
+    int residual_drop(const float* t, const float* R, float* y, Operand* y_op, size_t n, const DropKey& k) {
+        return launch_drop_axpy(y_op ? npl : 0, t, R, y, y_op, n, dr.s, k, st);
+    }
+    int mask_dh(float* dh, const float*, size_t n, const DropKey& k) { return launch_drop_axpy(0, dh, nullptr, dh, nullptr, n, 1.0f, k, st); }
 
     int cast(const float* x, Operand* u, size_t n) { return launch_cast16(npl, x, u, n, st); }
     // y (M, l.N) -> the y_op that linear(x, l, R, y, y_op, nullptr) wrote beside it: the same bits, which in f16x3 depend on the kernel
@@ -445,7 +495,7 @@ static LayerAt<Operand> layer_at(const genie_cfg& c, char* acts, const TrainActs
 // norm1 / norm2 produce the operand, and the readout's comes from a cast.
 template <class Ops>
 static int layer_forward(Ops& o, const genie_layer_weights& lw, const LayerLins& n, const TrainActs& a,
-                         const LayerAt<typename Ops::Operand>& p, bool fc2) {
+                         const LayerAt<typename Ops::Operand>& p, int layer, bool fc2) {
     const bool idn = o.c.qk_norm;
     // spatial sub-block (st_transformer.py:73-74)
     if (!idn) GENIE_TRY(o.norm(p.x0, lw.norm1_w, lw.norm1_b, p.u1));
@@ -458,9 +508,16 @@ static int layer_forward(Ops& o, const genie_layer_weights& lw, const LayerLins&
     GENIE_TRY(o.linear(p.X(a.aot), n.proj_t, p.F(a.x1), p.F(a.x2), idn ? p.X(a.u2) : nullptr, nullptr));
     // MLP sub-block (st_transformer.py:81, 16-25)
     if (!idn) GENIE_TRY(o.norm(p.F(a.x2), lw.norm2_w, lw.norm2_b, p.X(a.u2)));
-    GENIE_TRY(o.linear(p.X(a.u2), n.fc1, nullptr, p.F(a.z), nullptr, p.X(a.h)));
+    if (!o.dr.on) {
+        GENIE_TRY(o.linear(p.X(a.u2), n.fc1, nullptr, p.F(a.z), nullptr, p.X(a.h)));
+        if (!fc2) return GENIE_OK;
+        return o.linear(p.X(a.h), n.fc2, p.F(a.x2), p.xnext, idn ? p.xnext_op : nullptr, nullptr);
+    }
+    // ... with dropout (st_transformer.py:22-25): h = m0 gelu(z), t = s h . W2^T + b2 in the output slot, x3 = x2 + m1 s t in place
+    GENIE_TRY(o.hidden_drop(p.X(a.u2), n.fc1, p.F(a.z), p.X(a.h), o.dr.key(layer, 0)));
     if (!fc2) return GENIE_OK;
-    return o.linear(p.X(a.h), n.fc2, p.F(a.x2), p.xnext, idn ? p.xnext_op : nullptr, nullptr);
+    GENIE_TRY(o.linear(p.X(a.h), n.fc2, nullptr, p.xnext, nullptr, nullptr, o.dr.s));
+    return o.residual_drop(p.xnext, p.F(a.x2), p.xnext, idn ? p.xnext_op : nullptr, (size_t)o.M * o.c.d_model, o.dr.key(layer, 1));
 }
 
 template <class Ops>
@@ -477,7 +534,7 @@ static int train_forward(Ops& o, const genie_weights* wt, const int64_t* input_i
     if (idn) GENIE_TRY(o.cast(first.x0, first.u1, pd));
     for (int l = 0; l < c.num_layers; ++l) {
         const genie_layer_weights& lw = wt->layers_host[l];
-        GENIE_TRY(layer_forward(o, lw, layer_lins(c, lw, nullptr, nullptr), a, layer_at<Operand>(c, acts, a, l), true));
+        GENIE_TRY(layer_forward(o, lw, layer_lins(c, lw, nullptr, nullptr), a, layer_at<Operand>(c, acts, a, l), l, true));
     }
     if (!idn) GENIE_TRY(o.cast(xL, xL_op, pd));
     GENIE_TRY(o.linear(xL_op, readout_lin(c, wt, nullptr, nullptr), nullptr, logits, nullptr, nullptr, c.readout_mult));
@@ -516,18 +573,27 @@ static int train_backward_layer(Ops& o, const genie_weights* wt, const genie_wei
 
     // ---- recompute: the layer's slots again from its checkpoint, as the forward made them.  Identity norms: u1 in the bits the
     // forward gave it -- layer 0's from a cast, a later layer's from the epilogue of the fc2 before it (every layer's fc2 has this
-    // layer's shape).  The 16-bit backend's attention scratch is w.d1, free until the MLP's backward below.
+    // layer's shape; with dropout from the site 1 pass behind that fc2, which rounds as the cast does).  The 16-bit backend's
+    // attention scratch is w.d1, free until the MLP's backward below.
     if (a.recompute) {
-        if (c.qk_norm) GENIE_TRY(layer == 0 ? o.cast(p.x0, p.u1, (size_t)M * d) : o.cast_like(p.x0, p.u1, n.fc2));
-        GENIE_TRY(layer_forward(o, lw, n, a, p, false));
+        if (c.qk_norm) GENIE_TRY(layer == 0 || o.dr.on ? o.cast(p.x0, p.u1, (size_t)M * d) : o.cast_like(p.x0, p.u1, n.fc2));
+        GENIE_TRY(layer_forward(o, lw, n, a, p, layer, false));
     }
 
     // ---- MLP: x3 = x2 + fc2(gelu(fc1(norm2(x2))))  (st_transformer.py:81, 16-25)
-    GENIE_TRY(o.linear_backward(dx, X(a.h), n.fc2, nullptr, nullptr, w.g));                 // dh
+    const float* z = F(a.z);
+    if (!o.dr.on) {
+        GENIE_TRY(o.linear_backward(dx, X(a.h), n.fc2, nullptr, nullptr, w.g));             // dh
+    } else {   // fc2's dy = m1 s dx in w.d1 (the residual branch keeps dx); dh = s dy . W2; then m0 on dh
+        GENIE_TRY(launch_drop_axpy(0, dx, nullptr, w.d1, nullptr, (size_t)M * d, o.dr.s, o.dr.key(layer, 1), st));
+        GENIE_TRY(o.linear_backward(w.d1, X(a.h), n.fc2, nullptr, nullptr, w.g, o.dr.s));
+        GENIE_TRY(o.mask_dh(w.g, z, (size_t)M * c.hidden, o.dr.key(layer, 0)));
+        if (Ops::kGeluInMask) z = nullptr;
+    }
     if (c.qk_norm) {
-        GENIE_TRY(o.linear_backward(w.g, X(a.u2), n.fc1, F(a.z), dx, dx));                  // Identity norm: dx += dz . W1
+        GENIE_TRY(o.linear_backward(w.g, X(a.u2), n.fc1, z, dx, dx));                       // Identity norm: dx += dz . W1
     } else {
-        GENIE_TRY(o.linear_backward(w.g, X(a.u2), n.fc1, F(a.z), nullptr, w.d1));           // d norm2 output
+        GENIE_TRY(o.linear_backward(w.g, X(a.u2), n.fc1, z, nullptr, w.d1));                // d norm2 output
         GENIE_TRY(launch_ln_bwd(F(a.x2), lw.norm2_w, w.d1, dx, (float*)g.norm2_w, (float*)g.norm2_b, M, d, LN_EPS, beta,
                                 w.lnpart, st));
     }
@@ -609,6 +675,13 @@ int genie_train_forward_cond(const genie_cfg* cfg, const genie_weights* wt, cons
 int genie_train_forward_ex(const genie_cfg* cfg, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels,
                            int B, float* acts, size_t acts_bytes, double* sums, void* stream, const genie_frame_cond* cond,
                            int recompute) {
+    return genie_train_forward_drop(cfg, wt, input_ids, labels, B, acts, acts_bytes, sums, stream, cond, recompute, nullptr);
+}
+
+int genie_train_forward_drop(const genie_cfg* cfg, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels,
+                             int B, float* acts, size_t acts_bytes, double* sums, void* stream, const genie_frame_cond* cond,
+                             int recompute, const genie_dropout* dr) {
+    GENIE_CHECK_ARG(drop_p_ok(dr), "genie_train_forward: dropout p = %g is not in [0, 1)", (double)dr->p);
     GENIE_TRY(check_mode(recompute, "genie_train_forward"));
     // argument errors (GENIE_E_ARG) are reported before geometry errors (GENIE_E_SHAPE), as they were before train_check
     // learnt to refuse a geometry that check_cfg admits
@@ -625,11 +698,11 @@ int genie_train_forward_ex(const genie_cfg* cfg, const genie_weights* wt, const 
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)acts;
     if (c.precision == GENIE_PREC_EXACT) {
-        ExactOps o{c, B, M, st, TrainWs{}, 0.0f};
+        ExactOps o{c, B, M, st, TrainWs{}, 0.0f, make_drop(dr)};
         return train_forward(o, wt, input_ids, labels, base, a, sums, act);
     }
     GENIE_CHECK_SHAPE(V >= c.d_model, "training step (16-bit): vocabulary rows %d < d_model %d", V, c.d_model);
-    Ops16 o{c, B, M, st, TrainWs{}, 0.0f, npl_of(c), TrainWs16{}, (float*)(base + a.logits)};
+    Ops16 o{c, B, M, st, TrainWs{}, 0.0f, npl_of(c), TrainWs16{}, (float*)(base + a.logits), make_drop(dr)};
     return train_forward(o, wt, input_ids, labels, base, a, sums, act);
 }
 
@@ -672,6 +745,14 @@ int genie_train_backward_layer(const genie_cfg* cfg, const genie_weights* wt, co
 int genie_train_backward_layer_ex(const genie_cfg* cfg, const genie_weights* wt, const genie_weights* wT,
                                   const genie_weights* grads, int layer, int B, float* acts, void* workspace,
                                   size_t workspace_bytes, int accumulate, void* stream, int recompute) {
+    return genie_train_backward_layer_drop(cfg, wt, wT, grads, layer, B, acts, workspace, workspace_bytes, accumulate, stream, recompute,
+                                           nullptr);
+}
+
+int genie_train_backward_layer_drop(const genie_cfg* cfg, const genie_weights* wt, const genie_weights* wT,
+                                    const genie_weights* grads, int layer, int B, float* acts, void* workspace,
+                                    size_t workspace_bytes, int accumulate, void* stream, int recompute, const genie_dropout* dr) {
+    GENIE_CHECK_ARG(drop_p_ok(dr), "genie_train_backward_layer: dropout p = %g is not in [0, 1)", (double)dr->p);
     GENIE_TRY(check_mode(recompute, "genie_train_backward_layer"));
     GENIE_TRY(train_check(cfg, B));
     GENIE_CHECK_ARG(wt && grads && acts && workspace, "genie_train_backward_layer: NULL argument");
@@ -684,13 +765,13 @@ int genie_train_backward_layer_ex(const genie_cfg* cfg, const genie_weights* wt,
     hipStream_t st = (hipStream_t)stream;
     if (c.precision == GENIE_PREC_EXACT) {
         GENIE_CHECK_ARG(workspace_bytes >= w.total, "training workspace too small: %zu < %zu", workspace_bytes, w.total);
-        ExactOps o{c, B, M, st, w, beta};
+        ExactOps o{c, B, M, st, w, beta, make_drop(dr)};
         return train_backward_layer(o, wt, wT, grads, layer, (char*)acts, a);
     }
     GENIE_TRY(need16(wT, c, "genie_train_backward_layer (transposed copies)"));
     const TrainWs16 h = train_ws16(c, B, npl_of(c), workspace, w.total);
     GENIE_CHECK_ARG(workspace_bytes >= h.total, "training workspace too small: %zu < %zu", workspace_bytes, h.total);
-    Ops16 o{c, B, M, st, w, beta, npl_of(c), h, recompute ? w.d1 : nullptr};
+    Ops16 o{c, B, M, st, w, beta, npl_of(c), h, recompute ? w.d1 : nullptr, make_drop(dr)};
     return train_backward_layer(o, wt, wT, grads, layer, (char*)acts, a);
 }
 
@@ -734,6 +815,20 @@ int genie_temporal_attention_backward(const float* qkv, const float* qk, int64_t
                       "genie_temporal_attention_backward: qk_ld %ld is neither 2*d_model nor 3*d_model", (long)qk_ld);
     return launch_attn_temporal_bwd(qkv, qk, (long)qk_ld, d_out, d_qkv, B, T, S, d_model, num_heads, head_dim, scale,
                                     (hipStream_t)stream);
+}
+
+int genie_dropout_layout(size_t* out_host, int n) {
+    const size_t v[4] = {sizeof(genie_dropout), offsetof(genie_dropout, p), offsetof(genie_dropout, call), offsetof(genie_dropout, seed)};
+    for (int i = 0; i < n && i < 4 && out_host; ++i) out_host[i] = v[i];
+    return 4;
+}
+
+int genie_dropout_mask(const genie_dropout* dr, int layer, int site, int64_t n, uint8_t* keep, void* stream) {
+    GENIE_CHECK_ARG(dr != nullptr, "genie_dropout_mask: NULL genie_dropout");
+    GENIE_CHECK_ARG(drop_p_ok(dr), "genie_dropout_mask: dropout p = %g is not in [0, 1)", (double)dr->p);
+    GENIE_CHECK_ARG(layer >= 0 && (site == 0 || site == 1) && n >= 0 && (keep || !n), "genie_dropout_mask: layer %d, site %d, n %lld or NULL keep",
+                    layer, site, (long long)n);
+    return launch_dropout_mask(keep, (size_t)n, Drop{true, 1.0f, drop_key(*dr)}.key(layer, site), (hipStream_t)stream);
 }
 
 int genie_sumsq(const float* x, size_t n, double* out, double* scratch, void* stream) {

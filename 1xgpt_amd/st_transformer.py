@@ -15,8 +15,11 @@ from .attention import SelfAttention, _ptr, _require_cuda, _stream, hip_linear
 class Mlp(nn.Module):
     def __init__(self, d_model: int, mlp_ratio: float = 4.0, mlp_bias: bool = True, mlp_drop: float = 0.0) -> None:
         super().__init__()
-        if mlp_drop != 0.0:
-            raise NotImplementedError("inference path: mlp_drop must be 0")
+        # training only (GenieTrainer reads config.mlp_drop; include/genie_hip.h, "MLP dropout"): `forward` and every inference entry
+        # point behave as model.eval() does and ignore it
+        if not 0.0 <= mlp_drop < 1.0:
+            raise ValueError(f"mlp_drop must be in [0, 1), got {mlp_drop!r}")
+        self.mlp_drop = float(mlp_drop)
         hidden_dim = int(d_model * mlp_ratio)
         self.fc1 = nn.Linear(d_model, hidden_dim, bias=mlp_bias)
         self.fc2 = nn.Linear(hidden_dim, d_model, bias=mlp_bias)

@@ -173,8 +173,11 @@ def bucket_bounds(segments, target_elems):
 
 class GenieTrainer:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0,
-                 gradient_accumulation_steps=1, lr_lambda=None, bucket_mb=64, group=None, recompute=False):
-        """recompute: keep only each layer's input from the forward and rebuild the layer's other activations in front of its
+                 gradient_accumulation_steps=1, lr_lambda=None, bucket_mb=64, group=None, recompute=False, dropout_seed=0):
+        """dropout_seed: with config.mlp_drop > 0 the step trains with the reference's MLP dropout (st_transformer.py:22-25).  The masks
+        are a pure function of (dropout_seed + rank, micro-batch counter, layer, site, element) (include/genie_hip.h, "MLP dropout"): nothing
+        is stored, and a run resumed from `state_dict` draws the masks it would have drawn.  mlp_drop = 0 is the step without dropout.
+        recompute: keep only each layer's input from the forward and rebuild the layer's other activations in front of its
         backward (include/genie_hip.h, "Activation recomputation"): the same loss and gradient bits from an activation buffer of
         about one layer plus L checkpoints, for about one more layer forward per layer of time."""
         self.model, self.config = model, model.config
@@ -188,6 +191,10 @@ class GenieTrainer:
         self.accum = gradient_accumulation_steps
         self.lr_lambda = lr_lambda or (lambda step: 1.0)
         self.completed_steps, self._micro = 0, 0
+        self.mlp_drop = float(getattr(self.config, "mlp_drop", 0.0))
+        if not 0.0 <= self.mlp_drop < 1.0:
+            raise ValueError(f"config.mlp_drop must be in [0, 1), got {self.mlp_drop!r}")
+        self.dropout_seed, self._drop_call = int(dropout_seed), 0   # the counter advances once per forward_backward
 
         named = dict(model.named_parameters())
         self.order = ready_order(self.config, named.keys())
@@ -287,6 +294,15 @@ class GenieTrainer:
     def _stream():
         return torch.cuda.current_stream().cuda_stream
 
+    def _dropout(self):
+        """The genie_dropout of the next micro-batch (None without dropout: the entry points of before), advancing the counter."""
+        if self.mlp_drop == 0.0:
+            return None
+        rank = dist.get_rank(self.reducer.group) if dist.is_available() and dist.is_initialized() else 0
+        dr = _lib.Dropout(p=self.mlp_drop, call=self._drop_call & 0xFFFFFFFF, seed=(self.dropout_seed + rank) & (2 ** 64 - 1))
+        self._drop_call += 1
+        return dr
+
     # ------------------------------------------------------------------ forward / backward (train.py:611-617)
     def forward_backward(self, input_ids, labels, accumulate=False, reduce=True, action_ids=None, action_vectors=None, action_drop=None):
         """One micro-batch: loss/acc of STMaskGIT.forward and gradients into the flat buffer (added when
@@ -320,8 +336,9 @@ class GenieTrainer:
         acts, ws = self._buffers(B)
         lib, cfg, st = self.lib, self.cfg, self._stream()
         acc_flag = 1 if accumulate else 0
-        _lib.check(_lib.call_recompute(lib, "genie_train_forward", self.recompute, cfg, self.w_table, ids.data_ptr(), lab.data_ptr(), B,
-                                       acts.data_ptr(), acts.numel(), self.sums.data_ptr(), st, cond=cond), "genie_train_forward")
+        drop = self._dropout()
+        _lib.check(_lib.call_drop(lib, "genie_train_forward", self.recompute, drop, cfg, self.w_table, ids.data_ptr(), lab.data_ptr(), B,
+                                  acts.data_ptr(), acts.numel(), self.sums.data_ptr(), st, cond=cond), "genie_train_forward")
         sums = self.sums.clone()
         self.reducer.reset()
         _lib.check(_lib.call_recompute(lib, "genie_train_backward_head", self.recompute, cfg, self.w_table, self.wT_table,
@@ -331,8 +348,8 @@ class GenieTrainer:
             self.reducer.ready(self.segments[0][1])
         L = self.config.num_layers
         for k, layer in enumerate(reversed(range(L))):
-            _lib.check(_lib.call_recompute(lib, "genie_train_backward_layer", self.recompute, cfg, self.w_table, self.wT_table,
-                                           self.g_table, layer, B, acts.data_ptr(), ws.data_ptr(), ws.numel(), acc_flag, st),
+            _lib.check(_lib.call_drop(lib, "genie_train_backward_layer", self.recompute, drop, cfg, self.w_table, self.wT_table,
+                                      self.g_table, layer, B, acts.data_ptr(), ws.data_ptr(), ws.numel(), acc_flag, st),
                        "genie_train_backward_layer")
             if reduce:
                 self.reducer.ready(self.segments[1 + k][1])
@@ -423,6 +440,7 @@ class GenieTrainer:
             st[n] = {"exp_avg": self.exp_avg[lo:hi].view(named[n].shape).clone(),
                      "exp_avg_sq": self.exp_avg_sq[lo:hi].view(named[n].shape).clone()}
         return {"state": st, "completed_steps": self.completed_steps, "micro_step": self._micro,
+                "dropout": {"seed": self.dropout_seed, "call": self._drop_call},
                 "hyper": {"lr": self.base_lr, "betas": tuple(self.betas), "eps": self.eps,
                           "weight_decay": self.weight_decay, "max_grad_norm": self.max_grad_norm,
                           "gradient_accumulation_steps": self.accum, "recompute": bool(self.recompute)}}
@@ -444,4 +462,6 @@ class GenieTrainer:
             self.exp_avg_sq[lo:hi].copy_(sd["state"][n]["exp_avg_sq"].reshape(-1))
         self.completed_steps = int(sd["completed_steps"])
         self._micro = int(sd.get("micro_step", 0))
+        if "dropout" in sd:   # the masks of the resumed run are those the saved one would have drawn next
+            self.dropout_seed, self._drop_call = int(sd["dropout"]["seed"]), int(sd["dropout"]["call"])
         self.pack_weights()

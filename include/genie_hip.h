@@ -756,7 +756,7 @@ int genie_rescale_u8_nhwc_bf16(const uint16_t* x, uint8_t* out, int n, int HW, i
 size_t genie_train_activation_bytes(const genie_cfg* cfg, int B);
 size_t genie_train_workspace_bytes(const genie_cfg* cfg, int B);
 
-/* STMaskGIT.forward in training mode (st_mask_git.py:267-279; dropout is 0 in every shipped config): embeds
+/* STMaskGIT.forward in training mode (st_mask_git.py:267-279; without dropout -- mlp_drop > 0 is genie_train_forward_drop below): embeds
  * input_ids (B,T,S), runs the L blocks keeping what the backward needs, the readout, and the masked factored CE of
  * compute_loss_and_acc (:231-253) against labels (B,T,S).  sums_out (3 doubles, overwritten) =
  * [sum CE over counted tokens, sum (all factors argmax-correct), n counted] with counted = frame >= 1 and
@@ -817,6 +817,39 @@ int genie_train_backward_head_ex(const genie_cfg* cfg, const genie_weights* w, c
 int genie_train_backward_layer_ex(const genie_cfg* cfg, const genie_weights* w, const genie_weights* wT,
                                   const genie_weights* grads, int layer, int B, float* acts, void* workspace,
                                   size_t workspace_bytes, int accumulate, void* stream, int recompute);
+
+/* MLP dropout in the training step (additions; nothing above changes).  Reference: st_transformer.py:22-25 and :81, one
+ * nn.Dropout(mlp_drop) behind the GELU (site 0) and behind fc2 (site 1):
+ *     h  = m0 * s * gelu(fc1(u2))           (M, hidden)
+ *     x3 = x2 + m1 * s * (fc2(h) + b2)      (M, d_model)          s = 1 / (1 - p) in f32, keep masks m in {0, 1}
+ * Training only: no inference entry point takes a genie_dropout.  The masks are never stored: every kernel that applies one makes it
+ * in registers from Philox4x32-10 with
+ *     key = (seed low 32, seed high 32),  counter = (g low 32, g high 32, layer * 2 + site, call),  g = e / 4,
+ * whose four output words serve elements 4g .. 4g + 3; e is the row-major index into the (M, hidden) or (M, d_model) matrix with
+ * token-major rows, M = B*T*S.  Element e is kept iff its word >= floor((double)p * 2^32): integers only, bit-exact in NumPy.
+ * `call` is the caller's micro-batch counter; under data parallelism the caller adds its rank to the seed.
+ * The *_drop forms take the arguments of the *_ex forms and the struct: dr == NULL or dr->p == 0 is the *_ex call itself (same
+ * launches, same bits); p < 0, p >= 1 or NaN: GENIE_E_ARG before any other check.  The forward and every backward_layer call of one
+ * step get the same struct, in both `recompute` modes (the recomputation draws the forward's masks again: same gradient bits as
+ * recompute = 0).  Head and embed backward do not depend on it.  Buffer sizes are those of the *_ex forms: the two passes' scratch
+ * are regions that are dead when they run.  The struct is read on the host during the call. */
+typedef struct genie_dropout {
+    float p;         /* drop probability, 0 <= p < 1 */
+    uint32_t call;   /* counter word 3 */
+    uint64_t seed;   /* Philox key */
+} genie_dropout;
+/* sizeof(genie_dropout) and the offsets of p, call, seed: writes min(n, 4) entries, returns 4. */
+int genie_dropout_layout(size_t* out_host, int n);
+/* keep[e] = 1 / 0 for e in [0, n): the mask of (layer, site) under *dr, as the step's kernels draw it (a window for tests; the step
+ * never materialises a mask).  p = 0 keeps everything.  NULL dr, a bad p, layer < 0, site not 0 / 1, n < 0: GENIE_E_ARG. */
+int genie_dropout_mask(const genie_dropout* dr, int layer, int site, int64_t n, uint8_t* keep, void* stream);
+int genie_train_forward_drop(const genie_cfg* cfg, const genie_weights* w, const int64_t* input_ids, const int64_t* labels,
+                             int B, float* acts, size_t acts_bytes, double* sums_out, void* stream,
+                             const genie_frame_cond* cond, int recompute, const genie_dropout* dr);
+int genie_train_backward_layer_drop(const genie_cfg* cfg, const genie_weights* w, const genie_weights* wT,
+                                    const genie_weights* grads, int layer, int B, float* acts, void* workspace,
+                                    size_t workspace_bytes, int accumulate, void* stream, int recompute,
+                                    const genie_dropout* dr);
 
 /* The temporal (causal, over the T frames of one spatial position) attention backward of the step, alone -- the counterpart of
  * genie_attention_core for the backward; f32 in every precision.  qkv (B,T,S,3*d_model) is the saved q | k | v; qk holds the q | k the

@@ -25,6 +25,7 @@ def main():
     ap.add_argument("--precision", default="exact", choices=["exact", "f16x3", "bf16"])
     ap.add_argument("--recompute", action="store_true",
                     help="keep one checkpoint per layer and rebuild each layer's activations in its backward (GenieTrainer(recompute=True))")
+    ap.add_argument("--mlp_drop", type=float, default=0.0, help="train with MLP dropout of this probability (config.mlp_drop)")
     a = ap.parse_args()
     cfgm, syn, _lib = pkg("config"), pkg("synthetic"), pkg("_lib")
     cfg = cfgm.c138() if a.config == "c138" else cfgm.c35()
@@ -33,6 +34,7 @@ def main():
         cfg.num_layers = a.layers
     if a.T:
         cfg.T = a.T
+    cfg.mlp_drop = a.mlp_drop
     sd = syn.make_state_dict(cfg, seed=0, law="init")
     model = pkg("st_mask_git").STMaskGIT(cfg, precision=a.precision).load_numpy_state_dict(sd).to("cuda")
     tr = pkg("train").GenieTrainer(model, lr=1e-4, max_grad_norm=1.0, recompute=a.recompute)
@@ -58,7 +60,7 @@ def main():
     n_params = sum(p.numel() for p in model.parameters())
     flops = 6.0 * n_params * tokens  # the reference's own estimate (train.py:543)
     act_bytes = [lib.genie_train_activation_bytes_ex(tr.cfg, a.batch, m) for m in (0, 1)]
-    print(f"{a.config} L={cfg.num_layers} T={cfg.T} B={a.batch} recompute={int(a.recompute)}: {dt*1e3:.1f} ms/step, {tokens/dt:.0f} tokens/s, "
+    print(f"{a.config} L={cfg.num_layers} T={cfg.T} B={a.batch} recompute={int(a.recompute)} mlp_drop={a.mlp_drop:g}: {dt*1e3:.1f} ms/step, {tokens/dt:.0f} tokens/s, "
           f"{flops/dt/1e12:.1f} TFLOP/s (6ND), loss {float(out['loss']):.4f}, |g| {float(out['grad_norm']):.4f}, "
           f"acts {tr._acts.numel()/2**30:.1f} GiB, ws {tr._ws.numel()/2**30:.1f} GiB, "
           f"activation bytes saved / recomputed {act_bytes[0]} / {act_bytes[1]}")
@@ -70,6 +72,13 @@ def main():
             if buf[0]:
                 print(f"  {name:14s} launches {int(buf[0]):6d}  {buf[1]/a.steps:9.2f} ms/step  "
                       f"{buf[2]/max(buf[1],1e-9)/1e9:8.1f} TFLOP/s  {buf[3]/max(buf[1],1e-9)/1e6:8.1f} GB/s")
+        if a.mlp_drop:   # the dropout kernels by name (class "other"): launches and milliseconds per step
+            kbuf = C.create_string_buffer(16384)
+            _lib.check(lib.genie_profile_kernels(_lib.KC_OTHER, kbuf, len(kbuf)), "profile_kernels")
+            for ln in kbuf.value.decode().splitlines():
+                name, n, ms = ln.split("\t")[:3]
+                if name.startswith("drop_"):
+                    print(f"    {name:22s} launches {float(n) / a.steps:6.0f}  {float(ms) / a.steps:9.4f} ms/step")
         lib.genie_profile_enable(0)
 
 

@@ -62,6 +62,11 @@ def parse_args():
     p.add_argument("--action_dropout", type=float, default=0.0,
                    help="share of the training clips whose actions are replaced by --null_action (trains the null action of "
                         "classifier-free guidance; action-conditioned configs only)")
+    p.add_argument("--mlp_drop", type=float, default=None,
+                   help="MLP dropout probability in [0, 1) of the training step (overrides the config's mlp_drop; evaluation and "
+                        "generation ignore it)")
+    p.add_argument("--dropout_seed", type=int, default=0,
+                   help="seed of the dropout masks (each rank adds its rank); saved with the trainer state")
     p.add_argument("--action_dim", type=int, default=0,
                    help="condition the model on continuous per-frame action vectors of this many values (the datasets' states.bin; "
                         "random vectors under --synthetic); with --action_dropout a dropped clip reads the model's learned null row")
@@ -154,6 +159,10 @@ def main():
         # of nn.Linear / nn.Embedding stays (kept here too, so from-scratch dynamics follow the reference recipe)
         model.init_weights()
     model = model.to(dev)
+    if args.mlp_drop is not None:
+        if not 0.0 <= args.mlp_drop < 1.0:
+            sys.exit(f"train.py: --mlp_drop {args.mlp_drop} is not in [0, 1)")
+        model.config.mlp_drop = args.mlp_drop   # read by the trainer; saved with the checkpoint's config
     if args.seed is not None:
         torch.manual_seed(args.seed + rank)  # collator draws differ per rank; the weights above do not
 
@@ -171,7 +180,8 @@ def main():
                  "custom_cosine": trainmod.lr_factor_custom_cosine(warm, max_steps)}[args.lr_scheduler_type]
     tr = trainmod.GenieTrainer(model, lr=args.learning_rate, betas=(args.adam_beta_1, args.adam_beta_2), eps=args.adam_eps,
                                weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm,
-                               gradient_accumulation_steps=accum, lr_lambda=lr_lambda, recompute=args.recompute_activations)
+                               gradient_accumulation_steps=accum, lr_lambda=lr_lambda, recompute=args.recompute_activations,
+                               dropout_seed=args.dropout_seed)
     if args.resume_from_checkpoint:  # optimizer moments, step counters (train.py:560-590)
         tr.load_state_dict(torch.load(os.path.join(args.resume_from_checkpoint, "trainer_state.pt"), map_location=dev))
     n_params = sum(p.numel() for p in model.parameters())
