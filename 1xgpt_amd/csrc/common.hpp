@@ -12,6 +12,10 @@ namespace genie {
 
 constexpr int WAVE = 64;
 
+// a lane's share of an f32 MFMA accumulator tile: 4 values of a 16x16 one, 16 of a 32x32 one
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
 void set_error(const char* fmt, ...);
 
 #define GENIE_CHECK_ARG(cond, ...)        \

@@ -302,17 +302,6 @@ int launch_ln_bwd(const float* x, const float* gamma, const float* dy, float* dx
                   long rows, int C, float eps, float beta, float* part, hipStream_t st);
 int launch_gelu_fwd(const float* z, float* h, size_t n, hipStream_t st);
 int launch_gelu_bwd(const float* z, float* g, size_t n, hipStream_t st);
-int launch_softmax_rows(float* P, long rows, int N, hipStream_t st);
-int launch_softmax_bwd_rows(const float* P, float* dP, long rows, int N, hipStream_t st);
-// q, k rows are read from `qk` (leading dim qk_ld; q at column 0, k at column d), v from qkv
-int launch_attn_temporal_bwd(const float* qkv, const float* qk, long qk_ld, const float* dO, float* dqkv, int B, int T,
-                             int S, int d, int H, int Dh, float scale, hipStream_t st);
-int launch_attn_spatial_bwd_fused(const float* qkv, const float* qk, long qk_ld, const float* dO, float* dqkv, long n_bt, int S,
-                                  int d, int H, int Dh, float scale, hipStream_t st);
-int launch_qk_norm_fwd(const float* qkv, float* qkn, const float* nw, const float* nb, long M, int H, int Dh, int d,
-                       hipStream_t st);
-int launch_qk_norm_bwd(const float* qkv, float* dqkv, const float* nw, float* dnw, float* dnb, long M, int H, int Dh,
-                       int d, float beta, float* part, hipStream_t st);
 int launch_ce_fwd_bwd(const genie_cfg& c, float* logits, const int64_t* ids, const int64_t* labels, int B, double* sums,
                       hipStream_t st);
 int launch_embed_bwd(const genie_cfg& c, const float* dx, const int64_t* ids, int B, float* dpos, float* dmask,
@@ -371,6 +360,19 @@ int launch_gemm16_pp(int npl, int terms, int f16, const uint16_t* A, long lda, l
                      long planeW, const float* bias, const float* Rf, float* Cf, uint16_t* C16, long plane16, long ldc, int M,
                      int N, int K, int flags, float alpha, hipStream_t st, int batch, long strideA, long strideW, long strideC,
                      float qscale = 1.0f, int head_dim = 0, const float* qn_g = nullptr, const float* qn_b = nullptr);
+// kernels_attn_bwd.hip: the f32 attention backward of the training step (every precision's temporal backward; the spatial one of exact
+// and f16x3) and the qk-norm pair around it
+int launch_softmax_rows(float* P, long rows, int N, hipStream_t st);
+int launch_softmax_bwd_rows(const float* P, float* dP, long rows, int N, hipStream_t st);
+// q, k rows are read from `qk` (leading dim qk_ld; q at column 0, k at column d), v from qkv
+int launch_attn_temporal_bwd(const float* qkv, const float* qk, long qk_ld, const float* dO, float* dqkv, int B, int T,
+                             int S, int d, int H, int Dh, float scale, hipStream_t st);
+int launch_attn_spatial_bwd_fused(const float* qkv, const float* qk, long qk_ld, const float* dO, float* dqkv, long n_bt, int S,
+                                  int d, int H, int Dh, float scale, hipStream_t st);
+int launch_qk_norm_fwd(const float* qkv, float* qkn, const float* nw, const float* nb, long M, int H, int Dh, int d,
+                       hipStream_t st);
+int launch_qk_norm_bwd(const float* qkv, float* dqkv, const float* nw, float* dnw, float* dnb, long M, int H, int Dh,
+                       int d, float beta, float* part, hipStream_t st);
 // kernels_attn_bwd16.hip: spatial attention backward on the bf16 matrix cores (bf16 training precision)
 int launch_attn_spatial_bwd_bf16(const float* qkv, const float* qk, long qk_ld, const float* dO, float* dqkv, float* stats, long n_bt,
                                  int S, int d, int H, int Dh, float scale, hipStream_t st);

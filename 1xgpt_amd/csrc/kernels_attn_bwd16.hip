@@ -24,7 +24,6 @@ namespace genie {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ f32x16 mma_bf16(const s16x8& a, const s16x8& b, const f32x16& c) {

@@ -8,8 +8,6 @@
 
 namespace genie {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // N contiguous values of a temporal qkv row as f32: from an f32 buffer (exact, f16x3) or from a bf16 one (GENIE_PREC_BF16 keeps
 // its temporal qkv / KV cache in bf16: half the bytes of these HBM-bound kernels; the arithmetic below stays f32)
 template <int N>

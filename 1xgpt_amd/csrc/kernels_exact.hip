@@ -299,8 +299,6 @@ int launch_split_f16(const float* src, uint16_t* dst, size_t plane, size_t n, hi
 // LDS rows are padded to BK+4 floats (80 B): the 16-lane groups of ds_read_b128 then hit 16 distinct
 // 16-byte slots -> conflict-free.
 // ------------------------------------------------------------------------------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int GEMM_BM = 128, GEMM_BN = 128, GEMM_BK = 16, GEMM_LDS_LD = GEMM_BK + 4;
 
 __global__ __launch_bounds__(256) void gemm_f32_nt_kernel(const float* __restrict__ A, long lda, long strideA,
@@ -1240,7 +1238,6 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
 // The same for token-major logits with vf = 64 PER: a lane's PER consecutive logits arrive as 16-byte loads and stay in registers
 // for the three passes (sample_kernel issues PER 4-byte loads at a 4 PER-byte lane stride per pass: 16 lines touched per
 // instruction for 2 lines of data).  Same operations in the same order: bit-identical samples and confidences.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 template <int PER>
 __global__ __launch_bounds__(256) void sample_rows_kernel(const float* __restrict__ logits, long n_tok, long V, int vf, int nfac,
                                                           float temperature, const float* __restrict__ uniforms,

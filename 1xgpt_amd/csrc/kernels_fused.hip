@@ -43,7 +43,6 @@
 
 namespace genie {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -473,8 +472,6 @@ int launch_pack_temporal_fused(const float* qkv_w, const float* proj_w, uint16_t
 //   * 4 waves / 128 rows per block, 2 workgroups per CU.
 // Numerics = the bf16 contract (oracle BF16_MFMA): LayerNorm f32 -> bf16 operand, f32 accumulate + bias, erf-GELU in f32
 // (gelu_erf_fast, |error| 1.5e-7) -> bf16 operand, f32 accumulate + bias + f32 residual.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 __global__ void pack_mlp_fused_kernel(const float* __restrict__ fc1_w, const float* __restrict__ fc2_w, uint16_t* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;  // one thread per output value
     if (i >= 64 * 16 * 64 * 8) return;

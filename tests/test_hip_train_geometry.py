@@ -4,7 +4,7 @@ dtype=np.float64; the f32 restatement sits 6e-7 .. 1.4e-6 from it on these cases
 tests/test_hip_train.py (loss 1e-5 relative, accuracy 1e-7, every gradient tensor within GRAD_TOL = 1e-4 of its largest
 element), restated here, in exact AND in f16x3 ("f32-class gradients").
 
-What each case reaches (csrc/train_api.hip, csrc/kernels_train.hip); (H, d, T, S, B, qk_norm, use_mup, layers):
+What each case reaches (csrc/train_api.hip, csrc/kernels_train.hip, csrc/kernels_attn_bwd.hip); (H, d, T, S, B, qk_norm, use_mup, layers):
   s144       (1, 64, 2, 144, 1, F, F, 2)   Dh 64; spatial backward through materialised scores (every S != 256): five batched
                                            gemm_f32_gen_kernel launches (P and dP row-major x row-major, dV and dK k-major x
                                            k-major, dQ row-major x k-major) whose 128 x 128 tiles cover 128 + 16 rows, columns and

@@ -1,4 +1,4 @@
-"""Training at T = 32 and 64 frames: the tiled MFMA temporal attention backward (csrc/kernels_train.hip
+"""Training at T = 32 and 64 frames: the tiled MFMA temporal attention backward (csrc/kernels_attn_bwd.hip
 attn_temporal_bwd_tiled_kernel<head_dim, T / 16>) alone through genie_temporal_attention_backward, and whole trainer steps behind it.
 
 The kernel alone is compared with a float64 NumPy restatement of the formulas above attn_temporal_bwd_kernel on the same f32 inputs;

@@ -119,7 +119,9 @@ def test_cases_have_the_geometry_they_claim(name):
 
 def test_compiled_tiled_backward_has_no_scratch():
     """Every instantiation of attn_temporal_bwd_tiled_kernel (head_dim 32 / 64 x T 32 / 64) in the built library: no scratch, MFMAs
-    present, and no more registers than one wave per SIMD has (512: the kernel runs one wave per SIMD by design)."""
+    present, and no more registers than one wave per SIMD has (512: the kernel runs one wave per SIMD by design).  The T = 16 kernel
+    beside it (attn_temporal_bwd_mfma_kernel) keeps its occupancy: registers are allocated in blocks of 8, and 128 at head_dim 64 / 72
+    at head_dim 32 are 4 / 7 waves per SIMD."""
     if not (os.path.exists(f"{LLVM}/llvm-objdump") and os.path.exists(f"{LLVM}/clang-offload-bundler")):
         pytest.skip("no ROCm LLVM tools")
     lib_mod = pkg("_lib")
@@ -128,7 +130,11 @@ def test_compiled_tiled_backward_has_no_scratch():
     spec = importlib.util.spec_from_file_location("isa_audit", os.path.join(REPO, "tools", "isa_audit.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    rows = {r[0]: r for r in mod.audit(lib_mod.LIB_PATH, all_kernels=True) if "attn_temporal_bwd_tiled_kernel<" in r[0]}
+    audit = mod.audit(lib_mod.LIB_PATH, all_kernels=True)
+    rows = {r[0]: r for r in audit if "attn_temporal_bwd_tiled_kernel<" in r[0]}
+    for dh, allocated in ((64, 128), (32, 72)):
+        (row,) = [r for r in audit if f"attn_temporal_bwd_mfma_kernel<{dh}>" in r[0]]
+        assert row[6] == 0 and row[5] > 0 and (row[7] + 7) // 8 * 8 <= allocated, row
     assert len(rows) == 4, sorted(rows)
     for name, (_, _, _, _, _, mfma, scratch, vgpr) in rows.items():
         print(name, "mfma", mfma, "scratch", scratch, "vgpr", vgpr)

@@ -24,7 +24,8 @@ The training battery (--battery train; the default runs both, each in its own pa
 forward_backward, a second one with accumulate=True, one optimizer_step.  Recorded: the loss sums and every gradient tensor after each
 call, the flat parameters after the step, genie_train_activation_bytes / genie_train_workspace_bytes, and the kernel tables around the
 whole case (the trainer's weight packing included).  TRAIN_CASES are geometries tests/test_hip_train*.py pin, in all three precisions;
-s144 (T*S = 288) is refused by the 16-bit step and counts through its return code.
+s144 (T*S = 288) is refused by the 16-bit step and counts through its return code.  Then TEMPORAL_BWD_CASES: genie_temporal_attention_backward
+alone on seeded inputs, into a sentinel-filled output.
 
 The loops battery (--battery loops): the generate loops of csrc/generate_api.hip, called through ctypes on LOOP_MODELS.  Per model and
 clip count: genie_maskgit_generate_ex / _guided (3 steps; random, greedy and confidence unmasking at temperature 0 and under a
@@ -83,7 +84,19 @@ TRAIN_CASES = [("d64", 2, 64, 4, 16, 1, False, 2, 0),         # transposed-copy 
                ("d256qk", 8, 256, 4, 256, 2, True, 2, 0),     # every weight on TN (bf16); wgrad16 ns > 1 (f16x3)
                ("d384t16", 6, 384, 16, 64, 1, False, 1, 0),   # T = 16 MFMA temporal backward; TN and transposed-copy mixed in one layer
                ("s144", 1, 64, 2, 144, 1, False, 2, 0),       # exact only: the 16-bit step refuses T*S = 288
-               ("d64act", 2, 64, 4, 16, 1, False, 2, 5)]      # the _cond forward and the embed backward with a table gradient
+               ("d64act", 2, 64, 4, 16, 1, False, 2, 5),      # the _cond forward and the embed backward with a table gradient
+               # the tiled MFMA temporal backward at its other instantiations (d384t16 is T = 16, head_dim 64): one layer, one clip, S = 16
+               ("t16h32qk", 2, 64, 16, 16, 1, True, 1, 0),
+               ("t32h32", 2, 64, 32, 16, 1, False, 1, 0),
+               ("t32h64", 1, 64, 32, 16, 1, False, 1, 0),
+               ("t64h32", 2, 64, 64, 16, 1, False, 1, 0),
+               ("t64h64", 1, 64, 64, 16, 1, False, 1, 0)]
+# ... and genie_temporal_attention_backward alone: (T, head_dim, clips, S, heads, qk_ld / d_model).  B S H = 12 fills its workgroups of 4 waves,
+# 3 and 5 leave idle waves in the last one; qk_ld = 3 d: qk is qkv itself, 2 d: a buffer of its own.  T = 8 and head_dim 128 are the
+# scalar kernel's; the last two are refused (E_SHAPE, E_UNSUPPORTED) and must leave the output as it was.
+TEMPORAL_BWD_CASES = ([(T, Dh, *g) for T in (16, 32, 64) for Dh in (32, 64) for g in ((2, 3, 2, 3), (1, 3, 1, 2), (1, 5, 1, 3))]
+                      + [(8, 32, 2, 3, 2, 3), (8, 64, 1, 5, 1, 2), (16, 128, 1, 3, 1, 3), (16, 128, 1, 5, 1, 2), (4, 32, 2, 3, 2, 2),
+                         (32, 128, 1, 3, 1, 3), (8, 16, 1, 3, 1, 3)])
 TRAIN_WATCHED = ["gemm_f32_gen_kernel", "attn_spatial_bwd_fused_kernel", "wgrad16_tn_kernel", "attn_bwd16_"]
 # loops battery: (name, d_model, heads, T, S, precisions, clip counts), a LayerNorm and a qk-norm model each.  d64: the generic kernels --
 # every merged commit is refused and the loops fall back, the context runs frame by frame; d256 / d512 in f16x3: the fragment-order
@@ -166,6 +179,20 @@ def child(out_path, battery):
                 record[f"{name}/{prec}"]["sizes"] = list(sizes)
                 print(f"{name}/{prec} activation / workspace bytes {sizes}", flush=True)
                 torch.cuda.empty_cache()
+        for T, Dh, B, S, H, ldm in TEMPORAL_BWD_CASES:
+            d = H * Dh
+            gen = torch.Generator().manual_seed(1000 * T + Dh + B * S * H)
+            qkv = torch.randn(B, T, S, 3 * d, generator=gen).cuda()
+            qk = qkv if ldm == 3 else torch.randn(B, T, S, 2 * d, generator=gen).cuda()
+            d_out = torch.randn(B, T, S, d, generator=gen).cuda()
+
+            def bwd():
+                d_qkv = torch.full((B, T, S, 3 * d), 12345.0, device="cuda")   # an element the kernel leaves unwritten shows in the digest
+                rc = lib.genie_temporal_attention_backward(qkv.data_ptr(), qk.data_ptr(), ldm * d, d_out.data_ptr(), d_qkv.data_ptr(), B, T, S,
+                                                           d, H, Dh, Dh ** -0.5, torch.cuda.current_stream().cuda_stream)
+                assert bool(torch.isfinite(d_qkv).all())
+                return rc, {"d_qkv": d_qkv}
+            record_case(f"temporal_bwd/T{T}/h{Dh}/B{B}S{S}H{H}/ld{ldm}d", bwd, keep_refused=True)
         with open(out_path, "w") as f:
             json.dump(record, f)
         return
