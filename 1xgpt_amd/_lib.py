@@ -257,6 +257,14 @@ for _n in ("genie_train_forward", "genie_train_backward_layer"):
     SIGNATURES[_n + "_drop"] = (SIGNATURES[_n + "_ex"][0], SIGNATURES[_n + "_ex"][1] + [C.POINTER(Dropout)])
 del _n
 
+# EMA of the weights: genie_adamw_step's arguments with `ema` behind exp_avg_sq and one_minus_decay in front of the stream; the EMA
+# line alone, (ema, params, n, one_minus_decay, stream); the in-place exchange, (a, b, n, stream)
+_a = SIGNATURES["genie_adamw_step"][1]
+SIGNATURES["genie_adamw_ema_step"] = (C.c_int, _a[:4] + [c_ptr] + _a[4:-1] + [C.c_float, c_ptr])
+del _a
+SIGNATURES["genie_ema_update"] = (C.c_int, [c_ptr, c_ptr, C.c_size_t, C.c_float, c_ptr])
+SIGNATURES["genie_swap_f32"] = (C.c_int, [c_ptr, c_ptr, C.c_size_t, c_ptr])
+
 _lib = None
 
 

@@ -447,6 +447,11 @@ int temporal_attention(const genie_cfg& c, const genie_attn_weights& aw, const B
 
 int launch_adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
                  float weight_decay, int step, float grad_mult, const double* sumsq, float max_norm, hipStream_t st);
+// EMA of the weights (kernels_train.hip): launch_adamw's update and ema -= omd * (ema - p_new) in one pass; that line alone; a <-> b
+int launch_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr, float beta1, float beta2, float eps,
+                     float weight_decay, int step, float grad_mult, const double* sumsq, float max_norm, float omd, hipStream_t st);
+int launch_ema_update(float* ema, const float* p, size_t n, float omd, hipStream_t st);
+int launch_swap_f32(float* a, float* b, size_t n, hipStream_t st);
 
 // api.hip: the host helpers its entry points share with the generate loops (generate_api.hip)
 Workspace carve(const genie_cfg& c, int B, void* base);   // base == NULL: sizes only

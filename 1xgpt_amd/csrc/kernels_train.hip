@@ -722,34 +722,161 @@ int launch_sumsq(const float* x, size_t n, double* out, double* scratch, hipStre
     return GENIE_OK;
 }
 
-__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                             float* __restrict__ v, size_t n, float lr, float beta1, float beta2, float eps, float decay,
-                             float step_size, float inv_sqrt_bc2, float grad_mult, const double* __restrict__ sumsq,
-                             float max_norm) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+// The AdamW update of one element, stated once for adamw_kernel and adamw_ema_kernel (the build does not contract: -ffp-contract=off).
+struct AdamwScalars {
+    float beta1, beta2, eps, decay, step_size, inv_sqrt_bc2;
+};
+// grad_mult times the clip coefficient of clip_grad_norm_: min(1, max_norm / (total_norm + 1e-6))
+__device__ __forceinline__ float adamw_coef(float grad_mult, const double* __restrict__ sumsq, float max_norm) {
     float coef = grad_mult;
-    if (sumsq && max_norm > 0.f) {  // clip_grad_norm_: coef = min(1, max_norm / (total_norm + 1e-6))
+    if (sumsq && max_norm > 0.f) {
         const float tn = (float)sqrt(*sumsq) * grad_mult;
         coef *= fminf(1.0f, max_norm / (tn + 1e-6f));
     }
-    const float gi = g[i] * coef;
-    float pi = p[i] * decay;  // decoupled weight decay: p *= 1 - lr*wd
-    const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
-    const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
+    return coef;
+}
+__device__ __forceinline__ void adamw_element(float& p, float g, float& m, float& v, float coef, const AdamwScalars& a) {
+    const float gi = g * coef;
+    const float pi = p * a.decay;  // decoupled weight decay: p *= 1 - lr*wd
+    const float mi = a.beta1 * m + (1.0f - a.beta1) * gi;
+    const float vi = a.beta2 * v + (1.0f - a.beta2) * gi * gi;
+    m = mi;
+    v = vi;
+    const float denom = sqrtf(vi) * a.inv_sqrt_bc2 + a.eps;
+    p = pi - a.step_size * (mi / denom);
+}
+// LitEma.forward's line (include/genie_hip.h, "EMA of the weights"): three f32 operations, each rounded on its own
+__device__ __forceinline__ float ema_element(float e, float p, float omd) {
+    return __fsub_rn(e, __fmul_rn(omd, __fsub_rn(e, p)));
+}
+
+__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                             float* __restrict__ v, size_t n, AdamwScalars a, float grad_mult, const double* __restrict__ sumsq,
+                             float max_norm) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float pi = p[i], mi = m[i], vi = v[i];
+    adamw_element(pi, g[i], mi, vi, adamw_coef(grad_mult, sumsq, max_norm), a);
     m[i] = mi;
     v[i] = vi;
-    const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
-    p[i] = pi - step_size * (mi / denom);
+    p[i] = pi;
+}
+static AdamwScalars adamw_scalars(float lr, float beta1, float beta2, float eps, float weight_decay, int step) {
+    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    return {beta1, beta2, eps, (float)(1.0 - (double)lr * weight_decay), (float)(lr / bc1), (float)(1.0 / sqrt(bc2))};
 }
 int launch_adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
                  float weight_decay, int step, float grad_mult, const double* sumsq, float max_norm, hipStream_t st) {
     if (!n) return GENIE_OK;
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    adamw_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(p, g, m, v, n, lr, beta1, beta2, eps,
-                                                             (float)(1.0 - (double)lr * weight_decay), (float)(lr / bc1),
-                                                             (float)(1.0 / sqrt(bc2)), grad_mult, sumsq, max_norm);
+    adamw_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(p, g, m, v, n, adamw_scalars(lr, beta1, beta2, eps, weight_decay, step),
+                                                             grad_mult, sumsq, max_norm);
     GENIE_LAUNCH_CHECK("adamw");
+    return GENIE_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// EMA of the weights: three streaming kernels of one shape.  Every thread walks float4 groups [0, n4) with a grid stride, 16 bytes per
+// load and store, then the elements [4 n4, n) one at a time; the host gives n4 = n / 4 when every base pointer is 16-byte aligned and
+// n4 = 0 (all of the range on the one-element path) when one is not.  The grid is capped at STREAM_MAX_BLOCKS workgroups of 256.
+// No LDS, no atomics: the same bytes run to run.
+// ------------------------------------------------------------------------------------------------
+constexpr unsigned STREAM_MAX_BLOCKS = 2048;
+struct StreamShape {
+    size_t n4;
+    unsigned blocks;
+};
+template <typename... P>
+static StreamShape stream_shape(size_t n, const P*... base) {
+    const bool aligned = (((uintptr_t)base | ...) & 15) == 0;
+    const size_t n4 = aligned ? n / 4 : 0;
+    const size_t items = n4 > n - 4 * n4 ? n4 : n - 4 * n4;   // the longer of the two loops
+    const size_t blocks = (items + 255) / 256;
+    return {n4, (unsigned)(blocks < STREAM_MAX_BLOCKS ? (blocks ? blocks : 1) : STREAM_MAX_BLOCKS)};
+}
+
+__global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, float* __restrict__ ema, size_t n, size_t n4,
+                                                        AdamwScalars a, float grad_mult, const double* __restrict__ sumsq,
+                                                        float max_norm, float omd) {
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    const float coef = adamw_coef(grad_mult, sumsq, max_norm);
+    for (size_t i = tid; i < n4; i += stride) {
+        float4 p4 = reinterpret_cast<const float4*>(p)[i], m4 = reinterpret_cast<const float4*>(m)[i];
+        float4 v4 = reinterpret_cast<const float4*>(v)[i], e4 = reinterpret_cast<const float4*>(ema)[i];
+        const float4 g4 = reinterpret_cast<const float4*>(g)[i];
+        adamw_element(p4.x, g4.x, m4.x, v4.x, coef, a);
+        adamw_element(p4.y, g4.y, m4.y, v4.y, coef, a);
+        adamw_element(p4.z, g4.z, m4.z, v4.z, coef, a);
+        adamw_element(p4.w, g4.w, m4.w, v4.w, coef, a);
+        e4.x = ema_element(e4.x, p4.x, omd);
+        e4.y = ema_element(e4.y, p4.y, omd);
+        e4.z = ema_element(e4.z, p4.z, omd);
+        e4.w = ema_element(e4.w, p4.w, omd);
+        reinterpret_cast<float4*>(m)[i] = m4;
+        reinterpret_cast<float4*>(v)[i] = v4;
+        reinterpret_cast<float4*>(p)[i] = p4;
+        reinterpret_cast<float4*>(ema)[i] = e4;
+    }
+    for (size_t i = 4 * n4 + tid; i < n; i += stride) {
+        float pi = p[i], mi = m[i], vi = v[i];
+        adamw_element(pi, g[i], mi, vi, coef, a);
+        m[i] = mi;
+        v[i] = vi;
+        p[i] = pi;
+        ema[i] = ema_element(ema[i], pi, omd);
+    }
+}
+int launch_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr, float beta1, float beta2, float eps,
+                     float weight_decay, int step, float grad_mult, const double* sumsq, float max_norm, float omd, hipStream_t st) {
+    if (!n) return GENIE_OK;
+    const StreamShape s = stream_shape(n, p, g, m, v, ema);
+    adamw_ema_kernel<<<s.blocks, 256, 0, st>>>(p, g, m, v, ema, n, s.n4, adamw_scalars(lr, beta1, beta2, eps, weight_decay, step),
+                                               grad_mult, sumsq, max_norm, omd);
+    GENIE_LAUNCH_CHECK("adamw_ema");
+    return GENIE_OK;
+}
+
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ p, size_t n, size_t n4,
+                                                         float omd) {
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    for (size_t i = tid; i < n4; i += stride) {
+        float4 e4 = reinterpret_cast<const float4*>(ema)[i];
+        const float4 p4 = reinterpret_cast<const float4*>(p)[i];
+        e4.x = ema_element(e4.x, p4.x, omd);
+        e4.y = ema_element(e4.y, p4.y, omd);
+        e4.z = ema_element(e4.z, p4.z, omd);
+        e4.w = ema_element(e4.w, p4.w, omd);
+        reinterpret_cast<float4*>(ema)[i] = e4;
+    }
+    for (size_t i = 4 * n4 + tid; i < n; i += stride) ema[i] = ema_element(ema[i], p[i], omd);
+}
+int launch_ema_update(float* ema, const float* p, size_t n, float omd, hipStream_t st) {
+    if (!n) return GENIE_OK;
+    const StreamShape s = stream_shape(n, ema, p);
+    ema_update_kernel<<<s.blocks, 256, 0, st>>>(ema, p, n, s.n4, omd);
+    GENIE_LAUNCH_CHECK("ema_update");
+    return GENIE_OK;
+}
+
+// a <-> b elementwise (the ranges do not overlap: checked by the entry point)
+__global__ __launch_bounds__(256) void swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, size_t n, size_t n4) {
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    for (size_t i = tid; i < n4; i += stride) {
+        const float4 a4 = reinterpret_cast<const float4*>(a)[i], b4 = reinterpret_cast<const float4*>(b)[i];
+        reinterpret_cast<float4*>(a)[i] = b4;
+        reinterpret_cast<float4*>(b)[i] = a4;
+    }
+    for (size_t i = 4 * n4 + tid; i < n; i += stride) {
+        const float ai = a[i], bi = b[i];
+        a[i] = bi;
+        b[i] = ai;
+    }
+}
+int launch_swap_f32(float* a, float* b, size_t n, hipStream_t st) {
+    if (!n) return GENIE_OK;
+    const StreamShape s = stream_shape(n, a, b);
+    swap_f32_kernel<<<s.blocks, 256, 0, st>>>(a, b, n, s.n4);
+    GENIE_LAUNCH_CHECK("swap_f32");
     return GENIE_OK;
 }
 

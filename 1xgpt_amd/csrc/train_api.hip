@@ -845,4 +845,29 @@ int genie_adamw_step(float* params, const float* grads, float* exp_avg, float* e
                         grad_sumsq, max_grad_norm, (hipStream_t)stream);
 }
 
+static bool omd_ok(float omd) { return omd >= 0.0f && omd <= 1.0f; }   // false for NaN
+
+int genie_adamw_ema_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, size_t n, float lr,
+                         float beta1, float beta2, float eps, float weight_decay, int step, float grad_mult, const double* grad_sumsq,
+                         float max_grad_norm, float ema_one_minus_decay, void* stream) {
+    GENIE_CHECK_ARG((params && grads && exp_avg && exp_avg_sq && ema) || !n, "genie_adamw_ema_step: NULL argument");
+    GENIE_CHECK_ARG(step >= 1, "genie_adamw_ema_step: step counts from 1");
+    GENIE_CHECK_ARG(omd_ok(ema_one_minus_decay), "genie_adamw_ema_step: ema_one_minus_decay %g is not in [0, 1]", (double)ema_one_minus_decay);
+    return launch_adamw_ema(params, grads, exp_avg, exp_avg_sq, ema, n, lr, beta1, beta2, eps, weight_decay, step, grad_mult,
+                            grad_sumsq, max_grad_norm, ema_one_minus_decay, (hipStream_t)stream);
+}
+
+int genie_ema_update(float* ema, const float* params, size_t n, float one_minus_decay, void* stream) {
+    GENIE_CHECK_ARG((ema && params) || !n, "genie_ema_update: NULL argument");
+    GENIE_CHECK_ARG(omd_ok(one_minus_decay), "genie_ema_update: one_minus_decay %g is not in [0, 1]", (double)one_minus_decay);
+    return launch_ema_update(ema, params, n, one_minus_decay, (hipStream_t)stream);
+}
+
+int genie_swap_f32(float* a, float* b, size_t n, void* stream) {
+    GENIE_CHECK_ARG((a && b) || !n, "genie_swap_f32: NULL argument");
+    const uintptr_t ua = (uintptr_t)a, ub = (uintptr_t)b;
+    GENIE_CHECK_ARG(!n || ua + 4 * n <= ub || ub + 4 * n <= ua, "genie_swap_f32: the two ranges overlap");
+    return launch_swap_f32(a, b, n, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -16,10 +16,17 @@ Design (MI355X-first):
   * precisions: the model's (`exact` f32 MFMA; `f16x3` split-f16 MFMA with f32-class gradients; `bf16` = what
     accelerate's bf16 autocast computes); parameters, gradients and Adam moments are f32 in all of them;
   * GPU only: there is no CPU fallback for the model math (the collator in data.py is device-agnostic data prep).
+  * EMA of the weights (`ema_decay`; the reference's mechanism is magvit2/modules/ema.py, LitEma): one more flat f32 buffer that the AdamW
+    launch itself updates (genie_adamw_ema_step: one more read and write per element, no second pass); `ema_scope()` swaps it
+    with the parameters in place to evaluate, sample or save with the averaged weights.
 MuAdamW (--mu_transfer, train.py:439; third-party mup fork) is not built.
 """
+import contextlib
 import ctypes as C
 import math
+import warnings
+
+import numpy as np
 
 import torch
 import torch.distributed as dist
@@ -52,6 +59,25 @@ def decays(name: str) -> bool:
     parameter is called layer_norm.* (they are norm1/norm2/norm), so LayerNorm weights DO decay, as in the reference.
     The learned null row of a model conditioned on action vectors (no reference counterpart) is a bias-like row and does not decay."""
     return not ("bias" in name or "layer_norm.weight" in name or name == "action_null")
+
+
+# ------------------------------------------------------------------ EMA schedule (magvit2/modules/ema.py, LitEma.forward)
+def ema_decay_at(decay, n, warmup=False):
+    """d_n, the f32 decay of EMA update n = 1, 2, ... (include/genie_hip.h, "EMA of the weights"): float32(decay), or with `warmup`
+    (LitEma's use_num_upates) min(float32(decay), float32((1 + n) / (10 + n))).  Raises ValueError unless 0 <= decay <= 1."""
+    if not 0.0 <= decay <= 1.0:   # (False for NaN)
+        raise ValueError(f"ema_decay must be in [0, 1], got {decay!r}")
+    if n < 1:
+        raise ValueError(f"EMA updates count from 1, got {n!r}")
+    d = np.float32(decay)
+    if warmup:
+        d = min(d, np.float32(1 + n) / np.float32(10 + n))
+    return float(d)
+
+
+def ema_one_minus_decay(decay, n, warmup=False):
+    """omd = float32(1) - d_n, the scalar the kernels take."""
+    return float(np.float32(1) - np.float32(ema_decay_at(decay, n, warmup)))
 
 
 # ------------------------------------------------------------------ pointer tables
@@ -173,8 +199,15 @@ def bucket_bounds(segments, target_elems):
 
 class GenieTrainer:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0,
-                 gradient_accumulation_steps=1, lr_lambda=None, bucket_mb=64, group=None, recompute=False, dropout_seed=0):
-        """dropout_seed: with config.mlp_drop > 0 the step trains with the reference's MLP dropout (st_transformer.py:22-25).  The masks
+                 gradient_accumulation_steps=1, lr_lambda=None, bucket_mb=64, group=None, recompute=False, dropout_seed=0,
+                 ema_decay=None, ema_warmup=False):
+        """ema_decay: keep an exponential moving average of the weights in `self.ema`, a flat f32 buffer with the layout of `self.params`
+        that starts as a copy of it (after the rank-0 broadcast: replicas hold identical averages, nothing is communicated).  Every
+        optimizer step -- not every micro-batch -- moves it by ema = ema - omd * (ema - p_new) inside the AdamW launch, with
+        omd = 1 - ema_decay_at(ema_decay, ema_updates + 1, ema_warmup); ema_warmup is LitEma's use_num_upates, min(decay, (1 + n) / (10 + n)).
+        `ema_scope()` runs the model on the averaged weights, `ema_state_dict()` / `save_ema_pretrained(dir)` export them, `state_dict()`
+        carries them.  None (the default): no buffer, and exactly the launches of a trainer without the feature.
+        dropout_seed: with config.mlp_drop > 0 the step trains with the reference's MLP dropout (st_transformer.py:22-25).  The masks
         are a pure function of (dropout_seed + rank, micro-batch counter, layer, site, element) (include/genie_hip.h, "MLP dropout"): nothing
         is stored, and a run resumed from `state_dict` draws the masks it would have drawn.  mlp_drop = 0 is the step without dropout.
         recompute: keep only each layer's input from the forward and rebuild the layer's other activations in front of its
@@ -195,6 +228,10 @@ class GenieTrainer:
         if not 0.0 <= self.mlp_drop < 1.0:
             raise ValueError(f"config.mlp_drop must be in [0, 1), got {self.mlp_drop!r}")
         self.dropout_seed, self._drop_call = int(dropout_seed), 0   # the counter advances once per forward_backward
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        if self.ema_decay is not None:
+            ema_decay_at(self.ema_decay, 1, self.ema_warmup)   # ValueError outside [0, 1]
 
         named = dict(model.named_parameters())
         self.order = ready_order(self.config, named.keys())
@@ -219,6 +256,9 @@ class GenieTrainer:
         # all-reduces gradients, so replicas that start apart would stay apart
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
             dist.broadcast(self.params, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
+        # the average starts from the (broadcast) parameters; padding is zero in both and stays zero
+        self.ema = self.params.clone() if self.ema_decay is not None else None
+        self.ema_updates, self._in_ema_scope = 0, False
         model.refresh_weights()
         self.p_views = {n: self.params[offs[n][0]:offs[n][1]] for n in self.order}
         self.g_views = {n: self.grads[offs[n][0]:offs[n][1]].view(named[n].shape) for n in self.order}
@@ -313,6 +353,7 @@ class GenieTrainer:
         the gradients of action_proj (genie_action_rows_backward, one launch) and of action_null.
         action_drop: (B,) bool with action_vectors (action dropout, data.maskgit_collate): a dropped clip's frames read the null row, so
         their projected rows get a zero gradient and the null row theirs."""
+        self._not_in_ema_scope("forward_backward")
         if not (input_ids.is_cuda and labels.is_cuda):
             raise RuntimeError("1xgpt_amd runs on the GPU only (no CPU fallback): move the batch to cuda")
         ids = input_ids.to(torch.int64).contiguous()
@@ -390,6 +431,7 @@ class GenieTrainer:
         return self.base_lr * self.lr_lambda(self.completed_steps)
 
     def optimizer_step(self):
+        self._not_in_ema_scope("optimizer_step")
         world = self.reducer.world
         mult = 1.0 / (world * self.accum)
         ss = self.grad_sumsq()
@@ -397,14 +439,22 @@ class GenieTrainer:
         clip = self.max_grad_norm if self.max_grad_norm is not None else 0.0
         step = self.completed_steps + 1
         st = self._stream()
+        omd = None if self.ema is None else ema_one_minus_decay(self.ema_decay, self.ema_updates + 1, self.ema_warmup)
         for lo, hi, dk in self.adam_runs:
             off = lo * 4
-            _lib.check(self.lib.genie_adamw_step(
-                self.params.data_ptr() + off, self.grads.data_ptr() + off, self.exp_avg.data_ptr() + off,
-                self.exp_avg_sq.data_ptr() + off, hi - lo, lr, self.betas[0], self.betas[1], self.eps,
-                self.weight_decay if dk else 0.0, step, mult, ss.data_ptr() if clip > 0 else None, clip, st),
-                "genie_adamw_step")
+            scalars = (hi - lo, lr, self.betas[0], self.betas[1], self.eps, self.weight_decay if dk else 0.0, step, mult,
+                       ss.data_ptr() if clip > 0 else None, clip)
+            if omd is None:
+                _lib.check(self.lib.genie_adamw_step(
+                    self.params.data_ptr() + off, self.grads.data_ptr() + off, self.exp_avg.data_ptr() + off,
+                    self.exp_avg_sq.data_ptr() + off, *scalars, st), "genie_adamw_step")
+            else:   # the same update and the average's, in one pass over the run
+                _lib.check(self.lib.genie_adamw_ema_step(
+                    self.params.data_ptr() + off, self.grads.data_ptr() + off, self.exp_avg.data_ptr() + off,
+                    self.exp_avg_sq.data_ptr() + off, self.ema.data_ptr() + off, *scalars, omd, st), "genie_adamw_ema_step")
         self.completed_steps += 1
+        if omd is not None:
+            self.ema_updates += 1
         self.pack_weights()
         self.model.refresh_weights()  # the module's own 16-bit copies (inference entry points) are stale
         return torch.sqrt(ss[0]) * mult, lr
@@ -412,6 +462,7 @@ class GenieTrainer:
     def train_step(self, batch):
         """One micro-batch of the reference loop (train.py:604-633); the optimizer runs every
         `gradient_accumulation_steps` calls.  Returns device scalars (no host sync)."""
+        self._not_in_ema_scope("train_step")
         is_update = (self._micro + 1) % self.accum == 0
         loss, acc = self.forward_backward(batch["input_ids"], batch["labels"], accumulate=self._micro % self.accum != 0,
                                           reduce=is_update and self.accum == 1, action_ids=batch.get("action_ids"),
@@ -429,31 +480,88 @@ class GenieTrainer:
         """{state-dict name: gradient view} (shapes of the parameters)."""
         return self.g_views
 
+    # ------------------------------------------------------------------ EMA of the weights
+    def _not_in_ema_scope(self, what):
+        if self._in_ema_scope:
+            raise RuntimeError(f"GenieTrainer.{what} inside ema_scope(): the parameters hold the averaged weights")
+
+    def _need_ema(self, what):
+        if self.ema is None:
+            raise RuntimeError(f"GenieTrainer.{what} needs a trainer built with ema_decay")
+
+    def _swap_ema(self):
+        _lib.check(self.lib.genie_swap_f32(self.params.data_ptr(), self.ema.data_ptr(), self.n_flat, self._stream()), "genie_swap_f32")
+        self.sync_external_weights()
+
+    @contextlib.contextmanager
+    def ema_scope(self):
+        """Run `self.model` on the averaged weights: the flat parameter buffer and `self.ema` are exchanged in place (one launch) and the
+        16-bit operand copies repacked, so every entry point of the model -- forward, generate, save_pretrained -- sees the average, in
+        every precision; on exit (also when the body raises) the same exchange and repack put the raw weights back, bit for bit.
+        Training calls inside the scope raise RuntimeError; scopes do not nest."""
+        self._need_ema("ema_scope")
+        self._not_in_ema_scope("ema_scope")
+        self._swap_ema()
+        self._in_ema_scope = True
+        try:
+            yield self.model
+        finally:
+            self._in_ema_scope = False
+            self._swap_ema()
+
+    def ema_state_dict(self):
+        """{state-dict name: clone of the averaged weights} in the parameters' shapes."""
+        self._need_ema("ema_state_dict")
+        avg = self.params if self._in_ema_scope else self.ema   # inside the scope the two buffers have changed places
+        named = dict(self.model.named_parameters())
+        return {n: avg[self.offsets[n][0]:self.offsets[n][1]].view(named[n].shape).clone() for n in self.order}
+
+    def save_ema_pretrained(self, save_directory):
+        """`model.save_pretrained(save_directory)` with the averaged weights: STMaskGIT.from_pretrained loads it as an ordinary checkpoint."""
+        self._need_ema("save_ema_pretrained")
+        if self._in_ema_scope:
+            self.model.save_pretrained(save_directory)
+        else:
+            with self.ema_scope():
+                self.model.save_pretrained(save_directory)
+
     # ------------------------------------------------------------------ optimizer checkpoint (train.py:560-590 resume)
     def state_dict(self):
         """Optimizer state in torch.optim.AdamW's vocabulary, keyed by parameter NAME (the model's own weights are
         saved by `model.save_pretrained` / `state_dict`)."""
+        self._not_in_ema_scope("state_dict")
         named = dict(self.model.named_parameters())
         st = {}
         for n in self.order:
             lo, hi = self.offsets[n]
             st[n] = {"exp_avg": self.exp_avg[lo:hi].view(named[n].shape).clone(),
                      "exp_avg_sq": self.exp_avg_sq[lo:hi].view(named[n].shape).clone()}
-        return {"state": st, "completed_steps": self.completed_steps, "micro_step": self._micro,
-                "dropout": {"seed": self.dropout_seed, "call": self._drop_call},
-                "hyper": {"lr": self.base_lr, "betas": tuple(self.betas), "eps": self.eps,
-                          "weight_decay": self.weight_decay, "max_grad_norm": self.max_grad_norm,
-                          "gradient_accumulation_steps": self.accum, "recompute": bool(self.recompute)}}
+        out = {"state": st, "completed_steps": self.completed_steps, "micro_step": self._micro,
+               "dropout": {"seed": self.dropout_seed, "call": self._drop_call},
+               "hyper": {"lr": self.base_lr, "betas": tuple(self.betas), "eps": self.eps,
+                         "weight_decay": self.weight_decay, "max_grad_norm": self.max_grad_norm,
+                         "gradient_accumulation_steps": self.accum, "recompute": bool(self.recompute)}}
+        if self.ema is not None:
+            out["ema"] = {"state": self.ema_state_dict(), "updates": self.ema_updates, "decay": self.ema_decay,
+                          "warmup": self.ema_warmup}
+        return out
 
     def load_state_dict(self, sd):
         """Inverse of `state_dict` (moments, step counters); hyper-parameters stay those of this trainer (a warning
-        names every saved value that differs)."""
+        names every saved value that differs).  The average: a saved "ema" entry restores `self.ema` and `ema_updates`; a state without
+        one loaded into a trainer with EMA restarts the average from the current parameters, and a saved average loaded into a trainer
+        without EMA is ignored -- each with a warning."""
+        self._not_in_ema_scope("load_state_dict")
+        saved_ema = sd.get("ema")
         mine = {"lr": self.base_lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
                 "max_grad_norm": self.max_grad_norm, "gradient_accumulation_steps": self.accum}
         diff = {k: (v, mine[k]) for k, v in (sd.get("hyper") or {}).items()
                 if k in mine and (tuple(v) if isinstance(v, (list, tuple)) else v) != mine[k]}
+        if saved_ema is not None and self.ema is not None:
+            for k, cur in (("decay", self.ema_decay), ("warmup", self.ema_warmup)):
+                if saved_ema.get(k) != cur:
+                    diff["ema_" + k] = (saved_ema.get(k), cur)
         if diff:
-            import warnings
             warnings.warn("GenieTrainer.load_state_dict: resuming with different hyper-parameters (saved, current): "
                           + ", ".join(f"{k}={a}->{b}" for k, (a, b) in diff.items()))
         for n in self.order:
@@ -464,4 +572,17 @@ class GenieTrainer:
         self._micro = int(sd.get("micro_step", 0))
         if "dropout" in sd:   # the masks of the resumed run are those the saved one would have drawn next
             self.dropout_seed, self._drop_call = int(sd["dropout"]["seed"]), int(sd["dropout"]["call"])
+        if self.ema is not None:
+            if saved_ema is None:
+                warnings.warn("GenieTrainer.load_state_dict: the saved state has no EMA of the weights: the average restarts from the "
+                              "current parameters")
+                self.ema.copy_(self.params)
+                self.ema_updates = 0
+            else:
+                for n in self.order:
+                    lo, hi = self.offsets[n]
+                    self.ema[lo:hi].copy_(saved_ema["state"][n].reshape(-1))
+                self.ema_updates = int(saved_ema["updates"])
+        elif saved_ema is not None:
+            warnings.warn("GenieTrainer.load_state_dict: the saved state carries an EMA of the weights, this trainer keeps none: ignored")
         self.pack_weights()

@@ -878,6 +878,29 @@ int genie_adamw_step(float* params, const float* grads, float* exp_avg, float* e
                      float beta2, float eps, float weight_decay, int step, float grad_mult, const double* grad_sumsq,
                      float max_grad_norm, void* stream);
 
+/* EMA of the weights (additions; nothing above changes).  Reference: magvit2/modules/ema.py, LitEma.forward.  The averaged buffer
+ * `ema` has the layout of `params` (same offsets; padding that is zero stays zero: 0 - omd * (0 - 0)) and starts as a copy of it.
+ * After the optimizer has produced an element's p_new:
+ *     ema = ema - (omd * (ema - p_new))
+ * three f32 operations, each rounded on its own, no FMA contraction -- LitEma's `shadow.sub_(one_minus_decay * (shadow - param))`
+ * bit for bit, and restated in NumPy f32 by tests/ema_model.py.  omd is the CALLER's float: omd = float32(1) - d_n with
+ *     d_n = float32(decay)                                        without warm-up,
+ *     d_n = min(float32(decay), float32((1 + n) / (10 + n)))      with it (LitEma's use_num_upates),
+ * n = 1, 2, ... the number of EMA updates including this one (1xgpt_amd/train.py, ema_decay_at).
+ * genie_adamw_ema_step: genie_adamw_step (same arguments, the same bits in params / exp_avg / exp_avg_sq) and that line on `ema` in
+ * ONE pass over the range -- 36 bytes per element against 28 + 12 for the two calls.  genie_ema_update: the line alone, for a caller
+ * with another optimizer.  genie_swap_f32: a[i] <-> b[i] in place (evaluate with the averaged weights: swap params and ema, repack
+ * the 16-bit copies, evaluate, swap back -- exact by construction).  All three: one launch, 16-byte loads and stores when every
+ * pointer is 16-byte aligned (any n; the n % 4 tail and a misaligned pointer take a one-element path), no atomics: the same bytes
+ * run to run.  `ema` must not overlap the other ranges.  Refused with GENIE_E_ARG before the device or the stream is touched, outputs
+ * as they were: a NULL pointer with n > 0; step < 1; one_minus_decay < 0, > 1 or not finite; overlapping a / b.  n == 0: GENIE_OK,
+ * nothing enqueued. */
+int genie_adamw_ema_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, size_t n, float lr,
+                         float beta1, float beta2, float eps, float weight_decay, int step, float grad_mult,
+                         const double* grad_sumsq, float max_grad_norm, float ema_one_minus_decay, void* stream);
+int genie_ema_update(float* ema, const float* params, size_t n, float one_minus_decay, void* stream);
+int genie_swap_f32(float* a, float* b, size_t n, void* stream);
+
 /* Continuous per-frame actions (ABI 3 addition; nothing above changes).  A model conditioned on float action vectors of A values per
  * frame projects them, once per call, into the rows that genie_frame_cond addresses: the caller builds a table of one learned "no
  * action" row plus one projected row per frame of the call, points cond->table at it and cond->ids at "row of frame (b, t)", and every

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Time the HIP training step (forward + backward + clip + AdamW) on synthetic clips.
-   python tools/bench_train.py --config c138 --batch 8 --steps 3"""
+   python tools/bench_train.py --config c138 --batch 8 --steps 3
+   python tools/bench_train.py --config c138 --precision bf16 --batch 8 --breakdown --ema_decay 0.999 [--ema_unfused]"""
 import argparse
 import importlib
 import os
@@ -11,6 +12,20 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 pkg = lambda n: importlib.import_module("1xgpt_amd" + ("." + n if n else ""))  # noqa: E731
+
+
+def unfuse_ema(tr, lib, _lib):
+    """Replace the trainer's fused AdamW + EMA launch by the two-pass pair it stands for (same bits; a yardstick for the fusion)."""
+    class Unfused:
+        def __getattr__(self, name):
+            return getattr(lib, name)
+
+        @staticmethod
+        def genie_adamw_ema_step(p, g, m, v, ema, n, *rest):
+            *adam, omd, st = rest
+            rc = lib.genie_adamw_step(p, g, m, v, n, *adam, st)
+            return rc or lib.genie_ema_update(ema, p, n, omd, st)
+    tr.lib = Unfused()
 
 
 def main():
@@ -26,6 +41,10 @@ def main():
     ap.add_argument("--recompute", action="store_true",
                     help="keep one checkpoint per layer and rebuild each layer's activations in its backward (GenieTrainer(recompute=True))")
     ap.add_argument("--mlp_drop", type=float, default=0.0, help="train with MLP dropout of this probability (config.mlp_drop)")
+    ap.add_argument("--ema_decay", type=float, default=None, help="time the step with an EMA of the weights (GenieTrainer(ema_decay=...))")
+    ap.add_argument("--ema_unfused", action="store_true",
+                    help="bench only, with --ema_decay: run the optimizer as genie_adamw_step followed by genie_ema_update per range (two passes) "
+                         "instead of the one fused launch the trainer makes")
     a = ap.parse_args()
     cfgm, syn, _lib = pkg("config"), pkg("synthetic"), pkg("_lib")
     cfg = cfgm.c138() if a.config == "c138" else cfgm.c35()
@@ -37,17 +56,33 @@ def main():
     cfg.mlp_drop = a.mlp_drop
     sd = syn.make_state_dict(cfg, seed=0, law="init")
     model = pkg("st_mask_git").STMaskGIT(cfg, precision=a.precision).load_numpy_state_dict(sd).to("cuda")
-    tr = pkg("train").GenieTrainer(model, lr=1e-4, max_grad_norm=1.0, recompute=a.recompute)
+    tr = pkg("train").GenieTrainer(model, lr=1e-4, max_grad_norm=1.0, recompute=a.recompute, ema_decay=a.ema_decay)
+    lib = _lib.load()
+    if a.ema_unfused:
+        if a.ema_decay is None:
+            ap.error("--ema_unfused needs --ema_decay")
+        unfuse_ema(tr, lib, _lib)
+    opt_events = []   # the optimizer step (sum of squares, AdamW [+ EMA], 16-bit repack) between two events of its own, no host sync
+    inner = tr.optimizer_step
+
+    def timed_optimizer_step():
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        out = inner()
+        ev[1].record()
+        opt_events.append(ev)
+        return out
+    tr.optimizer_step = timed_optimizer_step
     ids = torch.from_numpy(syn.make_clips(a.batch, cfg, seed=1)).cuda()
     collate = pkg("data").maskgit_collate
     torch.manual_seed(0)
     import random
     random.seed(0)
     batch = collate(ids, cfg)
-    lib = _lib.load()
     for _ in range(a.warmup):
         out = tr.train_step(batch)
     torch.cuda.synchronize()
+    opt_events.clear()
     if a.breakdown:
         lib.genie_profile_enable(0x1F)
         lib.genie_profile_reset()
@@ -60,10 +95,14 @@ def main():
     n_params = sum(p.numel() for p in model.parameters())
     flops = 6.0 * n_params * tokens  # the reference's own estimate (train.py:543)
     act_bytes = [lib.genie_train_activation_bytes_ex(tr.cfg, a.batch, m) for m in (0, 1)]
-    print(f"{a.config} L={cfg.num_layers} T={cfg.T} B={a.batch} recompute={int(a.recompute)} mlp_drop={a.mlp_drop:g}: {dt*1e3:.1f} ms/step, {tokens/dt:.0f} tokens/s, "
+    ema = "off" if a.ema_decay is None else f"{a.ema_decay:g}" + ("(unfused)" if a.ema_unfused else "")
+    print(f"{a.config} L={cfg.num_layers} T={cfg.T} B={a.batch} recompute={int(a.recompute)} mlp_drop={a.mlp_drop:g} ema={ema}: {dt*1e3:.3f} ms/step, {tokens/dt:.0f} tokens/s, "
           f"{flops/dt/1e12:.1f} TFLOP/s (6ND), loss {float(out['loss']):.4f}, |g| {float(out['grad_norm']):.4f}, "
           f"acts {tr._acts.numel()/2**30:.1f} GiB, ws {tr._ws.numel()/2**30:.1f} GiB, "
           f"activation bytes saved / recomputed {act_bytes[0]} / {act_bytes[1]}")
+    ms = sorted(e0.elapsed_time(e1) for e0, e1 in opt_events)
+    print(f"  optimizer_step: AdamW launches {len(tr.adam_runs) * (2 if a.ema_unfused else 1)}, {sum(ms) / len(ms):.3f} ms/step "
+          f"(min {ms[0]:.3f}, median {ms[len(ms) // 2]:.3f}, max {ms[-1]:.3f}; {tr.n_flat * 4 / 1e9:.3f} GB per flat f32 buffer)")
     if a.breakdown:
         import ctypes as C
         buf = (C.c_double * 4)()

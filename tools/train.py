@@ -3,6 +3,9 @@
 what is built (dataset windows, GenieConfig json, AdamW + decay grouping, linear / custom_cosine schedules, gradient
 accumulation, clipping, periodic teacher-forced eval, `save_pretrained` checkpoints with the optimizer state, resume).
 Not built: accelerate/wandb logging, torch.compile, the Llama baseline, MuAdamW (--mu_transfer).
+--ema_decay D keeps an exponential moving average of the weights (updated inside the AdamW launch): every checkpoint directory gains an
+ema/ sub-directory that STMaskGIT.from_pretrained loads like any checkpoint, --eval_ema also evaluates with the averaged weights, and
+--resume_from_checkpoint restores the average from trainer_state.pt.
 A config with action_vocab_size > 0 trains an action-conditioned model on the datasets' actions.bin (refused without one);
 --warmstart_path from an unconditioned checkpoint then starts from a zero action table.
 
@@ -67,6 +70,13 @@ def parse_args():
                         "generation ignore it)")
     p.add_argument("--dropout_seed", type=int, default=0,
                    help="seed of the dropout masks (each rank adds its rank); saved with the trainer state")
+    p.add_argument("--ema_decay", type=float, default=None,
+                   help="keep an exponential moving average of the weights with this decay in [0, 1] (e.g. 0.999); checkpoints gain an "
+                        "ema/ directory with the averaged weights")
+    p.add_argument("--ema_warmup", action="store_true",
+                   help="with --ema_decay: use min(decay, (1 + n) / (10 + n)) at update n, so that the average follows the weights early on")
+    p.add_argument("--eval_ema", action="store_true",
+                   help="with --ema_decay: run the periodic evaluation with the averaged weights as well and log both losses")
     p.add_argument("--action_dim", type=int, default=0,
                    help="condition the model on continuous per-frame action vectors of this many values (the datasets' states.bin; "
                         "random vectors under --synthetic); with --action_dropout a dropped clip reads the model's learned null row")
@@ -78,6 +88,10 @@ def parse_args():
 
 def main():
     args = parse_args()
+    if args.ema_decay is None and (args.ema_warmup or args.eval_ema):
+        sys.exit("train.py: --ema_warmup and --eval_ema need --ema_decay")
+    if args.ema_decay is not None and not 0.0 <= args.ema_decay <= 1.0:
+        sys.exit(f"train.py: --ema_decay {args.ema_decay} is not in [0, 1]")
     if args.mu_transfer:
         raise NotImplementedError("--mu_transfer needs the un-vendored mup fork (MuAdamW, set_base_shapes): not built")
     P = lambda n: importlib.import_module("1xgpt_amd." + n)  # noqa: E731
@@ -181,8 +195,8 @@ def main():
     tr = trainmod.GenieTrainer(model, lr=args.learning_rate, betas=(args.adam_beta_1, args.adam_beta_2), eps=args.adam_eps,
                                weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm,
                                gradient_accumulation_steps=accum, lr_lambda=lr_lambda, recompute=args.recompute_activations,
-                               dropout_seed=args.dropout_seed)
-    if args.resume_from_checkpoint:  # optimizer moments, step counters (train.py:560-590)
+                               dropout_seed=args.dropout_seed, ema_decay=args.ema_decay, ema_warmup=args.ema_warmup)
+    if args.resume_from_checkpoint:  # optimizer moments, step counters (train.py:560-590), the EMA of the weights
         tr.load_state_dict(torch.load(os.path.join(args.resume_from_checkpoint, "trainer_state.pt"), map_location=dev))
     n_params = sum(p.numel() for p in model.parameters())
     if rank == 0:
@@ -234,10 +248,17 @@ def main():
                 el, ea = evaluate()
                 if rank == 0:
                     print(f"step {completed}: eval_loss {el:.4f} eval_teacher_acc {ea:.4f}", flush=True)
+                if args.eval_ema:
+                    with tr.ema_scope():
+                        el, ea = evaluate()
+                    if rank == 0:
+                        print(f"step {completed}: ema_eval_loss {el:.4f} ema_eval_teacher_acc {ea:.4f}", flush=True)
             if rank == 0 and ((ckpt_every and completed % ckpt_every == 0) or completed == max_steps):
                 ck = os.path.join(args.output_dir, "final_checkpt" if completed == max_steps else f"step_{completed}")
                 model.save_pretrained(ck)
                 torch.save(tr.state_dict(), os.path.join(ck, "trainer_state.pt"))
+                if args.ema_decay is not None:   # the averaged weights as a checkpoint of their own (a swap local to this rank)
+                    tr.save_ema_pretrained(os.path.join(ck, "ema"))
             if completed >= max_steps:
                 dist_mod.barrier()
                 return
