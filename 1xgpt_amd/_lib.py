@@ -70,6 +70,13 @@ class Dropout(C.Structure):
     _fields_ = [("p", C.c_float), ("call", C.c_uint32), ("seed", C.c_uint64)]
 
 
+class Objective(C.Structure):
+    """genie_objective: label smoothing, z-loss and per-frame loss weights of the training step (1xgpt_amd/train.py); n_frames 0 = all
+    frames weigh 1, else T."""
+    _fields_ = [("label_smoothing", C.c_float), ("z_loss", C.c_float), ("n_frames", C.c_int32), ("reserved", C.c_int32),
+                ("frame_weight", C.c_float * 64)]
+
+
 ACTION_MAX_DIM = 256   # GENIE_ACTION_MAX_DIM
 WIDE_QKV, WIDE_PROJ, WIDE_FC1, WIDE_FC2 = 1, 2, 1, 2          # bits of the w16_wide fields (genie_hip.h)
 FUSED_QKV_STREAM = 4                                        # spatial attention: fused_w16 = [proj stream | qkv stream]
@@ -257,6 +264,12 @@ for _n in ("genie_train_forward", "genie_train_backward_layer"):
     SIGNATURES[_n + "_drop"] = (SIGNATURES[_n + "_ex"][0], SIGNATURES[_n + "_ex"][1] + [C.POINTER(Dropout)])
 del _n
 
+# the training objective: genie_train_forward_drop's arguments + a trailing genie_objective* (NULL or neutral: that entry point), and the
+# loss launch alone, (logits, ids, labels, n_clips, T, S, vf, nfac, mask_id, obj, sums, stream)
+SIGNATURES["genie_objective_layout"] = (C.c_int, [C.POINTER(C.c_size_t), C.c_int])
+SIGNATURES["genie_train_forward_obj"] = (C.c_int, SIGNATURES["genie_train_forward_drop"][1] + [C.POINTER(Objective)])
+SIGNATURES["genie_ce_objective"] = (C.c_int, [c_ptr, c_ptr, c_ptr] + [C.c_int] * 5 + [C.c_int64, C.POINTER(Objective), c_ptr, c_ptr])
+
 # EMA of the weights: genie_adamw_step's arguments with `ema` behind exp_avg_sq and one_minus_decay in front of the stream; the EMA
 # line alone, (ema, params, n, one_minus_decay, stream); the in-place exchange, (a, b, n, stream)
 _a = SIGNATURES["genie_adamw_step"][1]
@@ -311,6 +324,9 @@ def load():
         mine = [C.sizeof(Dropout)] + [getattr(Dropout, n).offset for n, _ in Dropout._fields_]
         if "genie_dropout_layout" not in missing and (lib.genie_dropout_layout(lay, 4) != 4 or list(lay)[:4] != mine):
             raise RuntimeError(f"genie_dropout layout {list(lay)[:4]} != the ctypes declaration {mine}")
+        mine = [C.sizeof(Objective)] + [getattr(Objective, n).offset for n, _ in Objective._fields_]
+        if "genie_objective_layout" not in missing and (lib.genie_objective_layout(lay, 6) != 6 or list(lay) != mine):
+            raise RuntimeError(f"genie_objective layout {list(lay)} != the ctypes declaration {mine}")
         if os.environ.get("GENIE_HIP_LIBRARY") or lib.genie_study_build():
             import sys
             print(f"1xgpt_amd: using {LIB_PATH} (study build: {bool(lib.genie_study_build())}) -- not the shipping library"

@@ -304,6 +304,10 @@ int launch_gelu_fwd(const float* z, float* h, size_t n, hipStream_t st);
 int launch_gelu_bwd(const float* z, float* g, size_t n, hipStream_t st);
 int launch_ce_fwd_bwd(const genie_cfg& c, float* logits, const int64_t* ids, const int64_t* labels, int B, double* sums,
                       hipStream_t st);
+// the general objective (label smoothing, z-loss, per-frame weights; include/genie_hip.h, "Training objective") on (n_clips, T, S)
+// tokens of nfac factors of vf logits: five sums, d logits in place.  `obj` was checked by the caller (objective_ok in train_api.hip).
+int launch_ce_objective(float* logits, const int64_t* ids, const int64_t* labels, long n_clips, int T, int S, int vf, int nfac,
+                        int64_t mask_id, const genie_objective& obj, double* sums, hipStream_t st);
 int launch_embed_bwd(const genie_cfg& c, const float* dx, const int64_t* ids, int B, float* dpos, float* dmask,
                      float* const* tables_host, float beta, float* colpart, hipStream_t st);
 // gradient of the action table: d_table[k] = sum over frames (b, t) with act_ids[b, t] == k (ascending) of sum_s dx[b, t, s, :];

@@ -42,6 +42,12 @@
 // norms in the 16-bit precisions it also writes the next layer's operand, in launch_cast16's rounding, which is what the recomputation
 // then rebuilds it with); the backward hands fc2 a masked, scaled copy of the running dx in w.d1, dead at that point, and the residual
 // branch keeps dx itself.  p = 0 launches exactly the step above.
+//
+// Training objective (genie_train_forward_obj, a genie_objective that is not neutral): the forward is the one above up to the logits;
+// the loss launch is launch_ce_objective (kernels_train.hip: label smoothing, z-loss, per-frame weights; five sums) instead of
+// launch_ce_fwd_bwd, and leaves d loss / d logits in the same slot, so no backward entry point knows about it.  Neutral: the step above.
+#include <cmath>
+
 #include "kernels.hpp"
 
 namespace genie {
@@ -344,6 +350,24 @@ static Drop make_drop(const genie_dropout* dr) {
     return Drop{true, 1.0f / (1.0f - dr->p), drop_key(*dr)};
 }
 
+// The training objective of one call (genie_objective): neutral = the step's own loss kernels, untouched.  T: the frames of the call
+// (n_frames is 0 or T; the struct holds 64 weights)
+static bool objective_neutral(const genie_objective* ob) {
+    return !ob || (ob->label_smoothing == 0.0f && ob->z_loss == 0.0f && ob->n_frames == 0);
+}
+static int objective_ok(const genie_objective* ob, int T, const char* fn) {
+    if (!ob) return GENIE_OK;
+    GENIE_CHECK_ARG(ob->label_smoothing >= 0.0f && ob->label_smoothing < 1.0f, "%s: label_smoothing %g is not in [0, 1)", fn,
+                    (double)ob->label_smoothing);   // (NaN fails both)
+    GENIE_CHECK_ARG(ob->z_loss >= 0.0f && std::isfinite(ob->z_loss), "%s: z_loss %g is negative or not finite", fn, (double)ob->z_loss);
+    GENIE_CHECK_ARG(ob->n_frames == 0 || (ob->n_frames == T && T <= 64), "%s: n_frames %d is neither 0 nor T = %d (at most 64)", fn,
+                    ob->n_frames, T);
+    for (int t = 0; t < ob->n_frames; ++t)
+        GENIE_CHECK_ARG(ob->frame_weight[t] >= 0.0f && std::isfinite(ob->frame_weight[t]),
+                        "%s: frame_weight[%d] = %g is negative or not finite", fn, t, (double)ob->frame_weight[t]);
+    return GENIE_OK;
+}
+
 // ================================================================================================
 // The two backends.  Same members: Operand (the element type of a saved Linear input), cast / norm / attention (produce an
 // operand), linear, linear_backward.  M tokens; beta 1 accumulates into the gradients; w is unused by the forward.
@@ -522,7 +546,7 @@ static int layer_forward(Ops& o, const genie_layer_weights& lw, const LayerLins&
 
 template <class Ops>
 static int train_forward(Ops& o, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels, char* acts,
-                         const TrainActs& a, double* sums, const EmbedAct* act) {
+                         const TrainActs& a, double* sums, const EmbedAct* act, const genie_objective* obj) {
     using Operand = typename Ops::Operand;
     const genie_cfg& c = o.c;
     const size_t pd = (size_t)o.M * c.d_model;
@@ -538,11 +562,13 @@ static int train_forward(Ops& o, const genie_weights* wt, const int64_t* input_i
     }
     if (!idn) GENIE_TRY(o.cast(xL, xL_op, pd));
     GENIE_TRY(o.linear(xL_op, readout_lin(c, wt, nullptr, nullptr), nullptr, logits, nullptr, nullptr, c.readout_mult));
-    if (hipMemsetAsync(sums, 0, 3 * sizeof(double), o.st) != hipSuccess) {
+    if (hipMemsetAsync(sums, 0, (obj ? 5 : 3) * sizeof(double), o.st) != hipSuccess) {
         set_error("genie_train_forward: hipMemsetAsync failed");
         return GENIE_E_LAUNCH;
     }
-    return launch_ce_fwd_bwd(c, logits, input_ids, labels, o.B, sums, o.st);
+    if (!obj) return launch_ce_fwd_bwd(c, logits, input_ids, labels, o.B, sums, o.st);
+    return launch_ce_objective(logits, input_ids, labels, o.B, c.T, c.S, c.factored_vocab, c.num_factored, (int64_t)c.image_vocab_size,
+                               *obj, sums, o.st);
 }
 
 // d loss / d logits (in the logits slot) -> the readout's gradients and d xL in w.dx
@@ -678,9 +704,10 @@ int genie_train_forward_ex(const genie_cfg* cfg, const genie_weights* wt, const 
     return genie_train_forward_drop(cfg, wt, input_ids, labels, B, acts, acts_bytes, sums, stream, cond, recompute, nullptr);
 }
 
-int genie_train_forward_drop(const genie_cfg* cfg, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels,
+// genie_train_forward_drop, and with obj != NULL (checked, not neutral) the general objective behind the same forward
+static int train_forward_any(const genie_cfg* cfg, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels,
                              int B, float* acts, size_t acts_bytes, double* sums, void* stream, const genie_frame_cond* cond,
-                             int recompute, const genie_dropout* dr) {
+                             int recompute, const genie_dropout* dr, const genie_objective* obj) {
     GENIE_CHECK_ARG(drop_p_ok(dr), "genie_train_forward: dropout p = %g is not in [0, 1)", (double)dr->p);
     GENIE_TRY(check_mode(recompute, "genie_train_forward"));
     // argument errors (GENIE_E_ARG) are reported before geometry errors (GENIE_E_SHAPE), as they were before train_check
@@ -699,11 +726,25 @@ int genie_train_forward_drop(const genie_cfg* cfg, const genie_weights* wt, cons
     char* base = (char*)acts;
     if (c.precision == GENIE_PREC_EXACT) {
         ExactOps o{c, B, M, st, TrainWs{}, 0.0f, make_drop(dr)};
-        return train_forward(o, wt, input_ids, labels, base, a, sums, act);
+        return train_forward(o, wt, input_ids, labels, base, a, sums, act, obj);
     }
     GENIE_CHECK_SHAPE(V >= c.d_model, "training step (16-bit): vocabulary rows %d < d_model %d", V, c.d_model);
     Ops16 o{c, B, M, st, TrainWs{}, 0.0f, npl_of(c), TrainWs16{}, (float*)(base + a.logits), make_drop(dr)};
-    return train_forward(o, wt, input_ids, labels, base, a, sums, act);
+    return train_forward(o, wt, input_ids, labels, base, a, sums, act, obj);
+}
+
+int genie_train_forward_drop(const genie_cfg* cfg, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels,
+                             int B, float* acts, size_t acts_bytes, double* sums, void* stream, const genie_frame_cond* cond,
+                             int recompute, const genie_dropout* dr) {
+    return train_forward_any(cfg, wt, input_ids, labels, B, acts, acts_bytes, sums, stream, cond, recompute, dr, nullptr);
+}
+
+int genie_train_forward_obj(const genie_cfg* cfg, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels,
+                            int B, float* acts, size_t acts_bytes, double* sums, void* stream, const genie_frame_cond* cond,
+                            int recompute, const genie_dropout* dr, const genie_objective* obj) {
+    GENIE_TRY(objective_ok(obj, cfg ? cfg->T : (obj ? obj->n_frames : 0), "genie_train_forward_obj"));
+    return train_forward_any(cfg, wt, input_ids, labels, B, acts, acts_bytes, sums, stream, cond, recompute, dr,
+                             objective_neutral(obj) ? nullptr : obj);
 }
 
 int genie_train_backward_head(const genie_cfg* cfg, const genie_weights* wt, const genie_weights* wT,
@@ -821,6 +862,39 @@ int genie_dropout_layout(size_t* out_host, int n) {
     const size_t v[4] = {sizeof(genie_dropout), offsetof(genie_dropout, p), offsetof(genie_dropout, call), offsetof(genie_dropout, seed)};
     for (int i = 0; i < n && i < 4 && out_host; ++i) out_host[i] = v[i];
     return 4;
+}
+
+int genie_objective_layout(size_t* out_host, int n) {
+    const size_t v[6] = {sizeof(genie_objective), offsetof(genie_objective, label_smoothing), offsetof(genie_objective, z_loss),
+                         offsetof(genie_objective, n_frames), offsetof(genie_objective, reserved), offsetof(genie_objective, frame_weight)};
+    for (int i = 0; i < n && i < 6 && out_host; ++i) out_host[i] = v[i];
+    return 6;
+}
+
+int genie_ce_objective(float* logits, const int64_t* ids, const int64_t* labels, int n_clips, int T, int S, int vf, int nfac,
+                       int64_t mask_id, const genie_objective* obj, double* sums, void* stream) {
+    GENIE_TRY(objective_ok(obj, T, "genie_ce_objective"));
+    GENIE_CHECK_ARG(logits && ids && labels && sums, "genie_ce_objective: NULL argument");
+    GENIE_CHECK_ARG(n_clips >= 1 && T >= 1 && S >= 1 && vf >= 1 && nfac >= 1 && nfac <= 4,
+                    "genie_ce_objective: n_clips %d, T %d, S %d, vf %d must be positive and nfac %d in 1 .. 4", n_clips, T, S, vf, nfac);
+    GENIE_CHECK_ARG((long)vf * nfac <= INT32_MAX, "genie_ce_objective: a row of %d x %d logits", nfac, vf);
+    hipStream_t st = (hipStream_t)stream;
+    if (!obj) {   // the neutral step's kernels (they take the geometry from a genie_cfg)
+        GENIE_CHECK_ARG(mask_id >= INT32_MIN && mask_id <= INT32_MAX, "genie_ce_objective: mask_id %lld beyond int32 without an objective",
+                        (long long)mask_id);
+        genie_cfg c{};
+        c.T = T; c.S = S; c.factored_vocab = vf; c.num_factored = nfac; c.image_vocab_size = (int32_t)mask_id;
+        if (hipMemsetAsync(sums, 0, 3 * sizeof(double), st) != hipSuccess) {
+            set_error("genie_ce_objective: hipMemsetAsync failed");
+            return GENIE_E_LAUNCH;
+        }
+        return launch_ce_fwd_bwd(c, logits, ids, labels, n_clips, sums, st);
+    }
+    if (hipMemsetAsync(sums, 0, 5 * sizeof(double), st) != hipSuccess) {
+        set_error("genie_ce_objective: hipMemsetAsync failed");
+        return GENIE_E_LAUNCH;
+    }
+    return launch_ce_objective(logits, ids, labels, n_clips, T, S, vf, nfac, mask_id, *obj, sums, st);
 }
 
 int genie_dropout_mask(const genie_dropout* dr, int layer, int site, int64_t n, uint8_t* keep, void* stream) {

@@ -19,6 +19,8 @@ Design (MI355X-first):
   * EMA of the weights (`ema_decay`; the reference's mechanism is magvit2/modules/ema.py, LitEma): one more flat f32 buffer that the AdamW
     launch itself updates (genie_adamw_ema_step: one more read and write per element, no second pass); `ema_scope()` swaps it
     with the parameters in place to evaluate, sample or save with the averaged weights.
+  * training objective (`label_smoothing`, `z_loss`, `frame_weights`): label smoothing, z-loss and per-frame loss weights inside the
+    fused loss kernel (genie_train_forward_obj); the backward reads its d logits as it reads the plain loss's; evaluation ignores it.
 MuAdamW (--mu_transfer, train.py:439; third-party mup fork) is not built.
 """
 import contextlib
@@ -78,6 +80,40 @@ def ema_decay_at(decay, n, warmup=False):
 def ema_one_minus_decay(decay, n, warmup=False):
     """omd = float32(1) - d_n, the scalar the kernels take."""
     return float(np.float32(1) - np.float32(ema_decay_at(decay, n, warmup)))
+
+
+# ------------------------------------------------------------------ training objective (include/genie_hip.h, "Training objective")
+def objective_settings(label_smoothing=0.0, z_loss=0.0, frame_weights=None, T=None):
+    """(eps, zeta, weights) as the trainer keeps them: floats, and a tuple of T floats or None.  All-ones weights are None.  Raises
+    ValueError for eps outside [0, 1), a negative or non-finite zeta, a wrong number of weights, a negative or non-finite weight, or no
+    positive weight behind frame 0 (frame 0 is never counted: nothing would be left to train on)."""
+    eps, zeta = float(label_smoothing), float(z_loss)
+    if not 0.0 <= eps < 1.0:   # (False for NaN)
+        raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing!r}")
+    if not (zeta >= 0.0 and math.isfinite(zeta)):
+        raise ValueError(f"z_loss must be finite and >= 0, got {z_loss!r}")
+    if frame_weights is None:
+        return eps, zeta, None
+    w = tuple(float(v) for v in frame_weights)
+    if T is not None and len(w) != T:
+        raise ValueError(f"frame_weights needs one weight per frame: {len(w)} given, T = {T}")
+    if len(w) > 64:
+        raise ValueError(f"frame_weights holds at most 64 frames, got {len(w)}")
+    if not all(v >= 0.0 and math.isfinite(v) for v in w):
+        raise ValueError(f"frame_weights must be finite and >= 0, got {w!r}")
+    if not any(v > 0.0 for v in w[1:]):
+        raise ValueError(f"frame_weights needs a positive weight behind frame 0 (frame 0 is never counted), got {w!r}")
+    return eps, zeta, (None if all(v == 1.0 for v in w) else w)
+
+
+def make_objective(eps, zeta, weights):
+    """The genie_objective of objective_settings' values; None when they are neutral (the entry points of before)."""
+    if np.float32(eps) == 0.0 and np.float32(zeta) == 0.0 and weights is None:   # the library's values are floats
+        return None
+    ob = _lib.Objective(label_smoothing=eps, z_loss=zeta, n_frames=0 if weights is None else len(weights), reserved=0)
+    for t, v in enumerate(weights or ()):
+        ob.frame_weight[t] = v
+    return ob
 
 
 # ------------------------------------------------------------------ pointer tables
@@ -200,8 +236,14 @@ def bucket_bounds(segments, target_elems):
 class GenieTrainer:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0,
                  gradient_accumulation_steps=1, lr_lambda=None, bucket_mb=64, group=None, recompute=False, dropout_seed=0,
-                 ema_decay=None, ema_warmup=False):
-        """ema_decay: keep an exponential moving average of the weights in `self.ema`, a flat f32 buffer with the layout of `self.params`
+                 ema_decay=None, ema_warmup=False, label_smoothing=0.0, z_loss=0.0, frame_weights=None):
+        """label_smoothing, z_loss, frame_weights: the training objective (include/genie_hip.h, "Training objective"): per factor
+        F.cross_entropy(label_smoothing=eps) + z_loss * logsumexp^2, each counted token weighted by its frame's entry of `frame_weights`
+        (T floats >= 0; frame 0 is never counted) and the sum divided by the summed weights of the counted tokens.  All in the fused loss
+        kernel, which still reads and writes the logits once; the backward is untouched.  `forward_backward` returns this objective as
+        its loss -- the quantity the gradients are of -- and `last_ce` holds the plain masked cross-entropy of the same micro-batch, which
+        is what the evaluators report.  At the defaults (all-ones weights count as None): no new buffer and the entry points of before.
+        ema_decay: keep an exponential moving average of the weights in `self.ema`, a flat f32 buffer with the layout of `self.params`
         that starts as a copy of it (after the rank-0 broadcast: replicas hold identical averages, nothing is communicated).  Every
         optimizer step -- not every micro-batch -- moves it by ema = ema - omd * (ema - p_new) inside the AdamW launch, with
         omd = 1 - ema_decay_at(ema_decay, ema_updates + 1, ema_warmup); ema_warmup is LitEma's use_num_upates, min(decay, (1 + n) / (10 + n)).
@@ -232,6 +274,9 @@ class GenieTrainer:
         self.ema_warmup = bool(ema_warmup)
         if self.ema_decay is not None:
             ema_decay_at(self.ema_decay, 1, self.ema_warmup)   # ValueError outside [0, 1]
+        self.label_smoothing, self.z_loss, self.frame_weights = objective_settings(label_smoothing, z_loss, frame_weights, self.config.T)
+        self._objective = make_objective(self.label_smoothing, self.z_loss, self.frame_weights)   # None: neutral
+        self.last_ce = None   # plain masked CE of the last micro-batch (0-dim device tensor)
 
         named = dict(model.named_parameters())
         self.order = ready_order(self.config, named.keys())
@@ -296,7 +341,8 @@ class GenieTrainer:
             segs.append((lo, hi))
         self.segments = segs  # [head, layer L-1, ..., layer 0, embeddings]
         self.reducer = BucketReducer(self.grads, bucket_bounds(segs, bucket_mb * (1 << 20) // 4), group)
-        self.sums = torch.zeros(3, dtype=torch.float64, device=dev)
+        # [sum loss, sum hits, n]; with an objective [sum w l, sum hits, W, sum plain nll, n]
+        self.sums = torch.zeros(3 if self._objective is None else 5, dtype=torch.float64, device=dev)
         self.sumsq = torch.zeros(1, dtype=torch.float64, device=dev)
         self.scratch = torch.zeros(1024, dtype=torch.float64, device=dev)
         self._acts = self._ws = None
@@ -378,8 +424,13 @@ class GenieTrainer:
         lib, cfg, st = self.lib, self.cfg, self._stream()
         acc_flag = 1 if accumulate else 0
         drop = self._dropout()
-        _lib.check(_lib.call_drop(lib, "genie_train_forward", self.recompute, drop, cfg, self.w_table, ids.data_ptr(), lab.data_ptr(), B,
-                                  acts.data_ptr(), acts.numel(), self.sums.data_ptr(), st, cond=cond), "genie_train_forward")
+        if self._objective is None:
+            _lib.check(_lib.call_drop(lib, "genie_train_forward", self.recompute, drop, cfg, self.w_table, ids.data_ptr(), lab.data_ptr(), B,
+                                      acts.data_ptr(), acts.numel(), self.sums.data_ptr(), st, cond=cond), "genie_train_forward")
+        else:   # the same forward, the general loss kernel behind it; every backward call below reads its d logits as before
+            _lib.check(lib.genie_train_forward_obj(cfg, self.w_table, ids.data_ptr(), lab.data_ptr(), B, acts.data_ptr(), acts.numel(),
+                                                   self.sums.data_ptr(), st, cond, self.recompute, drop, self._objective),
+                       "genie_train_forward_obj")
         sums = self.sums.clone()
         self.reducer.reset()
         _lib.check(_lib.call_recompute(lib, "genie_train_backward_head", self.recompute, cfg, self.w_table, self.wT_table,
@@ -418,7 +469,12 @@ class GenieTrainer:
                        "genie_train_backward_embed_cond")
         if reduce:
             self.reducer.finish()
-        return sums[0] / sums[2], sums[1] / sums[2]
+        loss = sums[0] / sums[2]
+        if self._objective is None:
+            self.last_ce = loss
+            return loss, sums[1] / sums[2]
+        self.last_ce = sums[3] / sums[4]   # hits and the plain CE are taken over every counted token, whatever its frame weighs
+        return loss, sums[1] / sums[4]
 
     # ------------------------------------------------------------------ clip + AdamW + scheduler (train.py:628-633)
     def grad_sumsq(self):
@@ -469,6 +525,8 @@ class GenieTrainer:
                                           action_vectors=batch.get("action_vectors"), action_drop=batch.get("action_drop"))
         self._micro += 1
         out = {"loss": loss, "acc": acc}
+        if self._objective is not None:
+            out["ce"] = self.last_ce
         if is_update:
             if self.accum > 1 and self.reducer.world > 1:  # no_sync() micro-batches: reduce once, after the last
                 self.reducer.reset()
@@ -540,7 +598,8 @@ class GenieTrainer:
                "dropout": {"seed": self.dropout_seed, "call": self._drop_call},
                "hyper": {"lr": self.base_lr, "betas": tuple(self.betas), "eps": self.eps,
                          "weight_decay": self.weight_decay, "max_grad_norm": self.max_grad_norm,
-                         "gradient_accumulation_steps": self.accum, "recompute": bool(self.recompute)}}
+                         "gradient_accumulation_steps": self.accum, "recompute": bool(self.recompute),
+                         "label_smoothing": self.label_smoothing, "z_loss": self.z_loss, "frame_weights": self.frame_weights}}
         if self.ema is not None:
             out["ema"] = {"state": self.ema_state_dict(), "updates": self.ema_updates, "decay": self.ema_decay,
                           "warmup": self.ema_warmup}
@@ -554,7 +613,8 @@ class GenieTrainer:
         self._not_in_ema_scope("load_state_dict")
         saved_ema = sd.get("ema")
         mine = {"lr": self.base_lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
-                "max_grad_norm": self.max_grad_norm, "gradient_accumulation_steps": self.accum}
+                "max_grad_norm": self.max_grad_norm, "gradient_accumulation_steps": self.accum,
+                "label_smoothing": self.label_smoothing, "z_loss": self.z_loss, "frame_weights": self.frame_weights}
         diff = {k: (v, mine[k]) for k, v in (sd.get("hyper") or {}).items()
                 if k in mine and (tuple(v) if isinstance(v, (list, tuple)) else v) != mine[k]}
         if saved_ema is not None and self.ema is not None:

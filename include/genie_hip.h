@@ -851,6 +851,55 @@ int genie_train_backward_layer_drop(const genie_cfg* cfg, const genie_weights* w
                                     size_t workspace_bytes, int accumulate, void* stream, int recompute,
                                     const genie_dropout* dr);
 
+/* Training objective (additions; nothing above changes): label smoothing eps, z-loss zeta and per-frame loss weights w_t in the fused
+ * loss kernel.  A token n in frame t is counted iff t >= 1 and its input id is the mask id (the rule above).  For a counted token and
+ * factor f with logits z (vf values) and target y:
+ *     lse   = max + log sum_k exp(z_k - max)
+ *     nll_f = lse - z_y
+ *     l_f   = (1 - eps) nll_f + eps (lse - (1/vf) sum_k z_k) + zeta lse^2          l_n = sum_f l_f
+ *     p_k   = exp(z_k - lse),   q_k = (1 - eps) [k = y] + eps / vf
+ *     d l_f / d z_k = p_k (1 + 2 zeta lse) - q_k
+ * (the first two terms are F.cross_entropy(label_smoothing = eps) per factor).  With frame weights w_0 .. w_{T-1} (w_0 is never used;
+ * all ones by default):
+ *     c_t  = number of counted tokens in frame t (integers, exact)
+ *     W    = sum_t (double) w_t c_t   (t ascending),        n = sum_t c_t
+ *     loss = sum_counted w_t l_n / W
+ *     d loss / d z_k = (float)((double) w_t / W) d l_f / d z_k
+ * Uncounted tokens and counted tokens with w_t = 0 get a zero row and are never multiplied by 1 / W; W = 0 with n > 0 gives loss NaN
+ * (0/0, as the empty mask above) and all-zero gradients.  The sums buffer holds FIVE doubles
+ *     [sum w l, sum hits, W, sum plain nll, n]        loss = s0 / s2,  acc = s1 / s4,  ce = s3 / s4
+ * with hits (all factors argmax-correct) and the plain nll (l_n at eps = zeta = 0) taken over ALL counted tokens whatever their
+ * weight, so that acc and ce stay comparable between runs with different objectives and with the evaluators.  f32 in all three
+ * precisions; per token nll is evaluated as (logf(se) + max) - z_y and an element as (p (1 + 2 zeta lse) - q) wgt, in the summation
+ * order of the neutral kernel: with eps = zeta = 0 and all weights 1 the rows are that kernel's bits.  d logits has a fixed summation
+ * order and no atomics (the same bytes run to run); the three loss sums are accumulated with double atomics, as the neutral step's.
+ * Neutral means eps == 0, zeta == 0 and n_frames == 0.  The struct is read on the host during the call; the weights travel in the
+ * kernel arguments (no copy, no sync).  Refused with GENIE_E_ARG before any other check: eps outside [0, 1) or NaN; zeta negative
+ * or not finite; n_frames neither 0 nor T; a negative or non-finite weight among the first n_frames. */
+typedef struct genie_objective {
+    float label_smoothing;   /* eps, 0 <= eps < 1 */
+    float z_loss;            /* zeta >= 0 */
+    int32_t n_frames;        /* 0 = all frames weigh 1, else == T */
+    int32_t reserved;        /* 0 */
+    float frame_weight[64];  /* w_t, t < n_frames */
+} genie_objective;
+/* sizeof(genie_objective) and the offsets of its five fields, in declaration order: writes min(n, 6) entries, returns 6. */
+int genie_objective_layout(size_t* out_host, int n);
+/* genie_train_forward_drop with the objective: the same arguments and `obj`; sums_out always has room for five doubles.  obj == NULL
+ * or neutral: the call IS the _drop call (same launches, same bits, only three doubles written).  Else the five sums above, and the
+ * logits slot holds d loss / d logits of this objective: head, layers and embed backward are untouched (recomputation and dropout
+ * compose as they are). */
+int genie_train_forward_obj(const genie_cfg* cfg, const genie_weights* w, const int64_t* input_ids, const int64_t* labels,
+                            int B, float* acts, size_t acts_bytes, double* sums_out, void* stream,
+                            const genie_frame_cond* cond, int recompute, const genie_dropout* dr, const genie_objective* obj);
+/* The loss launch alone on caller-owned logits (n_clips, T, S, nfac * vf) f32, replaced by d loss / d logits; ids and labels
+ * (n_clips, T, S) int64; no genie_cfg and no geometry limits beyond vf >= 1 and 1 <= nfac <= 4 (n_frames == T needs T <= 64).
+ * obj == NULL: the neutral step's own kernels, sums_out = its three doubles.  obj != NULL: always the general kernels, also at
+ * neutral values, five doubles.  sums_out is overwritten.  A NULL pointer, n_clips, T, S or vf < 1, nfac outside 1 .. 4, or (obj ==
+ * NULL) a mask_id beyond int32: GENIE_E_ARG, nothing enqueued. */
+int genie_ce_objective(float* logits, const int64_t* ids, const int64_t* labels, int n_clips, int T, int S, int vf, int nfac,
+                       int64_t mask_id, const genie_objective* obj, double* sums_out, void* stream);
+
 /* The temporal (causal, over the T frames of one spatial position) attention backward of the step, alone -- the counterpart of
  * genie_attention_core for the backward; f32 in every precision.  qkv (B,T,S,3*d_model) is the saved q | k | v; qk holds the q | k the
  * scores were made from, q at column 0 and k at column d_model of rows of qk_ld floats: qkv itself (qk_ld = 3*d_model) or the

@@ -41,6 +41,10 @@ def main():
     ap.add_argument("--recompute", action="store_true",
                     help="keep one checkpoint per layer and rebuild each layer's activations in its backward (GenieTrainer(recompute=True))")
     ap.add_argument("--mlp_drop", type=float, default=0.0, help="train with MLP dropout of this probability (config.mlp_drop)")
+    ap.add_argument("--label_smoothing", type=float, default=0.0, help="train with this label smoothing (GenieTrainer(label_smoothing=...))")
+    ap.add_argument("--z_loss", type=float, default=0.0, help="train with this z-loss weight (GenieTrainer(z_loss=...))")
+    ap.add_argument("--frame_loss_weights", type=str, default=None,
+                    help="comma-separated per-frame loss weights, one per frame (GenieTrainer(frame_weights=...))")
     ap.add_argument("--ema_decay", type=float, default=None, help="time the step with an EMA of the weights (GenieTrainer(ema_decay=...))")
     ap.add_argument("--ema_unfused", action="store_true",
                     help="bench only, with --ema_decay: run the optimizer as genie_adamw_step followed by genie_ema_update per range (two passes) "
@@ -56,7 +60,9 @@ def main():
     cfg.mlp_drop = a.mlp_drop
     sd = syn.make_state_dict(cfg, seed=0, law="init")
     model = pkg("st_mask_git").STMaskGIT(cfg, precision=a.precision).load_numpy_state_dict(sd).to("cuda")
-    tr = pkg("train").GenieTrainer(model, lr=1e-4, max_grad_norm=1.0, recompute=a.recompute, ema_decay=a.ema_decay)
+    fw = None if a.frame_loss_weights is None else [float(v) for v in a.frame_loss_weights.split(",")]
+    tr = pkg("train").GenieTrainer(model, lr=1e-4, max_grad_norm=1.0, recompute=a.recompute, ema_decay=a.ema_decay,
+                                   label_smoothing=a.label_smoothing, z_loss=a.z_loss, frame_weights=fw)
     lib = _lib.load()
     if a.ema_unfused:
         if a.ema_decay is None:
@@ -96,7 +102,9 @@ def main():
     flops = 6.0 * n_params * tokens  # the reference's own estimate (train.py:543)
     act_bytes = [lib.genie_train_activation_bytes_ex(tr.cfg, a.batch, m) for m in (0, 1)]
     ema = "off" if a.ema_decay is None else f"{a.ema_decay:g}" + ("(unfused)" if a.ema_unfused else "")
-    print(f"{a.config} L={cfg.num_layers} T={cfg.T} B={a.batch} recompute={int(a.recompute)} mlp_drop={a.mlp_drop:g} ema={ema}: {dt*1e3:.3f} ms/step, {tokens/dt:.0f} tokens/s, "
+    objective = "off" if tr._objective is None else (f"eps={a.label_smoothing:g},zeta={a.z_loss:g},weights={'on' if tr.frame_weights else 'off'}"
+                                                    f" (ce {float(out['ce']):.4f})")
+    print(f"{a.config} L={cfg.num_layers} T={cfg.T} B={a.batch} recompute={int(a.recompute)} mlp_drop={a.mlp_drop:g} ema={ema} objective={objective}: {dt*1e3:.3f} ms/step, {tokens/dt:.0f} tokens/s, "
           f"{flops/dt/1e12:.1f} TFLOP/s (6ND), loss {float(out['loss']):.4f}, |g| {float(out['grad_norm']):.4f}, "
           f"acts {tr._acts.numel()/2**30:.1f} GiB, ws {tr._ws.numel()/2**30:.1f} GiB, "
           f"activation bytes saved / recomputed {act_bytes[0]} / {act_bytes[1]}")
@@ -111,6 +119,13 @@ def main():
             if buf[0]:
                 print(f"  {name:14s} launches {int(buf[0]):6d}  {buf[1]/a.steps:9.2f} ms/step  "
                       f"{buf[2]/max(buf[1],1e-9)/1e9:8.1f} TFLOP/s  {buf[3]/max(buf[1],1e-9)/1e6:8.1f} GB/s")
+        if tr._objective is not None:   # the general loss kernels by name (class "other"; the neutral step's are not bracketed)
+            kbuf = C.create_string_buffer(16384)
+            _lib.check(lib.genie_profile_kernels(_lib.KC_OTHER, kbuf, len(kbuf)), "profile_kernels")
+            for ln in kbuf.value.decode().splitlines():
+                name, n, ms = ln.split("\t")[:3]
+                if name in ("ce_objective_kernel", "count_frames_kernel"):
+                    print(f"    {name:22s} launches {float(n) / a.steps:6.0f}  {float(ms) / a.steps:9.4f} ms/step")
         if a.mlp_drop:   # the dropout kernels by name (class "other"): launches and milliseconds per step
             kbuf = C.create_string_buffer(16384)
             _lib.check(lib.genie_profile_kernels(_lib.KC_OTHER, kbuf, len(kbuf)), "profile_kernels")

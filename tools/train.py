@@ -6,6 +6,9 @@ Not built: accelerate/wandb logging, torch.compile, the Llama baseline, MuAdamW 
 --ema_decay D keeps an exponential moving average of the weights (updated inside the AdamW launch): every checkpoint directory gains an
 ema/ sub-directory that STMaskGIT.from_pretrained loads like any checkpoint, --eval_ema also evaluates with the averaged weights, and
 --resume_from_checkpoint restores the average from trainer_state.pt.
+--label_smoothing E, --z_loss Z and --frame_loss_weights w0,w1,... shape the training loss (per factor F.cross_entropy(label_smoothing=E)
++ Z * logsumexp^2, weighted per frame); the step line then prints the plain cross-entropy as `ce` next to train_loss, and evaluation
+reports the plain cross-entropy as before.
 A config with action_vocab_size > 0 trains an action-conditioned model on the datasets' actions.bin (refused without one);
 --warmstart_path from an unconditioned checkpoint then starts from a zero action table.
 
@@ -70,6 +73,15 @@ def parse_args():
                         "generation ignore it)")
     p.add_argument("--dropout_seed", type=int, default=0,
                    help="seed of the dropout masks (each rank adds its rank); saved with the trainer state")
+    p.add_argument("--label_smoothing", type=float, default=0.0,
+                   help="label smoothing in [0, 1) of the training loss, per factor as F.cross_entropy(label_smoothing=); evaluation "
+                        "reports the plain cross-entropy")
+    p.add_argument("--z_loss", type=float, default=0.0,
+                   help="weight >= 0 of the z-loss, z_loss * logsumexp^2 per softmax (e.g. 1e-4): keeps the readout's log-partition "
+                        "from drifting in bf16 runs")
+    p.add_argument("--frame_loss_weights", type=str, default=None,
+                   help="comma-separated loss weights >= 0, one per frame of the window (w0,w1,...; frame 0 is never counted): the "
+                        "loss is the weighted mean over the masked tokens")
     p.add_argument("--ema_decay", type=float, default=None,
                    help="keep an exponential moving average of the weights with this decay in [0, 1] (e.g. 0.999); checkpoints gain an "
                         "ema/ directory with the averaged weights")
@@ -92,6 +104,16 @@ def main():
         sys.exit("train.py: --ema_warmup and --eval_ema need --ema_decay")
     if args.ema_decay is not None and not 0.0 <= args.ema_decay <= 1.0:
         sys.exit(f"train.py: --ema_decay {args.ema_decay} is not in [0, 1]")
+    frame_weights = None
+    if args.frame_loss_weights is not None:
+        try:
+            frame_weights = [float(v) for v in args.frame_loss_weights.split(",")]
+        except ValueError:
+            sys.exit(f"train.py: --frame_loss_weights {args.frame_loss_weights!r} is not a comma-separated list of numbers")
+    try:   # the trainer's own rules, before anything is built
+        importlib.import_module("1xgpt_amd.train").objective_settings(args.label_smoothing, args.z_loss, frame_weights)
+    except ValueError as e:
+        sys.exit(f"train.py: --label_smoothing / --z_loss / --frame_loss_weights: {e}")
     if args.mu_transfer:
         raise NotImplementedError("--mu_transfer needs the un-vendored mup fork (MuAdamW, set_base_shapes): not built")
     P = lambda n: importlib.import_module("1xgpt_amd." + n)  # noqa: E731
@@ -157,6 +179,8 @@ def main():
                              f"{name} dataset has no actions.bin")
             get_train_acts, get_eval_acts = tds.action_batch, eds.action_batch
 
+    if frame_weights is not None and len(frame_weights) != cfg.T:
+        sys.exit(f"train.py: --frame_loss_weights has {len(frame_weights)} entries, the window has {cfg.T} frames")
     load_from = args.resume_from_checkpoint or args.warmstart_path
     warm_actions = cfg.action_vocab_size if (args.warmstart_path and not args.resume_from_checkpoint) else None
     warm_dim = cfg.action_dim if (args.warmstart_path and not args.resume_from_checkpoint) else None
@@ -195,7 +219,8 @@ def main():
     tr = trainmod.GenieTrainer(model, lr=args.learning_rate, betas=(args.adam_beta_1, args.adam_beta_2), eps=args.adam_eps,
                                weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm,
                                gradient_accumulation_steps=accum, lr_lambda=lr_lambda, recompute=args.recompute_activations,
-                               dropout_seed=args.dropout_seed, ema_decay=args.ema_decay, ema_warmup=args.ema_warmup)
+                               dropout_seed=args.dropout_seed, ema_decay=args.ema_decay, ema_warmup=args.ema_warmup,
+                               label_smoothing=args.label_smoothing, z_loss=args.z_loss, frame_weights=frame_weights)
     if args.resume_from_checkpoint:  # optimizer moments, step counters (train.py:560-590), the EMA of the weights
         tr.load_state_dict(torch.load(os.path.join(args.resume_from_checkpoint, "trainer_state.pt"), map_location=dev))
     n_params = sum(p.numel() for p in model.parameters())
@@ -221,7 +246,8 @@ def main():
 
     ckpt_every = int(args.checkpointing_steps) if args.checkpointing_steps.isdigit() else None
     completed, t0 = tr.completed_steps, time.time()
-    loss_info = torch.zeros(2, dtype=torch.float64, device=dev)
+    with_ce = tr._objective is not None   # a training objective: the step also reports the plain CE
+    loss_info = torch.zeros(3 if with_ce else 2, dtype=torch.float64, device=dev)   # sum loss, clips [, sum plain CE]
     consumed = completed * accum  # micro-batches already trained on (resume): skip them in the data order
     for epoch in range(consumed // micro_per_epoch, 10 ** 9):
         g = torch.Generator().manual_seed((args.seed or 0) + epoch)
@@ -232,17 +258,19 @@ def main():
                                             action_dropout=args.action_dropout if conditioned else 0.0,
                                             null_action=args.null_action)
             out = tr.train_step(batch)
-            loss_info += torch.stack([out["loss"] * B, torch.tensor(float(B), device=dev, dtype=torch.float64)])
+            loss_info += torch.stack([out["loss"] * B, torch.tensor(float(B), device=dev, dtype=torch.float64)]
+                                     + ([out["ce"] * B] if with_ce else []))
             if "lr" not in out:
                 continue
             completed += 1
             if world > 1:
                 torch.distributed.all_reduce(loss_info)
             avg = (loss_info[0] / loss_info[1]).item()
+            ce = f" ce {(loss_info[2] / loss_info[1]).item():.4f}" if with_ce else ""
             loss_info.zero_()
             if rank == 0:
                 dt, t0 = time.time() - t0, time.time()
-                print(f"step {completed}: train_loss {avg:.4f} ppl {math.exp(min(avg, 50)):.1f} lr {out['lr']:.3e} "
+                print(f"step {completed}: train_loss {avg:.4f}{ce} ppl {math.exp(min(avg, 50)):.1f} lr {out['lr']:.3e} "
                       f"|g| {float(out['grad_norm']):.3f} {B * accum * world / dt:.1f} examples/s", flush=True)
             if completed % args.eval_every_n_steps == 0 or completed == max_steps:
                 el, ea = evaluate()
