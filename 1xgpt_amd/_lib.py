@@ -278,6 +278,11 @@ del _a
 SIGNATURES["genie_ema_update"] = (C.c_int, [c_ptr, c_ptr, C.c_size_t, C.c_float, c_ptr])
 SIGNATURES["genie_swap_f32"] = (C.c_int, [c_ptr, c_ptr, C.c_size_t, c_ptr])
 
+# frozen tensors: genie_train_pack_weights' arguments with a `select` table (NULL = every Linear) in front of the stream
+_a = SIGNATURES["genie_train_pack_weights"][1]
+SIGNATURES["genie_train_pack_weights_some"] = (C.c_int, _a[:-1] + [C.POINTER(Weights), c_ptr])
+del _a
+
 _lib = None
 
 

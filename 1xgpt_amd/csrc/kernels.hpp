@@ -292,7 +292,8 @@ int launch_pack_bf16(const float* src, uint16_t* dst, size_t n, hipStream_t st);
 int launch_gemm_f32_gen(bool ta, bool tb, const float* A, long lda, long sA1, long sA2, const float* W, long ldw, long sW1,
                         long sW2, const float* bias, const float* R, float* C, long ldc, long sC1, long sC2, int M, int N,
                         int K, int batch1, int batch2, int nsplit, long sCsplit, float alpha, hipStream_t st);
-int launch_slab_reduce(const float* part, int ns, size_t n, float* out, float beta, hipStream_t st);
+// what: NULL, or a string LITERAL under which the launch is bracketed for the profile (genie_profile_kernels, GENIE_KC_OTHER)
+int launch_slab_reduce(const float* part, int ns, size_t n, float* out, float beta, hipStream_t st, const char* what = nullptr);
 int launch_wgrad_f32(const float* dY, long ldy, const float* X, long ldx, float* dW, int Mtok, int N, int K, float alpha,
                      float beta, float* slabs, size_t slab_floats, hipStream_t st);
 constexpr int COLSUM_CHUNKS = 256;  // row chunks of the two-stage column sums (= slabs of their scratch)

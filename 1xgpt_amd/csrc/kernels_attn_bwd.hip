@@ -502,7 +502,7 @@ int launch_attn_temporal_bwd(const float* qkv, const float* qk, long qk_ld, cons
                       "temporal attention backward: T=%d > 16 needs T in {32, 64} and head_dim in {32, 64}, not %d", T, Dh);
     const long n_grp = (long)B * S * H;
     if (n_grp <= 0) return GENIE_OK;
-    ProfScope prof(GENIE_KC_ATTN_TEMPORAL, 10.0 * n_grp * T * T * Dh, 4.0 * n_grp * T * Dh * 7, st);
+    ProfScope prof(GENIE_KC_ATTN_TEMPORAL, 10.0 * n_grp * T * T * Dh, 4.0 * n_grp * T * Dh * 7, st, "attn_temporal_bwd");
     const unsigned blocks = (unsigned)((n_grp + 3) / 4);
     if (T >= 16 && (Dh == 64 || Dh == 32)) {   // T is 16, 32 or 64 here
         const long n_bs = (long)B * S;
@@ -842,12 +842,12 @@ __global__ __launch_bounds__(256) void qk_norm_fwd_kernel(const float* __restric
         make_float4(a * rstd * g.x + bb.x, b * rstd * g.y + bb.y, c * rstd * g.z + bb.z, e * rstd * g.w + bb.w);
 }
 constexpr int QKN_BLOCKS = 512;
-template <int DH>
+// PARAMS = false (the shared affine's two gradients frozen): dqkv alone -- no dg / db accumulators, no LDS, `part` is not touched
+template <int DH, bool PARAMS>
 __global__ __launch_bounds__(256) void qk_norm_bwd_kernel(const float* __restrict__ qkv, float* __restrict__ dqkv,
                                                           const float* __restrict__ nw, float* __restrict__ part,
                                                           long n_items, int H, int d) {
     constexpr int LPI = DH / 4, IPB = 256 / LPI;
-    __shared__ float red[256][8];
     const int sub = threadIdx.x % LPI;
     const float4 g = *reinterpret_cast<const float4*>(nw + sub * 4);
     float dg[4] = {0.f, 0.f, 0.f, 0.f}, db[4] = {0.f, 0.f, 0.f, 0.f};
@@ -869,22 +869,24 @@ __global__ __launch_bounds__(256) void qk_norm_bwd_kernel(const float* __restric
             gy[k] = dyv[k] * gv[k];
             s1 += gy[k];
             s2 += gy[k] * xh[k];
-            dg[k] += dyv[k] * xh[k];
-            db[k] += dyv[k];
+            if constexpr (PARAMS) { dg[k] += dyv[k] * xh[k]; db[k] += dyv[k]; }
         }
         s1 = sub_sum<LPI>(s1) * (1.0f / DH);
         s2 = sub_sum<LPI>(s2) * (1.0f / DH);
         *reinterpret_cast<float4*>(dqkv + off) = make_float4((gy[0] - s1 - xh[0] * s2) * rstd, (gy[1] - s1 - xh[1] * s2) * rstd,
                                                             (gy[2] - s1 - xh[2] * s2) * rstd, (gy[3] - s1 - xh[3] * s2) * rstd);
     }
+    if constexpr (PARAMS) {
+        __shared__ float red[256][8];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { red[threadIdx.x][k] = dg[k]; red[threadIdx.x][4 + k] = db[k]; }
-    __syncthreads();
-    if (threadIdx.x < 2 * DH) {  // part[block][which][DH]: channel c is held by the threads with sub == c/4
-        const int which = threadIdx.x / DH, c = threadIdx.x - which * DH;
-        float s = 0.f;
-        for (int t = c / 4; t < 256; t += LPI) s += red[t][which * 4 + (c & 3)];
-        part[(size_t)blockIdx.x * 2 * DH + threadIdx.x] = s;
+        for (int k = 0; k < 4; ++k) { red[threadIdx.x][k] = dg[k]; red[threadIdx.x][4 + k] = db[k]; }
+        __syncthreads();
+        if (threadIdx.x < 2 * DH) {  // part[block][which][DH]: channel c is held by the threads with sub == c/4
+            const int which = threadIdx.x / DH, c = threadIdx.x - which * DH;
+            float s = 0.f;
+            for (int t = c / 4; t < 256; t += LPI) s += red[t][which * 4 + (c & 3)];
+            part[(size_t)blockIdx.x * 2 * DH + threadIdx.x] = s;
+        }
     }
 }
 int launch_qk_norm_fwd(const float* qkv, float* qkn, const float* nw, const float* nb, long M, int H, int Dh, int d,
@@ -899,20 +901,29 @@ int launch_qk_norm_fwd(const float* qkv, float* qkn, const float* nw, const floa
     GENIE_LAUNCH_CHECK("qk_norm_fwd");
     return GENIE_OK;
 }
-// in place on the q,k columns of dqkv; dnw/dnb (Dh) = beta * old + sums over rows, q and k, and heads
+// in place on the q,k columns of dqkv; dnw/dnb (Dh) = beta * old + sums over rows, q and k, and heads.  A NULL dnw / dnb is a frozen
+// tensor (include/genie_hip.h, "Frozen tensors"): its half is not reduced; both NULL: the parameter-free kernel and no reduction at all
 int launch_qk_norm_bwd(const float* qkv, float* dqkv, const float* nw, float* dnw, float* dnb, long M, int H, int Dh,
                        int d, float beta, float* part, hipStream_t st) {
     const long n_items = M * 2 * H;
     if (n_items <= 0) return GENIE_OK;
-    if (Dh == 64) qk_norm_bwd_kernel<64><<<QKN_BLOCKS, 256, 0, st>>>(qkv, dqkv, nw, part, n_items, H, d);
-    else if (Dh == 32) qk_norm_bwd_kernel<32><<<QKN_BLOCKS, 256, 0, st>>>(qkv, dqkv, nw, part, n_items, H, d);
-    else if (Dh == 128) qk_norm_bwd_kernel<128><<<QKN_BLOCKS, 256, 0, st>>>(qkv, dqkv, nw, part, n_items, H, d);
+    if (!dnw && !dnb) {
+        if (Dh == 64) qk_norm_bwd_kernel<64, false><<<QKN_BLOCKS, 256, 0, st>>>(qkv, dqkv, nw, nullptr, n_items, H, d);
+        else if (Dh == 32) qk_norm_bwd_kernel<32, false><<<QKN_BLOCKS, 256, 0, st>>>(qkv, dqkv, nw, nullptr, n_items, H, d);
+        else if (Dh == 128) qk_norm_bwd_kernel<128, false><<<QKN_BLOCKS, 256, 0, st>>>(qkv, dqkv, nw, nullptr, n_items, H, d);
+        else { set_error("qk-norm: head_dim %d not in {32, 64, 128}", Dh); return GENIE_E_UNSUPPORTED; }
+        GENIE_LAUNCH_CHECK("qk_norm_bwd");
+        return GENIE_OK;
+    }
+    if (Dh == 64) qk_norm_bwd_kernel<64, true><<<QKN_BLOCKS, 256, 0, st>>>(qkv, dqkv, nw, part, n_items, H, d);
+    else if (Dh == 32) qk_norm_bwd_kernel<32, true><<<QKN_BLOCKS, 256, 0, st>>>(qkv, dqkv, nw, part, n_items, H, d);
+    else if (Dh == 128) qk_norm_bwd_kernel<128, true><<<QKN_BLOCKS, 256, 0, st>>>(qkv, dqkv, nw, part, n_items, H, d);
     else { set_error("qk-norm: head_dim %d not in {32, 64, 128}", Dh); return GENIE_E_UNSUPPORTED; }
     GENIE_LAUNCH_CHECK("qk_norm_bwd");
     float* tmp = part + (size_t)QKN_BLOCKS * 2 * Dh;
-    GENIE_TRY(launch_slab_reduce(part, QKN_BLOCKS, (size_t)2 * Dh, tmp, 0.f, st));
-    GENIE_TRY(launch_slab_reduce(tmp, 1, (size_t)Dh, dnw, beta, st));
-    return launch_slab_reduce(tmp + Dh, 1, (size_t)Dh, dnb, beta, st);
+    GENIE_TRY(launch_slab_reduce(part, QKN_BLOCKS, (size_t)2 * Dh, tmp, 0.f, st, "slab_reduce_norm"));
+    if (dnw) GENIE_TRY(launch_slab_reduce(tmp, 1, (size_t)Dh, dnw, beta, st, "slab_reduce_norm"));
+    return dnb ? launch_slab_reduce(tmp + Dh, 1, (size_t)Dh, dnb, beta, st, "slab_reduce_norm") : GENIE_OK;
 }
 
 }  // namespace genie

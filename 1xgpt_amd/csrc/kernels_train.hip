@@ -196,9 +196,14 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
         out[i] = (beta != 0.f ? beta * out[i] : 0.f) + s;
     }
 }
-int launch_slab_reduce(const float* part, int ns, size_t n, float* out, float beta, hipStream_t st) {
+int launch_slab_reduce(const float* part, int ns, size_t n, float* out, float beta, hipStream_t st, const char* what) {
     if (!n) return GENIE_OK;
-    slab_reduce_kernel<<<(unsigned)((n + 63) / 64), 256, 0, st>>>(part, ns, n, out, beta);
+    if (what) {   // a named reduction is bracketed for the profile; the others stay outside it, as they always were
+        ProfScope prof(GENIE_KC_OTHER, 0.0, 4.0 * ((double)ns + 1.0) * (double)n, st, what);
+        slab_reduce_kernel<<<(unsigned)((n + 63) / 64), 256, 0, st>>>(part, ns, n, out, beta);
+    } else {
+        slab_reduce_kernel<<<(unsigned)((n + 63) / 64), 256, 0, st>>>(part, ns, n, out, beta);
+    }
     GENIE_LAUNCH_CHECK("slab_reduce");
     return GENIE_OK;
 }
@@ -263,6 +268,8 @@ int launch_colsum(const float* Y, long ld, long rows, int N, float* out, float b
 // ------------------------------------------------------------------------------------------------
 constexpr int LNB_MAXI = 16;  // C <= 1024
 constexpr int LNB_BLOCKS = 512;
+// PARAMS = false (both parameter gradients frozen): dxout alone -- no dg / db accumulators, no LDS, `part` is not touched
+template <bool PARAMS>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                      const float* __restrict__ dy, float* __restrict__ dxout,
                                                      float* __restrict__ part, long rows, int C, float eps) {
@@ -271,7 +278,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
     float dg[LNB_MAXI], db[LNB_MAXI], gm[LNB_MAXI];
 #pragma unroll
     for (int i = 0; i < LNB_MAXI; ++i) {
-        dg[i] = 0.f; db[i] = 0.f;
+        if constexpr (PARAMS) { dg[i] = 0.f; db[i] = 0.f; }
         const int c = lane + 64 * i;
         gm[i] = c < C ? gamma[c] : 0.f;
     }
@@ -305,8 +312,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
             const float gy = dv[i] * gm[i];
             s1 += gy;
             s2 += gy * xv[i];
-            dg[i] += dv[i] * xv[i];
-            db[i] += dv[i];
+            if constexpr (PARAMS) { dg[i] += dv[i] * xv[i]; db[i] += dv[i]; }
         }
         s1 = wave_sum(s1) * invC;
         s2 = wave_sum(s2) * invC;
@@ -317,28 +323,29 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
             if (c < C) o[c] += (dv[i] * gm[i] - s1 - xv[i] * s2) * rstd;
         }
     }
+    if constexpr (PARAMS) {
 #pragma unroll
-    for (int i = 0; i < LNB_MAXI; ++i) {
-        const int c = lane + 64 * i;
-        if (c < C) { red[(wid * 2 + 0) * C + c] = dg[i]; red[(wid * 2 + 1) * C + c] = db[i]; }
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < 2 * C; c += 256) {
-        const int which = c / C, cc = c - which * C;
-        float s = 0.f;
-        for (int w = 0; w < 4; ++w) s += red[(w * 2 + which) * C + cc];
-        part[(size_t)blockIdx.x * 2 * C + c] = s;  // [block][which][C]
+        for (int i = 0; i < LNB_MAXI; ++i) {
+            const int c = lane + 64 * i;
+            if (c < C) { red[(wid * 2 + 0) * C + c] = dg[i]; red[(wid * 2 + 1) * C + c] = db[i]; }
+        }
+        __syncthreads();
+        for (int c = threadIdx.x; c < 2 * C; c += 256) {
+            const int which = c / C, cc = c - which * C;
+            float s = 0.f;
+            for (int w = 0; w < 4; ++w) s += red[(w * 2 + which) * C + cc];
+            part[(size_t)blockIdx.x * 2 * C + c] = s;  // [block][which][C]
+        }
     }
 }
 // The same for C = 256 / 512 with the access pattern of layer_norm_fast_kernel: a lane owns VPL = C/64 contiguous
 // channels (float4 loads / read-modify-write of dxout instead of 4-byte strided ones), the next row's x and dy are in
 // flight while the current row is reduced.
-template <int VPL>
+template <int VPL, bool PARAMS>
 __global__ __launch_bounds__(256) void ln_bwd_fast_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                           const float* __restrict__ dy, float* __restrict__ dxout,
                                                           float* __restrict__ part, long rows, float eps) {
     constexpr int C = 64 * VPL;
-    __shared__ float red[4][2][C];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     float dg[VPL], db[VPL], gm[VPL], xv[VPL], dv[VPL], xn[VPL], dn[VPL];
     auto load = [&](const float* p, float (&v)[VPL]) {
@@ -349,8 +356,10 @@ __global__ __launch_bounds__(256) void ln_bwd_fast_kernel(const float* __restric
         }
     };
     load(gamma, gm);
+    if constexpr (PARAMS) {
 #pragma unroll
-    for (int k = 0; k < VPL; ++k) { dg[k] = 0.f; db[k] = 0.f; }
+        for (int k = 0; k < VPL; ++k) { dg[k] = 0.f; db[k] = 0.f; }
+    }
     const long stride = (long)gridDim.x * 4;
     long row = (long)blockIdx.x * 4 + wid;
     if (row < rows) { load(x + (size_t)row * C, xv); load(dy + (size_t)row * C, dv); }
@@ -372,8 +381,7 @@ __global__ __launch_bounds__(256) void ln_bwd_fast_kernel(const float* __restric
             const float gy = dv[k] * gm[k];
             s1 += gy;
             s2 += gy * xv[k];
-            dg[k] += dv[k] * xv[k];
-            db[k] += dv[k];
+            if constexpr (PARAMS) { dg[k] += dv[k] * xv[k]; db[k] += dv[k]; }
         }
         s1 = wave_sum(s1) * (1.0f / C);
         s2 = wave_sum(s2) * (1.0f / C);
@@ -390,31 +398,42 @@ __global__ __launch_bounds__(256) void ln_bwd_fast_kernel(const float* __restric
 #pragma unroll
         for (int k = 0; k < VPL; ++k) { xv[k] = xn[k]; dv[k] = dn[k]; }
     }
+    if constexpr (PARAMS) {
+        __shared__ float red[4][2][C];
 #pragma unroll
-    for (int k = 0; k < VPL; ++k) { red[wid][0][lane * VPL + k] = dg[k]; red[wid][1][lane * VPL + k] = db[k]; }
-    __syncthreads();
-    for (int c = threadIdx.x; c < 2 * C; c += 256) {
-        const int which = c / C, cc = c - which * C;
-        part[(size_t)blockIdx.x * 2 * C + c] = ((red[0][which][cc] + red[1][which][cc]) + red[2][which][cc]) + red[3][which][cc];
+        for (int k = 0; k < VPL; ++k) { red[wid][0][lane * VPL + k] = dg[k]; red[wid][1][lane * VPL + k] = db[k]; }
+        __syncthreads();
+        for (int c = threadIdx.x; c < 2 * C; c += 256) {
+            const int which = c / C, cc = c - which * C;
+            part[(size_t)blockIdx.x * 2 * C + c] = ((red[0][which][cc] + red[1][which][cc]) + red[2][which][cc]) + red[3][which][cc];
+        }
     }
 }
 
-// part slabs are [block][2][C]: dgamma = reduce of the first C, dbeta of the second C
+// part slabs are [block][2][C]: dgamma = reduce of the first C, dbeta of the second C.  A NULL dgamma / dbeta is a frozen tensor
+// (include/genie_hip.h, "Frozen tensors"): its half is not reduced; both NULL: the parameter-free kernels and no reduction at all
 int launch_ln_bwd(const float* x, const float* gamma, const float* dy, float* dxout, float* dgamma, float* dbeta,
                   long rows, int C, float eps, float beta, float* part, hipStream_t st) {
     GENIE_CHECK_SHAPE(C <= 64 * LNB_MAXI, "ln_bwd: C=%d > %d", C, 64 * LNB_MAXI);
     if (rows <= 0) return GENIE_OK;
     ProfScope prof(GENIE_KC_LAYERNORM, 12.0 * rows * C, 16.0 * rows * C, st);
-    if (C == 512) ln_bwd_fast_kernel<8><<<LNB_BLOCKS, 256, 0, st>>>(x, gamma, dy, dxout, part, rows, eps);
-    else if (C == 256) ln_bwd_fast_kernel<4><<<LNB_BLOCKS, 256, 0, st>>>(x, gamma, dy, dxout, part, rows, eps);
-    else ln_bwd_kernel<<<LNB_BLOCKS, 256, (size_t)8 * C * sizeof(float), st>>>(x, gamma, dy, dxout, part, rows, C, eps);
+    if (!dgamma && !dbeta) {
+        if (C == 512) ln_bwd_fast_kernel<8, false><<<LNB_BLOCKS, 256, 0, st>>>(x, gamma, dy, dxout, nullptr, rows, eps);
+        else if (C == 256) ln_bwd_fast_kernel<4, false><<<LNB_BLOCKS, 256, 0, st>>>(x, gamma, dy, dxout, nullptr, rows, eps);
+        else ln_bwd_kernel<false><<<LNB_BLOCKS, 256, 0, st>>>(x, gamma, dy, dxout, nullptr, rows, C, eps);
+        GENIE_LAUNCH_CHECK("ln_bwd");
+        return GENIE_OK;
+    }
+    if (C == 512) ln_bwd_fast_kernel<8, true><<<LNB_BLOCKS, 256, 0, st>>>(x, gamma, dy, dxout, part, rows, eps);
+    else if (C == 256) ln_bwd_fast_kernel<4, true><<<LNB_BLOCKS, 256, 0, st>>>(x, gamma, dy, dxout, part, rows, eps);
+    else ln_bwd_kernel<true><<<LNB_BLOCKS, 256, (size_t)8 * C * sizeof(float), st>>>(x, gamma, dy, dxout, part, rows, C, eps);
     GENIE_LAUNCH_CHECK("ln_bwd");
     // the two halves of each slab are contiguous ([2][C]), so one reduce of 2C columns serves both when dbeta follows
     // dgamma in memory; they need not, so reduce separately through strided views
     float* tmp = part + (size_t)LNB_BLOCKS * 2 * C;  // [2][C] reduced
-    GENIE_TRY(launch_slab_reduce(part, LNB_BLOCKS, (size_t)2 * C, tmp, 0.f, st));
-    GENIE_TRY(launch_slab_reduce(tmp, 1, (size_t)C, dgamma, beta, st));
-    return launch_slab_reduce(tmp + C, 1, (size_t)C, dbeta, beta, st);
+    GENIE_TRY(launch_slab_reduce(part, LNB_BLOCKS, (size_t)2 * C, tmp, 0.f, st, "slab_reduce_norm"));
+    if (dgamma) GENIE_TRY(launch_slab_reduce(tmp, 1, (size_t)C, dgamma, beta, st, "slab_reduce_norm"));
+    return dbeta ? launch_slab_reduce(tmp + C, 1, (size_t)C, dbeta, beta, st, "slab_reduce_norm") : GENIE_OK;
 }
 size_t ln_bwd_scratch_floats(int C) { return (size_t)(LNB_BLOCKS + 1) * 2 * C; }
 
@@ -736,6 +755,7 @@ __global__ __launch_bounds__(256) void embed_bwd_tables_kernel(const float* __re
     const int blk = blockIdx.x;
     constexpr bool is_mask_row = false;
     const int f = blk / vf, v = blk - f * vf;
+    if (!tables.p[f]) return;   // a frozen table: the whole block leaves, in front of every barrier
     int64_t div = 1;
     for (int k = 0; k < f; ++k) div *= vf;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -780,16 +800,26 @@ __global__ __launch_bounds__(256) void embed_bwd_tables_kernel(const float* __re
 }
 int launch_embed_bwd(const genie_cfg& c, const float* dx, const int64_t* ids, int B, float* dpos, float* dmask,
                      float* const* tables_host, float beta, float* colpart, hipStream_t st) {
+    // dpos, dmask and each table may be NULL: a frozen tensor (include/genie_hip.h, "Frozen tensors"), whose part is skipped
     EmbedTables tables_dev;
-    for (int j = 0; j < 4; ++j) tables_dev.p[j] = j < c.num_factored ? tables_host[j] : nullptr;
+    bool any_table = false;
+    for (int j = 0; j < 4; ++j) {
+        tables_dev.p[j] = j < c.num_factored ? tables_host[j] : nullptr;
+        any_table = any_table || tables_dev.p[j];
+    }
     GENIE_CHECK_SHAPE(c.d_model <= 1024, "embed backward: d_model > 1024");
     const size_t per_clip = (size_t)c.T * c.S * c.d_model;
-    embed_bwd_pos_kernel<<<(unsigned)((per_clip + 255) / 256), 256, 0, st>>>(dx, dpos, B, per_clip, beta);
-    GENIE_LAUNCH_CHECK("embed_bwd_pos");
-    embed_bwd_tables_kernel<<<c.num_factored * c.factored_vocab, 256, 0, st>>>(
-        dx, ids, (long)B * c.T * c.S, c.d_model, c.factored_vocab, c.num_factored, (int64_t)c.image_vocab_size, tables_dev,
-        dmask, beta);
-    GENIE_LAUNCH_CHECK("embed_bwd_tables");
+    if (dpos) {
+        embed_bwd_pos_kernel<<<(unsigned)((per_clip + 255) / 256), 256, 0, st>>>(dx, dpos, B, per_clip, beta);
+        GENIE_LAUNCH_CHECK("embed_bwd_pos");
+    }
+    if (any_table) {
+        embed_bwd_tables_kernel<<<c.num_factored * c.factored_vocab, 256, 0, st>>>(
+            dx, ids, (long)B * c.T * c.S, c.d_model, c.factored_vocab, c.num_factored, (int64_t)c.image_vocab_size, tables_dev,
+            dmask, beta);
+        GENIE_LAUNCH_CHECK("embed_bwd_tables");
+    }
+    if (!dmask) return GENIE_OK;
     return launch_colsum_where(dx, c.d_model, (long)B * c.T * c.S, c.d_model, ids, (int64_t)c.image_vocab_size, dmask, beta,
                                colpart, st);
 }

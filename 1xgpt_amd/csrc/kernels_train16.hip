@@ -23,11 +23,13 @@ __device__ __forceinline__ float gelu_grad16(float z) {
 }
 
 // in (rows, cols) f32 row-major (leading dim ld) -> out16 (rows, cols) [optional] and out16T (cols, rows)
-template <int NPL, int MODE>
+// TR = false: the rows-only form (the weight of this gradient is frozen, so no product reads its transposed planes): out16, the
+// write-back and the column sums exactly as with TR = true -- same values, same summation order -- and no tile, no out16T
+template <int NPL, int MODE, bool TR>
 __global__ __launch_bounds__(256) void cast_transpose_kernel(float* __restrict__ in, long ld, const float* __restrict__ z,
                                                              uint16_t* __restrict__ out16, uint16_t* __restrict__ out16T,
                                                              int rows, int cols, float* __restrict__ colpart, float scale16) {
-    __shared__ uint16_t tile[NPL][64][66];
+    __shared__ uint16_t tile[TR ? NPL : 1][TR ? 64 : 1][TR ? 66 : 1];
     __shared__ float csum[4][64];
     float cs = 0.f;  // column c0+tx over this thread's 16 rows (bias gradient partial)
     const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
@@ -49,8 +51,10 @@ __global__ __launch_bounds__(256) void cast_transpose_kernel(float* __restrict__
             v = v > 65504.0f ? 65504.0f : (v < -65504.0f ? -65504.0f : v);
         }
         to16<NPL>(v, hi, lo);
-        tile[0][rl][tx] = hi;
-        if constexpr (NPL == 2) tile[1][rl][tx] = lo;
+        if constexpr (TR) {
+            tile[0][rl][tx] = hi;
+            if constexpr (NPL == 2) tile[1][rl][tx] = lo;
+        }
         if (out16) {
             const size_t dst = (size_t)(r0 + rl) * cols + c0 + tx;
             out16[dst] = hi;
@@ -61,12 +65,14 @@ __global__ __launch_bounds__(256) void cast_transpose_kernel(float* __restrict__
     __syncthreads();
     if (colpart && ty == 0)
         colpart[(size_t)blockIdx.y * cols + c0 + tx] = ((csum[0][tx] + csum[1][tx]) + csum[2][tx]) + csum[3][tx];
+    if constexpr (TR) {
 #pragma unroll 4
-    for (int i = 0; i < 16; ++i) {
-        const int cl = ty * 16 + i;
-        const size_t dst = (size_t)(c0 + cl) * rows + r0 + tx;
-        out16T[dst] = tile[0][tx][cl];
-        if constexpr (NPL == 2) out16T[plane + dst] = tile[1][tx][cl];
+        for (int i = 0; i < 16; ++i) {
+            const int cl = ty * 16 + i;
+            const size_t dst = (size_t)(c0 + cl) * rows + r0 + tx;
+            out16T[dst] = tile[0][tx][cl];
+            if constexpr (NPL == 2) out16T[plane + dst] = tile[1][tx][cl];
+        }
     }
 }
 
@@ -155,20 +161,24 @@ static int check64(int rows, int cols, const char* what) {
     return GENIE_OK;
 }
 
-// mode 0: plain cast; mode 1: in *= gelu'(z) first (in place).  out16 may be NULL.
+// mode 0: plain cast; mode 1: in *= gelu'(z) first (in place).  out16 may be NULL; or out16T (the rows-only form), not both.
 int launch_cast_transpose16(int npl, float* in, long ld, const float* z, uint16_t* out16, uint16_t* out16T, int rows,
                             int cols, hipStream_t st, float* colpart, float scale16) {
     GENIE_TRY(check64(rows, cols, "cast_transpose16"));
+    GENIE_CHECK_ARG(out16 || out16T, "cast_transpose16: no output");
     if (!rows || !cols) return GENIE_OK;
     dim3 grid(cols / 64, rows / 64);
-    ProfScope prof(GENIE_KC_OTHER, 0.0, (double)rows * cols * (4.0 + (z ? 8.0 : 0.0) + 2.0 * npl * (out16 ? 2 : 1)), st);
-    if (npl == 1) {
-        if (z) cast_transpose_kernel<1, 1><<<grid, 256, 0, st>>>(in, ld, z, out16, out16T, rows, cols, colpart, scale16);
-        else cast_transpose_kernel<1, 0><<<grid, 256, 0, st>>>(in, ld, nullptr, out16, out16T, rows, cols, colpart, scale16);
+    ProfScope prof(GENIE_KC_OTHER, 0.0, (double)rows * cols * (4.0 + (z ? 8.0 : 0.0) + 2.0 * npl * (out16 && out16T ? 2 : 1)), st);
+#define CT_LAUNCH(NPL_, MODE_, TR_) \
+    cast_transpose_kernel<NPL_, MODE_, TR_><<<grid, 256, 0, st>>>(in, ld, z, out16, out16T, rows, cols, colpart, scale16)
+    if (out16T) {
+        if (npl == 1) { if (z) CT_LAUNCH(1, 1, true); else CT_LAUNCH(1, 0, true); }
+        else { if (z) CT_LAUNCH(2, 1, true); else CT_LAUNCH(2, 0, true); }
     } else {
-        if (z) cast_transpose_kernel<2, 1><<<grid, 256, 0, st>>>(in, ld, z, out16, out16T, rows, cols, colpart, scale16);
-        else cast_transpose_kernel<2, 0><<<grid, 256, 0, st>>>(in, ld, nullptr, out16, out16T, rows, cols, colpart, scale16);
+        if (npl == 1) { if (z) CT_LAUNCH(1, 1, false); else CT_LAUNCH(1, 0, false); }
+        else { if (z) CT_LAUNCH(2, 1, false); else CT_LAUNCH(2, 0, false); }
     }
+#undef CT_LAUNCH
     GENIE_LAUNCH_CHECK("cast_transpose16");
     return GENIE_OK;
 }

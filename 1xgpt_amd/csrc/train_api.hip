@@ -153,7 +153,8 @@ static int train_check(const genie_cfg* c, int B) {
 }
 
 // one Linear y = x . W^T + b, W (N,K): the weight in every form a backend reads (wT16: the transposed 16-bit copy the 16-bit dgrad
-// multiplies with), its bias (NULL: none) and, in the backward, where its gradients go
+// multiplies with), its bias (NULL: none) and, in the backward, where its gradients go (dw NULL: the weight is frozen; db NULL: no
+// bias, or the bias is frozen -- include/genie_hip.h, "Frozen tensors")
 struct Lin {
     const float* w; const uint16_t *w16, *wT16; const float* b;
     float *dw, *db;
@@ -411,7 +412,7 @@ struct ExactOps {
     // dx = alpha * dy . W (+ R), W (N,K) read k-major
     int linear_backward(float* dy, const Operand* x, const Lin& l, const float* z, const float* R, float* dx, float alpha = 1.0f) {
         if (z) GENIE_TRY(launch_gelu_bwd(z, dy, (size_t)M * l.N, st));
-        GENIE_TRY(launch_wgrad_f32(dy, l.N, x, l.K, l.dw, M, l.N, l.K, alpha, beta, w.slabs, w.slab_floats, st));
+        if (l.dw) GENIE_TRY(launch_wgrad_f32(dy, l.N, x, l.K, l.dw, M, l.N, l.K, alpha, beta, w.slabs, w.slab_floats, st));
         if (l.db) GENIE_TRY(launch_colsum(dy, l.N, M, l.N, l.db, beta, w.colpart, st));
         return launch_gemm_f32_gen(false, true, dy, l.N, 0, 0, l.w, l.K, 0, 0, nullptr, R, dx, l.K, 0, 0, M, l.K, l.N, 1, 1, 1, 0,
                                    alpha, st);
@@ -463,13 +464,15 @@ struct Ops16 {
     // linear_backward that read them take alpha / grad_scale16(), exact in f32.  bf16: 1.
     float grad_scale16() const { return npl == 2 ? GRAD_SCALE16 : 1.0f; }
     // 16-bit copies of a gradient matrix (row-major, and transposed unless its weight gradient takes the TN kernel: Kw = the K of
-    // that weight gradient), with gelu'(z) applied when z, and, in the same pass, its column sums (= the bias gradient)
-    int cast_t_bias(float* in, int cols, const float* z, float* dbias, int Kw) {
+    // that weight gradient), with gelu'(z) applied when z, and, in the same pass, its column sums (= the bias gradient).
+    // transposed = false (the weight is frozen): the row-major copy alone, from the kernel that would have made both -- the same
+    // bits in h.dy16 and the same slabs in w.colpart
+    int cast_t_bias(float* in, int cols, const float* z, float* dbias, int Kw, bool transposed) {
         if (use_tn(npl, M, cols, Kw))
             GENIE_TRY(launch_cast_rows16(in, cols, z, h.dy16, M, cols, st, dbias ? w.colpart : nullptr));
         else
-            GENIE_TRY(launch_cast_transpose16(npl, in, cols, z, h.dy16, h.dy16T, M, cols, st, dbias ? w.colpart : nullptr,
-                                              grad_scale16()));
+            GENIE_TRY(launch_cast_transpose16(npl, in, cols, z, h.dy16, transposed ? h.dy16T : nullptr, M, cols, st,
+                                              dbias ? w.colpart : nullptr, grad_scale16()));
         return dbias ? launch_slab_reduce(w.colpart, M / 64, (size_t)cols, dbias, beta, st) : GENIE_OK;
     }
     // weight gradient from the gradient copies in `h` and the saved row-major 16-bit activation X16 (M, K)
@@ -484,8 +487,8 @@ struct Ops16 {
     }
     int linear_backward(float* dy, const Operand* x, const Lin& l, const float* z, const float* R, float* dx, float alpha = 1.0f) {
         const float ga = alpha / grad_scale16();
-        GENIE_TRY(cast_t_bias(dy, l.N, z, l.db, l.K));
-        GENIE_TRY(wgrad_any(x, l.dw, l.N, l.K, ga));
+        GENIE_TRY(cast_t_bias(dy, l.N, z, l.db, l.K, l.dw != nullptr));
+        if (l.dw) GENIE_TRY(wgrad_any(x, l.dw, l.N, l.K, ga));
         return lin16(npl, h.dy16, l.wT16, nullptr, R, dx, nullptr, M, l.K, l.N, ga, st);
     }
 };
@@ -665,26 +668,35 @@ size_t genie_train_workspace_bytes_ex(const genie_cfg* cfg, int B, int recompute
 
 int genie_train_pack_weights(const genie_cfg* cfg, const genie_weights* w, const genie_weights* w16,
                              const genie_weights* w16T, void* stream) {
+    return genie_train_pack_weights_some(cfg, w, w16, w16T, nullptr, stream);
+}
+
+// select: NULL packs every Linear; else only those whose *_w member in it is non-NULL (the trainer's gradient table: a frozen
+// weight has not moved, its copies are current)
+int genie_train_pack_weights_some(const genie_cfg* cfg, const genie_weights* w, const genie_weights* w16,
+                                  const genie_weights* w16T, const genie_weights* select, void* stream) {
     GENIE_CHECK_ARG(cfg && w && w16 && w16T, "genie_train_pack_weights: NULL argument");
     GENIE_CHECK_ARG(cfg->precision != GENIE_PREC_EXACT, "genie_train_pack_weights: exact precision has no 16-bit copies");
     const genie_cfg& c = *cfg;
     const int npl = npl_of(c), d = c.d_model, hid = c.hidden, V = c.factored_vocab * c.num_factored;
     hipStream_t st = (hipStream_t)stream;
-    auto pack = [&](const float* src, const uint16_t* rowm, const uint16_t* tr, int out, int in) -> int {
+    auto pack = [&](bool wanted, const float* src, const uint16_t* rowm, const uint16_t* tr, int out, int in) -> int {
+        if (!wanted) return GENIE_OK;
         GENIE_CHECK_ARG(src && rowm && tr, "genie_train_pack_weights: missing pointer");
         GENIE_TRY(launch_cast16(npl, src, (uint16_t*)rowm, (size_t)out * in, st));
         return launch_cast_transpose16(npl, (float*)src, in, nullptr, nullptr, (uint16_t*)tr, out, in, st);
     };
     for (int l = 0; l < c.num_layers; ++l) {
         const genie_layer_weights &a = w->layers_host[l], &b = w16->layers_host[l], &t = w16T->layers_host[l];
-        GENIE_TRY(pack(a.spatial.qkv_w, b.spatial.qkv_w16, t.spatial.qkv_w16, 3 * d, d));
-        GENIE_TRY(pack(a.spatial.proj_w, b.spatial.proj_w16, t.spatial.proj_w16, d, d));
-        GENIE_TRY(pack(a.temporal.qkv_w, b.temporal.qkv_w16, t.temporal.qkv_w16, 3 * d, d));
-        GENIE_TRY(pack(a.temporal.proj_w, b.temporal.proj_w16, t.temporal.proj_w16, d, d));
-        GENIE_TRY(pack(a.fc1_w, b.fc1_w16, t.fc1_w16, hid, d));
-        GENIE_TRY(pack(a.fc2_w, b.fc2_w16, t.fc2_w16, d, hid));
+        const genie_layer_weights* s = select ? &select->layers_host[l] : nullptr;
+        GENIE_TRY(pack(!s || s->spatial.qkv_w, a.spatial.qkv_w, b.spatial.qkv_w16, t.spatial.qkv_w16, 3 * d, d));
+        GENIE_TRY(pack(!s || s->spatial.proj_w, a.spatial.proj_w, b.spatial.proj_w16, t.spatial.proj_w16, d, d));
+        GENIE_TRY(pack(!s || s->temporal.qkv_w, a.temporal.qkv_w, b.temporal.qkv_w16, t.temporal.qkv_w16, 3 * d, d));
+        GENIE_TRY(pack(!s || s->temporal.proj_w, a.temporal.proj_w, b.temporal.proj_w16, t.temporal.proj_w16, d, d));
+        GENIE_TRY(pack(!s || s->fc1_w, a.fc1_w, b.fc1_w16, t.fc1_w16, hid, d));
+        GENIE_TRY(pack(!s || s->fc2_w, a.fc2_w, b.fc2_w16, t.fc2_w16, d, hid));
     }
-    return pack(w->out_w, w16->out_w16, w16T->out_w16, V, d);
+    return pack(!select || select->out_w, w->out_w, w16->out_w16, w16T->out_w16, V, d);
 }
 
 int genie_train_forward(const genie_cfg* cfg, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels,
@@ -836,6 +848,7 @@ int genie_train_backward_embed_cond(const genie_cfg* cfg, const genie_weights* g
     for (int j = 0; j < cfg->num_factored && j < 4; ++j) tables[j] = (float*)grads->embed[j];
     const float beta = accumulate ? 1.0f : 0.0f;
     hipStream_t st = (hipStream_t)stream;
+    // NULL members are frozen tensors: launch_embed_bwd skips each one's part (all of them: nothing is enqueued)
     GENIE_TRY(launch_embed_bwd(*cfg, w.dx, input_ids, B, (float*)grads->pos_embed, (float*)grads->mask_embed, tables, beta,
                                w.colpart, st));
     if (!act) return GENIE_OK;

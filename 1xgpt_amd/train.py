@@ -25,6 +25,7 @@ MuAdamW (--mu_transfer, train.py:439; third-party mup fork) is not built.
 """
 import contextlib
 import ctypes as C
+import fnmatch
 import math
 import warnings
 
@@ -183,6 +184,124 @@ def ready_order(config, names):
     return out
 
 
+# ------------------------------------------------------------------ training a subset of the weights
+def _patterns(p):
+    """None, one comma-separated string or an iterable of fnmatch patterns -> list of patterns (None stays None)."""
+    if p is None:
+        return None
+    return [q for q in p.split(",") if q] if isinstance(p, str) else list(p)
+
+
+def select_trainable(names, train_only=None, freeze=None):
+    """The set of trainable state-dict names: those matching a `train_only` pattern (None: every name) and no `freeze` pattern.
+    Patterns are fnmatch patterns, case-sensitive, over the whole name ("action_*", "decoder.layers.3[01].*", "*.bias"); each argument
+    is a list of them or one comma-separated string.  Raises ValueError for a pattern that matches no name (a typo would otherwise
+    freeze or train silently) and for an empty result."""
+    names = list(names)
+    chosen = set(names)
+    for what, pats in (("train_only", _patterns(train_only)), ("freeze", _patterns(freeze))):
+        if pats is None:
+            continue
+        hit = set()
+        for p in pats:
+            m = [n for n in names if fnmatch.fnmatchcase(n, p)]
+            if not m:
+                raise ValueError(f"{what} pattern {p!r} matches no parameter name")
+            hit.update(m)
+        chosen = chosen & hit if what == "train_only" else chosen - hit
+    if not chosen:
+        raise ValueError("no trainable parameter is left: train_only / freeze select nothing")
+    return chosen
+
+
+def lr_factors(names, lr_scale=None):
+    """{name: factor} of `lr_scale` = {pattern: factor}: the factor of the first pattern (in the mapping's order) that matches the name,
+    1.0 when none does.  Raises ValueError for a factor that is not finite and > 0, and for a pattern that matches no name."""
+    names = list(names)
+    out = {n: 1.0 for n in names}
+    if not lr_scale:
+        return out
+    seen = set()
+    for p, f in lr_scale.items():
+        f = float(f)
+        if not (f > 0.0 and math.isfinite(f)):
+            raise ValueError(f"lr_scale[{p!r}] = {f!r} must be finite and > 0")
+        m = [n for n in names if fnmatch.fnmatchcase(n, p)]
+        if not m:
+            raise ValueError(f"lr_scale pattern {p!r} matches no parameter name")
+        for n in m:
+            if n not in seen:
+                out[n] = f
+                seen.add(n)
+    return out
+
+
+def _pad64(n):
+    return (n + 63) // 64 * 64   # 256-byte aligned tensors (float4 / MFMA staging loads)
+
+
+def _layer_of(name):
+    return int(name.split(".")[2]) if name.startswith("decoder.layers.") else None
+
+
+class FlatLayout:
+    """Where every tensor lives in the flat buffers, for a set of trainable names (None: all of them).
+
+    order     trainable names in ready order, then the frozen ones in ready order
+    offsets   {name: (lo, hi)} into the parameter buffer (tensors 256-byte aligned)
+    n_flat    elements of the parameter buffer; n_train: of its trainable prefix = of the gradient, moment and EMA buffers
+    trainable the set of trainable names; all: every name is trainable
+    adam_runs [(lo, hi, decays, lr factor)]: maximal runs of consecutive trainable tensors with equal (decay flag, lr factor)
+    groups    [(key, lo, hi)] over the prefix, key "head", a layer index (L-1 .. 0) or "embed": one all-reduce segment per group that
+              holds a trainable tensor, in ready order (segments = the (lo, hi) alone)
+    stop      the backward runs layers L-1 .. stop: the lowest layer holding a trainable tensor, 0 when an embedding-side tensor
+              (action tensors included) trains, num_layers when only the readout does
+    embed     something on the embedding side trains: the embedding backward is called"""
+
+    def __init__(self, config, numels, trainable=None, lr_scale=None):
+        names = list(numels)
+        ro = ready_order(config, names)
+        self.trainable = set(names) if trainable is None else set(trainable)
+        unknown = self.trainable - set(names)
+        if unknown or not self.trainable:
+            raise ValueError(f"trainable names {sorted(unknown)} are not parameters" if unknown else "no trainable parameter")
+        self.all = len(self.trainable) == len(names)
+        self.order = [n for n in ro if n in self.trainable] + [n for n in ro if n not in self.trainable]
+        self.lr_factor = lr_factors(names, lr_scale)
+        self.offsets, o = {}, 0
+        for n in self.order:
+            self.offsets[n] = (o, o + numels[n])
+            o += _pad64(numels[n])
+        self.n_flat = o
+        prefix = self.order[:len(self.trainable)]
+        self.n_train = self.offsets[prefix[-1]][0] + _pad64(numels[prefix[-1]])
+        # AdamW ranges (padding between tensors is zero and stays zero: zero gradient, zero moments)
+        runs = []
+        for n in prefix:
+            lo = self.offsets[n][0]
+            key = (decays(n), self.lr_factor[n])
+            if runs and (runs[-1][2], runs[-1][3]) == key:
+                runs[-1][1] = lo + _pad64(numels[n])
+            else:
+                runs.append([lo, lo + _pad64(numels[n]), key[0], key[1]])
+        self.adam_runs = [tuple(r) for r in runs]
+        # all-reduce segments: one per group with a trainable tensor
+        def group(n):
+            return "head" if n.startswith("out_x_proj.") else ("embed" if _embedding_side(n) else _layer_of(n))
+        self.groups = []
+        for n in prefix:
+            lo = self.offsets[n][0]
+            if self.groups and self.groups[-1][0] == group(n):
+                self.groups[-1][2] = lo + _pad64(numels[n])
+            else:
+                self.groups.append([group(n), lo, lo + _pad64(numels[n])])
+        self.groups = [tuple(g) for g in self.groups]
+        self.segments = [(lo, hi) for _, lo, hi in self.groups]
+        self.embed = any(_embedding_side(n) for n in prefix)
+        layers = [k for k, _, _ in self.groups if isinstance(k, int)]
+        self.stop = 0 if self.embed else (min(layers) if layers else config.num_layers)
+
+
 class BucketReducer:
     """Sum-all-reduce of contiguous slices of one flat gradient buffer, one slice per bucket, asynchronously.
 
@@ -236,8 +355,18 @@ def bucket_bounds(segments, target_elems):
 class GenieTrainer:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0,
                  gradient_accumulation_steps=1, lr_lambda=None, bucket_mb=64, group=None, recompute=False, dropout_seed=0,
-                 ema_decay=None, ema_warmup=False, label_smoothing=0.0, z_loss=0.0, frame_weights=None):
-        """label_smoothing, z_loss, frame_weights: the training objective (include/genie_hip.h, "Training objective"): per factor
+                 ema_decay=None, ema_warmup=False, label_smoothing=0.0, z_loss=0.0, frame_weights=None, trainable=None, lr_scale=None):
+        """trainable: train a subset of the weights (fine-tuning; the reference: requires_grad = False on the rest, which torch.optim.AdamW
+        and clip_grad_norm_ then skip).  None: everything.  Else fnmatch patterns over state-dict names (a list, or one comma-separated
+        string; `select_trainable` also takes a freeze list and returns names, which are patterns too), or a callable name -> bool.  A
+        frozen tensor costs nothing: no gradient (a NULL in the gradient table: include/genie_hip.h, "Frozen tensors"), no moments, no
+        average, no all-reduce bytes, no 16-bit repack; the backward stops at the lowest layer that holds a trainable tensor (`layout.stop`)
+        and, with `recompute`, rebuilds nothing below it.  The flat parameter buffer keeps the trainable tensors first (ready order), then
+        the frozen ones; `grads`, `exp_avg`, `exp_avg_sq` and `ema` cover that prefix (`n_train` elements).  The gradients that are
+        computed are the bits of the full step; grad norm and clip run over them alone, which is torch's semantics.
+        lr_scale: {pattern: factor}: a tensor's learning rate is lr * factor of the first pattern that matches it (1 when none does).
+        With both None: the buffers and the library calls of before.
+        label_smoothing, z_loss, frame_weights: the training objective (include/genie_hip.h, "Training objective"): per factor
         F.cross_entropy(label_smoothing=eps) + z_loss * logsumexp^2, each counted token weighted by its frame's entry of `frame_weights`
         (T floats >= 0; frame 0 is never counted) and the sum divided by the summed weights of the counted tokens.  All in the fused loss
         kernel, which still reads and writes the logits once; the backward is untouched.  `forward_backward` returns this objective as
@@ -279,17 +408,24 @@ class GenieTrainer:
         self.last_ce = None   # plain masked CE of the last micro-batch (0-dim device tensor)
 
         named = dict(model.named_parameters())
-        self.order = ready_order(self.config, named.keys())
-        offs, o = {}, 0
-        for n in self.order:
-            offs[n] = (o, o + named[n].numel())
-            o += (named[n].numel() + 63) // 64 * 64  # 256-byte aligned tensors (float4 / MFMA staging loads)
-        self.n_flat = o
-        self.params = torch.zeros(o, dtype=torch.float32, device=dev)
-        self.grads = torch.zeros_like(self.params)
-        self.exp_avg = torch.zeros_like(self.params)
-        self.exp_avg_sq = torch.zeros_like(self.params)
-        self.offsets = offs
+        if trainable is None:
+            chosen = None
+        elif callable(trainable):
+            chosen = {n for n in named if trainable(n)}
+            if not chosen:
+                raise ValueError("no trainable parameter is left: `trainable` accepts no parameter name")
+        else:
+            chosen = select_trainable(named.keys(), train_only=trainable)
+        self.lr_scale = dict(lr_scale) if lr_scale else None
+        lay = self.layout = FlatLayout(self.config, {n: p.numel() for n, p in named.items()}, chosen, self.lr_scale)
+        self.order, self.offsets, self.n_flat, self.n_train = lay.order, lay.offsets, lay.n_flat, lay.n_train
+        self.trainable = [n for n in self.order if n in lay.trainable]   # the prefix, in ready order
+        offs = self.offsets
+        self.params = torch.zeros(self.n_flat, dtype=torch.float32, device=dev)
+        # gradients, moments (and the average) exist for the trainable prefix alone
+        self.grads = torch.zeros(self.n_train, dtype=torch.float32, device=dev)
+        self.exp_avg = torch.zeros_like(self.grads)
+        self.exp_avg_sq = torch.zeros_like(self.grads)
         with torch.no_grad():
             for n in self.order:
                 lo, hi = offs[n]
@@ -302,11 +438,11 @@ class GenieTrainer:
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
             dist.broadcast(self.params, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
         # the average starts from the (broadcast) parameters; padding is zero in both and stays zero
-        self.ema = self.params.clone() if self.ema_decay is not None else None
+        self.ema = self.params[:self.n_train].clone() if self.ema_decay is not None else None
         self.ema_updates, self._in_ema_scope = 0, False
         model.refresh_weights()
         self.p_views = {n: self.params[offs[n][0]:offs[n][1]] for n in self.order}
-        self.g_views = {n: self.grads[offs[n][0]:offs[n][1]].view(named[n].shape) for n in self.order}
+        self.g_views = {n: self.grads[offs[n][0]:offs[n][1]].view(named[n].shape) for n in self.trainable}
         # 16-bit operand copies of the Linear weights, both orientations (bf16: 1 plane, f16x3: [hi | lo])
         self.w16 = self.w16T = None
         self.wT_table = None
@@ -317,30 +453,16 @@ class GenieTrainer:
             self.w16T = {n: torch.empty((npl,) + tuple(named[n].shape)[::-1], dtype=torch.int16, device=dev) for n in lin}
             self.wT_table, self._wTk = weights_table(self.config, {}, self.w16T)
         self.w_table, self._wk = weights_table(self.config, {n: named[n].data for n in self.order}, self.w16)
-        self.g_table, self._gk = weights_table(self.config, self.g_views)
+        self.g_table, self._gk = weights_table(self.config, self.g_views)   # NULL members: frozen tensors (genie_hip.h, "Frozen tensors")
         self.pack_weights()
-        # AdamW ranges: maximal runs of consecutive tensors with the same decay flag (padding between tensors is zero
-        # and stays zero: zero gradient, zero moments)
-        runs = []
-        for n in self.order:
-            lo, hi = offs[n]
-            hi_pad = lo + (hi - lo + 63) // 64 * 64
-            if runs and runs[-1][2] == decays(n):
-                runs[-1][1] = hi_pad
-            else:
-                runs.append([lo, hi_pad, decays(n)])
-        self.adam_runs = [(lo, hi, dk) for lo, hi, dk in runs]
-        # all-reduce buckets: per-layer segments merged up to bucket_mb
-        segs, L = [], self.config.num_layers
-        groups = [[n for n in self.order if n.startswith("out_x_proj.")]]
-        groups += [[n for n in self.order if n.startswith(f"decoder.layers.{i}.")] for i in reversed(range(L))]
-        groups += [[n for n in self.order if _embedding_side(n)]]
-        for gnames in groups:
-            lo = offs[gnames[0]][0]
-            hi = offs[gnames[-1]][0] + (named[gnames[-1]].numel() + 63) // 64 * 64
-            segs.append((lo, hi))
-        self.segments = segs  # [head, layer L-1, ..., layer 0, embeddings]
-        self.reducer = BucketReducer(self.grads, bucket_bounds(segs, bucket_mb * (1 << 20) // 4), group)
+        # AdamW ranges: maximal runs of consecutive trainable tensors with the same (decay flag, lr factor)
+        self.adam_runs = lay.adam_runs
+        # all-reduce buckets: the segments of the groups that hold a trainable tensor ([head, layer L-1, ..., layer 0, embeddings] when
+        # everything trains), merged up to bucket_mb
+        self.segments = lay.segments
+        self._group_hi = {k: hi for k, _, hi in lay.groups}   # group -> "gradients [0, hi) are final" once its backward is enqueued
+        self.reducer = BucketReducer(self.grads, bucket_bounds(self.segments, bucket_mb * (1 << 20) // 4), group)
+        self._dw_scratch = None   # where the gradient of a frozen action_proj.weight goes (genie_action_rows_backward needs a d_weight)
         # [sum loss, sum hits, n]; with an objective [sum w l, sum hits, W, sum plain nll, n]
         self.sums = torch.zeros(3 if self._objective is None else 5, dtype=torch.float64, device=dev)
         self.sumsq = torch.zeros(1, dtype=torch.float64, device=dev)
@@ -356,6 +478,15 @@ class GenieTrainer:
         if self.precision != "exact":
             _lib.check(self.lib.genie_train_pack_weights(self.cfg, self.w_table, self.w_table, self.wT_table,
                                                          self._stream()), "genie_train_pack_weights")
+
+    def _pack_trained(self):
+        """pack_weights after a change the trainer made itself (optimizer step, EMA exchange): those move the trainable prefix alone,
+        so only the trainable Linears are repacked -- the gradient table says which."""
+        if self.layout.all:
+            return self.pack_weights()
+        if self.precision != "exact":
+            _lib.check(self.lib.genie_train_pack_weights_some(self.cfg, self.w_table, self.w_table, self.wT_table, self.g_table,
+                                                              self._stream()), "genie_train_pack_weights_some")
 
     def sync_external_weights(self):
         """After the caller changed the model's parameters in place (they are views of the flat buffer): repack the
@@ -436,19 +567,23 @@ class GenieTrainer:
         _lib.check(_lib.call_recompute(lib, "genie_train_backward_head", self.recompute, cfg, self.w_table, self.wT_table,
                                        self.g_table, B, acts.data_ptr(), ws.data_ptr(), ws.numel(), acc_flag, st),
                    "genie_train_backward_head")
-        if reduce:
-            self.reducer.ready(self.segments[0][1])
+        ready = self._group_hi.get   # None: the group holds no trainable tensor, nothing of it is exchanged
+        if reduce and ready("head") is not None:
+            self.reducer.ready(ready("head"))
         L = self.config.num_layers
-        for k, layer in enumerate(reversed(range(L))):
+        for layer in reversed(range(self.layout.stop, L)):   # below `stop` nothing trains: no backward, no recomputation
             _lib.check(_lib.call_drop(lib, "genie_train_backward_layer", self.recompute, drop, cfg, self.w_table, self.wT_table,
                                       self.g_table, layer, B, acts.data_ptr(), ws.data_ptr(), ws.numel(), acc_flag, st),
                        "genie_train_backward_layer")
-            if reduce:
-                self.reducer.ready(self.segments[1 + k][1])
-        if cond is None:
-            _lib.check(lib.genie_train_backward_embed(cfg, self.g_table, ids.data_ptr(), B, ws.data_ptr(), ws.numel(),
-                                                      acc_flag, st), "genie_train_backward_embed")
-        elif vec:
+            if reduce and ready(layer) is not None:
+                self.reducer.ready(ready(layer))
+        g = self.g_views.get
+        # the action tensors train one by one: without a trainable one the conditioning leaves the embedding backward
+        vec_on = vec and cond is not None and any(g(n) is not None for n in ("action_proj.weight", "action_proj.bias", "action_null"))
+        ids_on = not vec and cond is not None and g("action_embed.weight") is not None
+        if not self.layout.embed:
+            pass
+        elif vec_on:
             n, d = B * self.config.T, self.config.d_model
             if self._d_rows is None or self._d_rows.shape[0] != 1 + n:
                 self._d_rows = torch.empty(1 + n, d, dtype=torch.float32, device=self.params.device)
@@ -457,16 +592,25 @@ class GenieTrainer:
             _lib.check(lib.genie_train_backward_embed_cond(cfg, self.g_table, ids.data_ptr(), B, ws.data_ptr(), ws.numel(),
                                                            acc_flag, st, self._d_rows.data_ptr(), cond),
                        "genie_train_backward_embed_cond")
-            _lib.check(lib.genie_action_rows_backward(self.model._action_proj_struct(), cond.vectors.data_ptr(),
-                                                      self._d_rows[1:].data_ptr(), n, d, self.g_views["action_proj.weight"].data_ptr(),
-                                                      self.g_views["action_proj.bias"].data_ptr(), acc_flag, st),
-                       "genie_action_rows_backward")
-            g_null = self.g_views["action_null"]
-            g_null.add_(self._d_rows[0]) if accumulate else g_null.copy_(self._d_rows[0])
-        else:
+            g_w, g_b = g("action_proj.weight"), g("action_proj.bias")
+            if g_w is not None or g_b is not None:
+                if g_w is None:   # the entry point needs a d_weight: a frozen weight's gradient lands in a scratch nobody reads
+                    if self._dw_scratch is None:
+                        self._dw_scratch = torch.zeros(d, self.config.action_dim, dtype=torch.float32, device=self.params.device)
+                    g_w = self._dw_scratch
+                _lib.check(lib.genie_action_rows_backward(self.model._action_proj_struct(), cond.vectors.data_ptr(),
+                                                          self._d_rows[1:].data_ptr(), n, d, g_w.data_ptr(), _ptr(g_b), acc_flag, st),
+                           "genie_action_rows_backward")
+            g_null = g("action_null")
+            if g_null is not None:
+                g_null.add_(self._d_rows[0]) if accumulate else g_null.copy_(self._d_rows[0])
+        elif ids_on:
             _lib.check(lib.genie_train_backward_embed_cond(cfg, self.g_table, ids.data_ptr(), B, ws.data_ptr(), ws.numel(),
-                                                           acc_flag, st, self.g_views["action_embed.weight"].data_ptr(), cond),
+                                                           acc_flag, st, g("action_embed.weight").data_ptr(), cond),
                        "genie_train_backward_embed_cond")
+        else:
+            _lib.check(lib.genie_train_backward_embed(cfg, self.g_table, ids.data_ptr(), B, ws.data_ptr(), ws.numel(),
+                                                      acc_flag, st), "genie_train_backward_embed")
         if reduce:
             self.reducer.finish()
         loss = sums[0] / sums[2]
@@ -479,7 +623,7 @@ class GenieTrainer:
     # ------------------------------------------------------------------ clip + AdamW + scheduler (train.py:628-633)
     def grad_sumsq(self):
         self.sumsq.zero_()
-        _lib.check(self.lib.genie_sumsq(self.grads.data_ptr(), self.n_flat, self.sumsq.data_ptr(),
+        _lib.check(self.lib.genie_sumsq(self.grads.data_ptr(), self.n_train, self.sumsq.data_ptr(),
                                         self.scratch.data_ptr(), self._stream()), "genie_sumsq")
         return self.sumsq
 
@@ -496,9 +640,9 @@ class GenieTrainer:
         step = self.completed_steps + 1
         st = self._stream()
         omd = None if self.ema is None else ema_one_minus_decay(self.ema_decay, self.ema_updates + 1, self.ema_warmup)
-        for lo, hi, dk in self.adam_runs:
+        for lo, hi, dk, factor in self.adam_runs:
             off = lo * 4
-            scalars = (hi - lo, lr, self.betas[0], self.betas[1], self.eps, self.weight_decay if dk else 0.0, step, mult,
+            scalars = (hi - lo, lr * factor, self.betas[0], self.betas[1], self.eps, self.weight_decay if dk else 0.0, step, mult,
                        ss.data_ptr() if clip > 0 else None, clip)
             if omd is None:
                 _lib.check(self.lib.genie_adamw_step(
@@ -511,7 +655,7 @@ class GenieTrainer:
         self.completed_steps += 1
         if omd is not None:
             self.ema_updates += 1
-        self.pack_weights()
+        self._pack_trained()
         self.model.refresh_weights()  # the module's own 16-bit copies (inference entry points) are stale
         return torch.sqrt(ss[0]) * mult, lr
 
@@ -535,7 +679,7 @@ class GenieTrainer:
         return out
 
     def gradients(self):
-        """{state-dict name: gradient view} (shapes of the parameters)."""
+        """{state-dict name: gradient view} (shapes of the parameters) of the trainable tensors."""
         return self.g_views
 
     # ------------------------------------------------------------------ EMA of the weights
@@ -548,8 +692,10 @@ class GenieTrainer:
             raise RuntimeError(f"GenieTrainer.{what} needs a trainer built with ema_decay")
 
     def _swap_ema(self):
-        _lib.check(self.lib.genie_swap_f32(self.params.data_ptr(), self.ema.data_ptr(), self.n_flat, self._stream()), "genie_swap_f32")
-        self.sync_external_weights()
+        # the trainable prefix alone: a frozen tensor's average is the tensor itself
+        _lib.check(self.lib.genie_swap_f32(self.params.data_ptr(), self.ema.data_ptr(), self.n_train, self._stream()), "genie_swap_f32")
+        self._pack_trained()
+        self.model.refresh_weights()
 
     @contextlib.contextmanager
     def ema_scope(self):
@@ -568,11 +714,13 @@ class GenieTrainer:
             self._swap_ema()
 
     def ema_state_dict(self):
-        """{state-dict name: clone of the averaged weights} in the parameters' shapes."""
+        """{state-dict name: clone of the averaged weights} in the parameters' shapes, for every tensor: a frozen tensor's average is
+        the tensor itself."""
         self._need_ema("ema_state_dict")
         avg = self.params if self._in_ema_scope else self.ema   # inside the scope the two buffers have changed places
         named = dict(self.model.named_parameters())
-        return {n: avg[self.offsets[n][0]:self.offsets[n][1]].view(named[n].shape).clone() for n in self.order}
+        src = lambda n: avg if n in self.g_views else self.params   # noqa: E731
+        return {n: src(n)[self.offsets[n][0]:self.offsets[n][1]].view(named[n].shape).clone() for n in self.order}
 
     def save_ema_pretrained(self, save_directory):
         """`model.save_pretrained(save_directory)` with the averaged weights: STMaskGIT.from_pretrained loads it as an ordinary checkpoint."""
@@ -590,18 +738,21 @@ class GenieTrainer:
         self._not_in_ema_scope("state_dict")
         named = dict(self.model.named_parameters())
         st = {}
-        for n in self.order:
+        for n in self.trainable:   # a frozen tensor has no moments
             lo, hi = self.offsets[n]
             st[n] = {"exp_avg": self.exp_avg[lo:hi].view(named[n].shape).clone(),
                      "exp_avg_sq": self.exp_avg_sq[lo:hi].view(named[n].shape).clone()}
         out = {"state": st, "completed_steps": self.completed_steps, "micro_step": self._micro,
+               "trainable": sorted(self.trainable),
                "dropout": {"seed": self.dropout_seed, "call": self._drop_call},
                "hyper": {"lr": self.base_lr, "betas": tuple(self.betas), "eps": self.eps,
                          "weight_decay": self.weight_decay, "max_grad_norm": self.max_grad_norm,
                          "gradient_accumulation_steps": self.accum, "recompute": bool(self.recompute),
-                         "label_smoothing": self.label_smoothing, "z_loss": self.z_loss, "frame_weights": self.frame_weights}}
+                         "label_smoothing": self.label_smoothing, "z_loss": self.z_loss, "frame_weights": self.frame_weights,
+                         "lr_scale": self.lr_scale}}
         if self.ema is not None:
-            out["ema"] = {"state": self.ema_state_dict(), "updates": self.ema_updates, "decay": self.ema_decay,
+            avg = self.ema_state_dict()
+            out["ema"] = {"state": {n: avg[n] for n in self.trainable}, "updates": self.ema_updates, "decay": self.ema_decay,
                           "warmup": self.ema_warmup}
         return out
 
@@ -614,7 +765,8 @@ class GenieTrainer:
         saved_ema = sd.get("ema")
         mine = {"lr": self.base_lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
                 "max_grad_norm": self.max_grad_norm, "gradient_accumulation_steps": self.accum,
-                "label_smoothing": self.label_smoothing, "z_loss": self.z_loss, "frame_weights": self.frame_weights}
+                "label_smoothing": self.label_smoothing, "z_loss": self.z_loss, "frame_weights": self.frame_weights,
+                "lr_scale": self.lr_scale}
         diff = {k: (v, mine[k]) for k, v in (sd.get("hyper") or {}).items()
                 if k in mine and (tuple(v) if isinstance(v, (list, tuple)) else v) != mine[k]}
         if saved_ema is not None and self.ema is not None:
@@ -624,10 +776,22 @@ class GenieTrainer:
         if diff:
             warnings.warn("GenieTrainer.load_state_dict: resuming with different hyper-parameters (saved, current): "
                           + ", ".join(f"{k}={a}->{b}" for k, (a, b) in diff.items()))
-        for n in self.order:
+        # the names trainable on both sides are restored; a tensor that was frozen when the state was saved starts from zero moments
+        saved = set(sd["state"])
+        only_saved, only_here = sorted(saved - set(self.trainable)), [n for n in self.trainable if n not in saved]
+        if only_saved or only_here:
+            warnings.warn("GenieTrainer.load_state_dict: resuming with a different selection of trainable tensors: "
+                          f"{len(only_saved)} saved ones are frozen here and their state is ignored ({', '.join(only_saved[:4])}"
+                          f"{', ...' if len(only_saved) > 4 else ''}); {len(only_here)} trainable here were frozen there and start from "
+                          f"zero moments ({', '.join(only_here[:4])}{', ...' if len(only_here) > 4 else ''})")
+        for n in self.trainable:
             lo, hi = self.offsets[n]
-            self.exp_avg[lo:hi].copy_(sd["state"][n]["exp_avg"].reshape(-1))
-            self.exp_avg_sq[lo:hi].copy_(sd["state"][n]["exp_avg_sq"].reshape(-1))
+            if n in saved:
+                self.exp_avg[lo:hi].copy_(sd["state"][n]["exp_avg"].reshape(-1))
+                self.exp_avg_sq[lo:hi].copy_(sd["state"][n]["exp_avg_sq"].reshape(-1))
+            else:
+                self.exp_avg[lo:hi].zero_()
+                self.exp_avg_sq[lo:hi].zero_()
         self.completed_steps = int(sd["completed_steps"])
         self._micro = int(sd.get("micro_step", 0))
         if "dropout" in sd:   # the masks of the resumed run are those the saved one would have drawn next
@@ -636,12 +800,12 @@ class GenieTrainer:
             if saved_ema is None:
                 warnings.warn("GenieTrainer.load_state_dict: the saved state has no EMA of the weights: the average restarts from the "
                               "current parameters")
-                self.ema.copy_(self.params)
+                self.ema.copy_(self.params[:self.n_train])
                 self.ema_updates = 0
             else:
-                for n in self.order:
+                for n in self.trainable:   # a tensor without a saved average (frozen there) restarts its own from the parameter
                     lo, hi = self.offsets[n]
-                    self.ema[lo:hi].copy_(saved_ema["state"][n].reshape(-1))
+                    self.ema[lo:hi].copy_(saved_ema["state"][n].reshape(-1) if n in saved_ema["state"] else self.params[lo:hi])
                 self.ema_updates = int(saved_ema["updates"])
         elif saved_ema is not None:
             warnings.warn("GenieTrainer.load_state_dict: the saved state carries an EMA of the weights, this trainer keeps none: ignored")

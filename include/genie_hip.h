@@ -950,6 +950,34 @@ int genie_adamw_ema_step(float* params, const float* grads, float* exp_avg, floa
 int genie_ema_update(float* ema, const float* params, size_t n, float one_minus_decay, void* stream);
 int genie_swap_f32(float* a, float* b, size_t n, void* stream);
 
+/* Frozen tensors (additions; nothing above changes).  Fine-tuning trains a subset of the weights (torch: requires_grad = False on the
+ * rest; torch.optim.AdamW and clip_grad_norm_ skip them).  A NULL member of the `grads` table passed to genie_train_backward_head[_ex],
+ * genie_train_backward_layer[_ex|_drop] or genie_train_backward_embed[_cond] means "this tensor is frozen": its gradient is not
+ * computed and nothing is written for it, with or without `accumulate`.  The running d loss / d x is propagated exactly as before, so
+ * a caller may also stop calling genie_train_backward_layer* below the lowest layer that holds a trainable tensor (and skip the
+ * embedding call when nothing on that side trains); with recompute = 1 the layers never called are never rebuilt.  (Before this
+ * section a NULL member was undefined: no defined behaviour changes.  A bias the configuration does not have was and is ignored.)
+ * With every member non-NULL each call enqueues the launches it always did; the gradients that are computed are the same bits
+ * whatever else is frozen -- they come from the same kernels in the same order.  What a NULL skips:
+ *   a Linear weight   exact: the weight-gradient product.  16-bit: that product, the transposed copy of the saved activation and the
+ *                     transposed planes of the gradient operand; the row-major operand of the input-gradient product (f16x3: scaled
+ *                     by 2^12 and saturated as above; fc1: with gelu' folded in) is made as before, by a rows-only form of the same
+ *                     kernel, and with a trainable bias the column sums keep their slab layout and order;
+ *   a Linear bias     the column sums and their reduction;
+ *   norm1 / norm2 / a qk-norm's weight and bias   both NULL: a parameter-free backward kernel (no accumulators, no LDS reduction, no
+ *                     partial store) and none of the three reductions behind it; one NULL: the full kernel, and only the wanted half
+ *                     of the reduction;
+ *   pos_embed, mask_embed, embed[j]   that part of the embedding backward, each on its own; all NULL and no actions: nothing is
+ *                     enqueued.  (d_table of genie_train_backward_embed_cond stays required with actions: a caller whose action table
+ *                     is frozen passes cond = NULL.)
+ * genie_train_pack_weights_some: genie_train_pack_weights for the Linears whose *_w member (qkv_w, proj_w, fc1_w, fc2_w, out_w) in
+ * `select` is non-NULL -- the caller's gradient table serves: a frozen weight has not moved, so its 16-bit copies are current.
+ * select == NULL packs everything.  GENIE_PREC_EXACT: GENIE_E_ARG, like genie_train_pack_weights.
+ * genie_adamw_step, genie_adamw_ema_step, genie_sumsq and genie_swap_f32 are unchanged: the caller runs them over the ranges that
+ * hold trainable tensors. */
+int genie_train_pack_weights_some(const genie_cfg* cfg, const genie_weights* w, const genie_weights* w16,
+                                  const genie_weights* w16T, const genie_weights* select, void* stream);
+
 /* Continuous per-frame actions (ABI 3 addition; nothing above changes).  A model conditioned on float action vectors of A values per
  * frame projects them, once per call, into the rows that genie_frame_cond addresses: the caller builds a table of one learned "no
  * action" row plus one projected row per frame of the call, points cond->table at it and cond->ids at "row of frame (b, t)", and every

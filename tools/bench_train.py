@@ -49,6 +49,10 @@ def main():
     ap.add_argument("--ema_unfused", action="store_true",
                     help="bench only, with --ema_decay: run the optimizer as genie_adamw_step followed by genie_ema_update per range (two passes) "
                          "instead of the one fused launch the trainer makes")
+    ap.add_argument("--action_dim", type=int, default=0, help="condition the model on random per-frame action vectors of this many values")
+    ap.add_argument("--train_only", type=str, default=None, metavar="P[,P...]",
+                    help="train only the tensors matching these fnmatch patterns over state-dict names (GenieTrainer(trainable=...))")
+    ap.add_argument("--freeze", type=str, default=None, metavar="P[,P...]", help="freeze the tensors matching these patterns")
     a = ap.parse_args()
     cfgm, syn, _lib = pkg("config"), pkg("synthetic"), pkg("_lib")
     cfg = cfgm.c138() if a.config == "c138" else cfgm.c35()
@@ -57,12 +61,20 @@ def main():
         cfg.num_layers = a.layers
     if a.T:
         cfg.T = a.T
+    if a.action_dim:
+        cfg = cfgm.GenieConfig(**{**vars(cfg), "action_dim": a.action_dim})
     cfg.mlp_drop = a.mlp_drop
     sd = syn.make_state_dict(cfg, seed=0, law="init")
     model = pkg("st_mask_git").STMaskGIT(cfg, precision=a.precision).load_numpy_state_dict(sd).to("cuda")
     fw = None if a.frame_loss_weights is None else [float(v) for v in a.frame_loss_weights.split(",")]
+    trainable = None
+    if a.train_only or a.freeze:
+        try:
+            trainable = sorted(pkg("train").select_trainable([n for n, _ in model.named_parameters()], a.train_only, a.freeze))
+        except ValueError as e:
+            ap.error(str(e))
     tr = pkg("train").GenieTrainer(model, lr=1e-4, max_grad_norm=1.0, recompute=a.recompute, ema_decay=a.ema_decay,
-                                   label_smoothing=a.label_smoothing, z_loss=a.z_loss, frame_weights=fw)
+                                   label_smoothing=a.label_smoothing, z_loss=a.z_loss, frame_weights=fw, trainable=trainable)
     lib = _lib.load()
     if a.ema_unfused:
         if a.ema_decay is None:
@@ -84,7 +96,8 @@ def main():
     torch.manual_seed(0)
     import random
     random.seed(0)
-    batch = collate(ids, cfg)
+    vecs = torch.randn(a.batch, cfg.T, a.action_dim, generator=torch.Generator().manual_seed(2)).cuda() if a.action_dim else None
+    batch = collate(ids, cfg, action_vectors=vecs)
     for _ in range(a.warmup):
         out = tr.train_step(batch)
     torch.cuda.synchronize()
@@ -111,6 +124,10 @@ def main():
     ms = sorted(e0.elapsed_time(e1) for e0, e1 in opt_events)
     print(f"  optimizer_step: AdamW launches {len(tr.adam_runs) * (2 if a.ema_unfused else 1)}, {sum(ms) / len(ms):.3f} ms/step "
           f"(min {ms[0]:.3f}, median {ms[len(ms) // 2]:.3f}, max {ms[-1]:.3f}; {tr.n_flat * 4 / 1e9:.3f} GB per flat f32 buffer)")
+    n_state = 2 + (tr.ema is not None)   # exp_avg, exp_avg_sq (and the average): one f32 per trainable element each
+    print(f"  trainable {len(tr.trainable)} of {len(tr.order)} tensors, backward layers {cfg.num_layers - tr.layout.stop} of {cfg.num_layers}, "
+          f"embedding backward {'on' if tr.layout.embed else 'off'}: gradient buffer = all-reduce traffic per step {tr.n_train * 4} bytes, "
+          f"optimizer state {n_state * tr.n_train * 4} bytes (all-trainable: {tr.n_flat * 4} and {n_state * tr.n_flat * 4})")
     if a.breakdown:
         import ctypes as C
         buf = (C.c_double * 4)()

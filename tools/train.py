@@ -92,6 +92,14 @@ def parse_args():
     p.add_argument("--action_dim", type=int, default=0,
                    help="condition the model on continuous per-frame action vectors of this many values (the datasets' states.bin; "
                         "random vectors under --synthetic); with --action_dropout a dropped clip reads the model's learned null row")
+    p.add_argument("--train_only", type=str, default=None, metavar="P[,P...]",
+                   help="fine-tune: train only the tensors whose state-dict name matches one of these fnmatch patterns (e.g. "
+                        "'action_*' or 'decoder.layers.3[01].*,out_x_proj.*'); the rest are frozen and cost no gradient, optimizer state, "
+                        "all-reduce or repack (GenieTrainer(trainable=...))")
+    p.add_argument("--freeze", type=str, default=None, metavar="P[,P...]",
+                   help="freeze the tensors matching these patterns (applied after --train_only)")
+    p.add_argument("--lr_scale", type=str, default=None, metavar="P=F[,P=F...]",
+                   help="learning-rate factors by pattern, first match wins (e.g. 'action_*=10'): lr * F for the tensors matching P")
     p.add_argument("--null_action", type=int, default=None, help="row of the action table that stands for 'no action'")
     p.add_argument("--synthetic", type=int, default=0, help="train on N synthetic clips (no dataset on disk)")
     p.add_argument("--model", choices=["c138", "c35", "tiny"], default="c35", help="shape when no --genie_config is given")
@@ -216,16 +224,33 @@ def main():
     warm = args.num_warmup_steps
     lr_lambda = {"linear": trainmod.lr_factor_linear(warm, max_steps), "constant": lambda s: 1.0,
                  "custom_cosine": trainmod.lr_factor_custom_cosine(warm, max_steps)}[args.lr_scheduler_type]
+    trainable = lr_scale = None
+    try:   # the trainer's own rules: a pattern that matches nothing, an empty selection, a factor that is not a positive number
+        names = [n for n, _ in model.named_parameters()]
+        if args.train_only or args.freeze:
+            trainable = sorted(trainmod.select_trainable(names, args.train_only, args.freeze))
+        if args.lr_scale:
+            pairs = [kv.rpartition("=") for kv in args.lr_scale.split(",") if kv]
+            if any(not k or not v for k, _, v in pairs):
+                raise ValueError(f"{args.lr_scale!r} is not a comma-separated list of PATTERN=FACTOR")
+            lr_scale = {k: float(v) for k, _, v in pairs}
+            trainmod.lr_factors(names, lr_scale)
+    except ValueError as e:
+        sys.exit(f"train.py: --train_only / --freeze / --lr_scale: {e}")
     tr = trainmod.GenieTrainer(model, lr=args.learning_rate, betas=(args.adam_beta_1, args.adam_beta_2), eps=args.adam_eps,
                                weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm,
                                gradient_accumulation_steps=accum, lr_lambda=lr_lambda, recompute=args.recompute_activations,
                                dropout_seed=args.dropout_seed, ema_decay=args.ema_decay, ema_warmup=args.ema_warmup,
-                               label_smoothing=args.label_smoothing, z_loss=args.z_loss, frame_weights=frame_weights)
+                               label_smoothing=args.label_smoothing, z_loss=args.z_loss, frame_weights=frame_weights,
+                               trainable=trainable, lr_scale=lr_scale)
     if args.resume_from_checkpoint:  # optimizer moments, step counters (train.py:560-590), the EMA of the weights
         tr.load_state_dict(torch.load(os.path.join(args.resume_from_checkpoint, "trainer_state.pt"), map_location=dev))
     n_params = sum(p.numel() for p in model.parameters())
     if rank == 0:
         os.makedirs(args.output_dir, exist_ok=True)
+        if trainable is not None:
+            print(f"training {len(tr.trainable)} of {len(tr.order)} tensors ({tr.n_train / 1e6:.2f} M of {tr.n_flat / 1e6:.1f} M flat "
+                  f"elements); the backward stops at layer {tr.layout.stop}", flush=True)
         print(f"params {n_params / 1e6:.1f} M, {n_train} train windows, batch {B} x {accum} x {world}, "
               f"{max_steps} update steps, precision {args.precision}", flush=True)
 
