@@ -14,6 +14,36 @@
  *  - token ids are int64 (torch.LongTensor), activations/logits float32, flags uint8.
  *  - activations are token-major (B, T, S, C) row-major; nothing is ever physically transposed to
  *    (B S) T C (reference st_transformer.py:77,82): the temporal kernel reads frame-strided rows.
+ *
+ * Memory the caller provides
+ *  The library never allocates, so every buffer below is the caller's, and most of them are re-used from call to call with other
+ *  batch sizes, prompt lengths and precisions.  What a buffer may hold ON ENTRY:
+ *  - ANYTHING (uninitialised, NaN, the leftovers of any earlier call):
+ *      `workspace` of every entry point.  The library initialises whatever it reads there: the loops' id tables (context ids, the
+ *        one- and two-frame pass rows, the frame being decoded, samples, the per-call action tables) are written by a launch before
+ *        the pass that reads them, and their `unmasked` bytes are cleared by the call at the top of every frame.
+ *      `cache` of genie_clean_pass* (whole), of genie_frame(s)_pass* (the slots >= t0: a pass reads slots [0, t0) and writes its own),
+ *        of genie_generate_cached*, of genie_rollout_cached with resume == 0 or at the first frame of a window, and `trunk` / `branch`
+ *        of genie_generate_fanout / genie_score_fanout.  The attention kernels read fixed-size tiles of frame slots; slots no pass
+ *        has written must not reach a result: a kernel clamps or predicates such loads, and never masks one by 0 * value, which a
+ *        stale NaN survives.
+ *      every OUTPUT: logits, logits0_out, hidden states, samples_out, gen_out, conf, keys_out, nll / hits / token_nll, the
+ *        destinations of the genie_pack_* functions (bf16 / split-f16 planes, the fused and fragment-order streams), the MAGVIT2
+ *        conv outputs, GroupNorm statistics and partials.  Outputs are WRITTEN IN FULL: after the call no element of the documented
+ *        shape holds what was there before.  (Argument errors return before anything is enqueued and leave them untouched.)
+ *  - ZEROED BY THE CALLER, because the entry point accumulates into it:
+ *      sums_out of genie_factored_ce / genie_readout_ce (3 doubles, atomicAdd) and sums6[2] of genie_metric_hits;
+ *      status_flag of genie_maskgit_generate* (set on a violation, never cleared);
+ *      `unmasked` of genie_mask_step before the first step of a frame (in/out across the steps of that frame).
+ *  - CARRIED OVER from the call that produced it, byte for byte:
+ *      `cache` between genie_clean_pass* and the genie_masked_frames_logits* calls that read it (same B and nframes), and between
+ *        consecutive genie_frame(s)_pass* calls (slots [0, t0));
+ *      `cache` of genie_rollout_cached with resume == 1 in mid-window: the slots of [start_j, f0 - 1).  The slot of the pending frame
+ *        f0 - 1 and every later slot may hold anything, and so may the whole cache when f0 opens a window;
+ *      `frames` [0, f0) of genie_rollout_cached; `prompt` of genie_maskgit_generate* (in/out).
+ *  Training (genie_train_*): the activation buffer and the workspace may hold anything before genie_train_forward*; between the forward
+ *  and the backward calls of one step both are carried over.
+ *  Enforced by tests/test_hip_stale_memory.py: every call above gives the same bits on buffers filled with 0x00, 0xFF and 0x3C bytes.
  */
 #ifndef GENIE_HIP_H
 #define GENIE_HIP_H
