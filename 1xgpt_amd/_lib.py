@@ -77,6 +77,12 @@ class Objective(C.Structure):
                 ("frame_weight", C.c_float * 64)]
 
 
+class Distill(C.Structure):
+    """genie_distill: mix alpha, temperature and the teacher's logits (device pointer, read only) of one training micro-batch
+    (1xgpt_amd/train.py); alpha 0 = no distillation."""
+    _fields_ = [("alpha", C.c_float), ("temperature", C.c_float), ("teacher_logits", c_ptr)]
+
+
 ACTION_MAX_DIM = 256   # GENIE_ACTION_MAX_DIM
 WIDE_QKV, WIDE_PROJ, WIDE_FC1, WIDE_FC2 = 1, 2, 1, 2          # bits of the w16_wide fields (genie_hip.h)
 FUSED_QKV_STREAM = 4                                        # spatial attention: fused_w16 = [proj stream | qkv stream]
@@ -270,6 +276,13 @@ SIGNATURES["genie_objective_layout"] = (C.c_int, [C.POINTER(C.c_size_t), C.c_int
 SIGNATURES["genie_train_forward_obj"] = (C.c_int, SIGNATURES["genie_train_forward_drop"][1] + [C.POINTER(Objective)])
 SIGNATURES["genie_ce_objective"] = (C.c_int, [c_ptr, c_ptr, c_ptr] + [C.c_int] * 5 + [C.c_int64, C.POINTER(Objective), c_ptr, c_ptr])
 
+# distillation: genie_train_forward_obj's arguments + a trailing genie_distill* (NULL or alpha = 0: that entry point), and the loss
+# launch alone, genie_ce_objective's arguments with teacher_logits behind logits and the genie_distill* behind the objective
+SIGNATURES["genie_distill_layout"] = (C.c_int, [C.POINTER(C.c_size_t), C.c_int])
+SIGNATURES["genie_train_forward_distill"] = (C.c_int, SIGNATURES["genie_train_forward_obj"][1] + [C.POINTER(Distill)])
+SIGNATURES["genie_ce_distill"] = (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr] + [C.c_int] * 5 + [C.c_int64, C.POINTER(Objective), C.POINTER(Distill),
+                                            c_ptr, c_ptr])
+
 # EMA of the weights: genie_adamw_step's arguments with `ema` behind exp_avg_sq and one_minus_decay in front of the stream; the EMA
 # line alone, (ema, params, n, one_minus_decay, stream); the in-place exchange, (a, b, n, stream)
 _a = SIGNATURES["genie_adamw_step"][1]
@@ -332,6 +345,9 @@ def load():
         mine = [C.sizeof(Objective)] + [getattr(Objective, n).offset for n, _ in Objective._fields_]
         if "genie_objective_layout" not in missing and (lib.genie_objective_layout(lay, 6) != 6 or list(lay) != mine):
             raise RuntimeError(f"genie_objective layout {list(lay)} != the ctypes declaration {mine}")
+        mine = [C.sizeof(Distill)] + [getattr(Distill, n).offset for n, _ in Distill._fields_]
+        if "genie_distill_layout" not in missing and (lib.genie_distill_layout(lay, 4) != 4 or list(lay)[:4] != mine):
+            raise RuntimeError(f"genie_distill layout {list(lay)[:4]} != the ctypes declaration {mine}")
         if os.environ.get("GENIE_HIP_LIBRARY") or lib.genie_study_build():
             import sys
             print(f"1xgpt_amd: using {LIB_PATH} (study build: {bool(lib.genie_study_build())}) -- not the shipping library"

@@ -309,6 +309,21 @@ int launch_ce_fwd_bwd(const genie_cfg& c, float* logits, const int64_t* ids, con
 // tokens of nfac factors of vf logits: five sums, d logits in place.  `obj` was checked by the caller (objective_ok in train_api.hip).
 int launch_ce_objective(float* logits, const int64_t* ids, const int64_t* labels, long n_clips, int T, int S, int vf, int nfac,
                         int64_t mask_id, const genie_objective& obj, double* sums, hipStream_t st);
+// the per-frame loss weights as the loss kernels take them (by value in the kernel arguments: no copy, no sync), and the launch that
+// counts the counted tokens per frame: sums[2] = W = sum_t w_t c_t, sums[4] = n = sum_t c_t
+struct FrameWeights {
+    float w[64];
+    int n;   // frames t >= n weigh 1 (n = 0: every frame)
+    __device__ __forceinline__ float at(int t) const { return t < n ? w[t] : 1.0f; }
+};
+FrameWeights frame_weights_of(const genie_objective& obj);
+int launch_count_frames(const int64_t* ids, long n_clips, int T, int S, int64_t mask_id, const FrameWeights& fw, double* sums,
+                        hipStream_t st);
+// kernels_distill.hip: launch_ce_objective with a read-only row of teacher logits beside every student row (include/genie_hip.h,
+// "Distillation"): count_frames, then the distillation kernel; seven sums, d logits in place.  obj, alpha, tau were checked by the caller.
+int launch_ce_distill(float* logits, const float* teacher, const int64_t* ids, const int64_t* labels, long n_clips, int T, int S,
+                      int vf, int nfac, int64_t mask_id, const genie_objective& obj, float alpha, float tau, double* sums,
+                      hipStream_t st);
 int launch_embed_bwd(const genie_cfg& c, const float* dx, const int64_t* ids, int B, float* dpos, float* dmask,
                      float* const* tables_host, float beta, float* colpart, hipStream_t st);
 // gradient of the action table: d_table[k] = sum over frames (b, t) with act_ids[b, t] == k (ascending) of sum_s dx[b, t, s, :];

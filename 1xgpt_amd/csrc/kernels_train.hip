@@ -573,11 +573,7 @@ int launch_ce_fwd_bwd(const genie_cfg& c, float* logits, const int64_t* ids, con
 // (eight per lane), so the row comes from memory once; else the three passes of the kernel above, sum z riding in the first.
 // The weights travel by value in the kernel arguments (64 floats): no copy, no sync.
 // ------------------------------------------------------------------------------------------------
-struct FrameWeights {
-    float w[64];
-    int n;   // frames t >= n weigh 1 (n = 0: every frame)
-    __device__ __forceinline__ float at(int t) const { return t < n ? w[t] : 1.0f; }
-};
+// (FrameWeights: kernels.hpp -- the distillation kernel of kernels_distill.hip takes the same struct)
 __global__ __launch_bounds__(1024) void count_frames_kernel(const int64_t* __restrict__ ids, long n_clips, int T, int S,
                                                             int64_t mask_id, FrameWeights fw, double* __restrict__ sums) {
     __shared__ unsigned int cnt[64];            // frames 0 .. 63 one by one: the only ones that can carry a weight
@@ -703,19 +699,26 @@ __global__ __launch_bounds__(256) void ce_objective_kernel(float* __restrict__ l
         if (c != 0.0) atomicAdd(&sums[3], c);
     }
 }
+FrameWeights frame_weights_of(const genie_objective& obj) {
+    FrameWeights fw;
+    fw.n = obj.n_frames;
+    for (int t = 0; t < 64; ++t) fw.w[t] = t < obj.n_frames ? obj.frame_weight[t] : 1.0f;
+    return fw;
+}
+int launch_count_frames(const int64_t* ids, long n_clips, int T, int S, int64_t mask_id, const FrameWeights& fw, double* sums,
+                        hipStream_t st) {
+    ProfScope prof(GENIE_KC_OTHER, 0.0, 8.0 * n_clips * T * S, st, "count_frames_kernel");
+    count_frames_kernel<<<1, 1024, 0, st>>>(ids, n_clips, T, S, mask_id, fw, sums);
+    GENIE_LAUNCH_CHECK("count_frames");
+    return GENIE_OK;
+}
 int launch_ce_objective(float* logits, const int64_t* ids, const int64_t* labels, long n_clips, int T, int S, int vf, int nfac,
                         int64_t mask_id, const genie_objective& obj, double* sums, hipStream_t st) {
     const long n_tok = n_clips * T * (long)S;
     if (n_tok <= 0) return GENIE_OK;
-    FrameWeights fw;
-    fw.n = obj.n_frames;
-    for (int t = 0; t < 64; ++t) fw.w[t] = t < obj.n_frames ? obj.frame_weight[t] : 1.0f;
+    const FrameWeights fw = frame_weights_of(obj);
     const double row_bytes = 8.0 * n_tok * vf * nfac;
-    {
-        ProfScope prof(GENIE_KC_OTHER, 0.0, 8.0 * n_tok, st, "count_frames_kernel");
-        count_frames_kernel<<<1, 1024, 0, st>>>(ids, n_clips, T, S, mask_id, fw, sums);
-        GENIE_LAUNCH_CHECK("count_frames");
-    }
+    GENIE_TRY(launch_count_frames(ids, n_clips, T, S, mask_id, fw, sums, st));
     ProfScope prof(GENIE_KC_OTHER, 0.0, row_bytes, st, "ce_objective_kernel");
     const unsigned grid = (unsigned)((n_tok + 3) / 4);
     if (vf <= 512)

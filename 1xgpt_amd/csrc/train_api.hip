@@ -369,6 +369,27 @@ static int objective_ok(const genie_objective* ob, int T, const char* fn) {
     return GENIE_OK;
 }
 
+// Distillation of one call (genie_distill): neutral = no struct or alpha == 0, the call of before; the teacher pointer is then never looked at
+static bool distill_neutral(const genie_distill* ds) { return !ds || ds->alpha == 0.0f; }
+// (teacher: the rows of this call -- the struct's pointer, or genie_ce_distill's own argument)
+static int distill_ok(const genie_distill* ds, const float* teacher, const char* fn) {
+    if (!ds) return GENIE_OK;
+    GENIE_CHECK_ARG(ds->alpha >= 0.0f && ds->alpha <= 1.0f, "%s: distillation alpha %g is not in [0, 1]", fn, (double)ds->alpha);   // (NaN fails both)
+    GENIE_CHECK_ARG(ds->temperature > 0.0f && std::isfinite(ds->temperature), "%s: distillation temperature %g is not finite and > 0", fn,
+                    (double)ds->temperature);
+    GENIE_CHECK_ARG(ds->alpha == 0.0f || teacher, "%s: distillation alpha %g without teacher logits", fn, (double)ds->alpha);
+    return GENIE_OK;
+}
+// the teacher rows [teacher, teacher + floats) must not meet the student logits (same extent) or the seven sums
+static int distill_apart(const float* teacher, const float* logits, size_t floats, const double* sums, const char* fn) {
+    const uintptr_t t0 = (uintptr_t)teacher, t1 = t0 + floats * sizeof(float), l0 = (uintptr_t)logits, l1 = l0 + floats * sizeof(float),
+                    s0 = (uintptr_t)sums, s1 = s0 + 7 * sizeof(double);
+    GENIE_CHECK_ARG(t1 <= l0 || l1 <= t0, "%s: the teacher logits overlap the student logits", fn);
+    GENIE_CHECK_ARG(t1 <= s0 || s1 <= t0, "%s: the teacher logits overlap the sums", fn);
+    return GENIE_OK;
+}
+static const genie_objective kNeutralObjective = {};   // eps = zeta = 0, n_frames = 0: every frame weighs 1
+
 // ================================================================================================
 // The two backends.  Same members: Operand (the element type of a saved Linear input), cast / norm / attention (produce an
 // operand), linear, linear_backward.  M tokens; beta 1 accumulates into the gradients; w is unused by the forward.
@@ -549,7 +570,7 @@ static int layer_forward(Ops& o, const genie_layer_weights& lw, const LayerLins&
 
 template <class Ops>
 static int train_forward(Ops& o, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels, char* acts,
-                         const TrainActs& a, double* sums, const EmbedAct* act, const genie_objective* obj) {
+                         const TrainActs& a, double* sums, const EmbedAct* act, const genie_objective* obj, const genie_distill* ds) {
     using Operand = typename Ops::Operand;
     const genie_cfg& c = o.c;
     const size_t pd = (size_t)o.M * c.d_model;
@@ -565,10 +586,13 @@ static int train_forward(Ops& o, const genie_weights* wt, const int64_t* input_i
     }
     if (!idn) GENIE_TRY(o.cast(xL, xL_op, pd));
     GENIE_TRY(o.linear(xL_op, readout_lin(c, wt, nullptr, nullptr), nullptr, logits, nullptr, nullptr, c.readout_mult));
-    if (hipMemsetAsync(sums, 0, (obj ? 5 : 3) * sizeof(double), o.st) != hipSuccess) {
+    if (hipMemsetAsync(sums, 0, (ds ? 7 : obj ? 5 : 3) * sizeof(double), o.st) != hipSuccess) {
         set_error("genie_train_forward: hipMemsetAsync failed");
         return GENIE_E_LAUNCH;
     }
+    if (ds)   // distillation (checked, not neutral): the objective's loss with the teacher's rows beside the student's, seven sums
+        return launch_ce_distill(logits, ds->teacher_logits, input_ids, labels, o.B, c.T, c.S, c.factored_vocab, c.num_factored,
+                                 (int64_t)c.image_vocab_size, obj ? *obj : kNeutralObjective, ds->alpha, ds->temperature, sums, o.st);
     if (!obj) return launch_ce_fwd_bwd(c, logits, input_ids, labels, o.B, sums, o.st);
     return launch_ce_objective(logits, input_ids, labels, o.B, c.T, c.S, c.factored_vocab, c.num_factored, (int64_t)c.image_vocab_size,
                                *obj, sums, o.st);
@@ -716,10 +740,11 @@ int genie_train_forward_ex(const genie_cfg* cfg, const genie_weights* wt, const 
     return genie_train_forward_drop(cfg, wt, input_ids, labels, B, acts, acts_bytes, sums, stream, cond, recompute, nullptr);
 }
 
-// genie_train_forward_drop, and with obj != NULL (checked, not neutral) the general objective behind the same forward
+// genie_train_forward_drop, and with obj != NULL (checked, not neutral) the general objective behind the same forward; with ds != NULL
+// (checked, not neutral) the distillation loss there instead
 static int train_forward_any(const genie_cfg* cfg, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels,
                              int B, float* acts, size_t acts_bytes, double* sums, void* stream, const genie_frame_cond* cond,
-                             int recompute, const genie_dropout* dr, const genie_objective* obj) {
+                             int recompute, const genie_dropout* dr, const genie_objective* obj, const genie_distill* ds = nullptr) {
     GENIE_CHECK_ARG(drop_p_ok(dr), "genie_train_forward: dropout p = %g is not in [0, 1)", (double)dr->p);
     GENIE_TRY(check_mode(recompute, "genie_train_forward"));
     // argument errors (GENIE_E_ARG) are reported before geometry errors (GENIE_E_SHAPE), as they were before train_check
@@ -736,13 +761,14 @@ static int train_forward_any(const genie_cfg* cfg, const genie_weights* wt, cons
     const int M = B * c.T * c.S, V = c.factored_vocab * c.num_factored;
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)acts;
+    if (ds) GENIE_TRY(distill_apart(ds->teacher_logits, (const float*)(base + a.logits), (size_t)M * V, sums, "genie_train_forward_distill"));
     if (c.precision == GENIE_PREC_EXACT) {
         ExactOps o{c, B, M, st, TrainWs{}, 0.0f, make_drop(dr)};
-        return train_forward(o, wt, input_ids, labels, base, a, sums, act, obj);
+        return train_forward(o, wt, input_ids, labels, base, a, sums, act, obj, ds);
     }
     GENIE_CHECK_SHAPE(V >= c.d_model, "training step (16-bit): vocabulary rows %d < d_model %d", V, c.d_model);
     Ops16 o{c, B, M, st, TrainWs{}, 0.0f, npl_of(c), TrainWs16{}, (float*)(base + a.logits), make_drop(dr)};
-    return train_forward(o, wt, input_ids, labels, base, a, sums, act, obj);
+    return train_forward(o, wt, input_ids, labels, base, a, sums, act, obj, ds);
 }
 
 int genie_train_forward_drop(const genie_cfg* cfg, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels,
@@ -757,6 +783,17 @@ int genie_train_forward_obj(const genie_cfg* cfg, const genie_weights* wt, const
     GENIE_TRY(objective_ok(obj, cfg ? cfg->T : (obj ? obj->n_frames : 0), "genie_train_forward_obj"));
     return train_forward_any(cfg, wt, input_ids, labels, B, acts, acts_bytes, sums, stream, cond, recompute, dr,
                              objective_neutral(obj) ? nullptr : obj);
+}
+
+int genie_train_forward_distill(const genie_cfg* cfg, const genie_weights* wt, const int64_t* input_ids, const int64_t* labels,
+                                int B, float* acts, size_t acts_bytes, double* sums, void* stream, const genie_frame_cond* cond,
+                                int recompute, const genie_dropout* dr, const genie_objective* obj, const genie_distill* ds) {
+    GENIE_TRY(distill_ok(ds, ds ? ds->teacher_logits : nullptr, "genie_train_forward_distill"));
+    if (distill_neutral(ds))
+        return genie_train_forward_obj(cfg, wt, input_ids, labels, B, acts, acts_bytes, sums, stream, cond, recompute, dr, obj);
+    GENIE_TRY(objective_ok(obj, cfg ? cfg->T : (obj ? obj->n_frames : 0), "genie_train_forward_distill"));
+    return train_forward_any(cfg, wt, input_ids, labels, B, acts, acts_bytes, sums, stream, cond, recompute, dr,
+                             objective_neutral(obj) ? nullptr : obj, ds);
 }
 
 int genie_train_backward_head(const genie_cfg* cfg, const genie_weights* wt, const genie_weights* wT,
@@ -908,6 +945,32 @@ int genie_ce_objective(float* logits, const int64_t* ids, const int64_t* labels,
         return GENIE_E_LAUNCH;
     }
     return launch_ce_objective(logits, ids, labels, n_clips, T, S, vf, nfac, mask_id, *obj, sums, st);
+}
+
+int genie_distill_layout(size_t* out_host, int n) {
+    const size_t v[4] = {sizeof(genie_distill), offsetof(genie_distill, alpha), offsetof(genie_distill, temperature),
+                         offsetof(genie_distill, teacher_logits)};
+    for (int i = 0; i < n && i < 4 && out_host; ++i) out_host[i] = v[i];
+    return 4;
+}
+
+int genie_ce_distill(float* logits, const float* teacher_logits, const int64_t* ids, const int64_t* labels, int n_clips, int T, int S,
+                     int vf, int nfac, int64_t mask_id, const genie_objective* obj, const genie_distill* ds, double* sums, void* stream) {
+    GENIE_TRY(distill_ok(ds, teacher_logits, "genie_ce_distill"));
+    if (distill_neutral(ds)) return genie_ce_objective(logits, ids, labels, n_clips, T, S, vf, nfac, mask_id, obj, sums, stream);
+    GENIE_TRY(objective_ok(obj, T, "genie_ce_distill"));
+    GENIE_CHECK_ARG(logits && ids && labels && sums, "genie_ce_distill: NULL argument");
+    GENIE_CHECK_ARG(n_clips >= 1 && T >= 1 && S >= 1 && vf >= 1 && nfac >= 1 && nfac <= 4,
+                    "genie_ce_distill: n_clips %d, T %d, S %d, vf %d must be positive and nfac %d in 1 .. 4", n_clips, T, S, vf, nfac);
+    GENIE_CHECK_ARG((long)vf * nfac <= INT32_MAX, "genie_ce_distill: a row of %d x %d logits", nfac, vf);
+    GENIE_TRY(distill_apart(teacher_logits, logits, (size_t)n_clips * T * S * vf * nfac, sums, "genie_ce_distill"));
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(sums, 0, 7 * sizeof(double), st) != hipSuccess) {
+        set_error("genie_ce_distill: hipMemsetAsync failed");
+        return GENIE_E_LAUNCH;
+    }
+    return launch_ce_distill(logits, teacher_logits, ids, labels, n_clips, T, S, vf, nfac, mask_id, obj ? *obj : kNeutralObjective, ds->alpha,
+                             ds->temperature, sums, st);
 }
 
 int genie_dropout_mask(const genie_dropout* dr, int layer, int site, int64_t n, uint8_t* keep, void* stream) {

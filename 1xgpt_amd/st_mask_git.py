@@ -451,21 +451,26 @@ class STMaskGIT(nn.Module):
         n = B * self.config.T * self.config.S * self.config.d_model
         return ws[: n * 4].view(torch.float32).view(B, self.config.T, self.config.S, self.config.d_model)
 
-    def compute_logits_frames(self, x_THW, t0, t1, layout="bcthw", action_ids=None, action_vectors=None):
-        """Logits of frames [t0,t1): (B, V, t1-t0, H, W) for layout='bcthw', (B, t1-t0, S, V) for 'token'."""
+    def compute_logits_frames(self, x_THW, t0, t1, layout="bcthw", action_ids=None, action_vectors=None, out=None, cond=None):
+        """Logits of frames [t0,t1): (B, V, t1-t0, H, W) for layout='bcthw', (B, t1-t0, S, V) for 'token'.
+        out: a contiguous f32 tensor of that many elements on the device to write into (and return) instead of a new one.
+        cond: a genie_frame_cond the caller built from this model (`_cond` / `_frame_cond`), used instead of action_ids / action_vectors."""
         lib = _lib.load()
         cfg, w = self._weights()[:2]
         ids = self._ids(x_THW, whole_clips=True)
         B = ids.shape[0]
-        cond = self._cond(action_ids, B, action_vectors=action_vectors)
+        if cond is None:
+            cond = self._cond(action_ids, B, action_vectors=action_vectors)
         ws = self._workspace(B)
         nt, V = t1 - t0, self.config.factored_vocab_size * self.config.num_factored_vocabs
-        if layout == "bcthw":
-            out = torch.empty(B, V, nt, self.h, self.w, dtype=torch.float32, device=ids.device)
-            lay = _lib.LAYOUT_BCTHW
+        shape = (B, V, nt, self.h, self.w) if layout == "bcthw" else (B, nt, self.config.S, V)
+        lay = _lib.LAYOUT_BCTHW if layout == "bcthw" else _lib.LAYOUT_TOKEN_MAJOR
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=ids.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == math.prod(shape)):
+            raise RuntimeError(f"compute_logits_frames: out must be a contiguous float32 device tensor of {math.prod(shape)} elements")
         else:
-            out = torch.empty(B, nt, self.config.S, V, dtype=torch.float32, device=ids.device)
-            lay = _lib.LAYOUT_TOKEN_MAJOR
+            out = out.view(shape)
         _lib.check(_lib.call_cond(lib, "genie_compute_logits", cond, cfg, w, ids.data_ptr(), B, t0, t1, lay, out.data_ptr(),
                                   ws.data_ptr(), ws.numel(), self._stream()), "genie_compute_logits")
         return out

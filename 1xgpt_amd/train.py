@@ -19,6 +19,8 @@ Design (MI355X-first):
   * EMA of the weights (`ema_decay`; the reference's mechanism is magvit2/modules/ema.py, LitEma): one more flat f32 buffer that the AdamW
     launch itself updates (genie_adamw_ema_step: one more read and write per element, no second pass); `ema_scope()` swaps it
     with the parameters in place to evaluate, sample or save with the averaged weights.
+  * distillation (`teacher`, `distill_alpha`, `distill_temperature`): soft targets from a teacher model's logits, mixed into the same fused
+    loss kernel (genie_train_forward_distill), which reads the teacher's row beside the student's; the teacher's forward is the inference path.
   * training objective (`label_smoothing`, `z_loss`, `frame_weights`): label smoothing, z-loss and per-frame loss weights inside the
     fused loss kernel (genie_train_forward_obj); the backward reads its d logits as it reads the plain loss's; evaluation ignores it.
 MuAdamW (--mu_transfer, train.py:439; third-party mup fork) is not built.
@@ -115,6 +117,29 @@ def make_objective(eps, zeta, weights):
     for t, v in enumerate(weights or ()):
         ob.frame_weight[t] = v
     return ob
+
+
+# ------------------------------------------------------------------ distillation (include/genie_hip.h, "Distillation")
+def distill_settings(distill_alpha=0.0, distill_temperature=1.0):
+    """(alpha, tau) as floats.  Raises ValueError for alpha outside [0, 1] and for a temperature that is not finite and > 0."""
+    alpha, tau = float(distill_alpha), float(distill_temperature)
+    if not 0.0 <= alpha <= 1.0:   # (False for NaN)
+        raise ValueError(f"distill_alpha must be in [0, 1], got {distill_alpha!r}")
+    if not (tau > 0.0 and math.isfinite(tau)):
+        raise ValueError(f"distill_temperature must be finite and > 0, got {distill_temperature!r}")
+    return alpha, tau
+
+
+def check_teacher(config, teacher_config):
+    """A teacher may differ from the student in depth, width, heads and norms; it must share the clip geometry and the vocabulary, and
+    be unconditioned or conditioned exactly as the student is.  Raises ValueError otherwise."""
+    for k in ("T", "S", "image_vocab_size", "num_factored_vocabs"):
+        if getattr(config, k) != getattr(teacher_config, k):
+            raise ValueError(f"the teacher's {k} = {getattr(teacher_config, k)} differs from the student's {getattr(config, k)}")
+    t_cond = (teacher_config.action_vocab_size, teacher_config.action_dim)
+    if t_cond != (0, 0) and t_cond != (config.action_vocab_size, config.action_dim):
+        raise ValueError(f"the teacher is conditioned on (action_vocab_size, action_dim) = {t_cond}, the student on "
+                         f"{(config.action_vocab_size, config.action_dim)}: a teacher is unconditioned or conditioned as the student is")
 
 
 # ------------------------------------------------------------------ pointer tables
@@ -355,8 +380,19 @@ def bucket_bounds(segments, target_elems):
 class GenieTrainer:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0,
                  gradient_accumulation_steps=1, lr_lambda=None, bucket_mb=64, group=None, recompute=False, dropout_seed=0,
-                 ema_decay=None, ema_warmup=False, label_smoothing=0.0, z_loss=0.0, frame_weights=None, trainable=None, lr_scale=None):
-        """trainable: train a subset of the weights (fine-tuning; the reference: requires_grad = False on the rest, which torch.optim.AdamW
+                 ema_decay=None, ema_warmup=False, label_smoothing=0.0, z_loss=0.0, frame_weights=None, trainable=None, lr_scale=None,
+                 teacher=None, distill_alpha=0.0, distill_temperature=1.0):
+        """teacher, distill_alpha, distill_temperature: distillation (include/genie_hip.h, "Distillation"): the loss becomes
+        (1 - alpha) * the objective's hard loss + alpha * tau^2 KL(softmax(teacher / tau) || softmax(student / tau)) + the z-loss, still
+        inside the fused loss kernel, which reads the teacher's logits beside the student's.  `teacher` is an STMaskGIT on the same
+        device, in any precision, depth, width and norm of its own, with the student's T, S and vocabulary, unconditioned or conditioned as
+        the student is (ValueError otherwise).  Every `forward_backward` runs its `compute_logits` on the ids the student sees (and the
+        student's actions and action_drop flags when it is conditioned), on the trainer's stream, into a trainer-owned (B, T, S, V) f32
+        buffer: no host synchronisation.  Without a teacher, `forward_backward(teacher_logits=)` takes precomputed logits.  `last_kd` (the
+        unweighted tau^2 KL per counted token) and `last_teacher_ce` (the teacher's own cross-entropy on the same tokens: it tells a
+        mis-wired teacher at once) sit beside `last_ce`.  The teacher is never trained, saved, averaged, all-reduced or repacked; under
+        data parallelism every rank holds its own.  With teacher None and distill_alpha 0: no new buffer and the entry points of before.
+        trainable: train a subset of the weights (fine-tuning; the reference: requires_grad = False on the rest, which torch.optim.AdamW
         and clip_grad_norm_ then skip).  None: everything.  Else fnmatch patterns over state-dict names (a list, or one comma-separated
         string; `select_trainable` also takes a freeze list and returns names, which are patterns too), or a callable name -> bool.  A
         frozen tensor costs nothing: no gradient (a NULL in the gradient table: include/genie_hip.h, "Frozen tensors"), no moments, no
@@ -406,6 +442,15 @@ class GenieTrainer:
         self.label_smoothing, self.z_loss, self.frame_weights = objective_settings(label_smoothing, z_loss, frame_weights, self.config.T)
         self._objective = make_objective(self.label_smoothing, self.z_loss, self.frame_weights)   # None: neutral
         self.last_ce = None   # plain masked CE of the last micro-batch (0-dim device tensor)
+        self.distill_alpha, self.distill_temperature = distill_settings(distill_alpha, distill_temperature)
+        if teacher is not None:
+            check_teacher(self.config, teacher.config)
+            if teacher._device() != dev:
+                raise ValueError(f"the teacher is on {teacher._device()}, the student on {dev}")
+        self.teacher = teacher
+        self._distilling = np.float32(self.distill_alpha) != 0.0   # the library's alpha is a float
+        self._teacher_logits = None   # (B, T, S, V) f32, per batch size
+        self.last_kd = self.last_teacher_ce = None   # tau^2 KL and the teacher's own CE per counted token, of the last micro-batch
 
         named = dict(model.named_parameters())
         if trainable is None:
@@ -464,7 +509,8 @@ class GenieTrainer:
         self.reducer = BucketReducer(self.grads, bucket_bounds(self.segments, bucket_mb * (1 << 20) // 4), group)
         self._dw_scratch = None   # where the gradient of a frozen action_proj.weight goes (genie_action_rows_backward needs a d_weight)
         # [sum loss, sum hits, n]; with an objective [sum w l, sum hits, W, sum plain nll, n]
-        self.sums = torch.zeros(3 if self._objective is None else 5, dtype=torch.float64, device=dev)
+        # distilling: [.., sum plain kd, sum teacher plain nll]
+        self.sums = torch.zeros(7 if self._distilling else (3 if self._objective is None else 5), dtype=torch.float64, device=dev)
         self.sumsq = torch.zeros(1, dtype=torch.float64, device=dev)
         self.scratch = torch.zeros(1024, dtype=torch.float64, device=dev)
         self._acts = self._ws = None
@@ -497,15 +543,56 @@ class GenieTrainer:
     # ------------------------------------------------------------------ buffers
     def _buffers(self, B):
         if B != self._B:
-            self._acts = self._ws = None
+            self._acts = self._ws = self._teacher_logits = None
             na = _lib.call_recompute(self.lib, "genie_train_activation_bytes", self.recompute, self.cfg, B)
             nw = _lib.call_recompute(self.lib, "genie_train_workspace_bytes", self.recompute, self.cfg, B)
             if na == 0 or nw == 0:
                 _lib.check(self.lib.genie_check_config(self.cfg), "genie_check_config")
             self._acts = torch.empty(na, dtype=torch.uint8, device=self.params.device)
             self._ws = torch.empty(nw, dtype=torch.uint8, device=self.params.device)
+            if self._distilling and self.teacher is not None:
+                V = self.config.factored_vocab_size * self.config.num_factored_vocabs
+                self._teacher_logits = torch.empty(B, self.config.T, self.config.S, V, dtype=torch.float32, device=self.params.device)
+                self.teacher._workspace(B)   # the teacher's own workspace, allocated here and not inside the first step
             self._B = B
         return self._acts, self._ws
+
+    def _frame_cond(self, model, action_ids, action_vectors, drop, B):
+        """The genie_frame_cond of `model` (the student or a conditioned teacher) for one micro-batch; `drop`: checked (B,) bool or None."""
+        cond = model._cond(action_ids, B, action_vectors=action_vectors)
+        if drop is not None:
+            vectors = cond.vectors
+            rows_ids = torch.where(drop.to(cond.keep.device)[:, None], model.NULL_ROW, cond.keep).contiguous()
+            cond = model._frame_cond(rows_ids, like=cond)
+            cond.vectors = vectors
+        return cond
+
+    def _distill(self, ids, B, teacher_logits, action_ids, action_vectors, drop):
+        """The genie_distill of one micro-batch (None when not distilling): the teacher's logits of the ids the student sees, from the
+        caller or from the live teacher (one inference forward on this stream into the trainer's buffer)."""
+        if not self._distilling:
+            if teacher_logits is not None:
+                raise ValueError("teacher_logits given to a trainer with distill_alpha == 0")
+            return None
+        c = self.config
+        shape = (B, c.T, c.S, c.factored_vocab_size * c.num_factored_vocabs)
+        if teacher_logits is not None:
+            tl = teacher_logits
+            if not (tl.is_cuda and tl.dtype == torch.float32 and tuple(tl.shape) == shape):
+                raise RuntimeError(f"expected teacher_logits of shape {shape}, float32, on the device; got {tuple(tl.shape)} {tl.dtype} "
+                                   f"{tl.device}")
+            tl = tl.contiguous()
+        elif self.teacher is not None:
+            t = self.teacher
+            conditioned = t.config.action_vocab_size or t.config.action_dim
+            cond = self._frame_cond(t, action_ids, action_vectors, drop, B) if conditioned else None
+            with torch.no_grad():
+                tl = t.compute_logits_frames(ids, 0, c.T, "token", out=self._teacher_logits, cond=cond)
+        else:
+            raise ValueError(f"distill_alpha = {self.distill_alpha} needs a teacher: build the trainer with teacher=, or pass teacher_logits=")
+        ds = _lib.Distill(alpha=self.distill_alpha, temperature=self.distill_temperature, teacher_logits=tl.data_ptr())
+        ds.keep = tl   # the logits live as long as the struct
+        return ds
 
     @staticmethod
     def _stream():
@@ -521,7 +608,8 @@ class GenieTrainer:
         return dr
 
     # ------------------------------------------------------------------ forward / backward (train.py:611-617)
-    def forward_backward(self, input_ids, labels, accumulate=False, reduce=True, action_ids=None, action_vectors=None, action_drop=None):
+    def forward_backward(self, input_ids, labels, accumulate=False, reduce=True, action_ids=None, action_vectors=None, action_drop=None,
+                         teacher_logits=None):
         """One micro-batch: loss/acc of STMaskGIT.forward and gradients into the flat buffer (added when
         `accumulate`).  Returns (loss, acc) as 0-dim float64 CUDA tensors (no host sync).
         action_ids: (B, T) per-frame actions of an action-conditioned model (config.action_vocab_size > 0).
@@ -529,7 +617,9 @@ class GenieTrainer:
         the existing forward and backward run on those rows, and d loss / d rows -- a (1 + B T, d) scratch, row 0 the null row's -- becomes
         the gradients of action_proj (genie_action_rows_backward, one launch) and of action_null.
         action_drop: (B,) bool with action_vectors (action dropout, data.maskgit_collate): a dropped clip's frames read the null row, so
-        their projected rows get a zero gradient and the null row theirs."""
+        their projected rows get a zero gradient and the null row theirs.
+        teacher_logits: (B, T, S, V) f32 device logits of a teacher on these input_ids, token-major, for a trainer with distill_alpha > 0
+        (offline distillation from saved logits): used instead of the trainer's teacher.  They are read, never written."""
         self._not_in_ema_scope("forward_backward")
         if not (input_ids.is_cuda and labels.is_cuda):
             raise RuntimeError("1xgpt_amd runs on the GPU only (no CPU fallback): move the batch to cuda")
@@ -545,17 +635,17 @@ class GenieTrainer:
             drop = torch.as_tensor(action_drop)
             if drop.dtype != torch.bool or tuple(drop.shape) != (B,):
                 raise RuntimeError(f"expected action_drop of shape ({B},) and dtype bool, got {tuple(drop.shape)} {drop.dtype}")
-        cond = self.model._cond(action_ids, B, action_vectors=action_vectors)
-        if drop is not None:
-            vectors = cond.vectors
-            rows_ids = torch.where(drop.to(cond.keep.device)[:, None], self.model.NULL_ROW, cond.keep).contiguous()
-            cond = self.model._frame_cond(rows_ids, like=cond)
-            cond.vectors = vectors
+        cond = self._frame_cond(self.model, action_ids, action_vectors, drop, B)
         acts, ws = self._buffers(B)
+        distill = self._distill(ids, B, teacher_logits, action_ids, action_vectors, drop)
         lib, cfg, st = self.lib, self.cfg, self._stream()
         acc_flag = 1 if accumulate else 0
         drop = self._dropout()
-        if self._objective is None:
+        if distill is not None:   # the same forward, the distillation loss kernel behind it; the backward reads its d logits as before
+            _lib.check(lib.genie_train_forward_distill(cfg, self.w_table, ids.data_ptr(), lab.data_ptr(), B, acts.data_ptr(), acts.numel(),
+                                                       self.sums.data_ptr(), st, cond, self.recompute, drop, self._objective, distill),
+                       "genie_train_forward_distill")
+        elif self._objective is None:
             _lib.check(_lib.call_drop(lib, "genie_train_forward", self.recompute, drop, cfg, self.w_table, ids.data_ptr(), lab.data_ptr(), B,
                                       acts.data_ptr(), acts.numel(), self.sums.data_ptr(), st, cond=cond), "genie_train_forward")
         else:   # the same forward, the general loss kernel behind it; every backward call below reads its d logits as before
@@ -614,6 +704,9 @@ class GenieTrainer:
         if reduce:
             self.reducer.finish()
         loss = sums[0] / sums[2]
+        if distill is not None:
+            self.last_ce, self.last_kd, self.last_teacher_ce = sums[3] / sums[4], sums[5] / sums[4], sums[6] / sums[4]
+            return loss, sums[1] / sums[4]
         if self._objective is None:
             self.last_ce = loss
             return loss, sums[1] / sums[2]
@@ -666,11 +759,15 @@ class GenieTrainer:
         is_update = (self._micro + 1) % self.accum == 0
         loss, acc = self.forward_backward(batch["input_ids"], batch["labels"], accumulate=self._micro % self.accum != 0,
                                           reduce=is_update and self.accum == 1, action_ids=batch.get("action_ids"),
-                                          action_vectors=batch.get("action_vectors"), action_drop=batch.get("action_drop"))
+                                          action_vectors=batch.get("action_vectors"), action_drop=batch.get("action_drop"),
+                                          # (a trainer that does not distil ignores the key, as it ignores every key it does not know)
+                                          teacher_logits=batch.get("teacher_logits") if self._distilling else None)
         self._micro += 1
         out = {"loss": loss, "acc": acc}
-        if self._objective is not None:
+        if self._objective is not None or self._distilling:
             out["ce"] = self.last_ce
+        if self._distilling:
+            out["kd"], out["teacher_ce"] = self.last_kd, self.last_teacher_ce
         if is_update:
             if self.accum > 1 and self.reducer.world > 1:  # no_sync() micro-batches: reduce once, after the last
                 self.reducer.reset()
@@ -750,6 +847,8 @@ class GenieTrainer:
                          "gradient_accumulation_steps": self.accum, "recompute": bool(self.recompute),
                          "label_smoothing": self.label_smoothing, "z_loss": self.z_loss, "frame_weights": self.frame_weights,
                          "lr_scale": self.lr_scale}}
+        if self._distilling:   # (a trainer that does not distil keeps the state of before, key for key)
+            out["hyper"].update(distill_alpha=self.distill_alpha, distill_temperature=self.distill_temperature)
         if self.ema is not None:
             avg = self.ema_state_dict()
             out["ema"] = {"state": {n: avg[n] for n in self.trainable}, "updates": self.ema_updates, "decay": self.ema_decay,
@@ -766,7 +865,7 @@ class GenieTrainer:
         mine = {"lr": self.base_lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
                 "max_grad_norm": self.max_grad_norm, "gradient_accumulation_steps": self.accum,
                 "label_smoothing": self.label_smoothing, "z_loss": self.z_loss, "frame_weights": self.frame_weights,
-                "lr_scale": self.lr_scale}
+                "lr_scale": self.lr_scale, "distill_alpha": self.distill_alpha, "distill_temperature": self.distill_temperature}
         diff = {k: (v, mine[k]) for k, v in (sd.get("hyper") or {}).items()
                 if k in mine and (tuple(v) if isinstance(v, (list, tuple)) else v) != mine[k]}
         if saved_ema is not None and self.ema is not None:

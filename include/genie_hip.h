@@ -930,6 +930,56 @@ int genie_train_forward_obj(const genie_cfg* cfg, const genie_weights* w, const 
 int genie_ce_objective(float* logits, const int64_t* ids, const int64_t* labels, int n_clips, int T, int S, int vf, int nfac,
                        int64_t mask_id, const genie_objective* obj, double* sums_out, void* stream);
 
+/* Distillation (additions; nothing above changes): soft targets from a teacher's logits in the fused loss kernel.  The counted-token rule,
+ * the frame weights, c_t, W, n and the (float)((double) w_t / W) gradient scale are those of "Training objective".  For a counted token and
+ * factor f with student logits z (vf values), teacher logits u (vf values; f32, token-major, the student's (n_clips, T, S, nfac * vf)
+ * shape), target y, mix alpha in [0, 1] and temperature tau > 0:
+ *     lse    = logsumexp(z)                    p_k  = exp(z_k - lse)
+ *     pt_k   = softmax(z / tau)_k              r_k  = softmax(u / tau)_k
+ *     hard_f = (1 - eps) (lse - z_y) + eps (lse - mean_k z_k)                      (the smoothed CE above)
+ *     kd_f   = tau^2 sum_k r_k (log r_k - log pt_k)                                (tau^2 KL(r || pt), Hinton et al. 2015)
+ *     l_f    = (1 - alpha) hard_f + alpha kd_f + zeta lse^2                        l_n = sum_f l_f
+ *     d l_f / d z_k = (1 - alpha)(p_k - q_k) + 2 zeta lse p_k + alpha tau (pt_k - r_k)
+ * with q the smoothed target above: at alpha = 0 the formula of "Training objective", term for term.  log r_k and log pt_k are evaluated in
+ * log-softmax form, (u_k - max u) / tau - log sum_j exp((u_j - max u) / tau), never as the log of a probability: a class whose r_k
+ * underflowed to 0 contributes 0.  Logits are finite.  The sums buffer holds SEVEN doubles
+ *     [sum w l, sum hits, W, sum plain nll, n, sum plain kd, sum teacher plain nll]
+ *     loss = s0 / s2,  acc = s1 / s4,  ce = s3 / s4,  kd = s5 / s4,  teacher_ce = s6 / s4
+ * entries 5 and 6 over ALL counted tokens whatever their weight, as hits and the plain nll: kd is the unweighted tau^2 KL per token, and
+ * teacher_ce the teacher's own cross-entropy sum_f (logsumexp(u) - u_y) on the same tokens -- the cheap check that the teacher is wired
+ * to the same ids, layout and vocabulary order.  f32 in all three precisions: per lane and factor, with inv_tau = 1.0f / tau,
+ * d = (z - max z) [* inv_tau], c = (u - max u) [* inv_tau] (the products only when tau != 1), kd_f = (tau * tau) * wave sum of
+ * r ((c - d) - (log su - log st)), an element ((1 - alpha)(p - q) + (2 zeta lse) p + (alpha tau)(pt - r)) wgt; tests/distill_model.py
+ * restates the order.  The student logits are replaced by d loss / d logits; the teacher logits are read only.  Fixed summation order and
+ * no atomics on d logits (the same bytes run to run); the five accumulated sums use double atomics.
+ * Neutral means ds == NULL or alpha == 0: the call of before, and the teacher pointer is never dereferenced.  A struct that is given is
+ * validated BEFORE the neutral shortcut is taken: alpha == 0 with a temperature <= 0 is refused, not passed on.  The struct is read on the
+ * host during the call.  Refused with GENIE_E_ARG before anything is enqueued: alpha outside [0, 1] or NaN; a temperature that is not
+ * finite or <= 0; alpha > 0 with a NULL teacher pointer; teacher logits that overlap the student logits or the seven sums; and
+ * everything "Training objective" refuses. */
+typedef struct genie_distill {
+    float alpha;                  /* mix, 0 <= alpha <= 1; 0 = no distillation */
+    float temperature;            /* tau > 0 */
+    const float* teacher_logits;  /* (n_clips, T, S, nfac * vf) f32 on the device, read only */
+} genie_distill;
+/* sizeof(genie_distill) and the offsets of alpha, temperature, teacher_logits: writes min(n, 4) entries, returns 4. */
+int genie_distill_layout(size_t* out_host, int n);
+/* genie_train_forward_obj with distillation: the same arguments and `ds`; sums_out always has room for seven doubles.  ds == NULL or
+ * alpha == 0: the call IS the _obj call (same launches, same bits, three or five doubles written).  Else the seven sums above, and the
+ * logits slot holds d loss / d logits of the mixed loss: head, layers and embed backward are untouched (recomputation, dropout, frozen
+ * tensors and accumulation compose as they are). */
+int genie_train_forward_distill(const genie_cfg* cfg, const genie_weights* w, const int64_t* input_ids, const int64_t* labels,
+                                int B, float* acts, size_t acts_bytes, double* sums_out, void* stream,
+                                const genie_frame_cond* cond, int recompute, const genie_dropout* dr, const genie_objective* obj,
+                                const genie_distill* ds);
+/* The loss launch alone on caller-owned buffers, the counterpart of genie_ce_objective (its geometry freedom; obj == NULL: eps = zeta = 0,
+ * all frames weigh 1).  The teacher rows are `teacher_logits`; alpha and temperature come from `ds`, whose own pointer is not read.
+ * ds == NULL or alpha == 0: the call IS genie_ce_objective(logits, ids, labels, ..., obj, sums_out, stream).  Else seven doubles,
+ * overwritten. */
+int genie_ce_distill(float* logits, const float* teacher_logits, const int64_t* ids, const int64_t* labels, int n_clips, int T, int S,
+                     int vf, int nfac, int64_t mask_id, const genie_objective* obj, const genie_distill* ds, double* sums_out,
+                     void* stream);
+
 /* The temporal (causal, over the T frames of one spatial position) attention backward of the step, alone -- the counterpart of
  * genie_attention_core for the backward; f32 in every precision.  qkv (B,T,S,3*d_model) is the saved q | k | v; qk holds the q | k the
  * scores were made from, q at column 0 and k at column d_model of rows of qk_ld floats: qkv itself (qk_ld = 3*d_model) or the

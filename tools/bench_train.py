@@ -53,6 +53,11 @@ def main():
     ap.add_argument("--train_only", type=str, default=None, metavar="P[,P...]",
                     help="train only the tensors matching these fnmatch patterns over state-dict names (GenieTrainer(trainable=...))")
     ap.add_argument("--freeze", type=str, default=None, metavar="P[,P...]", help="freeze the tensors matching these patterns")
+    ap.add_argument("--teacher", default=None, choices=["c35", "c138"],
+                    help="distil from a teacher of this shape (synthetic weights; GenieTrainer(teacher=...)): its forward runs in every step")
+    ap.add_argument("--teacher_precision", default=None, choices=["exact", "f16x3", "bf16"], help="the teacher's precision (default: --precision)")
+    ap.add_argument("--distill_alpha", type=float, default=0.5, help="with --teacher: the mix of the distillation loss")
+    ap.add_argument("--distill_temperature", type=float, default=1.0, help="with --teacher: the temperature of the distillation loss")
     a = ap.parse_args()
     cfgm, syn, _lib = pkg("config"), pkg("synthetic"), pkg("_lib")
     cfg = cfgm.c138() if a.config == "c138" else cfgm.c35()
@@ -73,8 +78,16 @@ def main():
             trainable = sorted(pkg("train").select_trainable([n for n, _ in model.named_parameters()], a.train_only, a.freeze))
         except ValueError as e:
             ap.error(str(e))
+    teacher = None
+    if a.teacher:
+        tcfg = cfgm.c138() if a.teacher == "c138" else cfgm.c35()
+        tcfg.qk_norm, tcfg.T = False, cfg.T
+        teacher = pkg("st_mask_git").STMaskGIT(tcfg, precision=a.teacher_precision or a.precision)
+        teacher = teacher.load_numpy_state_dict(syn.make_state_dict(tcfg, seed=5, law="init")).to("cuda")
     tr = pkg("train").GenieTrainer(model, lr=1e-4, max_grad_norm=1.0, recompute=a.recompute, ema_decay=a.ema_decay,
-                                   label_smoothing=a.label_smoothing, z_loss=a.z_loss, frame_weights=fw, trainable=trainable)
+                                   label_smoothing=a.label_smoothing, z_loss=a.z_loss, frame_weights=fw, trainable=trainable,
+                                   teacher=teacher, distill_alpha=a.distill_alpha if teacher is not None else 0.0,
+                                   distill_temperature=a.distill_temperature)
     lib = _lib.load()
     if a.ema_unfused:
         if a.ema_decay is None:
@@ -91,6 +104,18 @@ def main():
         opt_events.append(ev)
         return out
     tr.optimizer_step = timed_optimizer_step
+    teacher_events = []   # the teacher's forward (inside forward_backward) between two events of its own
+    inner_distill = tr._distill
+
+    def timed_distill(*args):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        out = inner_distill(*args)
+        ev[1].record()
+        teacher_events.append(ev)
+        return out
+    if teacher is not None:
+        tr._distill = timed_distill
     ids = torch.from_numpy(syn.make_clips(a.batch, cfg, seed=1)).cuda()
     collate = pkg("data").maskgit_collate
     torch.manual_seed(0)
@@ -102,6 +127,7 @@ def main():
         out = tr.train_step(batch)
     torch.cuda.synchronize()
     opt_events.clear()
+    teacher_events.clear()
     if a.breakdown:
         lib.genie_profile_enable(0x1F)
         lib.genie_profile_reset()
@@ -124,6 +150,11 @@ def main():
     ms = sorted(e0.elapsed_time(e1) for e0, e1 in opt_events)
     print(f"  optimizer_step: AdamW launches {len(tr.adam_runs) * (2 if a.ema_unfused else 1)}, {sum(ms) / len(ms):.3f} ms/step "
           f"(min {ms[0]:.3f}, median {ms[len(ms) // 2]:.3f}, max {ms[-1]:.3f}; {tr.n_flat * 4 / 1e9:.3f} GB per flat f32 buffer)")
+    if teacher is not None:
+        tms = sorted(e0.elapsed_time(e1) for e0, e1 in teacher_events)
+        print(f"  distillation: teacher {a.teacher} {a.teacher_precision or a.precision}, alpha {a.distill_alpha:g}, tau {a.distill_temperature:g}: "
+              f"teacher forward {sum(tms) / len(tms):.3f} ms/step (min {tms[0]:.3f}, max {tms[-1]:.3f}) = {sum(tms) / len(tms) / (dt * 1e3):.1%} "
+              f"of the step; kd {float(out['kd']):.4f}, teacher_ce {float(out['teacher_ce']):.4f}, ce {float(out['ce']):.4f}")
     n_state = 2 + (tr.ema is not None)   # exp_avg, exp_avg_sq (and the average): one f32 per trainable element each
     print(f"  trainable {len(tr.trainable)} of {len(tr.order)} tensors, backward layers {cfg.num_layers - tr.layout.stop} of {cfg.num_layers}, "
           f"embedding backward {'on' if tr.layout.embed else 'off'}: gradient buffer = all-reduce traffic per step {tr.n_train * 4} bytes, "
@@ -136,12 +167,12 @@ def main():
             if buf[0]:
                 print(f"  {name:14s} launches {int(buf[0]):6d}  {buf[1]/a.steps:9.2f} ms/step  "
                       f"{buf[2]/max(buf[1],1e-9)/1e9:8.1f} TFLOP/s  {buf[3]/max(buf[1],1e-9)/1e6:8.1f} GB/s")
-        if tr._objective is not None:   # the general loss kernels by name (class "other"; the neutral step's are not bracketed)
+        if tr._objective is not None or tr._distilling:   # the general loss kernels by name (class "other"; the neutral step's are not bracketed)
             kbuf = C.create_string_buffer(16384)
             _lib.check(lib.genie_profile_kernels(_lib.KC_OTHER, kbuf, len(kbuf)), "profile_kernels")
             for ln in kbuf.value.decode().splitlines():
                 name, n, ms = ln.split("\t")[:3]
-                if name in ("ce_objective_kernel", "count_frames_kernel"):
+                if name in ("ce_objective_kernel", "count_frames_kernel", "ce_distill_kernel"):
                     print(f"    {name:22s} launches {float(n) / a.steps:6.0f}  {float(ms) / a.steps:9.4f} ms/step")
         if a.mlp_drop:   # the dropout kernels by name (class "other"): launches and milliseconds per step
             kbuf = C.create_string_buffer(16384)

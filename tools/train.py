@@ -9,6 +9,10 @@ ema/ sub-directory that STMaskGIT.from_pretrained loads like any checkpoint, --e
 --label_smoothing E, --z_loss Z and --frame_loss_weights w0,w1,... shape the training loss (per factor F.cross_entropy(label_smoothing=E)
 + Z * logsumexp^2, weighted per frame); the step line then prints the plain cross-entropy as `ce` next to train_loss, and evaluation
 reports the plain cross-entropy as before.
+--teacher_path DIR --distill_alpha A --distill_temperature TAU distil a trained model into this one: the loss becomes (1 - A) * the loss
+above + A * TAU^2 KL(teacher || student) at temperature TAU, inside the same loss kernel; the teacher (a from_pretrained directory with
+the student's window and vocabulary, any depth and width, --teacher_precision) runs one inference forward per micro-batch on the ids the
+student sees.  The step line then prints `kd` (the KL per masked token) and `teacher_ce` (the teacher's own cross-entropy there).
 A config with action_vocab_size > 0 trains an action-conditioned model on the datasets' actions.bin (refused without one);
 --warmstart_path from an unconditioned checkpoint then starts from a zero action table.
 
@@ -82,6 +86,14 @@ def parse_args():
     p.add_argument("--frame_loss_weights", type=str, default=None,
                    help="comma-separated loss weights >= 0, one per frame of the window (w0,w1,...; frame 0 is never counted): the "
                         "loss is the weighted mean over the masked tokens")
+    p.add_argument("--teacher_path", type=str, default=None, metavar="DIR",
+                   help="distil from this model (a save_pretrained directory with the student's T, S and vocabulary; any depth and width)")
+    p.add_argument("--teacher_precision", choices=["exact", "f16x3", "bf16"], default=None,
+                   help="precision of the teacher's forward (default: --precision)")
+    p.add_argument("--distill_alpha", type=float, default=0.0,
+                   help="mix in [0, 1] of the distillation loss: (1 - alpha) * hard loss + alpha * tau^2 KL(teacher || student); needs "
+                        "--teacher_path when > 0")
+    p.add_argument("--distill_temperature", type=float, default=1.0, help="temperature tau > 0 of both softmaxes in the KL")
     p.add_argument("--ema_decay", type=float, default=None,
                    help="keep an exponential moving average of the weights with this decay in [0, 1] (e.g. 0.999); checkpoints gain an "
                         "ema/ directory with the averaged weights")
@@ -122,6 +134,12 @@ def main():
         importlib.import_module("1xgpt_amd.train").objective_settings(args.label_smoothing, args.z_loss, frame_weights)
     except ValueError as e:
         sys.exit(f"train.py: --label_smoothing / --z_loss / --frame_loss_weights: {e}")
+    try:
+        importlib.import_module("1xgpt_amd.train").distill_settings(args.distill_alpha, args.distill_temperature)
+    except ValueError as e:
+        sys.exit(f"train.py: --distill_alpha / --distill_temperature: {e}")
+    if args.distill_alpha > 0 and not args.teacher_path:
+        sys.exit(f"train.py: --distill_alpha {args.distill_alpha} needs --teacher_path")
     if args.mu_transfer:
         raise NotImplementedError("--mu_transfer needs the un-vendored mup fork (MuAdamW, set_base_shapes): not built")
     P = lambda n: importlib.import_module("1xgpt_amd." + n)  # noqa: E731
@@ -237,12 +255,20 @@ def main():
             trainmod.lr_factors(names, lr_scale)
     except ValueError as e:
         sys.exit(f"train.py: --train_only / --freeze / --lr_scale: {e}")
+    teacher = None
+    if args.teacher_path and args.distill_alpha > 0:   # never trained, saved or exchanged: every rank loads its own
+        teacher = STMaskGIT.from_pretrained(args.teacher_path, precision=args.teacher_precision or args.precision).to(dev)
+        try:
+            trainmod.check_teacher(model.config, teacher.config)
+        except ValueError as e:
+            sys.exit(f"train.py: --teacher_path {args.teacher_path}: {e}")
     tr = trainmod.GenieTrainer(model, lr=args.learning_rate, betas=(args.adam_beta_1, args.adam_beta_2), eps=args.adam_eps,
                                weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm,
                                gradient_accumulation_steps=accum, lr_lambda=lr_lambda, recompute=args.recompute_activations,
                                dropout_seed=args.dropout_seed, ema_decay=args.ema_decay, ema_warmup=args.ema_warmup,
                                label_smoothing=args.label_smoothing, z_loss=args.z_loss, frame_weights=frame_weights,
-                               trainable=trainable, lr_scale=lr_scale)
+                               trainable=trainable, lr_scale=lr_scale, teacher=teacher, distill_alpha=args.distill_alpha,
+                               distill_temperature=args.distill_temperature)
     if args.resume_from_checkpoint:  # optimizer moments, step counters (train.py:560-590), the EMA of the weights
         tr.load_state_dict(torch.load(os.path.join(args.resume_from_checkpoint, "trainer_state.pt"), map_location=dev))
     n_params = sum(p.numel() for p in model.parameters())
@@ -271,8 +297,9 @@ def main():
 
     ckpt_every = int(args.checkpointing_steps) if args.checkpointing_steps.isdigit() else None
     completed, t0 = tr.completed_steps, time.time()
-    with_ce = tr._objective is not None   # a training objective: the step also reports the plain CE
-    loss_info = torch.zeros(3 if with_ce else 2, dtype=torch.float64, device=dev)   # sum loss, clips [, sum plain CE]
+    # a training objective: the step also reports the plain CE; distillation: the KL and the teacher's own CE too
+    extras = (["ce"] if tr._objective is not None or tr._distilling else []) + (["kd", "teacher_ce"] if tr._distilling else [])
+    loss_info = torch.zeros(2 + len(extras), dtype=torch.float64, device=dev)   # sum loss, clips [, sum plain CE [, sum kd, sum teacher CE]]
     consumed = completed * accum  # micro-batches already trained on (resume): skip them in the data order
     for epoch in range(consumed // micro_per_epoch, 10 ** 9):
         g = torch.Generator().manual_seed((args.seed or 0) + epoch)
@@ -284,14 +311,14 @@ def main():
                                             null_action=args.null_action)
             out = tr.train_step(batch)
             loss_info += torch.stack([out["loss"] * B, torch.tensor(float(B), device=dev, dtype=torch.float64)]
-                                     + ([out["ce"] * B] if with_ce else []))
+                                     + [out[k] * B for k in extras])
             if "lr" not in out:
                 continue
             completed += 1
             if world > 1:
                 torch.distributed.all_reduce(loss_info)
             avg = (loss_info[0] / loss_info[1]).item()
-            ce = f" ce {(loss_info[2] / loss_info[1]).item():.4f}" if with_ce else ""
+            ce = "".join(f" {k} {(loss_info[2 + i] / loss_info[1]).item():.4f}" for i, k in enumerate(extras))
             loss_info.zero_()
             if rank == 0:
                 dt, t0 = time.time() - t0, time.time()
