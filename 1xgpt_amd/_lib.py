@@ -83,6 +83,13 @@ class Distill(C.Structure):
     _fields_ = [("alpha", C.c_float), ("temperature", C.c_float), ("teacher_logits", c_ptr)]
 
 
+class LoraItem(C.Structure):
+    """genie_lora_item: one adapted Linear of a genie_lora_merge / genie_lora_project call (device pointers; 1xgpt_amd/lora.py)."""
+    _fields_ = [(n, c_ptr) for n in ("w", "w0", "a", "b", "dw", "da", "db")] + [(n, C.c_int32) for n in ("out", "in_", "rank")] + [
+        ("scale", C.c_float)]
+
+
+LORA_MAX_ITEMS, LORA_MAX_RANK = 8, 64   # GENIE_LORA_MAX_ITEMS, GENIE_LORA_MAX_RANK
 ACTION_MAX_DIM = 256   # GENIE_ACTION_MAX_DIM
 WIDE_QKV, WIDE_PROJ, WIDE_FC1, WIDE_FC2 = 1, 2, 1, 2          # bits of the w16_wide fields (genie_hip.h)
 FUSED_QKV_STREAM = 4                                        # spatial attention: fused_w16 = [proj stream | qkv stream]
@@ -296,6 +303,12 @@ _a = SIGNATURES["genie_train_pack_weights"][1]
 SIGNATURES["genie_train_pack_weights_some"] = (C.c_int, _a[:-1] + [C.POINTER(Weights), c_ptr])
 del _a
 
+# LoRA adapters: (items, n, stream), (items, n) and (items, n, accumulate, scratch, scratch_bytes, stream)
+SIGNATURES["genie_lora_layout"] = (C.c_int, [C.POINTER(C.c_size_t), C.c_int])
+SIGNATURES["genie_lora_merge"] = (C.c_int, [C.POINTER(LoraItem), C.c_int, c_ptr])
+SIGNATURES["genie_lora_project_scratch_bytes"] = (C.c_size_t, [C.POINTER(LoraItem), C.c_int])
+SIGNATURES["genie_lora_project"] = (C.c_int, [C.POINTER(LoraItem), C.c_int, C.c_int, c_ptr, C.c_size_t, c_ptr])
+
 _lib = None
 
 
@@ -348,6 +361,10 @@ def load():
         mine = [C.sizeof(Distill)] + [getattr(Distill, n).offset for n, _ in Distill._fields_]
         if "genie_distill_layout" not in missing and (lib.genie_distill_layout(lay, 4) != 4 or list(lay)[:4] != mine):
             raise RuntimeError(f"genie_distill layout {list(lay)[:4]} != the ctypes declaration {mine}")
+        lay = (C.c_size_t * 12)()
+        mine = [C.sizeof(LoraItem)] + [getattr(LoraItem, n).offset for n, _ in LoraItem._fields_]
+        if "genie_lora_layout" not in missing and (lib.genie_lora_layout(lay, 12) != 12 or list(lay) != mine):
+            raise RuntimeError(f"genie_lora_item layout {list(lay)} != the ctypes declaration {mine}")
         if os.environ.get("GENIE_HIP_LIBRARY") or lib.genie_study_build():
             import sys
             print(f"1xgpt_amd: using {LIB_PATH} (study build: {bool(lib.genie_study_build())}) -- not the shipping library"

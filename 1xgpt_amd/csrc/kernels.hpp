@@ -473,6 +473,20 @@ int launch_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, s
 int launch_ema_update(float* ema, const float* p, size_t n, float omd, hipStream_t st);
 int launch_swap_f32(float* a, float* b, size_t n, hipStream_t st);
 
+// LoRA adapters (kernels_lora.hip): what one launch is told, by value -- the caller's items, the running tile counts of the merge /
+// project grid (`first`) and block counts of the reduce grid (`rfirst`, segments dA, dB per item), and where each item's slabs lie
+constexpr int LORA_MAX_ITEMS = GENIE_LORA_MAX_ITEMS, LORA_MAX_RANK = GENIE_LORA_MAX_RANK;
+struct LoraTable {
+    genie_lora_item it[LORA_MAX_ITEMS];
+    size_t da_off[LORA_MAX_ITEMS], db_off[LORA_MAX_ITEMS];   // floats into scratch
+    float* scratch;
+    int first[LORA_MAX_ITEMS + 1], rfirst[2 * LORA_MAX_ITEMS + 1];
+    int n;
+};
+bool lora_table(const genie_lora_item* items, int n, LoraTable& tb, size_t& scratch_floats);
+int launch_lora_merge(const LoraTable& tb, hipStream_t st);
+int launch_lora_project(const LoraTable& tb, int accumulate, hipStream_t st);
+
 // api.hip: the host helpers its entry points share with the generate loops (generate_api.hip)
 Workspace carve(const genie_cfg& c, int B, void* base);   // base == NULL: sizes only
 int check_cfg(const genie_cfg* c);

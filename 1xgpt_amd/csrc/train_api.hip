@@ -1020,4 +1020,89 @@ int genie_swap_f32(float* a, float* b, size_t n, void* stream) {
     return launch_swap_f32(a, b, n, (hipStream_t)stream);
 }
 
+int genie_lora_layout(size_t* out_host, int n) {
+    const size_t v[12] = {sizeof(genie_lora_item), offsetof(genie_lora_item, w), offsetof(genie_lora_item, w0),
+                          offsetof(genie_lora_item, a), offsetof(genie_lora_item, b), offsetof(genie_lora_item, dw),
+                          offsetof(genie_lora_item, da), offsetof(genie_lora_item, db), offsetof(genie_lora_item, out),
+                          offsetof(genie_lora_item, in), offsetof(genie_lora_item, rank), offsetof(genie_lora_item, scale)};
+    for (int i = 0; i < n && i < 12 && out_host; ++i) out_host[i] = v[i];
+    return 12;
+}
+
+static bool lora_overlap(const void* p, size_t np, const void* q, size_t nq) {   // ranges of np / nq floats
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + 4 * nq && b < a + 4 * np;
+}
+// what genie_lora_merge (project = false) or genie_lora_project accepts, on the host alone
+static int lora_ok(const genie_lora_item* items, int n, bool project, const char* where) {
+    GENIE_CHECK_ARG(items != nullptr, "%s: NULL items", where);
+    GENIE_CHECK_ARG(n >= 1 && n <= GENIE_LORA_MAX_ITEMS, "%s: n = %d is not in 1 .. %d", where, n, GENIE_LORA_MAX_ITEMS);
+    for (int e = 0; e < n; ++e) {
+        const genie_lora_item& it = items[e];
+        GENIE_CHECK_ARG(it.rank >= 1 && it.rank <= GENIE_LORA_MAX_RANK, "%s: item %d: rank %d is not in 1 .. %d", where, e, it.rank,
+                        GENIE_LORA_MAX_RANK);
+        GENIE_CHECK_ARG(it.out >= 1, "%s: item %d: out = %d", where, e, it.out);
+        GENIE_CHECK_ARG(it.in >= 16 && it.in % 16 == 0, "%s: item %d: in = %d is not a positive multiple of 16", where, e, it.in);
+        GENIE_CHECK_ARG(std::isfinite(it.scale), "%s: item %d: the scale is not finite", where, e);
+        const size_t nw = (size_t)it.out * it.in, na = (size_t)it.rank * it.in, nb = (size_t)it.out * it.rank;
+        GENIE_CHECK_ARG(it.a && it.b, "%s: item %d: NULL a or b", where, e);
+        if (!project) {
+            GENIE_CHECK_ARG(it.w && it.w0, "%s: item %d: NULL w or w0", where, e);
+            GENIE_CHECK_ARG(((uintptr_t)it.w | (uintptr_t)it.w0 | (uintptr_t)it.a) % 16 == 0, "%s: item %d: w, w0 and a must be 16-byte aligned",
+                            where, e);
+            GENIE_CHECK_ARG(it.w == it.w0 || !lora_overlap(it.w, nw, it.w0, nw), "%s: item %d: w overlaps w0 without being w0", where, e);
+            GENIE_CHECK_ARG(!lora_overlap(it.a, na, it.w, nw) && !lora_overlap(it.b, nb, it.w, nw), "%s: item %d: a or b overlaps the output w",
+                            where, e);
+        } else {
+            GENIE_CHECK_ARG(it.dw && it.da && it.db, "%s: item %d: NULL dw, da or db", where, e);
+            GENIE_CHECK_ARG(((uintptr_t)it.dw | (uintptr_t)it.da) % 16 == 0, "%s: item %d: dw and da must be 16-byte aligned", where, e);
+            GENIE_CHECK_ARG(!lora_overlap(it.a, na, it.da, na) && !lora_overlap(it.a, na, it.db, nb) && !lora_overlap(it.b, nb, it.da, na) &&
+                                !lora_overlap(it.b, nb, it.db, nb),
+                            "%s: item %d: a or b overlaps an output (da, db)", where, e);
+            GENIE_CHECK_ARG(!lora_overlap(it.dw, nw, it.da, na) && !lora_overlap(it.dw, nw, it.db, nb) && !lora_overlap(it.da, na, it.db, nb),
+                            "%s: item %d: dw, da and db overlap", where, e);
+        }
+    }
+    return GENIE_OK;
+}
+
+int genie_lora_merge(const genie_lora_item* items, int n, void* stream) {
+    GENIE_TRY(lora_ok(items, n, false, "genie_lora_merge"));
+    LoraTable tb;
+    size_t floats;
+    GENIE_CHECK_ARG(lora_table(items, n, tb, floats), "genie_lora_merge: the table is beyond 2^31 tiles");
+    return launch_lora_merge(tb, (hipStream_t)stream);
+}
+
+size_t genie_lora_project_scratch_bytes(const genie_lora_item* items, int n) {
+    if (lora_ok(items, n, true, "genie_lora_project_scratch_bytes") != GENIE_OK) return 0;
+    LoraTable tb;
+    size_t floats;
+    if (!lora_table(items, n, tb, floats)) {
+        set_error("genie_lora_project_scratch_bytes: the table is beyond 2^31 tiles");
+        return 0;
+    }
+    return floats * sizeof(float);
+}
+
+int genie_lora_project(const genie_lora_item* items, int n, int accumulate, void* scratch, size_t scratch_bytes, void* stream) {
+    GENIE_TRY(lora_ok(items, n, true, "genie_lora_project"));
+    LoraTable tb;
+    size_t floats;
+    GENIE_CHECK_ARG(lora_table(items, n, tb, floats), "genie_lora_project: the table is beyond 2^31 tiles");
+    GENIE_CHECK_ARG(scratch != nullptr && (uintptr_t)scratch % 16 == 0, "genie_lora_project: NULL or misaligned scratch");
+    GENIE_CHECK_ARG(scratch_bytes >= floats * sizeof(float), "genie_lora_project: scratch of %zu bytes, %zu needed", scratch_bytes,
+                    floats * sizeof(float));
+    for (int e = 0; e < n; ++e) {
+        const genie_lora_item& it = items[e];
+        GENIE_CHECK_ARG(!lora_overlap(scratch, floats, it.dw, (size_t)it.out * it.in) && !lora_overlap(scratch, floats, it.a, (size_t)it.rank * it.in) &&
+                            !lora_overlap(scratch, floats, it.b, (size_t)it.out * it.rank) &&
+                            !lora_overlap(scratch, floats, it.da, (size_t)it.rank * it.in) &&
+                            !lora_overlap(scratch, floats, it.db, (size_t)it.out * it.rank),
+                        "genie_lora_project: item %d: scratch overlaps one of its buffers", e);
+    }
+    tb.scratch = (float*)scratch;
+    return launch_lora_project(tb, accumulate ? 1 : 0, (hipStream_t)stream);
+}
+
 }  // extern "C"

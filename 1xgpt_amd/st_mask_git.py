@@ -789,6 +789,48 @@ class STMaskGIT(nn.Module):
         model.eval()
         return model
 
+    # ------------------------------------------------------------------ LoRA adapters (lora.py; include/genie_hip.h, "LoRA adapters")
+    def load_adapter(self, adapter):
+        """Serve an adapter: every targeted Linear weight becomes W0 + (alpha / rank) B A, merged in place by genie_lora_merge (the kernel
+        the trainer merges with: the logits are the trained model's bits), and the packed copies are rebuilt.  `adapter`: a directory
+        GenieTrainer.save_adapter wrote, or (config dict, {name: tensor}).  The base tensors that were replaced are remembered:
+        `unload_adapter()` puts their bits back; loading a second adapter unloads the first.  ValueError -- the model unchanged -- for an
+        adapter of another base geometry, a target that is no Linear of this model, or a missing, surplus or wrong-shaped tensor."""
+        from . import lora as _lora
+        dev = self._device()
+        cfg, tensors = _lora.load_adapter_files(adapter) if isinstance(adapter, (str, os.PathLike)) else adapter
+        named = dict(self.named_parameters())
+        rank, scale, targets = _lora.check_adapter(cfg, tensors, self.config, {n: tuple(p.shape) for n, p in named.items()})
+        self.unload_adapter()
+        keep = {n: torch.as_tensor(t).to(dev, torch.float32).contiguous() for n, t in tensors.items()}
+        base, items = {}, []
+        for n in targets:
+            w = named[n].data
+            base[n] = w.clone()
+            a, b = _lora.adapter_names(n)
+            items.append(_lora.item(scale, w.shape[0], w.shape[1], rank, keep[a].data_ptr(), keep[b].data_ptr(), w=w.data_ptr(),
+                                    w0=w.data_ptr()))
+        try:
+            _lora.merge(_lib.load(), items, self._stream())
+        except Exception:
+            for n, t in base.items():
+                named[n].data.copy_(t)
+            raise
+        self._adapter_base = base
+        self.refresh_weights()
+        return self
+
+    def unload_adapter(self):
+        """Put back the base weights `load_adapter` replaced (their saved bits) and rebuild the packed copies.  No adapter: nothing happens."""
+        base = getattr(self, "_adapter_base", None)
+        if base:
+            named = dict(self.named_parameters())
+            for n, t in base.items():
+                named[n].data.copy_(t)
+            self.refresh_weights()
+        self._adapter_base = None
+        return self
+
     def load_numpy_state_dict(self, sd: dict):
         """Load {key: ndarray} (e.g. from 1xgpt_amd.synthetic.make_state_dict)."""
         self.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)

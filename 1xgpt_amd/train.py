@@ -37,6 +37,8 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
+from . import lora as _lora
+from .lora import LINEAR_WEIGHTS, LoraConfig, linear_weight_names   # noqa: F401  (public here as well)
 
 
 # ------------------------------------------------------------------ schedules (train.py:468-492)
@@ -147,13 +149,8 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-LINEAR_WEIGHTS = ("spatial_attn.qkv", "spatial_attn.proj", "temporal_attn.qkv", "temporal_attn.proj", "mlp.fc1", "mlp.fc2")
-
-
-def linear_weight_names(config):
-    """The nn.Linear weights that have 16-bit operand copies in the bf16 / f16x3 precisions."""
-    out = [f"decoder.layers.{i}.{n}.weight" for i in range(config.num_layers) for n in LINEAR_WEIGHTS]
-    return out + ["out_x_proj.weight"]
+# (LINEAR_WEIGHTS and linear_weight_names -- the nn.Linear weights that have 16-bit operand copies in the bf16 / f16x3 precisions, and
+# that an adapter may target -- live in lora.py)
 
 
 def weights_table(config, tensors, w16=None):
@@ -381,8 +378,21 @@ class GenieTrainer:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0,
                  gradient_accumulation_steps=1, lr_lambda=None, bucket_mb=64, group=None, recompute=False, dropout_seed=0,
                  ema_decay=None, ema_warmup=False, label_smoothing=0.0, z_loss=0.0, frame_weights=None, trainable=None, lr_scale=None,
-                 teacher=None, distill_alpha=0.0, distill_temperature=1.0):
-        """teacher, distill_alpha, distill_temperature: distillation (include/genie_hip.h, "Distillation"): the loss becomes
+                 teacher=None, distill_alpha=0.0, distill_temperature=1.0, lora=None):
+        """lora: a LoraConfig: train low-rank adapters on the Linears its `targets` select (lora.py; include/genie_hip.h, "LoRA adapters").
+        Each adapted <linear>.weight keeps its base W0 in a trainer-owned f32 buffer (`self.w0`) and gains <linear>.lora_A (rank, in) and
+        <linear>.lora_B (out, rank): not module parameters, but tensors of the flat buffers like any trainable one (ready order inside
+        their layer's group, decaying; AdamW ranges, all-reduce segments, the norm, the clip, the EMA and `lr_scale` patterns cover them by
+        name).  The module's parameter holds W = W0 + (alpha / rank) B A, so the untouched step, `forward`, `generate` and
+        `save_pretrained` (a merged stand-alone checkpoint) see the adapted model in every precision.  The backward writes dW of an
+        adapted Linear into a scratch (one layer's worth, reused by every layer; the readout has its own) and genie_lora_project turns it
+        into dA, dB in `grads` right behind each head / layer call; after an optimizer step or an EMA exchange the weights are merged
+        again and the adapted Linears repacked.  The weight-gradient products of adapted Linears still run: the step is not faster than
+        a full fine-tune, it is smaller (state, all-reduce bytes, what is shipped).  With `lora`, `trainable=None` means "the adapters
+        alone" and `trainable=` names ADDITIONAL fully trained tensors ("action_*"); an adapted weight named by it raises ValueError.  A
+        starts as U(-1/sqrt(in), 1/sqrt(in)) from (seed, name), B as zero: the fresh trainer computes the base model.
+        `adapter_state_dict`, `load_adapter_state_dict`, `save_adapter`.  None: no new buffer and the library calls of before.
+        teacher, distill_alpha, distill_temperature: distillation (include/genie_hip.h, "Distillation"): the loss becomes
         (1 - alpha) * the objective's hard loss + alpha * tau^2 KL(softmax(teacher / tau) || softmax(student / tau)) + the z-loss, still
         inside the fused loss kernel, which reads the teacher's logits beside the student's.  `teacher` is an STMaskGIT on the same
         device, in any precision, depth, width and norm of its own, with the student's T, S and vocabulary, unconditioned or conditioned as
@@ -453,6 +463,15 @@ class GenieTrainer:
         self.last_kd = self.last_teacher_ce = None   # tau^2 KL and the teacher's own CE per counted token, of the last micro-batch
 
         named = dict(model.named_parameters())
+        shapes = {n: tuple(p.shape) for n, p in named.items()}
+        self.lora, self.lora_targets, adapters = lora, [], {}
+        if lora is not None:
+            if not isinstance(lora, LoraConfig):
+                raise TypeError(f"lora must be a LoraConfig, got {type(lora).__name__}")
+            self.lora_targets = _lora.select_targets(self.config, lora.targets)
+            adapters = _lora.adapter_shapes(self.lora_targets, shapes, lora.rank)
+            shapes.update(adapters)
+        self._shapes = shapes
         if trainable is None:
             chosen = None
         elif callable(trainable):
@@ -461,8 +480,13 @@ class GenieTrainer:
                 raise ValueError("no trainable parameter is left: `trainable` accepts no parameter name")
         else:
             chosen = select_trainable(named.keys(), train_only=trainable)
+        if lora is not None:   # the adapters, and what `trainable` names beside them
+            both = sorted(set(chosen or ()) & set(self.lora_targets))
+            if both:
+                raise ValueError(f"{both[:4]} are adapted by `lora` and named by `trainable`: a weight trains fully or through its adapter")
+            chosen = set(chosen or ()) | set(adapters)
         self.lr_scale = dict(lr_scale) if lr_scale else None
-        lay = self.layout = FlatLayout(self.config, {n: p.numel() for n, p in named.items()}, chosen, self.lr_scale)
+        lay = self.layout = FlatLayout(self.config, {n: int(np.prod(s)) for n, s in shapes.items()}, chosen, self.lr_scale)
         self.order, self.offsets, self.n_flat, self.n_train = lay.order, lay.offsets, lay.n_flat, lay.n_train
         self.trainable = [n for n in self.order if n in lay.trainable]   # the prefix, in ready order
         offs = self.offsets
@@ -474,6 +498,10 @@ class GenieTrainer:
         with torch.no_grad():
             for n in self.order:
                 lo, hi = offs[n]
+                if n in adapters:   # B stays zero
+                    if n.endswith(_lora.SUFFIX_A):
+                        self.params[lo:hi].copy_(torch.from_numpy(_lora.draw_a(n, shapes[n], lora.seed)).reshape(-1))
+                    continue
                 view = self.params[lo:hi].view(named[n].shape)
                 view.copy_(named[n].data)
                 named[n].data = view  # the module now reads (and checkpoints) the flat buffer
@@ -487,7 +515,7 @@ class GenieTrainer:
         self.ema_updates, self._in_ema_scope = 0, False
         model.refresh_weights()
         self.p_views = {n: self.params[offs[n][0]:offs[n][1]] for n in self.order}
-        self.g_views = {n: self.grads[offs[n][0]:offs[n][1]].view(named[n].shape) for n in self.trainable}
+        self.g_views = {n: self.grads[offs[n][0]:offs[n][1]].view(shapes[n]) for n in self.trainable}
         # 16-bit operand copies of the Linear weights, both orientations (bf16: 1 plane, f16x3: [hi | lo])
         self.w16 = self.w16T = None
         self.wT_table = None
@@ -497,8 +525,11 @@ class GenieTrainer:
             self.w16 = {n: torch.empty((npl,) + tuple(named[n].shape), dtype=torch.int16, device=dev) for n in lin}
             self.w16T = {n: torch.empty((npl,) + tuple(named[n].shape)[::-1], dtype=torch.int16, device=dev) for n in lin}
             self.wT_table, self._wTk = weights_table(self.config, {}, self.w16T)
-        self.w_table, self._wk = weights_table(self.config, {n: named[n].data for n in self.order}, self.w16)
-        self.g_table, self._gk = weights_table(self.config, self.g_views)   # NULL members: frozen tensors (genie_hip.h, "Frozen tensors")
+        self.w_table, self._wk = weights_table(self.config, {n: named[n].data for n in self.order if n in named}, self.w16)
+        g_entries = self.g_views
+        if lora is not None:   # an adapted weight's gradient-table entry is its dW scratch: the backward computes it, the repack selects it
+            g_entries = dict(self.g_views, **self._lora_setup(named, dev))
+        self.g_table, self._gk = weights_table(self.config, g_entries)   # NULL members: frozen tensors (genie_hip.h, "Frozen tensors")
         self.pack_weights()
         # AdamW ranges: maximal runs of consecutive trainable tensors with the same (decay flag, lr factor)
         self.adam_runs = lay.adam_runs
@@ -517,6 +548,83 @@ class GenieTrainer:
         self._B = 0
         self._d_rows = None   # (1 + B T, d) scratch: d loss / d rows of a model conditioned on action vectors, overwritten per call
 
+    # ------------------------------------------------------------------ LoRA adapters
+    def _lora_setup(self, named, dev):
+        """The base weights, the dW scratch and the item tables.  Returns {adapted weight name: its dW scratch view}."""
+        lc, shapes = self.lora, self._shapes
+        self.w0 = {n: named[n].data.clone() for n in self.lora_targets}   # after the rank-0 broadcast; B = 0: the parameters ARE W0
+        # one layer's worth of dW, shared by every layer (a layer's backward is projected before the next one runs); the head's own
+        short = lambda n: n.split(".", 3)[3] if n.startswith("decoder.layers.") else n   # noqa: E731
+        dw = {}
+        for n in self.lora_targets:
+            if short(n) not in dw:
+                dw[short(n)] = torch.zeros(shapes[n], dtype=torch.float32, device=dev)
+        self._lora_dw = dw
+        self._lora_items, self._lora_dw_of, merge_items = {}, {}, []   # group key ("head" or a layer index) -> [LoraItem], [dW scratch]
+        for n in self.lora_targets:
+            (o, i), (na, nb) = shapes[n], _lora.adapter_names(n)
+            it = _lora.item(lc.scale, o, i, lc.rank, self.p_views[na].data_ptr(), self.p_views[nb].data_ptr(), w=named[n].data.data_ptr(),
+                            w0=self.w0[n].data_ptr(), dw=dw[short(n)].data_ptr(), da=self.g_views[na].data_ptr(),
+                            db=self.g_views[nb].data_ptr())
+            key = _layer_of(n)
+            key = "head" if key is None else key
+            self._lora_items.setdefault(key, []).append(it)
+            self._lora_dw_of.setdefault(key, []).append(dw[short(n)])
+            merge_items.append(it)
+        self._lora_merge_items = merge_items
+        self._lora_tables = {k: _lora.table(v) for k, v in self._lora_items.items()}
+        need = max(self.lib.genie_lora_project_scratch_bytes(arr, n) for arr, n in self._lora_tables.values())
+        if need == 0:
+            _lib.check(_lib.E_ARG, "genie_lora_project_scratch_bytes")
+        self._lora_scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        return {n: dw[short(n)] for n in self.lora_targets}
+
+    def _lora_merge(self):
+        """W = W0 + s B A into the module's parameters, from whatever the flat buffer holds for A and B now."""
+        _lora.merge(self.lib, self._lora_merge_items, self._stream())
+
+    def _lora_zero_dw(self, key):
+        """accumulate: the backward's flag applies to every gradient of the call, dW included -- the reused scratch starts from zero."""
+        for t in self._lora_dw_of.get(key, ()):
+            t.zero_()
+
+    def _lora_project(self, key, acc_flag):
+        """dW scratch of group `key` -> dA, dB in the flat gradient buffer (added when acc_flag)."""
+        if key in self._lora_tables:
+            arr, n = self._lora_tables[key]
+            _lib.check(self.lib.genie_lora_project(arr, n, acc_flag, self._lora_scratch.data_ptr(), self._lora_scratch.numel(),
+                                                   self._stream()), "genie_lora_project")
+
+    def adapter_state_dict(self):
+        """{<linear>.lora_A / .lora_B: clone} of the adapters (inside ema_scope(): of their averages)."""
+        self._need_lora("adapter_state_dict")
+        return {n: self.p_views[n].view(self._shapes[n]).clone() for t in self.lora_targets for n in _lora.adapter_names(t)}
+
+    def load_adapter_state_dict(self, sd):
+        """Inverse of `adapter_state_dict`: copies the tensors (names and shapes must match exactly: ValueError), merges and repacks."""
+        self._need_lora("load_adapter_state_dict")
+        self._not_in_ema_scope("load_adapter_state_dict")
+        want = {n: self._shapes[n] for t in self.lora_targets for n in _lora.adapter_names(t)}
+        if set(sd) != set(want):
+            raise ValueError(f"adapter tensors do not match this trainer's: missing {sorted(set(want) - set(sd))[:4]}, unexpected "
+                             f"{sorted(set(sd) - set(want))[:4]}")
+        for n, shp in want.items():
+            if tuple(sd[n].shape) != shp:
+                raise ValueError(f"adapter tensor {n} has shape {tuple(sd[n].shape)}, expected {shp}")
+        for n in want:
+            self.p_views[n].copy_(torch.as_tensor(sd[n]).to(self.params.device, torch.float32).reshape(-1))
+        self._pack_trained()
+        self.model.refresh_weights()
+
+    def save_adapter(self, save_directory):
+        """adapter_config.json (rank, alpha, target names, the base's shape fields) + adapter.safetensors: what STMaskGIT.load_adapter takes."""
+        self._need_lora("save_adapter")
+        _lora.save_adapter(save_directory, _lora.adapter_config(self.lora, self.lora_targets, self.config), self.adapter_state_dict())
+
+    def _need_lora(self, what):
+        if self.lora is None:
+            raise RuntimeError(f"GenieTrainer.{what} needs a trainer built with lora=")
+
     def pack_weights(self):
         """Refresh the 16-bit weight copies from the f32 parameters (no-op in the exact precision).  Call this (or
         `sync_external_weights`) after ANY weight mutation the trainer did not make itself -- `model.load_state_dict`,
@@ -528,6 +636,8 @@ class GenieTrainer:
     def _pack_trained(self):
         """pack_weights after a change the trainer made itself (optimizer step, EMA exchange): those move the trainable prefix alone,
         so only the trainable Linears are repacked -- the gradient table says which."""
+        if self.lora is not None:   # the adapters moved: the effective weights follow, and the gradient table selects them below
+            self._lora_merge()
         if self.layout.all:
             return self.pack_weights()
         if self.precision != "exact":
@@ -654,17 +764,25 @@ class GenieTrainer:
                        "genie_train_forward_obj")
         sums = self.sums.clone()
         self.reducer.reset()
+        if self.lora is not None and accumulate:
+            self._lora_zero_dw("head")
         _lib.check(_lib.call_recompute(lib, "genie_train_backward_head", self.recompute, cfg, self.w_table, self.wT_table,
                                        self.g_table, B, acts.data_ptr(), ws.data_ptr(), ws.numel(), acc_flag, st),
                    "genie_train_backward_head")
+        if self.lora is not None:
+            self._lora_project("head", acc_flag)
         ready = self._group_hi.get   # None: the group holds no trainable tensor, nothing of it is exchanged
         if reduce and ready("head") is not None:
             self.reducer.ready(ready("head"))
         L = self.config.num_layers
         for layer in reversed(range(self.layout.stop, L)):   # below `stop` nothing trains: no backward, no recomputation
+            if self.lora is not None and accumulate:
+                self._lora_zero_dw(layer)
             _lib.check(_lib.call_drop(lib, "genie_train_backward_layer", self.recompute, drop, cfg, self.w_table, self.wT_table,
                                       self.g_table, layer, B, acts.data_ptr(), ws.data_ptr(), ws.numel(), acc_flag, st),
                        "genie_train_backward_layer")
+            if self.lora is not None:
+                self._lora_project(layer, acc_flag)
             if reduce and ready(layer) is not None:
                 self.reducer.ready(ready(layer))
         g = self.g_views.get
@@ -814,10 +932,12 @@ class GenieTrainer:
         """{state-dict name: clone of the averaged weights} in the parameters' shapes, for every tensor: a frozen tensor's average is
         the tensor itself."""
         self._need_ema("ema_state_dict")
+        if self.lora is not None and not self._in_ema_scope:   # an adapted weight's average is merge(W0, averaged adapters): made by the scope
+            with self.ema_scope():
+                return self.ema_state_dict()
         avg = self.params if self._in_ema_scope else self.ema   # inside the scope the two buffers have changed places
-        named = dict(self.model.named_parameters())
         src = lambda n: avg if n in self.g_views else self.params   # noqa: E731
-        return {n: src(n)[self.offsets[n][0]:self.offsets[n][1]].view(named[n].shape).clone() for n in self.order}
+        return {n: src(n)[self.offsets[n][0]:self.offsets[n][1]].view(self._shapes[n]).clone() for n in self.order}
 
     def save_ema_pretrained(self, save_directory):
         """`model.save_pretrained(save_directory)` with the averaged weights: STMaskGIT.from_pretrained loads it as an ordinary checkpoint."""
@@ -833,12 +953,11 @@ class GenieTrainer:
         """Optimizer state in torch.optim.AdamW's vocabulary, keyed by parameter NAME (the model's own weights are
         saved by `model.save_pretrained` / `state_dict`)."""
         self._not_in_ema_scope("state_dict")
-        named = dict(self.model.named_parameters())
         st = {}
         for n in self.trainable:   # a frozen tensor has no moments
             lo, hi = self.offsets[n]
-            st[n] = {"exp_avg": self.exp_avg[lo:hi].view(named[n].shape).clone(),
-                     "exp_avg_sq": self.exp_avg_sq[lo:hi].view(named[n].shape).clone()}
+            st[n] = {"exp_avg": self.exp_avg[lo:hi].view(self._shapes[n]).clone(),
+                     "exp_avg_sq": self.exp_avg_sq[lo:hi].view(self._shapes[n]).clone()}
         out = {"state": st, "completed_steps": self.completed_steps, "micro_step": self._micro,
                "trainable": sorted(self.trainable),
                "dropout": {"seed": self.dropout_seed, "call": self._drop_call},
@@ -850,8 +969,8 @@ class GenieTrainer:
         if self._distilling:   # (a trainer that does not distil keeps the state of before, key for key)
             out["hyper"].update(distill_alpha=self.distill_alpha, distill_temperature=self.distill_temperature)
         if self.ema is not None:
-            avg = self.ema_state_dict()
-            out["ema"] = {"state": {n: avg[n] for n in self.trainable}, "updates": self.ema_updates, "decay": self.ema_decay,
+            avg = {n: self.ema[self.offsets[n][0]:self.offsets[n][1]].view(self._shapes[n]).clone() for n in self.trainable}
+            out["ema"] = {"state": avg, "updates": self.ema_updates, "decay": self.ema_decay,
                           "warmup": self.ema_warmup}
         return out
 

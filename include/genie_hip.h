@@ -1058,6 +1058,46 @@ int genie_swap_f32(float* a, float* b, size_t n, void* stream);
 int genie_train_pack_weights_some(const genie_cfg* cfg, const genie_weights* w, const genie_weights* w16,
                                   const genie_weights* w16T, const genie_weights* select, void* stream);
 
+/* LoRA adapters (additions; nothing above changes).  Hu et al. 2021; reference counterpart: none.  An adapted Linear (out, in) keeps its
+ * base weight W0 and trains A (rank, in) and B (out, rank), row-major f32, with s = alpha / rank the caller's float:
+ *     W = W0 + s B A                                                  (genie_lora_merge)
+ * Every entry point above runs on W and is untouched; the step's weight gradient dW = d loss / d W is then projected onto the adapters,
+ *     dA = s B^T dW        dB = s dW A^T                              (genie_lora_project)
+ * which by the chain rule are the gradients of the adapters.  The weight-gradient product of an adapted Linear still runs.
+ * Arithmetic, f32: an element of W is fma(s, sum_k b[i,k] a[k,j], w0[i,j]) with the sum built by one fma per k, ascending from 0.0f.
+ * An element of dA is a sum over the `out` rows: within each run of 64 rows one fma per row, ascending; the ceil(out / 64) run sums
+ * ("slabs", in `scratch`) are then added in four interleaved chains t = 0, 4, .. / 1, 5, .. / 2, 6, .. / 3, 7, .. combined as
+ * (c0 + c1) + (c2 + c3), and the result is fma(s, sum, accumulate ? old : 0.0f).  dB likewise over runs of 64 of the `in` columns.
+ * No atomics and no dependence on what scratch held: the same bytes run to run.  dw is read from memory once for both results.
+ * One call serves 1 .. GENIE_LORA_MAX_ITEMS Linears of any mix of shapes in ONE launch (project: one more for the slab sums); the table
+ * is read on the host during the call and travels to the kernels by value.  Per item: out >= 1; in >= 16 and a multiple of 16;
+ * 1 <= rank <= GENIE_LORA_MAX_RANK; w, w0, a, dw and da 16-byte aligned.  genie_lora_merge reads w0, a, b and writes w, which may BE w0
+ * (the in-place merge; any other overlap of the two is refused); dw, da, db are ignored.  genie_lora_project reads dw, a, b and writes
+ * da and db (accumulate = 1: adds to them); w and w0 are ignored.
+ * Every function validates all items before the device or the stream is touched and never allocates.  Refused with GENIE_E_ARG, every
+ * buffer as it was: a NULL table or a NULL pointer the call uses; n outside 1 .. GENIE_LORA_MAX_ITEMS; out < 1; rank outside
+ * 1 .. GENIE_LORA_MAX_RANK; in not a positive multiple of 16; a scale that is not finite; a misaligned pointer; a or b overlapping an
+ * output of its item (w; da, db), or dw overlapping da or db; a NULL scratch or fewer scratch_bytes than
+ * genie_lora_project_scratch_bytes(items, n), which returns 0 for a table it refuses. */
+#define GENIE_LORA_MAX_ITEMS 8
+#define GENIE_LORA_MAX_RANK 64
+typedef struct genie_lora_item {
+    float* w;          /* merge: (out, in) result; may be w0 */
+    const float* w0;   /* merge: (out, in) base weight */
+    const float* a;    /* (rank, in) */
+    const float* b;    /* (out, rank) */
+    const float* dw;   /* project: (out, in) d loss / d W */
+    float* da;         /* project: (rank, in) */
+    float* db;         /* project: (out, rank) */
+    int32_t out, in, rank;
+    float scale;       /* s = alpha / rank */
+} genie_lora_item;
+/* sizeof(genie_lora_item) and the offsets of its eleven fields, in declaration order: writes min(n, 12) entries, returns 12. */
+int genie_lora_layout(size_t* out_host, int n);
+int genie_lora_merge(const genie_lora_item* items, int n, void* stream);
+size_t genie_lora_project_scratch_bytes(const genie_lora_item* items, int n);
+int genie_lora_project(const genie_lora_item* items, int n, int accumulate, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Continuous per-frame actions (ABI 3 addition; nothing above changes).  A model conditioned on float action vectors of A values per
  * frame projects them, once per call, into the rows that genie_frame_cond addresses: the caller builds a table of one learned "no
  * action" row plus one projected row per frame of the call, points cond->table at it and cond->ids at "row of frame (b, t)", and every

@@ -53,6 +53,8 @@ def main():
     ap.add_argument("--train_only", type=str, default=None, metavar="P[,P...]",
                     help="train only the tensors matching these fnmatch patterns over state-dict names (GenieTrainer(trainable=...))")
     ap.add_argument("--freeze", type=str, default=None, metavar="P[,P...]", help="freeze the tensors matching these patterns")
+    ap.add_argument("--lora_rank", type=int, default=0, help="train adapters of this rank instead of the weights (GenieTrainer(lora=LoraConfig(...)))")
+    ap.add_argument("--lora_targets", type=str, default="decoder.layers.*", metavar="P[,P...]", help="with --lora_rank: the adapted Linears")
     ap.add_argument("--teacher", default=None, choices=["c35", "c138"],
                     help="distil from a teacher of this shape (synthetic weights; GenieTrainer(teacher=...)): its forward runs in every step")
     ap.add_argument("--teacher_precision", default=None, choices=["exact", "f16x3", "bf16"], help="the teacher's precision (default: --precision)")
@@ -87,7 +89,14 @@ def main():
     tr = pkg("train").GenieTrainer(model, lr=1e-4, max_grad_norm=1.0, recompute=a.recompute, ema_decay=a.ema_decay,
                                    label_smoothing=a.label_smoothing, z_loss=a.z_loss, frame_weights=fw, trainable=trainable,
                                    teacher=teacher, distill_alpha=a.distill_alpha if teacher is not None else 0.0,
-                                   distill_temperature=a.distill_temperature)
+                                   distill_temperature=a.distill_temperature,
+                                   lora=pkg("train").LoraConfig(rank=a.lora_rank, alpha=2.0 * a.lora_rank, targets=a.lora_targets) if a.lora_rank else None)
+    if a.lora_rank:   # B = 0 would make dA exactly zero: time the step on adapters that have moved
+        sd = tr.adapter_state_dict()
+        g = torch.Generator(device="cuda").manual_seed(3)
+        tr.load_adapter_state_dict({n: (t if n.endswith(".lora_A") else 0.02 * torch.randn(t.shape, generator=g, device="cuda")) for n, t in sd.items()})
+        print(f"lora rank {a.lora_rank}: {len(tr.lora_targets)} adapted Linears, {tr.n_train} trainable elements of {tr.n_flat} flat; "
+              f"optimizer state {8 * tr.n_train} bytes, all-reduce {4 * tr.n_train} bytes, {len(tr.adam_runs)} AdamW launches")
     lib = _lib.load()
     if a.ema_unfused:
         if a.ema_decay is None:

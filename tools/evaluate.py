@@ -22,6 +22,8 @@ def build_parser():
     ap = argparse.ArgumentParser(description="Evaluate GENIE-style models (MI355X path).")
     ap.add_argument("--val_data_dir", type=str, default="data/val_v1.1")
     ap.add_argument("--checkpoint_dir", type=str)
+    ap.add_argument("--adapter", type=str, default=None, metavar="DIR",
+                    help="serve this adapter (a directory GenieTrainer.save_adapter / tools/train.py --lora_rank wrote) merged into the checkpoint's weights")
     ap.add_argument("--batch_size", type=int, default=16)
     ap.add_argument("--maskgit_steps", type=int, default=2)
     ap.add_argument("--temperature", type=float, default=0,
@@ -69,6 +71,12 @@ def main():
     args.latent_h = args.latent_w = side
     lo, hi = dist_mod.shard_range(clips.shape[0], rank, world)
     ev = ev_mod.GenieEvaluator(args, None, dev, model=model)
+    if args.adapter:
+        try:
+            ev.model.load_adapter(args.adapter)
+        except (ValueError, FileNotFoundError) as e:
+            sys.exit(f"evaluate.py: --adapter {args.adapter}: {e}")
+        print(f"adapter {args.adapter} merged", flush=True)
     res = ev_mod.evaluate_clips(ev, clips[lo:hi], batch_size=args.batch_size, distributed=world > 1,
                                 reuse=not args.no_reuse, action_ids=None if actions is None else actions[lo:hi])
     if rank == 0:

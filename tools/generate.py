@@ -26,6 +26,8 @@ def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--val_data_dir", type=str, default="data/val_v1.1")
     ap.add_argument("--checkpoint_dir", type=str)
+    ap.add_argument("--adapter", type=str, default=None, metavar="DIR",
+                    help="serve this adapter (a directory GenieTrainer.save_adapter / tools/train.py --lora_rank wrote) merged into the checkpoint's weights")
     ap.add_argument("--output_dir", type=str, default="data/genie_generated")
     ap.add_argument("--num_prompt_frames", type=int, default=8)
     ap.add_argument("--window_size", type=int, default=16)
@@ -129,6 +131,11 @@ def main():
                 sys.exit(f"generate.py: the model is action-conditioned but {args.val_data_dir} has no actions.bin")
             actions = item["action_ids"][None]
     model = model.to("cuda")
+    if args.adapter:
+        try:
+            model.load_adapter(args.adapter)
+        except (ValueError, FileNotFoundError) as e:
+            sys.exit(f"generate.py: --adapter {args.adapter}: {e}")
     ex = example.to("cuda").view(1, args.window_size, model.h, model.w)
     if args.score:
         return score_main(args, model, ex, actions, G)

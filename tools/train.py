@@ -112,6 +112,14 @@ def parse_args():
                    help="freeze the tensors matching these patterns (applied after --train_only)")
     p.add_argument("--lr_scale", type=str, default=None, metavar="P=F[,P=F...]",
                    help="learning-rate factors by pattern, first match wins (e.g. 'action_*=10'): lr * F for the tensors matching P")
+    p.add_argument("--lora_rank", type=int, default=0,
+                   help="train low-rank adapters of this rank (1 .. 64) on the Linears --lora_targets selects instead of the weights: "
+                        "the adapters alone train (plus what --train_only names), checkpoints gain an adapter/ directory "
+                        "(adapter_config.json + adapter.safetensors) beside the merged weights; resuming needs the base model as "
+                        "--warmstart_path")
+    p.add_argument("--lora_alpha", type=float, default=None, help="the adapters' scale is alpha / rank (default: 2 * rank)")
+    p.add_argument("--lora_targets", type=str, default="decoder.layers.*", metavar="P[,P...]",
+                   help="fnmatch patterns over the Linear weight names (six per layer and out_x_proj.weight)")
     p.add_argument("--null_action", type=int, default=None, help="row of the action table that stands for 'no action'")
     p.add_argument("--synthetic", type=int, default=0, help="train on N synthetic clips (no dataset on disk)")
     p.add_argument("--model", choices=["c138", "c35", "tiny"], default="c35", help="shape when no --genie_config is given")
@@ -140,6 +148,18 @@ def main():
         sys.exit(f"train.py: --distill_alpha / --distill_temperature: {e}")
     if args.distill_alpha > 0 and not args.teacher_path:
         sys.exit(f"train.py: --distill_alpha {args.distill_alpha} needs --teacher_path")
+    lora = None
+    if args.lora_rank:
+        try:
+            lora = importlib.import_module("1xgpt_amd.train").LoraConfig(
+                rank=args.lora_rank, alpha=2.0 * args.lora_rank if args.lora_alpha is None else args.lora_alpha,
+                targets=args.lora_targets, seed=args.seed or 0)
+        except ValueError as e:
+            sys.exit(f"train.py: --lora_rank / --lora_alpha / --lora_targets: {e}")
+        if args.freeze:
+            sys.exit("train.py: --freeze has no meaning with --lora_rank (the adapters train, and what --train_only names)")
+        if args.resume_from_checkpoint and not args.warmstart_path:
+            sys.exit("train.py: resuming an adapter run needs the base model as --warmstart_path (the checkpoint holds merged weights)")
     if args.mu_transfer:
         raise NotImplementedError("--mu_transfer needs the un-vendored mup fork (MuAdamW, set_base_shapes): not built")
     P = lambda n: importlib.import_module("1xgpt_amd." + n)  # noqa: E731
@@ -207,9 +227,10 @@ def main():
 
     if frame_weights is not None and len(frame_weights) != cfg.T:
         sys.exit(f"train.py: --frame_loss_weights has {len(frame_weights)} entries, the window has {cfg.T} frames")
-    load_from = args.resume_from_checkpoint or args.warmstart_path
-    warm_actions = cfg.action_vocab_size if (args.warmstart_path and not args.resume_from_checkpoint) else None
-    warm_dim = cfg.action_dim if (args.warmstart_path and not args.resume_from_checkpoint) else None
+    # (an adapter run resumes on the base model: the adapters and the optimizer state come from the checkpoint further down)
+    load_from = args.warmstart_path if lora is not None else (args.resume_from_checkpoint or args.warmstart_path)
+    warm_actions = cfg.action_vocab_size if (args.warmstart_path and (lora is not None or not args.resume_from_checkpoint)) else None
+    warm_dim = cfg.action_dim if (args.warmstart_path and (lora is not None or not args.resume_from_checkpoint)) else None
     model = (STMaskGIT.from_pretrained(load_from, precision=args.precision, action_vocab_size=warm_actions or None,
                                        action_dim=warm_dim or None) if load_from
              else STMaskGIT(cfg, precision=args.precision))
@@ -268,13 +289,16 @@ def main():
                                dropout_seed=args.dropout_seed, ema_decay=args.ema_decay, ema_warmup=args.ema_warmup,
                                label_smoothing=args.label_smoothing, z_loss=args.z_loss, frame_weights=frame_weights,
                                trainable=trainable, lr_scale=lr_scale, teacher=teacher, distill_alpha=args.distill_alpha,
-                               distill_temperature=args.distill_temperature)
+                               distill_temperature=args.distill_temperature, lora=lora)
+    if args.resume_from_checkpoint and lora is not None:
+        _, tensors = importlib.import_module("1xgpt_amd.lora").load_adapter_files(os.path.join(args.resume_from_checkpoint, "adapter"))
+        tr.load_adapter_state_dict(tensors)
     if args.resume_from_checkpoint:  # optimizer moments, step counters (train.py:560-590), the EMA of the weights
         tr.load_state_dict(torch.load(os.path.join(args.resume_from_checkpoint, "trainer_state.pt"), map_location=dev))
     n_params = sum(p.numel() for p in model.parameters())
     if rank == 0:
         os.makedirs(args.output_dir, exist_ok=True)
-        if trainable is not None:
+        if trainable is not None or lora is not None:
             print(f"training {len(tr.trainable)} of {len(tr.order)} tensors ({tr.n_train / 1e6:.2f} M of {tr.n_flat / 1e6:.1f} M flat "
                   f"elements); the backward stops at layer {tr.layout.stop}", flush=True)
         print(f"params {n_params / 1e6:.1f} M, {n_train} train windows, batch {B} x {accum} x {world}, "
@@ -337,6 +361,8 @@ def main():
                 ck = os.path.join(args.output_dir, "final_checkpt" if completed == max_steps else f"step_{completed}")
                 model.save_pretrained(ck)
                 torch.save(tr.state_dict(), os.path.join(ck, "trainer_state.pt"))
+                if lora is not None:
+                    tr.save_adapter(os.path.join(ck, "adapter"))
                 if args.ema_decay is not None:   # the averaged weights as a checkpoint of their own (a swap local to this rank)
                     tr.save_ema_pretrained(os.path.join(ck, "ema"))
             if completed >= max_steps:
