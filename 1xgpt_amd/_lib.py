@@ -60,6 +60,12 @@ class Guidance(C.Structure):
     _fields_ = [("scale", C.c_float), ("null_action", C.c_int32)]
 
 
+class Known(C.Structure):
+    """genie_known: the known tokens of the frames a generate call decodes (device pointer, clip stride in elements); a value outside
+    [0, image_vocab_size) marks a token to generate (1xgpt_amd/generate.py: known_tokens)."""
+    _fields_ = [("ids", c_ptr), ("clip_stride", C.c_int64)]
+
+
 class ActionProj(C.Structure):
     """genie_action_proj: the projection of continuous per-frame action vectors (weight (d, A), bias, input mean and 1/std; device pointers)."""
     _fields_ = [("weight", c_ptr), ("bias", c_ptr), ("mean", c_ptr), ("inv_std", c_ptr), ("action_dim", C.c_int32)]
@@ -269,6 +275,19 @@ SIGNATURES["genie_score_workspace_bytes"] = (C.c_size_t, [C.POINTER(GenieCfg), C
 SIGNATURES["genie_score_fanout"] = (C.c_int, [C.POINTER(GenieCfg), C.POINTER(Weights), c_ptr] + [C.c_int] * 5 + [c_ptr, c_ptr, c_ptr, c_ptr,
                                               C.c_size_t, c_ptr, C.c_size_t, c_ptr, C.c_size_t, c_ptr, C.POINTER(FrameCond)])
 
+# known tokens: the start state of a frame, (known, known_clip_stride, mask_id, frame, frame_clip_stride, unmasked, B, S, copies, stream);
+# genie_mask_step with a double `frac` for n and (known, known_clip_stride) behind mask_id; the four loops: the arguments of the widest
+# existing variant + a trailing genie_known* (NULL = that variant)
+SIGNATURES["genie_known_layout"] = (C.c_int, [C.POINTER(C.c_size_t), C.c_int])
+SIGNATURES["genie_mask_fraction"] = (C.c_double, [C.c_int, C.c_int])
+SIGNATURES["genie_known_begin"] = (C.c_int, [c_ptr, C.c_int64, C.c_int64, c_ptr, C.c_int64, c_ptr, C.c_int, C.c_int, C.c_int, c_ptr])
+SIGNATURES["genie_mask_step_known"] = (C.c_int, [c_ptr, C.c_double, C.c_int, C.c_int64, c_ptr, C.c_int64, c_ptr, c_ptr, c_ptr, C.c_int64, C.c_int,
+                                                 C.c_int, c_ptr])
+for _n, _w in (("genie_maskgit_generate", "genie_maskgit_generate_guided"), ("genie_generate_cached", "genie_generate_cached_guided"),
+               ("genie_rollout_cached", "genie_rollout_cached"), ("genie_generate_fanout", "genie_generate_fanout")):
+    SIGNATURES[_n + "_known"] = (C.c_int, SIGNATURES[_w][1] + [C.POINTER(Known)])
+del _n, _w
+
 # MLP dropout in the training step: the mask law alone, (dr, layer, site, n, keep, stream), and the *_ex arguments + a trailing
 # genie_dropout* (NULL or p = 0: the *_ex entry point)
 SIGNATURES["genie_dropout_layout"] = (C.c_int, [C.POINTER(C.c_size_t), C.c_int])
@@ -352,6 +371,9 @@ def load():
         mine = [C.sizeof(Guidance)] + [getattr(Guidance, n).offset for n, _ in Guidance._fields_]
         if lib.genie_guidance_layout(lay, 3) != 3 or list(lay)[:3] != mine:
             raise RuntimeError(f"genie_guidance layout {list(lay)[:3]} != the ctypes declaration {mine}")
+        mine = [C.sizeof(Known)] + [getattr(Known, n).offset for n, _ in Known._fields_]
+        if "genie_known_layout" not in missing and (lib.genie_known_layout(lay, 3) != 3 or list(lay)[:3] != mine):
+            raise RuntimeError(f"genie_known layout {list(lay)[:3]} != the ctypes declaration {mine}")
         mine = [C.sizeof(Dropout)] + [getattr(Dropout, n).offset for n, _ in Dropout._fields_]
         if "genie_dropout_layout" not in missing and (lib.genie_dropout_layout(lay, 4) != 4 or list(lay)[:4] != mine):
             raise RuntimeError(f"genie_dropout layout {list(lay)[:4]} != the ctypes declaration {mine}")
@@ -420,6 +442,28 @@ def call_guided(lib, name, cond, sampling, guidance, *args):
     if guidance is None:
         return call_ex(lib, name, cond, sampling, *args)
     return getattr(lib, name + "_guided")(*args, cond, sampling, guidance)
+
+
+def call_known(lib, name, cond, sampling, guidance, known, *args):
+    """call_guided when `known` is None (the entry points of before, unchanged), else lib.<name>_known(*args, cond, sampling, guidance,
+    known).  For genie_rollout_cached and genie_generate_fanout, whose one entry point already takes all three, use call_known3."""
+    if known is None:
+        return call_guided(lib, name, cond, sampling, guidance, *args)
+    return getattr(lib, name + "_known")(*args, cond, sampling, guidance, known)
+
+
+def call_known3(lib, name, known, *args):
+    """lib.<name>(*args) when `known` is None (unchanged), else lib.<name>_known(*args, known): genie_rollout_cached, genie_generate_fanout."""
+    if known is None:
+        return getattr(lib, name)(*args)
+    return getattr(lib, name + "_known")(*args, known)
+
+
+def make_known(known, frames, S):
+    """The genie_known of a contiguous int64 device tensor whose trailing dimensions are (frames, S)-many elements per clip; None -> None."""
+    if known is None:
+        return None
+    return Known(known.data_ptr(), int(frames) * int(S))
 
 
 def make_cfg(config, precision=PREC_EXACT) -> GenieCfg:

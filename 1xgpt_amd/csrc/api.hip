@@ -130,10 +130,14 @@ int decoder(const genie_cfg& c, const genie_weights& wt, float* x, Workspace& w,
                       [&](int, const genie_layer_weights* next) { return BlockPass::plain(c, next, c.T); });
 }
 
+double mask_fraction(int step, int steps) {
+    double u = (double)(step + 1) / (double)steps;
+    return cos(u * M_PI / 2.0);
+}
+
 int mask_count(int step, int steps, int S) {
     // n = ceil(cos(pi/2 * (step+1)/steps) * S), python float math (st_mask_git.py:17-26,199)
-    double u = (double)(step + 1) / (double)steps;
-    return (int)ceil(cos(u * M_PI / 2.0) * (double)S);
+    return (int)ceil(mask_fraction(step, steps) * (double)S);
 }
 
 // a genie_sampling law (NULL = none), checked on the host before anything is enqueued
@@ -197,6 +201,11 @@ int genie_sampling_layout(size_t* out_host, int n) {
 }
 int genie_guidance_layout(size_t* out_host, int n) {
     const size_t v[3] = {sizeof(genie_guidance), offsetof(genie_guidance, scale), offsetof(genie_guidance, null_action)};
+    for (int i = 0; i < n && i < 3 && out_host; ++i) out_host[i] = v[i];
+    return 3;
+}
+int genie_known_layout(size_t* out_host, int n) {
+    const size_t v[3] = {sizeof(genie_known), offsetof(genie_known, ids), offsetof(genie_known, clip_stride)};
     for (int i = 0; i < n && i < 3 && out_host; ++i) out_host[i] = v[i];
     return 3;
 }
@@ -673,6 +682,26 @@ int genie_mask_step(const float* keys, int n, int last_step, int64_t mask_id, ui
     GENIE_CHECK_ARG(last_step || (n >= 0 && n <= S), "mask_step: n=%d out of range", n);
     return launch_mask_step(keys, n, last_step, mask_id, unmasked, samples, prompt_frame, (long)prompt_clip_stride, B,
                             S, as_stream(stream));
+}
+
+double genie_mask_fraction(int step, int steps) { return steps >= 1 ? mask_fraction(step, steps) : 0.0; }
+
+int genie_known_begin(const int64_t* known, int64_t known_clip_stride, int64_t mask_id, int64_t* frame, int64_t frame_clip_stride,
+                      uint8_t* unmasked, int B, int S, int copies, void* stream) {
+    GENIE_CHECK_ARG(known && frame && B >= 1 && S >= 1 && (copies == 1 || copies == 2), "known_begin: bad argument");
+    GENIE_CHECK_ARG(B <= 0x3fffffff, "known_begin: B=%d too large", B);
+    return launch_known_begin(known, (long)known_clip_stride, mask_id, frame, (long)frame_clip_stride, unmasked, B, S, copies,
+                              as_stream(stream));
+}
+
+int genie_mask_step_known(const float* keys, double frac, int last_step, int64_t mask_id, const int64_t* known, int64_t known_clip_stride,
+                          uint8_t* unmasked, int64_t* samples, int64_t* prompt_frame, int64_t prompt_clip_stride, int B, int S,
+                          void* stream) {
+    GENIE_CHECK_ARG(unmasked && samples && prompt_frame && B >= 1 && S >= 1, "mask_step_known: bad argument");
+    GENIE_CHECK_ARG(last_step || keys, "mask_step_known: keys required unless last_step");
+    GENIE_CHECK_ARG(last_step || (frac >= 0.0 && frac <= 1.0), "mask_step_known: frac=%g outside [0, 1]", frac);
+    return launch_mask_step_known(keys, frac, last_step, mask_id, known, (long)known_clip_stride, unmasked, samples, prompt_frame,
+                                  (long)prompt_clip_stride, B, S, as_stream(stream));
 }
 
 int genie_profile_enable(int class_mask) {

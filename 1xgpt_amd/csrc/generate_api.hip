@@ -2,7 +2,9 @@
 // the full-forward MaskGIT loop.  Each is a sequence of passes (api.hip: frames_pass, the clean pass, the full forward) with token-id,
 // sample and mask-step launches between them; everything is enqueued on the caller's stream, nothing allocates or synchronises.
 // What a pass needs is a PassCtx, the checked decode options of a call a Decode; the MaskGIT step (maskgit_step), the commit rule
-// (commit_slot) and the fan-out prologue (fanout_prologue) are each stated once.
+// (commit_slot) and the fan-out prologue (fanout_prologue) are each stated once.  Known tokens (genie_known: inpainting) ride in the
+// Decode: where they are set a slot starts from them (launch_known_begin) and the mask step counts per clip (launch_mask_step_known);
+// where they are not, every loop enqueues the launches it always did.
 #include <stddef.h>
 
 #include "common.hpp"
@@ -170,10 +172,21 @@ struct Decode {
     const genie_guidance* guidance;
     bool guided;                 // guidance of a scale other than 1: every pass runs [conditional ; null], copies = 2
     int copies;
+    const int64_t* known;        // known tokens of the call's first decoded frame (clip stride known_stride), or NULL: all-mask starts
+    long known_stride;
 };
+// a genie_known (NULL = none) over `frames` decoded frames of S tokens, checked on the host before anything is enqueued
+static int check_known(const genie_known* known, long frames, int S, const char* where) {
+    if (!known) return GENIE_OK;
+    GENIE_CHECK_ARG(known->ids, "%s: known: ids is NULL", where);
+    GENIE_CHECK_ARG(known->clip_stride >= frames * S, "%s: known: clip_stride %lld is below %ld frames x S=%d", where,
+                    (long long)known->clip_stride, frames, S);
+    return GENIE_OK;
+}
 // ... checked on the host before anything is enqueued; where: the entry point's name in the messages
 static int make_decode(Decode& D, int B, int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
-                       const genie_sampling* sampling, const genie_guidance* guidance, const genie_frame_cond* cond, const char* where) {
+                       const genie_sampling* sampling, const genie_guidance* guidance, const genie_frame_cond* cond, const char* where,
+                       const genie_known* known) {
     GENIE_TRY(check_guidance(guidance, cond, where));
     GENIE_TRY(check_sampling(sampling, where));
     GENIE_TRY(check_unmask(unmask_mode, unmask_mode != -1, steps, noise, where));
@@ -184,6 +197,7 @@ static int make_decode(Decode& D, int B, int steps, float temperature, int unmas
     // null_action at every frame; B rows are sampled, masked and written out
     D.guided = guidance && guidance->scale != 1.0f;
     D.copies = D.guided ? 2 : 1;
+    D.known = known ? known->ids : nullptr, D.known_stride = known ? (long)known->clip_stride : 0;
     GENIE_CHECK_ARG(!D.guided || B <= 0x3fffffff, "%s: B=%d too large for guidance", where, B);
     return GENIE_OK;
 }
@@ -239,15 +253,22 @@ static int run_context(const PassCtx& X, const GenScratch& g, int B, int copies,
 // logits are in g.logits), which whoever consumes them resets.
 struct Commit {
     bool merge = false, opened = false;
+    const int64_t* next_known = nullptr;   // the known tokens of the slot a merged commit opens (clip stride known_stride), or NULL
+    long known_stride = 0;
 };
 // Commit slot t from the tokens that put(dst, dst_stride) lays into the pass's rows of dst: in the two-frame pass that also carries the
-// all-mask slot t + 1 (B clips, each `copies` times), for good on its own once the library refuses that pass
+// start tokens of slot t + 1 (all-mask, or cm.next_known where known; B clips, each `copies` times), for good on its own once the
+// library refuses that pass
 template <class Put>
 static int commit_slot(const PassCtx& X, const GenScratch& g, Commit& cm, int t, int B, int copies, Put put) {
     const genie_cfg& c = *X.cfg;
     if (cm.merge) {
         GENIE_TRY(put(g.two, 2L * c.S));
-        GENIE_TRY(put_frame_ids(nullptr, 0, g.two + c.S, 2L * c.S, c.S, B, c.image_vocab_size, as_stream(X.stream), copies));
+        if (cm.next_known)
+            GENIE_TRY(launch_known_begin(cm.next_known, cm.known_stride, c.image_vocab_size, g.two + c.S, 2L * c.S, nullptr, B, c.S, copies,
+                                         as_stream(X.stream)));
+        else
+            GENIE_TRY(put_frame_ids(nullptr, 0, g.two + c.S, 2L * c.S, c.S, B, c.image_vocab_size, as_stream(X.stream), copies));
         const int rc = run_pass(X, g.two, t, 2, g.logits);
         if (rc == GENIE_E_UNSUPPORTED) cm.merge = false;
         else { GENIE_TRY(rc); cm.opened = true; }
@@ -261,10 +282,11 @@ static int commit_slot(const PassCtx& X, const GenScratch& g, Commit& cm, int t,
 
 // One MaskGIT step of one frame: sample B rows from the frame's token-major logits (logits_null: the null half under guidance), then
 // mask-step the samples into the frame's tokens at `frame` (clip stride in elements).  noise / uniforms: the call's draws for this frame,
-// (steps - 1, B, S) and (steps, num_factored, B, S).
+// (steps - 1, B, S) and (steps, num_factored, B, S).  known: the frame's known tokens (clip stride D.known_stride): each clip re-masks
+// ceil(frac * (S - K_b)) tokens, K_b counted by the kernel; NULL: mask_count of S for all.
 static int maskgit_step(const genie_cfg& c, const Decode& D, int B, const float* logits, const float* logits_null, int64_t* samples,
                         float* conf, uint8_t* unmasked, int64_t* frame, long clip_stride, int step, const float* noise,
-                        const float* uniforms, hipStream_t st) {
+                        const float* uniforms, const int64_t* known, hipStream_t st) {
     const size_t BS = (size_t)B * c.S;
     const bool last = step == D.steps - 1, by_conf = D.unmask_mode == GENIE_UNMASK_CONFIDENCE;
     const float* u = D.temperature > 1e-8f ? uniforms + (size_t)step * c.num_factored * BS : nullptr;
@@ -278,6 +300,9 @@ static int maskgit_step(const genie_cfg& c, const Decode& D, int B, const float*
     else
         GENIE_TRY(launch_sample_ex(c, logits, GENIE_LAYOUT_TOKEN_MAJOR, B, D.temperature, u, samples, conf, D.law, keys_out, draws, anneal, st));
     const float* keys = last ? nullptr : (D.unmask_mode == GENIE_UNMASK_RANDOM ? draws : conf);
+    if (known)
+        return launch_mask_step_known(keys, last ? 0.0 : mask_fraction(step, D.steps), last, c.image_vocab_size, known, D.known_stride,
+                                      unmasked, samples, frame, clip_stride, B, c.S, st);
     return launch_mask_step(keys, last ? 0 : mask_count(step, D.steps, c.S), last, c.image_vocab_size, unmasked, samples, frame, clip_stride,
                             B, c.S, st);
 }
@@ -287,10 +312,11 @@ static int maskgit_step(const genie_cfg& c, const Decode& D, int B, const float*
 // logits0_out[:, k] of (B, n, S, V) when wanted.  Every slot but the LAST is committed -- from its final tokens, or from tf + k * S (clip
 // stride tf_stride) when tf is given (teacher forcing in time) --, merged with step 0 of the next slot where merge_commit is set and the
 // library covers it.  pend != NULL: slot t0 - 1 is still pending; its final tokens (pend, clip stride pend_stride) are committed first, by
-// the same rule.
+// the same rule.  known != NULL: slot t0 + k starts from the known tokens at known + k * S (clip stride D.known_stride) instead of
+// all-mask, in one launch, and so does the second frame of the merged commit that opens it.
 static int decode_slots(const PassCtx& X, const Decode& D, int B, const GenScratch& g, int merge_commit, int t0, int n, const float* noise,
                         const float* uniforms, int64_t* out, long out_stride, float* logits0_out, const int64_t* tf, long tf_stride,
-                        const int64_t* pend, long pend_stride) {
+                        const int64_t* pend, long pend_stride, const int64_t* known) {
     const genie_cfg& c = *X.cfg;
     const int S = c.S, steps = D.steps;
     hipStream_t st = as_stream(X.stream);
@@ -298,16 +324,23 @@ static int decode_slots(const PassCtx& X, const Decode& D, int B, const GenScrat
     const float* logits_null = g.logits + BS * V;   // guided: rows B .. 2B - 1 of every pass's logits
     Commit cm;
     cm.merge = merge_commit != 0;
-    auto commit = [&](int t, const int64_t* fsrc, long fstride) {
+    cm.known_stride = D.known_stride;
+    auto commit = [&](int t, const int64_t* fsrc, long fstride, int k_next) {   // k_next: the slot it opens, t + 1 = t0 + k_next
+        cm.next_known = known ? known + (size_t)k_next * S : nullptr;
         return commit_slot(X, g, cm, t, B, D.copies, [&](int64_t* dst, long dst_stride) {
             return put_frame_ids(fsrc, fstride, dst, dst_stride, S, B, 0, st, D.copies);
         });
     };
-    if (pend) GENIE_TRY(commit(t0 - 1, pend, pend_stride));
+    if (pend) GENIE_TRY(commit(t0 - 1, pend, pend_stride, 0));
     for (int k = 0; k < n; ++k) {
         const int t = t0 + k;
-        GENIE_TRY(put_frame_ids(nullptr, 0, g.cur, S, S, B, c.image_vocab_size, st, D.copies));
-        if (hipMemsetAsync(g.unmasked, 0, BS, st) != hipSuccess) { set_error("memset failed"); return GENIE_E_LAUNCH; }
+        const int64_t* kn = known ? known + (size_t)k * S : nullptr;
+        if (kn) {
+            GENIE_TRY(launch_known_begin(kn, D.known_stride, c.image_vocab_size, g.cur, S, g.unmasked, B, S, D.copies, st));
+        } else {
+            GENIE_TRY(put_frame_ids(nullptr, 0, g.cur, S, S, B, c.image_vocab_size, st, D.copies));
+            if (hipMemsetAsync(g.unmasked, 0, BS, st) != hipSuccess) { set_error("memset failed"); return GENIE_E_LAUNCH; }
+        }
         for (int step = 0; step < steps; ++step) {
             if (!(step == 0 && cm.opened))
                 GENIE_TRY(run_pass(X, g.cur, t, 1, g.logits));
@@ -323,13 +356,13 @@ static int decode_slots(const PassCtx& X, const Decode& D, int B, const GenScrat
             }
             GENIE_TRY(maskgit_step(c, D, B, g.logits, logits_null, g.samples, g.conf, g.unmasked, g.cur, S, step,
                                    noise ? noise + (size_t)k * (steps - 1) * BS : nullptr,
-                                   uniforms ? uniforms + (size_t)k * steps * c.num_factored * BS : nullptr, st));
+                                   uniforms ? uniforms + (size_t)k * steps * c.num_factored * BS : nullptr, kn, st));
             if (D.guided) GENIE_TRY(put_frame_ids(g.cur, S, g.cur + BS, S, S, B, 0, st));   // the null half sees the same tokens
         }
         GENIE_TRY(put_frame_ids(g.cur, S, out + (size_t)k * S, out_stride, S, B, 0, st));
         cm.opened = false;
         if (k + 1 < n)   // commit slot t: its final tokens, or the ground truth when teacher-forcing in time
-            GENIE_TRY(commit(t, tf ? tf + (size_t)k * S : g.cur, tf ? tf_stride : (long)S));
+            GENIE_TRY(commit(t, tf ? tf + (size_t)k * S : g.cur, tf ? tf_stride : (long)S, k + 1));
     }
     return GENIE_OK;
 }
@@ -413,14 +446,16 @@ static int fanout_prologue(const char* where, const char* sizer, const genie_cfg
     return run_context(ctx, F.g, B, copies, P, ids, ids_stride);
 }
 
-// The full-forward MaskGIT loop (genie_maskgit_generate_ex is this with guidance NULL): B clips decoded, NB per forward
-int genie_maskgit_generate_guided(const genie_cfg* cfg, const genie_weights* wt, int64_t* prompt, int B, int out_t, int steps,
-                                  float temperature, int unmask_mode, const float* noise, const float* uniforms,
-                                  int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
-                                  void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond,
-                                  const genie_sampling* sampling, const genie_guidance* guidance) {
+// The full-forward MaskGIT loop (genie_maskgit_generate_guided is this with known NULL, _ex with guidance NULL too): B clips decoded,
+// NB per forward
+int genie_maskgit_generate_known(const genie_cfg* cfg, const genie_weights* wt, int64_t* prompt, int B, int out_t, int steps,
+                                 float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                                 int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
+                                 void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond,
+                                 const genie_sampling* sampling, const genie_guidance* guidance, const genie_known* known) {
     GENIE_TRY(check_cfg(cfg));
     const genie_cfg& c = *cfg;
+    GENIE_TRY(check_known(known, 1, c.S, "maskgit_generate"));
     GENIE_CHECK_ARG(wt && wt->layers_host && prompt && samples_out, "maskgit_generate: NULL pointer");
     GENIE_TRY(check_frame_cond(cond, "maskgit_generate"));
     if (!(out_t >= 1 && out_t < c.T)) {  // assert out_t  (st_mask_git.py:154)
@@ -430,7 +465,7 @@ int genie_maskgit_generate_guided(const genie_cfg* cfg, const genie_weights* wt,
     }
     GENIE_CHECK_ARG(steps >= 1, "maskgit_generate: steps=%d must be >= 1", steps);
     Decode D;
-    GENIE_TRY(make_decode(D, B, steps, temperature, unmask_mode, noise, uniforms, sampling, guidance, cond, "maskgit_generate"));
+    GENIE_TRY(make_decode(D, B, steps, temperature, unmask_mode, noise, uniforms, sampling, guidance, cond, "maskgit_generate", known));
     // under guidance every forward runs 2 B clips, [conditional ; null], on a doubled copy of the prompt behind the workspace
     const int NB = D.copies * B;
     GENIE_TRY(check_ws(c, NB, workspace, workspace_bytes));
@@ -458,7 +493,12 @@ int genie_maskgit_generate_guided(const genie_cfg* cfg, const genie_weights* wt,
     float* logits_g = w.logits + 2 * BS * V;
 
     GENIE_TRY(launch_check_masked(prompt, B, c.T, c.S, out_t, c.image_vocab_size, status_flag, st));
-    if (hipMemsetAsync(w.unmasked, 0, BS, st) != hipSuccess) { set_error("memset failed"); return GENIE_E_LAUNCH; }
+    if (D.known) {   // the frame starts from the known tokens, in the prompt and in both halves of its doubled copy
+        GENIE_TRY(launch_known_begin(D.known, D.known_stride, c.image_vocab_size, frame, clip, w.unmasked, B, c.S, 1, st));
+        if (D.guided)
+            GENIE_TRY(launch_known_begin(D.known, D.known_stride, c.image_vocab_size, const_cast<int64_t*>(tokens) + (size_t)out_t * c.S, clip,
+                                         nullptr, B, c.S, 2, st));
+    } else if (hipMemsetAsync(w.unmasked, 0, BS, st) != hipSuccess) { set_error("memset failed"); return GENIE_E_LAUNCH; }
     EmbedAct act;
     const EmbedAct* pact = frame_act(cond, c.S, 0, c.T, act);
     for (int step = 0; step < steps; ++step) {
@@ -477,7 +517,7 @@ int genie_maskgit_generate_guided(const genie_cfg* cfg, const genie_weights* wt,
                 GENIE_TRY(launch_transpose(D.guided ? logits_g : w.logits, logits0_out, B, c.S, (int)V, st));
             }
         }
-        GENIE_TRY(maskgit_step(c, D, B, w.logits, logits_null, w.samples, w.conf, w.unmasked, frame, clip, step, noise, uniforms, st));
+        GENIE_TRY(maskgit_step(c, D, B, w.logits, logits_null, w.samples, w.conf, w.unmasked, frame, clip, step, noise, uniforms, D.known, st));
         if (D.guided && step != steps - 1)   // both halves of the next forward see the frame's current tokens
             GENIE_TRY(put_frame_ids(frame, clip, const_cast<int64_t*>(tokens) + (size_t)out_t * c.S, clip, c.S, B, 0, st, 2));
     }
@@ -488,20 +528,22 @@ int genie_maskgit_generate_guided(const genie_cfg* cfg, const genie_weights* wt,
     return GENIE_OK;
 }
 
-// The cached generate loop (genie_generate_cached_ex is this with guidance NULL): B clips decoded, NB per pass
-int genie_generate_cached_guided(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int P, int n_new,
-                                 int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
-                                 int teacher_force_time, int merge_commit, int64_t* gen_out, float* logits0_out, float* cache,
-                                 size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
-                                 const genie_frame_cond* cond, const genie_sampling* sampling, const genie_guidance* guidance) {
+// The cached generate loop (genie_generate_cached_guided is this with known NULL, _ex with guidance NULL too): B clips decoded, NB per pass
+int genie_generate_cached_known(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int P, int n_new,
+                                int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                                int teacher_force_time, int merge_commit, int64_t* gen_out, float* logits0_out, float* cache,
+                                size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
+                                const genie_frame_cond* cond, const genie_sampling* sampling, const genie_guidance* guidance,
+                                const genie_known* known) {
     GENIE_TRY(check_cfg(cfg));
     const genie_cfg& c = *cfg;
+    GENIE_TRY(check_known(known, n_new, c.S, "generate_cached"));
     GENIE_CHECK_ARG(wt && wt->layers_host && ids && gen_out && cache, "generate_cached: NULL pointer");
     GENIE_TRY(check_frame_cond(cond, "generate_cached"));
     GENIE_CHECK_ARG(B >= 1 && P >= 1 && n_new >= 1 && P + n_new <= c.T && steps >= 1,
                     "generate_cached: B=%d, %d prompt + %d new frames of at most %d, steps %d", B, P, n_new, c.T, steps);
     Decode D;
-    GENIE_TRY(make_decode(D, B, steps, temperature, unmask_mode, noise, uniforms, sampling, guidance, cond, "generate_cached"));
+    GENIE_TRY(make_decode(D, B, steps, temperature, unmask_mode, noise, uniforms, sampling, guidance, cond, "generate_cached", known));
     const int NB = D.copies * B;
     GENIE_CHECK_ARG(cache_bytes >= genie_prefix_cache_bytes(cfg, NB), "generate_cached: cache too small");
     GENIE_TRY(check_ws(c, NB, workspace, workspace_bytes));
@@ -525,7 +567,7 @@ int genie_generate_cached_guided(const genie_cfg* cfg, const genie_weights* wt, 
         GENIE_TRY(put_frame_ids(ids + (size_t)t * S, (long)T * S, g.idsP + (size_t)t * S, (long)P * S, S, B, 0, st, D.copies));
     GENIE_TRY(run_context(X, g, B, D.copies, P, ids, (long)T * S));
     return decode_slots(X, D, B, g, merge_commit, P, n_new, noise, uniforms, gen_out, (long)n_new * S, logits0_out,
-                        teacher_force_time ? ids + (size_t)P * S : nullptr, (long)T * S, nullptr, 0);
+                        teacher_force_time ? ids + (size_t)P * S : nullptr, (long)T * S, nullptr, 0, D.known);
 }
 
 extern "C" {
@@ -560,6 +602,16 @@ int genie_generate_cached_cond(const genie_cfg* cfg, const genie_weights* wt, co
                                     nullptr);
 }
 
+int genie_generate_cached_guided(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int P, int n_new,
+                                 int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                                 int teacher_force_time, int merge_commit, int64_t* gen_out, float* logits0_out, float* cache,
+                                 size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
+                                 const genie_frame_cond* cond, const genie_sampling* sampling, const genie_guidance* guidance) {
+    return genie_generate_cached_known(cfg, wt, ids, B, P, n_new, steps, temperature, unmask_mode, noise, uniforms, teacher_force_time,
+                                       merge_commit, gen_out, logits0_out, cache, cache_bytes, workspace, workspace_bytes, stream, cond,
+                                       sampling, guidance, nullptr);
+}
+
 int genie_generate_cached_ex(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int P, int n_new,
                              int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
                              int teacher_force_time, int merge_commit, int64_t* gen_out, float* logits0_out, float* cache,
@@ -581,6 +633,15 @@ int genie_rollout_cached(const genie_cfg* cfg, const genie_weights* wt, int64_t*
                          int resume, int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
                          int merge_commit, float* cache, size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
                          const genie_frame_cond* cond, const genie_sampling* sampling, const genie_guidance* guidance) {
+    return genie_rollout_cached_known(cfg, wt, frames, B, P, keep, cap, f0, f1, resume, steps, temperature, unmask_mode, noise, uniforms,
+                                      merge_commit, cache, cache_bytes, workspace, workspace_bytes, stream, cond, sampling, guidance, nullptr);
+}
+
+int genie_rollout_cached_known(const genie_cfg* cfg, const genie_weights* wt, int64_t* frames, int B, int P, int keep, int cap, int f0,
+                               int f1, int resume, int steps, float temperature, int unmask_mode, const float* noise,
+                               const float* uniforms, int merge_commit, float* cache, size_t cache_bytes, void* workspace,
+                               size_t workspace_bytes, void* stream, const genie_frame_cond* cond, const genie_sampling* sampling,
+                               const genie_guidance* guidance, const genie_known* known) {
     GENIE_TRY(check_cfg(cfg));
     const genie_cfg& c = *cfg;
     const int T = c.T, S = c.S;
@@ -589,9 +650,10 @@ int genie_rollout_cached(const genie_cfg* cfg, const genie_weights* wt, int64_t*
     GENIE_CHECK_ARG(keep >= 1 && keep <= T - 1, "rollout_cached: keep %d outside [1, %d]", keep, T - 1);
     GENIE_CHECK_ARG(P <= f0 && f0 < f1 && f1 <= cap, "rollout_cached: frames [%d, %d) must lie in [%d prompt frames, cap %d]", f0, f1, P, cap);
     GENIE_CHECK_ARG(resume == 0 || resume == 1, "rollout_cached: resume %d must be 0 or 1", resume);
+    GENIE_TRY(check_known(known, (long)f1 - f0, S, "rollout_cached"));
     GENIE_TRY(check_frame_cond(cond, "rollout_cached"));
     Decode D;
-    GENIE_TRY(make_decode(D, B, steps, temperature, unmask_mode, noise, uniforms, sampling, guidance, cond, "rollout_cached"));
+    GENIE_TRY(make_decode(D, B, steps, temperature, unmask_mode, noise, uniforms, sampling, guidance, cond, "rollout_cached", known));
     GENIE_CHECK_ARG(wt && wt->layers_host && frames && cache, "rollout_cached: NULL pointer");
     const int NB = D.copies * B, hop = T - keep;
     GENIE_CHECK_ARG(cache_bytes >= genie_prefix_cache_bytes(cfg, NB), "rollout_cached: cache too small");
@@ -626,7 +688,8 @@ int genie_rollout_cached(const genie_cfg* cfg, const genie_weights* wt, int64_t*
         if (fresh) GENIE_TRY(run_context(X, g, B, D.copies, ctx, frames + (size_t)start * S, stride));
         GENIE_TRY(decode_slots(X, D, B, g, merge_commit, f - start, end - f, noise ? noise + (size_t)(f - f0) * (steps - 1) * B * S : nullptr,
                                uniforms ? uniforms + (size_t)(f - f0) * steps * c.num_factored * B * S : nullptr, frames + (size_t)f * S,
-                               stride, nullptr, nullptr, 0, fresh ? nullptr : frames + (size_t)(f - 1) * S, stride));
+                               stride, nullptr, nullptr, 0, fresh ? nullptr : frames + (size_t)(f - 1) * S, stride,
+                               D.known ? D.known + (size_t)(f - f0) * S : nullptr));
         f = end;
     }
     return GENIE_OK;
@@ -648,19 +711,30 @@ int genie_generate_fanout(const genie_cfg* cfg, const genie_weights* wt, const i
                           float temperature, int unmask_mode, const float* noise, const float* uniforms, int merge_commit, int64_t* gen_out,
                           float* trunk, size_t trunk_bytes, float* branch, size_t branch_bytes, void* workspace, size_t workspace_bytes,
                           void* stream, const genie_frame_cond* cond, const genie_sampling* sampling, const genie_guidance* guidance) {
+    return genie_generate_fanout_known(cfg, wt, ids, B, K, P, n_new, steps, temperature, unmask_mode, noise, uniforms, merge_commit, gen_out,
+                                       trunk, trunk_bytes, branch, branch_bytes, workspace, workspace_bytes, stream, cond, sampling, guidance,
+                                       nullptr);
+}
+
+int genie_generate_fanout_known(const genie_cfg* cfg, const genie_weights* wt, const int64_t* ids, int B, int K, int P, int n_new,
+                                int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                                int merge_commit, int64_t* gen_out, float* trunk, size_t trunk_bytes, float* branch, size_t branch_bytes,
+                                void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond,
+                                const genie_sampling* sampling, const genie_guidance* guidance, const genie_known* known) {
     GENIE_TRY(check_cfg(cfg));
+    GENIE_TRY(check_known(known, n_new, cfg->S, "generate_fanout"));
     GENIE_TRY(check_frame_cond(cond, "generate_fanout"));
     GENIE_CHECK_ARG(B >= 1 && K >= 1 && P >= 1 && n_new >= 1 && P + n_new <= cfg->T && steps >= 1,
                     "generate_fanout: B=%d, K=%d, %d prompt + %d new frames of at most %d, steps %d", B, K, P, n_new, cfg->T, steps);
     Decode D;
-    GENIE_TRY(make_decode(D, B, steps, temperature, unmask_mode, noise, uniforms, sampling, guidance, cond, "generate_fanout"));
+    GENIE_TRY(make_decode(D, B, steps, temperature, unmask_mode, noise, uniforms, sampling, guidance, cond, "generate_fanout", known));
     FanCall F;
     GENIE_TRY(fanout_prologue("generate_fanout", "genie_fanout_workspace_bytes", cfg, wt, ids, (long)P * cfg->S, gen_out, B, K, P, n_new,
                               D.copies, D.guided ? guidance->null_action : 0, trunk, trunk_bytes, branch, branch_bytes, workspace,
                               workspace_bytes, stream, cond, F));
     // ... then the loop of genie_generate_cached decodes B * K clips over the split cache, starting at slot P with nothing pending
     return decode_slots(F.br, D, B * K, F.g, merge_commit, P, n_new, noise, uniforms, gen_out, (long)n_new * cfg->S, nullptr, nullptr, 0,
-                        nullptr, 0);
+                        nullptr, 0, D.known);
 }
 
 // ---- scoring observed futures: per-(clip, branch, frame) NLL over the fan-out cache ----------------------------------------
@@ -696,6 +770,15 @@ int genie_maskgit_generate_cond(const genie_cfg* cfg, const genie_weights* wt, i
     if (unmask_mode == GENIE_UNMASK_CONFIDENCE) unmask_mode = -1;   // (only genie_maskgit_generate_ex knows that mode)
     return genie_maskgit_generate_ex(cfg, wt, prompt, B, out_t, steps, temperature, unmask_mode, noise, uniforms, samples_out,
                                      logits0_out, layout, status_flag, workspace, workspace_bytes, stream, cond, nullptr);
+}
+
+int genie_maskgit_generate_guided(const genie_cfg* cfg, const genie_weights* wt, int64_t* prompt, int B, int out_t, int steps,
+                                  float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                                  int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
+                                  void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond,
+                                  const genie_sampling* sampling, const genie_guidance* guidance) {
+    return genie_maskgit_generate_known(cfg, wt, prompt, B, out_t, steps, temperature, unmask_mode, noise, uniforms, samples_out, logits0_out,
+                                        layout, status_flag, workspace, workspace_bytes, stream, cond, sampling, guidance, nullptr);
 }
 
 int genie_maskgit_generate_ex(const genie_cfg* cfg, const genie_weights* wt, int64_t* prompt, int B, int out_t, int steps,

@@ -262,6 +262,11 @@ int launch_action_rows_backward(const genie_action_proj& p, const float* vecs, c
                                 float* d_bias, int accumulate, hipStream_t st);
 int launch_mask_step(const float* keys, int n, int last_step, int64_t mask_id, uint8_t* unmasked, int64_t* samples,
                      int64_t* prompt_frame, long clip_stride, int B, int S, hipStream_t st);
+// known tokens (kernels_known.hip): a frame's start state, and the mask step with a per-clip count n_b = ceil(frac * (S - K_b))
+int launch_known_begin(const int64_t* known, long known_stride, int64_t mask_id, int64_t* frame, long frame_stride, uint8_t* unmasked, int B,
+                       int S, int copies, hipStream_t st);
+int launch_mask_step_known(const float* keys, double frac, int last_step, int64_t mask_id, const int64_t* known, long known_stride,
+                           uint8_t* unmasked, int64_t* samples, int64_t* prompt_frame, long clip_stride, int B, int S, hipStream_t st);
 int launch_check_masked(const int64_t* prompt, int B, int T, int S, int out_t, int64_t mask_id, int32_t* flag,
                         hipStream_t st);
 int launch_bits(const int64_t* ids, float* z, int n, int hw, int bits, hipStream_t st);
@@ -493,6 +498,7 @@ int check_cfg(const genie_cfg* c);
 int check_ws(const genie_cfg& c, int B, void* ws, size_t bytes);
 int decoder(const genie_cfg& c, const genie_weights& wt, float* x, Workspace& w, int B, hipStream_t st);
 int mask_count(int step, int steps, int S);
+double mask_fraction(int step, int steps);   // cos(pi/2 * (step+1)/steps) as mask_count takes it
 // what a caller's decode options must satisfy, checked on the host before anything is enqueued (NULL = none; where: the entry point)
 int check_sampling(const genie_sampling* sp, const char* where);
 int check_unmask(int unmask_mode, bool ex, int steps, const float* noise, const char* where);

@@ -15,10 +15,39 @@ import torch
 STRIDE = 15
 
 
+def known_tokens(frames, keep, mask_token_id):
+    """The ``known=`` tensor of the generate functions from ``frames`` (..., H, W) and a boolean ``keep`` mask, (H, W) or of the frames' full
+    shape: the frame's token where keep is true, ``mask_token_id`` (model.mask_token_id: "generate this one") where it is false."""
+    frames = torch.as_tensor(frames).to(torch.int64)
+    keep = torch.as_tensor(keep, device=frames.device)
+    if keep.dtype != torch.bool:
+        raise RuntimeError(f"keep must be a boolean mask, got {keep.dtype}")
+    if tuple(keep.shape) not in (tuple(frames.shape), tuple(frames.shape[-2:])):
+        raise RuntimeError(f"keep must have shape {tuple(frames.shape[-2:])} or {tuple(frames.shape)}, got {tuple(keep.shape)}")
+    return torch.where(keep, frames, torch.full_like(frames, int(mask_token_id))).contiguous()
+
+
+def check_known(known, shape, device, what="known"):
+    """The checked ``known`` tensor of a generate call: int64, on ``device``, exactly ``shape`` -- raised before any launch; returned
+    contiguous.  Values are not inspected (that would need a host synchronisation): a value in [0, image_vocab_size) is a known token, any
+    other marks a token to generate.  None -> None."""
+    if known is None:
+        return None
+    if not isinstance(known, torch.Tensor):
+        raise RuntimeError(f"{what} must be a torch tensor, got {type(known).__name__}")
+    if known.dtype != torch.int64:
+        raise RuntimeError(f"{what} must be an int64 tensor, got {known.dtype}")
+    if tuple(known.shape) != tuple(shape):
+        raise RuntimeError(f"expected {what} of shape {tuple(shape)}, got {tuple(known.shape)}")
+    if known.device != torch.device(device):
+        raise RuntimeError(f"{what} must be on {device}, got {known.device}")
+    return known.contiguous()
+
+
 @torch.no_grad()
 def generate_frames(model, example_THW: torch.LongTensor, num_prompt_frames=8, maskgit_steps=2, temperature=0.0,
                     teacher_force_time=False, noise=None, action_ids=None, sampling=None, unmask_mode="random", uniforms=None,
-                    guidance=None, action_vectors=None):
+                    guidance=None, action_vectors=None, known=None):
     """example_THW (B, T, H, W) on the model's device -> outputs (B, T + (T - num_prompt_frames), H, W):
     [prompt frames | predicted frames | ground-truth frames] (generate.py:97-103).
     noise: optional (T - num_prompt_frames, maskgit_steps-1, B, S).
@@ -26,10 +55,12 @@ def generate_frames(model, example_THW: torch.LongTensor, num_prompt_frames=8, m
     sampling: a SamplingConfig (1xgpt_amd/sampling.py) or None = the reference's law; unmask_mode: "random" (the reference's
     harness), "greedy" or "confidence"; uniforms: optional (T - num_prompt_frames, maskgit_steps, num_factored_vocabs, B, S).
     guidance: a Guidance(scale, null_action) or None: classifier-free guidance of an action-conditioned model.
-    action_vectors: (B, T, action_dim) float actions of a model with config.action_dim > 0 (then Guidance(scale) suffices)."""
+    action_vectors: (B, T, action_dim) float actions of a model with config.action_dim > 0 (then Guidance(scale) suffices).
+    known: optional (B, T - num_prompt_frames, H, W) int64 known tokens of the predicted frames (known_tokens; mask_token_id = generate)."""
     window_size = example_THW.shape[1]
     assert num_prompt_frames <= window_size
     example_THW = example_THW.to(torch.int64).contiguous()
+    known = check_known(known, (example_THW.shape[0], window_size - num_prompt_frames) + tuple(example_THW.shape[2:]), example_THW.device)
     samples = []
     prompt_THW = example_THW.clone()
     prompt_THW[:, num_prompt_frames:] = model.mask_token_id
@@ -41,7 +72,7 @@ def generate_frames(model, example_THW: torch.LongTensor, num_prompt_frames=8, m
                                                temperature=temperature, noise=None if noise is None else noise[k],
                                                return_logits=False, action_ids=action_ids, action_vectors=action_vectors, sampling=sampling,
                                                unmask_mode=unmask_mode, uniforms=None if uniforms is None else uniforms[k],
-                                               guidance=guidance)
+                                               guidance=guidance, known=None if known is None else known[:, k])
         samples.append(samples_HW)
         if not teacher_force_time:
             prompt_THW[:, timestep] = samples_HW  # autoregressive (already written in place by maskgit_generate)
@@ -53,7 +84,7 @@ def generate_frames(model, example_THW: torch.LongTensor, num_prompt_frames=8, m
 @torch.no_grad()
 def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_frames=8, maskgit_steps=2, temperature=0.0,
                            teacher_force_time=False, noise=None, unmask_mode="random", merge_commit=True, host_loop=False,
-                           action_ids=None, sampling=None, uniforms=None, guidance=None, action_vectors=None):
+                           action_ids=None, sampling=None, uniforms=None, guidance=None, action_vectors=None, known=None):
     """``generate_frames`` with a temporal KV cache (genie_frame_pass): every pass runs ONE frame through the stack
     against the cached temporal keys/values of the earlier frames instead of the full 16-frame forward --
     one P-frame pass for the prompt + (T-P)*(steps+1) single-frame passes (= 2 full-pass equivalents at P=8, steps=2) instead of (T-P)*steps full
@@ -69,7 +100,9 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
     uniforms: optional (T - num_prompt_frames, maskgit_steps, num_factored_vocabs, B, S) sampling draws to replay.
     guidance: a Guidance(scale, null_action) or None: classifier-free guidance.  Every pass then runs 2 B clips -- the clips under their
     actions, and the same tokens under null_action at every frame --, genie_sample_guided draws B rows from scale * conditional +
-    (1 - scale) * null, and the frame's current tokens are mirrored into the second half before the next pass (both loop forms)."""
+    (1 - scale) * null, and the frame's current tokens are mirrored into the second half before the next pass (both loop forms).
+    known: optional (B, T - num_prompt_frames, H, W) int64 known tokens of the predicted frames (known_tokens): every frame starts from
+    them, each clip re-masks by its own count of tokens left to generate, and its output keeps them (both loop forms)."""
     import math
     from . import _lib
     from .sampling import SamplingConfig, as_struct, unmask_code
@@ -89,6 +122,8 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
     assert P <= T and P >= 1
     dev = ex.device
     ids = ex.view(B, T, S)
+    known = check_known(known, (B, T - P) + tuple(ex.shape[2:]), dev)
+    kn = None if known is None else known.view(B, T - P, S)
     guide = model._guidance(guidance)
     cond = model._cond(action_ids, B, n_frames=T, action_vectors=action_vectors)
     NB = B if guide is None else 2 * B   # clips per pass: [conditional ; null] under guidance
@@ -108,8 +143,8 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
             uni = torch.rand(T - P, steps, nv, B, S, device=dev) if uniforms is None else uniforms
             assert uni.numel() == (T - P) * steps * nv * B * S, "uniforms: (T - P, maskgit_steps, num_factored_vocabs, B, S)"
         gen = torch.empty(B, T - P, S, dtype=torch.int64, device=dev)
-        _lib.check(_lib.call_guided(lib, "genie_generate_cached", cond, law, guide, cfg, w, ids.data_ptr(), B, P, T - P, steps, float(temperature),
-                                             mode,
+        _lib.check(_lib.call_known(lib, "genie_generate_cached", cond, law, guide, _lib.make_known(kn, T - P, S), cfg, w, ids.data_ptr(), B,
+                                             P, T - P, steps, float(temperature), mode,
                                              0 if nz is None else nz.data_ptr(), 0 if uni is None else uni.data_ptr(),
                                              int(bool(teacher_force_time)), int(bool(merge_commit)), gen.data_ptr(), 0, cache.data_ptr(),
                                              nbytes, ws.data_ptr(), ws.numel(), st), "genie_generate_cached")
@@ -160,6 +195,9 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
     for k, t in enumerate(range(P, T)):
         cur = torch.full((NB, S), model.mask_token_id, dtype=torch.int64, device=dev)   # (mask step: rows [0, B))
         unmasked = torch.zeros(B, S, dtype=torch.uint8, device=dev)
+        if kn is not None:   # the frame starts from its known tokens, in both halves under guidance
+            _lib.check(lib.genie_known_begin(kn[:, k].data_ptr(), (T - P) * S, model.mask_token_id, cur.data_ptr(), S, unmasked.data_ptr(),
+                                             B, S, NB // B, st), "genie_known_begin")
         for step in range(maskgit_steps):
             if not (step == 0 and opened):
                 frame_pass(cur, t, logits)
@@ -195,9 +233,15 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
                                                0 if uni is None else uni.data_ptr(), samples.data_ptr(), conf.data_ptr(), st, law,
                                                keys.data_ptr() if by_conf else 0, draws.data_ptr() if by_conf else 0,
                                                1.0 - (step + 1) / maskgit_steps), "genie_sample_ex")
-            _lib.check(lib.genie_mask_step(0 if keys is None else keys.data_ptr(), n, int(last), model.mask_token_id,
-                                           unmasked.data_ptr(), samples.data_ptr(), cur.data_ptr(), S, B, S, st),
-                       "genie_mask_step")
+            if kn is not None:   # each clip's own count: ceil(frac * (S - its known tokens)), taken by the kernel
+                frac = 0.0 if last else lib.genie_mask_fraction(step, maskgit_steps)
+                _lib.check(lib.genie_mask_step_known(0 if keys is None else keys.data_ptr(), frac, int(last), model.mask_token_id,
+                                                     kn[:, k].data_ptr(), (T - P) * S, unmasked.data_ptr(), samples.data_ptr(),
+                                                     cur.data_ptr(), S, B, S, st), "genie_mask_step_known")
+            else:
+                _lib.check(lib.genie_mask_step(0 if keys is None else keys.data_ptr(), n, int(last), model.mask_token_id,
+                                               unmasked.data_ptr(), samples.data_ptr(), cur.data_ptr(), S, B, S, st),
+                           "genie_mask_step")
             if guide is not None:
                 cur[B:] = cur[:B]   # the null half sees the same tokens
         gen.append(cur[:B].view(B, model.h, model.w))
@@ -205,7 +249,11 @@ def generate_frames_cached(model, example_THW: torch.LongTensor, num_prompt_fram
         if t + 1 < T:  # commit frame t (its final tokens, or the ground truth when teacher-forcing in time)
             final = ids[:, t].contiguous() if teacher_force_time else cur
             if merge_commit:
-                opened = commit_and_open(final, torch.full_like(cur, model.mask_token_id), t, logits)
+                nxt = torch.full_like(cur, model.mask_token_id)
+                if kn is not None:   # the slot the commit opens starts from ITS known tokens
+                    _lib.check(lib.genie_known_begin(kn[:, k + 1].data_ptr(), (T - P) * S, model.mask_token_id, nxt.data_ptr(), S, 0, B, S,
+                                                     NB // B, st), "genie_known_begin")
+                opened = commit_and_open(final, nxt, t, logits)
                 merge_commit = opened   # (unsupported once = unsupported for the whole call)
             if not opened:
                 frame_pass(final, t)
@@ -305,9 +353,10 @@ class _Decode:
         return nz, uni
 
 
-def rollout_call(model, frames_BcS, actions_Bc, P, keep, f0, f1, resume, cache, dec, nz, uni, rows=None):
+def rollout_call(model, frames_BcS, actions_Bc, P, keep, f0, f1, resume, cache, dec, nz, uni, rows=None, known=None):
     """ONE genie_rollout_cached call: generates the absolute frames [f0, f1) of frames_BcS (B, cap, S) int64 in place.  actions_Bc: (B, cap)
-    int64 or None -- rows of the model's action table, or of `rows` (a projected row table of a model conditioned on action vectors); cache: uint8 tensor of genie_prefix_cache_bytes(cfg, NB); dec: the _Decode options; nz / uni: this call's draws."""
+    int64 or None -- rows of the model's action table, or of `rows` (a projected row table of a model conditioned on action vectors); cache: uint8 tensor of genie_prefix_cache_bytes(cfg, NB); dec: the _Decode options; nz / uni: this call's draws.
+    known: (B, f1 - f0, S) int64 contiguous known tokens of this call's frames, or None."""
     from . import _lib
     lib = _lib.load()
     cfg, w = model._weights()[:2]
@@ -328,10 +377,13 @@ def rollout_call(model, frames_BcS, actions_Bc, P, keep, f0, f1, resume, cache, 
     ctx = [fb - start for _, start, fb, _ in wins[1:]]
     ctx.append(f0 - wins[0][1] if (not resume or f0 == wins[0][2]) else 1)
     ws = model._workspace(B, guided=dec.guide is not None, rollout_ctx=max(ctx))
-    _lib.check(lib.genie_rollout_cached(cfg, w, frames_BcS.data_ptr(), B, P, keep, cap, f0, f1, int(resume), dec.steps, dec.temperature,
-                                        dec.mode, 0 if nz is None else nz.data_ptr(), 0 if uni is None else uni.data_ptr(),
-                                        int(dec.merge_commit), cache.data_ptr(), cache.numel(), ws.data_ptr(), ws.numel(),
-                                        torch.cuda.current_stream().cuda_stream, cond, dec.law, dec.guide), "genie_rollout_cached")
+    if known is not None:
+        assert known.shape == (B, f1 - f0, S) and known.dtype == torch.int64 and known.is_contiguous()
+    _lib.check(_lib.call_known3(lib, "genie_rollout_cached", _lib.make_known(known, f1 - f0, S), cfg, w, frames_BcS.data_ptr(), B, P, keep,
+                                cap, f0, f1, int(resume), dec.steps, dec.temperature,
+                                dec.mode, 0 if nz is None else nz.data_ptr(), 0 if uni is None else uni.data_ptr(),
+                                int(dec.merge_commit), cache.data_ptr(), cache.numel(), ws.data_ptr(), ws.numel(),
+                                torch.cuda.current_stream().cuda_stream, cond, dec.law, dec.guide), "genie_rollout_cached")
 
 
 def _rollout_cache(model, B, dec, dev):
@@ -342,7 +394,8 @@ def _rollout_cache(model, B, dec, dev):
 
 @torch.no_grad()
 def rollout_frames(model, prompt_BPHW: torch.LongTensor, n_new, keep=None, maskgit_steps=2, temperature=0.0, unmask_mode="random",
-                   noise=None, uniforms=None, action_ids=None, sampling=None, guidance=None, merge_commit=True, action_vectors=None):
+                   noise=None, uniforms=None, action_ids=None, sampling=None, guidance=None, merge_commit=True, action_vectors=None,
+                   known=None):
     """Generate n_new frames behind the P prompt frames of prompt_BPHW (B, P, H, W), past the model's window T if need be, in ONE library
     call (genie_rollout_cached) -> (B, P + n_new, H, W).  Window 0 decodes frames [P, T); after that the window slides: the last ``keep``
     frames (default P; 1 <= keep <= T - 1) are re-run as the context of the next hop = T - keep frames (window_schedule; positions are
@@ -350,10 +403,12 @@ def rollout_frames(model, prompt_BPHW: torch.LongTensor, n_new, keep=None, maskg
     for bit, to chaining generate_frames_cached window by window on the same draws.
     noise: optional (n_new, maskgit_steps - 1, B, S); uniforms: optional (n_new, maskgit_steps, num_factored_vocabs, B, S); fresh
     torch.rand draws otherwise.  action_ids: (B, P + n_new), the actions of the absolute frames; action_vectors: (B, P + n_new, action_dim)
-    for a model with config.action_dim > 0 (one launch projects all of them before the call).  The other options: generate_frames_cached."""
+    for a model with config.action_dim > 0 (one launch projects all of them before the call).  The other options: generate_frames_cached.
+    known: optional (B, n_new, H, W) int64 known tokens of the generated frames (known_tokens)."""
     cfg = model.config
     pr = prompt_BPHW.to(torch.int64)
     B, P = pr.shape[0], pr.shape[1]
+    known = check_known(known, (B, int(n_new), model.h, model.w), pr.device)
     keep = P if keep is None else int(keep)
     n_new = int(n_new)
     if n_new < 1:
@@ -370,7 +425,8 @@ def rollout_frames(model, prompt_BPHW: torch.LongTensor, n_new, keep=None, maskg
     frames = torch.full((B, P + n_new, cfg.S), model.mask_token_id, dtype=torch.int64, device=dev)
     frames[:, :P] = pr.reshape(B, P, cfg.S)
     nz, uni = dec.draws(model, n_new, B, noise, uniforms, dev)
-    rollout_call(model, frames, acts, P, keep, P, P + n_new, 0, _rollout_cache(model, B, dec, dev), dec, nz, uni, rows=rows)
+    rollout_call(model, frames, acts, P, keep, P, P + n_new, 0, _rollout_cache(model, B, dec, dev), dec, nz, uni, rows=rows,
+                 known=None if known is None else known.view(B, n_new, cfg.S))
     return frames.view(B, P + n_new, model.h, model.w)
 
 
@@ -418,7 +474,7 @@ def _fanout_inputs(model, prompt_BPHW, n_new, K, action_ids, action_vectors, pro
 @torch.no_grad()
 def fanout_frames(model, prompt_BPHW: torch.LongTensor, n_new, K=None, action_ids=None, action_vectors=None, prompt_actions=None,
                   prompt_action_vectors=None, maskgit_steps=2, temperature=0.0, unmask_mode="random", sampling=None, guidance=None,
-                  merge_commit=True, noise=None, uniforms=None):
+                  merge_commit=True, noise=None, uniforms=None, known=None):
     """K candidate futures of n_new frames for each of the B prompts (B, P, H, W) -> (B, K, n_new, H, W), in ONE library call
     (genie_generate_fanout): the context runs once per clip into a shared trunk cache, and the decode passes run B * K clips that read the
     trunk's slots [0, P) and keep only their own n_new slots.  In-window: P + n_new <= T.  Branch k of clip b equals clip b * K + k of
@@ -428,14 +484,19 @@ def fanout_frames(model, prompt_BPHW: torch.LongTensor, n_new, K=None, action_id
     one row table; row 0 is action_null).  K is taken from them; an unconditioned model takes K explicitly, and its branches differ by
     their draws only.  noise: optional (n_new, maskgit_steps - 1, B * K, S); uniforms: optional (n_new, maskgit_steps, num_factored_vocabs,
     B * K, S); fresh torch.rand draws otherwise.  The other options: generate_frames_cached.
+    known: optional int64 known tokens of the new frames (known_tokens), (B, K, n_new, H, W) per branch or (B, n_new, H, W) for all K.
     A longer horizon continues by handing the (B * K) results, behind their prompts, to rollout_frames as prompts."""
     B, P, K, pa, ba, pv, bv = _fanout_inputs(model, prompt_BPHW, n_new, K, action_ids, action_vectors, prompt_actions, prompt_action_vectors)
     n_new = int(n_new)
     dec = _Decode(model, maskgit_steps, temperature, unmask_mode, sampling, guidance, merge_commit)
     pr = prompt_BPHW.to(torch.int64).reshape(B, P, model.config.S).contiguous()
+    if isinstance(known, torch.Tensor) and known.dim() == 4:   # one set of known tokens for the K branches of a clip
+        known = check_known(known, (B, n_new, model.h, model.w), pr.device)[:, None].expand(B, K, n_new, model.h, model.w)
+    known = check_known(known, (B, K, n_new, model.h, model.w), pr.device)
     cond = fanout_cond(model, B, P, K, n_new, pa, ba, pv, bv, pr.device)
     nz, uni = dec.draws(model, n_new, B * K, noise, uniforms, pr.device)
-    return fanout_call(model, pr, K, n_new, cond, dec, nz, uni).view(B, K, n_new, model.h, model.w)
+    return fanout_call(model, pr, K, n_new, cond, dec, nz, uni,
+                       known=None if known is None else known.reshape(B * K, n_new, model.config.S)).view(B, K, n_new, model.h, model.w)
 
 
 def fanout_cond(model, B, P, K, n_new, prompt_ids, branch_ids, prompt_vectors, branch_vectors, dev):
@@ -462,15 +523,18 @@ def fanout_cond(model, B, P, K, n_new, prompt_ids, branch_ids, prompt_vectors, b
     return cond
 
 
-def fanout_call(model, prompt_BPS, K, n_new, cond, dec, nz, uni, trunk=None, branch=None):
+def fanout_call(model, prompt_BPS, K, n_new, cond, dec, nz, uni, trunk=None, branch=None, known=None):
     """ONE genie_generate_fanout call -> gen (B, K, n_new, S) int64.  prompt_BPS: (B, P, S) int64, contiguous; cond: fanout_cond; dec: the
     _Decode options; nz / uni: the call's draws over B K rows.  trunk / branch: uint8 tensors of genie_prefix_cache_bytes(cfg, NB) and
-    genie_fanout_branch_bytes(cfg, NB, K, n_new) to keep what the call leaves in them (allocated here otherwise)."""
+    genie_fanout_branch_bytes(cfg, NB, K, n_new) to keep what the call leaves in them (allocated here otherwise).  known: (B K, n_new, S)
+    int64 contiguous known tokens of the branches' frames, or None."""
     from . import _lib
     lib = _lib.load()
     cfg, w = model._weights()[:2]
     B, P, S = prompt_BPS.shape
     assert prompt_BPS.dtype == torch.int64 and prompt_BPS.is_contiguous()
+    if known is not None:
+        assert known.shape == (B * K, n_new, S) and known.dtype == torch.int64 and known.is_contiguous()
     dev = prompt_BPS.device
     NB = B if dec.guide is None else 2 * B
     if trunk is None:
@@ -479,10 +543,11 @@ def fanout_call(model, prompt_BPS, K, n_new, cond, dec, nz, uni, trunk=None, bra
         branch = torch.empty(lib.genie_fanout_branch_bytes(cfg, NB, K, n_new), dtype=torch.uint8, device=dev)
     ws = torch.empty(lib.genie_fanout_workspace_bytes(cfg, B, K, P, int(dec.guide is not None)), dtype=torch.uint8, device=dev)
     gen = torch.empty(B, K, n_new, S, dtype=torch.int64, device=dev)
-    _lib.check(lib.genie_generate_fanout(cfg, w, prompt_BPS.data_ptr(), B, K, P, n_new, dec.steps, dec.temperature, dec.mode,
-                                         0 if nz is None else nz.data_ptr(), 0 if uni is None else uni.data_ptr(), int(dec.merge_commit),
-                                         gen.data_ptr(), trunk.data_ptr(), trunk.numel(), branch.data_ptr(), branch.numel(), ws.data_ptr(),
-                                         ws.numel(), torch.cuda.current_stream().cuda_stream, cond, dec.law, dec.guide), "genie_generate_fanout")
+    _lib.check(_lib.call_known3(lib, "genie_generate_fanout", _lib.make_known(known, n_new, S), cfg, w, prompt_BPS.data_ptr(), B, K, P, n_new,
+                                dec.steps, dec.temperature, dec.mode,
+                                0 if nz is None else nz.data_ptr(), 0 if uni is None else uni.data_ptr(), int(dec.merge_commit),
+                                gen.data_ptr(), trunk.data_ptr(), trunk.numel(), branch.data_ptr(), branch.numel(), ws.data_ptr(),
+                                ws.numel(), torch.cuda.current_stream().cuda_stream, cond, dec.law, dec.guide), "genie_generate_fanout")
     return gen
 
 
@@ -633,13 +698,15 @@ class Rollout:
             self._acts = acts
 
     @torch.no_grad()
-    def extend(self, n, action_ids=None, noise=None, uniforms=None, action_vectors=None):
+    def extend(self, n, action_ids=None, noise=None, uniforms=None, action_vectors=None, known=None):
         """Generate the next n frames -> (B, n, H, W).  action_ids: (B, n) actions of the new frames (action_vectors: (B, n, action_dim)
         for a model with config.action_dim > 0); noise (n, steps - 1, B, S) and
-        uniforms (n, steps, nv, B, S): this call's draws, or fresh torch.rand ones."""
+        uniforms (n, steps, nv, B, S): this call's draws, or fresh torch.rand ones.  known: optional (B, n, H, W) int64 known tokens of
+        the new frames (known_tokens)."""
         n = int(n)
         if n < 1:
             raise ValueError("Rollout.extend: n must be >= 1")
+        known = check_known(known, (self.B, n, self.model.h, self.model.w), self._frames.device)
         acts, vecs = _rollout_inputs(self.model, action_ids, action_vectors, self.B, n)
         f0, f1 = self.n, self.n + n
         self._grow(f1)
@@ -649,21 +716,22 @@ class Rollout:
             self._acts[:, f0:f1] = acts
         nz, uni = self.dec.draws(self.model, n, self.B, noise, uniforms, self._frames.device)
         rollout_call(self.model, self._frames, self._acts, self.P, self.keep, f0, f1, self._resume, self._cache, self.dec, nz, uni,
-                     rows=self._rows)
+                     rows=self._rows, known=None if known is None else known.view(self.B, n, -1))
         self.n, self._resume = f1, 1
         return self._frames[:, f0:f1].reshape(self.B, n, self.model.h, self.model.w)
 
-    def step(self, action=None, noise=None, uniforms=None):
+    def step(self, action=None, noise=None, uniforms=None, known=None):
         """Generate the next frame under ``action`` (B,) -> (B, H, W); a model with config.action_dim > 0 takes the frame's (B, action_dim)
-        float vectors.  noise (steps - 1, B, S), uniforms (steps, nv, B, S): its draws."""
+        float vectors.  noise (steps - 1, B, S), uniforms (steps, nv, B, S): its draws.  known: optional (B, H, W) int64 known tokens."""
+        known = None if known is None else check_known(known, (self.B, self.model.h, self.model.w), self._frames.device)[:, None]
         nz, uni = None if noise is None else noise[None], None if uniforms is None else uniforms[None]
         if self.model.config.action_dim and action is not None:
             v = torch.as_tensor(action)
             if v.dim() != 2 or v.shape[0] != self.B:
                 raise RuntimeError(f"expected the frame's action vectors of shape ({self.B}, {self.model.config.action_dim}), got {tuple(v.shape)}")
-            return self.extend(1, None, nz, uni, action_vectors=v[:, None])[:, 0]
+            return self.extend(1, None, nz, uni, action_vectors=v[:, None], known=known)[:, 0]
         a = None if action is None else torch.as_tensor(action).reshape(self.B, 1)
-        return self.extend(1, a, nz, uni)[:, 0]
+        return self.extend(1, a, nz, uni, known=known)[:, 0]
 
 
 def write_outputs(outputs_THW: torch.LongTensor, output_dir, dataset_metadata: dict, args: dict):

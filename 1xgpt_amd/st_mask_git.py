@@ -539,7 +539,7 @@ class STMaskGIT(nn.Module):
     @torch.no_grad()
     def maskgit_generate(self, prompt_THW, out_t, maskgit_steps=1, temperature=0.0, unmask_mode="random",
                          noise=None, uniforms=None, return_logits=True, check=True, action_ids=None, sampling=None, guidance=None,
-                         action_vectors=None):
+                         action_vectors=None, known=None):
         """MaskGIT decode of frame ``out_t`` (reference :123-229): the whole loop runs on the device.
 
         Mutates ``prompt_THW[:, out_t]`` in place (reference :223) and returns
@@ -554,6 +554,10 @@ class STMaskGIT(nn.Module):
         guidance: a ``Guidance(scale, null_action)`` (1xgpt_amd/sampling.py) or None: classifier-free guidance of an action-conditioned
         model -- every forward runs the clips twice, under their actions and under the null action, and the law is applied to
         scale * conditional + (1 - scale) * null; the returned step-0 logits are the guided ones.
+        known: optional (B, H, W) int64 known tokens of the frame (generate.known_tokens): a value in [0, image_vocab_size) is kept,
+        ``mask_token_id`` (any other value) is generated.  The prompt's frame ``out_t`` is still passed all-mask; each clip re-masks by
+        its own count of tokens left to generate; the step-0 logits at known positions are the model's logits there, as for any
+        unmasked input token.  The reference has no counterpart (it asserts an all-mask frame, st_mask_git.py:155).
         """
         mode = unmask_code(unmask_mode)
         law = as_struct(sampling)
@@ -572,6 +576,8 @@ class STMaskGIT(nn.Module):
             raise RuntimeError(f"maskgit_generate expects a (B, T={self.config.T}, H, W) prompt, got {tuple(prompt_THW.shape)}")
         S, V = self.config.S, self.config.factored_vocab_size * self.config.num_factored_vocabs
         dev = prompt.device
+        from .generate import check_known
+        known = check_known(known, (B, self.h, self.w), dev)
         cond = self._cond(action_ids, B, action_vectors=action_vectors)
         ws = self._workspace(B, guided=guide is not None)
         if unmask_mode != "greedy" and maskgit_steps > 1:
@@ -592,8 +598,8 @@ class STMaskGIT(nn.Module):
         status = torch.zeros(1, dtype=torch.int32, device=dev) if check else None
         if mode == _lib.UNMASK_CONFIDENCE and law is None:
             law = as_struct(SamplingConfig())
-        rc = _lib.call_guided(
-            lib, "genie_maskgit_generate", cond, law, guide, cfg, w, prompt.data_ptr(), B, int(out_t), int(maskgit_steps), float(temperature),
+        rc = _lib.call_known(
+            lib, "genie_maskgit_generate", cond, law, guide, _lib.make_known(known, 1, S), cfg, w, prompt.data_ptr(), B, int(out_t), int(maskgit_steps), float(temperature),
             mode,
             0 if noise is None else noise.data_ptr(), 0 if uniforms is None else uniforms.data_ptr(),
             samples.data_ptr(), 0 if logits0 is None else logits0.data_ptr(), _lib.LAYOUT_BCTHW,
@@ -694,13 +700,15 @@ class STMaskGIT(nn.Module):
 
     def rollout(self, prompt_BPHW, n_new, keep=None, **kwargs):
         """n_new frames behind the prompt frames (B, P, H, W), past the window T if need be -> (B, P + n_new, H, W): generate.rollout_frames
-        (one library call; the window slides by T - keep frames, re-running the last `keep` as its context)."""
+        (one library call; the window slides by T - keep frames, re-running the last `keep` as its context; known=(B, n_new, H, W)
+        keeps given tokens of the generated frames)."""
         from .generate import rollout_frames
         return rollout_frames(self, prompt_BPHW, n_new, keep=keep, **kwargs)
 
     def fanout(self, prompt_BPHW, n_new, K=None, **kwargs):
         """K candidate futures of n_new frames per prompt (B, P, H, W) -> (B, K, n_new, H, W) over one shared context cache:
-        generate.fanout_frames (one library call, in-window: P + n_new <= T)."""
+        generate.fanout_frames (one library call, in-window: P + n_new <= T; known=(B, K, n_new, H, W) or (B, n_new, H, W) keeps given
+        tokens of the new frames)."""
         from .generate import fanout_frames
         return fanout_frames(self, prompt_BPHW, n_new, K=K, **kwargs)
 

@@ -673,6 +673,76 @@ int genie_score_fanout(const genie_cfg* cfg, const genie_weights* w, const int64
                        double* nll, double* hits, float* token_nll, float* trunk, size_t trunk_bytes, float* branch, size_t branch_bytes,
                        void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond);
 
+/* ---- known tokens: inpainting through every MaskGIT decode loop (ABI 3 addition; reference counterpart: none -- st_mask_git.py:155
+ * asserts the opposite, that the frame being decoded is all-mask) ---------------------------------------------------------------------
+ * Some tokens of a frame are given and only the rest are generated: a partial observation, a counterfactual edit of a region, a crop to
+ * complete.  `known` is shaped like the frames a call decodes.  A value v with 0 <= v < image_vocab_size is a known token; ANY other value
+ * (image_vocab_size, the mask id, is the conventional one) marks a token to generate.  Values are never inspected on the host.
+ * For one frame of clip b let K_b be its number of known tokens and M_b = S - K_b.
+ *   1. Start: the frame's current tokens are the known tokens and the mask id elsewhere; unmasked[b, s] = 1 exactly where a token is known.
+ *   2. Each step: the pass runs on the current tokens and all S rows are sampled as without known tokens -- noise and uniforms keep their
+ *      shapes; draws at known positions have no effect on any output.
+ *   3. Mask step of a non-final step: unmasked tokens carry key +inf; n_b = ceil(frac(step) * M_b) with
+ *      frac(step) = cos(pi/2 * (step + 1) / steps), computed once on the host in double (genie_mask_fraction, the expression of the
+ *      all-mask count) and passed to the kernel, which performs the double multiply and the ceil: host and device agree bit for bit.  The
+ *      n_b still-masked tokens of lowest stable rank are re-masked, the rest become unmasked.  K_b = 0 gives the count of genie_mask_step's
+ *      callers exactly, ceil(frac * S).  A clip's schedule does not depend on the other clips of its batch.
+ *   4. Final step: every still-masked token takes its sample.  The final tokens equal `known` at every known position and never contain
+ *      the mask id.
+ *   5. A fully known frame (M_b = 0) is legal: its passes still run (the other clips need them, and the slot is committed); its output is
+ *      `known`.
+ *   6. Merged commits: whenever the two-frame pass of a commit opens slot t (the pending-slot commit of a resumed rollout included), its
+ *      second frame carries the start tokens of slot t by rule 1 instead of all-mask.
+ *   7. Guidance: both halves of every pass see the same tokens, known ones included.
+ *   8. logits0_out rows at known positions are the model's logits at those positions, as for any unmasked input token.
+ * genie_known_begin: rule 1 for one frame of B clips in one launch: frame rows b (and b + B when copies == 2) at clip stride
+ *   frame_clip_stride, and unmasked (B, S) unless NULL.  A token is known when 0 <= known[b * known_clip_stride + s] < mask_id.
+ * genie_mask_step_known: genie_mask_step with the count of rule 3 per clip; known == NULL means M_b = S for every clip.  One block per
+ *   clip counts K_b from the clip's known row each step (8 S bytes; the loops' workspace holds no new buffer), S <= 8192.
+ * The four loops: the arguments of the widest existing variant plus a trailing genie_known*.  NULL is that variant itself.  Otherwise
+ *   ids == NULL or a clip_stride below (frames the call decodes) * S is GENIE_E_ARG before anything is enqueued.  Sizes of cache, trunk,
+ *   branch and workspace are those of the variant.
+ *   genie_maskgit_generate_known: the frame is out_t (j = 0); prompt[:, out_t:] must still be all-mask on entry (same device check); the
+ *     call lays the known tokens itself.  samples_out equals the final prompt frame.
+ *   genie_generate_cached_known: j counts the n_new frames.  Under teacher_force_time the committed tokens are the ground truth of `ids`
+ *     as before; gen_out still keeps `known`.
+ *   genie_rollout_cached_known: j = f - f0, the frames of THIS call, like noise and uniforms.
+ *   genie_generate_fanout_known: rows are the B * K branches, row b * K + k.
+ * Tests: tests/test_inpaint_cpu.py, tests/test_hip_inpaint.py. */
+typedef struct genie_known {
+    const int64_t* ids;  /* device; token s of the call's j-th decoded frame of clip b: ids[b*clip_stride + j*S + s] */
+    int64_t clip_stride; /* elements, >= (frames the call decodes) * S */
+} genie_known;
+/* sizeof(genie_known) and the offsets of its two fields, in declaration order: writes min(n, 3) entries, returns 3. */
+int genie_known_layout(size_t* out_host, int n);
+/* cos(pi/2 * (step + 1) / steps): the host double the loops pass to genie_mask_step_known (0 when steps < 1). */
+double genie_mask_fraction(int step, int steps);
+int genie_known_begin(const int64_t* known, int64_t known_clip_stride, int64_t mask_id, int64_t* frame, int64_t frame_clip_stride,
+                      uint8_t* unmasked /* (B,S) or NULL */, int B, int S, int copies, void* stream);
+int genie_mask_step_known(const float* keys, double frac, int last_step, int64_t mask_id, const int64_t* known, int64_t known_clip_stride,
+                          uint8_t* unmasked, int64_t* samples, int64_t* prompt_frame, int64_t prompt_clip_stride, int B, int S, void* stream);
+int genie_maskgit_generate_known(const genie_cfg* cfg, const genie_weights* w, int64_t* prompt, int B, int out_t, int steps,
+                                 float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                                 int64_t* samples_out, float* logits0_out, int layout, int32_t* status_flag,
+                                 void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond,
+                                 const genie_sampling* sampling, const genie_guidance* guidance, const genie_known* known);
+int genie_generate_cached_known(const genie_cfg* cfg, const genie_weights* w, const int64_t* ids, int B, int P, int n_new,
+                                int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                                int teacher_force_time, int merge_commit, int64_t* gen_out, float* logits0_out, float* cache,
+                                size_t cache_bytes, void* workspace, size_t workspace_bytes, void* stream,
+                                const genie_frame_cond* cond, const genie_sampling* sampling, const genie_guidance* guidance,
+                                const genie_known* known);
+int genie_rollout_cached_known(const genie_cfg* cfg, const genie_weights* w, int64_t* frames, int B, int P, int keep, int cap, int f0,
+                               int f1, int resume, int steps, float temperature, int unmask_mode, const float* noise,
+                               const float* uniforms, int merge_commit, float* cache, size_t cache_bytes, void* workspace,
+                               size_t workspace_bytes, void* stream, const genie_frame_cond* cond, const genie_sampling* sampling,
+                               const genie_guidance* guidance, const genie_known* known);
+int genie_generate_fanout_known(const genie_cfg* cfg, const genie_weights* w, const int64_t* ids, int B, int K, int P, int n_new,
+                                int steps, float temperature, int unmask_mode, const float* noise, const float* uniforms,
+                                int merge_commit, int64_t* gen_out, float* trunk, size_t trunk_bytes, float* branch, size_t branch_bytes,
+                                void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond,
+                                const genie_sampling* sampling, const genie_guidance* guidance, const genie_known* known);
+
 /* ---- optional per-launch timing (bench.py's roofline leg) ------------------------------------------------
  * When enabled, every launch of a kernel whose class bit is set in `class_mask` is bracketed by a pair of
  * HIP events recorded on the launch stream.  genie_profile_read synchronises those events and returns, for

@@ -11,7 +11,10 @@ re-runs the last --keep frames as its context); the output is then [prompt | N g
 --fanout K generates K candidate futures of the example over one shared context cache (in-window; branches differ by their sampling
 draws and, for an action-conditioned model, by the (K, n_new) action ids of --fanout_actions); branch k is written to OUTPUT_DIR/branch_k.
 --score generates nothing: it prints the negative log-likelihood of each observed frame behind the prompt (score_frames), one row per
-action hypothesis of --fanout_actions (or the example's own actions)."""
+action hypothesis of --fanout_actions (or the example's own actions).
+--known_box top,left,height,width (token coordinates) inpaints: every generated frame keeps the ground-truth tokens of that box and the
+model fills in the rest, consistent with them.  With --teacher_force_time this is the edit: the observed clip is the context and only
+the tokens outside the box are regenerated; it also works with --num_new_frames (inside the example's frames) and --fanout."""
 import argparse
 import importlib
 import os
@@ -61,7 +64,28 @@ def build_parser():
                     help="Generate nothing: print the per-frame negative log-likelihood of the example's observed frames behind the prompt "
                          "(score_frames). On an action-conditioned model --fanout_actions scores K hypotheses (K rows of ids) and names the "
                          "likeliest; without it the example's own actions are scored.")
+    ap.add_argument("--known_box", type=str, default=None, metavar="TOP,LEFT,HEIGHT,WIDTH",
+                    help="Keep the ground-truth tokens of this box (token coordinates) in every generated frame and generate only the rest "
+                         "(inpainting). Works with and without --teacher_force_time.")
     return ap
+
+
+def known_box(args, model, ex, G, N):
+    """--known_box: the (1, N, H, W) known tokens of the N frames behind the prompt, or None without the flag."""
+    if args.known_box is None:
+        return None
+    try:
+        top, left, height, width = (int(v) for v in args.known_box.split(","))
+    except ValueError:
+        sys.exit(f"generate.py: --known_box wants top,left,height,width, got {args.known_box!r}")
+    if not (0 <= top and 0 <= left and height >= 1 and width >= 1 and top + height <= model.h and left + width <= model.w):
+        sys.exit(f"generate.py: --known_box {args.known_box} does not lie inside the {model.h} x {model.w} token grid")
+    P = args.num_prompt_frames
+    if P + N > ex.shape[1]:
+        sys.exit(f"generate.py: --known_box keeps ground-truth tokens, and the example has {ex.shape[1] - P} frames behind the prompt, not {N}")
+    keep = torch.zeros(model.h, model.w, dtype=torch.bool, device=ex.device)
+    keep[top:top + height, left:left + width] = True
+    return G.known_tokens(ex[:, P:P + N], keep, model.mask_token_id)
 
 
 def score_main(args, model, ex, actions, G):
@@ -99,7 +123,7 @@ def fanout_main(args, model, ex, actions, meta, sampling, guidance, G):
             sys.exit(f"generate.py: --fanout_actions holds {ids.shape} ids, expected ({K}, {N})")
         kw = dict(action_ids=torch.from_numpy(ids)[None].to("cuda"), prompt_actions=actions[:, :P].to("cuda"))
     out = G.fanout_frames(model, ex[:, :P], N, K=K, maskgit_steps=args.maskgit_steps, temperature=args.temperature,
-                          unmask_mode=args.unmask_mode, sampling=sampling, guidance=guidance, **kw)
+                          unmask_mode=args.unmask_mode, sampling=sampling, guidance=guidance, known=known_box(args, model, ex, G, N), **kw)
     for k in range(K):
         frames = torch.cat([ex[:, :P], out[:, k], ex[:, P:]], dim=1)
         print(G.write_outputs(frames, os.path.join(args.output_dir, f"branch_{k}"), meta, vars(args)))
@@ -138,6 +162,8 @@ def main():
             sys.exit(f"generate.py: --adapter {args.adapter}: {e}")
     ex = example.to("cuda").view(1, args.window_size, model.h, model.w)
     if args.score:
+        if args.known_box is not None:
+            sys.exit("generate.py: --score has no --known_box (scoring conditional on known tokens is not supported)")
         return score_main(args, model, ex, actions, G)
     if args.fanout is not None:
         return fanout_main(args, model, ex, actions, meta, sampling, guidance, G)
@@ -149,13 +175,13 @@ def main():
             sys.exit(f"generate.py: {P} + {N} frames need as many actions, the example has {actions.shape[1]}: raise --window_size")
         out = G.rollout_frames(model, ex[:, :P], N, keep=args.keep, maskgit_steps=args.maskgit_steps, temperature=args.temperature,
                                unmask_mode=args.unmask_mode, action_ids=None if actions is None else actions[:, :P + N].to("cuda"),
-                               sampling=sampling, guidance=guidance)
+                               sampling=sampling, guidance=guidance, known=known_box(args, model, ex, G, N))
         print(G.write_outputs(torch.cat([out, ex[:, P:]], dim=1), args.output_dir, meta, vars(args)))
         return
     fn = G.generate_frames_cached if args.schedule == "kv_cache" else G.generate_frames
     out = fn(model, ex, args.num_prompt_frames, args.maskgit_steps, args.temperature, args.teacher_force_time,
              action_ids=None if actions is None else actions.to("cuda"), sampling=sampling, unmask_mode=args.unmask_mode,
-             guidance=guidance)
+             guidance=guidance, known=known_box(args, model, ex, G, args.window_size - args.num_prompt_frames))
     print(G.write_outputs(out, args.output_dir, meta, vars(args)))
 
 
