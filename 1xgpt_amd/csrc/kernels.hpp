@@ -233,15 +233,6 @@ int launch_layer_norm_split(const float* x, const float* g, const float* b, uint
                             float eps, hipStream_t st);
 int launch_split_f16(const float* src, uint16_t* dst, size_t plane, size_t n, hipStream_t st);
 int launch_transpose(const float* in, float* out, int batch, int rows, int cols, hipStream_t st);
-int launch_count_equal(const int64_t* a, long sa, const int64_t* b, long sb, int batch, long n, const double* ce3, double* sums6,
-                       double n_tokens, double n_frames, double n_clips, hipStream_t st);
-int launch_factored_ce(const genie_cfg& c, const float* logits, int layout, const int64_t* targets,
-                       const int64_t* weight_ids, int B, int t0, int t1, double* sums, hipStream_t st);
-// per-row NLL of one frame's token-major (N, S, V) logits: row i against the S targets at targets + (i / K) * target_clip_stride.
-// nll / hits: f64, row i at [i * nll_stride] (hits may be NULL); token_nll: NULL or f32, row i at [i * token_stride + s].  Fixed-order
-// f64 reduction inside the workgroup, no atomics.
-int launch_score_rows(const genie_cfg& c, const float* logits, const int64_t* targets, long target_clip_stride, int K, long N, double* nll,
-                      long nll_stride, double* hits, float* token_nll, long token_stride, hipStream_t st);
 int launch_sample(const genie_cfg& c, const float* logits, int layout, int B, float temperature,
                   const float* uniforms, int64_t* samples, float* conf, hipStream_t st);
 // kernels_sample.hip: the tempered / top-k / top-p filtered law (genie_sampling); NULL or all-off without keys_out = launch_sample
@@ -292,6 +283,35 @@ int launch_gemm_bf16_out16(const uint16_t* A16, const uint16_t* W16, const float
                            hipStream_t st);
 int launch_pack_bf16(const float* src, uint16_t* dst, size_t n, hipStream_t st);
 
+// ---- loss and scoring (kernels_loss.hip; the contract of each loss heads that file) ----
+int launch_count_equal(const int64_t* a, long sa, const int64_t* b, long sb, int batch, long n, const double* ce3, double* sums6,
+                       double n_tokens, double n_frames, double n_clips, hipStream_t st);
+int launch_factored_ce(const genie_cfg& c, const float* logits, int layout, const int64_t* targets,
+                       const int64_t* weight_ids, int B, int t0, int t1, double* sums, hipStream_t st);
+// per-row NLL of one frame's token-major (N, S, V) logits: row i against the S targets at targets + (i / K) * target_clip_stride.
+// nll / hits: f64, row i at [i * nll_stride] (hits may be NULL); token_nll: NULL or f32, row i at [i * token_stride + s].  Fixed-order
+// f64 reduction inside the workgroup, no atomics.
+int launch_score_rows(const genie_cfg& c, const float* logits, const int64_t* targets, long target_clip_stride, int K, long N, double* nll,
+                      long nll_stride, double* hits, float* token_nll, long token_stride, hipStream_t st);
+// the training losses on (n_clips, T, S) tokens of nfac factors of vf logits, d logits in place; each is its count kernel, then its loss
+// kernel, into sums the caller zeroed.  Neutral step: three sums.
+int launch_ce_fwd_bwd(const genie_cfg& c, float* logits, const int64_t* ids, const int64_t* labels, int B, double* sums,
+                      hipStream_t st);
+// the general objective (label smoothing, z-loss, per-frame weights; include/genie_hip.h, "Training objective"): five sums.  `obj` was
+// checked by the caller (objective_ok in train_api.hip).
+int launch_ce_objective(float* logits, const int64_t* ids, const int64_t* labels, long n_clips, int T, int S, int vf, int nfac,
+                        int64_t mask_id, const genie_objective& obj, double* sums, hipStream_t st);
+// ... with a read-only row of teacher logits beside every student row (include/genie_hip.h, "Distillation"): seven sums.  obj, alpha,
+// tau were checked by the caller.
+int launch_ce_distill(float* logits, const float* teacher, const int64_t* ids, const int64_t* labels, long n_clips, int T, int S,
+                      int vf, int nfac, int64_t mask_id, const genie_objective& obj, float alpha, float tau, double* sums,
+                      hipStream_t st);
+// the loss launch of a training call: zeroes the 3 / 5 / 7 sums (a failure is reported under `fn`), then one of the three above --
+// ds (non-neutral distillation of `teacher`), else obj (a struct), else (both NULL) the neutral step
+int launch_train_loss(const char* fn, float* logits, const int64_t* ids, const int64_t* labels, long n_clips, int T, int S, int vf,
+                      int nfac, int64_t mask_id, const genie_objective* obj, const genie_distill* ds, const float* teacher, double* sums,
+                      hipStream_t st);
+
 // ---- training step (kernels_train.hip) ----
 // C[b1][b2][M,N] = alpha * A.B (+bias) (+R); ta/tb: operand stored k-major; nsplit > 1: slabs C + s*sCsplit
 int launch_gemm_f32_gen(bool ta, bool tb, const float* A, long lda, long sA1, long sA2, const float* W, long ldw, long sW1,
@@ -308,27 +328,6 @@ int launch_ln_bwd(const float* x, const float* gamma, const float* dy, float* dx
                   long rows, int C, float eps, float beta, float* part, hipStream_t st);
 int launch_gelu_fwd(const float* z, float* h, size_t n, hipStream_t st);
 int launch_gelu_bwd(const float* z, float* g, size_t n, hipStream_t st);
-int launch_ce_fwd_bwd(const genie_cfg& c, float* logits, const int64_t* ids, const int64_t* labels, int B, double* sums,
-                      hipStream_t st);
-// the general objective (label smoothing, z-loss, per-frame weights; include/genie_hip.h, "Training objective") on (n_clips, T, S)
-// tokens of nfac factors of vf logits: five sums, d logits in place.  `obj` was checked by the caller (objective_ok in train_api.hip).
-int launch_ce_objective(float* logits, const int64_t* ids, const int64_t* labels, long n_clips, int T, int S, int vf, int nfac,
-                        int64_t mask_id, const genie_objective& obj, double* sums, hipStream_t st);
-// the per-frame loss weights as the loss kernels take them (by value in the kernel arguments: no copy, no sync), and the launch that
-// counts the counted tokens per frame: sums[2] = W = sum_t w_t c_t, sums[4] = n = sum_t c_t
-struct FrameWeights {
-    float w[64];
-    int n;   // frames t >= n weigh 1 (n = 0: every frame)
-    __device__ __forceinline__ float at(int t) const { return t < n ? w[t] : 1.0f; }
-};
-FrameWeights frame_weights_of(const genie_objective& obj);
-int launch_count_frames(const int64_t* ids, long n_clips, int T, int S, int64_t mask_id, const FrameWeights& fw, double* sums,
-                        hipStream_t st);
-// kernels_distill.hip: launch_ce_objective with a read-only row of teacher logits beside every student row (include/genie_hip.h,
-// "Distillation"): count_frames, then the distillation kernel; seven sums, d logits in place.  obj, alpha, tau were checked by the caller.
-int launch_ce_distill(float* logits, const float* teacher, const int64_t* ids, const int64_t* labels, long n_clips, int T, int S,
-                      int vf, int nfac, int64_t mask_id, const genie_objective& obj, float alpha, float tau, double* sums,
-                      hipStream_t st);
 int launch_embed_bwd(const genie_cfg& c, const float* dx, const int64_t* ids, int B, float* dpos, float* dmask,
                      float* const* tables_host, float beta, float* colpart, hipStream_t st);
 // gradient of the action table: d_table[k] = sum over frames (b, t) with act_ids[b, t] == k (ascending) of sum_s dx[b, t, s, :];

@@ -1,5 +1,5 @@
 // Exact-precision (f32) kernels of the GENIE path for gfx950: embedding gather, LayerNorm, the f32-MFMA
-// "NT" GEMM with fused bias / erf-GELU / residual epilogue, the generic strided attention, factored CE,
+// "NT" GEMM with fused bias / erf-GELU / residual epilogue, the generic strided attention,
 // MaskGIT sampling and mask step, layout transposes.  Every kernel cites the reference op it replaces.
 #include <type_traits>
 
@@ -862,306 +862,6 @@ int launch_transpose(const float* in, float* out, int batch, int rows, int cols,
     dim3 grid((cols + 31) / 32, (rows + 31) / 32, batch), block(32, 8);
     transpose_kernel<<<grid, block, 0, st>>>(in, out, rows, cols);
     GENIE_LAUNCH_CHECK("transpose");
-    return GENIE_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// a12  factored cross-entropy + "all factors argmax-correct" (st_mask_git.py:231-253, eval_utils.py:72-77)
-// token-major: one wavefront per token (V contiguous, 2 KB per factor, coalesced).
-// BCTHW: one lane per token, 64 consecutive tokens per wave, loop over the vocab (coalesced across lanes).
-// Partial sums go to 3 doubles with one atomicAdd per block.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void block_accumulate3(double ce, double hit, double cnt, double* sums) {
-    __shared__ double red[3][4];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        ce += __shfl_xor(ce, o);
-        hit += __shfl_xor(hit, o);
-        cnt += __shfl_xor(cnt, o);
-    }
-    if (lane == 0) { red[0][wid] = ce; red[1][wid] = hit; red[2][wid] = cnt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0, b = 0, c = 0;
-        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) { a += red[0][w]; b += red[1][w]; c += red[2][w]; }
-        if (c != 0.0) { atomicAdd(&sums[0], a); atomicAdd(&sums[1], b); atomicAdd(&sums[2], c); }
-    }
-}
-
-// logits token-major (B, nt, S, V): token index n = (b*nt + tt)*S + s
-__global__ __launch_bounds__(256) void ce_token_major_kernel(const float* __restrict__ logits,
-                                                             const int64_t* __restrict__ targets,
-                                                             const int64_t* __restrict__ weight_ids, long n_tok,
-                                                             int nt, int S, int T, int t0, int vf, int nfac,
-                                                             int64_t mask_id, double* sums) {
-    const int lane = threadIdx.x & 63;
-    double ce = 0, hit = 0, cnt = 0;
-    // grid-stride over tokens: the three f64 atomics per block all land on the same addresses (~6 ns each at the L2), so one
-    // block per four tokens made the atomics, not the 4 KB of logits per token, the kernel's time (1.2 ms for 246 k tokens)
-    for (long n = (long)blockIdx.x * 4 + (threadIdx.x >> 6); n < n_tok; n += (long)gridDim.x * 4) {
-        long b = n / ((long)nt * S);
-        long rem = n - b * (long)nt * S;
-        long gi = (b * T + t0) * (long)S + rem;  // index into the full (B,T,S) clip
-        bool counted = weight_ids ? (weight_ids[gi] == mask_id) : true;
-        if (counted) {
-            int64_t tgt = targets[gi];
-            const float* lp = logits + (size_t)n * vf * nfac;
-            float loss = 0.f;
-            bool all_ok = true;
-            if (vf == 512 && nfac == 2) {
-                // the shipped vocabulary (2 x 512): a lane owns 8 consecutive logits of each factor -- all four 16-byte loads of the
-                // token are in flight before the first use (the strided dword loop below waited on a memory round trip per 64 logits:
-                // 1.2 ms for 1 GB of logits, 0.45 TB/s).  Same arithmetic: first-max-wins argmax, sum of expf(v - max), logf.
-                typedef float ce4 __attribute__((ext_vector_type(4)));
-                ce4 v[2][2];
-#pragma unroll
-                for (int f = 0; f < 2; ++f)
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) v[f][q] = *reinterpret_cast<const ce4*>(lp + f * 512 + lane * 8 + q * 4);
-#pragma unroll
-                for (int f = 0; f < 2; ++f) {
-                    const int tf = (int)(tgt % 512);
-                    tgt /= 512;
-                    float mx = -INFINITY;
-                    int mi = 0;
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const float x = v[f][q >> 2][q & 3];
-                        if (x > mx) { mx = x; mi = lane * 8 + q; }
-                    }
-                    wave_argmax(mx, mi);
-                    float se = 0.f;
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) se += expf(v[f][q >> 2][q & 3] - mx);
-                    se = wave_sum(se);
-                    // the target's logit sits in lane tf / 8, slot tf % 8
-                    float tv = 0.f;
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) tv = (tf & 7) == q ? v[f][q >> 2][q & 3] : tv;
-                    tv = __shfl(tv, tf >> 3);
-                    loss += (logf(se) + mx) - tv;
-                    all_ok = all_ok && (mi == tf);
-                }
-            } else
-            for (int f = 0; f < nfac; ++f) {
-                int tf = (int)(tgt % vf);
-                tgt /= vf;
-                float mx = -INFINITY;
-                int mi = 0;
-                for (int k = lane; k < vf; k += 64) {
-                    float v = lp[f * vf + k];
-                    if (v > mx) { mx = v; mi = k; }
-                }
-                wave_argmax(mx, mi);
-                float se = 0.f;
-                for (int k = lane; k < vf; k += 64) se += expf(lp[f * vf + k] - mx);
-                se = wave_sum(se);
-                loss += (logf(se) + mx) - lp[f * vf + tf];
-                all_ok = all_ok && (mi == tf);
-            }
-            if (lane == 0) { ce += loss; hit += all_ok ? 1.0 : 0.0; cnt += 1.0; }
-        }
-    }
-    block_accumulate3(ce, hit, cnt, sums);
-}
-
-// logits BCTHW (B, V, nt, S): element (b, v, tt, s) at ((b*V + v)*nt + tt)*S + s
-__global__ __launch_bounds__(256) void ce_bcthw_kernel(const float* __restrict__ logits,
-                                                       const int64_t* __restrict__ targets,
-                                                       const int64_t* __restrict__ weight_ids, long n_tok, int nt,
-                                                       int S, int T, int t0, int vf, int nfac, int64_t mask_id,
-                                                       double* sums) {
-    long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    double ce = 0, hit = 0, cnt = 0;
-    if (n < n_tok) {
-        long b = n / ((long)nt * S);
-        long rem = n - b * (long)nt * S;  // tt*S + s
-        long gi = (b * T + t0) * (long)S + rem;
-        bool counted = weight_ids ? (weight_ids[gi] == mask_id) : true;
-        if (counted) {
-            int64_t tgt = targets[gi];
-            const long vstride = (long)nt * S;
-            const float* lp = logits + (size_t)b * vf * nfac * vstride + rem;
-            float loss = 0.f;
-            bool all_ok = true;
-            for (int f = 0; f < nfac; ++f) {
-                int tf = (int)(tgt % vf);
-                tgt /= vf;
-                const float* lf = lp + (size_t)f * vf * vstride;
-                float mx = -INFINITY;
-                int mi = 0;
-                for (int k = 0; k < vf; ++k) {
-                    float v = lf[(size_t)k * vstride];
-                    if (v > mx) { mx = v; mi = k; }
-                }
-                float se = 0.f;
-                for (int k = 0; k < vf; ++k) se += expf(lf[(size_t)k * vstride] - mx);
-                loss += (logf(se) + mx) - lf[(size_t)tf * vstride];
-                all_ok = all_ok && (mi == tf);
-            }
-            ce = loss; hit = all_ok ? 1.0 : 0.0; cnt = 1.0;
-        }
-    }
-    block_accumulate3(ce, hit, cnt, sums);
-}
-
-// sampled-token accuracy numerator of the evaluator (evaluate.py:176-179: (samples == ground truth).sum()): a (batch, n) view
-// with batch stride `sa` against b (batch, n) with stride `sb`; the count is ADDED to sums6[2].  Block 0 also files the rest
-// of the metric vector: sums6 = [sum CE, n CE tokens, hits, n tokens, n frames, n clips] with the CE pair taken from the
-// 3-vector genie_factored_ce accumulated (ce3 = [sum CE, sum argmax-correct, n]; NULL = leave sums6[0..1] alone).
-__global__ __launch_bounds__(256) void count_equal_kernel(const int64_t* __restrict__ a, long sa, const int64_t* __restrict__ b,
-                                                          long sb, long n, long total, const double* __restrict__ ce3,
-                                                          double* sums6, double n_tokens, double n_frames, double n_clips) {
-    __shared__ int wsum[4];
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    int hit = 0;
-    if (i < total) {
-        const long bi = i / n, r = i - bi * n;
-        hit = a[bi * sa + r] == b[bi * sb + r];
-    }
-    const unsigned long long m = __ballot(hit);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int c = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        if (c) atomicAdd(&sums6[2], (double)c);  // integer-valued addends: the f64 sum is exact in any order
-        if (blockIdx.x == 0) {
-            if (ce3) { sums6[0] = ce3[0]; sums6[1] = ce3[2]; }
-            sums6[3] = n_tokens; sums6[4] = n_frames; sums6[5] = n_clips;
-        }
-    }
-}
-int launch_count_equal(const int64_t* a, long sa, const int64_t* b, long sb, int batch, long n, const double* ce3, double* sums6,
-                       double n_tokens, double n_frames, double n_clips, hipStream_t st) {
-    const long total = (long)batch * n;
-    if (total <= 0) return GENIE_OK;
-    count_equal_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(a, sa, b, sb, n, total, ce3, sums6, n_tokens, n_frames,
-                                                                        n_clips);
-    GENIE_LAUNCH_CHECK("count_equal");
-    return GENIE_OK;
-}
-
-int launch_factored_ce(const genie_cfg& c, const float* logits, int layout, const int64_t* targets,
-                       const int64_t* weight_ids, int B, int t0, int t1, double* sums, hipStream_t st) {
-    int nt = t1 - t0;
-    long n_tok = (long)B * nt * c.S;
-    if (n_tok <= 0) return GENIE_OK;
-    if (layout == GENIE_LAYOUT_TOKEN_MAJOR) {
-        const long blocks_all = (n_tok + 3) / 4;
-        ce_token_major_kernel<<<(unsigned)(blocks_all < 2048 ? blocks_all : 2048), 256, 0, st>>>(
-            logits, targets, weight_ids, n_tok, nt, c.S, c.T, t0, c.factored_vocab, c.num_factored,
-            (int64_t)c.image_vocab_size, sums);
-    } else {
-        ce_bcthw_kernel<<<(unsigned)((n_tok + 255) / 256), 256, 0, st>>>(
-            logits, targets, weight_ids, n_tok, nt, c.S, c.T, t0, c.factored_vocab, c.num_factored,
-            (int64_t)c.image_vocab_size, sums);
-    }
-    GENIE_LAUNCH_CHECK("factored_ce");
-    return GENIE_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Per-row negative log-likelihood of observed tokens (genie_score_logits / genie_score_fanout): the per-token loss of
-// ce_token_major_kernel, kept apart per row instead of summed over the batch.  Row i of the token-major (N, S, V) logits of ONE frame
-// is scored against the S targets at targets + (i / K) * target_clip_stride: the K branches of a clip share their parent's tokens.
-// One workgroup per row, one wave per token; wave w takes tokens w, w + nw, ... and keeps its own f64 partial, and thread 0 adds the nw
-// partials in wave order -- a fixed order and no atomics, so two launches give the same bits.
-// The token's arithmetic is ce_token_major_kernel's, restated here so that kernel's code stays as it is.
-// ------------------------------------------------------------------------------------------------
-#define GENIE_SCORE_MAX_WAVES 16
-__device__ __forceinline__ float score_token(const float* __restrict__ lp, uint64_t tgt, int vf, int nfac, int lane, bool& all_ok) {
-    float loss = 0.f;
-    all_ok = true;
-    if (vf == 512 && nfac == 2) {
-        // 2 x 512: a lane owns 8 consecutive logits of each factor; the four 16-byte loads are in flight before the first use
-        typedef float sc4 __attribute__((ext_vector_type(4)));
-        sc4 v[2][2];
-#pragma unroll
-        for (int f = 0; f < 2; ++f)
-#pragma unroll
-            for (int q = 0; q < 2; ++q) v[f][q] = *reinterpret_cast<const sc4*>(lp + f * 512 + lane * 8 + q * 4);
-#pragma unroll
-        for (int f = 0; f < 2; ++f) {
-            const int tf = (int)(tgt % 512);
-            tgt /= 512;
-            float mx = -INFINITY;
-            int mi = 0;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const float x = v[f][q >> 2][q & 3];
-                if (x > mx) { mx = x; mi = lane * 8 + q; }
-            }
-            wave_argmax(mx, mi);
-            float se = 0.f;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) se += expf(v[f][q >> 2][q & 3] - mx);
-            se = wave_sum(se);
-            float tv = 0.f;   // the target's logit sits in lane tf / 8, slot tf % 8
-#pragma unroll
-            for (int q = 0; q < 8; ++q) tv = (tf & 7) == q ? v[f][q >> 2][q & 3] : tv;
-            tv = __shfl(tv, tf >> 3);
-            loss += (logf(se) + mx) - tv;
-            all_ok = all_ok && (mi == tf);
-        }
-        return loss;
-    }
-    for (int f = 0; f < nfac; ++f) {
-        const int tf = (int)(tgt % (uint64_t)vf);
-        tgt /= (uint64_t)vf;
-        float mx = -INFINITY;
-        int mi = 0;
-        for (int k = lane; k < vf; k += 64) {
-            const float v = lp[f * vf + k];
-            if (v > mx) { mx = v; mi = k; }
-        }
-        wave_argmax(mx, mi);
-        float se = 0.f;
-        for (int k = lane; k < vf; k += 64) se += expf(lp[f * vf + k] - mx);
-        se = wave_sum(se);
-        loss += (logf(se) + mx) - lp[f * vf + tf];
-        all_ok = all_ok && (mi == tf);
-    }
-    return loss;
-}
-
-__global__ __launch_bounds__(64 * GENIE_SCORE_MAX_WAVES) void score_rows_kernel(const float* __restrict__ logits,
-                                                                                const int64_t* __restrict__ targets, long target_clip_stride,
-                                                                                int K, int S, int vf, int nfac, double* __restrict__ nll,
-                                                                                long nll_stride, double* __restrict__ hits,
-                                                                                float* __restrict__ token_nll, long token_stride) {
-    __shared__ double red[2][GENIE_SCORE_MAX_WAVES];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const long row = blockIdx.x;
-    const int64_t* tg = targets + (row / K) * target_clip_stride;
-    const float* lrow = logits + (size_t)row * S * vf * nfac;
-    double acc = 0, hit = 0;
-    for (int s = wid; s < S; s += nw) {
-        bool ok;
-        const float loss = score_token(lrow + (size_t)s * vf * nfac, (uint64_t)tg[s], vf, nfac, lane, ok);
-        acc += (double)loss;
-        hit += ok ? 1.0 : 0.0;
-        if (token_nll && lane == 0) token_nll[row * token_stride + s] = loss;
-    }
-    if (lane == 0) { red[0][wid] = acc; red[1][wid] = hit; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0, h = 0;
-        for (int w = 0; w < nw; ++w) { a += red[0][w]; h += red[1][w]; }
-        nll[row * nll_stride] = a;
-        if (hits) hits[row * nll_stride] = h;
-    }
-}
-
-int launch_score_rows(const genie_cfg& c, const float* logits, const int64_t* targets, long target_clip_stride, int K, long N, double* nll,
-                      long nll_stride, double* hits, float* token_nll, long token_stride, hipStream_t st) {
-    if (N <= 0) return GENIE_OK;
-    GENIE_CHECK_SHAPE(N <= 0x7fffffffL, "score_rows: %ld rows", N);
-    int nw = c.S / 4;   // four tokens per wave at the least: S = 16 runs 4 waves, S >= 64 all 16
-    nw = nw < 1 ? 1 : (nw > GENIE_SCORE_MAX_WAVES ? GENIE_SCORE_MAX_WAVES : nw);
-    score_rows_kernel<<<(unsigned)N, 64 * nw, 0, st>>>(logits, targets, target_clip_stride, K, c.S, c.factored_vocab, c.num_factored, nll,
-                                                       nll_stride, hits, token_nll, token_stride);
-    GENIE_LAUNCH_CHECK("score_rows");
     return GENIE_OK;
 }
 

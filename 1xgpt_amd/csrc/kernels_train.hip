@@ -476,262 +476,6 @@ int launch_gelu_bwd(const float* z, float* g, size_t n, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// masked factored cross-entropy, forward and backward in one pass (st_mask_git.py:231-253, 276):
-//   counted(token) = frame >= 1 and input id == MASK;  n = number of counted tokens (count_masked_kernel)
-//   sums += [sum ce, sum all-factors-correct, (n is written by the count kernel)]
-//   logits row (V = nfac*vf) is REPLACED by d loss / d logits = counted ? (softmax_f - onehot_f) / n : 0
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void count_masked_kernel(const int64_t* __restrict__ ids, long B, int T, int S,
-                                                            int64_t mask_id, double* __restrict__ sums) {
-    __shared__ unsigned long long red[16];
-    unsigned long long c = 0;
-    const long n = B * T * (long)S;
-    for (long i = threadIdx.x; i < n; i += 1024) {
-        const int t = (int)((i / S) % T);
-        c += (t >= 1 && ids[i] == mask_id) ? 1ull : 0ull;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long s = 0;
-        for (int w = 0; w < 16; ++w) s += red[w];
-        sums[2] = (double)s;
-    }
-}
-__global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(float* __restrict__ logits, const int64_t* __restrict__ ids,
-                                                         const int64_t* __restrict__ labels, long n_tok, int T, int S,
-                                                         int vf, int nfac, int64_t mask_id, double* __restrict__ sums) {
-    __shared__ double red[2][4];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const long n = (long)blockIdx.x * 4 + wid;
-    double ce = 0, hit = 0;
-    if (n < n_tok) {
-        float* lp = logits + (size_t)n * vf * nfac;
-        const int t = (int)((n / S) % T);
-        const bool counted = t >= 1 && ids[n] == mask_id;
-        if (!counted) {
-            for (int k = lane; k < vf * nfac; k += 64) lp[k] = 0.f;
-        } else {
-            const float wgt = (float)(1.0 / sums[2]);
-            int64_t tgt = labels[n];
-            float loss = 0.f;
-            bool all_ok = true;
-            for (int f = 0; f < nfac; ++f) {
-                const int tf = (int)(tgt % vf);
-                tgt /= vf;
-                float* lf = lp + f * vf;
-                float mx = -INFINITY;
-                int mi = 0;
-                for (int k = lane; k < vf; k += 64) {
-                    const float v = lf[k];
-                    if (v > mx) { mx = v; mi = k; }
-                }
-                wave_argmax(mx, mi);
-                float se = 0.f;
-                for (int k = lane; k < vf; k += 64) se += expf(lf[k] - mx);
-                se = wave_sum(se);
-                loss += logf(se) + mx - lf[tf];
-                all_ok = all_ok && (mi == tf);
-                const float inv = 1.0f / se;
-                for (int k = lane; k < vf; k += 64) {
-                    const float p = expf(lf[k] - mx) * inv;
-                    lf[k] = (p - (k == tf ? 1.0f : 0.0f)) * wgt;
-                }
-            }
-            if (lane == 0) { ce = loss; hit = all_ok ? 1.0 : 0.0; }
-        }
-    }
-    if (lane == 0) { red[0][wid] = ce; red[1][wid] = hit; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0, b = 0;
-        for (int w = 0; w < 4; ++w) { a += red[0][w]; b += red[1][w]; }
-        if (a != 0.0 || b != 0.0) { atomicAdd(&sums[0], a); atomicAdd(&sums[1], b); }
-    }
-}
-int launch_ce_fwd_bwd(const genie_cfg& c, float* logits, const int64_t* ids, const int64_t* labels, int B, double* sums,
-                      hipStream_t st) {
-    const long n_tok = (long)B * c.T * c.S;
-    if (n_tok <= 0) return GENIE_OK;
-    count_masked_kernel<<<1, 1024, 0, st>>>(ids, B, c.T, c.S, (int64_t)c.image_vocab_size, sums);
-    GENIE_LAUNCH_CHECK("count_masked");
-    ce_fwd_bwd_kernel<<<(unsigned)((n_tok + 3) / 4), 256, 0, st>>>(logits, ids, labels, n_tok, c.T, c.S, c.factored_vocab,
-                                                                  c.num_factored, (int64_t)c.image_vocab_size, sums);
-    GENIE_LAUNCH_CHECK("ce_fwd_bwd");
-    return GENIE_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// The general objective (include/genie_hip.h, "Training objective"): label smoothing eps, z-loss zeta, per-frame weights w_t.
-// The kernels above stay the neutral step's; these two run when any knob is set (and behind genie_ce_objective with a struct).
-//   sums = [sum w_t l_n, sum hits, W = sum_t w_t c_t, sum plain nll, n = sum_t c_t]; hits and plain nll over ALL counted tokens
-//   logits row <- counted and w_t > 0 ? (p (1 + 2 zeta lse) - q) (float)(w_t / W) : 0
-// Same mapping as ce_fwd_bwd_kernel (one wave per token, four tokens per workgroup) and, lane by lane, the same order of every
-// sum that kernel takes: at eps = zeta = 0 and w = 1 the rows are its bits.  REG: vf <= 512, a factor's values stay in registers
-// (eight per lane), so the row comes from memory once; else the three passes of the kernel above, sum z riding in the first.
-// The weights travel by value in the kernel arguments (64 floats): no copy, no sync.
-// ------------------------------------------------------------------------------------------------
-// (FrameWeights: kernels.hpp -- the distillation kernel of kernels_distill.hip takes the same struct)
-__global__ __launch_bounds__(1024) void count_frames_kernel(const int64_t* __restrict__ ids, long n_clips, int T, int S,
-                                                            int64_t mask_id, FrameWeights fw, double* __restrict__ sums) {
-    __shared__ unsigned int cnt[64];            // frames 0 .. 63 one by one: the only ones that can carry a weight
-    __shared__ unsigned long long red[16];      // every later frame (all weigh 1), summed
-    if (threadIdx.x < 64) cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    unsigned long long c = 0;
-    const long n = n_clips * T * (long)S;
-    for (long i = threadIdx.x; i < n; i += 1024) {
-        const int t = (int)((i / S) % T);
-        if (t >= 1 && ids[i] == mask_id) {
-            if (t < 64) atomicAdd(&cnt[t], 1u);   // integers: any order gives the same count
-            else c += 1ull;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long late = 0, all = 0;
-        for (int w = 0; w < 16; ++w) late += red[w];
-        double W = 0.0;
-        for (int t = 1; t < 64 && t < T; ++t) {
-            W += (double)fw.at(t) * (double)cnt[t];
-            all += cnt[t];
-        }
-        sums[2] = W + (double)late;
-        sums[4] = (double)(all + late);
-    }
-}
-
-template <bool REG>
-__global__ __launch_bounds__(256) void ce_objective_kernel(float* __restrict__ logits, const int64_t* __restrict__ ids,
-                                                           const int64_t* __restrict__ labels, long n_tok, int T, int S, int vf,
-                                                           int nfac, int64_t mask_id, float eps, float zeta, FrameWeights fw,
-                                                           double* __restrict__ sums) {
-    __shared__ double red[3][4];
-    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const long n = (long)blockIdx.x * 4 + wid;
-    double obj = 0, hit = 0, ce = 0;
-    if (n < n_tok) {
-        float* lp = logits + (size_t)n * vf * nfac;
-        const int t = (int)((n / S) % T);
-        const bool counted = t >= 1 && ids[n] == mask_id;
-        if (!counted) {
-            for (int k = lane; k < vf * nfac; k += 64) lp[k] = 0.f;
-        } else {
-            const float wt = fw.at(t);
-            const bool live = wt > 0.0f;   // a zero-weight frame: counted in hits and plain nll, a zero row, never times 1 / W
-            const float wgt = live ? (float)((double)wt / sums[2]) : 0.0f;
-            const float q_off = eps / (float)vf, q_on = (1.0f - eps) + q_off, inv_vf = 1.0f / (float)vf;
-            int64_t tgt = labels[n];
-            float nll = 0.f, loss = 0.f;
-            bool all_ok = true;
-            for (int f = 0; f < nfac; ++f) {
-                const int tf = (int)(tgt % vf);
-                tgt /= vf;
-                float* lf = lp + f * vf;
-                float v[REG ? 8 : 1];
-                float mx = -INFINITY, sz = 0.f;
-                int mi = 0;
-                if (REG) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int k = lane + 64 * j;
-                        v[j] = k < vf ? lf[k] : -INFINITY;
-                        if (k < vf) sz += v[j];
-                        if (v[j] > mx) { mx = v[j]; mi = k; }
-                    }
-                } else {
-                    for (int k = lane; k < vf; k += 64) {
-                        const float x = lf[k];
-                        sz += x;
-                        if (x > mx) { mx = x; mi = k; }
-                    }
-                }
-                wave_argmax(mx, mi);
-                const float zy = lf[tf];   // read before any lane stores into the row
-                float se = 0.f;
-                if (REG) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j)
-                        if (lane + 64 * j < vf) { v[j] = expf(v[j] - mx); se += v[j]; }
-                } else {
-                    for (int k = lane; k < vf; k += 64) se += expf(lf[k] - mx);
-                }
-                se = wave_sum(se);
-                const float lse = logf(se) + mx;
-                const float nll_f = lse - zy;
-                nll += nll_f;
-                all_ok = all_ok && (mi == tf);
-                if (!live) {
-                    for (int k = lane; k < vf; k += 64) lf[k] = 0.f;
-                    continue;
-                }
-                sz = wave_sum(sz);
-                loss += ((1.0f - eps) * nll_f + eps * (lse - sz * inv_vf)) + zeta * (lse * lse);
-                const float inv = 1.0f / se, fac = 1.0f + (2.0f * zeta) * lse;
-                if (REG) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int k = lane + 64 * j;
-                        if (k < vf) lf[k] = ((v[j] * inv) * fac - (k == tf ? q_on : q_off)) * wgt;
-                    }
-                } else {
-                    for (int k = lane; k < vf; k += 64) {
-                        const float p = expf(lf[k] - mx) * inv;
-                        lf[k] = (p * fac - (k == tf ? q_on : q_off)) * wgt;
-                    }
-                }
-            }
-            if (lane == 0) { obj = (double)wt * (double)loss; hit = all_ok ? 1.0 : 0.0; ce = nll; }
-        }
-    }
-    if (lane == 0) { red[0][wid] = obj; red[1][wid] = hit; red[2][wid] = ce; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0, b = 0, c = 0;
-        for (int w = 0; w < 4; ++w) { a += red[0][w]; b += red[1][w]; c += red[2][w]; }
-        if (a != 0.0) atomicAdd(&sums[0], a);
-        if (b != 0.0) atomicAdd(&sums[1], b);
-        if (c != 0.0) atomicAdd(&sums[3], c);
-    }
-}
-FrameWeights frame_weights_of(const genie_objective& obj) {
-    FrameWeights fw;
-    fw.n = obj.n_frames;
-    for (int t = 0; t < 64; ++t) fw.w[t] = t < obj.n_frames ? obj.frame_weight[t] : 1.0f;
-    return fw;
-}
-int launch_count_frames(const int64_t* ids, long n_clips, int T, int S, int64_t mask_id, const FrameWeights& fw, double* sums,
-                        hipStream_t st) {
-    ProfScope prof(GENIE_KC_OTHER, 0.0, 8.0 * n_clips * T * S, st, "count_frames_kernel");
-    count_frames_kernel<<<1, 1024, 0, st>>>(ids, n_clips, T, S, mask_id, fw, sums);
-    GENIE_LAUNCH_CHECK("count_frames");
-    return GENIE_OK;
-}
-int launch_ce_objective(float* logits, const int64_t* ids, const int64_t* labels, long n_clips, int T, int S, int vf, int nfac,
-                        int64_t mask_id, const genie_objective& obj, double* sums, hipStream_t st) {
-    const long n_tok = n_clips * T * (long)S;
-    if (n_tok <= 0) return GENIE_OK;
-    const FrameWeights fw = frame_weights_of(obj);
-    const double row_bytes = 8.0 * n_tok * vf * nfac;
-    GENIE_TRY(launch_count_frames(ids, n_clips, T, S, mask_id, fw, sums, st));
-    ProfScope prof(GENIE_KC_OTHER, 0.0, row_bytes, st, "ce_objective_kernel");
-    const unsigned grid = (unsigned)((n_tok + 3) / 4);
-    if (vf <= 512)
-        ce_objective_kernel<true><<<grid, 256, 0, st>>>(logits, ids, labels, n_tok, T, S, vf, nfac, mask_id, obj.label_smoothing,
-                                                        obj.z_loss, fw, sums);
-    else
-        ce_objective_kernel<false><<<grid, 256, 0, st>>>(logits, ids, labels, n_tok, T, S, vf, nfac, mask_id, obj.label_smoothing,
-                                                         obj.z_loss, fw, sums);
-    GENIE_LAUNCH_CHECK("ce_objective");
-    return GENIE_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
 // embedding backward (factorization_utils.py:29-52, st_mask_git.py:257-261), scatter-free and ordered:
 //   dpos[t,s,:]  = sum_b dx[b,t,s,:]
 //   row v of table f (block f*vf + v): sum over tokens n (ascending) with factor_f(id_n) == v and id_n != MASK

@@ -44,7 +44,7 @@
 // branch keeps dx itself.  p = 0 launches exactly the step above.
 //
 // Training objective (genie_train_forward_obj, a genie_objective that is not neutral): the forward is the one above up to the logits;
-// the loss launch is launch_ce_objective (kernels_train.hip: label smoothing, z-loss, per-frame weights; five sums) instead of
+// the loss launch is launch_ce_objective (kernels_loss.hip: label smoothing, z-loss, per-frame weights; five sums) instead of
 // launch_ce_fwd_bwd, and leaves d loss / d logits in the same slot, so no backward entry point knows about it.  Neutral: the step above.
 #include <cmath>
 
@@ -388,7 +388,15 @@ static int distill_apart(const float* teacher, const float* logits, size_t float
     GENIE_CHECK_ARG(t1 <= s0 || s1 <= t0, "%s: the teacher logits overlap the sums", fn);
     return GENIE_OK;
 }
-static const genie_objective kNeutralObjective = {};   // eps = zeta = 0, n_frames = 0: every frame weighs 1
+// the pointers and geometry of a loss launch on raw arguments (genie_ce_objective, genie_ce_distill)
+static int loss_call_ok(const float* logits, const int64_t* ids, const int64_t* labels, const double* sums, int n_clips, int T, int S, int vf,
+                        int nfac, const char* fn) {
+    GENIE_CHECK_ARG(logits && ids && labels && sums, "%s: NULL argument", fn);
+    GENIE_CHECK_ARG(n_clips >= 1 && T >= 1 && S >= 1 && vf >= 1 && nfac >= 1 && nfac <= 4,
+                    "%s: n_clips %d, T %d, S %d, vf %d must be positive and nfac %d in 1 .. 4", fn, n_clips, T, S, vf, nfac);
+    GENIE_CHECK_ARG((long)vf * nfac <= INT32_MAX, "%s: a row of %d x %d logits", fn, nfac, vf);
+    return GENIE_OK;
+}
 
 // ================================================================================================
 // The two backends.  Same members: Operand (the element type of a saved Linear input), cast / norm / attention (produce an
@@ -586,16 +594,9 @@ static int train_forward(Ops& o, const genie_weights* wt, const int64_t* input_i
     }
     if (!idn) GENIE_TRY(o.cast(xL, xL_op, pd));
     GENIE_TRY(o.linear(xL_op, readout_lin(c, wt, nullptr, nullptr), nullptr, logits, nullptr, nullptr, c.readout_mult));
-    if (hipMemsetAsync(sums, 0, (ds ? 7 : obj ? 5 : 3) * sizeof(double), o.st) != hipSuccess) {
-        set_error("genie_train_forward: hipMemsetAsync failed");
-        return GENIE_E_LAUNCH;
-    }
-    if (ds)   // distillation (checked, not neutral): the objective's loss with the teacher's rows beside the student's, seven sums
-        return launch_ce_distill(logits, ds->teacher_logits, input_ids, labels, o.B, c.T, c.S, c.factored_vocab, c.num_factored,
-                                 (int64_t)c.image_vocab_size, obj ? *obj : kNeutralObjective, ds->alpha, ds->temperature, sums, o.st);
-    if (!obj) return launch_ce_fwd_bwd(c, logits, input_ids, labels, o.B, sums, o.st);
-    return launch_ce_objective(logits, input_ids, labels, o.B, c.T, c.S, c.factored_vocab, c.num_factored, (int64_t)c.image_vocab_size,
-                               *obj, sums, o.st);
+    // ds (checked, not neutral): the objective's loss with the teacher's rows beside the student's
+    return launch_train_loss("genie_train_forward", logits, input_ids, labels, o.B, c.T, c.S, c.factored_vocab, c.num_factored,
+                             (int64_t)c.image_vocab_size, obj, ds, ds ? ds->teacher_logits : nullptr, sums, o.st);
 }
 
 // d loss / d logits (in the logits slot) -> the readout's gradients and d xL in w.dx
@@ -924,27 +925,12 @@ int genie_objective_layout(size_t* out_host, int n) {
 int genie_ce_objective(float* logits, const int64_t* ids, const int64_t* labels, int n_clips, int T, int S, int vf, int nfac,
                        int64_t mask_id, const genie_objective* obj, double* sums, void* stream) {
     GENIE_TRY(objective_ok(obj, T, "genie_ce_objective"));
-    GENIE_CHECK_ARG(logits && ids && labels && sums, "genie_ce_objective: NULL argument");
-    GENIE_CHECK_ARG(n_clips >= 1 && T >= 1 && S >= 1 && vf >= 1 && nfac >= 1 && nfac <= 4,
-                    "genie_ce_objective: n_clips %d, T %d, S %d, vf %d must be positive and nfac %d in 1 .. 4", n_clips, T, S, vf, nfac);
-    GENIE_CHECK_ARG((long)vf * nfac <= INT32_MAX, "genie_ce_objective: a row of %d x %d logits", nfac, vf);
-    hipStream_t st = (hipStream_t)stream;
-    if (!obj) {   // the neutral step's kernels (they take the geometry from a genie_cfg)
+    GENIE_TRY(loss_call_ok(logits, ids, labels, sums, n_clips, T, S, vf, nfac, "genie_ce_objective"));
+    if (!obj)   // the neutral step's kernels take the geometry from a genie_cfg
         GENIE_CHECK_ARG(mask_id >= INT32_MIN && mask_id <= INT32_MAX, "genie_ce_objective: mask_id %lld beyond int32 without an objective",
                         (long long)mask_id);
-        genie_cfg c{};
-        c.T = T; c.S = S; c.factored_vocab = vf; c.num_factored = nfac; c.image_vocab_size = (int32_t)mask_id;
-        if (hipMemsetAsync(sums, 0, 3 * sizeof(double), st) != hipSuccess) {
-            set_error("genie_ce_objective: hipMemsetAsync failed");
-            return GENIE_E_LAUNCH;
-        }
-        return launch_ce_fwd_bwd(c, logits, ids, labels, n_clips, sums, st);
-    }
-    if (hipMemsetAsync(sums, 0, 5 * sizeof(double), st) != hipSuccess) {
-        set_error("genie_ce_objective: hipMemsetAsync failed");
-        return GENIE_E_LAUNCH;
-    }
-    return launch_ce_objective(logits, ids, labels, n_clips, T, S, vf, nfac, mask_id, *obj, sums, st);
+    return launch_train_loss("genie_ce_objective", logits, ids, labels, n_clips, T, S, vf, nfac, mask_id, obj, nullptr, nullptr, sums,
+                             (hipStream_t)stream);
 }
 
 int genie_distill_layout(size_t* out_host, int n) {
@@ -959,18 +945,10 @@ int genie_ce_distill(float* logits, const float* teacher_logits, const int64_t* 
     GENIE_TRY(distill_ok(ds, teacher_logits, "genie_ce_distill"));
     if (distill_neutral(ds)) return genie_ce_objective(logits, ids, labels, n_clips, T, S, vf, nfac, mask_id, obj, sums, stream);
     GENIE_TRY(objective_ok(obj, T, "genie_ce_distill"));
-    GENIE_CHECK_ARG(logits && ids && labels && sums, "genie_ce_distill: NULL argument");
-    GENIE_CHECK_ARG(n_clips >= 1 && T >= 1 && S >= 1 && vf >= 1 && nfac >= 1 && nfac <= 4,
-                    "genie_ce_distill: n_clips %d, T %d, S %d, vf %d must be positive and nfac %d in 1 .. 4", n_clips, T, S, vf, nfac);
-    GENIE_CHECK_ARG((long)vf * nfac <= INT32_MAX, "genie_ce_distill: a row of %d x %d logits", nfac, vf);
+    GENIE_TRY(loss_call_ok(logits, ids, labels, sums, n_clips, T, S, vf, nfac, "genie_ce_distill"));
     GENIE_TRY(distill_apart(teacher_logits, logits, (size_t)n_clips * T * S * vf * nfac, sums, "genie_ce_distill"));
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(sums, 0, 7 * sizeof(double), st) != hipSuccess) {
-        set_error("genie_ce_distill: hipMemsetAsync failed");
-        return GENIE_E_LAUNCH;
-    }
-    return launch_ce_distill(logits, teacher_logits, ids, labels, n_clips, T, S, vf, nfac, mask_id, obj ? *obj : kNeutralObjective, ds->alpha,
-                             ds->temperature, sums, st);
+    return launch_train_loss("genie_ce_distill", logits, ids, labels, n_clips, T, S, vf, nfac, mask_id, obj, ds, teacher_logits, sums,
+                             (hipStream_t)stream);
 }
 
 int genie_dropout_mask(const genie_dropout* dr, int layer, int site, int64_t n, uint8_t* keep, void* stream) {

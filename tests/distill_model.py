@@ -8,7 +8,7 @@ the contract of include/genie_hip.h ("Distillation") in NumPy, and a float64 tor
 
 ce_distill works from the closed forms; autograd_step builds the loss from F.kl_div(log_softmax(z / tau), softmax(u / tau)) * tau^2,
 F.cross_entropy(label_smoothing=eps) and zeta * logsumexp^2 and lets autograd differentiate it; tests/test_train_distill_cpu.py holds one
-against the other.  ce_distill_f32 restates ce_distill_kernel (csrc/kernels_distill.hip) operation by operation in float32 -- lane l owns
+against the other.  ce_distill_f32 restates ce_distill_kernel (csrc/kernels_loss.hip) operation by operation in float32 -- lane l owns
 classes l + 64 j, summed j ascending, then the xor butterfly over the 64 lanes -- with NumPy's exp and log in place of the device's: it
 carries the roundings of the soft term that the neutral kernel does not have.
 """

@@ -16,7 +16,7 @@ clean; its cached workspace, any cached cache and everything the call allocates 
 object across calls of other batch sizes, paths and precisions, each call bit-equal to the same call on a freshly built object.
 
 The only outputs with a tolerance are scalars the library sums with atomicAdd on doubles, whose order is free:
-    out.loss of STMaskGIT.forward and the loss of GenieTrainer.forward_backward  (the CE sum of kernels_exact.hip; sums[0] / sums[2])
+    out.loss of STMaskGIT.forward and the loss of GenieTrainer.forward_backward  (the CE sum of kernels_loss.hip; sums[0] / sums[2])
 at 1e-9 relative -- a reordering moves a sum of N <= 2^20 addends by at most N * 2^-53 * sum|a_i| ~ 1.2e-10 of it.  The accuracy sums
 (counts, exact in a double in any order) and everything else are compared with torch.equal.
 

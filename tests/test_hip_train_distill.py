@@ -1,4 +1,4 @@
-"""Distilling a teacher into a student (include/genie_hip.h, "Distillation"; ce_distill_kernel in csrc/kernels_distill.hip): the loss
+"""Distilling a teacher into a student (include/genie_hip.h, "Distillation"; ce_distill_kernel in csrc/kernels_loss.hip): the loss
 launch alone against the float64 contract, neutral calls against the calls of before, trainer steps against the float64 autograd model
 of tests/distill_model.py in the three precisions with precomputed teacher logits and with a live teacher, composition with
 recomputation, accumulation, frozen tensors, dropout and stale memory, a short training run, refusals and the CLI.

@@ -1,5 +1,5 @@
 """Training with label smoothing, z-loss and per-frame loss weights (include/genie_hip.h, "Training objective"; ce_objective_kernel in
-csrc/kernels_train.hip): the loss launch alone against the float64 contract with the neutral step's kernel as the floor, trainer steps
+csrc/kernels_loss.hip): the loss launch alone against the float64 contract with the neutral step's kernel as the floor, trainer steps
 against the float64 autograd model of tests/objective_model.py in the three precisions, composition with recomputation, dropout and
 gradient accumulation, the neutral trainer against the trainer of before, W = 0, refusals, resume and the CLI.
 

@@ -25,7 +25,11 @@ forward_backward, a second one with accumulate=True, one optimizer_step.  Record
 call, the flat parameters after the step, genie_train_activation_bytes / genie_train_workspace_bytes, and the kernel tables around the
 whole case (the trainer's weight packing included).  TRAIN_CASES are geometries tests/test_hip_train*.py pin, in all three precisions;
 s144 (T*S = 288) is refused by the 16-bit step and counts through its return code.  Then TEMPORAL_BWD_CASES: genie_temporal_attention_backward
-alone on seeded inputs, into a sentinel-filled output.
+alone on seeded inputs, into a sentinel-filled output.  Then the loss and scoring launches of csrc/kernels_loss.hip alone (loss_cases):
+genie_ce_objective without and with a struct (eps 0.1, zeta 1e-4, frame weights 1, 0, 2) and genie_ce_distill at tau 1 and 2 on T = 3,
+S = 5 and 1 and 3 clips; genie_factored_ce in both layouts, with and without weight_ids, and genie_score_logits with hits and token_nll
+at the smallest geometry -- each at vocabularies 2 x 512, 3 x 80 and 1 x 576.  Their f64 sums that workgroups fill with atomics depend
+on arrival order and are compared within (workgroups) * 2^-52 relative; counts and every other slot exactly.
 
 The loops battery (--battery loops): the generate loops of csrc/generate_api.hip, called through ctypes on LOOP_MODELS.  Per model and
 clip count: genie_maskgit_generate_ex / _guided (3 steps; random, greedy and confidence unmasking at temperature 0 and under a
@@ -97,7 +101,8 @@ TRAIN_CASES = [("d64", 2, 64, 4, 16, 1, False, 2, 0),         # transposed-copy 
 TEMPORAL_BWD_CASES = ([(T, Dh, *g) for T in (16, 32, 64) for Dh in (32, 64) for g in ((2, 3, 2, 3), (1, 3, 1, 2), (1, 5, 1, 3))]
                       + [(8, 32, 2, 3, 2, 3), (8, 64, 1, 5, 1, 2), (16, 128, 1, 3, 1, 3), (16, 128, 1, 5, 1, 2), (4, 32, 2, 3, 2, 2),
                          (32, 128, 1, 3, 1, 3), (8, 16, 1, 3, 1, 3)])
-TRAIN_WATCHED = ["gemm_f32_gen_kernel", "attn_spatial_bwd_fused_kernel", "wgrad16_tn_kernel", "attn_bwd16_"]
+TRAIN_WATCHED = ["gemm_f32_gen_kernel", "attn_spatial_bwd_fused_kernel", "wgrad16_tn_kernel", "attn_bwd16_", "count_frames_kernel",
+                 "ce_objective_kernel", "ce_distill_kernel"]
 # loops battery: (name, d_model, heads, T, S, precisions, clip counts), a LayerNorm and a qk-norm model each.  d64: the generic kernels --
 # every merged commit is refused and the loops fall back, the context runs frame by frame; d256 / d512 in f16x3: the fragment-order
 # passes with merged commits and the multi-frame context pass; 9 clips of 8 context frames are past its 16,384-row cut (the clean pass runs)
@@ -134,8 +139,10 @@ def child(out_path, battery):
         the outputs of a refused call are digested too (sentinel-filled by the case: a refused call must not have touched them)"""
         _lib.check(lib.genie_profile_enable((1 << N_CLASSES) - 1), "profile_enable")
         lib.genie_profile_reset()
+        sums = {}
         try:
-            rc, outs = fn()
+            rc, outs, *more = fn()   # (a loss case adds its f64 sums: see loss_cases)
+            sums = more[0] if more else {}
         except _lib.GenieHipError as e:
             rc, outs = e.code, {}
         torch.cuda.synchronize()
@@ -147,7 +154,89 @@ def child(out_path, battery):
                 table[f"{kc}:{ln.split(chr(9))[0]}"] = int(float(ln.split("\t")[1]))
         lib.genie_profile_enable(0)
         record[name] = {"rc": rc, "outs": {k: digest(v) for k, v in outs.items()} if rc == 0 or keep_refused else {}, "kernels": table}
+        if sums:
+            record[name]["sums"] = {k: {"values": [float(x).hex() for x in t.cpu().tolist()], "atomic": list(atomic), "workgroups": wg}
+                                    for k, (t, atomic, wg) in sums.items()}
         print(name, "rc", rc, "launches", sum(table.values()), flush=True)
+
+    def loss_cases():
+        """The loss and scoring launches alone (csrc/kernels_loss.hip), on seeded logits into sentinel-filled outputs.  Digested: the
+        gradient rows that replace the logits, nll, hits, token_nll.  The f64 sums come back apart, as (tensor, the slots that workgroups
+        add to with atomics, the workgroups of the launch): those slots depend on arrival order and are compared within a bound, every
+        other slot (counts, normalisers, untouched sentinels) exactly."""
+        st = torch.cuda.current_stream().cuda_stream
+        VOCABS = [(512, 2), (80, 3), (576, 1)]   # the register paths; a ragged lane tail on the generic path; the streaming kernels
+
+        def seeded(seed, n_tok, vf, nfac):
+            g = torch.Generator().manual_seed(seed)
+            mask_id = vf ** nfac
+            labels = torch.randint(0, mask_id, (n_tok,), generator=g)
+            ids = torch.where(torch.rand(n_tok, generator=g) < 0.5, torch.full_like(labels, mask_id), labels)   # about half are masked
+            return g, mask_id, labels.cuda(), ids.cuda()
+
+        T, S = 3, 5   # 15 and 45 tokens: the last workgroup of four tokens is partial, frame 0 is present
+        for vf, nfac in VOCABS:
+            for clips in (1, 3):
+                n_tok, V = clips * T * S, vf * nfac
+                g, mask_id, labels, ids = seeded(100 * vf + clips, n_tok, vf, nfac)
+                src = (3.0 * torch.randn(n_tok, V, generator=g)).cuda()
+                teacher = (3.0 * torch.randn(n_tok, V, generator=g)).cuda()
+                ob = _lib.Objective(label_smoothing=0.1, z_loss=1e-4, n_frames=T)
+                ob.frame_weight[:T] = [1.0, 0.0, 2.0]
+                wg = (n_tok + 3) // 4
+
+                def training_loss(obj, tau, atomic):
+                    def fn():
+                        logits, sums = src.clone(), torch.full((8,), 12345.0, dtype=torch.float64, device="cuda")
+                        geom = (clips, T, S, vf, nfac, mask_id)
+                        if tau is None:
+                            rc = lib.genie_ce_objective(logits.data_ptr(), ids.data_ptr(), labels.data_ptr(), *geom, obj, sums.data_ptr(), st)
+                        else:
+                            ds = _lib.Distill(alpha=0.5, temperature=tau, teacher_logits=teacher.data_ptr())
+                            rc = lib.genie_ce_distill(logits.data_ptr(), teacher.data_ptr(), ids.data_ptr(), labels.data_ptr(), *geom, obj, ds,
+                                                      sums.data_ptr(), st)
+                        assert bool(torch.isfinite(logits).all()) and bool(torch.isfinite(sums).all())
+                        return rc, {"d_logits": logits}, {"sums": (sums, atomic, min(wg, 2048))}
+                    return fn
+                tag = f"loss/{nfac}x{vf}/clips{clips}"
+                record_case(f"{tag}/objective/neutral", training_loss(None, None, (0,)))
+                record_case(f"{tag}/objective/struct", training_loss(ob, None, (0, 3)))
+                for tau in (1.0, 2.0):
+                    record_case(f"{tag}/distill/tau{tau:g}", training_loss(ob, tau, (0, 3, 5, 6)))
+
+        # the two entry points that take a genie_cfg: the smallest geometry of GEOMETRIES with each vocabulary
+        _, d, heads, T, S, B = GEOMETRIES[0]
+        for vf, nfac in VOCABS:
+            cfg = GenieConfig(num_layers=2, num_heads=heads, d_model=d, T=T, S=S, num_factored_vocabs=nfac, image_vocab_size=vf ** nfac,
+                              qk_norm=False, use_mup=False, qkv_bias=True)
+            c = _lib.make_cfg(cfg)
+            V, t0 = vf * nfac, 1
+            g, mask_id, targets, ids = seeded(7 * vf, B * T * S, vf, nfac)
+            src = (3.0 * torch.randn(B, T - t0, S, V, generator=g)).cuda()
+            for layout, lname in ((_lib.LAYOUT_TOKEN_MAJOR, "token"), (_lib.LAYOUT_BCTHW, "bcthw")):
+                logits = src if layout == _lib.LAYOUT_TOKEN_MAJOR else src.permute(0, 3, 1, 2).contiguous()
+                n_tok = B * (T - t0) * S
+                wg = min((n_tok + 3) // 4, 2048) if layout == _lib.LAYOUT_TOKEN_MAJOR else (n_tok + 255) // 256
+                for weighted in (False, True):
+                    def evaluator_ce():
+                        sums = torch.full((8,), 12345.0, dtype=torch.float64, device="cuda")
+                        sums[:3] = 0.0   # the entry point adds to what it finds
+                        rc = lib.genie_factored_ce(c, logits.data_ptr(), layout, targets.data_ptr(), ids.data_ptr() if weighted else 0, B, t0, T,
+                                                   sums.data_ptr(), st)
+                        assert bool(torch.isfinite(sums).all())
+                        return rc, {}, {"sums": (sums, (0,), wg)}
+                    record_case(f"loss/{nfac}x{vf}/factored_ce/{lname}/{'weighted' if weighted else 'all'}", evaluator_ce)
+            K, N = 3, 2 * 3   # two clips of three branches: row i is scored against the tokens of clip i / K
+
+            def score():
+                rows = (3.0 * torch.randn(N, S, V, generator=torch.Generator().manual_seed(9 * vf))).cuda()
+                nll, hits = (torch.full((N,), 12345.0, dtype=torch.float64, device="cuda") for _ in range(2))
+                tok = torch.full((N, S), 12345.0, device="cuda")
+                rc = lib.genie_score_logits(c, rows.data_ptr(), targets.data_ptr(), T * S, K, N, nll.data_ptr(), 1, hits.data_ptr(), tok.data_ptr(),
+                                            S, st)
+                assert bool(torch.isfinite(nll).all()) and bool(torch.isfinite(tok).all())
+                return rc, {"nll": nll, "hits": hits, "token_nll": tok}
+            record_case(f"loss/{nfac}x{vf}/score_logits", score)
 
     if battery == "train":
         TO = importlib.import_module("oracle.genie_train_oracle")   # its collator draws from NumPy: the same batch in both children
@@ -193,6 +282,7 @@ def child(out_path, battery):
                 assert bool(torch.isfinite(d_qkv).all())
                 return rc, {"d_qkv": d_qkv}
             record_case(f"temporal_bwd/T{T}/h{Dh}/B{B}S{S}H{H}/ld{ldm}d", bwd, keep_refused=True)
+        loss_cases()
         with open(out_path, "w") as f:
             json.dump(record, f)
         return
@@ -592,6 +682,7 @@ def run_battery(a, battery):
             if ca["outs"].get(k) != cb["outs"].get(k):
                 bad += 1
                 print(f"DIFF {name}: tensor {k}: {ca['outs'].get(k)} != {cb['outs'].get(k)}")
+        bad += sums_differ(name, ca.get("sums", {}), cb.get("sums", {}))
         if ca["kernels"] != cb["kernels"]:
             bad += 1
             for k in sorted(set(ca["kernels"]) | set(cb["kernels"])):
@@ -619,6 +710,23 @@ def run_battery(a, battery):
         print(f"FAIL: {bad} differences in the {battery} battery")
         return 1
     return 0
+
+
+def sums_differ(name, sa, sb):
+    """The f64 sums of a loss case -> the number of differences.  A slot that workgroups add to with atomics holds non-negative addends in
+    arrival order: two orders differ by at most (workgroups) * 2^-52 relative.  Every other slot must be equal."""
+    if sorted(sa) != sorted(sb):
+        print(f"DIFF {name}: sums recorded {sorted(sa)} != {sorted(sb)}")
+        return 1
+    bad = 0
+    for k in sa:
+        va, vb = ([float.fromhex(x) for x in s[k]["values"]] for s in (sa, sb))
+        for i, (x, y) in enumerate(zip(va, vb)):
+            bound = sa[k]["workgroups"] * 2.0 ** -52 * max(abs(x), abs(y)) if i in sa[k]["atomic"] else 0.0
+            if len(va) != len(vb) or not abs(x - y) <= bound:
+                bad += 1
+                print(f"DIFF {name}: {k}[{i}]: {x!r} != {y!r} (bound {bound:g})")
+    return bad
 
 
 def inference_proxies(ra):
