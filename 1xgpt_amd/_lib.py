@@ -96,6 +96,22 @@ class LoraItem(C.Structure):
 
 
 LORA_MAX_ITEMS, LORA_MAX_RANK = 8, 64   # GENIE_LORA_MAX_ITEMS, GENIE_LORA_MAX_RANK
+
+
+class MuonItem(C.Structure):
+    """genie_muon_item: one target matrix of a genie_muon_step call (device pointers; 1xgpt_amd/muon.py)."""
+    _fields_ = [(n, c_ptr) for n in ("param", "grad", "momentum", "ema")] + [("rows", C.c_int32), ("cols", C.c_int32), ("lr", C.c_float),
+                                                                             ("weight_decay", C.c_float)]
+
+
+class MuonSettings(C.Structure):
+    """genie_muon_settings."""
+    _fields_ = [(n, C.c_float) for n in ("momentum", "a", "b", "c", "eps", "grad_mult", "max_grad_norm", "ema_one_minus_decay")] + [
+        (n, C.c_int32) for n in ("nesterov", "ns_steps", "adjust", "reserved")] + [("grad_sumsq", c_ptr)]
+
+
+MUON_MAX_ITEMS = 64   # GENIE_MUON_MAX_ITEMS
+MUON_ADJUST = {"original": 0, "match_rms_adamw": 1}   # GENIE_MUON_ADJUST_*
 ACTION_MAX_DIM = 256   # GENIE_ACTION_MAX_DIM
 WIDE_QKV, WIDE_PROJ, WIDE_FC1, WIDE_FC2 = 1, 2, 1, 2          # bits of the w16_wide fields (genie_hip.h)
 FUSED_QKV_STREAM = 4                                        # spatial attention: fused_w16 = [proj stream | qkv stream]
@@ -328,6 +344,13 @@ SIGNATURES["genie_lora_merge"] = (C.c_int, [C.POINTER(LoraItem), C.c_int, c_ptr]
 SIGNATURES["genie_lora_project_scratch_bytes"] = (C.c_size_t, [C.POINTER(LoraItem), C.c_int])
 SIGNATURES["genie_lora_project"] = (C.c_int, [C.POINTER(LoraItem), C.c_int, C.c_int, c_ptr, C.c_size_t, c_ptr])
 
+# Muon: (items, n), (items, n, settings, workspace, workspace_bytes, stream) and the unit entry point of the iteration alone
+SIGNATURES["genie_muon_layout"] = (C.c_int, [C.POINTER(C.c_size_t), C.c_int])
+SIGNATURES["genie_muon_workspace_bytes"] = (C.c_size_t, [C.POINTER(MuonItem), C.c_int])
+SIGNATURES["genie_muon_step"] = (C.c_int, [C.POINTER(MuonItem), C.c_int, C.POINTER(MuonSettings), c_ptr, C.c_size_t, c_ptr])
+SIGNATURES["genie_newton_schulz"] = (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
+                                               c_ptr, C.c_size_t, c_ptr])
+
 _lib = None
 
 
@@ -387,6 +410,10 @@ def load():
         mine = [C.sizeof(LoraItem)] + [getattr(LoraItem, n).offset for n, _ in LoraItem._fields_]
         if "genie_lora_layout" not in missing and (lib.genie_lora_layout(lay, 12) != 12 or list(lay) != mine):
             raise RuntimeError(f"genie_lora_item layout {list(lay)} != the ctypes declaration {mine}")
+        lay = (C.c_size_t * 23)()
+        mine = [v for T in (MuonItem, MuonSettings) for v in [C.sizeof(T)] + [getattr(T, n).offset for n, _ in T._fields_]]
+        if "genie_muon_layout" not in missing and (lib.genie_muon_layout(lay, 23) != 23 or list(lay) != mine):
+            raise RuntimeError(f"genie_muon_item / genie_muon_settings layout {list(lay)} != the ctypes declaration {mine}")
         if os.environ.get("GENIE_HIP_LIBRARY") or lib.genie_study_build():
             import sys
             print(f"1xgpt_amd: using {LIB_PATH} (study build: {bool(lib.genie_study_build())}) -- not the shipping library"

@@ -491,6 +491,24 @@ bool lora_table(const genie_lora_item* items, int n, LoraTable& tb, size_t& scra
 int launch_lora_merge(const LoraTable& tb, hipStream_t st);
 int launch_lora_project(const LoraTable& tb, int accumulate, hipStream_t st);
 
+// Muon (kernels_muon.hip): how one table is laid out in the workspace.  Items of equal (rows, cols) form a group (in order of first
+// appearance) and lie back to back in X0 and X1, so each product of the iteration is one launch per group with the item index in the grid.
+constexpr int MUON_MAX_ITEMS = GENIE_MUON_MAX_ITEMS;
+struct MuonPlan {
+    struct Group {
+        int rows, cols, first, count;   // items order[first .. first + count)
+        size_t x_off;                   // floats into X0 / X1
+    } group[MUON_MAX_ITEMS];
+    int order[MUON_MAX_ITEMS];
+    size_t x_of[MUON_MAX_ITEMS];        // per item (caller's index): floats into X0 / X1
+    size_t off_x0, off_x1, off_a, off_p, total_floats;   // floats into the workspace; the 64 f64 partial sums per item lie at 0
+    int n, ngroups;
+};
+bool muon_plan(const genie_muon_item* items, int n, MuonPlan& pl);
+int launch_muon_step(const genie_muon_item* items, const MuonPlan& pl, const genie_muon_settings& s, float* ws, hipStream_t st);
+int launch_newton_schulz(const float* in, float* out, int rows, int cols, int batch, int steps, float a, float b, float c, float eps,
+                         const MuonPlan& pl, float* ws, hipStream_t st);
+
 // api.hip: the host helpers its entry points share with the generate loops (generate_api.hip)
 Workspace carve(const genie_cfg& c, int B, void* base);   // base == NULL: sizes only
 int check_cfg(const genie_cfg* c);

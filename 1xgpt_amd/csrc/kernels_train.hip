@@ -9,7 +9,7 @@
 //     wgrad     dW = dY^T . X         A = dY [k][rows] (TA) B = X  [k][cols]   (TB), split over the token axis
 // All reductions that feed a gradient (split-K partials, LayerNorm / bias column sums, embedding scatter) are
 // two-stage with a fixed summation order: a training step is bit-reproducible run to run.
-#include "kernels.hpp"
+#include "train_device.hpp"
 
 namespace genie {
 
@@ -18,46 +18,9 @@ namespace genie {
 //   TA: A(m,k) = A[k*lda + m] else A[m*lda + k];   TB: B(n,k) = W[k*ldw + n] else W[n*ldw + k]
 //   blockIdx.y = b1, blockIdx.z = b2 * nsplit + split; split s contracts k in [s*K/nsplit, (s+1)*K/nsplit) and
 //   writes its own slab C + s*sCsplit (no bias / residual there; splitk_reduce adds the slabs in order).
-// 128x128x16 tile, 4 waves (2x2) x 64x64, double-buffered LDS.  Row-major operands use the k-permuted
-// ds_read_b128 fetch of gemm_f32_nt_kernel (kernels_exact.hip); k-major operands are staged as they lie
-// ([16][128] floats, coalesced float4) and fetched with one conflict-free ds_read_b32 per MFMA -- the f32 MFMA
-// issues every 64 cycles per SIMD, so four narrow LDS reads per four MFMAs stay hidden.
+// The 128x128x16 operand tile (gg_stage_load / gg_stage_store / gg_frag) is stated in train_device.hpp, which the batched
+// products of kernels_muon.hip share.
 // ------------------------------------------------------------------------------------------------
-constexpr int GG_BM = 128, GG_BK = 16, GG_LD = GG_BK + 4, GG_TLD = GG_BM + 4;
-constexpr int GG_TILE = GG_BM * GG_LD;  // 2560 floats >= 16 * 132
-
-template <bool TR>
-__device__ __forceinline__ void gg_stage_load(const float* __restrict__ G, long ld, int row0, int limit, int k0, int tid,
-                                              float4 (&regs)[2]) {
-    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        if constexpr (!TR) {
-            const int row = row0 + (tid >> 2) + p * 64;
-            regs[p] = row < limit ? *reinterpret_cast<const float4*>(G + (size_t)row * ld + k0 + ((tid & 3) << 2)) : z4;
-        } else {
-            const int kr = (tid >> 5) + p * 8, c4 = (tid & 31) << 2;
-            regs[p] = (row0 + c4) < limit ? *reinterpret_cast<const float4*>(G + (size_t)(k0 + kr) * ld + row0 + c4) : z4;
-        }
-    }
-}
-template <bool TR>
-__device__ __forceinline__ void gg_stage_store(float* s, int tid, const float4 (&regs)[2]) {
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        if constexpr (!TR)
-            *reinterpret_cast<float4*>(&s[((tid >> 2) + p * 64) * GG_LD + ((tid & 3) << 2)]) = regs[p];
-        else
-            *reinterpret_cast<float4*>(&s[((tid >> 5) + p * 8) * GG_TLD + ((tid & 31) << 2)]) = regs[p];
-    }
-}
-// the four k-values (8kk + 4h + j, j = 0..3) of operand row `row` that MFMA j consumes
-template <bool TR>
-__device__ __forceinline__ float4 gg_frag(const float* s, int row, int kk, int h) {
-    if constexpr (!TR) return *reinterpret_cast<const float4*>(&s[row * GG_LD + kk * 8 + 4 * h]);
-    const float* p = s + (kk * 8 + 4 * h) * GG_TLD + row;
-    return make_float4(p[0], p[GG_TLD], p[2 * GG_TLD], p[3 * GG_TLD]);
-}
 
 template <bool TA, bool TB>
 __global__ __launch_bounds__(256) void gemm_f32_gen_kernel(const float* __restrict__ A, long lda, long sA1, long sA2,
@@ -668,15 +631,7 @@ int launch_sumsq(const float* x, size_t n, double* out, double* scratch, hipStre
 struct AdamwScalars {
     float beta1, beta2, eps, decay, step_size, inv_sqrt_bc2;
 };
-// grad_mult times the clip coefficient of clip_grad_norm_: min(1, max_norm / (total_norm + 1e-6))
-__device__ __forceinline__ float adamw_coef(float grad_mult, const double* __restrict__ sumsq, float max_norm) {
-    float coef = grad_mult;
-    if (sumsq && max_norm > 0.f) {
-        const float tn = (float)sqrt(*sumsq) * grad_mult;
-        coef *= fminf(1.0f, max_norm / (tn + 1e-6f));
-    }
-    return coef;
-}
+// (adamw_coef, grad_mult times the clip coefficient of clip_grad_norm_, is stated in train_device.hpp: the Muon step shares it)
 __device__ __forceinline__ void adamw_element(float& p, float g, float& m, float& v, float coef, const AdamwScalars& a) {
     const float gi = g * coef;
     const float pi = p * a.decay;  // decoupled weight decay: p *= 1 - lr*wd
@@ -687,10 +642,7 @@ __device__ __forceinline__ void adamw_element(float& p, float g, float& m, float
     const float denom = sqrtf(vi) * a.inv_sqrt_bc2 + a.eps;
     p = pi - a.step_size * (mi / denom);
 }
-// LitEma.forward's line (include/genie_hip.h, "EMA of the weights"): three f32 operations, each rounded on its own
-__device__ __forceinline__ float ema_element(float e, float p, float omd) {
-    return __fsub_rn(e, __fmul_rn(omd, __fsub_rn(e, p)));
-}
+// (ema_element, LitEma.forward's line, is stated in train_device.hpp as well)
 
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, size_t n, AdamwScalars a, float grad_mult, const double* __restrict__ sumsq,

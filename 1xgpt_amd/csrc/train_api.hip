@@ -1083,4 +1083,98 @@ int genie_lora_project(const genie_lora_item* items, int n, int accumulate, void
     return launch_lora_project(tb, accumulate ? 1 : 0, (hipStream_t)stream);
 }
 
+int genie_muon_layout(size_t* out_host, int n) {
+    typedef genie_muon_item I;
+    typedef genie_muon_settings S;
+    const size_t v[23] = {sizeof(I), offsetof(I, param), offsetof(I, grad), offsetof(I, momentum), offsetof(I, ema), offsetof(I, rows),
+                          offsetof(I, cols), offsetof(I, lr), offsetof(I, weight_decay),
+                          sizeof(S), offsetof(S, momentum), offsetof(S, a), offsetof(S, b), offsetof(S, c), offsetof(S, eps),
+                          offsetof(S, grad_mult), offsetof(S, max_grad_norm), offsetof(S, ema_one_minus_decay), offsetof(S, nesterov),
+                          offsetof(S, ns_steps), offsetof(S, adjust), offsetof(S, reserved), offsetof(S, grad_sumsq)};
+    for (int i = 0; i < n && i < 23 && out_host; ++i) out_host[i] = v[i];
+    return 23;
+}
+
+// what the shapes of a Muon table must satisfy (all of it that genie_muon_workspace_bytes needs), on the host alone
+static int muon_shapes_ok(const genie_muon_item* items, int n, const char* where) {
+    GENIE_CHECK_ARG(items != nullptr, "%s: NULL items", where);
+    GENIE_CHECK_ARG(n >= 1 && n <= GENIE_MUON_MAX_ITEMS, "%s: n = %d is not in 1 .. %d", where, n, GENIE_MUON_MAX_ITEMS);
+    for (int e = 0; e < n; ++e) {
+        const genie_muon_item& it = items[e];
+        GENIE_CHECK_ARG(it.rows >= 16 && it.rows % 16 == 0 && it.cols >= 16 && it.cols % 16 == 0,
+                        "%s: item %d: (rows, cols) = (%d, %d) are not positive multiples of 16", where, e, it.rows, it.cols);
+        GENIE_CHECK_ARG((size_t)it.rows * it.cols <= ((size_t)1 << 30), "%s: item %d: more than 2^30 elements", where, e);
+    }
+    return GENIE_OK;
+}
+static int muon_steps_ok(int steps, float a, float b, float c, float eps, const char* where) {
+    GENIE_CHECK_ARG(steps >= 0 && steps < 100, "%s: ns_steps = %d is not in 0 .. 99", where, steps);
+    GENIE_CHECK_ARG(std::isfinite(a) && std::isfinite(b) && std::isfinite(c) && std::isfinite(eps), "%s: a, b, c or eps is not finite", where);
+    return GENIE_OK;
+}
+static int muon_ws_ok(const MuonPlan& pl, const void* ws, size_t bytes, const char* where) {
+    GENIE_CHECK_ARG(ws != nullptr && (uintptr_t)ws % 16 == 0, "%s: NULL or misaligned workspace", where);
+    GENIE_CHECK_ARG(bytes >= pl.total_floats * sizeof(float), "%s: workspace of %zu bytes, %zu needed", where, bytes,
+                    pl.total_floats * sizeof(float));
+    return GENIE_OK;
+}
+
+size_t genie_muon_workspace_bytes(const genie_muon_item* items, int n) {
+    if (muon_shapes_ok(items, n, "genie_muon_workspace_bytes") != GENIE_OK) return 0;
+    MuonPlan pl;
+    if (!muon_plan(items, n, pl)) {
+        set_error("genie_muon_workspace_bytes: the table is beyond 2^40 elements");
+        return 0;
+    }
+    return pl.total_floats * sizeof(float);
+}
+
+int genie_muon_step(const genie_muon_item* items, int n, const genie_muon_settings* s, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+    const char* where = "genie_muon_step";
+    GENIE_TRY(muon_shapes_ok(items, n, where));
+    GENIE_CHECK_ARG(s != nullptr, "%s: NULL settings", where);
+    GENIE_TRY(muon_steps_ok(s->ns_steps, s->a, s->b, s->c, s->eps, where));
+    GENIE_CHECK_ARG(std::isfinite(s->momentum) && std::isfinite(s->grad_mult) && std::isfinite(s->max_grad_norm),
+                    "%s: momentum, grad_mult or max_grad_norm is not finite", where);
+    GENIE_CHECK_ARG(s->adjust == GENIE_MUON_ADJUST_ORIGINAL || s->adjust == GENIE_MUON_ADJUST_MATCH_RMS_ADAMW, "%s: adjust = %d", where,
+                    s->adjust);
+    GENIE_CHECK_ARG(s->grad_sumsq == nullptr || (uintptr_t)s->grad_sumsq % 8 == 0, "%s: misaligned grad_sumsq", where);
+    bool any_ema = false;
+    for (int e = 0; e < n; ++e) {
+        const genie_muon_item& it = items[e];
+        GENIE_CHECK_ARG(it.param && it.grad && it.momentum, "%s: item %d: NULL param, grad or momentum", where, e);
+        GENIE_CHECK_ARG(((uintptr_t)it.param | (uintptr_t)it.grad | (uintptr_t)it.momentum | (uintptr_t)it.ema) % 16 == 0,
+                        "%s: item %d: param, grad, momentum and ema must be 16-byte aligned", where, e);
+        GENIE_CHECK_ARG(std::isfinite(it.lr) && std::isfinite(it.weight_decay), "%s: item %d: lr or weight_decay is not finite", where, e);
+        any_ema = any_ema || it.ema != nullptr;
+    }
+    GENIE_CHECK_ARG(!any_ema || (s->ema_one_minus_decay >= 0.f && s->ema_one_minus_decay <= 1.f),
+                    "%s: ema_one_minus_decay is not in [0, 1]", where);
+    MuonPlan pl;
+    GENIE_CHECK_ARG(muon_plan(items, n, pl), "%s: the table is beyond 2^40 elements", where);
+    GENIE_TRY(muon_ws_ok(pl, workspace, workspace_bytes, where));
+    return launch_muon_step(items, pl, *s, (float*)workspace, (hipStream_t)stream);
+}
+
+int genie_newton_schulz(const float* in, float* out, int rows, int cols, int batch, int steps, float a, float b, float c, float eps,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+    const char* where = "genie_newton_schulz";
+    GENIE_CHECK_ARG(in && out, "%s: NULL in or out", where);
+    GENIE_CHECK_ARG(batch >= 1 && batch <= GENIE_MUON_MAX_ITEMS, "%s: batch = %d is not in 1 .. %d", where, batch, GENIE_MUON_MAX_ITEMS);
+    genie_muon_item items[GENIE_MUON_MAX_ITEMS] = {};
+    for (int e = 0; e < batch; ++e) items[e].rows = rows, items[e].cols = cols;
+    GENIE_TRY(muon_shapes_ok(items, batch, where));
+    GENIE_TRY(muon_steps_ok(steps, a, b, c, eps, where));
+    GENIE_CHECK_ARG(((uintptr_t)in | (uintptr_t)out) % 16 == 0, "%s: in and out must be 16-byte aligned", where);
+    const size_t nall = (size_t)batch * rows * cols;
+    GENIE_CHECK_ARG(in == out || !lora_overlap(in, nall, out, nall), "%s: in overlaps out without being out", where);
+    MuonPlan pl;
+    GENIE_CHECK_ARG(muon_plan(items, batch, pl), "%s: the batch is beyond 2^40 elements", where);
+    GENIE_TRY(muon_ws_ok(pl, workspace, workspace_bytes, where));
+    GENIE_CHECK_ARG(!lora_overlap(workspace, pl.total_floats, in, nall) && !lora_overlap(workspace, pl.total_floats, out, nall),
+                    "%s: the workspace overlaps in or out", where);
+    return launch_newton_schulz(in, out, rows, cols, batch, steps, a, b, c, eps, pl, (float*)workspace, (hipStream_t)stream);
+}
+
 }  // extern "C"

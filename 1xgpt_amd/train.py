@@ -21,6 +21,8 @@ Design (MI355X-first):
     with the parameters in place to evaluate, sample or save with the averaged weights.
   * distillation (`teacher`, `distill_alpha`, `distill_temperature`): soft targets from a teacher model's logits, mixed into the same fused
     loss kernel (genie_train_forward_distill), which reads the teacher's row beside the student's; the teacher's forward is the inference path.
+  * Muon (`muon=MuonConfig(...)`): momentum and a Newton-Schulz orthogonalisation of the update of the hidden weight matrices, f32 on the
+    matrix cores in every precision (genie_muon_step: batched over the same-shape matrices of all layers); everything else stays on AdamW.
   * training objective (`label_smoothing`, `z_loss`, `frame_weights`): label smoothing, z-loss and per-frame loss weights inside the
     fused loss kernel (genie_train_forward_obj); the backward reads its d logits as it reads the plain loss's; evaluation ignores it.
 MuAdamW (--mu_transfer, train.py:439; third-party mup fork) is not built.
@@ -38,7 +40,9 @@ import torch.distributed as dist
 
 from . import _lib
 from . import lora as _lora
+from . import muon as _muon
 from .lora import LINEAR_WEIGHTS, LoraConfig, linear_weight_names   # noqa: F401  (public here as well)
+from .muon import MuonConfig   # noqa: F401
 
 
 # ------------------------------------------------------------------ schedules (train.py:468-492)
@@ -273,14 +277,15 @@ class FlatLayout:
     offsets   {name: (lo, hi)} into the parameter buffer (tensors 256-byte aligned)
     n_flat    elements of the parameter buffer; n_train: of its trainable prefix = of the gradient, moment and EMA buffers
     trainable the set of trainable names; all: every name is trainable
-    adam_runs [(lo, hi, decays, lr factor)]: maximal runs of consecutive trainable tensors with equal (decay flag, lr factor)
+    adam_runs [(lo, hi, decays, lr factor)]: maximal runs of consecutive trainable AdamW tensors with equal (decay flag, lr factor)
+    muon      the trainable names the Muon step updates (`muon=`; empty by default): they break the runs and belong to none
     groups    [(key, lo, hi)] over the prefix, key "head", a layer index (L-1 .. 0) or "embed": one all-reduce segment per group that
               holds a trainable tensor, in ready order (segments = the (lo, hi) alone)
     stop      the backward runs layers L-1 .. stop: the lowest layer holding a trainable tensor, 0 when an embedding-side tensor
               (action tensors included) trains, num_layers when only the readout does
     embed     something on the embedding side trains: the embedding backward is called"""
 
-    def __init__(self, config, numels, trainable=None, lr_scale=None):
+    def __init__(self, config, numels, trainable=None, lr_scale=None, muon=None):
         names = list(numels)
         ro = ready_order(config, names)
         self.trainable = set(names) if trainable is None else set(trainable)
@@ -297,16 +302,19 @@ class FlatLayout:
         self.n_flat = o
         prefix = self.order[:len(self.trainable)]
         self.n_train = self.offsets[prefix[-1]][0] + _pad64(numels[prefix[-1]])
-        # AdamW ranges (padding between tensors is zero and stays zero: zero gradient, zero moments)
+        self.muon = set(muon or ())
+        if self.muon - self.trainable:
+            raise ValueError(f"Muon names {sorted(self.muon - self.trainable)[:4]} are not trainable parameters")
+        # AdamW ranges (padding between tensors is zero and stays zero: zero gradient, zero moments); a Muon tensor ends the run before it
         runs = []
         for n in prefix:
             lo = self.offsets[n][0]
-            key = (decays(n), self.lr_factor[n])
-            if runs and (runs[-1][2], runs[-1][3]) == key:
+            key = (decays(n), self.lr_factor[n], n in self.muon)
+            if runs and tuple(runs[-1][2:]) == key:
                 runs[-1][1] = lo + _pad64(numels[n])
             else:
-                runs.append([lo, lo + _pad64(numels[n]), key[0], key[1]])
-        self.adam_runs = [tuple(r) for r in runs]
+                runs.append([lo, lo + _pad64(numels[n]), *key])
+        self.adam_runs = [tuple(r[:4]) for r in runs if not r[4]]
         # all-reduce segments: one per group with a trainable tensor
         def group(n):
             return "head" if n.startswith("out_x_proj.") else ("embed" if _embedding_side(n) else _layer_of(n))
@@ -378,8 +386,17 @@ class GenieTrainer:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0,
                  gradient_accumulation_steps=1, lr_lambda=None, bucket_mb=64, group=None, recompute=False, dropout_seed=0,
                  ema_decay=None, ema_warmup=False, label_smoothing=0.0, z_loss=0.0, frame_weights=None, trainable=None, lr_scale=None,
-                 teacher=None, distill_alpha=0.0, distill_temperature=1.0, lora=None):
-        """lora: a LoraConfig: train low-rank adapters on the Linears its `targets` select (lora.py; include/genie_hip.h, "LoRA adapters").
+                 teacher=None, distill_alpha=0.0, distill_temperature=1.0, lora=None, muon=None):
+        """muon: a MuonConfig: the trainable tensors among the Linear weights its `targets` select (muon.py; include/genie_hip.h, "Muon") are
+        updated by Muon -- momentum, then a Newton-Schulz orthogonalisation of the update, f32 on the matrix cores in all three precisions --
+        and everything else (embeddings, positions, norms, biases, action tensors, LoRA adapters, an untargeted readout) by AdamW with the
+        bits it has today.  A fused qkv weight is three matrices (q, k, v rows), orthogonalised separately.  A frozen target is skipped (the
+        base weight of a LoRA-adapted Linear included); ValueError when no target trains.  The momentum lives in the tensor's `exp_avg`
+        range, its `exp_avg_sq` range stays zero; `lr_scale`, `decays(name)`, the schedule, the global clip and the EMA apply as for AdamW.
+        The matrices of all layers are sorted by shape and cut into tables of GENIE_MUON_MAX_ITEMS: one genie_muon_step call per table,
+        into one workspace sized for the largest.  `state_dict` carries the settings; `load_state_dict` raises ValueError for a state saved
+        under other settings or under the other optimizer.  None: the layout, launches and bits of before.
+        lora: a LoraConfig: train low-rank adapters on the Linears its `targets` select (lora.py; include/genie_hip.h, "LoRA adapters").
         Each adapted <linear>.weight keeps its base W0 in a trainer-owned f32 buffer (`self.w0`) and gains <linear>.lora_A (rank, in) and
         <linear>.lora_B (out, rank): not module parameters, but tensors of the flat buffers like any trainable one (ready order inside
         their layer's group, decaying; AdamW ranges, all-reduce segments, the norm, the clip, the EMA and `lr_scale` patterns cover them by
@@ -486,7 +503,12 @@ class GenieTrainer:
                 raise ValueError(f"{both[:4]} are adapted by `lora` and named by `trainable`: a weight trains fully or through its adapter")
             chosen = set(chosen or ()) | set(adapters)
         self.lr_scale = dict(lr_scale) if lr_scale else None
-        lay = self.layout = FlatLayout(self.config, {n: int(np.prod(s)) for n, s in shapes.items()}, chosen, self.lr_scale)
+        self.muon, muon_names = muon, ()
+        if muon is not None:
+            if not isinstance(muon, MuonConfig):
+                raise TypeError(f"muon must be a MuonConfig, got {type(muon).__name__}")
+            muon_names = _muon.muon_names(self.config, muon.targets, set(shapes) if chosen is None else chosen)
+        lay = self.layout = FlatLayout(self.config, {n: int(np.prod(s)) for n, s in shapes.items()}, chosen, self.lr_scale, muon_names)
         self.order, self.offsets, self.n_flat, self.n_train = lay.order, lay.offsets, lay.n_flat, lay.n_train
         self.trainable = [n for n in self.order if n in lay.trainable]   # the prefix, in ready order
         offs = self.offsets
@@ -547,6 +569,44 @@ class GenieTrainer:
         self._acts = self._ws = None
         self._B = 0
         self._d_rows = None   # (1 + B T, d) scratch: d loss / d rows of a model conditioned on action vectors, overwritten per call
+        if muon is not None:
+            self._muon_setup(muon_names, dev)
+
+    # ------------------------------------------------------------------ Muon
+    def _muon_setup(self, names, dev):
+        """The item tables (one per chunk of same-shape matrices) and the workspace, once: the pointers never move."""
+        self.muon_names = list(names)
+        entries = []   # MuonItems, each carrying its tensor's name (q, k and v of a fused qkv share one)
+        for n in self.muon_names:
+            lo = self.offsets[n][0]
+            for r0, rows, cols in _muon.blocks(n, self._shapes[n]):
+                off = 4 * (lo + r0 * cols)
+                it = _muon.item(rows, cols, self.params.data_ptr() + off, self.grads.data_ptr() + off, self.exp_avg.data_ptr() + off,
+                                None if self.ema is None else self.ema.data_ptr() + off)
+                it.name = n
+                entries.append(it)
+        self.muon_items = entries
+        self._muon_tables = [(part, *_muon.table(part)) for part in _muon.chunks(entries)]
+        need = 0
+        for _, arr, k in self._muon_tables:
+            b = self.lib.genie_muon_workspace_bytes(arr, k)
+            if b == 0:
+                _lib.check(_lib.E_ARG, "genie_muon_workspace_bytes")
+            need = max(need, b)
+        self._muon_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+
+    def muon_launches(self):
+        """Kernel launches of the Muon part of one optimizer step."""
+        return _muon.launches(self.muon_items, self.muon.ns_steps) if self.muon is not None else 0
+
+    def _muon_step(self, lr, mult, ss, clip, omd, st):
+        stg = _muon.settings(self.muon, grad_mult=mult, grad_sumsq=ss.data_ptr() if clip > 0 else None, max_grad_norm=clip,
+                             ema_one_minus_decay=0.0 if omd is None else omd)
+        for part, arr, k in self._muon_tables:
+            for i, it in enumerate(part):
+                arr[i].lr = lr * self.layout.lr_factor[it.name]
+                arr[i].weight_decay = self.weight_decay if decays(it.name) else 0.0
+            _lib.check(self.lib.genie_muon_step(arr, k, stg, self._muon_ws.data_ptr(), self._muon_ws.numel(), st), "genie_muon_step")
 
     # ------------------------------------------------------------------ LoRA adapters
     def _lora_setup(self, named, dev):
@@ -863,6 +923,8 @@ class GenieTrainer:
                 _lib.check(self.lib.genie_adamw_ema_step(
                     self.params.data_ptr() + off, self.grads.data_ptr() + off, self.exp_avg.data_ptr() + off,
                     self.exp_avg_sq.data_ptr() + off, self.ema.data_ptr() + off, *scalars, omd, st), "genie_adamw_ema_step")
+        if self.muon is not None:
+            self._muon_step(lr, mult, ss, clip, omd, st)
         self.completed_steps += 1
         if omd is not None:
             self.ema_updates += 1
@@ -966,6 +1028,8 @@ class GenieTrainer:
                          "gradient_accumulation_steps": self.accum, "recompute": bool(self.recompute),
                          "label_smoothing": self.label_smoothing, "z_loss": self.z_loss, "frame_weights": self.frame_weights,
                          "lr_scale": self.lr_scale}}
+        if self.muon is not None:   # (a trainer on AdamW alone keeps the state of before, key for key)
+            out["muon"] = dict(self.muon.settings_dict(), names=list(self.muon_names))
         if self._distilling:   # (a trainer that does not distil keeps the state of before, key for key)
             out["hyper"].update(distill_alpha=self.distill_alpha, distill_temperature=self.distill_temperature)
         if self.ema is not None:
@@ -980,6 +1044,13 @@ class GenieTrainer:
         one loaded into a trainer with EMA restarts the average from the current parameters, and a saved average loaded into a trainer
         without EMA is ignored -- each with a warning."""
         self._not_in_ema_scope("load_state_dict")
+        saved_muon = sd.get("muon")
+        mine_muon = None if self.muon is None else dict(self.muon.settings_dict(), names=list(self.muon_names))
+        norm = lambda d: None if d is None else {k: (tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in d.items()}   # noqa: E731
+        if norm(saved_muon) != norm(mine_muon):   # an exp_avg range means a Muon momentum on one side and Adam's first moment on the other
+            raise ValueError("GenieTrainer.load_state_dict: the state was saved under "
+                             + ("AdamW alone" if saved_muon is None else f"Muon settings {saved_muon}") + ", this trainer runs "
+                             + ("AdamW alone" if mine_muon is None else f"Muon settings {mine_muon}"))
         saved_ema = sd.get("ema")
         mine = {"lr": self.base_lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
                 "max_grad_norm": self.max_grad_norm, "gradient_accumulation_steps": self.accum,

@@ -1168,6 +1168,79 @@ int genie_lora_merge(const genie_lora_item* items, int n, void* stream);
 size_t genie_lora_project_scratch_bytes(const genie_lora_item* items, int n);
 int genie_lora_project(const genie_lora_item* items, int n, int accumulate, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Muon (additions; nothing above changes).  Jordan et al. 2024; counterpart: torch.optim.Muon.  Momentum, then a Newton-Schulz
+ * orthogonalisation of each target matrix's update.  For a matrix W (rows, cols), row-major f32, with this step's gradient g, momentum
+ * buffer B (same shape; starts at zero) and the settings below:
+ *      1. g' = coef * g                    coef = grad_mult * min(1, max_grad_norm / (grad_mult * sqrt(*grad_sumsq) + 1e-6)), the
+ *                                          coefficient of genie_adamw_step (grad_sumsq == NULL or max_grad_norm <= 0: grad_mult alone)
+ *      2. B  = mu * B + g'
+ *      3. u  = g' + mu * B  (nesterov)     u = B  (otherwise)
+ *      4. X  = u  if rows <= cols, else u^T                       -- X is (m, n) with m = min(rows, cols)
+ *      5. X  = X / max(||X||_F, eps)
+ *      6. ns_steps times:   A = X X^T;   P = b A + c A A;   X = a X + P X
+ *      7. O  = X, transposed back if it was transposed
+ *      8. W  = W * (1 - lr * weight_decay)
+ *      9. W  = W - (lr * adj) * O          adj = 0.2 * sqrt(max(rows, cols))      GENIE_MUON_ADJUST_MATCH_RMS_ADAMW
+ *                                          adj = sqrt(max(1, rows / cols))        GENIE_MUON_ADJUST_ORIGINAL
+ *     10. ema = ema - omd * (ema - W)      when the item's ema is not NULL: the line of "EMA of the weights", in the pass that writes W
+ * torch.optim.Muon keeps (1 - mu) B and forms (1 - mu) u (its lerp_ form): the same X after step 5, up to rounding and the eps clamp.
+ * It runs steps 4 to 7 in bf16; here they are f32 in all three training precisions (the relative distance of torch's bf16 iteration
+ * from a float64 one is 1e-2 on Gaussian and 0.4 .. 0.8 on low-rank inputs, of this one 1e-6 and 1e-5).
+ * Arithmetic, f32 with every operation rounded on its own (no contraction) unless said: steps 1 to 3 as written; ||X||_F^2 is summed
+ * in f64 in a fixed two-stage order (64 partial sums per matrix, each a grid-stride walk, added ascending), no atomics; step 5 is one
+ * more elementwise pass, x / max((float)sqrt(sum), eps), not folded into the first product.  A tall matrix is never transposed in
+ * memory: its products are A = X^T X and X = a X + X P on the stored (rows, cols) array.  Each product is a batched matrix-core GEMM
+ * C_i = beta * R_i + alpha * op(A_i) op(B_i) on v_mfma_f32_32x32x2_f32 over all matrices of one shape in ONE launch: an output element
+ * is the MFMA fmaf chain over k ascending from 0.0f, then (beta * r) + (alpha * acc) (without R: alpha * acc).  The order depends on
+ * the shape alone: the same input gives the same bits run to run, whatever other items share the launch and whatever the workspace
+ * held.  A and P are computed in full (all tiles; they come out bit-symmetric).  Step 8: decay = (float)(1.0 - (double) lr *
+ * weight_decay), s = (float)((double) lr * adj) with adj in double; W = (W * decay) - (s * O).
+ * genie_muon_step: 1 .. GENIE_MUON_MAX_ITEMS matrices of any mix of shapes.  Launches: one for steps 1 to 3 and the partial sums of the
+ * whole table, one for step 5, 3 * ns_steps per distinct (rows, cols) among the items, one for steps 8 to 10.  The table and the
+ * settings are read on the host during the call and travel to the kernels by value.  Reads grad; updates param, momentum and, when
+ * given, ema.  genie_newton_schulz: steps 4 to 7 alone on `batch` contiguous (rows, cols) matrices, in -> out (in == out allowed; any
+ * other overlap refused).  Workspace layout (both; bytes from genie_muon_workspace_bytes, for the unit entry point of `batch` items of
+ * (rows, cols)): [64 doubles per item | X0: every item's u, later X | X1: the same layout, the iteration's other buffer | A | P: the
+ * largest shape group's (m, m) Grams], every part 256-byte aligned.
+ * Validated before the device or the stream is touched, never allocating; refused with GENIE_E_ARG, every buffer as it was: a NULL
+ * table, settings, param, grad or momentum; n outside 1 .. GENIE_MUON_MAX_ITEMS; rows or cols not a positive multiple of 16; a
+ * pointer not 16-byte aligned; ns_steps outside 0 .. 99; an adjust mode that is neither; a momentum, coefficient, eps, grad_mult,
+ * max_grad_norm, lr or weight_decay that is not finite; omd outside [0, 1] when an ema is given; a NULL or misaligned workspace or
+ * fewer workspace_bytes than genie_muon_workspace_bytes, which returns 0 for a table it refuses. */
+#define GENIE_MUON_MAX_ITEMS 64
+#define GENIE_MUON_ADJUST_ORIGINAL 0
+#define GENIE_MUON_ADJUST_MATCH_RMS_ADAMW 1
+typedef struct genie_muon_item {
+    float* param;         /* (rows, cols) W */
+    const float* grad;    /* (rows, cols) g */
+    float* momentum;      /* (rows, cols) B */
+    float* ema;           /* (rows, cols) average of W, or NULL */
+    int32_t rows, cols;
+    float lr, weight_decay;
+} genie_muon_item;
+typedef struct genie_muon_settings {
+    float momentum;              /* mu */
+    float a, b, c;               /* the polynomial's coefficients */
+    float eps;                   /* floor of the norm in step 5 */
+    float grad_mult;             /* 1 / (world size * accumulation steps) */
+    float max_grad_norm;         /* <= 0: no clip */
+    float ema_one_minus_decay;   /* omd of step 10; read only when an item has an ema */
+    int32_t nesterov;            /* 0 / 1 */
+    int32_t ns_steps;            /* 0 .. 99 */
+    int32_t adjust;              /* GENIE_MUON_ADJUST_* */
+    int32_t reserved;            /* 0 */
+    const double* grad_sumsq;    /* device: the sum of squares of ALL gradients (genie_sumsq), or NULL */
+} genie_muon_settings;
+/* sizeof(genie_muon_item), the offsets of its eight fields, sizeof(genie_muon_settings) and the offsets of its thirteen fields, in
+ * declaration order: writes min(n, 23) entries, returns 23. */
+int genie_muon_layout(size_t* out_host, int n);
+size_t genie_muon_workspace_bytes(const genie_muon_item* items, int n);
+int genie_muon_step(const genie_muon_item* items, int n, const genie_muon_settings* settings, void* workspace, size_t workspace_bytes,
+                    void* stream);
+/* workspace_bytes: genie_muon_workspace_bytes of `batch` items of (rows, cols); 1 <= batch <= GENIE_MUON_MAX_ITEMS. */
+int genie_newton_schulz(const float* in, float* out, int rows, int cols, int batch, int steps, float a, float b, float c, float eps,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* Continuous per-frame actions (ABI 3 addition; nothing above changes).  A model conditioned on float action vectors of A values per
  * frame projects them, once per call, into the rows that genie_frame_cond addresses: the caller builds a table of one learned "no
  * action" row plus one projected row per frame of the call, points cond->table at it and cond->ids at "row of frame (b, t)", and every

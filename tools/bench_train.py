@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Time the HIP training step (forward + backward + clip + AdamW) on synthetic clips.
    python tools/bench_train.py --config c138 --batch 8 --steps 3
-   python tools/bench_train.py --config c138 --precision bf16 --batch 8 --breakdown --ema_decay 0.999 [--ema_unfused]"""
+   python tools/bench_train.py --config c138 --precision bf16 --batch 8 --breakdown --ema_decay 0.999 [--ema_unfused]
+   python tools/bench_train.py --config c138 --layers 4 --batch 8 --optimizer muon"""
 import argparse
 import importlib
 import os
@@ -55,6 +56,9 @@ def main():
     ap.add_argument("--freeze", type=str, default=None, metavar="P[,P...]", help="freeze the tensors matching these patterns")
     ap.add_argument("--lora_rank", type=int, default=0, help="train adapters of this rank instead of the weights (GenieTrainer(lora=LoraConfig(...)))")
     ap.add_argument("--lora_targets", type=str, default="decoder.layers.*", metavar="P[,P...]", help="with --lora_rank: the adapted Linears")
+    ap.add_argument("--optimizer", default="adamw", choices=["adamw", "muon"],
+                    help="muon: Muon on the Linear weights of every layer, AdamW on the rest (GenieTrainer(muon=MuonConfig()))")
+    ap.add_argument("--muon_ns_steps", type=int, default=5, help="with --optimizer muon: Newton-Schulz iterations")
     ap.add_argument("--teacher", default=None, choices=["c35", "c138"],
                     help="distil from a teacher of this shape (synthetic weights; GenieTrainer(teacher=...)): its forward runs in every step")
     ap.add_argument("--teacher_precision", default=None, choices=["exact", "f16x3", "bf16"], help="the teacher's precision (default: --precision)")
@@ -90,7 +94,8 @@ def main():
                                    label_smoothing=a.label_smoothing, z_loss=a.z_loss, frame_weights=fw, trainable=trainable,
                                    teacher=teacher, distill_alpha=a.distill_alpha if teacher is not None else 0.0,
                                    distill_temperature=a.distill_temperature,
-                                   lora=pkg("train").LoraConfig(rank=a.lora_rank, alpha=2.0 * a.lora_rank, targets=a.lora_targets) if a.lora_rank else None)
+                                   lora=pkg("train").LoraConfig(rank=a.lora_rank, alpha=2.0 * a.lora_rank, targets=a.lora_targets) if a.lora_rank else None,
+                                   muon=pkg("train").MuonConfig(ns_steps=a.muon_ns_steps) if a.optimizer == "muon" else None)
     if a.lora_rank:   # B = 0 would make dA exactly zero: time the step on adapters that have moved
         sd = tr.adapter_state_dict()
         g = torch.Generator(device="cuda").manual_seed(3)
@@ -141,8 +146,13 @@ def main():
         lib.genie_profile_enable(0x1F)
         lib.genie_profile_reset()
     t0 = time.perf_counter()
+    step_events = []   # every whole step between two events of its own as well: the median and the range beside the mean
     for _ in range(a.steps):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
         out = tr.train_step(batch)
+        ev[1].record()
+        step_events.append(ev)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
     tokens = a.batch * cfg.T * cfg.S
@@ -156,9 +166,17 @@ def main():
           f"{flops/dt/1e12:.1f} TFLOP/s (6ND), loss {float(out['loss']):.4f}, |g| {float(out['grad_norm']):.4f}, "
           f"acts {tr._acts.numel()/2**30:.1f} GiB, ws {tr._ws.numel()/2**30:.1f} GiB, "
           f"activation bytes saved / recomputed {act_bytes[0]} / {act_bytes[1]}")
+    sms = sorted(e0.elapsed_time(e1) for e0, e1 in step_events)
+    print(f"  whole step by events: median {sms[len(sms) // 2]:.3f} ms (min {sms[0]:.3f}, max {sms[-1]:.3f}) over {len(sms)} steps")
     ms = sorted(e0.elapsed_time(e1) for e0, e1 in opt_events)
     print(f"  optimizer_step: AdamW launches {len(tr.adam_runs) * (2 if a.ema_unfused else 1)}, {sum(ms) / len(ms):.3f} ms/step "
           f"(min {ms[0]:.3f}, median {ms[len(ms) // 2]:.3f}, max {ms[-1]:.3f}; {tr.n_flat * 4 / 1e9:.3f} GB per flat f32 buffer)")
+    if tr.muon is not None:
+        shapes = sorted({(it.rows, it.cols) for it in tr.muon_items})
+        flop = sum(tr.muon.ns_steps * (4.0 * min(it.rows, it.cols) ** 2 * max(it.rows, it.cols) + 2.0 * min(it.rows, it.cols) ** 3) for it in tr.muon_items)
+        print(f"  muon: {len(tr.muon_names)} tensors = {len(tr.muon_items)} matrices of shapes {shapes} in {len(tr._muon_tables)} tables, "
+              f"{tr.muon_launches()} launches per step beside the AdamW ones, {flop / 1e12:.3f} TFLOP of iterations per step "
+              f"(at least {flop / 157e12 * 1e3:.2f} ms at the 157 TFLOP/s f32 peak), workspace {tr._muon_ws.numel() / 2**20:.1f} MiB")
     if teacher is not None:
         tms = sorted(e0.elapsed_time(e1) for e0, e1 in teacher_events)
         print(f"  distillation: teacher {a.teacher} {a.teacher_precision or a.precision}, alpha {a.distill_alpha:g}, tau {a.distill_temperature:g}: "

@@ -120,6 +120,16 @@ def parse_args():
     p.add_argument("--lora_alpha", type=float, default=None, help="the adapters' scale is alpha / rank (default: 2 * rank)")
     p.add_argument("--lora_targets", type=str, default="decoder.layers.*", metavar="P[,P...]",
                    help="fnmatch patterns over the Linear weight names (six per layer and out_x_proj.weight)")
+    p.add_argument("--optimizer", choices=["adamw", "muon"], default="adamw",
+                   help="muon: Muon (momentum and a Newton-Schulz orthogonalisation of the update) on the trainable Linear weights "
+                        "--muon_targets selects, AdamW on everything else, under the one learning-rate schedule")
+    p.add_argument("--muon_momentum", type=float, default=0.95)
+    p.add_argument("--muon_ns_steps", type=int, default=5, help="Newton-Schulz iterations (0 .. 99)")
+    p.add_argument("--muon_targets", type=str, default="decoder.layers.*", metavar="P[,P...]",
+                   help="fnmatch patterns over the Linear weight names (six per layer and out_x_proj.weight)")
+    p.add_argument("--muon_adjust_lr", choices=["match_rms_adamw", "original"], default="match_rms_adamw",
+                   help="lr * 0.2 sqrt(max(rows, cols)) or lr * sqrt(max(1, rows / cols))")
+    p.add_argument("--muon_no_nesterov", action="store_true", help="plain momentum instead of Nesterov's")
     p.add_argument("--null_action", type=int, default=None, help="row of the action table that stands for 'no action'")
     p.add_argument("--synthetic", type=int, default=0, help="train on N synthetic clips (no dataset on disk)")
     p.add_argument("--model", choices=["c138", "c35", "tiny"], default="c35", help="shape when no --genie_config is given")
@@ -160,6 +170,14 @@ def main():
             sys.exit("train.py: --freeze has no meaning with --lora_rank (the adapters train, and what --train_only names)")
         if args.resume_from_checkpoint and not args.warmstart_path:
             sys.exit("train.py: resuming an adapter run needs the base model as --warmstart_path (the checkpoint holds merged weights)")
+    muon = None
+    if args.optimizer == "muon":
+        try:
+            muon = importlib.import_module("1xgpt_amd.train").MuonConfig(
+                momentum=args.muon_momentum, nesterov=not args.muon_no_nesterov, ns_steps=args.muon_ns_steps, targets=args.muon_targets,
+                adjust_lr=args.muon_adjust_lr)
+        except ValueError as e:
+            sys.exit(f"train.py: --muon_momentum / --muon_ns_steps / --muon_targets / --muon_adjust_lr: {e}")
     if args.mu_transfer:
         raise NotImplementedError("--mu_transfer needs the un-vendored mup fork (MuAdamW, set_base_shapes): not built")
     P = lambda n: importlib.import_module("1xgpt_amd." + n)  # noqa: E731
@@ -289,7 +307,7 @@ def main():
                                dropout_seed=args.dropout_seed, ema_decay=args.ema_decay, ema_warmup=args.ema_warmup,
                                label_smoothing=args.label_smoothing, z_loss=args.z_loss, frame_weights=frame_weights,
                                trainable=trainable, lr_scale=lr_scale, teacher=teacher, distill_alpha=args.distill_alpha,
-                               distill_temperature=args.distill_temperature, lora=lora)
+                               distill_temperature=args.distill_temperature, lora=lora, muon=muon)
     if args.resume_from_checkpoint and lora is not None:
         _, tensors = importlib.import_module("1xgpt_amd.lora").load_adapter_files(os.path.join(args.resume_from_checkpoint, "adapter"))
         tr.load_adapter_state_dict(tensors)
@@ -301,6 +319,9 @@ def main():
         if trainable is not None or lora is not None:
             print(f"training {len(tr.trainable)} of {len(tr.order)} tensors ({tr.n_train / 1e6:.2f} M of {tr.n_flat / 1e6:.1f} M flat "
                   f"elements); the backward stops at layer {tr.layout.stop}", flush=True)
+        if muon is not None:
+            print(f"muon on {len(tr.muon_names)} tensors ({len(tr.muon_items)} matrices, {tr.muon_launches()} launches per step), AdamW on the "
+                  f"other {len(tr.trainable) - len(tr.muon_names)}", flush=True)
         print(f"params {n_params / 1e6:.1f} M, {n_train} train windows, batch {B} x {accum} x {world}, "
               f"{max_steps} update steps, precision {args.precision}", flush=True)
 
