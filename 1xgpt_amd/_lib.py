@@ -351,6 +351,10 @@ SIGNATURES["genie_muon_step"] = (C.c_int, [C.POINTER(MuonItem), C.c_int, C.POINT
 SIGNATURES["genie_newton_schulz"] = (C.c_int, [c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
                                                c_ptr, C.c_size_t, c_ptr])
 
+# image-space metrics: (n, C, H, W) and (a, b, n, C, H, W, out, workspace, workspace_bytes, stream)
+SIGNATURES["genie_frame_metrics_workspace_bytes"] = (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int])
+SIGNATURES["genie_frame_metrics"] = (C.c_int, [c_ptr, c_ptr, C.c_int64, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr, C.c_size_t, c_ptr])
+
 _lib = None
 
 

@@ -235,6 +235,28 @@ int genie_action_rows_backward(const genie_action_proj* p, const float* vecs, co
     if (n == 0) return GENIE_OK;
     return launch_action_rows_backward(*p, vecs, d_rows, (long)n, d_model, d_weight, d_bias, accumulate, as_stream(stream));
 }
+static int check_frame_metrics(int64_t n, int C, int H, int W) {
+    GENIE_CHECK_ARG(n >= 0 && C >= 1, "genie_frame_metrics: n %lld, C %d must be >= 0, >= 1", (long long)n, C);
+    GENIE_CHECK_SHAPE(H >= 11 && W >= 11, "genie_frame_metrics: frames of %d x %d are smaller than the 11 x 11 SSIM window", H, W);
+    // one workgroup per (image, channel, tile); the first factor in double, so that the product cannot wrap
+    GENIE_CHECK_SHAPE((double)C * ((double)H / 32 + 1) * ((double)W / 32 + 1) < 2.0e9 && n <= 0x7fffffffL / frame_metrics_tiles(C, H, W),
+                      "genie_frame_metrics: n %lld x %d x %d x %d exceeds the 2^31 - 1 tiles of one call", (long long)n, C, H, W);
+    return GENIE_OK;
+}
+size_t genie_frame_metrics_workspace_bytes(int64_t n, int C, int H, int W) {
+    if (check_frame_metrics(n, C, H, W) != GENIE_OK) return 0;
+    return frame_metrics_workspace_bytes((long)n, C, H, W);
+}
+int genie_frame_metrics(const uint8_t* a, const uint8_t* b, int64_t n, int C, int H, int W, double* out, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    GENIE_CHECK_ARG(a && b && out, "genie_frame_metrics: NULL pointer");
+    GENIE_TRY(check_frame_metrics(n, C, H, W));
+    if (n == 0) return GENIE_OK;
+    const size_t need = frame_metrics_workspace_bytes((long)n, C, H, W);
+    GENIE_CHECK_ARG(workspace && workspace_bytes >= need && (uintptr_t)workspace % 8 == 0 && (uintptr_t)out % 8 == 0,
+                    "genie_frame_metrics: workspace of %zu bytes, %zu needed (8-byte aligned, like out)", workspace ? workspace_bytes : (size_t)0, need);
+    return launch_frame_metrics(a, b, (long)n, C, H, W, out, workspace, as_stream(stream));
+}
 const char* genie_last_error(void) { return g_err; }
 int genie_check_config(const genie_cfg* cfg) { return check_cfg(cfg); }
 

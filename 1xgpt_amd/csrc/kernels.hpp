@@ -536,4 +536,10 @@ int frames_pass(const genie_cfg* cfg, const genie_weights* wt, const int64_t* fr
                 size_t cache_bytes, float* logits, void* workspace, size_t workspace_bytes, void* stream, const genie_frame_cond* cond,
                 const FanOut* fan);
 
+// kernels_metrics.hip: image-space metrics of two (n, C, H, W) uint8 batches (genie_frame_metrics).  The caller has checked H, W >= 11 and
+// that n * frame_metrics_tiles (the workgroups of the launch, one workspace record each) is at most 2^31 - 1
+long frame_metrics_tiles(int C, int H, int W);
+size_t frame_metrics_workspace_bytes(long n, int C, int H, int W);
+int launch_frame_metrics(const uint8_t* a, const uint8_t* b, long n, int C, int H, int W, double* out, void* workspace, hipStream_t st);
+
 }  // namespace genie

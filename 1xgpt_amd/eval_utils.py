@@ -2,7 +2,8 @@
 
 ``compute_loss`` is the challenge metric (eval_utils.py:44-77): sum of the two 512-way cross-entropies,
 plain mean over B*(T-1)*H*W, returned as a Python float.  The reduction runs in the HIP factored-CE
-kernel; LPIPS (eval_utils.py:80-88) is out of scope.
+kernel; LPIPS (eval_utils.py:80-88) is out of scope and ``compute_image_metrics`` (PSNR, SSIM, MSE per
+frame, 1xgpt_amd/image_metrics.py) stands where ``compute_lpips`` does.
 """
 import torch
 
@@ -73,3 +74,13 @@ def decode_tokens(reshaped_token_ids, decode_latents):
     B, T = reshaped_token_ids.shape[:2]
     imgs = decode_latents(reshaped_token_ids.reshape(B * T, *reshaped_token_ids.shape[2:]))
     return imgs.reshape(B, T, *imgs.shape[1:])
+
+
+def compute_image_metrics(gtruth_frames, pred_frames, psnr_cap=None) -> dict:
+    """Given two batches of video data (B, T-1, 3, H, W) uint8 on the device, in ``compute_lpips``'s argument order (eval_utils.py:80-88),
+    the frame-by-frame PSNR, SSIM and MSE of the prediction against the ground truth: {"psnr", "ssim", "mse"}, each the flat list of
+    B * (T-1) floats that ``AvgMetric.update_list`` takes.  psnr_cap: the dB at which a frame with mse == 0 counts (None keeps inf)."""
+    from .image_metrics import frame_metrics
+    fm = frame_metrics(pred_frames, gtruth_frames)
+    psnr = fm.psnr if psnr_cap is None else fm.psnr.clamp(max=psnr_cap)
+    return {"psnr": psnr.flatten().tolist(), "ssim": fm.ssim.flatten().tolist(), "mse": fm.mse.flatten().tolist()}

@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 from .eval_utils import AvgMetric, compute_loss
+from .image_metrics import PSNR_CAP
 from .st_mask_git import STMaskGIT
 
 # Hardcoded values for the v1.1 dataset (evaluate.py:31-32)
@@ -168,8 +169,8 @@ class GenieEvaluator:
         return samples_THW, fl
 
     @torch.no_grad()
-    def evaluate_metric_sums_reuse(self, input_ids, labels=None, noise=None, action_ids=None, action_vectors=None):
-        """``evaluate_metric_sums`` on the prefix-reuse path (same six sums)."""
+    def evaluate_metric_sums_reuse(self, input_ids, labels=None, noise=None, action_ids=None, action_vectors=None, return_samples=False):
+        """``evaluate_metric_sums`` on the prefix-reuse path (same six sums; return_samples likewise)."""
         lib = _lib.load()
         m = self.model
         T, S = m.config.T, m.config.S
@@ -195,13 +196,13 @@ class GenieEvaluator:
         _lib.check(lib.genie_metric_hits(ids.data_ptr() + S * 8, T * S, samples.data_ptr(), (T - 1) * S, B, (T - 1) * S,
                                          ce.data_ptr(), float(B * (T - 1) * S), float(B * (T - 1)), float(B), sums.data_ptr(), st),
                    "genie_metric_hits")
-        return sums
+        return (sums, samples) if return_samples else sums
 
     @torch.no_grad()
-    def evaluate_metric_sums(self, input_ids, labels=None, noise=None, action_ids=None, action_vectors=None):
+    def evaluate_metric_sums(self, input_ids, labels=None, noise=None, action_ids=None, action_vectors=None, return_samples=False):
         """One batch of the metric loop (evaluate.py:167-179) as device-side sums, no logits materialised
         for the caller: returns float64 tensor [sum CE, n CE tokens, sum (gt == sample), n sampled tokens,
-        n frames, n clips]."""
+        n frames, n clips]; with return_samples also the sampled frames (B, T-1, H, W) the sums were taken from."""
         lib = _lib.load()
         m = self.model
         T, S = m.config.T, m.config.S
@@ -215,6 +216,7 @@ class GenieEvaluator:
         sizes = (float(B * (T - 1) * S), float(B * (T - 1)), float(B))
         m._check_cond(action_ids, B, action_vectors)   # (argument errors before anything is enqueued)
         sampling, unmask_mode = self._sampling()
+        kept = []
         for k, t in enumerate(range(1, T)):
             p = ids.clone()
             p[:, t:] = m.mask_token_id
@@ -229,16 +231,32 @@ class GenieEvaluator:
             _lib.check(lib.genie_factored_ce(cfg, lg.data_ptr(), _lib.LAYOUT_BCTHW, lab.data_ptr(), 0, B, t, t + 1,
                                              ce.data_ptr(), stream), "genie_factored_ce")
             s = s.contiguous()
+            if return_samples:
+                kept.append(s)
             # (ids[:, t] == s).sum() accumulated on the device; the last call also files the CE pair and the sizes
             _lib.check(lib.genie_metric_hits(ids.data_ptr() + t * S * 8, T * S, s.data_ptr(), S, B, S,
                                              ce.data_ptr() if t == T - 1 else 0, *sizes, sums.data_ptr(), stream),
                        "genie_metric_hits")
-        return sums
+        return (sums, torch.stack(kept, dim=1)) if return_samples else sums
+
+    @torch.no_grad()
+    def image_metric_sums(self, input_ids, samples_THW, psnr_cap=PSNR_CAP):
+        """Decode the sampled frames (B, T-1, H, W) and the ground-truth frames 1..T-1 of ``input_ids`` and score one against the other
+        (image_metrics.frame_metrics): returns the per-horizon sums over the batch as one f64 device tensor (4, T-1), rows
+        [sum MSE, sum PSNR with mse == 0 counted at psnr_cap dB, sum SSIM, n frames]; column k is predicted frame k + 1."""
+        from .eval_utils import decode_tokens
+        from .image_metrics import frame_metrics
+        m = self.model
+        gt = input_ids.to(self.device).to(torch.int64).view(-1, m.config.T, m.h, m.w)[:, 1:]
+        fm = frame_metrics(self.predict_next_frames(samples_THW), decode_tokens(gt, self.decode_latents))
+        return torch.stack([fm.mse.sum(0), fm.psnr.clamp(max=psnr_cap).sum(0), fm.ssim.sum(0),
+                            torch.full_like(fm.mse[0], float(gt.shape[0]))])
 
 
 @torch.no_grad()
 def evaluate_clips(evaluator: GenieEvaluator, clips: torch.LongTensor, batch_size=16, noise_seed=None,
-                   distributed=False, reuse=True, clip_offset=0, action_ids=None, action_vectors=None):
+                   distributed=False, reuse=True, clip_offset=0, action_ids=None, action_vectors=None, image_metrics=False,
+                   psnr_cap=PSNR_CAP):
     """Metric loop over ``clips`` (N, T*H*W) with the reference's AvgMetric weighting (eval_utils.py:16-25).
 
     With ``distributed=True`` every rank passes ITS shard of the clips; the six sums are all-reduced (SUM)
@@ -248,9 +266,18 @@ def evaluate_clips(evaluator: GenieEvaluator, clips: torch.LongTensor, batch_siz
     (noise_seed, global index of its first clip), so a job gives the same draws however it is sharded over ranks (given
     shard boundaries that are multiples of batch_size).
     action_ids: (N, T) per-frame actions of the clips (an action-conditioned model), sharded like them; action_vectors: (N, T, action_dim)
-    float actions of a model with config.action_dim > 0, sharded alike."""
+    float actions of a model with config.action_dim > 0, sharded alike.
+    image_metrics: also decode the predicted and the ground-truth frames (the evaluator needs ``decode_latents``) and score them in image
+    space (image_metrics.frame_metrics).  The total vector grows by the per-horizon sums -- for each of the T-1 predicted frame indices
+    sum MSE, sum PSNR, sum SSIM and the frame count -- which ride in the same single all-reduce; the returned dict gains ``psnr``,
+    ``ssim``, ``mse`` (whole-job means over all predicted frames) and ``psnr_per_frame``, ``ssim_per_frame``, ``mse_per_frame`` (lists of
+    length T-1: quality against horizon, entry k is predicted frame k + 1).  A frame with mse == 0 counts at ``psnr_cap`` dB.  Off, the
+    call enqueues and returns exactly what it did before the keyword existed."""
     dev = evaluator.device
-    total = torch.zeros(6, dtype=torch.float64, device=dev)
+    n_h = evaluator.model.config.T - 1
+    if image_metrics and evaluator.decode_latents is None:
+        raise RuntimeError("evaluate_clips(image_metrics=True) needs an evaluator with a decode_latents callable (1xgpt_amd.magvit2)")
+    total = torch.zeros(6 + (4 * n_h if image_metrics else 0), dtype=torch.float64, device=dev)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     m = evaluator.model
@@ -262,8 +289,14 @@ def evaluate_clips(evaluator: GenieEvaluator, clips: torch.LongTensor, batch_siz
             noise = torch.rand(m.config.T - 1, evaluator.args.maskgit_steps - 1, batch.shape[0], m.config.S,
                                generator=g).to(dev)
         fn = evaluator.evaluate_metric_sums_reuse if reuse else evaluator.evaluate_metric_sums
-        total += fn(batch, noise=noise, action_ids=None if action_ids is None else action_ids[i:i + batch_size],
+        cond = dict(action_ids=None if action_ids is None else action_ids[i:i + batch_size],
                     action_vectors=None if action_vectors is None else action_vectors[i:i + batch_size])
+        if image_metrics:
+            sums, samples = fn(batch, noise=noise, return_samples=True, **cond)
+            total[:6] += sums
+            total[6:] += evaluator.image_metric_sums(batch, samples, psnr_cap).reshape(-1)
+        else:
+            total += fn(batch, noise=noise, **cond)
     torch.cuda.synchronize()
     seconds = time.perf_counter() - t0
     if distributed:
@@ -273,13 +306,23 @@ def evaluate_clips(evaluator: GenieEvaluator, clips: torch.LongTensor, batch_siz
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         seconds = float(t.item())
     tot = total.tolist()
-    return dict(loss=tot[0] / tot[1], acc=tot[2] / tot[3], frames=int(tot[4]), clips=int(tot[5]), seconds=seconds,
-                frames_per_sec=tot[4] / seconds)
+    res = dict(loss=tot[0] / tot[1], acc=tot[2] / tot[3], frames=int(tot[4]), clips=int(tot[5]), seconds=seconds,
+               frames_per_sec=tot[4] / seconds)
+    if image_metrics:
+        mse, psnr, ssim, cnt = (tot[6 + k * n_h:6 + (k + 1) * n_h] for k in range(4))
+        for key, v in (("psnr", psnr), ("ssim", ssim), ("mse", mse)):
+            res[key] = sum(v) / sum(cnt)
+            res[key + "_per_frame"] = [a / c for a, c in zip(v, cnt)]
+    return res
 
 
-def run_reference_style_loop(evaluator: GenieEvaluator, batches, verbose=True):
-    """The reference's per-batch loop (evaluate.py:167-191) minus LPIPS: gen_time / loss / acc AvgMetrics."""
+def run_reference_style_loop(evaluator: GenieEvaluator, batches, verbose=True, decode_image_metrics=False, psnr_cap=PSNR_CAP):
+    """The reference's per-batch loop (evaluate.py:167-191) minus LPIPS: gen_time / loss / acc AvgMetrics.
+    decode_image_metrics: when on and the evaluator has ``decode_latents``, also what the reference does with LPIPS at evaluate.py:184-189:
+    decode the predicted and the ground-truth frames (``dec_time``) and add ``pred_psnr``, ``pred_ssim``, ``pred_mse`` per frame
+    (eval_utils.compute_image_metrics; a frame with mse == 0 counts at ``psnr_cap`` dB)."""
     from collections import defaultdict
+    from .eval_utils import compute_image_metrics, decode_tokens
     metrics = defaultdict(AvgMetric)
     T = evaluator.model.config.T
     for batch in batches:
@@ -296,6 +339,15 @@ def run_reference_style_loop(evaluator: GenieEvaluator, batches, verbose=True):
         acc = (gt[:, 1:] == samples).float().mean().item()
         metrics["loss"].update(loss, bs)
         metrics["acc"].update(acc, bs)
+        if decode_image_metrics and evaluator.decode_latents is not None:
+            torch.cuda.synchronize()
+            start = time.time()
+            pred_frames = evaluator.predict_next_frames(samples)
+            torch.cuda.synchronize()
+            metrics["dec_time"].update((time.time() - start) / frames_per_batch, bs)
+            decoded_gtruth = decode_tokens(gt, evaluator.decode_latents)
+            for key, vals in compute_image_metrics(decoded_gtruth[:, 1:], pred_frames, psnr_cap=psnr_cap).items():
+                metrics["pred_" + key].update_list(vals)
         if verbose:
             print({key: f"{val.mean():.4f}" for key, val in metrics.items()})
     return metrics

@@ -237,6 +237,14 @@ class VQModel(nn.Module):
         """(n, 3, H, W) uint8 -> (n, h, w) ids with the dataset bit convention."""
         return self.hip_encoder().encode_tokens(frames_u8)
 
+    @torch.no_grad()
+    def reconstruction_metrics(self, frames_u8: torch.Tensor):
+        """The tokenizer's own loss: (n, 3, H, W) uint8 -> image_metrics.FrameMetrics (mse, mae, psnr, ssim per frame, f64 on the device) of
+        decode_tokens(encode_tokens(frames)) against the frames."""
+        from .image_metrics import frame_metrics
+        frames = frames_u8.to(next(self.parameters()).device)
+        return frame_metrics(self.decode_tokens(self.encode_tokens(frames)), frames)
+
 
 def _check_widths(module, what):
     bad = sorted({m.out_filters for m in module.modules() if isinstance(m, ResBlock) and m.out_filters % 64} |

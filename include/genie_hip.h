@@ -1273,6 +1273,31 @@ int genie_action_rows(const genie_action_proj* p, const float* vecs, float* rows
 int genie_action_rows_backward(const genie_action_proj* p, const float* vecs, const float* d_rows, int64_t n, int d_model,
                                float* d_weight, float* d_bias, int accumulate, void* stream);
 
+/* Image-space metrics of two uint8 frame batches (ABI 3 addition; nothing above changes).  a and b are (n, C, H, W) planar uint8 device
+ * tensors, contiguous, as genie_conv_direct_bf16's uint8 output mode (HipDecoder.decode_tokens) leaves them.  Row i of out (n, 4) f64 is
+ *     sse      = sum over C*H*W of (a - b)^2                       -- exact (integer sums, < 2^53)
+ *     sae      = sum over C*H*W of |a - b|                         -- exact
+ *     ssim_sum = sum of the SSIM index (Wang, Bovik, Sheikh, Simoncelli 2004) over every valid window position of every channel
+ *     n_win    = C * (H - 10) * (W - 10)                           -- the number of those positions; mean SSIM = ssim_sum / n_win
+ * so that MSE = sse / (C*H*W), MAE = sae / (C*H*W), PSNR = 10 log10(255^2 / MSE).  The SSIM index is fixed to:
+ *     window   11 x 11 separable Gaussian, sigma 1.5: taps g_r = exp(-r^2 / 4.5), r = -5 .. 5, divided by their sum
+ *     moments  weighted, population: mu_x = sum g x, var_x = sum g x^2 - mu_x^2, cov_xy = sum g xy - mu_x mu_y (likewise y)
+ *     C1 = (0.01 * 255)^2 = 6.5025,  C2 = (0.03 * 255)^2 = 58.5225
+ *     SSIM     = (2 mu_x mu_y + C1)(2 cov_xy + C2) / ((mu_x^2 + mu_y^2 + C1)(var_x + var_y + C2))
+ *     border   none: only the (H - 10)(W - 10) windows that lie inside the image count (no padding)
+ * which is the image skimage.metrics.structural_similarity(gaussian_weights=True, sigma=1.5, use_sample_covariance=False, data_range=255)
+ * averages.  Moments are accumulated in f64 on pixel values pivoted by 128, so the variances do not cancel on flat frames; measured
+ * |SSIM - f64 model| per frame: DESIGN.md section 8.10.  Results are bit-identical run to run and do not depend on n (fixed-order sums, no
+ * float atomics).  Neither out nor the workspace is read before it is written.  Two launches; 64-bit element offsets.
+ * Reference counterpart: none (its image-space metric is LPIPS, eval_utils.py:80-88, which needs a network's weights).
+ * Errors, each before anything is enqueued, out and workspace untouched: NULL a / b / out, n < 0, C < 1, a NULL or short workspace at
+ * n > 0: GENIE_E_ARG; H < 11 or W < 11, or more than 2^31 - 1 tiles (n * C * ceil((H - 10) / 32) * ceil((W - 10) / 32)): GENIE_E_SHAPE.
+ * n == 0: success, nothing enqueued, nothing written. */
+/* bytes of workspace genie_frame_metrics needs (0 for arguments it refuses and for n == 0) */
+size_t genie_frame_metrics_workspace_bytes(int64_t n, int C, int H, int W);
+int genie_frame_metrics(const uint8_t* a, const uint8_t* b, int64_t n, int C, int H, int W, double* out, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,11 @@
   python tools/evaluate.py --synthetic 32 --model c138            # no checkpoint / dataset offline: synthetic weights + clips
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/evaluate.py ...   # data-parallel
 
-Prints the running means like the reference ({gen_time, loss, acc}); LPIPS is out of scope (needs the `lpips` AlexNet).
+  python tools/evaluate.py --synthetic 32 --model c35 --image_metrics   # + PSNR / SSIM / MSE of the decoded frames, per horizon
+
+Prints the running means like the reference ({gen_time, loss, acc}); LPIPS is out of scope (needs the `lpips` AlexNet): --image_metrics
+decodes the predicted and the ground-truth frames with the MAGVIT2 tokenizer (--tokenizer_ckpt; synthetic weights with --synthetic) and
+adds PSNR, SSIM and MSE, as whole-job means and against the prediction horizon.
 An action-conditioned checkpoint (action_vocab_size > 0) is evaluated with the dataset's actions.bin (refused without one)."""
 import argparse
 import importlib
@@ -35,6 +39,9 @@ def build_parser():
     ap.add_argument("--synthetic", type=int, default=0, help="evaluate N synthetic clips with synthetic weights")
     ap.add_argument("--model", choices=["c138", "c35"], default="c35", help="shape for --synthetic")
     ap.add_argument("--no_reuse", action="store_true", help="reference schedule (15 x steps full forwards)")
+    ap.add_argument("--image_metrics", action="store_true",
+                    help="decode predicted and ground-truth frames and report PSNR / SSIM / MSE (means and per prediction horizon)")
+    ap.add_argument("--tokenizer_ckpt", type=str, default="data/magvit2.ckpt", help="MAGVIT2 checkpoint for --image_metrics")
     return ap
 
 
@@ -70,7 +77,17 @@ def main():
             actions = ds.action_batch(range(n))
     args.latent_h = args.latent_w = side
     lo, hi = dist_mod.shard_range(clips.shape[0], rank, world)
-    ev = ev_mod.GenieEvaluator(args, None, dev, model=model)
+    decode_latents = None
+    if args.image_metrics:
+        mv = importlib.import_module("1xgpt_amd.magvit2")
+        vq = None
+        if args.synthetic:
+            vq = mv.VQModel(mv.VQConfig())
+            vq.load_state_dict({k: torch.from_numpy(v) for k, v in mv.make_vq_state_dict(vq, seed=1).items()})
+        elif not os.path.exists(args.tokenizer_ckpt):
+            sys.exit(f"evaluate.py: --image_metrics needs the tokenizer, and {args.tokenizer_ckpt} does not exist (--tokenizer_ckpt)")
+        decode_latents = mv.decode_latents_wrapper(batch_size=64, tokenizer_ckpt=args.tokenizer_ckpt, model=vq, device=dev)
+    ev = ev_mod.GenieEvaluator(args, decode_latents, dev, model=model)
     if args.adapter:
         try:
             ev.model.load_adapter(args.adapter)
@@ -78,10 +95,14 @@ def main():
             sys.exit(f"evaluate.py: --adapter {args.adapter}: {e}")
         print(f"adapter {args.adapter} merged", flush=True)
     res = ev_mod.evaluate_clips(ev, clips[lo:hi], batch_size=args.batch_size, distributed=world > 1,
-                                reuse=not args.no_reuse, action_ids=None if actions is None else actions[lo:hi])
+                                reuse=not args.no_reuse, action_ids=None if actions is None else actions[lo:hi],
+                                **(dict(image_metrics=True) if args.image_metrics else {}))
     if rank == 0:
         res["gen_time_s_per_frame"] = res["seconds"] / max(res["frames"], 1)
         print(json.dumps(res))
+        if args.image_metrics:
+            print(f"loss {res['loss']:.4f}  acc {res['acc']:.4f}  PSNR {res['psnr']:.3f} dB  SSIM {res['ssim']:.4f}  MSE {res['mse']:.2f}")
+            print("PSNR by horizon (dB): " + " ".join(f"{v:.2f}" for v in res["psnr_per_frame"]))
 
 
 if __name__ == "__main__":
