@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("GENIE_HIP_LIBRARY") or os.path.join(HERE, "libgenie_h
 PREC_EXACT, PREC_BF16, PREC_F16X3 = 0, 1, 2
 LAYOUT_TOKEN_MAJOR, LAYOUT_BCTHW = 0, 1
 UNMASK_RANDOM, UNMASK_GREEDY, UNMASK_CONFIDENCE = 0, 1, 2
+SPATIAL_BWD_AUTO, SPATIAL_BWD_FUSED, SPATIAL_BWD_MATERIALISED, SPATIAL_BWD_BF16 = 0, 1, 2, 3
 KC_GEMM, KC_ATTN_SPATIAL, KC_ATTN_TEMPORAL, KC_LAYERNORM, KC_OTHER, KC_FUSED = range(6)
 E_ARG, E_SHAPE, E_UNSUPPORTED, E_LAUNCH, E_ASSERT = -1, -2, -3, -4, -5
 
@@ -190,6 +191,13 @@ SIGNATURES = {
                                                   C.c_int, c_ptr, c_ptr, C.POINTER(FrameCond)]),
     "genie_temporal_attention_backward": (C.c_int, [c_ptr, c_ptr, C.c_int64, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int,
                                                     C.c_int, C.c_int, C.c_float, c_ptr]),
+    "genie_spatial_attention_backward_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "genie_spatial_attention_backward": (C.c_int, [c_ptr, c_ptr, C.c_int64, c_ptr, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                   C.c_int, C.c_float, C.c_int, c_ptr, C.c_size_t, c_ptr]),
+    "genie_qk_norm_forward": (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_int64, C.c_int, C.c_int, c_ptr]),
+    "genie_qk_norm_backward_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "genie_qk_norm_backward": (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, C.c_int64, C.c_int, C.c_int, C.c_int, c_ptr,
+                                         C.c_size_t, c_ptr]),
     "genie_sumsq": (C.c_int, [c_ptr, C.c_size_t, c_ptr, c_ptr, c_ptr]),
     "genie_adamw_step": (C.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float,
                                    C.c_float, C.c_int, C.c_float, c_ptr, C.c_float, c_ptr]),

@@ -393,6 +393,10 @@ int launch_attn_temporal_bwd(const float* qkv, const float* qk, long qk_ld, cons
                              int S, int d, int H, int Dh, float scale, hipStream_t st);
 int launch_attn_spatial_bwd_fused(const float* qkv, const float* qk, long qk_ld, const float* dO, float* dqkv, long n_bt, int S,
                                   int d, int H, int Dh, float scale, hipStream_t st);
+// the geometries the fused kernel takes (its launcher answers GENIE_E_UNSUPPORTED for the others)
+inline bool attn_spatial_bwd_fused_takes(int S, int Dh) { return S == 256 && (Dh == 64 || Dh == 32); }
+// floats of `part` behind launch_qk_norm_bwd (0: head_dim not in {32, 64, 128})
+size_t qk_norm_bwd_scratch_floats(int Dh);
 int launch_qk_norm_fwd(const float* qkv, float* qkn, const float* nw, const float* nb, long M, int H, int Dh, int d,
                        hipStream_t st);
 int launch_qk_norm_bwd(const float* qkv, float* dqkv, const float* nw, float* dnw, float* dnb, long M, int H, int Dh,
@@ -400,6 +404,9 @@ int launch_qk_norm_bwd(const float* qkv, float* dqkv, const float* nw, float* dn
 // kernels_attn_bwd16.hip: spatial attention backward on the bf16 matrix cores (bf16 training precision)
 int launch_attn_spatial_bwd_bf16(const float* qkv, const float* qk, long qk_ld, const float* dO, float* dqkv, float* stats, long n_bt,
                                  int S, int d, int H, int Dh, float scale, hipStream_t st);
+inline bool attn_spatial_bwd_bf16_takes(int S, int Dh, long qk_ld, int d) {
+    return S == 256 && (Dh == 64 || Dh == 32) && qk_ld % 4 == 0 && d % 4 == 0;
+}
 // the operand form of src (M, N) f32 as that call's G16X_OUT16 epilogue writes it for (M, N, K), row-major operands (kernels_bf16.hip)
 int launch_cast16_like_gemm(int npl, const float* src, uint16_t* dst, int M, int N, int K, int flags, hipStream_t st);
 // kernels_gemm_sm.hip: small (latency-bound) problems; GENIE_E_UNSUPPORTED = not small / tiling does not fit

@@ -793,7 +793,7 @@ __global__ __launch_bounds__(256, 1) void attn_spatial_bwd_fused_kernel(const fl
 // GENIE_E_UNSUPPORTED for other geometries (the caller then takes the materialised-scores path)
 int launch_attn_spatial_bwd_fused(const float* qkv, const float* qk, long qk_ld, const float* dO, float* dqkv, long n_bt, int S,
                                   int d, int H, int Dh, float scale, hipStream_t st) {
-    if (S != 256 || (Dh != 64 && Dh != 32)) return GENIE_E_UNSUPPORTED;
+    if (!attn_spatial_bwd_fused_takes(S, Dh)) return GENIE_E_UNSUPPORTED;
     if (n_bt <= 0) return GENIE_OK;
     const size_t lds = (size_t)((2 * 256 + 2 * 32) * (Dh + 4) + 12 * 32 + 3 * 256) * sizeof(float);
     ProfScope prof(GENIE_KC_ATTN_SPATIAL, 14.0 * S * S * Dh * (double)n_bt * H, 4.0 * 10 * S * Dh * (double)n_bt * H, st,
@@ -924,6 +924,10 @@ int launch_qk_norm_bwd(const float* qkv, float* dqkv, const float* nw, float* dn
     GENIE_TRY(launch_slab_reduce(part, QKN_BLOCKS, (size_t)2 * Dh, tmp, 0.f, st, "slab_reduce_norm"));
     if (dnw) GENIE_TRY(launch_slab_reduce(tmp, 1, (size_t)Dh, dnw, beta, st, "slab_reduce_norm"));
     return dnb ? launch_slab_reduce(tmp + Dh, 1, (size_t)Dh, dnb, beta, st, "slab_reduce_norm") : GENIE_OK;
+}
+// part[QKN_BLOCKS][2][Dh] and the reduced [2][Dh] behind it
+size_t qk_norm_bwd_scratch_floats(int Dh) {
+    return (Dh == 32 || Dh == 64 || Dh == 128) ? (size_t)(QKN_BLOCKS + 1) * 2 * Dh : 0;
 }
 
 }  // namespace genie

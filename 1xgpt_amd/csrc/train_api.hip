@@ -232,38 +232,44 @@ static int qk_norm_backward(const genie_cfg& c, const genie_attn_weights& aw, co
                               c.head_dim, c.d_model, beta, w.lnpart, st);
 }
 
-// spatial attention backward through materialised scores: qkv (M,3d), dao (M,d) -> dqkv (M,3d)
-static int spatial_attn_bwd(const genie_cfg& c, const float* qkv, QkSrc qk, const float* dao, float* dqkv, TrainWs& w,
-                            int B, hipStream_t st) {
-    const int S = c.S, d = c.d_model, H = c.num_heads, Dh = c.head_dim, BT = B * c.T;
+// spatial attention backward: qkv (BT*S,3d), dao (BT*S,d) -> dqkv (BT*S,3d), by the implementation `path` names
+// (GENIE_SPATIAL_BWD_*).  A forced path that does not take the geometry answers GENIE_E_UNSUPPORTED with nothing enqueued; AUTO is
+// the fused f32 kernel where it takes the geometry, else the materialised scores.  Scratch: p and dp hold BT*H*S*S floats each for the
+// materialised path; the bf16 pair keeps its row statistics (BT*H*S*4 floats) in p; the fused kernel reads neither.
+static int spatial_attn_bwd(const float* qkv, QkSrc qk, const float* dao, float* dqkv, float* p, float* dp, int BT, int S, int d,
+                            int H, int Dh, float sc, int path, hipStream_t st) {
     const long q3 = (long)S * 3 * d, ss = (long)S * S, hss = (long)H * ss, sd = (long)S * d;
     const long qld = qk.ld, qs = (long)S * qk.ld;
-    const float sc = c.attn_scale;
-    if (c.precision == GENIE_PREC_BF16) {   // bf16 training: the backward products on the bf16 matrix cores as well
-        const int rc = launch_attn_spatial_bwd_bf16(qkv, qk.p, qk.ld, dao, dqkv, w.p, BT, S, d, H, Dh, sc, st);
-        if (rc != GENIE_E_UNSUPPORTED) return rc;
-    }
-    {   // production geometry: fused kernel, no S x S traffic
+    if (path == GENIE_SPATIAL_BWD_BF16)     // the backward products on the bf16 matrix cores as well
+        return launch_attn_spatial_bwd_bf16(qkv, qk.p, qk.ld, dao, dqkv, p, BT, S, d, H, Dh, sc, st);
+    if (path != GENIE_SPATIAL_BWD_MATERIALISED) {   // production geometry: fused kernel, no S x S traffic
         const int rc = launch_attn_spatial_bwd_fused(qkv, qk.p, qk.ld, dao, dqkv, BT, S, d, H, Dh, sc, st);
-        if (rc != GENIE_E_UNSUPPORTED) return rc;
+        if (path == GENIE_SPATIAL_BWD_FUSED || rc != GENIE_E_UNSUPPORTED) return rc;
     }
     // P = softmax(scale Q K^T)
-    GENIE_TRY(launch_gemm_f32_gen(false, false, qk.p, qld, qs, Dh, qk.p + d, qld, qs, Dh, nullptr, nullptr, w.p, S, hss,
+    GENIE_TRY(launch_gemm_f32_gen(false, false, qk.p, qld, qs, Dh, qk.p + d, qld, qs, Dh, nullptr, nullptr, p, S, hss,
                                   ss, S, S, Dh, BT, H, 1, 0, sc, st));
-    GENIE_TRY(launch_softmax_rows(w.p, (long)BT * H * S, S, st));
+    GENIE_TRY(launch_softmax_rows(p, (long)BT * H * S, S, st));
     // dV = P^T dO
-    GENIE_TRY(launch_gemm_f32_gen(true, true, w.p, S, hss, ss, dao, d, sd, Dh, nullptr, nullptr, dqkv + 2 * d, 3 * d, q3,
+    GENIE_TRY(launch_gemm_f32_gen(true, true, p, S, hss, ss, dao, d, sd, Dh, nullptr, nullptr, dqkv + 2 * d, 3 * d, q3,
                                   Dh, S, Dh, S, BT, H, 1, 0, 1.0f, st));
     // dP = dO V^T, dS = P (dP - rowsum(P dP))
-    GENIE_TRY(launch_gemm_f32_gen(false, false, dao, d, sd, Dh, qkv + 2 * d, 3 * d, q3, Dh, nullptr, nullptr, w.dp, S, hss,
+    GENIE_TRY(launch_gemm_f32_gen(false, false, dao, d, sd, Dh, qkv + 2 * d, 3 * d, q3, Dh, nullptr, nullptr, dp, S, hss,
                                   ss, S, S, Dh, BT, H, 1, 0, 1.0f, st));
-    GENIE_TRY(launch_softmax_bwd_rows(w.p, w.dp, (long)BT * H * S, S, st));
+    GENIE_TRY(launch_softmax_bwd_rows(p, dp, (long)BT * H * S, S, st));
     // dQ = scale dS K,  dK = scale dS^T Q
-    GENIE_TRY(launch_gemm_f32_gen(false, true, w.dp, S, hss, ss, qk.p + d, qld, qs, Dh, nullptr, nullptr, dqkv, 3 * d, q3,
+    GENIE_TRY(launch_gemm_f32_gen(false, true, dp, S, hss, ss, qk.p + d, qld, qs, Dh, nullptr, nullptr, dqkv, 3 * d, q3,
                                   Dh, S, Dh, S, BT, H, 1, 0, sc, st));
-    GENIE_TRY(launch_gemm_f32_gen(true, true, w.dp, S, hss, ss, qk.p, qld, qs, Dh, nullptr, nullptr, dqkv + d, 3 * d, q3,
+    GENIE_TRY(launch_gemm_f32_gen(true, true, dp, S, hss, ss, qk.p, qld, qs, Dh, nullptr, nullptr, dqkv + d, 3 * d, q3,
                                   Dh, S, Dh, S, BT, H, 1, 0, sc, st));
     return GENIE_OK;
+}
+// the training step's choice: the bf16 precision takes the bf16 pair where that takes the geometry (GENIE_ATTN_BWD16=0 in a study
+// build: never), every other case the f32 kernels
+static int train_spatial_bwd_path(const genie_cfg& c, long qk_ld) {
+    static const int bwd16 = study_env("GENIE_ATTN_BWD16", 1);
+    return c.precision == GENIE_PREC_BF16 && bwd16 && attn_spatial_bwd_bf16_takes(c.S, c.head_dim, qk_ld, c.d_model)
+               ? GENIE_SPATIAL_BWD_BF16 : GENIE_SPATIAL_BWD_AUTO;
 }
 
 struct TrainWs16 {
@@ -663,7 +669,8 @@ static int train_backward_layer(Ops& o, const genie_weights* wt, const genie_wei
     // ---- spatial: x1 = x0 + proj(attn(qkv(norm1(x0))))  (st_transformer.py:73-74)
     GENIE_TRY(o.linear_backward(dx, X(a.aos), n.proj_s, nullptr, nullptr, w.d1));
     GENIE_TRY(qk_source(c, lw.spatial, F(a.qkvs), w, B, &qk, st));
-    GENIE_TRY(spatial_attn_bwd(c, F(a.qkvs), qk, w.d1, w.g, w, B, st));
+    GENIE_TRY(spatial_attn_bwd(F(a.qkvs), qk, w.d1, w.g, w.p, w.dp, B * c.T, c.S, d, c.num_heads, c.head_dim, c.attn_scale,
+                               train_spatial_bwd_path(c, qk.ld), st));
     GENIE_TRY(qk_norm_backward(c, lw.spatial, g.spatial, F(a.qkvs), w.g, w, B, beta, st));
     if (c.qk_norm) return o.linear_backward(w.g, p.u1, n.qkv_s, nullptr, dx, dx);
     GENIE_TRY(o.linear_backward(w.g, p.u1, n.qkv_s, nullptr, nullptr, w.d1));               // d norm1 output
@@ -907,6 +914,79 @@ int genie_temporal_attention_backward(const float* qkv, const float* qk, int64_t
                       "genie_temporal_attention_backward: qk_ld %ld is neither 2*d_model nor 3*d_model", (long)qk_ld);
     return launch_attn_temporal_bwd(qkv, qk, (long)qk_ld, d_out, d_qkv, B, T, S, d_model, num_heads, head_dim, scale,
                                     (hipStream_t)stream);
+}
+
+// the two scratch slots of spatial_attn_bwd behind one workspace pointer: byte offset of the second one (= the first one's size)
+static size_t spatial_bwd_slot_bytes(int path, size_t n_frames, size_t S, size_t H) {
+    size_t floats = 0;
+    if (path == GENIE_SPATIAL_BWD_MATERIALISED) floats = n_frames * H * S * S;
+    else if (path == GENIE_SPATIAL_BWD_BF16) floats = n_frames * H * S * 4;
+    return (floats * 4 + 255) / 256 * 256;
+}
+static size_t spatial_bwd_bytes(int path, size_t n_frames, size_t S, size_t H) {
+    return spatial_bwd_slot_bytes(path, n_frames, S, H) * (path == GENIE_SPATIAL_BWD_MATERIALISED ? 2 : 1);
+}
+
+size_t genie_spatial_attention_backward_workspace_bytes(int path, int n_frames, int S, int num_heads) {
+    if (path < GENIE_SPATIAL_BWD_AUTO || path > GENIE_SPATIAL_BWD_BF16 || n_frames <= 0 || S <= 0 || num_heads <= 0) return 0;
+    if (path == GENIE_SPATIAL_BWD_AUTO) path = GENIE_SPATIAL_BWD_MATERIALISED;
+    return spatial_bwd_bytes(path, (size_t)n_frames, (size_t)S, (size_t)num_heads);
+}
+
+int genie_spatial_attention_backward(const float* qkv, const float* qk, int64_t qk_ld, const float* d_out, float* d_qkv,
+                                     int n_frames, int S, int d_model, int num_heads, int head_dim, float scale, int path,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+    GENIE_CHECK_ARG(qkv && qk && d_out && d_qkv && n_frames > 0, "genie_spatial_attention_backward: NULL argument or n_frames <= 0");
+    GENIE_CHECK_ARG(S > 0 && d_model > 0 && num_heads > 0 && head_dim > 0,
+                    "genie_spatial_attention_backward: S, d_model, num_heads, head_dim must be positive");
+    GENIE_CHECK_ARG(path >= GENIE_SPATIAL_BWD_AUTO && path <= GENIE_SPATIAL_BWD_BF16,
+                    "genie_spatial_attention_backward: path %d is not a GENIE_SPATIAL_BWD_* value", path);
+    GENIE_CHECK_SHAPE(S % 16 == 0 && head_dim % 16 == 0, "genie_spatial_attention_backward: S=%d and head_dim=%d must be multiples of 16",
+                      S, head_dim);
+    GENIE_CHECK_SHAPE((long)head_dim * num_heads == d_model, "genie_spatial_attention_backward: head_dim %d * num_heads %d != d_model %d",
+                      head_dim, num_heads, d_model);
+    GENIE_CHECK_SHAPE(qk_ld == 2L * d_model || qk_ld == 3L * d_model,
+                      "genie_spatial_attention_backward: qk_ld %ld is neither 2*d_model nor 3*d_model", (long)qk_ld);
+    const bool takes = path == GENIE_SPATIAL_BWD_FUSED  ? attn_spatial_bwd_fused_takes(S, head_dim)
+                       : path == GENIE_SPATIAL_BWD_BF16 ? attn_spatial_bwd_bf16_takes(S, head_dim, (long)qk_ld, d_model)
+                                                        : true;
+    if (!takes) {
+        set_error("genie_spatial_attention_backward: path %d does not take S=%d, head_dim=%d (S = 256 and head_dim 32 / 64)", path, S,
+                  head_dim);
+        return GENIE_E_UNSUPPORTED;
+    }
+    // what AUTO will run decides what it needs
+    const int taken = path != GENIE_SPATIAL_BWD_AUTO               ? path
+                      : attn_spatial_bwd_fused_takes(S, head_dim) ? GENIE_SPATIAL_BWD_FUSED
+                                                                  : GENIE_SPATIAL_BWD_MATERIALISED;
+    const size_t slot = spatial_bwd_slot_bytes(taken, (size_t)n_frames, (size_t)S, (size_t)num_heads);
+    const size_t need = spatial_bwd_bytes(taken, (size_t)n_frames, (size_t)S, (size_t)num_heads);
+    GENIE_CHECK_ARG(need == 0 || (workspace && workspace_bytes >= need),
+                    "genie_spatial_attention_backward: workspace too small or NULL: %zu < %zu", workspace ? workspace_bytes : (size_t)0, need);
+    float* p = need ? (float*)workspace : nullptr;
+    float* dp = need ? (float*)((char*)workspace + slot) : nullptr;
+    return spatial_attn_bwd(qkv, QkSrc{qk, (long)qk_ld}, d_out, d_qkv, p, dp, n_frames, S, d_model, num_heads, head_dim, scale, path,
+                            (hipStream_t)stream);
+}
+
+int genie_qk_norm_forward(const float* qkv, float* qkn, const float* norm_w, const float* norm_b, int64_t rows, int num_heads,
+                          int head_dim, void* stream) {
+    GENIE_CHECK_ARG(qkv && qkn && norm_w && norm_b && rows > 0, "genie_qk_norm_forward: NULL argument or rows <= 0");
+    GENIE_CHECK_ARG(num_heads > 0 && head_dim > 0, "genie_qk_norm_forward: num_heads and head_dim must be positive");
+    return launch_qk_norm_fwd(qkv, qkn, norm_w, norm_b, (long)rows, num_heads, head_dim, num_heads * head_dim, (hipStream_t)stream);
+}
+
+size_t genie_qk_norm_backward_scratch_bytes(int head_dim) { return qk_norm_bwd_scratch_floats(head_dim) * sizeof(float); }
+
+int genie_qk_norm_backward(const float* qkv, float* d_qkv, const float* norm_w, float* d_norm_w, float* d_norm_b, int64_t rows,
+                           int num_heads, int head_dim, int accumulate, void* scratch, size_t scratch_bytes, void* stream) {
+    GENIE_CHECK_ARG(qkv && d_qkv && norm_w && rows > 0, "genie_qk_norm_backward: NULL argument or rows <= 0");
+    GENIE_CHECK_ARG(num_heads > 0 && head_dim > 0, "genie_qk_norm_backward: num_heads and head_dim must be positive");
+    const size_t need = (d_norm_w || d_norm_b) ? genie_qk_norm_backward_scratch_bytes(head_dim) : 0;
+    GENIE_CHECK_ARG(need == 0 || (scratch && scratch_bytes >= need), "genie_qk_norm_backward: scratch too small or NULL: %zu < %zu",
+                    scratch ? scratch_bytes : (size_t)0, need);
+    return launch_qk_norm_bwd(qkv, d_qkv, norm_w, d_norm_w, d_norm_b, (long)rows, num_heads, head_dim, num_heads * head_dim,
+                              accumulate ? 1.0f : 0.0f, (float*)scratch, (hipStream_t)stream);
 }
 
 int genie_dropout_layout(size_t* out_host, int n) {

@@ -1064,6 +1064,48 @@ int genie_temporal_attention_backward(const float* qkv, const float* qk, int64_t
                                       float* d_qkv, int B, int T, int S, int d_model, int num_heads, int head_dim,
                                       float scale, void* stream);
 
+/* The spatial (non-causal, over the S tokens of one frame) attention backward of the step, alone, by the implementation `path`
+ * names.  qkv (n_frames,S,3*d_model) is the saved q | k | v; qk, qk_ld and d_out (n_frames,S,d_model) as above; d_qkv
+ * (n_frames,S,3*d_model) is OVERWRITTEN with dq | dk | dv:
+ *     p = softmax_j(scale q_i.k_j);  dp = d_out_i.v_j;  ds = p (dp - sum_j p dp);
+ *     dq = scale ds K;  dk = scale ds^T Q;  dv = p^T d_out
+ * in a fixed summation order, no atomics: the same bytes run to run.  This is the dispatch the training step runs: the step passes
+ * GENIE_SPATIAL_BWD_BF16 in the bf16 precision where that path takes the geometry and GENIE_SPATIAL_BWD_AUTO everywhere else.
+ *   AUTO          f32: FUSED where it takes the geometry, else MATERIALISED
+ *   FUSED         one f32 kernel, nothing of size S x S in memory; S = 256 and head_dim 32 / 64
+ *   MATERIALISED  f32 scores in the workspace (five batched GEMMs and a row softmax pair); every S, head_dim that are multiples of 16
+ *   BF16          the two kernels of the bf16 precision (operands of every product rounded to bf16, f32 accumulation and softmax);
+ *                 S = 256 and head_dim 32 / 64
+ * genie_spatial_attention_backward_workspace_bytes: what `workspace` must hold for that path (0: none, workspace may be NULL; AUTO
+ * answers for MATERIALISED, which covers either outcome; an unknown path, n_frames, S or num_heads <= 0: 0).
+ * NULL qkv / qk / d_out / d_qkv, n_frames <= 0, a non-positive dimension, an unknown path: GENIE_E_ARG; S or head_dim not a multiple of
+ * 16, head_dim * num_heads != d_model, qk_ld not 2*d_model or 3*d_model: GENIE_E_SHAPE; FUSED or BF16 outside their geometry:
+ * GENIE_E_UNSUPPORTED; a workspace smaller than the path taken needs (or NULL where it needs one): GENIE_E_ARG -- all before the
+ * device or the stream is touched, d_qkv untouched. */
+enum { GENIE_SPATIAL_BWD_AUTO = 0, GENIE_SPATIAL_BWD_FUSED = 1, GENIE_SPATIAL_BWD_MATERIALISED = 2, GENIE_SPATIAL_BWD_BF16 = 3 };
+size_t genie_spatial_attention_backward_workspace_bytes(int path, int n_frames, int S, int num_heads);
+int genie_spatial_attention_backward(const float* qkv, const float* qk, int64_t qk_ld, const float* d_out, float* d_qkv,
+                                     int n_frames, int S, int d_model, int num_heads, int head_dim, float scale, int path,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* qk-norm (LayerNorm over head_dim of every q and k head row, eps 1e-5, ONE affine norm_w / norm_b (head_dim) shared by q, k and all
+ * heads), alone; head_dim 32 / 64 / 128 (others: GENIE_E_UNSUPPORTED), d_model = num_heads * head_dim.
+ * genie_qk_norm_forward: qkv (rows,3*d_model) -> qkn (rows,2*d_model) = [LN(q) | LN(k)], the operands the attention backwards read with
+ * qk_ld = 2*d_model.
+ * genie_qk_norm_backward: d_qkv (rows,3*d_model) holds d loss / d (normalised q | k) in its q | k columns and is turned IN PLACE into
+ * d loss / d (raw q | k); its v columns are neither read nor written.  d_norm_w / d_norm_b (head_dim) receive the affine's gradient
+ * summed over rows, q and k, and heads (accumulate != 0: added to what they hold; 0: overwritten), in a fixed order.  A NULL d_norm_w
+ * or d_norm_b is a frozen tensor ("Frozen tensors" above): nothing is written for it; both NULL: no reduction runs and `scratch` is not
+ * touched (it may be NULL).  Otherwise scratch holds genie_qk_norm_backward_scratch_bytes(head_dim) bytes (0 for an unsupported
+ * head_dim).
+ * NULL qkv / qkn / norm_w / norm_b / d_qkv, rows, num_heads or head_dim <= 0, a scratch that is too small: GENIE_E_ARG, before the
+ * device or the stream is touched. */
+int genie_qk_norm_forward(const float* qkv, float* qkn, const float* norm_w, const float* norm_b, int64_t rows, int num_heads,
+                          int head_dim, void* stream);
+size_t genie_qk_norm_backward_scratch_bytes(int head_dim);
+int genie_qk_norm_backward(const float* qkv, float* d_qkv, const float* norm_w, float* d_norm_w, float* d_norm_b, int64_t rows,
+                           int num_heads, int head_dim, int accumulate, void* scratch, size_t scratch_bytes, void* stream);
+
 /* *out += sum x[i]^2 in f64, two-stage with a fixed order (scratch: 1024 doubles).  The global gradient norm of
  * clip_grad_norm_ (train.py:628-629) is sqrt of this summed over all gradient buffers. */
 int genie_sumsq(const float* x, size_t n, double* out, double* scratch, void* stream);
